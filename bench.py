@@ -9,6 +9,12 @@ reference sed.py:134-137.  Workload = BASELINE config 2 per GPU (mono, B=128, 25
 3x conv128 + BiGRU 2x128), weak scaling: every rank trains its own 128-sample shard of the global
 batch, gradients averaged.  Prints ONE JSON line on rank 0.
 
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, `ms_per_step_median`).
+`--full` also measures what the headline does not need, after the timed steps: the K steps again with in-library timers
+(`ms_per_step_instrumented`, `roofline`, per-rank `ranks`), the dominant kernel alone, the eval-mode forward
+(`eval_forward`) and the CPU baseline (`cpu_baseline`, unless `--no-cpu-baseline`).  `--dump-outputs DIR` writes what the
+last timed step computed to DIR/*.npy (see `dump_outputs`).
+
 Launching.  One process per GPU.  Three ways in, one code path (`run_rank`):
   * `python bench.py --gpus 1`              -> this process is rank 0 of 1;
   * under torchrun (RANK/WORLD_SIZE set)     -> this process is the rank torchrun says;
@@ -154,6 +160,21 @@ def cpu_baseline(steps=5):
             "c2_net": {"value": round(c2, 1), "unit": "mel-frames/s",
                        "sample": f"the bench workload's net (C128, GRU 2x128) at B=16 x 256 frames, same protocol, {c2_med*1e3:.0f} ms/step"},
             "host": info}
+
+
+def dump_outputs(path, model, loss, probs):
+    """What the timed path computed in its last fit step, as float32 .npy files under `path` (rank 0's, about 37 MB at the
+    workload's size): the loss and the frame probabilities the step returns, and the state it leaves in the model (the flat
+    parameters after Adam, the flat gradients of that step, the BatchNorm running statistics).  The inputs are seeded, so two
+    runs with the same arguments can be compared file by file."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    running = torch.cat([b.detach().reshape(-1).float() for b in model.buffers() if b.dtype.is_floating_point])
+    arrays = {"loss": loss, "probs": probs, "parameters": model.flat_parameters(), "gradients": model.flat_grads(),
+              "bn_running_stats": running}
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 # ───────────────────────── launcher (N > 1 without torchrun) ─────────────────────────
@@ -302,80 +323,86 @@ def run_rank(args):
     t0 = time.perf_counter()
     for i in range(args.steps):
         marks[i].record()
-        loss, _ = step.step(x, y)
+        loss, probs = step.step(x, y)
     marks[args.steps].record()
     barrier()
     dt = time.perf_counter() - t0
     step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
     med_ms = step_ms[len(step_ms) // 2] if len(step_ms) % 2 else 0.5 * (step_ms[len(step_ms) // 2 - 1] + step_ms[len(step_ms) // 2])
-    # ── the same K steps once more, instrumented: hipEvent pairs around every launch of the dominant kernel on its launch
-    # stream (sed_prof_*), and around the all-reduce wait of every step.  Kept OUT of the timed region (round-2 verdict,
-    # item 9); `ms_per_step_instrumented` beside `ms_per_step` shows what the instrumentation costs. ──
-    tag_dg = 12                                              # SED_K_CONV_MFMA_DGRAD: the same kernel's data-gradient instantiation
-    lib.sed_prof_enable((1 << tag) | (1 << tag_dg))
-    step.time_allreduce = world > 1
-    barrier()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        step.step(x, y)
-    barrier()
-    dt_inst = time.perf_counter() - t1
-    ms_f, n_f, units_f = C.c_double(), C.c_long(), C.c_double()
-    ms_d, n_d, units_d = C.c_double(), C.c_long(), C.c_double()
-    lib.sed_prof_read(tag, C.byref(ms_f), C.byref(n_f), C.byref(units_f))
-    lib.sed_prof_read(tag_dg, C.byref(ms_d), C.byref(n_d), C.byref(units_d))
-    lib.sed_prof_enable(0)
-    ms, n, units = (C.c_double(ms_f.value + ms_d.value), C.c_long(n_f.value + n_d.value),
-                    C.c_double(units_f.value + units_d.value))           # every launch of the kernel, both instantiations
-    step.time_allreduce = False
-    ar_wait = [a.elapsed_time(b) for a, b in step.allreduce_events]
-    step.allreduce_events.clear()
-    # the same kernel with the GPU to itself (outside the timed region): in the fit step one of its four launches per step
-    # (the data gradient of conv2) shares the CUs with the top block's weight gradient on the auxiliary stream, so its
-    # duration above covers part of that kernel's work too; the forward launches of a forward-only pass (same two shapes,
-    # in the same proportion) run alone
-    ms_x, n_x, units_x = C.c_double(), C.c_long(), C.c_double()
-    if rank == 0:
-        model.train()
-        lib.sed_prof_enable(1 << tag)
-        for _ in range(8):
-            model._run_forward(x, training=True)
-        torch.cuda.synchronize()
-        lib.sed_prof_read(tag, C.byref(ms_x), C.byref(n_x), C.byref(units_x))
-        lib.sed_prof_enable(0)
-    # ── inference: the eval-mode forward of the same net on the same resident batch (run_epoch with optim=None, sed.py:128-141:
-    # BatchNorm on running statistics folded into the conv weights, ReLU + pool in the conv epilogue, no dropout), after the
-    # timed region; SURVEY 8(d) "also report eval-forward frames/s" ──
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, loss, probs)
+    # ── everything below up to the result line is --full only: it runs the net again after the timed region, so a plain
+    # run leaves it out ──
     eval_fwd = None
-    if rank == 0:
-        model.eval()
-        with torch.no_grad():
-            for _ in range(3):
-                model(x)
-            em = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
-            em[0].record()
-            for i in range(args.steps):
-                model(x)
-                em[i + 1].record()
+    if args.full:
+        # ── the same K steps once more, instrumented: hipEvent pairs around every launch of the dominant kernel on its launch
+        # stream (sed_prof_*), and around the all-reduce wait of every step.  Kept OUT of the timed region (round-2 verdict,
+        # item 9); `ms_per_step_instrumented` beside `ms_per_step` shows what the instrumentation costs. ──
+        tag_dg = 12                                              # SED_K_CONV_MFMA_DGRAD: the same kernel's data-gradient instantiation
+        lib.sed_prof_enable((1 << tag) | (1 << tag_dg))
+        step.time_allreduce = world > 1
+        barrier()
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            step.step(x, y)
+        barrier()
+        dt_inst = time.perf_counter() - t1
+        ms_f, n_f, units_f = C.c_double(), C.c_long(), C.c_double()
+        ms_d, n_d, units_d = C.c_double(), C.c_long(), C.c_double()
+        lib.sed_prof_read(tag, C.byref(ms_f), C.byref(n_f), C.byref(units_f))
+        lib.sed_prof_read(tag_dg, C.byref(ms_d), C.byref(n_d), C.byref(units_d))
+        lib.sed_prof_enable(0)
+        ms, n, units = (C.c_double(ms_f.value + ms_d.value), C.c_long(n_f.value + n_d.value),
+                        C.c_double(units_f.value + units_d.value))           # every launch of the kernel, both instantiations
+        step.time_allreduce = False
+        ar_wait = [a.elapsed_time(b) for a, b in step.allreduce_events]
+        step.allreduce_events.clear()
+        # the same kernel with the GPU to itself (outside the timed region): in the fit step one of its four launches per step
+        # (the data gradient of conv2) shares the CUs with the top block's weight gradient on the auxiliary stream, so its
+        # duration above covers part of that kernel's work too; the forward launches of a forward-only pass (same two shapes,
+        # in the same proportion) run alone
+        ms_x, n_x, units_x = C.c_double(), C.c_long(), C.c_double()
+        if rank == 0:
+            model.train()
+            lib.sed_prof_enable(1 << tag)
+            for _ in range(8):
+                model._run_forward(x, training=True)
             torch.cuda.synchronize()
-        ems = sorted(em[i].elapsed_time(em[i + 1]) for i in range(args.steps))
-        e_med = ems[len(ems) // 2]
-        fl = forward_flops_per_batch(w)
-        peak_e = F32_MFMA_PEAK_TFLOPS
-        eval_fwd = {"ms": round(e_med, 4), "ms_min": round(ems[0], 4), "value": round(w["B"] * w["T"] / (e_med * 1e-3), 1), "unit": "mel-frames/s",
-                    "batches": args.steps,
-                    "roofline": {"bound": "mfma", "achieved": round(fl / (e_med * 1e-3) / 1e12, 2), "peak": peak_e, "unit": "TFLOP/s",
-                                 "frac": round(fl / (e_med * 1e-3) / 1e12 / peak_e, 4), "flops_per_batch": fl,
-                                 "ceiling_ms": round(fl / (peak_e * 1e12) * 1e3, 4),
-                                 "note": "conv2 / conv3 run as Winograd F(2x2,3x3) with BatchNorm folded and ReLU + pool in the epilogue (16/36 of the algorithmic multiply-adds are executed, hence frac > 1); "
-                                         "whole eval forward (one packing launch, 3 conv blocks, 2 BiGRU layers, head) against the fp32 "
-                                         "MFMA peak: 88 % of its FLOPs are conv2/conv3, exact fp32"}}
-        model.train()
+            lib.sed_prof_read(tag, C.byref(ms_x), C.byref(n_x), C.byref(units_x))
+            lib.sed_prof_enable(0)
+        # ── inference: the eval-mode forward of the same net on the same resident batch (run_epoch with optim=None, sed.py:128-141:
+        # BatchNorm on running statistics folded into the conv weights, ReLU + pool in the conv epilogue, no dropout), after the
+        # timed region; SURVEY 8(d) "also report eval-forward frames/s" ──
+        if rank == 0:
+            model.eval()
+            with torch.no_grad():
+                for _ in range(3):
+                    model(x)
+                em = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+                em[0].record()
+                for i in range(args.steps):
+                    model(x)
+                    em[i + 1].record()
+                torch.cuda.synchronize()
+            ems = sorted(em[i].elapsed_time(em[i + 1]) for i in range(args.steps))
+            e_med = ems[len(ems) // 2]
+            fl = forward_flops_per_batch(w)
+            peak_e = F32_MFMA_PEAK_TFLOPS
+            eval_fwd = {"ms": round(e_med, 4), "ms_min": round(ems[0], 4), "value": round(w["B"] * w["T"] / (e_med * 1e-3), 1), "unit": "mel-frames/s",
+                        "batches": args.steps,
+                        "roofline": {"bound": "mfma", "achieved": round(fl / (e_med * 1e-3) / 1e12, 2), "peak": peak_e, "unit": "TFLOP/s",
+                                     "frac": round(fl / (e_med * 1e-3) / 1e12 / peak_e, 4), "flops_per_batch": fl,
+                                     "ceiling_ms": round(fl / (peak_e * 1e12) * 1e3, 4),
+                                     "note": "conv2 / conv3 run as Winograd F(2x2,3x3) with BatchNorm folded and ReLU + pool in the epilogue (16/36 of the algorithmic multiply-adds are executed, hence frac > 1); "
+                                             "whole eval forward (one packing launch, 3 conv blocks, 2 BiGRU layers, head) against the fp32 "
+                                             "MFMA peak: 88 % of its FLOPs are conv2/conv3, exact fp32"}}
+            model.train()
     rank_stats = None
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
+    if world > 1 and args.full:
         # per-rank view, so that a slow scaling run can be diagnosed from the one line: every rank's median step time on its
         # own GPU timeline and the part of the all-reduce its backward did not hide
         mine = torch.tensor([med_ms, sum(ar_wait) / max(len(ar_wait), 1), dt_inst], device=dev, dtype=torch.float64)
@@ -415,7 +442,6 @@ def run_rank(args):
             "unit": "mel-frames/s",
             "ms_per_step": round(dt / args.steps * 1e3, 4),
             "ms_per_step_median": round(med_ms, 4),
-            "ms_per_step_instrumented": round(dt_inst / args.steps * 1e3, 4),
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -427,11 +453,14 @@ def run_rank(args):
                        "parallelism": (f"dp{world_seen}" if world_seen > 1 else "single") + ("-rehearsal-one-gpu" if args.share_gpu else ""),
                        "final_loss": round(final_loss, 6)},
         })
+        if args.full:
+            out["ms_per_step_instrumented"] = round(dt_inst / args.steps * 1e3, 4)
         out = {k: out[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "ms_per_step_median",
-                                   "ms_per_step_instrumented", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config")}
+                                   "ms_per_step_instrumented", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config")
+               if k in out}
         if rank_stats is not None:
             out["ranks"] = rank_stats
-        if n.value:
+        if args.full and n.value:
             avg_ms = ms.value / n.value
             tf = units.value / (ms.value * 1e-3) / 1e12
             wino = not args.conv_bf16x3 and not args.direct_conv
@@ -481,7 +510,7 @@ def run_rank(args):
                             "on the GPU)"}
         if eval_fwd is not None:
             out["eval_forward"] = eval_fwd
-        if not args.no_cpu_baseline and world == 1:              # rank 0 at N = 1 only (a reported baseline, not part of the step)
+        if args.full and not args.no_cpu_baseline and world == 1:              # rank 0 at N = 1 only (a reported baseline, not part of the step)
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if world > 1:
@@ -494,7 +523,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline does not need: the steps again with per-kernel "
+                         "timers (roofline, per-rank all-reduce view), the dominant kernel alone, the eval-mode forward and the "
+                         "CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned and left behind (loss, probabilities, parameters, gradients, "
+                         "BatchNorm running statistics) to DIR/<name>.npy as float32")
     ap.add_argument("--direct-conv", action="store_true", help="A/B: the direct 36-product conv kernels instead of the Winograd default")
     ap.add_argument("--breakdown", action="store_true", help="per-kernel-family times of 2 extra steps on stderr")
     ap.add_argument("--plumbing-only", action="store_true",

@@ -211,7 +211,8 @@ def test_bench_launches_two_ranks_and_runs_the_staged_step_on_the_hip_path():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2",
-                        "--backend", "gloo", "--share-gpu", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=560)
+                        "--backend", "gloo", "--share-gpu", "--full", "--no-cpu-baseline"], capture_output=True, text=True, env=env,
+                       timeout=560)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1

@@ -428,3 +428,38 @@ def test_captured_step_clears_the_weight_gradient_zero_rows_on_every_replay(sed)
     st2.step(x, y)
     torch.cuda.synchronize()
     assert torch.equal(m2.flat_grads(), g_ref)
+
+
+@pytest.mark.timeout(300)
+def test_bench_plain_line_and_dumped_outputs_of_the_last_timed_step(sed, tmp_path):
+    """`bench.py` without --full prints the headline only, and `--dump-outputs DIR` writes what the last timed step returned
+    and left in the model as float32 .npy files (under 64 MB); the inputs are seeded, so a second run with the same
+    arguments writes the same arrays."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    outs = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, env=env, timeout=280)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        outs.append(json.loads(lines[0]))
+    out = outs[0]
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert out["unit"] == "mel-frames/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert abs(out["value"] - 128 * 256 / (out["ms_per_step"] * 1e-3)) <= 1e-3 * out["value"]
+    for key in ("roofline", "eval_forward", "cpu_baseline", "ms_per_step_instrumented", "ranks"):
+        assert key not in out, key
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["bn_running_stats.npy", "gradients.npy", "loss.npy", "parameters.npy", "probs.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 << 20
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float32 and np.isfinite(a).all(), n
+        assert np.array_equal(a, b), n
+    assert np.load(tmp_path / "a" / "probs.npy").shape == (128, 32, 1)
+    assert round(float(np.load(tmp_path / "a" / "loss.npy")[0]), 6) == out["config"]["final_loss"] == outs[1]["config"]["final_loss"]

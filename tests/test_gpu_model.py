@@ -577,20 +577,28 @@ def test_staged_backward_completes_each_bucket_slice_when_its_stage_returns(sed,
     assert torch.equal(m.flat_grads()[valid], want[valid])
 
 
+# torch's CPU float32 run of the 40 steps is one draw of a chaotic process whose outcome depends on the reduction order, i.e.
+# on the host's CPU and thread count (its loss distance from float64 measured 2.5e-4 .. 1.6e-3 over 1-32 threads on two
+# host CPUs).  The yardstick therefore does not take whatever thread count the host offers: it runs torch-float32 at these
+# fixed counts and uses the run whose loss distance from float64 is the median.
+YARDSTICK_THREADS = (1, 2, 3, 4, 5)
+
+
 @pytest.fixture(scope="module")
 def forty_steps(sed):
     """The 40-step Adam run of a learnable synthetic task (labels = a threshold on a band of the input; 4 batches of 16
-    sequences, lr 2e-3) done three times from the same state: the HIP fused trainer, the fp32 oracle's fit_step, and the
-    oracle in FLOAT64 (the yardstick).  Shared by the two trajectory tests below."""
+    sequences, lr 2e-3) done from the same state by the HIP fused trainer, by the oracle in FLOAT64 (the yardstick), and by
+    the fp32 oracle's fit_step once per thread count of YARDSTICK_THREADS, of which the median run (by loss distance from
+    float64) is the torch-float32 run the tests compare with.  Shared by the two trajectory tests below."""
     from oracle import crnn_ref
     from sed_crnn_amd.trainer import FusedTrainStep
     torch.manual_seed(99)
     kw = dict(conv_channels=16, dropout=0.0, gru_hidden=16)
-    ref32 = crnn_ref.SedNetRef(**kw)
+    init = crnn_ref.SedNetRef(**kw).state_dict()
     ref64 = crnn_ref.SedNetRef(**kw).double()
-    ref64.load_state_dict({k: v.double() if v.dtype.is_floating_point else v for k, v in ref32.state_dict().items()})
+    ref64.load_state_dict({k: v.double() if v.dtype.is_floating_point else v for k, v in init.items()})
     m = sed.TimePooledCRNN(**kw)
-    m.load_state_dict(ref32.state_dict())
+    m.load_state_dict(init)
     m.cuda()
     g = torch.Generator().manual_seed(5)
     batches = []
@@ -599,25 +607,45 @@ def forty_steps(sed):
         band = x[:, 0, 8:16, :].mean(1)                                    # [B,T]
         y = (band.reshape(16, 8, 8).amax(2) > 0.45).float().unsqueeze(-1)  # [B,T',1]: learnable, ~55 % positive
         batches.append((x, y))
-    o32 = torch.optim.Adam(ref32.parameters(), lr=2e-3)
-    o64 = torch.optim.Adam(ref64.parameters(), lr=2e-3)
-    step = FusedTrainStep(m, lr=2e-3, loss="bce")
-    l32, l64, lh = [], [], []
-    for it in range(40):
-        x, y = batches[it % 4]
-        l32.append(float(crnn_ref.fit_step(ref32, o32, x, y)[0]))
-        l64.append(float(crnn_ref.fit_step(ref64, o64, x.double(), y.double())[0]))
-        lh.append(step.step(x.cuda(), y.cuda())[0])
-    lh = torch.stack([l.reshape(()) for l in lh]).cpu().numpy().astype(np.float64)
     xs = torch.cat([b[0] for b in batches])
     ys = torch.cat([b[1] for b in batches]).numpy()
-    for net in (ref32, ref64, m):
+    o64 = torch.optim.Adam(ref64.parameters(), lr=2e-3)
+    step = FusedTrainStep(m, lr=2e-3, loss="bce")
+    l64, lh = [], []
+    for it in range(40):
+        x, y = batches[it % 4]
+        l64.append(float(crnn_ref.fit_step(ref64, o64, x.double(), y.double())[0]))
+        lh.append(step.step(x.cuda(), y.cuda())[0])
+    l64 = np.asarray(l64)
+    lh = torch.stack([l.reshape(()) for l in lh]).cpu().numpy().astype(np.float64)
+    runs = []
+    threads = torch.get_num_threads()
+    try:
+        for nt in YARDSTICK_THREADS:
+            torch.set_num_threads(nt)
+            ref32 = crnn_ref.SedNetRef(**kw)
+            ref32.load_state_dict(init)
+            o32 = torch.optim.Adam(ref32.parameters(), lr=2e-3)
+            l32 = []
+            for it in range(40):
+                x, y = batches[it % 4]
+                l32.append(float(crnn_ref.fit_step(ref32, o32, x, y)[0]))
+            ref32.eval()
+            with torch.no_grad():
+                p32 = torch.sigmoid(ref32(xs)).double().numpy()
+            runs.append((np.abs(np.asarray(l32) - l64).max(), nt, ref32, np.asarray(l32), p32))
+    finally:
+        torch.set_num_threads(threads)
+    runs.sort(key=lambda r: r[0])
+    print("torch-f32 loss distance from float64 by thread count: "
+          + ", ".join(f"{nt}: {e:.2e}" for e, nt, *_ in sorted(runs, key=lambda r: r[1])))
+    _, _, ref32, l32, p32 = runs[len(runs) // 2]
+    for net in (ref64, m):
         net.eval()
     with torch.no_grad():
-        p32 = torch.sigmoid(ref32(xs)).double().numpy()
         p64 = torch.sigmoid(ref64(xs.double())).numpy()
         ph = torch.sigmoid(m(xs.cuda())).cpu().double().numpy()
-    return dict(kw=kw, ref32=ref32, m=m, xs=xs, ys=ys, l32=np.asarray(l32), l64=np.asarray(l64), lh=lh, p32=p32, p64=p64, ph=ph)
+    return dict(kw=kw, ref32=ref32, m=m, xs=xs, ys=ys, l32=l32, l64=l64, lh=lh, p32=p32, p64=p64, ph=ph)
 
 
 def test_forty_step_trajectory_tracks_the_oracle_and_scores_agree(sed, forty_steps):

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Refresh profiles/<round>/ on the GPU box:  bash tools/profile_round.sh r2
-#   1. rocprofv3 --kernel-trace --stats of the default bench command  -> bench_n1_kernel_stats.csv (+ the bench line)
+#   1. rocprofv3 --kernel-trace --stats of the bench command with --full -> bench_n1_kernel_stats.csv (+ the bench line)
 #   2. two separate --pmc passes (FETCH_SIZE, WRITE_SIZE) of a short bench run -> pmc_fetch_write_per_kernel.json
 #   3. the log-mel front end (not part of the timed fit step): kernel stats, FETCH/WRITE and SQ counters of
 #      tools/logmel_bench.py -> logmel_kernel_stats.csv, logmel_pmc.json, logmel_line.txt
@@ -12,7 +12,7 @@ OUT=$REPO/gpurun_out/prof_$ROUND
 DST=$REPO/gpurun_out/profiles_$ROUND
 mkdir -p $OUT $DST
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $REPO/bench.py --steps 20 --warmup 5 > $OUT/bench_line.txt 2> $OUT/bench_err.txt
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $REPO/bench.py --steps 20 --warmup 5 --full > $OUT/bench_line.txt 2> $OUT/bench_err.txt
 for c in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/pmc_$c -- python3 $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline > /dev/null 2> $OUT/pmc_${c}_err.txt
 done
