@@ -111,6 +111,18 @@ int sed_conv3x3_pack_weights_bn_folded(const float* w, const float* bias, const 
                                        float* wf, float* bias_folded, int Cout, int Cin, void* stream);
 int sed_conv3x3_bn_relu_pool_eval(const float* x, const float* wp_folded, const float* bias_folded, float* pooled,
                                   int B, int Cin, int F, int T, int Cout, void* stream);
+/* bf16 inference (opt-in: sed_net_cfg.conv_mode = 2) — the same block as sed_conv3x3_bn_relu_pool_eval on
+ * v_mfma_f32_32x32x16_bf16 with fp32 accumulation.  Rounded to bf16 (nearest even): the folded weights w * scale[co] (formed in
+ * fp32, then rounded; bias_folded stays fp32), the input x (x_is_bf16 = 0: fp32 x rounded while staged; 1: x is bf16 already) and
+ * the output after bias + ReLU + pool in fp32.  x [B][T][F][Cin] channels-last -> pooled bf16 [B][T/2][F][Cout] (floor pooling).
+ * wf_bf16: 9*Cout*Cin bf16 from sed_conv3x3_bf16_pack_weights_bn_folded (Cout % 32, Cin % 16 == 0).
+ * _supported: Cin % 32 == 0, Cout % 64 == 0, T >= 2, any mel width (direct form, tiles of <= 32 mel columns). */
+int sed_conv3x3_bf16_eval_supported(int B, int Cin, int F, int T, int Cout);
+int sed_conv3x3_bf16_pack_weights_bn_folded(const float* w, const float* bias, const float* gamma, const float* beta,
+                                            const float* running_mean, const float* running_var, float eps,
+                                            void* wf_bf16, float* bias_folded, int Cout, int Cin, void* stream);
+int sed_conv3x3_bf16_bn_relu_pool_eval(const void* x, int x_is_bf16, const void* wf_bf16, const float* bias_folded,
+                                       void* pooled_bf16, int B, int Cin, int F, int T, int Cout, void* stream);
 /* Data gradient of conv block l (the convolution of dy with wp_dgrad) FUSED with the reduction pass of the BatchNorm / ReLU /
  * max-pool / dropout backward of block l-1 (sed_bn_relu_pool_drop_bwd_reduce below), for the exact-fp32 MFMA shapes:
  * dy [B][T][F][C] -> dx [B][T][F][Cin] = gradient of block l-1's pooled output, and partials [rows][2][Cin] = per-workgroup
@@ -337,6 +349,12 @@ size_t sed_gemm_f32_workspace_bytes(int M, int N, int K);   /* covers sed_gemm_f
 int sed_gemm_f32_ws(const float* A, long a_si, long a_sk, const float* B, long b_sk, long b_sj,
                     float* C, long ldc, const float* bias, int M, int N, int K, void* workspace, void* stream);
 
+/* bf16 form (the input projection of GRU layer 0 in the bf16 inference plan): C[i][j] = sum_k A[i][k] B[j][k] + bias[j], A bf16
+ * [M][K] and B bf16 [N][K] row-major, C fp32 with leading dim ldc, bias fp32 (may be NULL), K % 32 == 0.  fp32 accumulation on
+ * v_mfma_f32_32x32x16_bf16, no split of K: every element sums its k-tiles in one fixed order whatever M (a batch equals its
+ * chunks bit for bit). */
+int sed_gemm_bf16_nt(const void* A, const void* B, const float* bias, float* C, long ldc, int M, int N, int K, void* stream);
+
 /* Weight-gradient form (dW = dY^T X under loss.backward(), sed.py:137): the same product, beta = 0, no bias, whose K axis is
  * the batch x time axis.  Besides the small-output split above it may be cut into two K-slices when its best tiling
  * gives at most one tile per CU (two co-resident workgroups per CU instead of one).  Deterministic for given (M,N,K). */
@@ -460,7 +478,10 @@ typedef struct sed_net_cfg {
     int D[SED_MAX_DENSE];             /* dense sizes; ReLU between layers, last = classes (logits) */
     float bn_eps, bn_momentum;
     int conv_mode;                    /* 0 = exact fp32 (default); 1 = EXPERIMENT: conv forward, data gradient and weight gradient of the
-                                         MFMA blocks on the 3-term bf16 split (sed_conv3x3_fwd_ex / sed_conv3x3_wgrad_ex) */
+                                         MFMA blocks on the 3-term bf16 split (sed_conv3x3_fwd_ex / sed_conv3x3_wgrad_ex);
+                                         2 = bf16 INFERENCE plan (training = 0 only, sed_net_forward only): the supported conv blocks
+                                         at the top of the stack and the GRU layer-0 input projection on bf16 operands
+                                         (sed_net_inference_plan says which), everything else as mode 0 */
     int flags;                        /* 0 (default) | SED_NET_* below: measurement / test switches of the backward schedule */
 } sed_net_cfg;
 /* The last backward phase runs the first block's passes (auxiliary stream) BESIDE the deferred MFMA weight gradients (main
@@ -537,7 +558,9 @@ int sed_net_backward_phases(const sed_net_cfg* cfg, const sed_net_params* p, con
 /* Where an intermediate of the plan lives inside `workspace` (offsets are a pure function of cfg and `training`), for hosts
  * that read activations and for parity tests of intermediates.  name / index:
  *   "conv_out"[l] conv output of block l, channels-last [B][T_l][F_l][C] (absent for a recomputed first block);
- *   "pooled"[l] block output [B][T_l/pt][F_l/pf][C] (last block: [B][T'][C][F'], the GRU feature order);
+ *   "pooled"[l] block output [B][T_l/pt][F_l/pf][C] (last block: [B][T'][C][F'], the GRU feature order, except in the eval
+ *   plans whose last block pools in its conv epilogue: channels-last there); a bf16 block of the bf16 inference plan
+ *   (sed_net_inference_plan) stores bf16 elements and n_floats counts ELEMENTS;
  *   "mean" / "rstd" / "scale" / "shift"[l] the batch statistics and fused BatchNorm coefficients of block l ([C]);
  *   "gi"[i] / "gru_out"[i] input projections [M][2][3H] and outputs [M][2H] of GRU layer i;
  *   training only: "dconv"[l] gradient of block l's conv output, "dgru_out"[i], "grad_act"[0] the buffer that carries the
@@ -553,6 +576,10 @@ int sed_net_workspace_region(const sed_net_cfg* cfg, int training, const char* n
  * (stored conv output) or sed_conv1_route (recomputed first block: it re-reads p->conv_b, so call this before the optimiser
  * moves the parameters).  For the parity tests of the gradient routing of
  * `loss.backward()` (sed.py:137): see oracle/crnn_ref.py forward_routed. */
+/* What the eval plan of cfg runs in bf16 (conv_mode 2; zeros otherwise): conv_bf16[n_conv] per conv block (weights, input and
+ * pooled output bf16 — its "pooled" region then holds bf16 elements), *proj_bf16 for the GRU layer-0 input projection. */
+int sed_net_inference_plan(const sed_net_cfg* cfg, int* conv_bf16, int* proj_bf16);
+
 int sed_net_routing(const sed_net_cfg* cfg, const sed_net_params* p, const float* x, const void* workspace, int block,
                     unsigned char* route, void* stream);
 

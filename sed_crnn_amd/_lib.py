@@ -63,6 +63,9 @@ SIGNATURES = {
     "sed_conv3x3_bn_relu_pool_eval_supported": (_i, [_i, _i, _i, _i, _i]),
     "sed_conv3x3_pack_weights_bn_folded": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _f, _fp, _fp, _i, _i, _stream]),
     "sed_conv3x3_bn_relu_pool_eval": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _stream]),
+    "sed_conv3x3_bf16_eval_supported": (_i, [_i, _i, _i, _i, _i]),
+    "sed_conv3x3_bf16_pack_weights_bn_folded": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _f, _fp, _fp, _i, _i, _stream]),
+    "sed_conv3x3_bf16_bn_relu_pool_eval": (_i, [_fp, _i, _fp, _fp, _fp, _i, _i, _i, _i, _i, _stream]),
     "sed_conv3x3_dgrad_bnred_rows": (_i, [_i, _i, _i, _i, _i]),
     "sed_conv3x3_dgrad_bnred": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _stream]),
     "sed_conv3x3_wino_rows": (_i, [_i, _i, _i, _i, _i]),
@@ -108,6 +111,7 @@ SIGNATURES = {
     "sed_gemm_f32": (_i, [_fp, _l, _l, _fp, _l, _l, _fp, _l, _fp, _f, _i, _i, _i, _stream]),
     "sed_gemm_f32_workspace_bytes": (_sz, [_i, _i, _i]),
     "sed_gemm_f32_ws": (_i, [_fp, _l, _l, _fp, _l, _l, _fp, _l, _fp, _i, _i, _i, _fp, _stream]),
+    "sed_gemm_bf16_nt": (_i, [_fp, _fp, _fp, _fp, _l, _i, _i, _i, _stream]),
     "sed_gemm_f32_wgrad": (_i, [_fp, _l, _l, _fp, _l, _l, _fp, _l, _i, _i, _i, _fp, _stream]),
     "sed_linear_fwd": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _stream]),
     "sed_linear_bwd_workspace_bytes": (_sz, [_i, _i, _i]),
@@ -142,6 +146,7 @@ SIGNATURES = {
     "sed_net_sync_region": (_i, [C.POINTER(NetCfg), _i, _i, C.POINTER(_sz), C.POINTER(_sz)]),
     "sed_net_workspace_region": (_i, [C.POINTER(NetCfg), _i, C.c_char_p, _i, C.POINTER(_sz), C.POINTER(_sz)]),
     "sed_net_routing": (_i, [C.POINTER(NetCfg), C.POINTER(NetParams), _fp, _fp, _i, _fp, _stream]),
+    "sed_net_inference_plan": (_i, [C.POINTER(NetCfg), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "sed_net_forward_phases": (_i, [C.POINTER(NetCfg), C.POINTER(NetParams), _fp, _fp, _fp, _i, _u64, _i, _i, _f, _stream]),
     "sed_net_backward_phases": (_i, [C.POINTER(NetCfg), C.POINTER(NetParams), C.POINTER(NetParams), _fp, _fp, _fp, _u64, _i, _i, _f, _stream]),
     "sed_net_backward": (_i, [C.POINTER(NetCfg), C.POINTER(NetParams), C.POINTER(NetParams), _fp, _fp, _fp, _u64, _fp, _i, _i, _stream, _stream]),

@@ -12,13 +12,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libsedcrnn.so")
-SOURCES = ["api.cpp", "conv.hip", "wino.hip", "conv1.hip", "bnpool.hip", "gemm.hip", "gru.hip", "misc.hip", "logmel.hip", "data.hip", "net.hip"]
+SOURCES = ["api.cpp", "conv.hip", "conv_bf16.hip", "wino.hip", "conv1.hip", "bnpool.hip", "gemm.hip", "gru.hip", "misc.hip", "logmel.hip", "data.hip", "net.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # per-file extras.  logmel: the SLP vectoriser packs the FFT's scalar adds into v_pk_add_f32 and pays for it with ~600
 # v_mov per frame pair to build the register pairs (packed f32 is no faster than scalar on gfx950)
 EXTRA_FLAGS = {"logmel.hip": ["-fno-slp-vectorize"],
                "conv.hip": ["-Rpass-analysis=kernel-resource-usage"],
-               "wino.hip": ["-Rpass-analysis=kernel-resource-usage"]}
+               "wino.hip": ["-Rpass-analysis=kernel-resource-usage"],
+               "conv_bf16.hip": ["-Rpass-analysis=kernel-resource-usage"]}
 # Kernels whose inline-asm loads are consumed after HAND-COUNTED s_waitcnt vmcnt(N) immediates (conv.hip: the fp32 and the
 # bf16x3 conv forward).  The counts are only right while hipcc keeps the load destinations in registers between the asm load
 # and its use: a spill (scratch store/reload) would insert memory operations the counts do not know about and the MFMAs
@@ -29,7 +30,9 @@ EXTRA_FLAGS = {"logmel.hip": ["-fno-slp-vectorize"],
 NO_SPILL_KERNELS = {"conv.hip": ("conv3x3_mfma_fwd2_k", "conv3x3_mfma_fwd_bf16x3_k")}
 # Kernels that hold their accumulators in AGPRs by design (one wave per SIMD, 256 accumulator registers) and leave all waits to
 # hipcc: a spill there is not a correctness hazard, it is a performance cliff nobody would notice — scratch must stay 0.
-NO_SCRATCH_KERNELS = {"wino.hip": ("conv3x3_wino_k",)}
+NO_SCRATCH_KERNELS = {"wino.hip": ("conv3x3_wino_k",),
+                      # bf16 inference: hipcc's own waits (no hand counts), accumulators may sit in AGPRs; a spill would be a cliff
+                      "conv_bf16.hip": ("conv3x3_bf16_eval_k", "gemm_bf16_nt_k")}
 
 
 def _hipcc():

@@ -53,12 +53,13 @@ int sed_internal_conv_pack_multi(int n, const float* const* w, float* const* wf,
 
 // internal (conv.hip): the inference form of the packing launch — every layer's fragments, the BatchNorm coefficients on running
 // statistics, BatchNorm folded into weights + bias where fold[l], and (perm_src) the GRU input weights re-ordered to
-// channels-last feature columns — see conv_pack_w_multi_k
+// channels-last feature columns — see conv_pack_w_multi_k.  bf16 plan (conv_mode 2): wbf16[l] (may be NULL) receives layer l's
+// folded weights as bf16 fragments (bf16_eval_frag_index) instead of wf[l]; perm_bf16: the re-ordered GRU weights are written as bf16
 int sed_internal_conv_pack_eval(int n, const float* const* w, const float* const* bias, const float* const* gamma,
                                 const float* const* beta, const float* const* rm, const float* const* rv, float eps,
                                 float* const* wf, float* const* scale, float* const* shift, float* const* bias_folded, const int* fold,
                                 const int* wino, const int* Cout, const int* Cin, const float* perm_src0, const float* perm_src1, float* perm_dst,
-                                int perm_rows, int perm_C, int perm_Fp, void* stream);
+                                int perm_rows, int perm_C, int perm_Fp, void* const* wbf16, int perm_bf16, void* stream);
 
 // internal (conv.hip): sed_conv3x3_wgrad_ex whose exact-fp32 MFMA kernels add 1 to *arrive (agent scope) as each workgroup
 // starts; _workgroups: how many that will be (0: this shape's kernel does not announce itself)

@@ -149,6 +149,9 @@ struct ConvPackMulti {
     // one more slice of the grid (blockIdx.y == n): a row-major [rows][C*Fp] matrix whose columns are re-ordered from the
     // reference's GRU feature order c*Fp + f (sed.py:108-110) to the channels-last order f*C + c of a pooled conv output
     const float* perm_src[2]; float* perm_dst; int perm_rows, perm_C, perm_Fp;      // two sources of perm_rows rows each -> [2 perm_rows][K]
+    // bf16 inference plan (conv_mode 2): wb[l] != NULL receives the folded weights as bf16 fragments (conv_bf16.hip) instead of wf[l];
+    // perm_bf16: perm_dst is a bf16 matrix
+    __bf16* wb[SED_MAX_CONV]; int perm_bf16;
 };
 __global__ void conv_pack_w_multi_k(ConvPackMulti a, int n) {
     const int l = blockIdx.y;
@@ -165,7 +168,8 @@ __global__ void conv_pack_w_multi_k(ConvPackMulti a, int n) {
             float* dst = a.perm_dst + (size_t)row * K;
             for (int k = threadIdx.x; k < K; k += blockDim.x) {
                 const int f = k / a.perm_C, c = k - f * a.perm_C;
-                dst[k] = prow[c * a.perm_Fp + f];
+                if (a.perm_bf16) ((__bf16*)a.perm_dst + (size_t)row * K)[k] = (__bf16)prow[c * a.perm_Fp + f];
+                else dst[k] = prow[c * a.perm_Fp + f];
             }
         }
         return;
@@ -184,6 +188,7 @@ __global__ void conv_pack_w_multi_k(ConvPackMulti a, int n) {
     float v = a.w[l][i];
     if (a.fold[l]) v *= a.gamma[l][co] / sqrtf(a.rv[l][co] + a.eps);
     const bool frag = (Cin % 32 == 0) && (Cout % 32 == 0);
+    if (a.wb[l]) a.wb[l][bf16_eval_frag_index(tap, co, ci, Cout, Cin)] = (__bf16)v;      // round to nearest even
     if (a.wf[l] && !a.wino_f[l]) a.wf[l][frag ? conv_frag_index(tap, co, ci, Cout, Cin) : ((size_t)tap * Cout + co) * Cin + ci] = v;
     if (a.wd[l] && !a.wino_d[l]) a.wd[l][frag ? conv_frag_index(8 - tap, ci, co, Cin, Cout) : ((size_t)(8 - tap) * Cin + ci) * Cout + co] = v;
 }
@@ -226,11 +231,14 @@ int sed_internal_conv_pack_eval(int n, const float* const* w, const float* const
                                 const float* const* beta, const float* const* rm, const float* const* rv, float eps,
                                 float* const* wf, float* const* scale, float* const* shift, float* const* bias_folded, const int* fold,
                                 const int* wino, const int* Cout, const int* Cin, const float* perm_src0, const float* perm_src1, float* perm_dst,
-                                int perm_rows, int perm_C, int perm_Fp, void* stream) {
+                                int perm_rows, int perm_C, int perm_Fp, void* const* wbf16, int perm_bf16, void* stream) {
     SED_REQUIRE(n > 0 && n <= SED_MAX_CONV && w && gamma && beta && rm && rv && wf && scale && shift && fold && Cout && Cin, "conv_pack_eval: bad arguments");
     ConvPackMulti a{};
     for (int l = 0; l < n; ++l) {
-        SED_REQUIRE(w[l] && gamma[l] && beta[l] && rm[l] && rv[l] && wf[l] && Cout[l] > 0 && Cin[l] > 0, "conv_pack_eval: bad layer %d", l);
+        const bool wb = wbf16 && wbf16[l];
+        SED_REQUIRE(w[l] && gamma[l] && beta[l] && rm[l] && rv[l] && (wf[l] || wb) && Cout[l] > 0 && Cin[l] > 0, "conv_pack_eval: bad layer %d", l);
+        SED_REQUIRE(!wb || (fold[l] && Cout[l] % 32 == 0 && Cin[l] % 16 == 0 && !(wino && wino[l])), "conv_pack_eval: layer %d cannot take the bf16 packing", l);
+        a.wb[l] = wb ? (__bf16*)wbf16[l] : nullptr;
         SED_REQUIRE(fold[l] ? (bias_folded && bias_folded[l]) : (scale[l] && shift[l]), "conv_pack_eval: layer %d lacks its outputs", l);
         a.w[l] = w[l]; a.wf[l] = wf[l]; a.Cout[l] = Cout[l]; a.Cin[l] = Cin[l];
         a.gamma[l] = gamma[l]; a.beta[l] = beta[l]; a.rm[l] = rm[l]; a.rv[l] = rv[l]; a.bias[l] = bias ? bias[l] : nullptr;
@@ -242,6 +250,7 @@ int sed_internal_conv_pack_eval(int n, const float* const* w, const float* const
     if (perm_src0) {
         SED_REQUIRE(perm_src1 && perm_dst && perm_rows > 0 && perm_C > 0 && perm_Fp > 0, "conv_pack_eval: bad permutation");
         a.perm_src[0] = perm_src0; a.perm_src[1] = perm_src1; a.perm_dst = perm_dst; a.perm_rows = perm_rows; a.perm_C = perm_C; a.perm_Fp = perm_Fp;
+        a.perm_bf16 = perm_bf16 ? 1 : 0;
     }
     return pack_multi_launch(a, n, stream);
 }

@@ -27,6 +27,11 @@ __host__ __device__ inline size_t wino_frag_index(int comp, int k, int n, int K,
     (void)N;
     return (((((((size_t)coh * 16 + comp) * (K >> 5) + cc) * 4 + g) * 2 + nt) * 64) + r + 32 * h) * 4 + j;
 }
+// bf16 inference plan (conv_bf16.hip): folded weights in the B-operand order of v_mfma_f32_32x32x16_bf16,
+// [tap][ci/16][co/32][lane = co%32 + 32 ((ci%16)/8)][ci%8] bf16 — one 1 KiB wave-load per (tap, 16-channel group, channel tile)
+__host__ __device__ inline size_t bf16_eval_frag_index(int tap, int co, int ci, int Cout, int Cin) {
+    return (((((size_t)tap * (Cin >> 4) + (ci >> 4)) * (Cout >> 5) + (co >> 5)) * 64) + (co & 31) + 32 * ((ci & 15) >> 3)) * 8 + (ci & 7);
+}
 #define WN_ZTAIL 256        // zero floats behind the packed weights: the source of the patch's zero padding (LDS-DMA cannot write a constant)
 // one thread per (co, ci): U = G g G^T for the forward (g[a][c] = w[co][ci][kh = c][kw = a]: a runs along time, c along mel) and for
 // the data gradient (contraction over co, g'[a][c] = w[co][ci][2 - c][2 - a])

@@ -14,12 +14,16 @@ struct ConvL { int Cin, C, T, F, Tp, Fp, pf, pt, rows, bn_rows, nchw, fused; flo
                int rg_rows;       // > 0 (block 0 only): so do its weight-gradient sums (sed_conv3x3_dgrad_bnred_rg), into c1_ws
                int rgrad;         // recomputed first block: its weight gradient comes from the pooled output, arg-max bits and input moments
                int wino, wino_d;  // forward / data gradient of this block run as Winograd F(2x2,3x3) (wino.hip)
-               int ev; };         // inference plan only: BatchNorm folded into the packed weights, ReLU + (1,2) pool in the conv epilogue
+               int ev;            // inference plan only: BatchNorm folded into the packed weights, ReLU + (1,2) pool in the conv epilogue
                                   // (sed_conv3x3_bn_relu_pool_eval): the block's un-pooled output is never written
+               int bf; };         // bf16 inference plan (conv_mode 2): the block runs sed_conv3x3_bf16_bn_relu_pool_eval; its packed
+                                  // weights and its pooled output are bf16
+
 struct GruL { int in, H; };
 
 struct Layout {
     int n_conv, n_gru, n_dense, M, Tp, Fp, feat;
+    int proj_bf;                   // bf16 plan: the input projection of GRU layer 0 is the bf16 GEMM (A = the last block's bf16 output)
     ConvL cv[SED_MAX_CONV];
     GruL gr[SED_MAX_GRU];
     int dK[SED_MAX_DENSE], dN[SED_MAX_DENSE];
@@ -52,10 +56,27 @@ int build_layout(const sed_net_cfg* c, int training, Layout* L) {
     SED_REQUIRE(c->n_conv >= 1 && c->n_conv <= SED_MAX_CONV, "net: n_conv=%d out of range", c->n_conv);
     SED_REQUIRE(c->n_gru >= 1 && c->n_gru <= SED_MAX_GRU, "net: n_gru=%d out of range", c->n_gru);
     SED_REQUIRE(c->n_dense >= 1 && c->n_dense <= SED_MAX_DENSE, "net: n_dense=%d out of range", c->n_dense);
-    SED_REQUIRE(c->conv_mode == 0 || c->conv_mode == 1, "net: conv_mode=%d (0 = exact fp32, 1 = bf16x3 experiment)", c->conv_mode);
+    SED_REQUIRE(c->conv_mode >= 0 && c->conv_mode <= 2, "net: conv_mode=%d (0 = exact fp32, 1 = bf16x3 experiment, 2 = bf16 inference)", c->conv_mode);
+    SED_REQUIRE(c->conv_mode != 2 || !training, "net: conv_mode 2 (bf16 inference) is an eval-only plan; training runs with conv_mode 0 or 1");
     SED_REQUIRE((c->flags & ~(SED_NET_AUX_FIRST | SED_NET_NO_GATE | SED_NET_DIRECT_CONV)) == 0, "net: unknown flags 0x%x", c->flags);
     memset(L, 0, sizeof(*L));
     L->n_conv = c->n_conv; L->n_gru = c->n_gru; L->n_dense = c->n_dense;
+    // bf16 inference: the blocks that run bf16 are the longest run of supported blocks at the TOP of the stack (>= 1, pool (1,2),
+    // Cin % 32, C % 64, a GRU input row the re-ordering buffer holds) — a bf16 block's output feeds a bf16 block or the bf16
+    // projection only, so no fp32 kernel ever reads a bf16 tensor.  Every other block is planned exactly as in mode 0.
+    const int fm = c->conv_mode == 2 ? 0 : c->conv_mode;       // the mode of the fp32 blocks
+    int bfl[SED_MAX_CONV] = {0};
+    if (c->conv_mode == 2) {
+        int Ci = c->Cin, Ti = c->T, Fi = c->F;
+        int ok[SED_MAX_CONV] = {0};
+        for (int l = 0; l < c->n_conv; ++l) {
+            const int pf = c->pool_f[l], pt = c->pool_t[l];
+            ok[l] = l > 0 && pf == 1 && pt == 2 && c->C[l] > 0 && Ti >= 2 && sed_conv3x3_bf16_eval_supported(c->B, Ci, Fi, Ti, c->C[l]);
+            if (l == c->n_conv - 1 && (size_t)c->C[l] * Fi * sizeof(float) > 64 * 1024) ok[l] = 0;
+            Ci = c->C[l]; Ti = pt > 0 ? Ti / pt : Ti; Fi = pf > 0 ? Fi / pf : Fi;
+        }
+        for (int l = c->n_conv - 1; l >= 0 && ok[l]; --l) bfl[l] = 1;
+    }
     Carver cv;
     int Cin = c->Cin, T = c->T, F = c->F;
     size_t max_pool = 0, max_wgrad = 0, c1_ws = 64, c1_stat_ws = 64;
@@ -74,12 +95,13 @@ int build_layout(const sed_net_cfg* c, int training, Layout* L) {
         // 3 or 4 input channels (config 5): recomputed as well when the whole moment-based chain is available — statistics from
         // the blocked moment kernel, (1,2) pool, and the data gradient of block 1 on the MFMA path (it forms this block's
         // BatchNorm-backward sums; the recomputing reduce / apply passes do not exist beyond 2 channels)
-        if (l == 0 && !q.fused && c->n_conv > 1 && q.Cin <= 4 && c->conv_mode == 0 &&
+        q.bf = bfl[l];
+        if (l == 0 && !q.fused && c->n_conv > 1 && q.Cin <= 4 && fm == 0 &&
             sed_conv1_rgrad_supported(q.Cin, q.F, q.T, q.C, q.pf, q.pt) &&
             sed_conv3x3_dgrad_bnred_rows(c->B, c->C[1], q.F / q.pf, q.T / q.pt, q.C) > 0)
             q.fused = 1;
         // 128 input channels, exact fp32: the Winograd form (2.25x fewer MFMAs, same epilogues) unless the caller asks for the direct kernels
-        const bool wino_ok = l > 0 && c->conv_mode == 0 && !(c->flags & SED_NET_DIRECT_CONV);
+        const bool wino_ok = l > 0 && fm == 0 && !q.bf && !(c->flags & SED_NET_DIRECT_CONV);
         q.wino = (wino_ok && sed_conv3x3_wino_rows(c->B, q.Cin, q.F, q.T, q.C) > 0) ? 1 : 0;
         q.wino_d = (wino_ok && training && sed_conv3x3_wino_rows(c->B, q.C, q.F, q.T, q.Cin) > 0) ? 1 : 0;
         if (q.fused) {
@@ -92,16 +114,16 @@ int build_layout(const sed_net_cfg* c, int training, Layout* L) {
         }
         // inference: blocks >= 1 on the 128-wide exact-fp32 MFMA tile with the reference's (1,2) pool (sed.py:90) end in the pooling
         // epilogue; everything else (and every training plan) keeps the conv output + the BatchNorm/ReLU/pool pass
-        q.ev = (!training && l > 0 && c->conv_mode == 0 && q.pf == 1 && q.pt == 2 &&
+        q.ev = (!training && l > 0 && fm == 0 && !q.bf && q.pf == 1 && q.pt == 2 &&
                 (q.wino || sed_conv3x3_bn_relu_pool_eval_supported(c->B, q.Cin, q.F, q.T, q.C))) ? 1 : 0;
         // (.wino of a pooling-epilogue block: the Winograd kernel with that epilogue; .wino_d is a training-only notion)
-        size_t nout = (q.fused || q.ev) ? 64 : (size_t)c->B * q.T * q.F * q.C, npool = (size_t)c->B * q.Tp * q.Fp * q.C;
-        L->wp_f[l] = cv.take(q.wino ? sed_conv3x3_wino_packed_floats(q.C, q.Cin) : (size_t)9 * q.C * q.Cin);
+        size_t nout = (q.fused || q.ev || q.bf) ? 64 : (size_t)c->B * q.T * q.F * q.C, npool = (size_t)c->B * q.Tp * q.Fp * q.C;
+        L->wp_f[l] = cv.take(q.wino ? sed_conv3x3_wino_packed_floats(q.C, q.Cin) : q.bf ? (size_t)9 * q.C * q.Cin / 2 : (size_t)9 * q.C * q.Cin);
         L->wp_d[l] = cv.take(q.wino_d ? sed_conv3x3_wino_packed_floats(q.C, q.Cin) : (size_t)9 * q.C * q.Cin);
         L->conv_out[l] = cv.take(nout);
         L->stat[l] = cv.take((size_t)q.rows * 2 * q.C);
         L->mean[l] = cv.take(q.C); L->rstd[l] = cv.take(q.C); L->scale[l] = cv.take(q.C); L->shift[l] = cv.take(q.C);
-        L->pooled[l] = cv.take(npool);
+        L->pooled[l] = cv.take(q.bf ? (npool + 1) / 2 : npool);
         L->bn_sums[l] = cv.take((size_t)2 * q.C);
         L->bias_f[l] = cv.take(q.C);
         if (npool > max_pool) max_pool = npool;
@@ -118,7 +140,7 @@ int build_layout(const sed_net_cfg* c, int training, Layout* L) {
             // the shared zero row: kept clean by the backward only when every block that shares the workspace has the same
             // one (a block without it, or with a shorter one, would put its slabs on top of the others' zero row)
             if (l > 0) {
-                const size_t zr = c->conv_mode == 0 ? sed_conv3x3_wgrad_zero_row_bytes(c->B, q.Cin, q.F, q.T, q.C) / sizeof(float) : 0;
+                const size_t zr = fm == 0 ? sed_conv3x3_wgrad_zero_row_bytes(c->B, q.Cin, q.F, q.T, q.C) / sizeof(float) : 0;
                 if (l == 1) L->wgrad_zrow = zr;
                 else if (zr != L->wgrad_zrow) L->wgrad_zrow = 0;
             }
@@ -133,7 +155,7 @@ int build_layout(const sed_net_cfg* c, int training, Layout* L) {
     // exact-fp32 MFMA blocks: the data gradient of block l forms the BatchNorm-backward sums of block l-1 in its epilogue
     for (int l = 1; l < c->n_conv; ++l) {
         const ConvL& q = L->cv[l];
-        const int rr = (c->conv_mode != 0) ? 0 : q.wino_d ? sed_conv3x3_wino_rows(c->B, q.C, q.F, q.T, q.Cin)
+        const int rr = (fm != 0) ? 0 : q.wino_d ? sed_conv3x3_wino_rows(c->B, q.C, q.F, q.T, q.Cin)
                                                            : sed_conv3x3_dgrad_bnred_rows(c->B, q.C, q.F, q.T, q.Cin);
         L->cv[l - 1].red_rows = rr;
         if (rr > max_bn_rows) max_bn_rows = rr;
@@ -158,7 +180,8 @@ int build_layout(const sed_net_cfg* c, int training, Layout* L) {
         q.ev = 0;
         L->conv_out[c->n_conv - 1] = cv.take((size_t)c->B * q.T * q.F * q.C);
     }
-    L->wih_perm = (L->cv[c->n_conv - 1].ev && c->H[0] > 0) ? cv.take((size_t)6 * c->H[0] * L->feat) : 0;
+    L->proj_bf = L->cv[c->n_conv - 1].bf;
+    L->wih_perm = ((L->cv[c->n_conv - 1].ev || L->proj_bf) && c->H[0] > 0) ? cv.take((size_t)6 * c->H[0] * L->feat / (L->proj_bf ? 2 : 1)) : 0;
     int in = L->feat, maxH = 0, max2H = 0;
     for (int i = 0; i < c->n_gru; ++i) {
         int H = c->H[i];
@@ -256,30 +279,38 @@ static int forward_impl(const sed_net_cfg* c, const sed_net_params* p, const flo
     // 5 us launch per layer standing between the layers of the critical chain
     // inference (no phases, exact fp32): ONE packing launch (fragments, BatchNorm coefficients on running statistics, folded
     // weights + bias of the pooling-epilogue blocks, re-ordered GRU input weights), then one launch per conv block
-    const bool eval_plan = !training && c->conv_mode == 0 && pb == 0 && pe == 2 * L.n_conv + 1;
+    // (conv_mode 2: the same plan with the bf16 blocks / projection of build_layout; it has no phases)
+    SED_REQUIRE(c->conv_mode != 2 || (pb == 0 && pe == 2 * L.n_conv + 1), "net_forward: the bf16 inference plan (conv_mode 2) runs whole, not in phases");
+    const bool eval_plan = !training && (c->conv_mode == 0 || c->conv_mode == 2) && pb == 0 && pe == 2 * L.n_conv + 1;
     const ConvL& qtop = L.cv[L.n_conv - 1];
-    const bool wih_permuted = eval_plan && qtop.ev && L.wih_perm != 0;
+    const bool wih_permuted = eval_plan && (qtop.ev || L.proj_bf) && L.wih_perm != 0;
     if (eval_plan) {
         const float* w[SED_MAX_CONV]; const float* bs[SED_MAX_CONV]; const float* gm[SED_MAX_CONV]; const float* bt[SED_MAX_CONV];
         const float* rm[SED_MAX_CONV]; const float* rv[SED_MAX_CONV];
         float* wf[SED_MAX_CONV]; float* sc[SED_MAX_CONV]; float* sh[SED_MAX_CONV]; float* bf[SED_MAX_CONV];
         int fold[SED_MAX_CONV], co[SED_MAX_CONV], ci[SED_MAX_CONV], wn[SED_MAX_CONV];
+        void* wb[SED_MAX_CONV];
         for (int l = 0; l < L.n_conv; ++l) {
             SED_REQUIRE(p->conv_w[l] && p->conv_b[l] && p->bn_g[l] && p->bn_b[l] && p->bn_rm[l] && p->bn_rv[l],
                         "net_forward: missing parameters of conv block %d", l);
             w[l] = p->conv_w[l]; bs[l] = p->conv_b[l]; gm[l] = p->bn_g[l]; bt[l] = p->bn_b[l]; rm[l] = p->bn_rm[l]; rv[l] = p->bn_rv[l];
             wf[l] = ws + L.wp_f[l]; sc[l] = ws + L.scale[l]; sh[l] = ws + L.shift[l]; bf[l] = ws + L.bias_f[l];
-            fold[l] = L.cv[l].ev; co[l] = L.cv[l].C; ci[l] = L.cv[l].Cin; wn[l] = L.cv[l].ev && L.cv[l].wino;
+            fold[l] = L.cv[l].ev || L.cv[l].bf; co[l] = L.cv[l].C; ci[l] = L.cv[l].Cin; wn[l] = L.cv[l].ev && L.cv[l].wino;
+            wb[l] = L.cv[l].bf ? (void*)wf[l] : nullptr;
+            if (L.cv[l].bf) wf[l] = nullptr;
         }
         if (wih_permuted) SED_REQUIRE(p->gru_wih[0][0] && p->gru_wih[0][1], "net_forward: missing parameters of GRU layer 0");
         SED_TRY(sed_internal_conv_pack_eval(L.n_conv, w, bs, gm, bt, rm, rv, c->bn_eps, wf, sc, sh, bf, fold, wn, co, ci,
                                             wih_permuted ? p->gru_wih[0][0] : nullptr, wih_permuted ? p->gru_wih[0][1] : nullptr,
-                                            ws + L.wih_perm, 3 * L.gr[0].H, qtop.C, qtop.Fp, stream));
+                                            ws + L.wih_perm, 3 * L.gr[0].H, qtop.C, qtop.Fp, wb, L.proj_bf, stream));
         for (int l = 0; l < L.n_conv; ++l) {
             const ConvL& q = L.cv[l];
             const float* in = (l == 0) ? x : ws + L.pooled[l - 1];
             const int last = (l == L.n_conv - 1);
-            if (q.fused) {
+            if (q.bf) {                 // input bf16 when the block below is bf16 too, else the fp32 pooled output (rounded while staged)
+                SED_TRY(sed_conv3x3_bf16_bn_relu_pool_eval(in, l > 0 && L.cv[l - 1].bf, ws + L.wp_f[l], ws + L.bias_f[l], ws + L.pooled[l],
+                                                           B, q.Cin, q.F, q.T, q.C, stream));
+            } else if (q.fused) {
                 SED_TRY(sed_conv1_bn_relu_pool_drop_fwd(in, ws + L.wp_f[l], p->conv_b[l], ws + L.scale[l], ws + L.shift[l], ws + L.pooled[l],
                                                         B, q.Cin, q.F, q.T, q.C, q.pf, q.pt, 0.f, 0, nullptr, nullptr, stream));
             } else if (q.ev && q.wino) {
@@ -369,7 +400,18 @@ static int forward_impl(const sed_net_cfg* c, const sed_net_params* p, const flo
         const float* wih[2] = {p->gru_wih[i][0], p->gru_wih[i][1]};
         if (i == 0 && wih_permuted) { wih[0] = ws + L.wih_perm; wih[1] = wih[0] + (size_t)3 * H * K; }      // channels-last feature columns
         const bool fused = wih[1] == wih[0] + (size_t)3 * H * K && p->gru_bih[i][1] == p->gru_bih[i][0] + 3 * H;
-        if (fused) {
+        if (i == 0 && eval_plan && L.proj_bf) {
+            // bf16 projection: A = the last block's bf16 output [M][F'*C], B = the bf16 re-ordered weights of both directions [6H][K]
+            // (one matrix); the biases per direction (they need not be adjacent)
+            const void* wb16 = (const void*)(ws + L.wih_perm);
+            if (p->gru_bih[i][1] == p->gru_bih[i][0] + 3 * H) {
+                SED_TRY(sed_gemm_bf16_nt(gin, wb16, p->gru_bih[i][0], ws + L.gi[i], 6 * H, M, 6 * H, K, stream));
+            } else {
+                for (int d = 0; d < 2; ++d)
+                    SED_TRY(sed_gemm_bf16_nt(gin, (const void*)((const uint16_t*)wb16 + (size_t)d * 3 * H * K), p->gru_bih[i][d],
+                                             ws + L.gi[i] + d * 3 * H, 6 * H, M, 3 * H, K, stream));
+            }
+        } else if (fused) {
             SED_TRY(sed_gemm_f32_ws(gin, K, 1, wih[0], 1, K, ws + L.gi[i], 6 * H, p->gru_bih[i][0], M, 6 * H, K, ws + L.gemm_ws, stream));
         } else {
             for (int d = 0; d < 2; ++d)
@@ -402,6 +444,7 @@ extern "C" int sed_net_forward_phases(const sed_net_cfg* c, const sed_net_params
                                       void* workspace, int training, uint64_t seed, int phase_begin, int phase_end,
                                       float count_scale, void* stream) {
     SED_REQUIRE(count_scale >= 1.f, "net_forward_phases: count_scale must be >= 1");
+    SED_REQUIRE(!c || c->conv_mode != 2, "net_forward_phases: conv_mode 2 (bf16 inference) has no phases; run it with sed_net_forward, training = 0");
     return forward_impl(c, p, x, logits, workspace, training, seed, nullptr, phase_begin, phase_end, count_scale, stream);
 }
 
@@ -428,7 +471,7 @@ extern "C" int sed_net_workspace_region(const sed_net_cfg* c, int training, cons
     if (conv_idx) {
         const ConvL& q = L.cv[index];
         const size_t nout = (size_t)c->B * q.T * q.F * q.C, npool = (size_t)c->B * q.Tp * q.Fp * q.C;
-        if (is("conv_out") && !q.fused && !q.ev) { off = L.conv_out[index]; n = nout; ok = true; }
+        if (is("conv_out") && !q.fused && !q.ev && !q.bf) { off = L.conv_out[index]; n = nout; ok = true; }
         else if (is("pooled")) { off = L.pooled[index]; n = npool; ok = true; }
         else if (is("mean")) { off = L.mean[index]; n = q.C; ok = true; }
         else if (is("rstd")) { off = L.rstd[index]; n = q.C; ok = true; }
@@ -460,6 +503,18 @@ extern "C" int sed_net_workspace_region(const sed_net_cfg* c, int training, cons
     SED_REQUIRE(ok, "net_workspace_region: no region '%s'[%d] in this plan (training=%d)", name, index, training);
     *offset_bytes = off * sizeof(float);
     *n_floats = n;
+    return 0;
+}
+
+// What the eval plan of this config runs in bf16 (conv_mode 2; all zero for modes 0 / 1): conv_bf16[l] for each conv block (its
+// weights, its input and its pooled output are bf16 — "pooled"[l] of sed_net_workspace_region then holds bf16 elements), *proj_bf16
+// for the input projection of GRU layer 0.
+extern "C" int sed_net_inference_plan(const sed_net_cfg* c, int* conv_bf16, int* proj_bf16) {
+    Layout L;
+    SED_TRY(build_layout(c, 0, &L));
+    SED_REQUIRE(conv_bf16 && proj_bf16, "net_inference_plan: null pointer");
+    for (int l = 0; l < L.n_conv; ++l) conv_bf16[l] = L.cv[l].bf;
+    *proj_bf16 = L.proj_bf;
     return 0;
 }
 

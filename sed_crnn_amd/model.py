@@ -320,7 +320,7 @@ class HipCRNN(nn.Module):
         return m
 
     # ── C structs ──
-    def _cfg(self, B, T):
+    def _cfg(self, B, T, training=True):
         c = NetCfg()
         c.B, c.Cin, c.F, c.T = B, self.in_channels, self.n_mels, T
         c.n_conv = len(self.conv_channels)
@@ -336,6 +336,8 @@ class HipCRNN(nn.Module):
             c.D[j] = d
         c.bn_eps, c.bn_momentum = self.bn_eps, self.bn_momentum
         c.conv_mode = int(getattr(self, "conv_mode", 0))
+        if not training and getattr(self, "inference_precision", "f32") == "bf16":
+            c.conv_mode = 2                                      # the bf16 inference plan (eval forward only)
         c.flags = int(getattr(self, "plan_flags", 0))          # SED_NET_* (tests / A-B measurements of the backward schedule)
         return c
 
@@ -345,6 +347,27 @@ class HipCRNN(nn.Module):
         the exact-fp32 MFMA path that every parity claim and the bench refer to."""
         self.conv_mode = {"f32": 0, "bf16x3": 1}[name]
         return self
+
+    def set_inference_precision(self, name="f32"):
+        """Precision of the EVAL-mode forward (``model.eval()``): ``"f32"`` (default) is the exact-fp32 plan every parity claim
+        refers to; ``"bf16"`` opts in to the bf16 inference plan: the 128-channel conv blocks at the top of the
+        stack and the first GRU layer's input projection run on bf16 operands with fp32 accumulation (rounded: the folded conv
+        weights, those blocks' inputs, both projection operands).  Training, the backward and ``set_conv_precision`` are not
+        affected.  A runtime setting: not part of ``state_dict``.  ``inference_plan()`` tells what runs in bf16."""
+        if name not in ("f32", "bf16"):
+            raise ValueError(f"inference precision must be 'f32' or 'bf16', got {name!r}")
+        self.inference_precision = name
+        return self
+
+    def inference_plan(self, B=1, T=None):
+        """What the eval forward of a [B, Cin, F, T] batch runs in under the current settings:
+        ``{"conv": ["f32" | "bf16", ...] per conv block, "proj": "f32" | "bf16"}`` (the GRU layer-0 input projection)."""
+        T = int(T) if T is not None else 32 * self.time_factor
+        cfg = self._cfg(int(B), T, training=False)
+        cb, pj = (C.c_int * _lib.SED_MAX_CONV)(), C.c_int(0)
+        check(lib().sed_net_inference_plan(C.byref(cfg), cb, C.byref(pj)), "sed_net_inference_plan")
+        name = {0: "f32", 1: "bf16"}
+        return {"conv": [name[cb[l]] for l in range(len(self.conv_channels))], "proj": name[pj.value]}
 
     def _param_structs(self):
         if self._structs is None:
@@ -375,6 +398,8 @@ class HipCRNN(nn.Module):
 
     def _workspace(self, cfg, training):
         key = (cfg.B, cfg.T, bool(training))
+        if cfg.conv_mode == 2:
+            key = key + ("bf16",)                # the bf16 inference plan has a layout of its own
         ws = self._ws.get(key)
         if ws is None:
             nbytes = lib().sed_net_workspace_bytes(C.byref(cfg), int(training))
@@ -456,6 +481,26 @@ class HipCRNN(nn.Module):
               "sed_net_workspace_region")
         return ws[off.value // 4: off.value // 4 + n.value]
 
+    def eval_workspace_view(self, name, index=0):
+        """The eval counterpart of ``workspace_view``: an intermediate of the LAST eval forward ("pooled"[l] block outputs,
+        "gi"[i], "gru_out"[i], ...).  A region the bf16 inference plan stores in bf16 comes back as a torch.bfloat16 view;
+        everything else flat fp32.  Valid until the next eval forward of that shape."""
+        if getattr(self, "_last_eval", None) is None:
+            raise RuntimeError("sed_crnn_amd: no eval forward to look into")
+        cfg, ws = self._last_eval
+        off, n = C.c_size_t(), C.c_size_t()
+        check(lib().sed_net_workspace_region(C.byref(cfg), 0, name.encode(), int(index), C.byref(off), C.byref(n)),
+              "sed_net_workspace_region")
+        bf16 = False
+        if name == "pooled" and cfg.conv_mode == 2:
+            cb, pj = (C.c_int * _lib.SED_MAX_CONV)(), C.c_int(0)
+            check(lib().sed_net_inference_plan(C.byref(cfg), cb, C.byref(pj)), "sed_net_inference_plan")
+            bf16 = bool(cb[int(index)])
+        o = off.value // 4
+        if bf16:
+            return ws[o: o + (n.value + 1) // 2].view(torch.bfloat16)[:n.value]
+        return ws[o: o + n.value]
+
     def routing(self, block):
         """The ReLU-gate / pooling arg-max decisions of conv block ``block`` in the LAST training forward, exactly as the
         backward kernels take them (``sed_net_routing``): uint8 [B, T_l/pt, F_l/pf, C], 0 = gate closed, 1 + w = the gradient
@@ -481,9 +526,11 @@ class HipCRNN(nn.Module):
         self._check_input(x)
         x = x.detach().contiguous().float()        # the kernels read dense fp32 [B,Cin,F,T]; backward re-reads THIS tensor
         B, _, _, T = x.shape
-        cfg = self._cfg(B, T)
+        cfg = self._cfg(B, T, training)
         P, _ = self._param_structs()
         ws = self._workspace(cfg, training)
+        if not training:
+            self._last_eval = (cfg, ws)
         logits = torch.empty(B, T // self.time_factor, self.dense[-1], device=x.device, dtype=torch.float32)
         if training:
             self._ticket += 1

@@ -92,6 +92,41 @@ def conv3x3_bn_relu_pool_eval(x, w, bias, gamma, beta, running_mean, running_var
     return out
 
 
+def conv3x3_bf16_pack_folded(w, bias, gamma, beta, running_mean, running_var, eps=1e-5):
+    """bf16 inference: BatchNorm folded into w (fp32), rounded to bf16 in the MFMA fragment order -> (wf bf16 [9*Cout*Cin], bias_folded fp32)"""
+    Cout, Cin = w.shape[:2]
+    wf = torch.empty(9 * Cout * Cin, device=w.device, dtype=torch.bfloat16)
+    bf = torch.empty(Cout, device=w.device)
+    check(lib().sed_conv3x3_bf16_pack_weights_bn_folded(ptr(_f32c(w)), ptr(bias), ptr(gamma), ptr(beta), ptr(running_mean),
+                                                        ptr(running_var), eps, ptr(wf), ptr(bf), Cout, Cin, stream_ptr()),
+          "conv3x3_bf16_pack_weights_bn_folded")
+    return wf, bf
+
+
+def conv3x3_bf16_bn_relu_pool_eval(x, wf, bias_folded, Cout):
+    """bf16 inference block: x [B,T,F,Cin] channels-last (bf16, or fp32 rounded while staged), wf / bias_folded from
+    conv3x3_bf16_pack_folded -> relu(max_pool((1,2))(conv3x3 + bias)) as bf16 [B,T//2,F,Cout]"""
+    B, T, F, Cin = x.shape
+    assert x.is_cuda and x.is_contiguous() and x.dtype in (torch.float32, torch.bfloat16)
+    assert wf.dtype == torch.bfloat16 and wf.numel() == 9 * Cout * Cin
+    if not lib().sed_conv3x3_bf16_eval_supported(B, Cin, F, T, Cout):
+        raise ValueError(f"conv3x3_bf16_bn_relu_pool_eval: shape B={B} Cin={Cin} F={F} T={T} Cout={Cout} not supported")
+    out = torch.empty(B, T // 2, F, Cout, device=x.device, dtype=torch.bfloat16)
+    check(lib().sed_conv3x3_bf16_bn_relu_pool_eval(ptr(x), int(x.dtype == torch.bfloat16), ptr(wf), ptr(_f32c(bias_folded)), ptr(out),
+                                                   B, Cin, F, T, Cout, stream_ptr()), "conv3x3_bf16_bn_relu_pool_eval")
+    return out
+
+
+def gemm_bf16_nt(A, B, bias=None):
+    """out fp32 [M,N] = A @ B^T (+ bias): A bf16 [M,K], B bf16 [N,K] (K % 32 == 0), fp32 accumulation"""
+    M, K = A.shape
+    N = B.shape[0]
+    assert A.dtype == torch.bfloat16 and B.dtype == torch.bfloat16 and A.is_contiguous() and B.is_contiguous() and B.shape[1] == K
+    out = torch.empty(M, N, device=A.device)
+    check(lib().sed_gemm_bf16_nt(ptr(A), ptr(B), ptr(bias), ptr(out), N, M, N, K, stream_ptr()), "gemm_bf16_nt")
+    return out
+
+
 def conv3x3_wgrad(x, dy, x_is_nchw, mode=0):
     if x_is_nchw:
         B, Cin, F, T = x.shape

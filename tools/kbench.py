@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Single-kernel timings on the GPU (tuning aid): python tools/kbench.py [conv|wgrad|gemm|bn|all] [--iters N]
+"""Single-kernel timings on the GPU (tuning aid): python tools/kbench.py [conv|bf16|wgrad|gemm|bn|all] [--iters N]
 Shapes are the BASELINE config-2 launches.  Times come from torch events on the launch stream."""
 import argparse
 import sys
@@ -45,6 +45,21 @@ def main():
             wfb, _ = ops.conv3x3_pack(w, mode=1)
             ms = timeit(lambda: ops.conv3x3_fwd(x, wfb, bias, False, mode=1), a.iters)
             print(f"conv3x3 bf16x3 (experiment)  B{B} T{T}: {ms:.3f} ms  {fl/ms/1e9:.1f} fp32-equivalent TFLOP/s")
+    if a.what in ("bf16", "all"):          # the bf16 inference plan: algorithmic TFLOP/s against the 2.5 PFLOP/s bf16 peak
+        for T in (128, 64):
+            x = torch.randn(B, T, 40, 128, device=dev).to(torch.bfloat16)
+            w = torch.randn(128, 128, 3, 3, device=dev) * 0.03
+            one, zero = torch.ones(128, device=dev), torch.zeros(128, device=dev)
+            wf, bf = ops.conv3x3_bf16_pack_folded(w, zero, one, zero, zero, one)
+            ms = timeit(lambda: ops.conv3x3_bf16_bn_relu_pool_eval(x, wf, bf, 128), a.iters)
+            fl = 2 * 9 * 128 * 128 * B * T * 40
+            print(f"conv3x3 bf16 eval (bias+relu+pool) B{B} T{T}: {ms:.3f} ms  {fl/ms/1e9:.1f} TFLOP/s ({fl/ms/1e9/2500*100:.1f} % of bf16 peak)")
+        for M, N, K in ((4096, 768, 5120), (1024, 1536, 16384), (32, 768, 5120)):
+            A = torch.randn(M, K, device=dev).to(torch.bfloat16)
+            W = (torch.randn(N, K, device=dev) * 0.01).to(torch.bfloat16)
+            ms = timeit(lambda: ops.gemm_bf16_nt(A, W), a.iters)
+            fl = 2 * M * N * K
+            print(f"gemm bf16 [{M},{K}] x [{N},{K}]^T: {ms:.3f} ms  {fl/ms/1e9:.1f} TFLOP/s ({fl/ms/1e9/2500*100:.1f} % of bf16 peak)")
     if a.what in ("wgrad", "all"):
         for T in (128, 64):
             x = torch.randn(B, T, 40, 128, device=dev)
