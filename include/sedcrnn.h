@@ -465,6 +465,27 @@ int sed_col_standardize(const float* x, long N, int F, const double* mean, const
 int sed_segment_counts(const float* pred, const float* lab, long rows, int K, int block, float threshold,
                        unsigned long long* counts17, void* stream);
 
+/* ───────────── whole-recording event detection (sed_crnn_amd/detect.py) ─────────────
+ * The eval forward runs on windows of a recording; these two entries turn its window logits into events.  Frames here are
+ * OUTPUT frames (tf = product of the time pools input frames each).  Window w covers output frames
+ * [start(w), start(w) + win_out) with start(w) = min(w * hop_out, last_start_out): the regular grid plus, where the last regular
+ * window stops short, one extra window aligned to the end (last_start_out + win_out == n_out).
+ * sed_detect_stitch: logits [n_win][win_out][K] -> probs [n_out][K] = sigmoid, then combined over the covering windows
+ * (combine 0 = mean, 1 = max) in increasing window order (bitwise deterministic, no atomics); `trim` drops that many outermost
+ * frames of each window on the sides that do not touch the recording's ends (refused if it would leave a frame uncovered). */
+int sed_detect_stitch(const float* logits, long n_win, int win_out, int K, int hop_out, long last_start_out, long n_out,
+                      int combine, int trim, float* probs, void* stream);
+/* sed_detect_events: probs [n_out][K] (K <= 32), per class: median filter of odd width `median` (1 = off, <= 31; edges
+ * 'nearest'), runs of p' > lo kept when max p' > hi (hi >= lo), kept runs merged across gaps of <= min_gap frames, events
+ * shorter than min_len frames dropped.  Event e: cls, onset (inclusive), offset (exclusive), peak = max of the UNFILTERED track
+ * over the event, peak_frame = its first arg-max; sorted by (class, onset).  *count (device int) = the true number of events;
+ * at most max_events are written (0: count only, the outputs may then be NULL), so a host can grow its buffers and rerun.
+ * workspace >= sed_detect_workspace_bytes(n_out, K, max_events) (0 = bad sizes). */
+size_t sed_detect_workspace_bytes(long n_out, int K, int max_events);
+int sed_detect_events(const float* probs, long n_out, int K, int median, float lo, float hi, int min_gap, int min_len,
+                      int max_events, void* workspace, size_t workspace_bytes, int* cls, int* onset, int* offset,
+                      float* peak, int* peak_frame, int* count, void* stream);
+
 /* ───────────── whole-network plan (TimePooledCRNN.forward sed.py:105-112 / crnn_lightning.py:66-73) ───────────── */
 typedef struct sed_net_cfg {
     int B, Cin, F, T;                 /* input x [B][Cin][F][T] */

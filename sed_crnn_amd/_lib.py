@@ -136,6 +136,9 @@ SIGNATURES = {
     "sed_col_mean_std": (_i, [_fp, _l, _i, _fp, _fp, _fp, _stream]),
     "sed_col_standardize": (_i, [_fp, _l, _i, _fp, _fp, _fp, _stream]),
     "sed_segment_counts": (_i, [_fp, _fp, _l, _i, _i, _f, _fp, _stream]),
+    "sed_detect_stitch": (_i, [_fp, _l, _i, _i, _i, _l, _l, _i, _i, _fp, _stream]),
+    "sed_detect_workspace_bytes": (_sz, [_l, _i, _i]),
+    "sed_detect_events": (_i, [_fp, _l, _i, _i, _f, _f, _i, _i, _i, _fp, _sz, _fp, _fp, _fp, _fp, _fp, _fp, _stream]),
     "sed_prof_enable": (_i, [C.c_uint]),
     "sed_prof_read": (_i, [_i, C.POINTER(_d), C.POINTER(_l), C.POINTER(_d)]),
     "sed_prof_tag_name": (C.c_char_p, [_i]),
