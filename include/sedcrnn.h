@@ -432,6 +432,16 @@ int sed_logmel_build_tables(const float* window_host, const float* melfb_host, i
 int sed_logmel(const float* pcm, long n_samples, const void* tables, size_t tables_bytes,
                const float* mu, const float* inv_sigma, float* out,
                int n_fft, int hop, int n_mels, int pad_mode, void* stream);
+/* sed_logmel_batch: R mono clips packed in ONE pcm buffer [pcm_len] -> out [sum_r (1 + n_r/hop)][n_mels], the clips' frames
+ * back to back in clip order, in one launch.  clips_host [R][2] = {first sample, n_r >= 1} (HOST array, validated: every
+ * clip inside the buffer) is uploaded into `workspace` (>= sed_logmel_batch_workspace_bytes(R), device) on the stream; out_rows
+ * must equal the frame total (< 2^31).  Each clip is framed and padded (pad_mode) at its own ends exactly like sed_logmel on
+ * that clip alone: the result is bit for bit that of R sed_logmel calls.  A clip whose first sample is not 8-byte aligned
+ * takes the guarded load path (same values). */
+size_t sed_logmel_batch_workspace_bytes(int R);
+int sed_logmel_batch(const float* pcm, long pcm_len, const long* clips_host, int R, const void* tables, size_t tables_bytes,
+                     const float* mu, const float* inv_sigma, float* out, long out_rows, int n_fft, int hop, int n_mels,
+                     int pad_mode, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ───────────── GPU-resident minibatch assembly (sed.py:64-79; decorte_datamodule.py:39-49,77-111; utils.py:15-41) ─────────────
  * mel [N][C*F] (a whole fold, device-resident; channel c = columns [c*F,(c+1)*F)), lab [N][K].
@@ -485,6 +495,23 @@ size_t sed_detect_workspace_bytes(long n_out, int K, int max_events);
 int sed_detect_events(const float* probs, long n_out, int K, int median, float lo, float hi, int min_gap, int min_len,
                       int max_events, void* workspace, size_t workspace_bytes, int* cls, int* onset, int* offset,
                       float* peak, int* peak_frame, int* count, void* stream);
+/* Batches of R recordings packed back to back (the tracks of recording r are rows [off_r, off_r + n_out_r) of probs).
+ * Recording tables are HOST arrays, validated and then uploaded into `workspace` on the stream (a bad table is an error,
+ * never a read out of bounds).  workspace >= sed_detect_batch_workspace_bytes(n_total, K, R, max_events) for both entries
+ * (n_total = sum of n_out_r < 2^31, n_total * K < 2^31; 0 = bad sizes).
+ * sed_detect_stitch_batch: recs_host [R][6] = {first logit (float index into logits [logits_len]), n_win, win_out, hop_out,
+ * last_start_out, n_out} per recording, logit extents n_win*win_out*K inside the buffer and not overlapping (any order);
+ * every grid checked like sed_detect_stitch's.  probs [n_total][K]: each recording's rows equal sed_detect_stitch of its logits.
+ * sed_detect_events_batch: n_out_host [R]; the decoder of sed_detect_events per recording (the median clamps, runs, gaps and
+ * events stop at each recording's ends; onset / offset / peak_frame are local to the recording), events sorted by
+ * (recording, class, onset) with rec = the recording.  event_off [R+1] (device ints): recording r's events are
+ * [event_off[r], event_off[r+1]); event_off[R] = the true total.  At most max_events are written (0: counts only). */
+size_t sed_detect_batch_workspace_bytes(long n_total, int K, int R, int max_events);
+int sed_detect_stitch_batch(const float* logits, long logits_len, const long* recs_host, int R, int K, int combine, int trim,
+                            float* probs, long n_total, void* workspace, size_t workspace_bytes, void* stream);
+int sed_detect_events_batch(const float* probs, const long* n_out_host, int R, int K, int median, float lo, float hi, int min_gap,
+                            int min_len, int max_events, void* workspace, size_t workspace_bytes, int* rec, int* cls, int* onset,
+                            int* offset, float* peak, int* peak_frame, int* event_off, void* stream);
 
 /* ───────────── whole-network plan (TimePooledCRNN.forward sed.py:105-112 / crnn_lightning.py:66-73) ───────────── */
 typedef struct sed_net_cfg {

@@ -130,6 +130,8 @@ SIGNATURES = {
     "sed_logmel_tables_bytes": (_sz, [_fp, _i, _i]),
     "sed_logmel_build_tables": (_i, [_fp, _fp, _i, _i, _fp, _sz]),
     "sed_logmel": (_i, [_fp, _l, _fp, _sz, _fp, _fp, _fp, _i, _i, _i, _i, _stream]),
+    "sed_logmel_batch_workspace_bytes": (_sz, [_i]),
+    "sed_logmel_batch": (_i, [_fp, _l, _fp, _i, _fp, _sz, _fp, _fp, _fp, _l, _i, _i, _i, _i, _fp, _sz, _stream]),
     "sed_window_batch": (_i, [_fp, _fp, _l, _i, _i, _i, _fp, _fp, _fp, _i, _i, _i, _fp, _fp, _i, _i, _i, _stream]),
     "sed_pack_sequences": (_i, [_fp, _l, _i, _i, _i, _i, _fp, _stream]),
     "sed_col_mean_std_workspace_bytes": (_sz, [_i]),
@@ -139,6 +141,9 @@ SIGNATURES = {
     "sed_detect_stitch": (_i, [_fp, _l, _i, _i, _i, _l, _l, _i, _i, _fp, _stream]),
     "sed_detect_workspace_bytes": (_sz, [_l, _i, _i]),
     "sed_detect_events": (_i, [_fp, _l, _i, _i, _f, _f, _i, _i, _i, _fp, _sz, _fp, _fp, _fp, _fp, _fp, _fp, _stream]),
+    "sed_detect_batch_workspace_bytes": (_sz, [_l, _i, _i, _i]),
+    "sed_detect_stitch_batch": (_i, [_fp, _l, _fp, _i, _i, _i, _i, _fp, _l, _fp, _sz, _stream]),
+    "sed_detect_events_batch": (_i, [_fp, _fp, _i, _i, _i, _f, _f, _i, _i, _i, _fp, _sz, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _stream]),
     "sed_prof_enable": (_i, [C.c_uint]),
     "sed_prof_read": (_i, [_i, C.POINTER(_d), C.POINTER(_l), C.POINTER(_d)]),
     "sed_prof_tag_name": (C.c_char_p, [_i]),

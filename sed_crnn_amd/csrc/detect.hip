@@ -4,40 +4,77 @@
 // Frame arithmetic (output frames, tf input frames each): window w covers [start(w), start(w) + win_out) with
 // start(w) = min(w * hop_out, last_start_out) — the regular grid 0, hop, 2 hop, ... plus, where the last regular window stops
 // short of the end, one extra window aligned to the end (last_start_out + win_out == n_out).  The host planner builds that grid.
+#include <algorithm>
+#include <vector>
 #include "common.h"
 
 // ───────────────────────── stitch: sigmoid, then mean / max over the covering windows ─────────────────────────
 // One thread per (output frame, class): the covering windows are a contiguous range of w (start(w) is strictly increasing);
 // they are visited in increasing w, so the sum has one fixed order (bitwise deterministic, no atomics).
+__device__ __forceinline__ float stitch_one(const float* __restrict__ logits, int n_win, int win_out, int K, int hop_out,
+                                            int last_start, int n_out, int combine, int trim, int j, int k) {
+    // last window whose start is <= j
+    int whi = j >= last_start ? n_win - 1 : j / hop_out;
+    if (whi > n_win - 1) whi = n_win - 1;
+    int wlo = whi;
+    while (wlo > 0) {                                                // first window that still reaches j
+        const long s = (long)(wlo - 1) * hop_out < last_start ? (long)(wlo - 1) * hop_out : last_start;
+        if (s + win_out <= j) break;
+        --wlo;
+    }
+    float acc = combine ? -INFINITY : 0.f;
+    int cnt = 0;
+    for (int w = wlo; w <= whi; ++w) {
+        const long s = (long)w * hop_out < last_start ? (long)w * hop_out : last_start;
+        const long lo = s + (s > 0 ? trim : 0);
+        const long hi = s + win_out - (s + win_out < n_out ? trim : 0);
+        if (j < lo || j >= hi) continue;
+        const float x = logits[((size_t)w * win_out + (j - s)) * K + k];
+        const float p = 1.0f / (1.0f + expf(-x));
+        if (combine) acc = fmaxf(acc, p);
+        else acc += p;
+        ++cnt;
+    }
+    return combine ? acc : acc / (float)cnt;                          // cnt >= 1: the host checked coverage
+}
+
 __global__ __launch_bounds__(256) void detect_stitch_k(const float* __restrict__ logits, int n_win, int win_out, int K,
                                                        int hop_out, int last_start, int n_out, int combine, int trim,
                                                        float* __restrict__ probs) {
     const long total = (long)n_out * K;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const int j = (int)(i / K), k = (int)(i - (long)j * K);
-        // last window whose start is <= j
-        int whi = j >= last_start ? n_win - 1 : j / hop_out;
-        if (whi > n_win - 1) whi = n_win - 1;
-        int wlo = whi;
-        while (wlo > 0) {                                            // first window that still reaches j
-            const long s = (long)(wlo - 1) * hop_out < last_start ? (long)(wlo - 1) * hop_out : last_start;
-            if (s + win_out <= j) break;
-            --wlo;
-        }
-        float acc = combine ? -INFINITY : 0.f;
-        int cnt = 0;
-        for (int w = wlo; w <= whi; ++w) {
-            const long s = (long)w * hop_out < last_start ? (long)w * hop_out : last_start;
-            const long lo = s + (s > 0 ? trim : 0);
-            const long hi = s + win_out - (s + win_out < n_out ? trim : 0);
-            if (j < lo || j >= hi) continue;
-            const float x = logits[((size_t)w * win_out + (j - s)) * K + k];
-            const float p = 1.0f / (1.0f + expf(-x));
-            if (combine) acc = fmaxf(acc, p);
-            else acc += p;
-            ++cnt;
-        }
-        probs[i] = combine ? acc : acc / (float)cnt;                  // cnt >= 1: the host checked coverage
+        probs[i] = stitch_one(logits, n_win, win_out, K, hop_out, last_start, n_out, combine, trim, j, k);
+    }
+}
+
+// the grid of one recording of a batch (sed_detect_stitch_batch): its logits start logit_off floats into the packed buffer
+struct DetRec { long logit_off; int n_win, win_out, hop_out, last_start, n_out, pad; };
+
+// last r with off[r] <= x (off[0] = 0 <= x, off ascending)
+__device__ __forceinline__ int find_seg(const int* __restrict__ off, int R, long x) {
+    int lo = 0, hi = R - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (off[mid] <= x) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// One thread per (packed output frame, class): its recording by binary search over the output offsets, then exactly the
+// arithmetic of detect_stitch_k with that recording's grid (so a recording's track equals sed_detect_stitch of its logits)
+__global__ __launch_bounds__(256) void detect_stitch_batch_k(const float* __restrict__ logits, const DetRec* __restrict__ recs,
+                                                             const int* __restrict__ out_off, int R, long total_out, int K,
+                                                             int combine, int trim, float* __restrict__ probs) {
+    const long total = total_out * K;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const long row = i / K;
+        const int k = (int)(i - row * K);
+        const int r = find_seg(out_off, R, row);
+        const DetRec d = recs[r];
+        probs[i] = stitch_one(logits + d.logit_off, d.n_win, d.win_out, K, d.hop_out, d.last_start, d.n_out, combine, trim,
+                              (int)(row - out_off[r]), k);
     }
 }
 
@@ -112,17 +149,27 @@ __global__ __launch_bounds__(256) void detect_bits_k(const float* __restrict__ p
     }
 }
 
+// Batched (SEG, sed_detect_events_batch): one wave per (recording r, class k), workgroup r*K + k; recording r's bit tracks
+// are [K][n_words_r] at word K*word_off[r] (every track starts on a word boundary), so no run, gap or event crosses recordings.
 #define DETECT_EDGE_CAP 4096                                      // 64 words x 64 bits: every edge of a chunk
+template <bool SEG = false>
 __global__ __launch_bounds__(64) void detect_walk_k(const unsigned long long* __restrict__ on_bits,
                                                     const unsigned long long* __restrict__ hi_bits, long n_words, int min_gap,
                                                     int min_len, int write, int max_events, int* __restrict__ counts,
                                                     const int* __restrict__ offsets, int* __restrict__ cls,
-                                                    int* __restrict__ onset, int* __restrict__ offset) {
+                                                    int* __restrict__ onset, int* __restrict__ offset,
+                                                    const int* __restrict__ word_off = nullptr, int K = 0, int* __restrict__ rec = nullptr) {
     __shared__ int epos[DETECT_EDGE_CAP], eh[DETECT_EDGE_CAP];
-    const int k = blockIdx.x, lane = threadIdx.x;
-    const unsigned long long* ob = on_bits + (size_t)k * n_words;
-    const unsigned long long* hb = hi_bits + (size_t)k * n_words;
-    const long base = write ? offsets[k] : 0;
+    const int lane = threadIdx.x, r = SEG ? (int)blockIdx.x / K : 0;
+    const int k = SEG ? (int)blockIdx.x - r * K : (int)blockIdx.x;
+    size_t track0 = 0;
+    if (SEG) {
+        track0 = (size_t)K * word_off[r];
+        n_words = word_off[r + 1] - word_off[r];
+    }
+    const unsigned long long* ob = on_bits + track0 + (size_t)k * n_words;
+    const unsigned long long* hb = hi_bits + track0 + (size_t)k * n_words;
+    const long base = write ? offsets[blockIdx.x] : 0;
     unsigned carry_top = 0;                      // bit 63 of the previous chunk's last word
     long hbase = 0;                              // high bits before this chunk
     // lane 0's walk state
@@ -164,6 +211,7 @@ __global__ __launch_bounds__(64) void detect_walk_k(const unsigned long long* __
                 if (have && p_off - p_on >= min_len) {
                     if (write && base + cnt < max_events) {
                         cls[base + cnt] = k; onset[base + cnt] = p_on; offset[base + cnt] = p_off;
+                        if (SEG) rec[base + cnt] = r;
                     }
                     ++cnt;
                 }
@@ -176,10 +224,13 @@ __global__ __launch_bounds__(64) void detect_walk_k(const unsigned long long* __
     }
     if (lane == 0) {
         if (have && p_off - p_on >= min_len) {
-            if (write && base + cnt < max_events) { cls[base + cnt] = k; onset[base + cnt] = p_on; offset[base + cnt] = p_off; }
+            if (write && base + cnt < max_events) {
+                cls[base + cnt] = k; onset[base + cnt] = p_on; offset[base + cnt] = p_off;
+                if (SEG) rec[base + cnt] = r;
+            }
             ++cnt;
         }
-        if (!write) counts[k] = cnt;
+        if (!write) counts[blockIdx.x] = cnt;
     }
 }
 
@@ -190,20 +241,58 @@ __global__ void detect_offsets_k(const int* __restrict__ counts, int K, int* __r
     *total = t;
 }
 
-// one workgroup per event (grid-stride over the events): max of the unfiltered track over [onset, offset), first arg-max
+// the batch: exclusive scan of the R*K counts by one workgroup (wave scans + the 16 wave totals, 1 024 counts per step) ->
+// offsets [R*K]; event_off [R+1] = the offset of each recording's first class, and the total
+__global__ __launch_bounds__(1024) void detect_scan_k(const int* __restrict__ counts, int n, int K, int* __restrict__ offsets,
+                                                      int* __restrict__ event_off) {
+    __shared__ int wsum[16];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    int carry = 0;
+    for (int base = 0; base < n; base += 1024) {
+        const int i = base + tid;
+        const int c = i < n ? counts[i] : 0;
+        int x = c;                                                    // inclusive wave scan
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int y = __shfl_up(x, o, 64);
+            if (lane >= o) x += y;
+        }
+        if (lane == 63) wsum[wv] = x;
+        __syncthreads();
+        int pre = 0, step = 0;
+        for (int w = 0; w < 16; ++w) {
+            pre += w < wv ? wsum[w] : 0;
+            step += wsum[w];
+        }
+        const int excl = carry + pre + x - c;
+        if (i < n) {
+            offsets[i] = excl;
+            if (i % K == 0) event_off[i / K] = excl;
+        }
+        carry += step;
+        __syncthreads();                                              // wsum is rewritten by the next step
+    }
+    if (tid == 0) event_off[n / K] = carry;
+}
+
+// one workgroup per event (grid-stride over the events): max of the unfiltered track over [onset, offset), first arg-max.
+// SEG: event e belongs to recording rec[e], whose track starts at packed row out_off[rec[e]]
+template <bool SEG = false>
 __global__ __launch_bounds__(256) void detect_peaks_k(const float* __restrict__ probs, int K, const int* __restrict__ total,
                                                       int max_events, const int* __restrict__ cls, const int* __restrict__ onset,
                                                       const int* __restrict__ offset, float* __restrict__ peak,
-                                                      int* __restrict__ peak_frame) {
+                                                      int* __restrict__ peak_frame, const int* __restrict__ rec = nullptr,
+                                                      const int* __restrict__ out_off = nullptr) {
     __shared__ float sv[4];
     __shared__ int si[4];
     const int n = *total < max_events ? *total : max_events;
     for (int e = blockIdx.x; e < n; e += gridDim.x) {
         const int k = cls[e], a = onset[e], b = offset[e];
+        const float* pr = SEG ? probs + (size_t)out_off[rec[e]] * K : probs;
         float bv = -INFINITY;
         int bi = 0x7fffffff;
         for (int j = a + (int)threadIdx.x; j < b; j += 256) {
-            const float v = probs[(size_t)j * K + k];
+            const float v = pr[(size_t)j * K + k];
             if (v > bv) { bv = v; bi = j; }                       // ascending j: the first maximum of this thread's frames
         }
 #pragma unroll
@@ -268,5 +357,178 @@ extern "C" int sed_detect_events(const float* probs, long n_out, int K, int medi
     SED_LAUNCH_CHECK("detect_walk(write)");
     detect_peaks_k<<<max_events < 1024 ? max_events : 1024, 256, 0, s>>>(probs, K, count, max_events, cls, onset, offset, peak, peak_frame);
     SED_LAUNCH_CHECK("detect_peaks");
+    return 0;
+}
+
+// ───────────────────────── batch: R recordings packed back to back ─────────────────────────
+// Phase 1 of the batch: one wave per (packed word, class).  A wave's 64 frames are one word of one recording's track (tracks
+// start on word boundaries), so the recording is wave-uniform; the median clamps at that recording's own ends.
+template <int M>
+__global__ __launch_bounds__(256) void detect_bits_batch_k(const float* __restrict__ probs, const int* __restrict__ out_off,
+                                                           const int* __restrict__ word_off, int R, int K, float lo, float hi,
+                                                           unsigned long long* __restrict__ on_bits,
+                                                           unsigned long long* __restrict__ hi_bits) {
+    const int k = blockIdx.y, lane = threadIdx.x & 63;
+    const int gw = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (gw >= word_off[R]) return;                                    // wave-uniform
+    const int r = __builtin_amdgcn_readfirstlane(find_seg(word_off, R, gw));
+    const int n_out = out_off[r + 1] - out_off[r], nw = word_off[r + 1] - word_off[r], lw = gw - word_off[r];
+    const int j = lw * 64 + lane;
+    bool on = false, high = false;
+    if (j < n_out) {
+        const float p = median_nearest<M>(probs + (size_t)out_off[r] * K, j, k, K, n_out);
+        on = p > lo;
+        high = p > hi;
+    }
+    const unsigned long long bo = __ballot(on), bh = __ballot(high);
+    if (lane == 0) {
+        const size_t at = (size_t)K * word_off[r] + (size_t)k * nw + lw;
+        on_bits[at] = bo;
+        hi_bits[at] = bh;
+    }
+}
+
+// workspace of the batch entries (16-byte aligned regions): the stitch's DetRec [R] and output offsets [R+1]; the decoder's output
+// and word offsets [R+1] each, counts [R*K], offsets [R*K]; then the two bit tracks [K][words], words <= n_total/64 + R
+static inline size_t al16(size_t b) { return (b + 15) & ~(size_t)15; }
+struct DetBatchWs {
+    DetRec* recs; int* s_out_off; int* out_off; int* word_off; int* counts; int* offs; unsigned long long* ob; unsigned long long* hb;
+};
+static DetBatchWs det_batch_layout(void* ws, int R, int K, long words) {
+    char* p = (char*)ws;
+    DetBatchWs w;
+    w.recs = (DetRec*)p; p += al16((size_t)R * sizeof(DetRec));
+    w.s_out_off = (int*)p; p += al16((size_t)(R + 1) * 4);
+    w.out_off = (int*)p; p += al16((size_t)(R + 1) * 8);           // out_off [R+1] then word_off [R+1]: one upload
+    w.word_off = w.out_off + R + 1;
+    w.counts = (int*)p; p += al16((size_t)R * K * 4);
+    w.offs = (int*)p; p += al16((size_t)R * K * 4);
+    w.ob = (unsigned long long*)p;
+    w.hb = w.ob + (size_t)K * words;
+    return w;
+}
+
+extern "C" size_t sed_detect_batch_workspace_bytes(long n_total, int K, int R, int max_events) {
+    if (R < 1 || n_total < R || n_total > 0x7fffffffL || K < 1 || K > 32 || max_events < 0 || n_total * K > 0x7fffffffL) return 0;
+    const long words = n_total / 64 + R;
+    return al16((size_t)R * sizeof(DetRec)) + al16((size_t)(R + 1) * 4) + al16((size_t)(R + 1) * 8) + 2 * al16((size_t)R * K * 4) +
+           (size_t)2 * K * words * sizeof(unsigned long long);
+}
+
+static int det_upload(void* dst, const void* src, size_t bytes, hipStream_t s, const char* what) {
+    const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) { sed_set_error("%s: upload of the recording table: %s", what, hipGetErrorString(e)); return (int)e; }
+    return 0;
+}
+
+extern "C" int sed_detect_stitch_batch(const float* logits, long logits_len, const long* recs_host, int R, int K, int combine, int trim,
+                                       float* probs, long n_total, void* workspace, size_t workspace_bytes, void* stream) {
+    SED_REQUIRE(logits && recs_host && probs && workspace, "detect_stitch_batch: null pointer");
+    const size_t need = sed_detect_batch_workspace_bytes(n_total, K, R, 0);
+    SED_REQUIRE(need > 0 && logits_len >= 1, "detect_stitch_batch: bad sizes (R=%d, K=%d in 1..32, n_total=%ld)", R, K, n_total);
+    SED_REQUIRE(workspace_bytes >= need, "detect_stitch_batch: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    SED_REQUIRE(combine == 0 || combine == 1, "detect_stitch_batch: combine must be 0 (mean) or 1 (max), got %d", combine);
+    SED_REQUIRE(trim >= 0, "detect_stitch_batch: trim must be >= 0 (got %d)", trim);
+    std::vector<DetRec> h(R);
+    std::vector<int> off(R + 1);
+    struct Ext { long lo, hi; int r; };
+    std::vector<Ext> ext(R);
+    long rows = 0;
+    for (int r = 0; r < R; ++r) {
+        const long* d = recs_host + 6 * r;
+        const long lo = d[0], n_win = d[1], win_out = d[2], hop_out = d[3], last = d[4], n_out = d[5];
+        SED_REQUIRE(n_win >= 1 && win_out >= 1 && hop_out >= 1 && last >= 0 && n_out >= 1 && n_win <= 0x7fffffffL &&
+                        win_out <= 0x7fffffffL && hop_out <= 0x7fffffffL && n_out <= n_total,
+                    "detect_stitch_batch: recording %d: bad sizes (n_win=%ld, win_out=%ld, hop_out=%ld, n_out=%ld)", r, n_win, win_out,
+                    hop_out, n_out);
+        SED_REQUIRE(last + win_out == n_out, "detect_stitch_batch: recording %d: the last window must end at the recording's end", r);
+        SED_REQUIRE((n_win - 1) * hop_out >= last && (n_win < 2 || (n_win - 2) * hop_out < last),
+                    "detect_stitch_batch: recording %d: last_start_out=%ld is not the last start of a %ld-window grid with hop %ld", r,
+                    last, n_win, hop_out);
+        SED_REQUIRE(n_win == 1 || hop_out + 2L * trim <= win_out,
+                    "detect_stitch_batch: recording %d: trim=%d leaves output frames uncovered (hop_out=%ld, win_out=%ld)", r, trim,
+                    hop_out, win_out);
+        // the logits [n_win][win_out][K] of the recording: inside the buffer (overlaps are checked below)
+        SED_REQUIRE(lo >= 0 && lo <= logits_len && n_win * win_out <= (logits_len - lo) / K,
+                    "detect_stitch_batch: recording %d: logits [%ld, +%ld x %ld x %d) leave the buffer of %ld floats", r, lo, n_win,
+                    win_out, K, logits_len);
+        ext[r] = {lo, lo + n_win * win_out * K, r};
+        h[r] = DetRec{lo, (int)n_win, (int)win_out, (int)hop_out, (int)last, (int)n_out, 0};
+        off[r] = (int)rows;
+        rows += n_out;
+        SED_REQUIRE(rows <= n_total, "detect_stitch_batch: the recordings have more than n_total=%ld output frames", n_total);
+    }
+    SED_REQUIRE(rows == n_total, "detect_stitch_batch: the recordings have %ld output frames, probs has %ld", rows, n_total);
+    std::sort(ext.begin(), ext.end(), [](const Ext& a, const Ext& b) { return a.lo < b.lo; });
+    for (int i = 1; i < R; ++i)
+        SED_REQUIRE(ext[i].lo >= ext[i - 1].hi, "detect_stitch_batch: the logits of recordings %d and %d overlap", ext[i - 1].r, ext[i].r);
+    off[R] = (int)rows;
+    hipStream_t s = as_stream(stream);
+    const DetBatchWs w = det_batch_layout(workspace, R, K, n_total / 64 + R);
+    if (int rc = det_upload(w.recs, h.data(), (size_t)R * sizeof(DetRec), s, "detect_stitch_batch")) return rc;
+    if (int rc = det_upload(w.s_out_off, off.data(), (size_t)(R + 1) * 4, s, "detect_stitch_batch")) return rc;
+    const long nb = (n_total * K + 255) / 256;
+    detect_stitch_batch_k<<<(unsigned)(nb < 8192 ? nb : 8192), 256, 0, s>>>(logits, w.recs, w.s_out_off, R, n_total, K, combine, trim,
+                                                                              probs);
+    SED_LAUNCH_CHECK("detect_stitch_batch");
+    return 0;
+}
+
+template <int M>
+static void launch_bits_batch(const float* probs, const int* out_off, const int* word_off, int R, int K, long words, float lo,
+                              float hi, unsigned long long* ob, unsigned long long* hb, hipStream_t s) {
+    detect_bits_batch_k<M><<<dim3((unsigned)cdiv(words, 4), (unsigned)K), 256, 0, s>>>(probs, out_off, word_off, R, K, lo, hi, ob, hb);
+}
+
+extern "C" int sed_detect_events_batch(const float* probs, const long* n_out_host, int R, int K, int median, float lo, float hi,
+                                       int min_gap, int min_len, int max_events, void* workspace, size_t workspace_bytes, int* rec,
+                                       int* cls, int* onset, int* offset, float* peak, int* peak_frame, int* event_off, void* stream) {
+    SED_REQUIRE(probs && n_out_host && workspace && event_off, "detect_events_batch: null pointer");
+    SED_REQUIRE(R >= 1 && K >= 1 && K <= 32 && max_events >= 0, "detect_events_batch: bad sizes (R=%d, K=%d in 1..32, max_events=%d)",
+                R, K, max_events);
+    SED_REQUIRE(median >= 1 && median <= 31 && (median & 1), "detect_events_batch: median width must be odd, 1..31 (got %d)", median);
+    SED_REQUIRE(hi >= lo, "detect_events_batch: need hi >= lo (got lo=%g, hi=%g)", (double)lo, (double)hi);
+    SED_REQUIRE(min_gap >= 0 && min_len >= 1, "detect_events_batch: min_gap >= 0 and min_len >= 1 (got %d, %d)", min_gap, min_len);
+    SED_REQUIRE(max_events == 0 || (rec && cls && onset && offset && peak && peak_frame), "detect_events_batch: null output pointer");
+    std::vector<int> h(2 * (size_t)(R + 1));
+    int *out_off = h.data(), *word_off = out_off + R + 1;
+    long rows = 0, words = 0;
+    for (int r = 0; r < R; ++r) {
+        const long n = n_out_host[r];
+        SED_REQUIRE(n >= 1 && n <= 0x7fffffffL - rows, "detect_events_batch: recording %d has %ld output frames", r, n);
+        out_off[r] = (int)rows;
+        word_off[r] = (int)words;
+        rows += n;
+        words += detect_words(n);
+        SED_REQUIRE(rows * K <= 0x7fffffffL, "detect_events_batch: more than 2^31 - 1 (frame, class) cells in one batch");
+    }
+    out_off[R] = (int)rows;
+    word_off[R] = (int)words;
+    const size_t need = sed_detect_batch_workspace_bytes(rows, K, R, max_events);
+    SED_REQUIRE(need > 0, "detect_events_batch: bad sizes (R=%d, K=%d, %ld output frames)", R, K, rows);
+    SED_REQUIRE(workspace_bytes >= need, "detect_events_batch: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    hipStream_t s = as_stream(stream);
+    const DetBatchWs w = det_batch_layout(workspace, R, K, rows / 64 + R);
+    if (int rc = det_upload(w.out_off, h.data(), h.size() * 4, s, "detect_events_batch")) return rc;
+    switch (median) {
+#define DETECT_MED(m) case m: launch_bits_batch<m>(probs, w.out_off, w.word_off, R, K, words, lo, hi, w.ob, w.hb, s); break;
+        DETECT_MED(1) DETECT_MED(3) DETECT_MED(5) DETECT_MED(7) DETECT_MED(9) DETECT_MED(11) DETECT_MED(13) DETECT_MED(15)
+        DETECT_MED(17) DETECT_MED(19) DETECT_MED(21) DETECT_MED(23) DETECT_MED(25) DETECT_MED(27) DETECT_MED(29) DETECT_MED(31)
+#undef DETECT_MED
+    }
+    SED_LAUNCH_CHECK("detect_bits_batch");
+    const unsigned groups = (unsigned)((long)R * K);
+    detect_walk_k<true><<<groups, 64, 0, s>>>(w.ob, w.hb, 0, min_gap, min_len, 0, max_events, w.counts, w.offs, cls, onset, offset,
+                                             w.word_off, K, rec);
+    SED_LAUNCH_CHECK("detect_walk_batch(count)");
+    detect_scan_k<<<1, 1024, 0, s>>>(w.counts, R * K, K, w.offs, event_off);
+    SED_LAUNCH_CHECK("detect_scan");
+    if (max_events == 0) return 0;
+    detect_walk_k<true><<<groups, 64, 0, s>>>(w.ob, w.hb, 0, min_gap, min_len, 1, max_events, w.counts, w.offs, cls, onset, offset,
+                                             w.word_off, K, rec);
+    SED_LAUNCH_CHECK("detect_walk_batch(write)");
+    detect_peaks_k<true><<<max_events < 1024 ? max_events : 1024, 256, 0, s>>>(probs, K, event_off + R, max_events, cls, onset, offset,
+                                                                              peak, peak_frame, rec, w.out_off);
+    SED_LAUNCH_CHECK("detect_peaks_batch");
     return 0;
 }

@@ -171,13 +171,44 @@ __device__ __forceinline__ float pcm_at(const float* __restrict__ pcm, long n, l
     return 0.f;
 }
 
+// Batched (SEG): R clips packed back to back in one PCM buffer; the launch walks the frame pairs of all of them, clip by clip.
+// Device tables (uploaded by sed_logmel_batch): pair_off [R+1] (first pair of each clip; the last entry is the total),
+// sample_off / n_samples / row_off [R] (the clip's first sample, its length and its first output row); n_pairs = pair_off[R].
+struct LmBatch { const long* pair_off; const long* sample_off; const long* n_samples; const long* row_off; int R; long n_pairs; };
+// where one frame pair lives: its clip's PCM, length and frame count, the pair's index in the clip and the clip's first row
+struct LmSeg { const float* pcm; long n_samples, n_frames, pair, row0; };
+
+__device__ __forceinline__ long uniform_long(long v) {       // v is wave-uniform: say so, so that what it addresses stays scalar
+    const unsigned long long u = (unsigned long long)v;
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
+    return (long)(((unsigned long long)hi << 32) | lo);
+}
+
+// Both frames of a pair belong to one clip, so the lookup (a binary search over pair_off) is wave-uniform.
+template <bool SEG>
+__device__ __forceinline__ LmSeg lm_locate(long pair, const float* pcm, long n_samples, long n_frames, const LmBatch& bt, int hop) {
+    if (!SEG) return LmSeg{pcm, n_samples, n_frames, pair, 0};
+    pair = uniform_long(pair);
+    int lo = 0, hi = bt.R - 1;                               // the last clip whose first pair is <= pair
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (bt.pair_off[mid] <= pair) lo = mid;
+        else hi = mid - 1;
+    }
+    const int c = __builtin_amdgcn_readfirstlane(lo);
+    const long ns = bt.n_samples[c];
+    return LmSeg{pcm + bt.sample_off[c], ns, 1 + ns / hop, pair - bt.pair_off[c], bt.row_off[c]};
+}
+
 // DB: the next pair's PCM goes to a second register set one iteration ahead (needs the 256 registers of <= 8 waves per CU);
-// otherwise it is loaded into the FFT registers before the mel pass of the current pair (they are dead by then)
-template <int WPB, bool DB = (WPB <= 8)>
+// otherwise it is loaded into the FFT registers before the mel pass of the current pair (they are dead by then).
+// SEG: the batched launch (LmBatch above; n_samples / n_frames are then unused).  The FFT, mel and scaler code is the same.
+template <int WPB, bool SEG = false, bool DB = (WPB <= 8)>
 __global__ __launch_bounds__(WPB * 64) void logmel_fft_k(const float* __restrict__ pcm, long n_samples,
                                                          const uint32_t* __restrict__ tables, int table_words,
                                                          const float* __restrict__ mu, const float* __restrict__ inv_sigma,
-                                                         float* __restrict__ out, long n_frames, int hop, int pad_mode, int n_mels_out) {
+                                                         float* __restrict__ out, long n_frames, int hop, int pad_mode, int n_mels_out,
+                                                         LmBatch bt = LmBatch{}) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x;
     {   // tables: global -> LDS, once per workgroup (table_words is a multiple of 4)
@@ -209,14 +240,14 @@ __global__ __launch_bounds__(WPB * 64) void logmel_fft_k(const float* __restrict
     const unsigned xbase = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(wscr - lds) * 4u +
                                                           (unsigned)__builtin_amdgcn_groupstaticsize());
     const int partner = (lane & 32) | ((32 - r) & 31);
-    const bool even_hop = (hop & 1) == 0 && (reinterpret_cast<uintptr_t>(pcm) & 7) == 0;
-    const long n_pairs = (n_frames + 1) >> 1;
+    const long n_pairs = SEG ? bt.n_pairs : (n_frames + 1) >> 1;
 
     // interior frame pairs with an even hop are read by plain 8-byte loads; the loads of the NEXT pair are issued before
     // the mel pass of the current one (the FFT registers are dead by then), so HBM latency hides behind it
-    auto fast_ok = [&](long pair) -> bool {
-        const long first = pair * 2 * hop - LM_NFFT / 2, last = first + hop + LM_NFFT;      // span of both frames (wave-uniform)
-        return even_hop && first >= 0 && last <= n_samples && pair * 2 + 1 < n_frames;
+    auto fast_ok = [&](const LmSeg& g) -> bool {
+        const bool even_hop = (hop & 1) == 0 && (reinterpret_cast<uintptr_t>(g.pcm) & 7) == 0;
+        const long first = g.pair * 2 * hop - LM_NFFT / 2, last = first + hop + LM_NFFT;    // span of both frames (wave-uniform)
+        return even_hop && first >= 0 && last <= g.n_samples && g.pair * 2 + 1 < g.n_frames;
     };
     f2 z[32];                                                // z[n] = (x[2n], x[2n+1]): one complex point per VGPR pair
     // Where the time goes (round 4, ablation builds on one box, one hour of audio, 12 waves per CU; the full kernel 0.33-0.35 ms):
@@ -232,44 +263,49 @@ __global__ __launch_bounds__(WPB * 64) void logmel_fft_k(const float* __restrict
     f2 zn[DB ? 32 : 1];
     const long stride = (long)gridDim.x * WPB;
     const long pair0 = (long)blockIdx.x * WPB + wave;
-    bool nloaded = DB && pair0 < n_pairs && fast_ok(pair0);
+    LmSeg cur = lm_locate<SEG>(pair0 < n_pairs ? pair0 : 0, pcm, n_samples, n_frames, bt, hop);
+    bool nloaded = DB && pair0 < n_pairs && fast_ok(cur);
     if (DB && nloaded) {
-        const f2* src = reinterpret_cast<const f2*>(pcm + (pair0 * 2 + half) * hop - LM_NFFT / 2) + r;
+        const f2* src = reinterpret_cast<const f2*>(cur.pcm + (cur.pair * 2 + half) * hop - LM_NFFT / 2) + r;
 #pragma unroll
         for (int n1 = 0; n1 < 32; ++n1) zn[DB ? n1 : 0] = src[32 * n1];
     }
     for (long pair = pair0; pair < n_pairs; pair += stride) {
-        long frame = pair * 2 + half;
-        const bool live = frame < n_frames;
-        if (!live) frame = n_frames - 1;                     // odd tail: the upper half recomputes the last frame, stores nothing
+        // the next pair (its clip when batched): what the prefetch below loads, and this loop's state one iteration from now
+        const LmSeg nxt = lm_locate<SEG>(pair + stride < n_pairs ? pair + stride : pair, pcm, n_samples, n_frames, bt, hop);
+        long frame = cur.pair * 2 + half;
+        const bool live = frame < cur.n_frames;
+        if (!live) frame = cur.n_frames - 1;                 // odd tail: the upper half recomputes the last frame, stores nothing
         const long start = frame * hop - LM_NFFT / 2;
+        const float* cpcm = cur.pcm;
+        const long cns = cur.n_samples;
         // ── z[32 n1 + r] = (x[64 n1 + 2r], x[64 n1 + 2r + 1]) * window ──
         const bool loaded = nloaded;
         if (DB && loaded) {
 #pragma unroll
             for (int n1 = 0; n1 < 32; ++n1) z[n1] = zn[DB ? n1 : 0];
         }
-        if (DB) nloaded = pair + stride < n_pairs && fast_ok(pair + stride);
+        if (DB) nloaded = pair + stride < n_pairs && fast_ok(nxt);
         if (DB && nloaded) {                                 // the next pair's PCM: first use is the copy above, one iteration from now
-            const f2* src = reinterpret_cast<const f2*>(pcm + ((pair + stride) * 2 + half) * hop - LM_NFFT / 2) + r;
+            const f2* src = reinterpret_cast<const f2*>(nxt.pcm + (nxt.pair * 2 + half) * hop - LM_NFFT / 2) + r;
 #pragma unroll
             for (int n1 = 0; n1 < 32; ++n1) zn[DB ? n1 : 0] = src[32 * n1];
         }
         if (!loaded) {
-            if (!DB && fast_ok(pair)) {
-                const f2* src = reinterpret_cast<const f2*>(pcm + start) + r;
+            if (!DB && fast_ok(cur)) {
+                const f2* src = reinterpret_cast<const f2*>(cpcm + start) + r;
 #pragma unroll
                 for (int n1 = 0; n1 < 32; ++n1) z[n1] = src[32 * n1];
             } else {                                         // edge frames / odd hop: guarded loads, staged through LDS so that
                 wave_lds_fence();                            //  this cold path costs no registers (dynamic index, not unrolled)
 #pragma unroll 1
-                for (int n1 = 0; n1 < 32; ++n1) scr[n1 * 32 + r] = pcm_at(pcm, start + 64 * n1 + 2 * r, n_samples, pad_mode);
+                for (int n1 = 0; n1 < 32; ++n1) scr[n1 * 32 + r] = pcm_at(cpcm, start + 64 * n1 + 2 * r, cns, pad_mode);
                 wave_lds_fence();
 #pragma unroll
                 for (int n1 = 0; n1 < 32; ++n1) z[n1].x = scr[n1 * 32 + r];
                 wave_lds_fence();
 #pragma unroll 1
-                for (int n1 = 0; n1 < 32; ++n1) scr[n1 * 32 + r] = pcm_at(pcm, start + 64 * n1 + 2 * r + 1, n_samples, pad_mode);
+                for (int n1 = 0; n1 < 32; ++n1) scr[n1 * 32 + r] = pcm_at(cpcm, start + 64 * n1 + 2 * r + 1, cns, pad_mode);
                 wave_lds_fence();
 #pragma unroll
                 for (int n1 = 0; n1 < 32; ++n1) z[n1].y = scr[n1 * 32 + r];
@@ -338,9 +374,9 @@ __global__ __launch_bounds__(WPB * 64) void logmel_fft_k(const float* __restrict
         if (r == 0) { const f2 zz = z[brev5(16)]; scr[512] = 4.f * (zz.x * zz.x + zz.y * zz.y); }
         wave_lds_fence();
         if (!DB) {
-            nloaded = pair + stride < n_pairs && fast_ok(pair + stride);
+            nloaded = pair + stride < n_pairs && fast_ok(nxt);
             if (nloaded) {                                   // single set: the FFT registers are dead here; first use is the next window multiply
-                const f2* src = reinterpret_cast<const f2*>(pcm + ((pair + stride) * 2 + half) * hop - LM_NFFT / 2) + r;
+                const f2* src = reinterpret_cast<const f2*>(nxt.pcm + (nxt.pair * 2 + half) * hop - LM_NFFT / 2) + r;
 #pragma unroll
                 for (int n1 = 0; n1 < 32; ++n1) z[n1] = src[32 * n1];
             }
@@ -390,7 +426,7 @@ __global__ __launch_bounds__(WPB * 64) void logmel_fft_k(const float* __restrict
                 v += part[l.w >> 16];
                 v = logf(v);
                 if (mu) v = (v - s_mu[m]) * s_is[m];
-                if (live) out[frame * n_mels_out + m] = v;
+                if (live) out[(cur.row0 + frame) * n_mels_out + m] = v;
             }
         } else {
             // ── list plan: lane r walks entries [r*iters, (r+1)*iters) of the band-major list ──
@@ -417,9 +453,10 @@ __global__ __launch_bounds__(WPB * 64) void logmel_fft_k(const float* __restrict
                 for (int j = 0; j < cnt; ++j) v += part[f0 + j];
                 v = logf(v);
                 if (mu) v = (v - s_mu[m]) * s_is[m];
-                if (live) out[frame * n_mels_out + m] = v;
+                if (live) out[(cur.row0 + frame) * n_mels_out + m] = v;
             }
         }
+        cur = nxt;
     }
 }
 
@@ -573,43 +610,96 @@ extern "C" int sed_logmel_build_tables(const float* window_host, const float* me
 // 12 waves per CU: the most that fit beside the tables (12 x 9.7 KB of exchange / power scratch + 38 KB of tables in 160 KB)
 #define LM_WPB 12
 #define LM_SCALER_BYTES ((size_t)2 * LM_MAX_MELS * sizeof(float))      // mean and 1/sigma of the fused scaler, behind the wave scratch
-template <int WPB>
+template <int WPB, bool SEG>
 static int launch_logmel(const float* pcm, long n_samples, const void* tables, int words, const float* mu, const float* inv_sigma,
-                         float* out, long frames, int hop, int n_mels, int pad_mode, hipStream_t s) {
+                         float* out, long frames, int hop, int n_mels, int pad_mode, const LmBatch& bt, hipStream_t s) {
     const size_t lds = (size_t)words * 4 + (size_t)WPB * 2 * LM_FRAME_SCR * sizeof(float) + LM_SCALER_BYTES;
     SED_REQUIRE(lds <= 160 * 1024, "logmel: tables + scratch (%zu B) exceed the 160 KiB LDS", lds);
-    hipError_t e = hipFuncSetAttribute((const void*)logmel_fft_k<WPB>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipError_t e = hipFuncSetAttribute((const void*)logmel_fft_k<WPB, SEG>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) { sed_set_error("logmel: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-    const long pairs = (frames + 1) / 2;
+    const long pairs = SEG ? bt.n_pairs : (frames + 1) / 2;
     long blocks = (pairs + WPB - 1) / WPB;
     const long resident = 256;                               // one persistent workgroup per CU: the tables are loaded once each
     if (blocks > resident) blocks = resident;
     SedProfScope prof(SED_K_LOGMEL, s, (double)frames * ((double)hop + n_mels) * 4.0);
-    logmel_fft_k<WPB><<<(unsigned)blocks, WPB * 64, lds, s>>>(pcm, n_samples, (const uint32_t*)tables, words, mu, inv_sigma,
-                                                              out, frames, hop, pad_mode, n_mels);
+    logmel_fft_k<WPB, SEG><<<(unsigned)blocks, WPB * 64, lds, s>>>(pcm, n_samples, (const uint32_t*)tables, words, mu, inv_sigma,
+                                                                   out, frames, hop, pad_mode, n_mels, bt);
     SED_LAUNCH_CHECK("logmel");
     return 0;
 }
 
-extern "C" int sed_logmel(const float* pcm, long n_samples, const void* tables, size_t tables_bytes, const float* mu,
-                          const float* inv_sigma, float* out, int n_fft, int hop, int n_mels, int pad_mode, void* stream) {
-    SED_REQUIRE(pcm && tables && out, "logmel: null pointer");
+// 12 waves per workgroup when the tables leave room for their scratch (the two-band plan of a Slaney bank: 38 KB); a large
+// list plan (up to 8 192 non-zeros = 67 KB of entries) runs with fewer waves per CU rather than being refused
+template <bool SEG>
+static int launch_logmel_any(const float* pcm, long n_samples, const void* tables, int words, const float* mu, const float* inv_sigma,
+                             float* out, long frames, int hop, int n_mels, int pad_mode, const LmBatch& bt, hipStream_t s) {
+    const size_t per_wave = (size_t)2 * LM_FRAME_SCR * sizeof(float), room = (size_t)160 * 1024 - LM_SCALER_BYTES;
+    const size_t tb = (size_t)words * 4;
+    if (tb + 12 * per_wave <= room) return launch_logmel<12, SEG>(pcm, n_samples, tables, words, mu, inv_sigma, out, frames, hop, n_mels, pad_mode, bt, s);
+    if (tb + 8 * per_wave <= room) return launch_logmel<8, SEG>(pcm, n_samples, tables, words, mu, inv_sigma, out, frames, hop, n_mels, pad_mode, bt, s);
+    if (tb + 4 * per_wave <= room) return launch_logmel<4, SEG>(pcm, n_samples, tables, words, mu, inv_sigma, out, frames, hop, n_mels, pad_mode, bt, s);
+    return launch_logmel<2, SEG>(pcm, n_samples, tables, words, mu, inv_sigma, out, frames, hop, n_mels, pad_mode, bt, s);
+}
+
+// the argument checks both entries share
+static int logmel_check_args(const void* tables, size_t tables_bytes, const float* mu, const float* inv_sigma, int n_fft, int hop,
+                             int n_mels, int pad_mode) {
     SED_REQUIRE(n_fft == LM_NFFT, "logmel: n_fft must be %d (got %d)", LM_NFFT, n_fft);
-    SED_REQUIRE(n_samples > 0 && hop > 0 && n_mels > 0 && n_mels <= LM_MAX_MELS, "logmel: bad sizes");
+    SED_REQUIRE(hop > 0 && n_mels > 0 && n_mels <= LM_MAX_MELS, "logmel: bad sizes");
     SED_REQUIRE((mu == nullptr) == (inv_sigma == nullptr), "logmel: mu and inv_sigma go together");
     SED_REQUIRE(pad_mode == 0 || pad_mode == 1, "logmel: pad_mode must be 0 (constant) or 1 (reflect)");
     const int words = (int)(tables_bytes / 4);
     SED_REQUIRE(tables_bytes % 16 == 0 && words >= LM_OFF_ENT + 64 + n_mels, "logmel: table blob of %zu bytes is malformed", tables_bytes);
     SED_REQUIRE((size_t)words * 4 + (size_t)2 * 2 * LM_FRAME_SCR * sizeof(float) + LM_SCALER_BYTES <= (size_t)160 * 1024,
                 "logmel: a table blob of %zu bytes leaves no room for the FFT scratch in the 160 KiB LDS", tables_bytes);
+    return 0;
+}
+
+extern "C" int sed_logmel(const float* pcm, long n_samples, const void* tables, size_t tables_bytes, const float* mu,
+                          const float* inv_sigma, float* out, int n_fft, int hop, int n_mels, int pad_mode, void* stream) {
+    SED_REQUIRE(pcm && tables && out, "logmel: null pointer");
+    SED_REQUIRE(n_samples > 0, "logmel: bad sizes");
+    if (int rc = logmel_check_args(tables, tables_bytes, mu, inv_sigma, n_fft, hop, n_mels, pad_mode)) return rc;
     const long frames = 1 + n_samples / hop;
+    return launch_logmel_any<false>(pcm, n_samples, tables, (int)(tables_bytes / 4), mu, inv_sigma, out, frames, hop, n_mels, pad_mode,
+                                    LmBatch{}, as_stream(stream));
+}
+
+// ───────────────────────── batch: R clips packed in one PCM buffer, one launch ─────────────────────────
+// workspace: pair_off [R+1], sample_off [R], n_samples [R], row_off [R] (64-bit), uploaded from the validated host table
+extern "C" size_t sed_logmel_batch_workspace_bytes(int R) {
+    if (R < 1 || R > (1 << 26)) return 0;
+    return ((size_t)4 * R + 1) * sizeof(long);
+}
+
+extern "C" int sed_logmel_batch(const float* pcm, long pcm_len, const long* clips_host, int R, const void* tables, size_t tables_bytes,
+                                const float* mu, const float* inv_sigma, float* out, long out_rows, int n_fft, int hop, int n_mels,
+                                int pad_mode, void* workspace, size_t workspace_bytes, void* stream) {
+    SED_REQUIRE(pcm && clips_host && tables && out && workspace, "logmel_batch: null pointer");
+    const size_t need = sed_logmel_batch_workspace_bytes(R);
+    SED_REQUIRE(need > 0 && pcm_len > 0, "logmel_batch: bad sizes (R=%d, pcm_len=%ld)", R, pcm_len);
+    SED_REQUIRE(workspace_bytes >= need, "logmel_batch: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    if (int rc = logmel_check_args(tables, tables_bytes, mu, inv_sigma, n_fft, hop, n_mels, pad_mode)) return rc;
+    std::vector<long> h((size_t)4 * R + 1);
+    long* pair_off = h.data();
+    long *soff = pair_off + R + 1, *slen = soff + R, *roff = slen + R;
+    long pairs = 0, rows = 0;
+    for (int c = 0; c < R; ++c) {
+        const long o = clips_host[2 * c], n = clips_host[2 * c + 1];
+        SED_REQUIRE(o >= 0 && n >= 1 && o <= pcm_len && n <= pcm_len - o,
+                    "logmel_batch: clip %d (offset %ld, %ld samples) is not inside the PCM buffer of %ld samples", c, o, n, pcm_len);
+        const long f = 1 + n / hop;
+        pair_off[c] = pairs; soff[c] = o; slen[c] = n; roff[c] = rows;
+        pairs += (f + 1) / 2;
+        rows += f;
+        SED_REQUIRE(rows <= 0x7fffffffL, "logmel_batch: more than 2^31 - 1 feature frames in one batch");
+    }
+    pair_off[R] = pairs;
+    SED_REQUIRE(out_rows == rows, "logmel_batch: out has %ld rows, the clips make %ld", out_rows, rows);
     hipStream_t s = as_stream(stream);
-    // 12 waves per workgroup when the tables leave room for their scratch (the two-band plan of a Slaney bank: 38 KB); a large
-    // list plan (up to 8 192 non-zeros = 67 KB of entries) runs with fewer waves per CU rather than being refused
-    const size_t per_wave = (size_t)2 * LM_FRAME_SCR * sizeof(float), room = (size_t)160 * 1024 - LM_SCALER_BYTES;
-    const size_t tb = (size_t)words * 4;
-    if (tb + 12 * per_wave <= room) return launch_logmel<12>(pcm, n_samples, tables, words, mu, inv_sigma, out, frames, hop, n_mels, pad_mode, s);
-    if (tb + 8 * per_wave <= room) return launch_logmel<8>(pcm, n_samples, tables, words, mu, inv_sigma, out, frames, hop, n_mels, pad_mode, s);
-    if (tb + 4 * per_wave <= room) return launch_logmel<4>(pcm, n_samples, tables, words, mu, inv_sigma, out, frames, hop, n_mels, pad_mode, s);
-    return launch_logmel<2>(pcm, n_samples, tables, words, mu, inv_sigma, out, frames, hop, n_mels, pad_mode, s);
+    long* dev = (long*)workspace;
+    hipError_t e = hipMemcpyAsync(dev, h.data(), h.size() * sizeof(long), hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) { sed_set_error("logmel_batch: upload of the clip table: %s", hipGetErrorString(e)); return (int)e; }
+    const LmBatch bt{dev, dev + R + 1, dev + 2 * R + 1, dev + 3 * R + 1, R, pairs};
+    return launch_logmel_any<true>(pcm, pcm_len, tables, (int)(tables_bytes / 4), mu, inv_sigma, out, rows, hop, n_mels, pad_mode, bt, s);
 }

@@ -80,6 +80,60 @@ def plan_windows(n_frames, tf, seq_len=SEQ_LEN_IN, hop=None, trim=0):
     return plan
 
 
+@dataclass(frozen=True)
+class BatchPlan:
+    """The windows of R recordings whose features are packed back to back (``plan_batch``).  Logits go to one flat buffer:
+    first every window of ``seq_len`` frames in (recording, window) order, then the recordings shorter than ``seq_len``
+    grouped by their window length (``groups``, in increasing length; a recording's windows are contiguous either way)."""
+    plans: tuple           # WindowPlan of every recording
+    row_off: tuple         # [R+1] first feature row of every recording in the packed features
+    out_off: tuple         # [R+1] first output frame of every recording in the packed track
+    full_starts: tuple     # absolute starts (packed rows) of every window of seq_len frames, (recording, window) order
+    groups: tuple          # ((win_len, (absolute start, ...)), ...): one window per short recording, by window length
+    logit_off: tuple       # [R] first logit (float index) of every recording in the flat buffer
+    n_logits: int          # floats in the flat buffer
+
+    def stitch_table(self):
+        """[R][6] int64 {first logit, n_win, win_out, hop_out, last_start_out, n_out}: sed_detect_stitch_batch's table"""
+        import numpy as np
+        return np.array([[o, p.n_win, p.win_out, p.hop_out, p.last_start_out, p.n_out] for o, p in zip(self.logit_off, self.plans)],
+                        dtype=np.int64).reshape(-1, 6)
+
+
+def plan_batch(n_frames, tf, K, seq_len=SEQ_LEN_IN, hop=None, trim=0):
+    """``plan_windows`` for every recording of a packed batch (``n_frames`` = feature frames per recording, ``K`` classes) ->
+    BatchPlan.  ValueError names the first recording that cannot be planned (N < tf), before anything runs."""
+    plans, row_off = [], [0]
+    for i, N in enumerate(n_frames):
+        try:
+            plans.append(plan_windows(N, tf, seq_len, hop, trim))
+        except ValueError as e:
+            raise ValueError(f"recording {i}: {e}") from None
+        row_off.append(row_off[-1] + int(N))
+    if row_off[-1] >= 2 ** 31:
+        raise ValueError(f"{row_off[-1]} feature frames in one batch: sed_window_batch takes int32 starts (at most 2^31 - 1)")
+    out_off = [0]
+    for p in plans:
+        out_off.append(out_off[-1] + p.n_out)
+    L = int(seq_len)
+    full, logit_off, short = [], [None] * len(plans), {}
+    for r, p in enumerate(plans):
+        if p.win_len == L and p.n_frames >= L:
+            logit_off[r] = len(full) * (L // tf) * K
+            full.extend(row_off[r] + s for s in p.starts)
+        else:
+            short.setdefault(p.win_len, []).append(r)
+    at = len(full) * (L // tf) * K
+    groups = []
+    for Lw in sorted(short):
+        rs = short[Lw]
+        for i, r in enumerate(rs):
+            logit_off[r] = at + i * (Lw // tf) * K
+        groups.append((Lw, tuple(row_off[r] for r in rs)))
+        at += len(rs) * (Lw // tf) * K
+    return BatchPlan(tuple(plans), tuple(row_off), tuple(out_off), tuple(full), tuple(groups), tuple(logit_off), at)
+
+
 class DetectionResult:
     """``probs`` [n_out, K] device track; ``events`` dict of device tensors (``cls``, ``onset``, ``offset``, ``peak_frame``
     int32 output frames, offset exclusive; ``peak`` float32), sorted by (class, onset); ``frame_seconds`` = tf*hop_length/sr."""
@@ -96,6 +150,37 @@ class DetectionResult:
         sel = ev["cls"] == int(k)
         fs = self.frame_seconds
         return [(int(a) * fs, int(b) * fs, float(p)) for a, b, p in zip(ev["onset"][sel], ev["offset"][sel], ev["peak"][sel])]
+
+
+class BatchDetectionResult:
+    """R recordings detected together.  ``len()`` = R; ``res[i]`` = a DetectionResult view of recording i (its slice of the
+    track and of the events, without ``rec``; frames local to the recording).  Packed: ``probs`` [sum n_out, K] device track,
+    ``events`` dict of device tensors with ``rec`` (sorted by recording, class, onset), and the host lists ``out_offsets``
+    [R+1] (recording i = rows [out_offsets[i], out_offsets[i+1])) and ``event_offsets`` [R+1]."""
+
+    def __init__(self, probs, events, frame_seconds, plans, out_offsets, event_offsets):
+        self.probs, self.events, self.frame_seconds, self.plans = probs, events, frame_seconds, tuple(plans)
+        self.out_offsets, self.event_offsets = list(out_offsets), list(event_offsets)
+
+    def __len__(self):
+        return len(self.plans)
+
+    def __getitem__(self, i):
+        R = len(self.plans)
+        if not -R <= int(i) < R:
+            raise IndexError(f"recording {i} of {R}")
+        i = int(i) % R
+        o0, o1 = self.out_offsets[i], self.out_offsets[i + 1]
+        e0, e1 = self.event_offsets[i], self.event_offsets[i + 1]
+        return DetectionResult(self.probs[o0:o1], {k: self.events[k][e0:e1] for k in _EVENT_KEYS}, self.frame_seconds,
+                               self.plans[i])
+
+    def __iter__(self):
+        return (self[i] for i in range(len(self)))
+
+    @property
+    def n_events(self):
+        return self.event_offsets[-1]
 
 
 class EventDetector:
@@ -135,6 +220,7 @@ class EventDetector:
         self.max_events = 256                   # grows to the largest count seen
         self._zlab = None                       # zero label column for sed_window_batch (it requires one)
         self._dws = None
+        self._bws = None                        # the batch entries' workspace
 
     @property
     def frame_seconds(self):
@@ -186,26 +272,34 @@ class EventDetector:
         return mel, plan_windows(mel.shape[0], m.time_factor, self.seq_len, self.hop, self.trim)
 
     def window_logits(self, mel, plan, marks=None):
-        """Every window of the plan through the eval forward -> logits [n_win, win_out, K].  Chunks of at most max_batch
-        windows: each is gathered by one sed_window_batch launch into a buffer of max_batch windows (memory is bounded by
-        max_batch, not by the recording's length) and run on ONE workspace, the largest chunk's (the eval forward of a batch
-        equals that of its chunks bit for bit).  ``marks`` (optional list): receives ("gather" | "forward", start, end)
-        hip event pairs around every launch, for per-phase timing."""
-        m, N = self.model, plan.n_frames
+        """Every window of the plan through the eval forward -> logits [n_win, win_out, K] (``_forward_windows``).
+        ``marks`` (optional list): receives ("gather" | "forward", start, end) hip event pairs around every launch, for
+        per-phase timing."""
+        m = self.model
         self._check_model()
+        logits = torch.empty(plan.n_win, plan.win_out, m.dense[-1], device=mel.device)
+        starts = torch.tensor(plan.starts, dtype=torch.int32).to(mel.device, non_blocking=True)
+        self._forward_windows(mel, [(starts, plan.win_len, logits)], marks)
+        return logits
+
+    def _forward_windows(self, mel, jobs, marks=None):
+        """The chunked eval forward of both paths.  ``jobs`` = [(starts, win_len, out), ...]: int32 device window starts
+        (rows of ``mel``), their length, and the logits [n, win_len // tf, K] they go to.  Chunks of at most max_batch windows:
+        each is gathered by one sed_window_batch launch into ONE reused buffer (memory is bounded by max_batch, not by the
+        input's length) and run on ONE workspace, that of the largest need among the jobs' shapes, checked with
+        sed_net_workspace_bytes for every other shape (the eval forward of a batch equals that of its chunks bit for bit)."""
+        m, N = self.model, mel.shape[0]
         dev = mel.device
         if self._zlab is None or self._zlab.numel() < N or self._zlab.device != dev:
             self._zlab = torch.zeros(max(N, 1 << 16), device=dev)
-        Lw, nw = plan.win_len, plan.n_win
-        bmax = min(self.max_batch, nw)
-        starts = torch.tensor(plan.starts, dtype=torch.int32).to(dev, non_blocking=True)
-        x = torch.empty(bmax, m.in_channels, m.n_mels, Lw, device=dev)
-        y = torch.empty(bmax, device=dev)                      # the pooled zero labels: pool = Lw -> one per window
-        m._check_input(x[:1])
-        logits = torch.empty(nw, plan.win_out, m.dense[-1], device=dev)
+        CF = m.in_channels * m.n_mels
+        shapes = [(min(self.max_batch, starts.numel()), Lw) for starts, Lw, _ in jobs]
+        xbuf = torch.empty(max(b * Lw for b, Lw in shapes) * CF, device=dev)
+        y = torch.empty(max(b for b, _ in shapes), device=dev)        # the pooled zero labels: pool = Lw -> one per window
         P, _ = m._param_structs()
-        cfg = m._cfg(bmax, Lw, training=False)
-        ws = m._workspace(cfg, False)
+        cfgs = [m._cfg(b, Lw, training=False) for b, Lw in shapes]
+        need = [lib().sed_net_workspace_bytes(C.byref(c), 0) for c in cfgs] if len(cfgs) > 1 else [0]
+        ws = m._workspace(cfgs[max(range(len(cfgs)), key=need.__getitem__)], False)
         cap = ws.numel() * 4
 
         def mark(name, fn):
@@ -217,18 +311,22 @@ class EventDetector:
             b.record()
             marks.append((name, a, b))
 
-        for b0 in range(0, nw, bmax):
-            b = min(bmax, nw - b0)
-            if b != cfg.B:
-                cfg = m._cfg(b, Lw, training=False)
-                if lib().sed_net_workspace_bytes(C.byref(cfg), 0) > cap:
-                    check(-1, "sed_net_workspace_bytes (a smaller chunk needs a larger workspace)")
-            mark("gather", lambda: check(lib().sed_window_batch(
-                ptr(mel), ptr(self._zlab), N, m.in_channels, m.n_mels, 1, ptr(starts[b0:b0 + b]), None, None, 0, 0, 0,
-                ptr(x), ptr(y), b, Lw, Lw, stream_ptr()), "sed_window_batch"))
-            mark("forward", lambda: check(lib().sed_net_forward(
-                C.byref(cfg), C.byref(P), ptr(x), ptr(logits[b0:b0 + b]), ptr(ws), 0, 0, None, stream_ptr()), "sed_net_forward"))
-        return logits
+        for (starts, Lw, logits), (bmax, _), cfg in zip(jobs, shapes, cfgs):
+            nw = starts.numel()
+            x = xbuf[:bmax * CF * Lw].view(bmax, m.in_channels, m.n_mels, Lw)
+            m._check_input(x[:1])
+            for b0 in range(0, nw, bmax):
+                b = min(bmax, nw - b0)
+                if b != cfg.B:
+                    cfg = m._cfg(b, Lw, training=False)
+                    if lib().sed_net_workspace_bytes(C.byref(cfg), 0) > cap:
+                        check(-1, "sed_net_workspace_bytes (a smaller chunk needs a larger workspace)")
+                mark("gather", lambda: check(lib().sed_window_batch(
+                    ptr(mel), ptr(self._zlab), N, m.in_channels, m.n_mels, 1, ptr(starts[b0:b0 + b]), None, None, 0, 0, 0,
+                    ptr(x), ptr(y), b, Lw, Lw, stream_ptr()), "sed_window_batch"))
+                mark("forward", lambda: check(lib().sed_net_forward(
+                    C.byref(cfg), C.byref(P), ptr(x), ptr(logits[b0:b0 + b]), ptr(ws), 0, 0, None, stream_ptr()),
+                    "sed_net_forward"))
 
     def stitch(self, logits, plan):
         """window logits -> probs [n_out, K] (sigmoid, then mean / max over the covering windows)."""
@@ -261,6 +359,141 @@ class EventDetector:
             if n <= cap:
                 return {k: v[:n] for k, v in out.items()}
             self.max_events = n
+
+    # ── batches: many recordings in one pass ──
+    def detect_many(self, waveforms):
+        """A list of mono PCM clips (1-D, host or device, any lengths) -> BatchDetectionResult.  One log-mel launch for all
+        (``feature.mbe_many``, fused scaler), then ``from_features_many``'s path.  A clip shorter than one output frame
+        raises ValueError naming its index before anything runs.
+
+        Memory, per input frame (hop_length samples): the packed PCM (4*hop_length B), the packed features (4*n_mels B),
+        the flat logits (4*K*seq_len/hop/tf B: every frame is in seq_len/hop windows) and the track (4*K/tf B); the window
+        buffer is bounded by max_batch windows, the decoder's bit tracks take 2 bits per output frame and class."""
+        m = self.model
+        if m.in_channels != 1:
+            raise ValueError(f"a mono waveform feeds a 1-channel net; this one has {m.in_channels} (use from_features_many)")
+        waves = list(waveforms)
+        n_frames = []
+        for i, w in enumerate(waves):
+            shape = tuple(w.shape) if hasattr(w, "shape") else (len(w),)
+            if len(shape) != 1:
+                raise ValueError(f"recording {i}: expected a mono 1-D waveform, got shape {shape}")
+            n_frames.append(1 + shape[0] // self.hop_length)
+        bp = plan_batch(n_frames, m.time_factor, m.dense[-1], self.seq_len, self.hop, self.trim)
+        self._check_model()
+        if not waves:
+            return self._empty_batch()
+        dev = m.flat_parameters().device
+        with torch.no_grad():
+            mel, _ = feature.mbe_many(waves, sr=self.sr, hop=self.hop_length, n_mels=m.n_mels, mean=self.mean, std=self.std,
+                                      device=dev)
+            return self._detect_packed(mel, bp)
+
+    def from_features_many(self, mels):
+        """A list of scaled features [N_r, C*F] (any channel count, host or device) -> BatchDetectionResult.  The features
+        are packed back to back; every window of every recording goes through the chunked eval forward, then ONE stitch
+        launch and ONE decode; the host reads the R+1 event offsets once at the end (see ``detect_many`` for the memory)."""
+        m = self.model
+        CF = m.in_channels * m.n_mels
+        mels = [torch.as_tensor(x) for x in mels]
+        for i, x in enumerate(mels):
+            if x.dim() != 2 or x.shape[1] != CF:
+                raise ValueError(f"recording {i}: expected features [N, {CF}] (C*F = {m.in_channels}*{m.n_mels}), "
+                                 f"got {tuple(x.shape)}")
+        bp = plan_batch([x.shape[0] for x in mels], m.time_factor, m.dense[-1], self.seq_len, self.hop, self.trim)
+        self._check_model()
+        if not mels:
+            return self._empty_batch()
+        dev = m.flat_parameters().device
+        with torch.no_grad():
+            if all(not x.is_cuda for x in mels):
+                mel = torch.cat([x.to(torch.float32) for x in mels]).to(dev)
+            else:
+                mel = torch.cat([x.to(dev, torch.float32) for x in mels])
+            return self._detect_packed(mel.contiguous(), bp)
+
+    def _empty_batch(self):
+        m = self.model
+        dev = m.flat_parameters().device
+        ev = {k: torch.empty(0, dtype=torch.float32 if k == "peak" else torch.int32, device=dev) for k in ("rec",) + _EVENT_KEYS}
+        return BatchDetectionResult(torch.empty(0, m.dense[-1], device=dev), ev, self.frame_seconds, (), [0], [0])
+
+    def _detect_packed(self, mel, bp):
+        logits = self.window_logits_many(mel, bp)
+        probs = self.stitch_many(logits, bp)
+        events, ev_off = self.decode_many(probs, bp)
+        return BatchDetectionResult(probs, events, self.frame_seconds, bp.plans, bp.out_off, ev_off)
+
+    def window_logits_many(self, mel, bp, marks=None):
+        """Packed features [sum N_r, C*F] and their BatchPlan -> the flat logits buffer [bp.n_logits]: all full windows in
+        chunks of at most max_batch (one sed_window_batch gather each, absolute starts), then every group of short
+        recordings, all on one workspace (``_forward_windows``).  ``marks`` as in ``window_logits``."""
+        self._check_model()
+        m, dev = self.model, mel.device
+        K, tf = m.dense[-1], m.time_factor
+        logits = torch.empty(bp.n_logits, device=dev)
+        jobs, at = [], 0
+        for Lw, starts in ((self.seq_len, bp.full_starts),) + bp.groups:
+            if not starts:
+                continue
+            n, wo = len(starts), Lw // tf
+            st = torch.tensor(starts, dtype=torch.int32).to(dev, non_blocking=True)
+            jobs.append((st, Lw, logits[at:at + n * wo * K].view(n, wo, K)))
+            at += n * wo * K
+        self._forward_windows(mel, jobs, marks)
+        return logits
+
+    def _batch_workspace(self, n_total, K, R):
+        need = lib().sed_detect_batch_workspace_bytes(n_total, K, R, self.max_events)
+        if need == 0:
+            check(-1, "sed_detect_batch_workspace_bytes")
+        if self._bws is None or self._bws.numel() < need or self._bws.device != self.model.flat_parameters().device:
+            self._bws = torch.empty(need, dtype=torch.uint8, device=self.model.flat_parameters().device)
+        return self._bws
+
+    def stitch_many(self, logits, bp):
+        """flat logits -> packed track [sum n_out, K] in ONE launch (sed_detect_stitch_batch); recording r's rows equal
+        ``stitch`` of its own logits bit for bit."""
+        K, R, n = self.model.dense[-1], len(bp.plans), bp.out_off[-1]
+        table = bp.stitch_table()
+        ws = self._batch_workspace(n, K, R)
+        probs = torch.empty(n, K, device=logits.device)
+        check(lib().sed_detect_stitch_batch(ptr(logits), logits.numel(), C.c_void_p(table.ctypes.data), R, K,
+                                            {"mean": 0, "max": 1}[self.combine], self.trim, ptr(probs), n, ptr(ws), ws.numel(),
+                                            stream_ptr()), "sed_detect_stitch_batch")
+        return probs
+
+    def decode_many(self, probs, bp):
+        """packed track -> (events with ``rec``, event offsets [R+1] host list).  The R+1 offsets are the one read of the
+        batch; when the total exceeds the buffers, they grow and only the decode runs again."""
+        import numpy as np
+        n_total, K = probs.shape
+        R = len(bp.plans)
+        n_out = np.ascontiguousarray(np.diff(np.asarray(bp.out_off, dtype=np.int64)))
+        ws = self._batch_workspace(n_total, K, R)
+        dev = probs.device
+        ev_off = torch.empty(R + 1, dtype=torch.int32, device=dev)
+        keys = ("rec",) + _EVENT_KEYS
+        while True:
+            cap = self.max_events
+            out = {n: torch.empty(cap, dtype=torch.float32 if n == "peak" else torch.int32, device=dev) for n in keys}
+            check(lib().sed_detect_events_batch(ptr(probs), C.c_void_p(n_out.ctypes.data), R, K, self.median, self.lo, self.hi,
+                                                self.min_gap, self.min_len, cap, ptr(ws), ws.numel(),
+                                                *(ptr(out[n]) for n in keys), ptr(ev_off), stream_ptr()), "sed_detect_events_batch")
+            offs = ev_off.cpu().tolist()
+            if offs[-1] <= cap:
+                return {k: v[:offs[-1]] for k, v in out.items()}, offs
+            self.max_events = offs[-1]
+
+
+def detect_events_many(model, xs, **kw):
+    """One shot over a list: ``EventDetector(model, **kw)`` on mono waveforms (all 1-D: ``detect_many``) or on scaled features
+    [N_r, C*F] (``from_features_many``) -> BatchDetectionResult."""
+    det = EventDetector(model, **kw)
+    xs = list(xs)
+    if xs and all(torch.as_tensor(x).dim() == 1 for x in xs):
+        return det.detect_many(xs)
+    return det.from_features_many(xs)
 
 
 def detect_events(model, x, **kw):

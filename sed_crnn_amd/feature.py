@@ -112,6 +112,81 @@ def mbe(y, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, pad_mode="constant", mean=
     return out
 
 
+def mbe_packed(pcm, clips, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, pad_mode="constant", mean=None, std=None, tables=None):
+    """R clips that lie in ONE mono float32 CUDA buffer ``pcm``, ``clips`` = [(first sample, n_samples >= 1), ...] -> (features
+    [sum_r (1 + n_r//hop), n_mels] in clip order, row offsets [R+1] as a host list), in one launch (``sed_logmel_batch``).
+    Each clip's rows are bit for bit ``mbe(clip)`` with the same options (its own centre padding at its own ends)."""
+    import ctypes as C
+    if not (isinstance(pcm, torch.Tensor) and pcm.is_cuda and pcm.dim() == 1):
+        raise RuntimeError("sed_crnn_amd.feature.mbe_packed needs a 1-D CUDA(HIP) PCM buffer; there is no CPU fallback")
+    if pad_mode not in ("constant", "reflect"):
+        raise ValueError(f"pad_mode must be 'constant' or 'reflect', got {pad_mode!r}")
+    table = np.ascontiguousarray(np.asarray(clips, dtype=np.int64).reshape(-1, 2))
+    R = table.shape[0]
+    for i, (o, n) in enumerate(table.tolist()):
+        if n < 1 or o < 0 or o + n > pcm.numel():
+            raise ValueError(f"clip {i} (first sample {o}, {n} samples) is empty or not inside the buffer of {pcm.numel()} samples")
+    if R == 0:
+        return torch.empty(0, n_mels, device=pcm.device), [0]
+    rows = np.concatenate([[0], np.cumsum(1 + table[:, 1] // hop)]).tolist()
+    if tables is None:
+        tables = _tables(pcm.device.index or 0, sr, n_fft, n_mels)
+    else:
+        n_mels = _validated_mels(tables)
+    out = torch.empty(rows[-1], n_mels, device=pcm.device)
+    if rows[-1] >= 2 ** 31:
+        raise ValueError(f"{rows[-1]} feature frames in one batch: at most 2^31 - 1")
+    pcm = pcm.contiguous().float()
+    inv = None
+    if mean is not None:
+        mean = mean.to(pcm.device).float().contiguous()
+        inv = (1.0 / std.to(pcm.device).double()).float().contiguous()
+    ws = torch.empty(lib().sed_logmel_batch_workspace_bytes(R), dtype=torch.uint8, device=pcm.device)
+    check(lib().sed_logmel_batch(ptr(pcm), pcm.numel(), C.c_void_p(table.ctypes.data), R, ptr(tables), tables.numel() * 4,
+                                 ptr(mean), ptr(inv), ptr(out), rows[-1], n_fft, hop, n_mels,
+                                 {"constant": 0, "reflect": 1}[pad_mode], ptr(ws), ws.numel(), stream_ptr()), "sed_logmel_batch")
+    return out, rows
+
+
+def pack_clips(waves, device):
+    """a list of 1-D clips (host arrays or tensors, any device) -> (one float32 buffer on ``device``, [(first sample, n), ...]);
+    every clip starts on a 16-byte boundary.  Host clips travel in one copy, device clips are joined by one torch.cat."""
+    clips, pieces, at = [], [], 0
+    on_host = all(not (isinstance(w, torch.Tensor) and w.is_cuda) for w in waves)
+    for i, w in enumerate(waves):
+        w = w if isinstance(w, torch.Tensor) else torch.as_tensor(np.asarray(w))
+        if w.dim() != 1:
+            raise ValueError(f"clip {i}: expected a mono 1-D waveform, got shape {tuple(w.shape)}")
+        n = w.numel()
+        clips.append((at, n))
+        pad = -n % 4
+        pieces.append(w.float() if on_host else w.to(device, torch.float32))
+        if pad:
+            pieces.append(torch.zeros(pad, dtype=torch.float32, device="cpu" if on_host else device))
+        at += n + pad
+    if not pieces:
+        return torch.empty(0, device=device), clips
+    buf = torch.cat(pieces)
+    return (buf.to(device) if on_host else buf), clips
+
+
+def mbe_many(waves, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, pad_mode="constant", mean=None, std=None, tables=None,
+             device=None):
+    """``mbe`` of every clip in a list of 1-D clips (host or device; ``device`` defaults to the first CUDA clip's, else
+    cuda:current) in one launch -> (features [sum_r (1 + n_r//hop), n_mels] in clip order, row offsets [R+1] host list).
+    Bit for bit ``torch.cat([mbe(w) for w in waves])``."""
+    waves = list(waves)
+    if device is None:
+        device = next((w.device for w in waves if isinstance(w, torch.Tensor) and w.is_cuda), None)
+        device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    pcm, clips = pack_clips(waves, device)
+    for i, (_, n) in enumerate(clips):
+        if n < 1:
+            raise ValueError(f"clip {i} is empty")
+    return mbe_packed(pcm, clips, sr=sr, n_fft=n_fft, hop=hop, n_mels=n_mels, pad_mode=pad_mode, mean=mean, std=std,
+                      tables=tables)
+
+
 # ───────────────────────── feature.py's on-disk formats (SURVEY 8f-2/3) ─────────────────────────
 def rasterize_hits(n_frames, hits, sr=SR, hop=HOP):
     """Frame labels of one recording from its hit intervals in seconds (feature.py:89-93): frames
