@@ -513,6 +513,44 @@ int sed_detect_events_batch(const float* probs, const long* n_out_host, int R, i
                             int min_len, int max_events, void* workspace, size_t workspace_bytes, int* rec, int* cls, int* onset,
                             int* offset, float* peak, int* peak_frame, int* event_off, void* stream);
 
+/* ───────────── live streams (sed_crnn_amd/stream.py) ─────────────
+ * S feeds keep their state on the device between calls, in ONE caller-owned buffer of sed_stream_state_bytes(...) bytes (0 = bad
+ * sizes: S in 1..65535, K in 1..32, 1 <= hop_out <= win_out, median odd 1..31, max_new_windows in 1..1024; the size depends on
+ * these arguments only): per stream a ring of window logits (window w in slot w mod WR, WR = 2 ceil(win_out / hop_out) +
+ * max_new_windows + 2), a ring of track rows (frame j in row j mod TR, TR = median - 1 + win_out + (max_new_windows + 1) hop_out + 2)
+ * and, per class, the decoder's state (open run, pending event, gap peak, decided frames).  Frames are OUTPUT frames from the
+ * start of the stream.  sed_stream_init clears every stream, sed_stream_reset the listed ones (streams_host NULL = all).
+ * sed_stream_step advances all streams: table_host [S][8] = {n_new windows, first logit (float index into logits
+ * [logits_len]), index of the first new window, n_out before, n_out now, end (0 / 1), output frames
+ * per new window (win_out; n_out for the single window of a stream that ends below win_out), first row in probs}.  The table is
+ * validated on the host against the window grid (regular window w is complete iff w hop_out + win_out <= n_out; at the end the
+ * offline grid's last window must arrive), then uploaded.  Track frame j is final iff j < n_out - win_out (all of them at the
+ * end) and is stitched by the device function of sed_detect_stitch; filtered frame g is decided once track frame g + median/2 is
+ * final (the 'nearest' clamp at the right edge applies at the end only).  A pending event [a, b) is emitted in the first step in
+ * which more than b + min_gap frames are decided and no run that began at or before b + min_gap is still open; at the end
+ * everything left is emitted and the stream restarts at frame 0.  Events: ev_stream, cls, onset, offset (exclusive), peak (max of
+ * the unfiltered track over the event, kept as a running value), peak_frame, sorted by (stream, class, onset); event_off [S+1]
+ * (device ints), event_off[S] = the true total, at most max_events are written (the state advances either way: size the outputs
+ * to sum_s K ((decided frames of s in this step) / 2 + 2)).  probs (may be NULL) receives the newly final track rows.
+ * max_new_decided >= every stream's newly decided frames; workspace >= sed_stream_step_workspace_bytes(S, K, max_new_decided).
+ * sed_stream_append: per stream, [buf[src, +n_keep) | fresh[new, +n_new)] goes to work[work, ...) (work may be NULL) and its
+ * last n_tail floats to buf[dst, ...): table_host [S][7] = {src, n_keep, new, n_new, work, dst, n_tail}; stream s owns
+ * buf[s stride, (s+1) stride), src and dst must not overlap.  The PCM carry and the feature rows of the streams move with it. */
+size_t sed_stream_state_bytes(int S, int K, int win_out, int hop_out, int median, int max_new_windows);
+int sed_stream_init(void* state, size_t state_bytes, int S, int K, int win_out, int hop_out, int median, int max_new_windows,
+                    void* stream);
+int sed_stream_reset(void* state, size_t state_bytes, int S, int K, int win_out, int hop_out, int median, int max_new_windows,
+                     const int* streams_host, int n_streams, void* stream);
+size_t sed_stream_step_workspace_bytes(int S, int K, int max_new_decided);
+int sed_stream_step(void* state, size_t state_bytes, int S, int K, int win_out, int hop_out, int median, int max_new_windows,
+                    int combine, int trim, float lo, float hi, int min_gap, int min_len, const float* logits, long logits_len,
+                    const long* table_host, int max_new_decided, float* probs, long probs_rows, int max_events, int* ev_stream,
+                    int* cls, int* onset, int* offset, float* peak, int* peak_frame, int* event_off, void* workspace,
+                    size_t workspace_bytes, void* stream);
+size_t sed_stream_append_workspace_bytes(int S);
+int sed_stream_append(float* buf, long buf_len, long stride, const float* fresh, long fresh_len, float* work, long work_len,
+                      const long* table_host, int S, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ───────────── whole-network plan (TimePooledCRNN.forward sed.py:105-112 / crnn_lightning.py:66-73) ───────────── */
 typedef struct sed_net_cfg {
     int B, Cin, F, T;                 /* input x [B][Cin][F][T] */

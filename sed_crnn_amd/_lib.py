@@ -144,6 +144,14 @@ SIGNATURES = {
     "sed_detect_batch_workspace_bytes": (_sz, [_l, _i, _i, _i]),
     "sed_detect_stitch_batch": (_i, [_fp, _l, _fp, _i, _i, _i, _i, _fp, _l, _fp, _sz, _stream]),
     "sed_detect_events_batch": (_i, [_fp, _fp, _i, _i, _i, _f, _f, _i, _i, _i, _fp, _sz, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _stream]),
+    "sed_stream_state_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "sed_stream_init": (_i, [_fp, _sz, _i, _i, _i, _i, _i, _i, _stream]),
+    "sed_stream_reset": (_i, [_fp, _sz, _i, _i, _i, _i, _i, _i, _fp, _i, _stream]),
+    "sed_stream_step_workspace_bytes": (_sz, [_i, _i, _i]),
+    "sed_stream_step": (_i, [_fp, _sz, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _i, _i, _fp, _l, _fp, _i, _fp, _l, _i, _fp, _fp, _fp,
+                             _fp, _fp, _fp, _fp, _fp, _sz, _stream]),
+    "sed_stream_append_workspace_bytes": (_sz, [_i]),
+    "sed_stream_append": (_i, [_fp, _l, _l, _fp, _l, _fp, _l, _fp, _i, _fp, _sz, _stream]),
     "sed_prof_enable": (_i, [C.c_uint]),
     "sed_prof_read": (_i, [_i, C.POINTER(_d), C.POINTER(_l), C.POINTER(_d)]),
     "sed_prof_tag_name": (C.c_char_p, [_i]),

@@ -7,44 +7,17 @@
 #include <algorithm>
 #include <vector>
 #include "common.h"
+#include "detect_shared.h"
 
 // ───────────────────────── stitch: sigmoid, then mean / max over the covering windows ─────────────────────────
-// One thread per (output frame, class): the covering windows are a contiguous range of w (start(w) is strictly increasing);
-// they are visited in increasing w, so the sum has one fixed order (bitwise deterministic, no atomics).
-__device__ __forceinline__ float stitch_one(const float* __restrict__ logits, int n_win, int win_out, int K, int hop_out,
-                                            int last_start, int n_out, int combine, int trim, int j, int k) {
-    // last window whose start is <= j
-    int whi = j >= last_start ? n_win - 1 : j / hop_out;
-    if (whi > n_win - 1) whi = n_win - 1;
-    int wlo = whi;
-    while (wlo > 0) {                                                // first window that still reaches j
-        const long s = (long)(wlo - 1) * hop_out < last_start ? (long)(wlo - 1) * hop_out : last_start;
-        if (s + win_out <= j) break;
-        --wlo;
-    }
-    float acc = combine ? -INFINITY : 0.f;
-    int cnt = 0;
-    for (int w = wlo; w <= whi; ++w) {
-        const long s = (long)w * hop_out < last_start ? (long)w * hop_out : last_start;
-        const long lo = s + (s > 0 ? trim : 0);
-        const long hi = s + win_out - (s + win_out < n_out ? trim : 0);
-        if (j < lo || j >= hi) continue;
-        const float x = logits[((size_t)w * win_out + (j - s)) * K + k];
-        const float p = 1.0f / (1.0f + expf(-x));
-        if (combine) acc = fmaxf(acc, p);
-        else acc += p;
-        ++cnt;
-    }
-    return combine ? acc : acc / (float)cnt;                          // cnt >= 1: the host checked coverage
-}
-
+// One thread per (output frame, class): stitch_one of detect_shared.h (shared with the streaming step of stream.hip).
 __global__ __launch_bounds__(256) void detect_stitch_k(const float* __restrict__ logits, int n_win, int win_out, int K,
                                                        int hop_out, int last_start, int n_out, int combine, int trim,
                                                        float* __restrict__ probs) {
     const long total = (long)n_out * K;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const int j = (int)(i / K), k = (int)(i - (long)j * K);
-        probs[i] = stitch_one(logits, n_win, win_out, K, hop_out, last_start, n_out, combine, trim, j, k);
+        probs[i] = stitch_one(LinearLogits{logits, win_out, K}, n_win, win_out, hop_out, last_start, n_out, combine, trim, j, k);
     }
 }
 
@@ -73,8 +46,8 @@ __global__ __launch_bounds__(256) void detect_stitch_batch_k(const float* __rest
         const int k = (int)(i - row * K);
         const int r = find_seg(out_off, R, row);
         const DetRec d = recs[r];
-        probs[i] = stitch_one(logits + d.logit_off, d.n_win, d.win_out, K, d.hop_out, d.last_start, d.n_out, combine, trim,
-                              (int)(row - out_off[r]), k);
+        probs[i] = stitch_one(LinearLogits{logits + d.logit_off, d.win_out, K}, d.n_win, d.win_out, d.hop_out, d.last_start, d.n_out,
+                              combine, trim, (int)(row - out_off[r]), k);
     }
 }
 
@@ -241,39 +214,7 @@ __global__ void detect_offsets_k(const int* __restrict__ counts, int K, int* __r
     *total = t;
 }
 
-// the batch: exclusive scan of the R*K counts by one workgroup (wave scans + the 16 wave totals, 1 024 counts per step) ->
-// offsets [R*K]; event_off [R+1] = the offset of each recording's first class, and the total
-__global__ __launch_bounds__(1024) void detect_scan_k(const int* __restrict__ counts, int n, int K, int* __restrict__ offsets,
-                                                      int* __restrict__ event_off) {
-    __shared__ int wsum[16];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    int carry = 0;
-    for (int base = 0; base < n; base += 1024) {
-        const int i = base + tid;
-        const int c = i < n ? counts[i] : 0;
-        int x = c;                                                    // inclusive wave scan
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int y = __shfl_up(x, o, 64);
-            if (lane >= o) x += y;
-        }
-        if (lane == 63) wsum[wv] = x;
-        __syncthreads();
-        int pre = 0, step = 0;
-        for (int w = 0; w < 16; ++w) {
-            pre += w < wv ? wsum[w] : 0;
-            step += wsum[w];
-        }
-        const int excl = carry + pre + x - c;
-        if (i < n) {
-            offsets[i] = excl;
-            if (i % K == 0) event_off[i / K] = excl;
-        }
-        carry += step;
-        __syncthreads();                                              // wsum is rewritten by the next step
-    }
-    if (tid == 0) event_off[n / K] = carry;
-}
+// the batch: detect_scan_k of detect_shared.h turns the R*K counts into offsets [R*K] and event_off [R+1]
 
 // one workgroup per event (grid-stride over the events): max of the unfiltered track over [onset, offset), first arg-max.
 // SEG: event e belongs to recording rec[e], whose track starts at packed row out_off[rec[e]]

@@ -234,6 +234,11 @@ class EventDetector:
         if arena is None or not arena.is_cuda:
             raise SedHipError("sed_crnn_amd: move the module to the GPU first (model.to('cuda')); there is no CPU fallback")
 
+    def stream(self, n_streams, keep_probs=False, **kw):
+        """a ``stream.StreamDetector`` for ``n_streams`` live feeds with this detector's settings"""
+        from .stream import StreamDetector
+        return StreamDetector(self.model, n_streams, keep_probs=keep_probs, _det=self, **kw)
+
     # ── the whole path ──
     def __call__(self, waveform):
         """mono PCM (1-D tensor / ndarray) -> DetectionResult.  The log-mel front end is ``feature.mbe(..., mean, std)``."""

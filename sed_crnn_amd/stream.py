@@ -1,0 +1,516 @@
+"""Live streams: stateful incremental event detection for S feeds at once.
+
+A stream gives exactly what the offline path gives on the concatenation of everything it received — ``det(wave)`` /
+``det.from_features(mel)`` — whatever the chunking.  That is possible because every quantity has a rule for when it is FINAL:
+
+* feature frame f (centre f*hop_length) is final once its ``n_fft`` samples are there: ``f*hop_length + n_fft/2 <= n``, that is
+  ``f < n // hop_length`` at the reference settings; the right-padded frames up to ``n // hop_length`` come at ``flush``;
+* with ``N`` final feature frames, ``n_out = N // tf`` and ``win_out = seq_len // tf``: track frame j is final iff
+  ``j < n_out - win_out`` (every window that covers it is complete, exists in the offline grid and keeps its right ``trim``);
+* filtered frame g is decided once track frame ``g + median // 2`` is final;
+* a pending event [a, b) is emitted in the first step in which more than ``b + min_gap`` frames are decided and no run that
+  began at or before ``b + min_gap`` is still open.
+
+``flush`` ends streams: the offline grid's last window (end-aligned, or one short sequence) runs, everything left is emitted and
+the streams restart at frame 0.  Between calls everything lives on the device, in buffers whose size depends on ``seq_len``,
+``hop``, ``median``, ``max_new_windows`` and S only; a long push is split into steps of at most ``max_new_windows`` windows per
+stream.  The host keeps the counters of all streams as arrays, so a push costs no Python per stream beyond reading its list of
+pieces.  There is no CPU fallback.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import feature
+from ._lib import SedHipError, check, lib, ptr, stream_ptr
+from .detect import EventDetector, plan_windows
+
+_KEYS = ("stream", "cls", "onset", "offset", "peak", "peak_frame")
+
+
+def _excl(x):
+    """exclusive prefix sums"""
+    return np.cumsum(x) - x
+
+
+class StreamSchedules:
+    """The host arithmetic of n streams as int64 arrays (input frames unless named ``*_out``): which windows are due after
+    every advance, and how many output frames are final / decided.  Per stream, over the advances up to the one that ends it,
+    the windows are exactly ``plan_windows(N, ...).starts``, each once (``StreamSchedule`` is the one-stream view)."""
+
+    def __init__(self, tf, seq_len, hop, trim=0, median=1, n=1):
+        plan_windows(4 * int(seq_len), tf, seq_len, hop, trim)            # the detector's own checks and messages
+        self.tf, self.L, self.trim = int(tf), int(seq_len), int(trim)
+        self.hop = self.L // 2 if hop is None else int(hop)
+        self.win_out, self.hop_out, self.r = self.L // self.tf, self.hop // self.tf, int(median) // 2
+        self.N = np.zeros(int(n), np.int64)            # final feature frames received
+        self.n_win = np.zeros(int(n), np.int64)        # regular windows scheduled so far
+
+    def reset(self, which):
+        self.N[which] = 0
+        self.n_win[which] = 0
+
+    @property
+    def n_out(self):
+        return self.N // self.tf
+
+    @property
+    def final_frames(self):
+        """output frames of the track that are final"""
+        return np.maximum(0, self.n_out - self.win_out)
+
+    @property
+    def decided(self):
+        """filtered frames that are decided (G)"""
+        return np.maximum(0, self.final_frames - self.r)
+
+    def keep_from(self):
+        """the first feature frame that a window still to come (regular, or the one that ends the stream) can need"""
+        return np.where(self.N < self.L, 0, np.minimum(self.n_win * self.hop, ((self.N - self.L) // self.tf) * self.tf))
+
+    def advance(self, rows, end=None):
+        """``rows`` [n] more final feature frames; the streams in the mask ``end`` end after them -> (index of the first new
+        window, regular windows that completed, start of the window that ends the stream or -1, length of the new windows)"""
+        first = self.n_win.copy()
+        self.N = self.N + rows
+        N, L = self.N, self.L
+        self.n_win = np.where(N >= L, (N - L) // self.hop + 1, 0)
+        extra, win_len = np.full(N.shape, -1, np.int64), np.full(N.shape, L, np.int64)
+        if end is not None and end.any():
+            last = ((N - L) // self.tf) * self.tf                           # the end-aligned window, unless the grid ends there
+            need = end & (N >= L) & ((self.n_win - 1) * self.hop != last)
+            extra[need] = last[need]
+            short = end & (N < L)                                           # one sequence of tf * n_out frames
+            extra[short] = 0
+            win_len[short] = (N // self.tf * self.tf)[short]
+        return first, self.n_win - first, extra, win_len
+
+
+class StreamSchedule:
+    """``StreamSchedules`` for one stream, in plain ints.  Over the advances plus ``finish`` the windows are exactly
+    ``plan_windows(N, ...).starts``, each once."""
+
+    def __init__(self, tf, seq_len, hop, trim=0, median=1):
+        self._v = StreamSchedules(tf, seq_len, hop, trim, median, 1)
+        self.tf, self.L, self.hop, self.trim = self._v.tf, self._v.L, self._v.hop, self._v.trim
+        self.win_out, self.hop_out = self._v.win_out, self._v.hop_out
+
+    def reset(self):
+        self._v.reset(0)
+
+    N = property(lambda self: int(self._v.N[0]))
+    n_win = property(lambda self: int(self._v.n_win[0]))
+    n_out = property(lambda self: int(self._v.n_out[0]))
+    final_frames = property(lambda self: int(self._v.final_frames[0]))
+    decided = property(lambda self: int(self._v.decided[0]))
+
+    def keep_from(self):
+        return int(self._v.keep_from()[0])
+
+    def advance(self, n_frames):
+        """``n_frames`` more final feature frames -> the starts of the regular windows that completed"""
+        first, n, _, _ = self._v.advance(np.array([int(n_frames)], np.int64))
+        return [w * self.hop for w in range(int(first[0]), int(first[0] + n[0]))]
+
+    def finish(self):
+        """the stream ends at N frames -> (starts still to run, their length, the offline WindowPlan); ValueError with
+        ``plan_windows``' message when it is shorter than one output frame"""
+        plan = plan_windows(self.N, self.tf, self.L, self.hop, self.trim)
+        _, _, extra, win_len = self._v.advance(np.zeros(1, np.int64), np.ones(1, bool))
+        return ([int(extra[0])] if extra[0] >= 0 else []), int(win_len[0]), plan
+
+
+class StreamEvents:
+    """What one ``push`` / ``push_features`` / ``flush`` made final.  ``events``: dict of device tensors ``stream``, ``cls``,
+    ``onset``, ``offset`` (exclusive), ``peak_frame`` (int32 output frames from the start of the stream) and ``peak`` (float32),
+    sorted by (stream, class, onset); ``event_offsets`` [S+1] host list (stream s = events [event_offsets[s],
+    event_offsets[s+1])); ``final_frames`` [S] host list: output frames of each stream that are final after this call; with
+    ``keep_probs``, ``probs`` [sum, K] = the newly final track rows, packed by stream, and ``prob_offsets`` [S+1]."""
+
+    def __init__(self, events, event_offsets, final_frames, frame_seconds, probs=None, prob_offsets=None):
+        self.events, self.event_offsets, self.final_frames = events, list(event_offsets), list(final_frames)
+        self.frame_seconds, self.probs, self.prob_offsets = frame_seconds, probs, prob_offsets
+
+    def __len__(self):
+        return self.event_offsets[-1]
+
+    def intervals(self, stream, k=0):
+        """[(start_s, end_s, peak), ...] of class ``k`` of one stream, on the host"""
+        e0, e1 = self.event_offsets[int(stream)], self.event_offsets[int(stream) + 1]
+        ev = {n: self.events[n][e0:e1].cpu().numpy() for n in ("cls", "onset", "offset", "peak")}
+        sel = ev["cls"] == int(k)
+        fs = self.frame_seconds
+        return [(int(a) * fs, int(b) * fs, float(p)) for a, b, p in zip(ev["onset"][sel], ev["offset"][sel], ev["peak"][sel])]
+
+
+class StreamDetector:
+    """``EventDetector`` for audio that is still arriving, S streams at once (module docstring).  The keyword arguments are
+    ``EventDetector``'s, checked the same way; ``max_new_windows``: windows per stream and step (longer pushes are split)."""
+
+    def __init__(self, model, n_streams, keep_probs=False, max_new_windows=4, _det=None, **kw):
+        self.det = _det if _det is not None else EventDetector(model, **kw)
+        det, m = self.det, self.det.model
+        S = int(n_streams)
+        if not 1 <= S <= 65535 or not 1 <= int(max_new_windows) <= 1024:
+            raise ValueError(f"need 1 <= n_streams <= 65535 and 1 <= max_new_windows <= 1024, got {n_streams}, {max_new_windows}")
+        self.S, self.keep_probs, self.max_new = S, bool(keep_probs), int(max_new_windows)
+        self.K, self.CF = m.dense[-1], m.in_channels * m.n_mels
+        tf = m.time_factor
+        self.sched = StreamSchedules(tf, det.seq_len, det.hop, det.trim, det.median, S)
+        self.win_out, self.hop_out = self.sched.win_out, self.sched.hop_out
+        self.step_frames = self.max_new * det.hop                          # feature frames per stream and step
+        self.FC = det.seq_len + tf + self.step_frames                      # rows per half of a stream's feature region
+        h = det.hop_length
+        self.q = -(-(feature.NFFT // 2) // h)                              # frames whose left half reaches before their hop
+        if self.q + 1 > self.step_frames:
+            raise ValueError(f"hop_length={h} is too small: the {self.q + 1} frames of a flush exceed one step of {self.step_frames}")
+        self.CC = (self.q + 1) * h + feature.NFFT // 2                     # samples per half of a stream's PCM carry (an upper bound)
+        self._dims = (S, self.K, self.win_out, self.hop_out, det.median, self.max_new)
+        self._core_bytes = lib().sed_stream_state_bytes(*self._dims)
+        if self._core_bytes == 0:
+            check(-1, "sed_stream_state_bytes")
+        self._state = self._feat = self._pcm = None                        # allocated by the first call that runs
+        self._aws = self._sws = self._lm = None
+        z = lambda: np.zeros(S, np.int64)                                   # noqa: E731
+        self._n, self._fdone = z(), z()                                    # samples received, feature frames made from them
+        self._cbase, self._clen, self._cpar = z(), z(), z()                # the PCM carry: first sample, length, which half
+        self._fbase, self._frows, self._fpar = z(), z(), z()               # the feature rows held: first frame, count, which half
+        self._ar = np.arange(S, dtype=np.int64)
+        self._none = np.zeros(S, bool)
+        self.marks = None                                                  # a list here receives (phase, start, end) hip events
+
+    # ── sizes ──
+    @property
+    def state_bytes(self):
+        """device bytes held between calls: the step's rings and decoder states, the feature rows and the PCM carry"""
+        return self._core_bytes + 4 * self.S * 2 * (self.FC * self.CF + self.CC)
+
+    @property
+    def frame_seconds(self):
+        return self.det.frame_seconds
+
+    def _reset_host(self, which):
+        self.sched.reset(which)
+        for x in (self._n, self._fdone, self._cbase, self._clen, self._cpar, self._fbase, self._frows, self._fpar):
+            x[which] = 0
+
+    def _ready(self):
+        """before any launch: the model's checks, then the device buffers (once)"""
+        self.det._check_model()
+        if self._state is None:
+            dev = self.det.model.flat_parameters().device
+            S = self.S
+            self._state = torch.empty(self._core_bytes, dtype=torch.uint8, device=dev)
+            self._feat = torch.empty(S * 2 * self.FC, self.CF, device=dev)
+            self._pcm = torch.empty(S * 2 * self.CC, device=dev)
+            self._aws = torch.empty(lib().sed_stream_append_workspace_bytes(S), dtype=torch.uint8, device=dev)
+            check(lib().sed_stream_init(ptr(self._state), self._state.numel(), *self._dims, stream_ptr()), "sed_stream_init")
+        return self._state.device
+
+    def _mark(self, name, fn):
+        if self.marks is None:
+            return fn()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        out = fn()
+        b.record()
+        self.marks.append((name, a, b))
+        return out
+
+    # ── log-mel of a round: carry + new samples as one clip per stream ──
+    def _logmel_round(self, fresh, takes, end):
+        """``fresh``: the round's new samples packed (device, or None), ``takes`` [S] how many belong to each stream; the
+        streams in the mask ``end`` also get their right-padded frames.  -> (features [rows, n_mels] or None, first row [S],
+        rows [S])"""
+        det, h, S, CC = self.det, self.det.hop_length, self.S, self.CC
+        dev = self._state.device
+        takes, half = np.asarray(takes, np.int64), feature.NFFT // 2
+        keep, done = self._clen, self._fdone
+        n = self._n + takes
+        # frames that need no right padding: f*h + n_fft/2 <= n; a stream that ends gets all 1 + n // h of them
+        upto = np.where(end, np.where(n > 0, 1 + n // h, 0), np.where(n >= half, (n - half) // h + 1, 0))
+        act = (takes > 0) | (upto != done)
+        # the carry [cbase, n_prev) and the new samples are one clip; the next carry starts q frames before frame `upto`
+        a_new = np.where(end, n, np.maximum(0, upto - self.q) * h)
+        total = np.where(act, keep + takes, 0)
+        work_at = _excl((total + 3) & ~3)                                   # clips start 16-byte aligned (the fast load path)
+        base = self._ar * (2 * CC)
+        table = np.stack([base + self._cpar * CC, keep, _excl(takes), takes, work_at, base + (1 - self._cpar) * CC, n - a_new], 1)
+        table[~act] = 0                                                     # sed_stream_append: zeros = nothing moves
+        clip = act & (upto > done)
+        clip_rows = np.where(clip, 1 + total // h, 0)
+        row0 = np.where(clip, _excl(clip_rows) + done - self._cbase // h, 0)
+        rows = np.where(clip, upto - done, 0)
+        n_rows, n_work = int(clip_rows.sum()), int(((total + 3) & ~3).sum())
+        self._n, self._fdone = n, upto
+        self._cbase, self._clen = np.where(act, a_new, self._cbase), np.where(act, n - a_new, self._clen)
+        self._cpar = np.where(act, 1 - self._cpar, self._cpar)
+        work = torch.empty(max(n_work, 1), device=dev) if n_rows else None
+        if act.any():
+            table = np.ascontiguousarray(table)
+            check(lib().sed_stream_append(ptr(self._pcm), self._pcm.numel(), 2 * CC, ptr(fresh), int(takes.sum()), ptr(work),
+                                          work.numel() if work is not None else 0, C.c_void_p(table.ctypes.data), S, ptr(self._aws),
+                                          self._aws.numel(), stream_ptr()), "sed_stream_append")
+        if not n_rows:
+            return None, row0, rows
+        if self._lm is None:
+            m = det.model
+            tables = feature._tables(dev.index or 0, det.sr, feature.NFFT, m.n_mels)
+            mean = inv = None
+            if det.mean is not None:
+                mean = det.mean.to(dev).float().contiguous()
+                inv = (1.0 / det.std.to(dev).double()).float().contiguous()
+            ws = torch.empty(lib().sed_logmel_batch_workspace_bytes(S), dtype=torch.uint8, device=dev)
+            self._lm = (tables, mean, inv, ws)
+        tables, mean, inv, ws = self._lm
+        ct = np.ascontiguousarray(np.stack([work_at[clip], total[clip]], 1))
+        out = torch.empty(n_rows, det.model.n_mels, device=dev)
+        self._mark("logmel", lambda: check(lib().sed_logmel_batch(
+            ptr(work), work.numel(), C.c_void_p(ct.ctypes.data), ct.shape[0], ptr(tables), tables.numel() * 4, ptr(mean), ptr(inv),
+            ptr(out), n_rows, feature.NFFT, h, det.model.n_mels, 0, ptr(ws), ws.numel(), stream_ptr()), "sed_logmel_batch"))
+        return out, row0, rows
+
+    # ── one step: new feature rows in, events out ──
+    def _step(self, fresh, row0, rows, end):
+        """``fresh`` [*, CF] device rows, stream s takes ``rows[s]`` of them from ``row0[s]`` (at most step_frames); the streams
+        in the mask ``end`` end after them.  -> (events dict, event offsets [S+1], probs or None, prob counts [S], final [S])"""
+        det, S, K, CF, FC, sc = self.det, self.S, self.K, self.CF, self.FC, self.sched
+        dev = self._state.device
+        tf, L, ar = det.model.time_factor, det.seq_len, self._ar
+        rows, row0 = np.asarray(rows, np.int64), np.asarray(row0, np.int64)
+        # 1. the feature rows: keep what a later window can need, append the new rows (into the stream's other half)
+        act = rows > 0
+        if act.any():
+            k0 = sc.keep_from()
+            keep = self._fbase + self._frows - k0
+            base = ar * (2 * FC * CF)
+            at = np.stack([base + (self._fpar * FC + (k0 - self._fbase)) * CF, keep * CF, row0 * CF, rows * CF, np.zeros(S, np.int64),
+                           base + (1 - self._fpar) * FC * CF, (keep + rows) * CF], 1)
+            at[~act] = 0
+            at = np.ascontiguousarray(at)
+            self._fbase, self._frows = np.where(act, k0, self._fbase), np.where(act, keep + rows, self._frows)
+            self._fpar = np.where(act, 1 - self._fpar, self._fpar)
+            check(lib().sed_stream_append(ptr(self._feat), self._feat.numel(), 2 * FC * CF, ptr(fresh), fresh.numel(), None, 0,
+                                          C.c_void_p(at.ctypes.data), S, ptr(self._aws), self._aws.numel(), stream_ptr()),
+                  "sed_stream_append")
+        # 2. the windows that are due, and the step's table
+        prev_out, prev_F, prev_G = sc.n_out, sc.final_frames, sc.decided
+        w0, n_reg, extra, win_len = sc.advance(rows, end)
+        now_out = sc.n_out
+        now_F, now_G = np.where(end, now_out, sc.final_frames), np.where(end, now_out, sc.decided)
+        row_base = ar * (2 * FC) + self._fpar * FC - self._fbase           # + a frame of the stream = its row in the feature state
+        short = win_len != L                                                # streams that end below seq_len: one window each
+        cf = n_reg + ((extra >= 0) & ~short)                                # windows of seq_len frames per stream
+        first = _excl(cf)
+        n_full = int(cf.sum())
+        idx = np.repeat(ar, cf)
+        within = np.arange(n_full, dtype=np.int64) - np.repeat(first, cf)
+        full = row_base[idx] + np.where(within < n_reg[idx], (w0[idx] + within) * sc.hop, extra[idx])
+        logit_off = first * (self.win_out * K)
+        n_logits, groups = n_full * self.win_out * K, []
+        for Lw in np.unique(win_len[short]).tolist():                       # grouped by length, like the offline batch
+            ss = np.nonzero(short & (win_len == Lw))[0]
+            logit_off[ss] = n_logits + np.arange(len(ss)) * ((Lw // tf) * K)
+            groups.append((Lw, row_base[ss]))
+            n_logits += len(ss) * (Lw // tf) * K
+        prob_n, dg = now_F - prev_F, now_G - prev_G
+        dg_max, cap, n_probs = int(dg.max()), int((K * (dg // 2 + 2)).sum()), int(prob_n.sum())
+        table = np.ascontiguousarray(np.stack([cf + short, logit_off, w0, prev_out, now_out, end.astype(np.int64), win_len // tf,
+                                               _excl(prob_n)], 1))
+        # 3. gather + forward, chunked exactly like the offline detector
+        logits = torch.empty(max(n_logits, 1), device=dev)
+        jobs, used = [], 0
+        if n_full:
+            jobs.append((torch.from_numpy(full.astype(np.int32)).to(dev, non_blocking=True), L,
+                         logits[:n_full * self.win_out * K].view(n_full, self.win_out, K)))
+            used = n_full * self.win_out * K
+        for Lw, starts in groups:
+            n, wo = len(starts), Lw // tf
+            jobs.append((torch.from_numpy(starts.astype(np.int32)).to(dev, non_blocking=True), Lw,
+                         logits[used:used + n * wo * K].view(n, wo, K)))
+            used += n * wo * K
+        if jobs:
+            with torch.no_grad():
+                det._forward_windows(self._feat, jobs, self.marks)
+        # 4. the step
+        need = lib().sed_stream_step_workspace_bytes(S, K, dg_max)
+        if self._sws is None or self._sws.numel() < need:
+            self._sws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ev = torch.empty(6, max(cap, 1), dtype=torch.int32, device=dev)
+        ev_off = torch.empty(S + 1, dtype=torch.int32, device=dev)
+        probs = torch.empty(n_probs, K, device=dev) if self.keep_probs else None
+        give = probs is not None and n_probs > 0
+        self._mark("step", lambda: check(lib().sed_stream_step(
+            ptr(self._state), self._state.numel(), *self._dims, {"mean": 0, "max": 1}[det.combine], det.trim, det.lo, det.hi,
+            det.min_gap, det.min_len, ptr(logits) if n_logits else None, n_logits, C.c_void_p(table.ctypes.data), dg_max,
+            ptr(probs) if give else None, n_probs if give else 0, cap, *(ptr(ev[i]) for i in range(6)), ptr(ev_off), ptr(self._sws),
+            self._sws.numel(), stream_ptr()), "sed_stream_step"))
+        offs = ev_off.cpu().tolist()                                        # the one blocking read of a step
+        if offs[-1] > cap:
+            raise SedHipError(f"sed_stream_step emitted {offs[-1]} events, more than the bound {cap}")
+        n = offs[-1]
+        events = {k: (ev[i, :n].view(torch.float32) if k == "peak" else ev[i, :n]) for i, k in enumerate(_KEYS)}
+        if end.any():
+            self._reset_host(end)
+        return events, offs, probs, prob_n, now_F
+
+    # ── rounds: a push of any size as steps of bounded size ──
+    def _run(self, rounds):
+        """``rounds``: an iterator of (fresh, row0, rows, end mask) steps -> one StreamEvents for all of them"""
+        S, K = self.S, self.K
+        dev = self._state.device
+        parts = []
+        final = self.sched.final_frames
+        for fresh, row0, rows, end in rounds:
+            if not rows.any() and not end.any():
+                continue
+            parts.append(self._step(fresh, row0, rows, end))
+            final = parts[-1][4]
+        final = final.tolist()
+        if not parts:
+            ev = {k: torch.empty(0, dtype=torch.float32 if k == "peak" else torch.int32, device=dev) for k in _KEYS}
+            probs = torch.empty(0, K, device=dev) if self.keep_probs else None
+            return StreamEvents(ev, [0] * (S + 1), final, self.frame_seconds, probs, [0] * (S + 1) if self.keep_probs else None)
+        if len(parts) == 1:
+            ev, offs, probs, prob_n, _ = parts[0]
+            poffs = np.concatenate([[0], np.cumsum(prob_n)]).tolist() if self.keep_probs else None
+            return StreamEvents(ev, offs, final, self.frame_seconds, probs, poffs)
+        # several steps: a stream's events (and rows) of step 1, then of step 2, ...: one stable sort by (stream, class)
+        ev = {k: torch.cat([p[0][k] for p in parts]) for k in _KEYS}
+        order = torch.sort(ev["stream"].long() * K + ev["cls"].long(), stable=True).indices
+        ev = {k: v[order] for k, v in ev.items()}
+        counts = np.sum([np.diff(p[1]) for p in parts], axis=0)
+        offs = np.concatenate([[0], np.cumsum(counts)]).tolist()
+        probs = poffs = None
+        if self.keep_probs:
+            owner = np.concatenate([np.repeat(self._ar, p[3]) for p in parts])     # the stream of every row, steps in order
+            idx = np.argsort(owner, kind="stable")                          # by stream, steps in order within a stream
+            allp = torch.cat([p[2] for p in parts])
+            probs = allp[torch.from_numpy(idx).to(dev)]
+            poffs = np.concatenate([[0], np.cumsum(np.sum([p[3] for p in parts], axis=0))]).tolist()
+        return StreamEvents(ev, offs, final, self.frame_seconds, probs, poffs)
+
+    def _pieces(self, xs, what, check_one):
+        xs = list(xs)
+        if len(xs) != self.S:
+            raise ValueError(f"expected {self.S} {what} (one per stream, None = nothing new), got {len(xs)}")
+        pieces, lens = [], np.zeros(self.S, np.int64)
+        for s, x in enumerate(xs):
+            if x is not None:
+                x = check_one(s, x)
+                lens[s] = x.shape[0]
+            pieces.append(x)
+        return pieces, lens
+
+    def _pack(self, pieces, lens, done, takes, dev):
+        """the round's share of every piece, back to back on the device (host pieces travel in one copy)"""
+        parts = [pieces[s] if takes[s] == lens[s] else pieces[s][done[s]:done[s] + takes[s]] for s in np.nonzero(takes)[0]]
+        if all(not p.is_cuda for p in parts):
+            return torch.cat([p.to(torch.float32) for p in parts]).to(dev)
+        return torch.cat([p.to(dev, torch.float32) for p in parts])
+
+    def push(self, chunks):
+        """a list of S mono PCM pieces (1-D, host or device, any length >= 0; None = nothing new) -> StreamEvents"""
+        m = self.det.model
+        if m.in_channels != 1:
+            raise ValueError(f"a mono waveform feeds a 1-channel net; this one has {m.in_channels} (use push_features)")
+
+        def one(s, c):
+            c = c if isinstance(c, torch.Tensor) else torch.as_tensor(np.asarray(c))
+            if c.dim() != 1:
+                raise ValueError(f"stream {s}: expected a mono 1-D waveform, got shape {tuple(c.shape)}")
+            return c
+        pieces, lens = self._pieces(chunks, "waveform pieces", one)
+        dev = self._ready()
+        per_round = (self.step_frames - 1) * self.det.hop_length
+
+        def rounds():
+            done = np.zeros(self.S, np.int64)
+            while True:
+                takes = np.minimum(per_round, lens - done)
+                if not takes.any():
+                    return
+                fresh = self._pack(pieces, lens, done, takes, dev)
+                done = done + takes
+                mel, row0, rows = self._logmel_round(fresh, takes, self._none)
+                yield mel, row0, rows, self._none
+        return self._run(rounds())
+
+    def push_features(self, mels):
+        """a list of S scaled feature pieces [n_s, C*F] (any channel count, host or device; None = nothing new) -> StreamEvents"""
+        def one(s, x):
+            x = torch.as_tensor(x)
+            if x.dim() != 2 or x.shape[1] != self.CF:
+                m = self.det.model
+                raise ValueError(f"stream {s}: expected features [N, {self.CF}] (C*F = {m.in_channels}*{m.n_mels}), got {tuple(x.shape)}")
+            return x
+        pieces, lens = self._pieces(mels, "feature pieces", one)
+        dev = self._ready()
+
+        def rounds():
+            done = np.zeros(self.S, np.int64)
+            while True:
+                rows = np.minimum(self.step_frames, lens - done)
+                if not rows.any():
+                    return
+                fresh = self._pack(pieces, lens, done, rows, dev).contiguous()
+                done = done + rows
+                yield fresh, _excl(rows), rows, self._none
+        return self._run(rounds())
+
+    def flush(self, streams=None):
+        """end these streams (default: all): their right-padded log-mel frames and the offline grid's last window run, what
+        is left is emitted, and they restart at frame 0.  A stream that received nothing is left alone; one shorter than one
+        output frame raises ValueError (``plan_windows``' message) before anything runs."""
+        which = range(self.S) if streams is None else [int(s) for s in streams]
+        for s in which:
+            if not 0 <= s < self.S:
+                raise ValueError(f"stream {s} of {self.S}")
+        h, sc = self.det.hop_length, self.sched
+        end = np.zeros(self.S, bool)
+        for s in sorted(set(which)):
+            N = int(sc.N[s]) + (int(1 + self._n[s] // h - self._fdone[s]) if self._n[s] else 0)
+            if N == 0:
+                continue
+            try:
+                plan_windows(N, sc.tf, sc.L, sc.hop, sc.trim)
+            except ValueError as e:
+                raise ValueError(f"stream {s}: {e}") from None
+            end[s] = True
+        self._ready()
+
+        def rounds():
+            if not end.any():
+                return
+            zero = np.zeros(self.S, np.int64)
+            if (self._n[end] > 0).any():
+                mel, row0, rows = self._logmel_round(None, zero, end)
+            else:
+                mel, row0, rows = None, zero, zero
+            yield mel, row0, rows, end
+        return self._run(rounds())
+
+    def reset(self, streams=None):
+        """drop these streams (default: all) where they stand: nothing is emitted, they restart at frame 0"""
+        which = np.arange(self.S) if streams is None else np.asarray([int(s) for s in streams], np.int64).reshape(-1)
+        if which.size and not ((which >= 0) & (which < self.S)).all():
+            raise ValueError(f"streams {which.tolist()} of {self.S}")
+        self._ready()
+        if which.size:
+            ids = (C.c_int * which.size)(*which.tolist())
+            check(lib().sed_stream_reset(ptr(self._state), self._state.numel(), *self._dims, ids, which.size, stream_ptr()),
+                  "sed_stream_reset")
+            self._reset_host(which)
+
+    def active(self):
+        """[(stream, cls, onset), ...] of the events that are open right now: a run that is known to be kept and has not closed
+        (with the onset of the pending event it will merge with, if there is one)"""
+        self._ready()
+        n = self.S * self.K
+        d = self._state[self._core_bytes - 64 * n:].view(torch.int32).view(n, 16).cpu().numpy()
+        out = []
+        for i in np.nonzero((d[:, 0] != 0) & (d[:, 2] != 0))[0]:
+            merge = d[i, 5] != 0 and d[i, 1] - d[i, 7] <= self.det.min_gap
+            out.append((int(i) // self.K, int(i) % self.K, int(d[i, 6] if merge else d[i, 1])))
+        return out
