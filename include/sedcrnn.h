@@ -513,6 +513,26 @@ int sed_detect_events_batch(const float* probs, const long* n_out_host, int R, i
                             int min_len, int max_events, void* workspace, size_t workspace_bytes, int* rec, int* cls, int* onset,
                             int* offset, float* peak, int* peak_frame, int* event_off, void* stream);
 
+/* ───────────── decoder sweep (sed_crnn_amd/tune.py) ─────────────
+ * Scores the events of sed_detect_events_batch against reference events for G decoder settings at once, without writing an
+ * event and without a read back.  probs [n_total][K] and n_out_host [R] as in sed_detect_events_batch.  settings_host [G]: the
+ * five decoder values of each setting, checked like that entry's (median odd 1..31, hi >= lo, min_gap >= 0, min_len >= 1).
+ * Reference events (DEVICE arrays, validated by the caller): ref_off [R*K + 1] is a CSR over (recording, class); within one
+ * (recording, class) the events [ref_onset, ref_offset) are sorted, pairwise disjoint and inside [0, n_out_r]; all four arrays
+ * non-NULL even when there is no event.  Matching per (recording, class): the system events in order, each taken by the first
+ * unmatched reference event j with |onset - ref_onset[j]| <= collar (0..31 output frames) and, when ref_tol[j] >= 0,
+ * |offset - ref_offset[j]| <= ref_tol[j].  Segments: blocks of `block` (>= 1) output frames from each recording's frame 0, the
+ * partial last block kept; a block is active on a side when an event of that side covers one of its frames.
+ * counts [G][K][6] (device, int64, cleared by the call) = ev_tp, n_sys, n_ref, seg_tp, seg_sys, seg_ref summed over recordings:
+ * integer arithmetic, exact and repeatable.  One bit track is packed per distinct (median, threshold value) among the settings'
+ * lo and hi; workspace >= sed_tune_workspace_bytes(n_total, K, R, n_tracks, G) with n_tracks that number (0 = bad sizes;
+ * G in 1..2^20, n_tracks in 1..2G).  G = 0 is a no-op that returns 0 once the recording table has been checked. */
+typedef struct sed_tune_setting { int median; float lo, hi; int min_gap, min_len; } sed_tune_setting;
+size_t sed_tune_workspace_bytes(long n_total, int K, int R, int n_tracks, int G);
+int sed_tune_sweep(const float* probs, const long* n_out_host, int R, int K, const sed_tune_setting* settings_host, int G,
+                   const int* ref_off, const int* ref_onset, const int* ref_offset, const int* ref_tol, int collar, int block,
+                   void* workspace, size_t workspace_bytes, long* counts, void* stream);
+
 /* ───────────── live streams (sed_crnn_amd/stream.py) ─────────────
  * S feeds keep their state on the device between calls, in ONE caller-owned buffer of sed_stream_state_bytes(...) bytes (0 = bad
  * sizes: S in 1..65535, K in 1..32, 1 <= hop_out <= win_out, median odd 1..31, max_new_windows in 1..1024; the size depends on

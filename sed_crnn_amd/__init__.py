@@ -15,6 +15,7 @@ from .losses import BCEWithLogitsLoss, FocalBCELoss  # noqa: F401
 from .model import (HipCRNN, LightningTimePooledCRNN, SEDNet, TimePooledCRNN,  # noqa: F401
                     get_model)
 from .stream import StreamDetector, StreamEvents, StreamSchedule, StreamSchedules  # noqa: F401
+from .tune import DecoderGrid, ReferenceEvents, SweepResult, tune_decoder  # noqa: F401
 from .optim import FusedAdam, clip_grad_norm_  # noqa: F401
 
 __version__ = "0.1.0"

@@ -44,6 +44,11 @@ class NetParams(C.Structure):
     ]
 
 
+class TuneSetting(C.Structure):
+    """sed_tune_setting: one decoder setting of sed_tune_sweep"""
+    _fields_ = [("median", C.c_int), ("lo", C.c_float), ("hi", C.c_float), ("min_gap", C.c_int), ("min_len", C.c_int)]
+
+
 _i, _l, _f, _d, _u64, _sz = C.c_int, C.c_long, C.c_float, C.c_double, C.c_uint64, C.c_size_t
 _pp = C.POINTER(_fp)
 
@@ -144,6 +149,8 @@ SIGNATURES = {
     "sed_detect_batch_workspace_bytes": (_sz, [_l, _i, _i, _i]),
     "sed_detect_stitch_batch": (_i, [_fp, _l, _fp, _i, _i, _i, _i, _fp, _l, _fp, _sz, _stream]),
     "sed_detect_events_batch": (_i, [_fp, _fp, _i, _i, _i, _f, _f, _i, _i, _i, _fp, _sz, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _stream]),
+    "sed_tune_workspace_bytes": (_sz, [_l, _i, _i, _i, _i]),
+    "sed_tune_sweep": (_i, [_fp, _fp, _i, _i, _fp, _i, _fp, _fp, _fp, _fp, _i, _i, _fp, _sz, _fp, _stream]),
     "sed_stream_state_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "sed_stream_init": (_i, [_fp, _sz, _i, _i, _i, _i, _i, _i, _stream]),
     "sed_stream_reset": (_i, [_fp, _sz, _i, _i, _i, _i, _i, _i, _fp, _i, _stream]),

@@ -24,17 +24,6 @@ __global__ __launch_bounds__(256) void detect_stitch_k(const float* __restrict__
 // the grid of one recording of a batch (sed_detect_stitch_batch): its logits start logit_off floats into the packed buffer
 struct DetRec { long logit_off; int n_win, win_out, hop_out, last_start, n_out, pad; };
 
-// last r with off[r] <= x (off[0] = 0 <= x, off ascending)
-__device__ __forceinline__ int find_seg(const int* __restrict__ off, int R, long x) {
-    int lo = 0, hi = R - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= x) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
 // One thread per (packed output frame, class): its recording by binary search over the output offsets, then exactly the
 // arithmetic of detect_stitch_k with that recording's grid (so a recording's track equals sed_detect_stitch of its logits)
 __global__ __launch_bounds__(256) void detect_stitch_batch_k(const float* __restrict__ logits, const DetRec* __restrict__ recs,
@@ -79,29 +68,6 @@ extern "C" int sed_detect_stitch(const float* logits, long n_win, int win_out, i
 // high bits before every edge from a wave scan of popcounts, so a run [a, b) is kept iff H(b) - H(a) > 0; lane 0 then walks the
 // chunk's edge list with the carried state (open run, pending event) to merge and drop.  Run once to count, a one-thread scan
 // turns the counts into per-class offsets, run again to write.  Phase 3: peak / first arg-max of the unfiltered track.
-static inline long detect_words(long n_out) { return n_out / 64 + 1; }
-
-template <int M>
-__device__ __forceinline__ float median_nearest(const float* __restrict__ probs, int j, int k, int K, int n_out) {
-    if (M == 1) return probs[(size_t)j * K + k];
-    float v[M];
-#pragma unroll
-    for (int d = 0; d < M; ++d) {
-        int t = j + d - M / 2;
-        t = t < 0 ? 0 : (t >= n_out ? n_out - 1 : t);
-        v[d] = probs[(size_t)t * K + k];
-    }
-    float med = v[0];
-#pragma unroll
-    for (int i = 0; i < M; ++i) {
-        int less = 0, leq = 0;
-#pragma unroll
-        for (int d = 0; d < M; ++d) { less += v[d] < v[i]; leq += v[d] <= v[i]; }
-        if (less <= M / 2 && M / 2 < leq) med = v[i];                 // v[i] is the (M/2)-th smallest
-    }
-    return med;
-}
-
 template <int M>
 __global__ __launch_bounds__(256) void detect_bits_k(const float* __restrict__ probs, int n_out, int K, long n_words, float lo,
                                                      float hi, unsigned long long* __restrict__ on_bits,
@@ -124,7 +90,22 @@ __global__ __launch_bounds__(256) void detect_bits_k(const float* __restrict__ p
 
 // Batched (SEG, sed_detect_events_batch): one wave per (recording r, class k), workgroup r*K + k; recording r's bit tracks
 // are [K][n_words_r] at word K*word_off[r] (every track starts on a word boundary), so no run, gap or event crosses recordings.
-#define DETECT_EDGE_CAP 4096                                      // 64 words x 64 bits: every edge of a chunk
+// The walk itself is detect_walk_body of detect_shared.h (shared with the decoder sweep of tune.hip); here every finished event
+// is counted and, in the write pass, stored.
+struct DetectEmit {
+    int write, max_events, k, r;
+    long base;
+    int *cls, *onset, *offset, *rec;
+    int cnt;
+    __device__ __forceinline__ void operator()(int on, int off) {
+        if (write && base + cnt < max_events) {
+            cls[base + cnt] = k; onset[base + cnt] = on; offset[base + cnt] = off;
+            if (rec) rec[base + cnt] = r;
+        }
+        ++cnt;
+    }
+};
+
 template <bool SEG = false>
 __global__ __launch_bounds__(64) void detect_walk_k(const unsigned long long* __restrict__ on_bits,
                                                     const unsigned long long* __restrict__ hi_bits, long n_words, int min_gap,
@@ -133,78 +114,17 @@ __global__ __launch_bounds__(64) void detect_walk_k(const unsigned long long* __
                                                     int* __restrict__ onset, int* __restrict__ offset,
                                                     const int* __restrict__ word_off = nullptr, int K = 0, int* __restrict__ rec = nullptr) {
     __shared__ int epos[DETECT_EDGE_CAP], eh[DETECT_EDGE_CAP];
-    const int lane = threadIdx.x, r = SEG ? (int)blockIdx.x / K : 0;
+    const int r = SEG ? (int)blockIdx.x / K : 0;
     const int k = SEG ? (int)blockIdx.x - r * K : (int)blockIdx.x;
     size_t track0 = 0;
     if (SEG) {
         track0 = (size_t)K * word_off[r];
         n_words = word_off[r + 1] - word_off[r];
     }
-    const unsigned long long* ob = on_bits + track0 + (size_t)k * n_words;
-    const unsigned long long* hb = hi_bits + track0 + (size_t)k * n_words;
-    const long base = write ? offsets[blockIdx.x] : 0;
-    unsigned carry_top = 0;                      // bit 63 of the previous chunk's last word
-    long hbase = 0;                              // high bits before this chunk
-    // lane 0's walk state
-    bool open = false, have = false;
-    int r_on = 0, p_on = 0, p_off = 0;
-    long r_h = 0;
-    int cnt = 0;
-    for (long w0 = 0; w0 < n_words; w0 += 64) {
-        const long w = w0 + lane;
-        const unsigned long long on = w < n_words ? ob[w] : 0ull, hi = w < n_words ? hb[w] : 0ull;
-        unsigned prev = __shfl((unsigned)(on >> 63), (lane + 63) & 63, 64);
-        if (lane == 0) prev = carry_top;
-        const unsigned long long sh = (on << 1) | prev;
-        const unsigned long long edges = on ^ sh;                // rises (on & ~sh) and falls (~on & sh) alternate globally
-        int hc = __popcll(hi), ne = __popcll(edges);
-        int hpre = hc, epre = ne;                                // inclusive wave scans
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int a = __shfl_up(hpre, o, 64), b = __shfl_up(epre, o, 64);
-            if (lane >= o) { hpre += a; epre += b; }
-        }
-        const int n_edges = __shfl(epre, 63, 64), n_high = __shfl(hpre, 63, 64);
-        hpre -= hc;
-        epre -= ne;
-        for (unsigned long long m = edges; m; m &= m - 1) {
-            const int b = __ffsll((long long)m) - 1;
-            epos[epre] = (int)(w * 64 + b);
-            eh[epre] = (int)(hbase + hpre + __popcll(hi & ((1ull << b) - 1ull)));
-            ++epre;
-        }
-        __syncthreads();
-        if (lane == 0) {
-            for (int e = 0; e < n_edges; ++e) {
-                if (!open) { open = true; r_on = epos[e]; r_h = eh[e]; continue; }
-                open = false;
-                const int r_off = epos[e];
-                if (eh[e] - r_h <= 0) continue;                  // no frame of the run above hi
-                if (have && r_on - p_off <= min_gap) { p_off = r_off; continue; }
-                if (have && p_off - p_on >= min_len) {
-                    if (write && base + cnt < max_events) {
-                        cls[base + cnt] = k; onset[base + cnt] = p_on; offset[base + cnt] = p_off;
-                        if (SEG) rec[base + cnt] = r;
-                    }
-                    ++cnt;
-                }
-                have = true; p_on = r_on; p_off = r_off;
-            }
-        }
-        __syncthreads();
-        carry_top = (unsigned)__shfl((unsigned)(on >> 63), 63, 64);
-        hbase += n_high;
-    }
-    if (lane == 0) {
-        if (have && p_off - p_on >= min_len) {
-            if (write && base + cnt < max_events) {
-                cls[base + cnt] = k; onset[base + cnt] = p_on; offset[base + cnt] = p_off;
-                if (SEG) rec[base + cnt] = r;
-            }
-            ++cnt;
-        }
-        if (!write) counts[blockIdx.x] = cnt;
-    }
+    DetectEmit emit{write, max_events, k, r, write ? (long)offsets[blockIdx.x] : 0l, cls, onset, offset, SEG ? rec : nullptr, 0};
+    detect_walk_body(on_bits + track0 + (size_t)k * n_words, hi_bits + track0 + (size_t)k * n_words, n_words, min_gap, min_len,
+                     epos, eh, emit);
+    if (threadIdx.x == 0 && !write) counts[blockIdx.x] = emit.cnt;
 }
 
 __global__ void detect_offsets_k(const int* __restrict__ counts, int K, int* __restrict__ offsets, int* __restrict__ total) {

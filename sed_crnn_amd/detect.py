@@ -221,6 +221,7 @@ class EventDetector:
         self._zlab = None                       # zero label column for sed_window_batch (it requires one)
         self._dws = None
         self._bws = None                        # the batch entries' workspace
+        self._tune_cache = {}                   # the sweep's workspace
 
     @property
     def frame_seconds(self):
@@ -238,6 +239,39 @@ class EventDetector:
         """a ``stream.StreamDetector`` for ``n_streams`` live feeds with this detector's settings"""
         from .stream import StreamDetector
         return StreamDetector(self.model, n_streams, keep_probs=keep_probs, _det=self, **kw)
+
+    # ── scoring and tuning the decoder (tune.py; DESIGN 5i) ──
+    def decoder_settings(self):
+        """this detector's decoder values, as ``DecoderGrid`` / ``with_decoder`` take them"""
+        return dict(threshold=self.hi, low=self.lo, median=self.median, min_gap=self.min_gap, min_len=self.min_len)
+
+    def with_decoder(self, **settings):
+        """A new detector that shares the model, the scaler and the window grid and has the decoder values (``threshold``,
+        ``low``, ``median``, ``min_gap``, ``min_len``) replaced.  ``threshold`` without ``low`` means low = threshold."""
+        extra = set(settings) - {"threshold", "low", "median", "min_gap", "min_len"}
+        if extra:
+            raise TypeError(f"with_decoder takes decoder settings only, got {sorted(extra)}")
+        kw = self.decoder_settings()
+        if "threshold" in settings and settings.get("low") is None:
+            kw["low"] = None
+        kw.update(settings)
+        return EventDetector(self.model, seq_len=self.seq_len, hop=self.hop, combine=self.combine, trim=self.trim, mean=self.mean,
+                             std=self.std, sr=self.sr, hop_length=self.hop_length, max_batch=self.max_batch, **kw)
+
+    def sweep(self, track, ref, grid, collar=1, offset_collar=None, offset_percent=None, block=None, max_workspace_bytes=1 << 30):
+        """Score every decoder setting of ``grid`` (a ``DecoderGrid``) on a track against ``ref`` (a ``ReferenceEvents``) on
+        the device -> ``SweepResult`` (``tune.sweep``).  ``track``: a BatchDetectionResult, a DetectionResult or
+        ``(probs, out_offsets)``; ``collar`` in output frames (0..31); onset-only scoring unless ``offset_collar`` /
+        ``offset_percent`` is given; ``block`` output frames per segment, default ``round(1 / frame_seconds)``."""
+        from . import tune
+        block = max(1, int(round(1.0 / self.frame_seconds))) if block is None else block
+        return tune.sweep(track, ref, grid, collar, offset_collar, offset_percent, block, max_workspace_bytes, self._tune_cache)
+
+    def score(self, result, ref, collar=1, offset_collar=None, offset_percent=None, block=None):
+        """the sweep with G = 1 and this detector's own decoder setting: how good are ``result``'s events against ``ref``"""
+        from .tune import DecoderGrid
+        return self.sweep(result, ref, DecoderGrid.from_settings([self.decoder_settings()]), collar, offset_collar, offset_percent,
+                          block)
 
     # ── the whole path ──
     def __call__(self, waveform):
@@ -470,7 +504,9 @@ class EventDetector:
 
     def decode_many(self, probs, bp):
         """packed track -> (events with ``rec``, event offsets [R+1] host list).  The R+1 offsets are the one read of the
-        batch; when the total exceeds the buffers, they grow and only the decode runs again."""
+        batch; when the total exceeds the buffers, they grow and only the decode runs again.  Of ``bp`` only ``plans`` (its
+        length, R) and ``out_off`` [R+1] are used: ``plan_batch([tf * n for n in n_out], tf, K)`` decodes a track that did
+        not come from this detector's forward."""
         import numpy as np
         n_total, K = probs.shape
         R = len(bp.plans)
