@@ -387,6 +387,11 @@ size_t sed_gru_seq_bwd_workspace_bytes(int B, int H);
 int sed_gru_seq_bwd(const float* dout, const float* saved, const float* const* whh,
                     float* dgi, float* dgh, float* const* dbih, float* const* dbhh, void* workspace,
                     int B, int T, int H, void* stream);
+/* Which kernel variant a (B, H) call of the two functions above runs (host only, the launches read the same rule):
+ * *bt = batch rows per workgroup (1, 2 or 4); *hreg = weights of a gate row held in registers (H: the whole row, 0: none,
+ * the row is streamed from L2 every step); *hlds = weights of a row held in LDS (> 0 only for the H = 256 hybrid, where
+ * *hreg is the forward kernel's share and the remaining H - hreg - hlds are streamed). */
+int sed_gru_seq_variant(int B, int H, int* bt, int* hreg, int* hlds);
 
 /* ───────────── loss heads (sed.py:136,160; crnn_lightning.py:27-35) ─────────────
  * kind 0: BCEWithLogits mean; kind 1: focal (alpha, gamma, log(pt+1e-12)); reduction_mean=0 -> sum.

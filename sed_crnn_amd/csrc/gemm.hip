@@ -284,8 +284,8 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce_k(const float* __restr
 //    trips (91 TFLOP/s against 117 for the 1280-tile data gradient that keeps several workgroups per CU): two K-slices make
 //    two co-resident workgroups per CU (113 TFLOP/s incl. the slice sum).  Weight gradients only (sed_gemm_f32_wgrad): their K
 //    axis is the batch x time axis, so no caller can expect the result to be independent of how that axis is cut.  The
-//    forward input projection (same shape class, +15 % with two slices) is NOT sliced: an eval forward of a whole batch must
-//    stay bit-identical to the forward of its chunks.
+//    forward input projection (same shape class, +15 % with two slices) is NOT sliced by this rule: it looks at the tile count,
+//    i.e. at M, and the eval forward of a batch should not depend on how the batch is cut into chunks.
 //  Slices are summed in slice order by gemm_splitk_reduce_k: deterministic.
 struct GemmPlan { int cand, splits, k_len; };
 static const struct { int bm, bn; double eff; } kCands[5] = {{128, 128, 1.00}, {128, 96, 0.95}, {128, 64, 0.88}, {64, 128, 0.88}, {64, 64, 0.78}};
@@ -324,9 +324,14 @@ static GemmPlan gemm_plan(int M, int N, int K, int policy) {
         p.splits = cdiv(K, p.k_len);
     }
     // forward projections (policy 1): two K-slices for a long K and a narrow output, decided by N and K ALONE — the same
-    // split for every batch size, so a sample's result does not depend on the batch it is evaluated in (the rule above
-    // looks at the tile count, i.e. at M, which is why it is reserved for weight gradients).  At N <= 1024 the usual
+    // split for every M that reaches this point, so a sample's result does not depend on the batch it is evaluated in (the
+    // rule above looks at the tile count, i.e. at M, which is why it is reserved for weight gradients).  At N <= 1024 the usual
     // batches give at most one workgroup per CU (one wave per SIMD); two co-resident slices hide each other's waits.
+    // NOT every M reaches this point: the small-output rule at the top of this function also applies to policy 1 and does
+    // look at M (blocks64 < 96 && K >= 1024).  For the 128-channel net (K = 5120, N = 768, 8 rows per 64-frame window) a chunk of
+    // at most 56 windows sums K in up to 21 slices, a larger one in these two, so logits of small and large chunks differ by
+    // rounding (<= 2e-6, measured 6e-8) and are bitwise equal only between chunks of 57 windows or more
+    // (tests/test_gpu_detect.py: test_chunking_of_the_128_channel_net_...; DESIGN 2 "Batch separability", 5f).
     if (policy == 1 && K >= 4096 && N <= 1024) {
         p.k_len = ((cdiv(K, 2) + GM_BK - 1) / GM_BK) * GM_BK;
         p.splits = cdiv(K, p.k_len);

@@ -35,6 +35,17 @@ __global__ void gru_pack_whh_t_k(const float* __restrict__ w0, const float* __re
 
 constexpr int gru_nt(int hreg) { return hreg > 0 ? ((3 * hreg + 63) / 64) * 64 : 1024; }
 
+// Four terms of a gate row's dot product with h, rounded the same way wherever the weights come from.  Left to the compiler,
+// `acc += w0*h0 + w1*h1 + w2*h2 + w3*h3` became a multiply and three fused multiply-adds in the register-resident
+// instantiations but four rounded products and three additions where the SLP vectoriser packed the streamed and LDS loops, so
+// the H = 256 hybrid (B < 256) and the streamed <0,2> (B >= 256) gave outputs 1e-7 apart and a recording's track depended on
+// how it was chunked (test_gpu_gru_variants.py, 300x8x256).  The chain below is spelled out — in the order the register-resident
+// instantiations already had, so their results are unchanged — and every instantiation sums the same groups of four in the same
+// k order: the forward of a row is bitwise the same whatever the batch tile and the weight placement.
+__device__ __forceinline__ float gru_dot4(float w0, float w1, float w2, float w3, const f32x4& h) {
+    return fmaf(w3, h[3], fmaf(w2, h[2], fmaf(w0, h[0], w1 * h[1])));
+}
+
 // Where a thread's gate row of W_hh lives.  HTOT == HREG: all of it in registers (H <= 128).  HREG == 0: all of it streamed
 // from L2 every step (any H).  Otherwise (round 4, H = 256): the first HREG weights in registers, the next HLDS in LDS (loaded
 // once; [j][3H], a thread reads its own column: conflict-free), the remaining HTOT - HREG - HLDS streamed.  At H = 256 the
@@ -98,7 +109,7 @@ __global__ __launch_bounds__(gru_nt(HTOT)) void gru_seq_fwd_k(
 #pragma unroll
                     for (int b = 0; b < GRU_BT; ++b) {
                         f32x4 hv = *(const f32x4*)(h_s + b * H + k);
-                        acc[b] += wreg[k] * hv[0] + wreg[k + 1] * hv[1] + wreg[k + 2] * hv[2] + wreg[k + 3] * hv[3];
+                        acc[b] += gru_dot4(wreg[k], wreg[k + 1], wreg[k + 2], wreg[k + 3], hv);
                     }
                 }
             }
@@ -109,7 +120,7 @@ __global__ __launch_bounds__(gru_nt(HTOT)) void gru_seq_fwd_k(
 #pragma unroll
                     for (int b = 0; b < GRU_BT; ++b) {
                         f32x4 hv = *(const f32x4*)(h_s + b * H + HREG + j);
-                        acc[b] += w0 * hv[0] + w1 * hv[1] + w2 * hv[2] + w3 * hv[3];
+                        acc[b] += gru_dot4(w0, w1, w2, w3, hv);
                     }
                 }
             }
@@ -120,7 +131,7 @@ __global__ __launch_bounds__(gru_nt(HTOT)) void gru_seq_fwd_k(
 #pragma unroll
                     for (int b = 0; b < GRU_BT; ++b) {
                         f32x4 hv = *(const f32x4*)(h_s + b * H + k);
-                        acc[b] += w0 * hv[0] + w1 * hv[1] + w2 * hv[2] + w3 * hv[3];
+                        acc[b] += gru_dot4(w0, w1, w2, w3, hv);
                     }
                 }
             }
@@ -318,23 +329,41 @@ static int gru_threads(int H) { return ((3 * H + 63) / 64) * 64; }
 
 extern "C" size_t sed_gru_seq_workspace_bytes(int H) { return (size_t)2 * 3 * H * H * sizeof(float); }
 
+// Which instantiation a (B, H) call runs: the batch tile, how many weights of a gate row sit in registers (H: all of them,
+// 0: none, every step streams the row from L2) and how many in LDS (> 0: the H = 256 hybrid).  GRU_DISPATCH launches from
+// this and sed_gru_seq_variant reports it, so the two cannot drift apart.  hyb_hreg: the hybrid's register share (the
+// forward kernel keeps GRU_HR_FWD, the backward GRU_HR).
+struct GruVariant { int bt, hreg, hlds; };
+static inline GruVariant gru_variant(int H, int B, int hyb_hreg) {
+    const int bt = gru_bt(H, B);
+    if (H == 8 || H == 16 || H == 32 || H == 64 || H == 128) return {bt, H, 0};
+    if (H == 256 && bt == 1) return {bt, hyb_hreg, GRU_HL};
+    return {bt, 0, 0};
+}
+
+extern "C" int sed_gru_seq_variant(int B, int H, int* bt, int* hreg, int* hlds) {
+    SED_REQUIRE(bt && hreg && hlds, "gru_seq_variant: null pointer");
+    SED_REQUIRE(B > 0 && H > 0 && H % 4 == 0 && 3 * H <= 1024, "gru_seq_variant: H=%d must be a multiple of 4 and <= 341", H);
+    const GruVariant v = gru_variant(H, B, GRU_HR_FWD);
+    *bt = v.bt; *hreg = v.hreg; *hlds = v.hlds;
+    return 0;
+}
+
 #define GRU_BT3(HR, KERNEL, ...)                                                              \
-    if (bt == 1) KERNEL<HR, 1><<<grid, nt, lds, s>>>(__VA_ARGS__);                            \
-    else if (bt == 2) KERNEL<HR, 2><<<grid, nt, lds, s>>>(__VA_ARGS__);                       \
+    if (v.bt == 1) KERNEL<HR, 1><<<grid, nt, lds, s>>>(__VA_ARGS__);                          \
+    else if (v.bt == 2) KERNEL<HR, 2><<<grid, nt, lds, s>>>(__VA_ARGS__);                     \
     else KERNEL<HR, 4><<<grid, nt, lds, s>>>(__VA_ARGS__)
 #define GRU_DISPATCH(KERNEL, ...)                                                             \
-    switch (H) {                                                                              \
+    if (v.hlds > 0) {                                                                         \
+        KERNEL<GRU_HRX, 1, 256, GRU_HL><<<grid, nt, lds + (size_t)GRU_HL * 768 * sizeof(float), s>>>(__VA_ARGS__); \
+    } else switch (v.hreg) {                                                                  \
         case 8: GRU_BT3(8, KERNEL, __VA_ARGS__); break;                                       \
         case 16: GRU_BT3(16, KERNEL, __VA_ARGS__); break;                                     \
         case 32: GRU_BT3(32, KERNEL, __VA_ARGS__); break;                                     \
         case 64: GRU_BT3(64, KERNEL, __VA_ARGS__); break;                                     \
         case 128:                                                                             \
-            if (bt == 1) KERNEL<128, 1><<<grid, nt, lds, s>>>(__VA_ARGS__);                   \
+            if (v.bt == 1) KERNEL<128, 1><<<grid, nt, lds, s>>>(__VA_ARGS__);                 \
             else KERNEL<128, 2><<<grid, nt, lds, s>>>(__VA_ARGS__);                           \
-            break;                                                                            \
-        case 256:                                                                             \
-            if (bt == 1) { hyb = 1; KERNEL<GRU_HRX, 1, 256, GRU_HL><<<grid, nt, lds + (size_t)GRU_HL * 768 * sizeof(float), s>>>(__VA_ARGS__); } \
-            else { GRU_BT3(0, KERNEL, __VA_ARGS__); }                                         \
             break;                                                                            \
         default: GRU_BT3(0, KERNEL, __VA_ARGS__); break;                                      \
     }
@@ -348,18 +377,16 @@ extern "C" int sed_gru_seq_fwd(const float* gi, const float* const* whh, const f
     int n = 2 * 3 * H * H;
     gru_pack_whh_t_k<<<cdiv(n, 256), 256, 0, s>>>(whh[0], whh[1], wt, H);
     SED_LAUNCH_CHECK("gru_pack_whh_t");
-    const int bt = gru_bt(H, B);
-    dim3 grid(cdiv(B, bt), 2);
+    const GruVariant v = gru_variant(H, B, GRU_HR_FWD);
+    dim3 grid(cdiv(B, v.bt), 2);
     int nt = gru_threads(H);
-    size_t lds = (size_t)bt * 4 * H * sizeof(float);
+    size_t lds = (size_t)v.bt * 4 * H * sizeof(float);
     SedProfScope prof(SED_K_GRU_FWD, s, 2.0 * 2 * B * (double)T * 3 * H * H);
-    int hyb = 0;
-    if (H == 256 && bt == 1)
+    if (v.hlds > 0)
         (void)hipFuncSetAttribute((const void*)gru_seq_fwd_k<GRU_HR_FWD, 1, 256, GRU_HL>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 #define GRU_HRX GRU_HR_FWD
     GRU_DISPATCH(gru_seq_fwd_k, gi, wt, bhh[0], bhh[1], out, saved, B, T, H);
 #undef GRU_HRX
-    (void)hyb;
     SED_LAUNCH_CHECK("gru_seq_fwd");
     return 0;
 }
@@ -375,21 +402,19 @@ extern "C" int sed_gru_seq_bwd(const float* dout, const float* saved, const floa
     float* bpart = want_bias ? (float*)workspace : nullptr;
     SED_REQUIRE(B > 0 && T > 0 && H > 0 && H % 4 == 0 && 3 * H <= 1024, "gru_seq_bwd: H=%d must be a multiple of 4 and <= 341", H);
     hipStream_t s = as_stream(stream);
-    const int bt = gru_bt(H, B);
-    dim3 grid(cdiv(B, bt), 2);
+    const GruVariant v = gru_variant(H, B, GRU_HR);
+    dim3 grid(cdiv(B, v.bt), 2);
     int nt = gru_threads(H);
-    size_t lds = (size_t)bt * 6 * H * sizeof(float);
+    size_t lds = (size_t)v.bt * 6 * H * sizeof(float);
     SedProfScope prof(SED_K_GRU_BWD, s, 2.0 * 2 * B * (double)T * 3 * H * H);
-    int hyb = 0;
-    if (H == 256 && bt == 1)
+    if (v.hlds > 0)
         (void)hipFuncSetAttribute((const void*)gru_seq_bwd_k<GRU_HR, 1, 256, GRU_HL>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 #define GRU_HRX GRU_HR
     GRU_DISPATCH(gru_seq_bwd_k, dout, saved, whh[0], whh[1], dgi, dgh, bpart, B, T, H);
 #undef GRU_HRX
-    (void)hyb;
     SED_LAUNCH_CHECK("gru_seq_bwd");
     if (want_bias) {
-        gru_bias_grad_k<<<cdiv(8 * H, 256), 256, 0, s>>>(bpart, cdiv(B, bt), H, dbih[0], dbih[1], dbhh[0], dbhh[1]);
+        gru_bias_grad_k<<<cdiv(8 * H, 256), 256, 0, s>>>(bpart, cdiv(B, v.bt), H, dbih[0], dbih[1], dbhh[0], dbhh[1]);
         SED_LAUNCH_CHECK("gru_bias_grad");
     }
     return 0;

@@ -324,6 +324,14 @@ def gru_seq_bwd(dout, saved, whh, want_bias=False):
     return dgi, dgh, dbih, dbhh
 
 
+def gru_seq_variant(B, H):
+    """-> (bt, hreg, hlds): the batch tile and the weight placement gru_seq_fwd / gru_seq_bwd use for a [B,T,...] call
+    (hreg == H: a gate row in registers, hreg == 0: streamed from L2, hlds > 0: the H = 256 registers + LDS + L2 hybrid)"""
+    bt, hreg, hlds = C.c_int(), C.c_int(), C.c_int()
+    check(lib().sed_gru_seq_variant(B, H, C.byref(bt), C.byref(hreg), C.byref(hlds)), "gru_seq_variant")
+    return bt.value, hreg.value, hlds.value
+
+
 def loss_fwd_bwd(logits, targets, kind="bce", alpha=0.25, gamma=2.0, reduction="mean"):
     """-> (loss scalar tensor, dlogits, probs)"""
     if kind not in ("bce", "focal"):

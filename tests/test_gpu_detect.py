@@ -256,6 +256,72 @@ def test_chunking_is_bitwise_invariant(sed):
         assert torch.equal(a.events[k], b.events[k]), k
 
 
+LONG_N = 20_500           # 639 windows on the hop grid and the end-aligned one: 640
+LONG_CHUNKS = (7, 255, 256, 1024)
+
+
+def test_chunking_is_bitwise_invariant_across_the_gru_batch_tiles(sed):
+    """a recording of 640 windows through the Lightning net: max_batch = 1024 runs the GRU's four-row tile (one chunk of 640),
+    256 the two-row tile (256, 256) and tile 1 (128), 255 and 7 tile 1 only.  The input projections have K = 640 < 1024, so no
+    chunk takes a split-K plan: tracks and events must be bitwise the same whatever the chunking."""
+    r, m = _nets(sed, "lightning", seed=5)
+    mel_h = _features(LONG_N, seed=6)
+    _centre_on_threshold(r, m, mel_h)
+    mel = torch.from_numpy(mel_h).cuda()
+    res = [sed.EventDetector(m, max_batch=mb, min_gap=1).from_features(mel) for mb in LONG_CHUNKS]
+    assert res[0].plan.n_win == 640 and len(res[0]) > 0
+    for mb, b in zip(LONG_CHUNKS[1:], res[1:]):
+        assert torch.equal(res[0].probs, b.probs), f"max_batch 7 vs {mb}: max |dp| {(res[0].probs - b.probs).abs().max().item():.2e}"
+        for k in b.events:
+            assert torch.equal(res[0].events[k], b.events[k]), (mb, k)
+
+
+def test_chunking_of_the_128_channel_net_is_invariant_to_rounding_and_bitwise_between_large_chunks(sed):
+    """the 128-channel net's first input projection has K = 5120: a chunk of at most 56 windows (M = 8 rows per window, fewer
+    than 96 64x64 output blocks) sums K in up to 21 slices, a larger one in two (csrc/gemm.hip, gemm_plan policy 1), so the
+    logits depend on the chunk size by rounding — DESIGN 2 bounds that by 2e-6, asserted here between every two of
+    max_batch = 7, 255, 256, 1024.  The recording has 640 windows so that the chunks of 255 (255, 255, 130), of 256 (256, 256,
+    128) and of 1024 (640) all have at least 57 windows, the last one included: those three run one GEMM plan and differ in
+    the GRU batch tile alone (1; 2 and 1; 2), and their logits, tracks and events must be bitwise equal.  max_batch = 7 ends in
+    a chunk of 3 and is held to the 2e-6 only; its events must agree wherever the track is further than 1e-5 from the threshold."""
+    from oracle import crnn_ref
+    kw = dict(conv_channels=128, dropout=0.0, gru_hidden=128)
+    r, m = crnn_ref.SedNetRef(**kw), sed.TimePooledCRNN(**kw)
+    sd = crnn_ref.rs_state_dict(r, 5)
+    r.load_state_dict(sd)
+    m.load_state_dict(sd)
+    r.eval()
+    m.cuda().eval()
+    mel_h = _features(LONG_N, seed=6)
+    _centre_on_threshold(r, m, mel_h)
+    mel = torch.from_numpy(mel_h).cuda()
+    dets = [sed.EventDetector(m, max_batch=mb) for mb in LONG_CHUNKS]
+    plan = dets[0]._prepare(mel)[1]
+    assert plan.n_win == 640
+    for mb in (255, 256, 1024):
+        assert min(min(mb, plan.n_win - b0) for b0 in range(0, plan.n_win, mb)) >= 57
+    with torch.no_grad():
+        logits = [d.window_logits(mel, plan) for d in dets]
+    res = [d.from_features(mel) for d in dets]
+    worst = 0.0
+    for i in range(len(dets)):
+        for j in range(i + 1, len(dets)):
+            d = (logits[i] - logits[j]).abs().max().item()
+            worst = max(worst, d)
+            print(f"128-channel net, max_batch {LONG_CHUNKS[i]} vs {LONG_CHUNKS[j]}: max |dlogit| {d:.2e}")
+            assert d <= 2e-6, (LONG_CHUNKS[i], LONG_CHUNKS[j], d)
+    assert worst > 0, "max_batch = 7 must take the many-slice projection (did the GEMM plan change?)"
+    for i in (2, 3):                                            # 256 and 1024 against 255
+        assert torch.equal(logits[1], logits[i]), (LONG_CHUNKS[i], (logits[1] - logits[i]).abs().max().item())
+        assert torch.equal(res[1].probs, res[i].probs)
+        for k in res[1].events:
+            assert torch.equal(res[1].events[k], res[i].events[k]), (LONG_CHUNKS[i], k)
+    p = res[1].probs.cpu().numpy()
+    sure = np.abs(p - np.float32(0.5)) > 1e-5
+    masks = [ref.event_mask({k: v.cpu().numpy() for k, v in x.events.items()}, plan.n_out, 1) for x in res]
+    assert np.array_equal(masks[0][sure], masks[1][sure]) and 0 < masks[1].sum() < masks[1].size
+
+
 @pytest.mark.parametrize("N", [8, 15, 50, 63])
 def test_short_recordings_run_as_one_sequence(sed, N):
     r, m = _nets(sed, "lightning", seed=7)

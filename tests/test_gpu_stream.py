@@ -348,6 +348,34 @@ def test_stream_end_to_end_equals_the_offline_detector(sed, which):
         _assert_events_equal(evs2[s], {k: v.cpu().numpy() for k, v in det.decode(tracks2[s]).items()}, f"at once {s}")
 
 
+def test_1024_feeds_pushed_together_equal_the_offline_detector(sed):
+    """the README's live-stream headline: 1024 feeds per push.  Every push hands the eval forward a few thousand windows, which
+    run in chunks of max_batch = 1024 — the GRU's four-row batch tile, which nothing smaller reaches.  Feeds of 200..499 feature
+    frames (every length different from its neighbours'), pushed in three calls and a flush; 16 sampled feeds (the first, the
+    last and 14 spread between) against the offline detector on the same features, the final frame count of all 1024."""
+    S = 1024
+    r, m = _nets(sed, "lightning", seed=21)
+    lengths = [200 + (s * 37) % 300 for s in range(S)]
+    mels = [_features(N, seed=500 + s) for s, N in enumerate(lengths)]
+    _centre_on_threshold(r, m, _features(10_007, seed=30))
+    det = sed.EventDetector(m, median=3)
+    assert det.max_batch == 1024
+    st = det.stream(n_streams=S, keep_probs=True)
+    outs = _push_all(st, lambda s: mels[s], [200, 150, 300], st.push_features)
+    assert len(outs) <= 4                                            # three pushes at the most, and the flush
+    assert outs[-1].final_frames == [N // 8 for N in lengths]
+    tracks, evs = _collect(outs, S)
+    sample = sorted({0, S - 1} | {(s * 73 + 5) % S for s in range(14)})
+    assert len(sample) == 16
+    n = 0
+    for s in sample:
+        one = det.from_features(torch.from_numpy(mels[s]).cuda())
+        _check_against_offline(det, tracks[s], evs[s], one, f"1024 feeds, feed {s} ({lengths[s]} frames)")
+        n += len(evs[s]["cls"])
+    assert n > 0
+    assert all(t.shape[0] == N // 8 for t, N in zip(tracks, lengths))
+
+
 def test_stream_is_bitwise_the_offline_track_at_the_same_chunk_sizes(sed):
     """one stream pushed one window hop at a time runs every window at batch 1, like the offline detector with max_batch=1"""
     r, m = _nets(sed, "lightning", seed=4)
