@@ -47,12 +47,7 @@ extern "C" int sed_detect_stitch(const float* logits, long n_win, int win_out, i
                     n_out <= 0x7fffffffL && n_win <= 0x7fffffffL && (long)n_out * K <= 0x7fffffffL,
                 "detect_stitch: bad sizes (n_win=%ld, win_out=%d, K=%d, hop_out=%d, n_out=%ld)", n_win, win_out, K, hop_out, n_out);
     SED_REQUIRE(combine == 0 || combine == 1, "detect_stitch: combine must be 0 (mean) or 1 (max), got %d", combine);
-    SED_REQUIRE(last_start_out + win_out == n_out, "detect_stitch: the last window must end at the recording's end");
-    // start(w) = min(w hop, last): the last window starts at `last`, every earlier one strictly before it
-    SED_REQUIRE((n_win - 1) * (long)hop_out >= last_start_out && (n_win < 2 || (n_win - 2) * (long)hop_out < last_start_out),
-                "detect_stitch: last_start_out=%ld is not the last start of a %ld-window grid with hop %d", last_start_out, n_win, hop_out);
-    SED_REQUIRE(trim >= 0 && (n_win == 1 || hop_out + 2L * trim <= win_out),
-                "detect_stitch: trim=%d leaves output frames uncovered (hop_out=%d, win_out=%d)", trim, hop_out, win_out);
+    SED_TRY(detect_check_grid("detect_stitch", -1, n_win, win_out, hop_out, last_start_out, n_out, trim));
     const long total = n_out * K;
     long nb = (total + 255) / 256;
     detect_stitch_k<<<(unsigned)(nb < 8192 ? nb : 8192), 256, 0, as_stream(stream)>>>(
@@ -76,7 +71,7 @@ __global__ __launch_bounds__(256) void detect_bits_k(const float* __restrict__ p
     const long j = (long)blockIdx.x * 256 + threadIdx.x;
     bool on = false, high = false;
     if (j < n_out) {
-        const float p = median_nearest<M>(probs, (int)j, k, K, n_out);
+        const float p = median_nearest<M>(LinearRows{probs, K}, (int)j, k, n_out - 1);
         on = p > lo;
         high = p > hi;
     }
@@ -89,7 +84,7 @@ __global__ __launch_bounds__(256) void detect_bits_k(const float* __restrict__ p
 }
 
 // Batched (SEG, sed_detect_events_batch): one wave per (recording r, class k), workgroup r*K + k; recording r's bit tracks
-// are [K][n_words_r] at word K*word_off[r] (every track starts on a word boundary), so no run, gap or event crosses recordings.
+// are [K][n_words_r] at word K*word_off[r] (detect_bits_seg_k), so no run, gap or event crosses recordings.
 // The walk itself is detect_walk_body of detect_shared.h (shared with the decoder sweep of tune.hip); here every finished event
 // is counted and, in the write pass, stored.
 struct DetectEmit {
@@ -179,12 +174,6 @@ extern "C" size_t sed_detect_workspace_bytes(long n_out, int K, int max_events) 
     return (size_t)2 * K * detect_words(n_out) * sizeof(unsigned long long) + (size_t)2 * K * sizeof(int);
 }
 
-template <int M>
-static void launch_bits(const float* probs, int n_out, int K, long n_words, float lo, float hi, unsigned long long* ob,
-                        unsigned long long* hb, hipStream_t s) {
-    detect_bits_k<M><<<dim3((unsigned)cdiv(n_words * 64, 256), (unsigned)K), 256, 0, s>>>(probs, n_out, K, n_words, lo, hi, ob, hb);
-}
-
 extern "C" int sed_detect_events(const float* probs, long n_out, int K, int median, float lo, float hi, int min_gap, int min_len,
                                  int max_events, void* workspace, size_t workspace_bytes, int* cls, int* onset, int* offset,
                                  float* peak, int* peak_frame, int* count, void* stream) {
@@ -192,9 +181,7 @@ extern "C" int sed_detect_events(const float* probs, long n_out, int K, int medi
     const size_t need = sed_detect_workspace_bytes(n_out, K, max_events);
     SED_REQUIRE(need > 0, "detect_events: bad sizes (n_out=%ld, K=%d in 1..32, max_events=%d >= 0)", n_out, K, max_events);
     SED_REQUIRE(workspace_bytes >= need, "detect_events: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-    SED_REQUIRE(median >= 1 && median <= 31 && (median & 1), "detect_events: median width must be odd, 1..31 (got %d)", median);
-    SED_REQUIRE(hi >= lo, "detect_events: need hi >= lo (got lo=%g, hi=%g)", (double)lo, (double)hi);
-    SED_REQUIRE(min_gap >= 0 && min_len >= 1, "detect_events: min_gap >= 0 and min_len >= 1 (got %d, %d)", min_gap, min_len);
+    SED_TRY(detect_check_decoder("detect_events", -1, median, lo, hi, min_gap, min_len));
     SED_REQUIRE(max_events == 0 || (cls && onset && offset && peak && peak_frame), "detect_events: null output pointer");
     hipStream_t s = as_stream(stream);
     const long nw = detect_words(n_out);
@@ -202,12 +189,10 @@ extern "C" int sed_detect_events(const float* probs, long n_out, int K, int medi
     unsigned long long* hb = ob + (size_t)K * nw;
     int* counts = (int*)(hb + (size_t)K * nw);
     int* offs = counts + K;
-    switch (median) {
-#define DETECT_MED(m) case m: launch_bits<m>(probs, (int)n_out, K, nw, lo, hi, ob, hb, s); break;
-        DETECT_MED(1) DETECT_MED(3) DETECT_MED(5) DETECT_MED(7) DETECT_MED(9) DETECT_MED(11) DETECT_MED(13) DETECT_MED(15)
-        DETECT_MED(17) DETECT_MED(19) DETECT_MED(21) DETECT_MED(23) DETECT_MED(25) DETECT_MED(27) DETECT_MED(29) DETECT_MED(31)
-#undef DETECT_MED
-    }
+    detect_with_median(median, [&](auto m) {
+        detect_bits_k<decltype(m)::value><<<dim3((unsigned)cdiv(nw * 64, 256), (unsigned)K), 256, 0, s>>>(probs, (int)n_out, K, nw, lo, hi, ob,
+                                                                                                   hb);
+    });
     SED_LAUNCH_CHECK("detect_bits");
     detect_walk_k<<<K, 64, 0, s>>>(ob, hb, nw, min_gap, min_len, 0, max_events, counts, offs, cls, onset, offset);
     SED_LAUNCH_CHECK("detect_walk(count)");
@@ -222,36 +207,11 @@ extern "C" int sed_detect_events(const float* probs, long n_out, int K, int medi
 }
 
 // ───────────────────────── batch: R recordings packed back to back ─────────────────────────
-// Phase 1 of the batch: one wave per (packed word, class).  A wave's 64 frames are one word of one recording's track (tracks
-// start on word boundaries), so the recording is wave-uniform; the median clamps at that recording's own ends.
-template <int M>
-__global__ __launch_bounds__(256) void detect_bits_batch_k(const float* __restrict__ probs, const int* __restrict__ out_off,
-                                                           const int* __restrict__ word_off, int R, int K, float lo, float hi,
-                                                           unsigned long long* __restrict__ on_bits,
-                                                           unsigned long long* __restrict__ hi_bits) {
-    const int k = blockIdx.y, lane = threadIdx.x & 63;
-    const int gw = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (gw >= word_off[R]) return;                                    // wave-uniform
-    const int r = __builtin_amdgcn_readfirstlane(find_seg(word_off, R, gw));
-    const int n_out = out_off[r + 1] - out_off[r], nw = word_off[r + 1] - word_off[r], lw = gw - word_off[r];
-    const int j = lw * 64 + lane;
-    bool on = false, high = false;
-    if (j < n_out) {
-        const float p = median_nearest<M>(probs + (size_t)out_off[r] * K, j, k, K, n_out);
-        on = p > lo;
-        high = p > hi;
-    }
-    const unsigned long long bo = __ballot(on), bh = __ballot(high);
-    if (lane == 0) {
-        const size_t at = (size_t)K * word_off[r] + (size_t)k * nw + lw;
-        on_bits[at] = bo;
-        hi_bits[at] = bh;
-    }
-}
-
+// Phase 1 of the batch is detect_bits_seg_k of detect_shared.h (shared with the decoder sweep) with the two thresholds lo, hi:
+// track 0 = on, track 1 = high.
+//
 // workspace of the batch entries (16-byte aligned regions): the stitch's DetRec [R] and output offsets [R+1]; the decoder's output
 // and word offsets [R+1] each, counts [R*K], offsets [R*K]; then the two bit tracks [K][words], words <= n_total/64 + R
-static inline size_t al16(size_t b) { return (b + 15) & ~(size_t)15; }
 struct DetBatchWs {
     DetRec* recs; int* s_out_off; int* out_off; int* word_off; int* counts; int* offs; unsigned long long* ob; unsigned long long* hb;
 };
@@ -276,12 +236,6 @@ extern "C" size_t sed_detect_batch_workspace_bytes(long n_total, int K, int R, i
            (size_t)2 * K * words * sizeof(unsigned long long);
 }
 
-static int det_upload(void* dst, const void* src, size_t bytes, hipStream_t s, const char* what) {
-    const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) { sed_set_error("%s: upload of the recording table: %s", what, hipGetErrorString(e)); return (int)e; }
-    return 0;
-}
-
 extern "C" int sed_detect_stitch_batch(const float* logits, long logits_len, const long* recs_host, int R, int K, int combine, int trim,
                                        float* probs, long n_total, void* workspace, size_t workspace_bytes, void* stream) {
     SED_REQUIRE(logits && recs_host && probs && workspace, "detect_stitch_batch: null pointer");
@@ -302,13 +256,7 @@ extern "C" int sed_detect_stitch_batch(const float* logits, long logits_len, con
                         win_out <= 0x7fffffffL && hop_out <= 0x7fffffffL && n_out <= n_total,
                     "detect_stitch_batch: recording %d: bad sizes (n_win=%ld, win_out=%ld, hop_out=%ld, n_out=%ld)", r, n_win, win_out,
                     hop_out, n_out);
-        SED_REQUIRE(last + win_out == n_out, "detect_stitch_batch: recording %d: the last window must end at the recording's end", r);
-        SED_REQUIRE((n_win - 1) * hop_out >= last && (n_win < 2 || (n_win - 2) * hop_out < last),
-                    "detect_stitch_batch: recording %d: last_start_out=%ld is not the last start of a %ld-window grid with hop %ld", r,
-                    last, n_win, hop_out);
-        SED_REQUIRE(n_win == 1 || hop_out + 2L * trim <= win_out,
-                    "detect_stitch_batch: recording %d: trim=%d leaves output frames uncovered (hop_out=%ld, win_out=%ld)", r, trim,
-                    hop_out, win_out);
+        SED_TRY(detect_check_grid("detect_stitch_batch", r, n_win, win_out, hop_out, last, n_out, trim));
         // the logits [n_win][win_out][K] of the recording: inside the buffer (overlaps are checked below)
         SED_REQUIRE(lo >= 0 && lo <= logits_len && n_win * win_out <= (logits_len - lo) / K,
                     "detect_stitch_batch: recording %d: logits [%ld, +%ld x %ld x %d) leave the buffer of %ld floats", r, lo, n_win,
@@ -326,19 +274,13 @@ extern "C" int sed_detect_stitch_batch(const float* logits, long logits_len, con
     off[R] = (int)rows;
     hipStream_t s = as_stream(stream);
     const DetBatchWs w = det_batch_layout(workspace, R, K, n_total / 64 + R);
-    if (int rc = det_upload(w.recs, h.data(), (size_t)R * sizeof(DetRec), s, "detect_stitch_batch")) return rc;
-    if (int rc = det_upload(w.s_out_off, off.data(), (size_t)(R + 1) * 4, s, "detect_stitch_batch")) return rc;
+    SED_TRY(detect_upload("detect_stitch_batch", w.recs, h.data(), (size_t)R * sizeof(DetRec), s));
+    SED_TRY(detect_upload("detect_stitch_batch", w.s_out_off, off.data(), (size_t)(R + 1) * 4, s));
     const long nb = (n_total * K + 255) / 256;
     detect_stitch_batch_k<<<(unsigned)(nb < 8192 ? nb : 8192), 256, 0, s>>>(logits, w.recs, w.s_out_off, R, n_total, K, combine, trim,
                                                                               probs);
     SED_LAUNCH_CHECK("detect_stitch_batch");
     return 0;
-}
-
-template <int M>
-static void launch_bits_batch(const float* probs, const int* out_off, const int* word_off, int R, int K, long words, float lo,
-                              float hi, unsigned long long* ob, unsigned long long* hb, hipStream_t s) {
-    detect_bits_batch_k<M><<<dim3((unsigned)cdiv(words, 4), (unsigned)K), 256, 0, s>>>(probs, out_off, word_off, R, K, lo, hi, ob, hb);
 }
 
 extern "C" int sed_detect_events_batch(const float* probs, const long* n_out_host, int R, int K, int median, float lo, float hi,
@@ -347,37 +289,19 @@ extern "C" int sed_detect_events_batch(const float* probs, const long* n_out_hos
     SED_REQUIRE(probs && n_out_host && workspace && event_off, "detect_events_batch: null pointer");
     SED_REQUIRE(R >= 1 && K >= 1 && K <= 32 && max_events >= 0, "detect_events_batch: bad sizes (R=%d, K=%d in 1..32, max_events=%d)",
                 R, K, max_events);
-    SED_REQUIRE(median >= 1 && median <= 31 && (median & 1), "detect_events_batch: median width must be odd, 1..31 (got %d)", median);
-    SED_REQUIRE(hi >= lo, "detect_events_batch: need hi >= lo (got lo=%g, hi=%g)", (double)lo, (double)hi);
-    SED_REQUIRE(min_gap >= 0 && min_len >= 1, "detect_events_batch: min_gap >= 0 and min_len >= 1 (got %d, %d)", min_gap, min_len);
+    SED_TRY(detect_check_decoder("detect_events_batch", -1, median, lo, hi, min_gap, min_len));
     SED_REQUIRE(max_events == 0 || (rec && cls && onset && offset && peak && peak_frame), "detect_events_batch: null output pointer");
-    std::vector<int> h(2 * (size_t)(R + 1));
-    int *out_off = h.data(), *word_off = out_off + R + 1;
-    long rows = 0, words = 0;
-    for (int r = 0; r < R; ++r) {
-        const long n = n_out_host[r];
-        SED_REQUIRE(n >= 1 && n <= 0x7fffffffL - rows, "detect_events_batch: recording %d has %ld output frames", r, n);
-        out_off[r] = (int)rows;
-        word_off[r] = (int)words;
-        rows += n;
-        words += detect_words(n);
-        SED_REQUIRE(rows * K <= 0x7fffffffL, "detect_events_batch: more than 2^31 - 1 (frame, class) cells in one batch");
-    }
-    out_off[R] = (int)rows;
-    word_off[R] = (int)words;
+    std::vector<int> h(2 * (size_t)(R + 1));                          // out_off [R+1] then word_off [R+1]
+    long rows, words;
+    SED_TRY(detect_seg_tables("detect_events_batch", n_out_host, R, K, h.data(), h.data() + R + 1, &rows, &words));
     const size_t need = sed_detect_batch_workspace_bytes(rows, K, R, max_events);
     SED_REQUIRE(need > 0, "detect_events_batch: bad sizes (R=%d, K=%d, %ld output frames)", R, K, rows);
     SED_REQUIRE(workspace_bytes >= need, "detect_events_batch: workspace of %zu bytes, %zu needed", workspace_bytes, need);
     hipStream_t s = as_stream(stream);
     const DetBatchWs w = det_batch_layout(workspace, R, K, rows / 64 + R);
-    if (int rc = det_upload(w.out_off, h.data(), h.size() * 4, s, "detect_events_batch")) return rc;
-    switch (median) {
-#define DETECT_MED(m) case m: launch_bits_batch<m>(probs, w.out_off, w.word_off, R, K, words, lo, hi, w.ob, w.hb, s); break;
-        DETECT_MED(1) DETECT_MED(3) DETECT_MED(5) DETECT_MED(7) DETECT_MED(9) DETECT_MED(11) DETECT_MED(13) DETECT_MED(15)
-        DETECT_MED(17) DETECT_MED(19) DETECT_MED(21) DETECT_MED(23) DETECT_MED(25) DETECT_MED(27) DETECT_MED(29) DETECT_MED(31)
-#undef DETECT_MED
-    }
-    SED_LAUNCH_CHECK("detect_bits_batch");
+    SED_TRY(detect_upload("detect_events_batch", w.out_off, h.data(), h.size() * 4, s));
+    launch_bits_seg(median, probs, w.out_off, w.word_off, R, K, words, TwoThresholds{lo, hi}, (size_t)(w.hb - w.ob), w.ob, s);
+    SED_LAUNCH_CHECK("detect_bits_seg");
     const unsigned groups = (unsigned)((long)R * K);
     detect_walk_k<true><<<groups, 64, 0, s>>>(w.ob, w.hb, 0, min_gap, min_len, 0, max_events, w.counts, w.offs, cls, onset, offset,
                                              w.word_off, K, rec);

@@ -1,13 +1,93 @@
-// detect_shared.h — device code shared by the offline detector (detect.hip), the streaming step (stream.hip) and the decoder
-// sweep (tune.hip): the stitch of one (output frame, class) cell, the exclusive scan of per-(segment, class) event counts, the
-// median by selection and the edge walk of the event decoder.  The files call the SAME functions, so a streamed track row is
-// bit for bit the row sed_detect_stitch writes, and the events a sweep scores are the events sed_detect_events_batch writes.
+// detect_shared.h — what the offline detector (detect.hip), the streaming step (stream.hip) and the decoder sweep (tune.hip)
+// share.  Device code: the stitch of one (output frame, class) cell, the median by selection, the segmented bit-track kernel,
+// the edge walk of the event decoder and the exclusive scan of per-(segment, class) event counts.  The files call the SAME
+// functions, so a streamed track row is bit for bit the row sed_detect_stitch writes, a streamed filtered frame is the frame the
+// offline decoder thresholds, and the events a sweep scores are the events sed_detect_events_batch writes.  Host code: the
+// checks that several entries make (decoder settings, window grid, segment tables), the table upload and the dispatch from a
+// runtime median width to its instantiation.
 #pragma once
+#include <type_traits>
 #include "common.h"
 
 // 64-bit words of one bit track of n_out frames: the extra word holds the fall edge of a run that reaches the end
 static inline long detect_words(long n_out) { return n_out / 64 + 1; }
+static inline size_t al16(size_t b) { return (b + 15) & ~(size_t)15; }
 
+// ───────────────────────── host: checks, upload, width dispatch ─────────────────────────
+// Every check takes the entry's name for the message prefix and returns the error code (SED_TRY); none of them touches HIP.
+
+// the message prefix "entry" or, with an index i >= 0, "entry: what i"; called only when a check fails
+static const char* detect_who(const char* entry, const char* what, long i) {
+    static thread_local char s[96];
+    if (i >= 0) snprintf(s, sizeof s, "%s: %s %ld", entry, what, i);
+    return i >= 0 ? s : entry;
+}
+
+// the decoder's settings; setting >= 0: the index of the setting in a sweep
+static int detect_check_decoder(const char* entry, long setting, int median, float lo, float hi, int min_gap, int min_len) {
+    const auto who = [&] { return detect_who(entry, "setting", setting); };
+    SED_REQUIRE(median >= 1 && median <= 31 && (median & 1), "%s: median width must be odd, 1..31 (got %d)", who(), median);
+    SED_REQUIRE(hi >= lo, "%s: need hi >= lo (got lo=%g, hi=%g)", who(), (double)lo, (double)hi);
+    SED_REQUIRE(min_gap >= 0 && min_len >= 1, "%s: min_gap >= 0 and min_len >= 1 (got %d, %d)", who(), min_gap, min_len);
+    return 0;
+}
+
+// trim output frames dropped at interior window edges must leave every frame covered (one window has no interior edge)
+static int detect_check_trim(const char* entry, long rec, long n_win, long win_out, long hop_out, int trim) {
+    SED_REQUIRE(trim >= 0 && (n_win == 1 || hop_out + 2L * trim <= win_out),
+                "%s: trim=%d leaves output frames uncovered (hop_out=%ld, win_out=%ld)", detect_who(entry, "recording", rec), trim,
+                hop_out, win_out);
+    return 0;
+}
+
+// the window grid of one recording, start(w) = min(w hop_out, last): the last window ends at n_out and starts at `last`, every
+// earlier one strictly before it; rec >= 0: the index of the recording in a batch
+static int detect_check_grid(const char* entry, long rec, long n_win, long win_out, long hop_out, long last, long n_out, int trim) {
+    const auto who = [&] { return detect_who(entry, "recording", rec); };
+    SED_REQUIRE(last + win_out == n_out, "%s: the last window must end at the recording's end", who());
+    SED_REQUIRE((n_win - 1) * hop_out >= last && (n_win < 2 || (n_win - 2) * hop_out < last),
+                "%s: last_start_out=%ld is not the last start of a %ld-window grid with hop %ld", who(), last, n_win, hop_out);
+    return detect_check_trim(entry, rec, n_win, win_out, hop_out, trim);
+}
+
+// n_out_host [R] -> out_off [R+1] (first packed row of every recording) and word_off [R+1] (first word of its bit tracks, per
+// class); *rows and *words receive the totals.  Rows and (frame, class) cells are int32 on the device.
+static int detect_seg_tables(const char* entry, const long* n_out_host, int R, int K, int* out_off, int* word_off, long* rows,
+                             long* words) {
+    *rows = *words = 0;
+    for (int r = 0; r < R; ++r) {
+        const long n = n_out_host[r];
+        SED_REQUIRE(n >= 1 && n <= 0x7fffffffL - *rows, "%s: recording %d has %ld output frames", entry, r, n);
+        out_off[r] = (int)*rows;
+        word_off[r] = (int)*words;
+        *rows += n;
+        *words += detect_words(n);
+        SED_REQUIRE(*rows * K <= 0x7fffffffL, "%s: more than 2^31 - 1 (frame, class) cells in one batch", entry);
+    }
+    out_off[R] = (int)*rows;
+    word_off[R] = (int)*words;
+    return 0;
+}
+
+// a host table into the workspace, in stream order before the kernels that read it
+static int detect_upload(const char* entry, void* dst, const void* src, size_t bytes, hipStream_t s) {
+    const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) { sed_set_error("%s: upload of the host tables: %s", entry, hipGetErrorString(e)); return (int)e; }
+    return 0;
+}
+
+// f(std::integral_constant<int, M>) with M = median, for every width the decoder accepts (detect_check_decoder)
+template <class F>
+static void detect_with_median(int median, F&& f) {
+    switch (median) {
+#define DETECT_MED(m) case m: f(std::integral_constant<int, m>{}); break;
+        DETECT_MED(1) DETECT_MED(3) DETECT_MED(5) DETECT_MED(7) DETECT_MED(9) DETECT_MED(11) DETECT_MED(13) DETECT_MED(15)
+        DETECT_MED(17) DETECT_MED(19) DETECT_MED(21) DETECT_MED(23) DETECT_MED(25) DETECT_MED(27) DETECT_MED(29) DETECT_MED(31)
+#undef DETECT_MED
+    }
+}
+
+// ───────────────────────── device ─────────────────────────
 // last r with off[r] <= x (off[0] = 0 <= x, off ascending)
 __device__ __forceinline__ int find_seg(const int* __restrict__ off, int R, long x) {
     int lo = 0, hi = R - 1;
@@ -19,16 +99,27 @@ __device__ __forceinline__ int find_seg(const int* __restrict__ off, int R, long
     return lo;
 }
 
-// median of the M frames around j of class k, edges 'nearest'; a selection (exact, ties included)
-template <int M>
-__device__ __forceinline__ float median_nearest(const float* __restrict__ probs, int j, int k, int K, int n_out) {
-    if (M == 1) return probs[(size_t)j * K + k];
+// where row t (class 0) of a track lives: rows back to back, or the streaming step's ring of TR rows
+struct LinearRows {
+    const float* base; int K;
+    __device__ __forceinline__ const float* at(int t) const { return base + (size_t)t * K; }
+};
+struct RingRows {
+    const float* base; int TR, K;
+    __device__ __forceinline__ const float* at(int t) const { return base + (size_t)(t % TR) * K; }
+};
+
+// median of the M frames around j of class k, edges 'nearest': the left edge clamps at frame 0, the right one at `last` (the
+// last frame of a finished track; INT_MAX while a stream goes on); a selection (exact, ties included)
+template <int M, class Rows>
+__device__ __forceinline__ float median_nearest(const Rows& rows, int j, int k, int last) {
+    if (M == 1) return rows.at(j)[k];
     float v[M];
 #pragma unroll
     for (int d = 0; d < M; ++d) {
         int t = j + d - M / 2;
-        t = t < 0 ? 0 : (t >= n_out ? n_out - 1 : t);
-        v[d] = probs[(size_t)t * K + k];
+        t = t < 0 ? 0 : (t > last ? last : t);
+        v[d] = rows.at(t)[k];
     }
     float med = v[0];
 #pragma unroll
@@ -39,6 +130,52 @@ __device__ __forceinline__ float median_nearest(const float* __restrict__ probs,
         if (less <= M / 2 && M / 2 < leq) med = v[i];                 // v[i] is the (M/2)-th smallest
     }
     return med;
+}
+
+// The thresholds a bit-track launch compares the filtered value with: the detector's two, by value, or a sweep's list
+struct TwoThresholds {
+    float lo, hi;
+    __device__ __forceinline__ int n() const { return 2; }
+    __device__ __forceinline__ float at(int t) const { return t ? hi : lo; }
+};
+struct ThresholdList {
+    const float* thr; int n_thr;
+    __device__ __forceinline__ int n() const { return n_thr; }
+    __device__ __forceinline__ float at(int t) const { return thr[t]; }
+};
+
+// Bit tracks of R recordings packed back to back (sed_detect_events_batch, sed_tune_sweep): one wave per (packed word, class).
+// A wave's 64 frames are one word of one recording's track (tracks start on word boundaries), so the recording is wave-uniform;
+// the median clamps at that recording's own ends.  The filtered value is computed once and compared with every threshold t:
+// track t = bits + t*track_stride, recording r's words [K][n_words_r] at word K*word_off[r] of it (one spare word per
+// recording), so no run, gap or event crosses recordings.
+template <int M, class Thr>
+__global__ __launch_bounds__(256) void detect_bits_seg_k(const float* __restrict__ probs, const int* __restrict__ out_off,
+                                                         const int* __restrict__ word_off, int R, int K, Thr thr, size_t track_stride,
+                                                         unsigned long long* __restrict__ bits) {
+    const int k = blockIdx.y, lane = threadIdx.x & 63;
+    const int gw = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (gw >= word_off[R]) return;                                    // wave-uniform
+    const int r = __builtin_amdgcn_readfirstlane(find_seg(word_off, R, gw));
+    const int n_out = out_off[r + 1] - out_off[r], nw = word_off[r + 1] - word_off[r], lw = gw - word_off[r];
+    const int j = lw * 64 + lane;
+    const bool in = j < n_out;
+    const float p = in ? median_nearest<M>(LinearRows{probs + (size_t)out_off[r] * K, K}, j, k, n_out - 1) : 0.f;
+    const size_t at = (size_t)K * word_off[r] + (size_t)k * nw + lw;
+    for (int t = 0; t < thr.n(); ++t) {
+        const unsigned long long b = __ballot(in && p > thr.at(t));
+        if (lane == 0) bits[(size_t)t * track_stride + at] = b;
+    }
+}
+
+// words = word_off[R] on the host
+template <class Thr>
+static void launch_bits_seg(int median, const float* probs, const int* out_off, const int* word_off, int R, int K, long words, Thr thr,
+                            size_t track_stride, unsigned long long* bits, hipStream_t s) {
+    detect_with_median(median, [&](auto m) {
+        detect_bits_seg_k<decltype(m)::value><<<dim3((unsigned)cdiv(words, 4), (unsigned)K), 256, 0, s>>>(probs, out_off, word_off, R, K, thr,
+                                                                                                   track_stride, bits);
+    });
 }
 
 // The edge walk of the event decoder, run by ONE wave over the two bit tracks of one (recording, class): ob = p' > lo,

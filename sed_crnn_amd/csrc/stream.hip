@@ -125,8 +125,7 @@ extern "C" int sed_stream_append(float* buf, long buf_len, long stride, const fl
     }
     if (longest == 0) return 0;
     hipStream_t st = as_stream(stream);
-    const hipError_t e = hipMemcpyAsync(workspace, h.data(), need, hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) { sed_set_error("stream_append: upload of the stream table: %s", hipGetErrorString(e)); return (int)e; }
+    SED_TRY(detect_upload("stream_append", workspace, h.data(), need, st));
     const long nb = (longest + 255) / 256;
     stream_append_k<<<dim3((unsigned)(nb < 1024 ? nb : 1024), (unsigned)S), 256, 0, st>>>(buf, fresh, work, (const AppendRec*)workspace);
     SED_LAUNCH_CHECK("stream_append");
@@ -174,32 +173,18 @@ __global__ __launch_bounds__(256) void stream_stitch_k(const StreamRec* __restri
     }
 }
 
-// one thread per (stream, newly decided frame, class): the median of width M (a selection: exact) over the track ring; the
-// left edge clamps at frame 0, the right edge only at the end of the stream ('nearest')
+// one thread per (stream, newly decided frame, class): median_nearest of detect_shared.h (the offline decoder's) over the track
+// ring; the right edge clamps only at the end of the stream, where the last frame is known
+template <int M>
 __global__ __launch_bounds__(256) void stream_median_k(const StreamRec* __restrict__ recs, const float* __restrict__ track, int TR,
-                                                       int K, int M, int max_dg, float* __restrict__ filt) {
+                                                       int K, int max_dg, float* __restrict__ filt) {
     const StreamRec r = recs[blockIdx.y];
     const long total = (long)(r.G_now - r.G_prev) * K;
-    const float* tr = track + (size_t)blockIdx.y * TR * K;
+    const RingRows rows{track + (size_t)blockIdx.y * TR * K, TR, K};
     const int last = r.end ? r.n_out - 1 : 0x7fffffff;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-        const int gg = (int)(i / K), k = (int)(i - (long)gg * K), g = r.G_prev + gg;
-        float v[31];
-#pragma unroll
-        for (int d = 0; d < 31; ++d) {
-            int t = g + d - M / 2;
-            t = t < 0 ? 0 : (t > last ? last : t);
-            v[d] = d < M ? tr[(size_t)(t % TR) * K + k] : 0.f;
-        }
-        float med = v[0];
-#pragma unroll
-        for (int a = 0; a < 31; ++a) {
-            int less = 0, leq = 0;
-#pragma unroll
-            for (int d = 0; d < 31; ++d) { less += (d < M) & (v[d] < v[a]); leq += (d < M) & (v[d] <= v[a]); }
-            if (a < M && less <= M / 2 && M / 2 < leq) med = v[a];  // v[a] is the (M/2)-th smallest
-        }
-        filt[((size_t)blockIdx.y * max_dg + gg) * K + k] = med;
+        const int gg = (int)(i / K), k = (int)(i - (long)gg * K);
+        filt[((size_t)blockIdx.y * max_dg + gg) * K + k] = median_nearest<M>(rows, r.G_prev + gg, k, last);
     }
 }
 
@@ -291,10 +276,8 @@ extern "C" int sed_stream_step(void* state, size_t state_bytes, int S, int K, in
     SED_REQUIRE(need > 0, "stream_step: bad max_new_decided=%d", max_new_decided);
     SED_REQUIRE(workspace_bytes >= need, "stream_step: workspace of %zu bytes, %zu needed", workspace_bytes, need);
     SED_REQUIRE(combine == 0 || combine == 1, "stream_step: combine must be 0 (mean) or 1 (max), got %d", combine);
-    SED_REQUIRE(trim >= 0 && (hop_out + 2L * trim <= win_out), "stream_step: trim=%d leaves output frames uncovered (hop_out=%d, win_out=%d)",
-                trim, hop_out, win_out);
-    SED_REQUIRE(hi >= lo, "stream_step: need hi >= lo (got lo=%g, hi=%g)", (double)lo, (double)hi);
-    SED_REQUIRE(min_gap >= 0 && min_len >= 1, "stream_step: min_gap >= 0 and min_len >= 1 (got %d, %d)", min_gap, min_len);
+    SED_TRY(detect_check_trim("stream_step", -1, 2, win_out, hop_out, trim));        // n_win = 2: a stream may always grow past one window
+    SED_TRY(detect_check_decoder("stream_step", -1, median, lo, hi, min_gap, min_len));
     SED_REQUIRE(max_events >= 0 && (max_events == 0 || (ev_stream && cls && onset && offset && peak && peak_frame)),
                 "stream_step: null output pointer");
     SED_REQUIRE(logits_len >= 0 && (logits || logits_len == 0) && probs_rows >= 0 && (probs || probs_rows == 0),
@@ -349,8 +332,7 @@ extern "C" int sed_stream_step(void* state, size_t state_bytes, int S, int K, in
     int* counts = (int*)p; p += st_al((size_t)S * K * 4);
     int* offs = (int*)p; p += st_al((size_t)S * K * 4);
     float* filt = (float*)p;
-    const hipError_t e = hipMemcpyAsync(recs, h.data(), (size_t)S * sizeof(StreamRec), hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) { sed_set_error("stream_step: upload of the stream table: %s", hipGetErrorString(e)); return (int)e; }
+    SED_TRY(detect_upload("stream_step", recs, h.data(), (size_t)S * sizeof(StreamRec), st));
     float* ring = (float*)state;
     float* track = (float*)((char*)state + d.track_off);
     DecState* dec = (DecState*)((char*)state + d.dec_off);
@@ -366,7 +348,9 @@ extern "C" int sed_stream_step(void* state, size_t state_bytes, int S, int K, in
         SED_LAUNCH_CHECK("stream_stitch");
     }
     if (most_dg) {
-        stream_median_k<<<dim3(blocks(most_dg), (unsigned)S), 256, 0, st>>>(recs, track, d.TR, K, median, max_new_decided, filt);
+        detect_with_median(median, [&](auto m) {
+            stream_median_k<decltype(m)::value><<<dim3(blocks(most_dg), (unsigned)S), 256, 0, st>>>(recs, track, d.TR, K, max_new_decided, filt);
+        });
         SED_LAUNCH_CHECK("stream_median");
     }
     const unsigned wb = (unsigned)cdiv((long)S * K, 256);

@@ -3,9 +3,9 @@
 // written: event-based matches (onset / offset collar) and per-recording segment-based block counts, summed over recordings into
 // counts [G][K][6] = (ev_tp, n_sys, n_ref, seg_tp, seg_sys, seg_ref), int64.  Integer work throughout: exact and repeatable.
 //
-//   1. tune_bits_k<M>, one launch per distinct median width: the track is filtered once per width and one bit track is packed per
-//      distinct (width, threshold value); lo and hi of every setting index into that pool.  Layout of one track: that of
-//      detect_bits_batch_k ([K][words_r] per recording at word K*word_off[r], one spare word per recording).
+//   1. detect_bits_seg_k<M> of detect_shared.h — the bit-track kernel of sed_detect_events_batch — with a list of thresholds,
+//      one launch per distinct median width: the track is filtered once per width and one bit track is packed per distinct
+//      (width, threshold value); lo and hi of every setting index into that pool.
 //   2. tune_refblocks_k: per (recording, class) the prefix count of reference-active blocks, P[b] = active blocks before block b.
 //   3. tune_walk_k, one wave per (setting, class, group of recordings): detect_walk_body of detect_shared.h — the walk of
 //      detect_walk_k — whose finished events go through the matcher and the block counter instead of being stored; the wave sums
@@ -13,26 +13,6 @@
 #include <vector>
 #include "common.h"
 #include "detect_shared.h"
-
-// one wave per (packed word, class); the filtered value is computed once and compared with every threshold of this width
-template <int M>
-__global__ __launch_bounds__(256) void tune_bits_k(const float* __restrict__ probs, const int* __restrict__ out_off,
-                                                   const int* __restrict__ word_off, int R, int K, const float* __restrict__ thr,
-                                                   int n_thr, size_t track_words, unsigned long long* __restrict__ bits) {
-    const int k = blockIdx.y, lane = threadIdx.x & 63;
-    const int gw = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (gw >= word_off[R]) return;                                    // wave-uniform
-    const int r = __builtin_amdgcn_readfirstlane(find_seg(word_off, R, gw));
-    const int n_out = out_off[r + 1] - out_off[r], nw = word_off[r + 1] - word_off[r], lw = gw - word_off[r];
-    const int j = lw * 64 + lane;
-    const bool in = j < n_out;
-    const float p = in ? median_nearest<M>(probs + (size_t)out_off[r] * K, j, k, K, n_out) : 0.f;
-    const size_t at = (size_t)K * word_off[r] + (size_t)k * nw + lw;
-    for (int t = 0; t < n_thr; ++t) {
-        const unsigned long long b = __ballot(in && p > thr[t]);
-        if (lane == 0) bits[(size_t)t * track_words + at] = b;
-    }
-}
 
 // One wave per (recording, class).  Block b = frames [b block, (b+1) block) is reference-active when a reference event covers one
 // of its frames: the events are sorted and disjoint, so that is the first event whose offset lies beyond the block's start.
@@ -169,7 +149,6 @@ __global__ __launch_bounds__(64) void tune_walk_k(const unsigned long long* __re
 // workspace (16-byte aligned regions): out_off, word_off, blk_off [R+1] each (one upload); the settings [G]; the thresholds
 // [n_tracks]; the block prefix counts, at most K (n_total + R) ints (block >= 1); then n_tracks bit tracks of K words each,
 // words <= n_total/64 + R
-static inline size_t tune_al16(size_t b) { return (b + 15) & ~(size_t)15; }
 #define TUNE_MAX_G (1 << 20)
 
 extern "C" size_t sed_tune_workspace_bytes(long n_total, int K, int R, int n_tracks, int G) {
@@ -177,21 +156,8 @@ extern "C" size_t sed_tune_workspace_bytes(long n_total, int K, int R, int n_tra
     if (G < 1 || G > TUNE_MAX_G || n_tracks < 1 || n_tracks > 2 * (long)G) return 0;
     if (n_total / 64 + R > 0x7fffffffL) return 0;
     const size_t words = (size_t)(n_total / 64 + R);
-    return tune_al16((size_t)3 * (R + 1) * 4) + tune_al16((size_t)G * sizeof(TuneSet)) + tune_al16((size_t)n_tracks * 4) +
-           tune_al16((size_t)K * ((size_t)n_total + R) * 4) + (size_t)n_tracks * K * words * sizeof(unsigned long long);
-}
-
-template <int M>
-static void launch_tune_bits(const float* probs, const int* out_off, const int* word_off, int R, int K, long words, const float* thr,
-                             int n_thr, size_t track_words, unsigned long long* bits, hipStream_t s) {
-    tune_bits_k<M><<<dim3((unsigned)cdiv(words, 4), (unsigned)K), 256, 0, s>>>(probs, out_off, word_off, R, K, thr, n_thr, track_words,
-                                                                              bits);
-}
-
-static int tune_upload(void* dst, const void* src, size_t bytes, hipStream_t s) {
-    const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) { sed_set_error("tune_sweep: upload of the host tables: %s", hipGetErrorString(e)); return (int)e; }
-    return 0;
+    return al16((size_t)3 * (R + 1) * 4) + al16((size_t)G * sizeof(TuneSet)) + al16((size_t)n_tracks * 4) +
+           al16((size_t)K * ((size_t)n_total + R) * 4) + (size_t)n_tracks * K * words * sizeof(unsigned long long);
 }
 
 extern "C" int sed_tune_sweep(const float* probs, const long* n_out_host, int R, int K, const sed_tune_setting* settings_host, int G,
@@ -204,20 +170,12 @@ extern "C" int sed_tune_sweep(const float* probs, const long* n_out_host, int R,
     SED_REQUIRE(n_out_host, "tune_sweep: null pointer (n_out_host)");
     std::vector<int> h(3 * (size_t)(R + 1));
     int *out_off = h.data(), *word_off = out_off + R + 1, *blk_off = word_off + R + 1;
-    long rows = 0, words = 0, blks = 0;
+    long rows, words, blks = 0;
+    SED_TRY(detect_seg_tables("tune_sweep", n_out_host, R, K, out_off, word_off, &rows, &words));
     for (int r = 0; r < R; ++r) {
-        const long n = n_out_host[r];
-        SED_REQUIRE(n >= 1 && n <= 0x7fffffffL - rows, "tune_sweep: recording %d has %ld output frames", r, n);
-        out_off[r] = (int)rows;
-        word_off[r] = (int)words;
         blk_off[r] = (int)blks;
-        rows += n;
-        words += detect_words(n);
-        blks += (n + block - 1) / block + 1;                          // n_blk + 1 prefix counts
-        SED_REQUIRE(rows * K <= 0x7fffffffL, "tune_sweep: more than 2^31 - 1 (frame, class) cells in one batch");
+        blks += (n_out_host[r] + block - 1) / block + 1;              // n_blk + 1 prefix counts
     }
-    out_off[R] = (int)rows;
-    word_off[R] = (int)words;
     blk_off[R] = (int)blks;
     if (G == 0) return 0;
     SED_REQUIRE(settings_host, "tune_sweep: null pointer (settings_host)");
@@ -227,11 +185,7 @@ extern "C" int sed_tune_sweep(const float* probs, const long* n_out_host, int R,
     std::vector<int> lo_m(G), lo_i(G), hi_i(G);
     for (int g = 0; g < G; ++g) {
         const sed_tune_setting& t = settings_host[g];
-        SED_REQUIRE(t.median >= 1 && t.median <= 31 && (t.median & 1), "tune_sweep: setting %d: median width must be odd, 1..31 (got %d)",
-                    g, t.median);
-        SED_REQUIRE(t.hi >= t.lo, "tune_sweep: setting %d: need hi >= lo (got lo=%g, hi=%g)", g, (double)t.lo, (double)t.hi);
-        SED_REQUIRE(t.min_gap >= 0 && t.min_len >= 1, "tune_sweep: setting %d: min_gap >= 0 and min_len >= 1 (got %d, %d)", g, t.min_gap,
-                    t.min_len);
+        SED_TRY(detect_check_decoder("tune_sweep", g, t.median, t.lo, t.hi, t.min_gap, t.min_len));
         size_t m = 0;
         while (m < med_of.size() && med_of[m] != t.median) ++m;
         if (m == med_of.size()) { med_of.push_back(t.median); thr_of.emplace_back(); }
@@ -265,30 +219,23 @@ extern "C" int sed_tune_sweep(const float* probs, const long* n_out_host, int R,
     SED_REQUIRE((long)G * K * RS <= 0x7fffffffL, "tune_sweep: G*K*R = %d*%d*%d is too large for one call", G, K, R);
 
     char* p = (char*)workspace;
-    int* d_off = (int*)p; p += tune_al16((size_t)3 * (R + 1) * 4);
-    TuneSet* d_sets = (TuneSet*)p; p += tune_al16((size_t)G * sizeof(TuneSet));
-    float* d_thr = (float*)p; p += tune_al16((size_t)n_tracks * 4);
-    int* d_P = (int*)p; p += tune_al16((size_t)K * ((size_t)rows + R) * 4);
+    int* d_off = (int*)p; p += al16((size_t)3 * (R + 1) * 4);
+    TuneSet* d_sets = (TuneSet*)p; p += al16((size_t)G * sizeof(TuneSet));
+    float* d_thr = (float*)p; p += al16((size_t)n_tracks * 4);
+    int* d_P = (int*)p; p += al16((size_t)K * ((size_t)rows + R) * 4);
     unsigned long long* d_bits = (unsigned long long*)p;
     const int *d_out_off = d_off, *d_word_off = d_off + R + 1, *d_blk_off = d_off + 2 * (R + 1);
     const size_t track_words = (size_t)K * words;                     // words <= rows/64 + R: inside the workspace
 
     hipStream_t s = as_stream(stream);
-    if (int rc = tune_upload(d_off, h.data(), h.size() * 4, s)) return rc;
-    if (int rc = tune_upload(d_sets, sets.data(), sets.size() * sizeof(TuneSet), s)) return rc;
-    if (int rc = tune_upload(d_thr, thr.data(), thr.size() * 4, s)) return rc;
+    SED_TRY(detect_upload("tune_sweep", d_off, h.data(), h.size() * 4, s));
+    SED_TRY(detect_upload("tune_sweep", d_sets, sets.data(), sets.size() * sizeof(TuneSet), s));
+    SED_TRY(detect_upload("tune_sweep", d_thr, thr.data(), thr.size() * 4, s));
     const hipError_t e = hipMemsetAsync(counts, 0, (size_t)G * K * 6 * sizeof(long), s);
     if (e != hipSuccess) { sed_set_error("tune_sweep: clearing counts: %s", hipGetErrorString(e)); return (int)e; }
     for (size_t m = 0; m < med_of.size(); ++m) {
-        const float* th = d_thr + first[m];
-        unsigned long long* bt = d_bits + (size_t)first[m] * track_words;
-        const int nt = (int)thr_of[m].size();
-        switch (med_of[m]) {
-#define TUNE_MED(w) case w: launch_tune_bits<w>(probs, d_out_off, d_word_off, R, K, words, th, nt, track_words, bt, s); break;
-            TUNE_MED(1) TUNE_MED(3) TUNE_MED(5) TUNE_MED(7) TUNE_MED(9) TUNE_MED(11) TUNE_MED(13) TUNE_MED(15)
-            TUNE_MED(17) TUNE_MED(19) TUNE_MED(21) TUNE_MED(23) TUNE_MED(25) TUNE_MED(27) TUNE_MED(29) TUNE_MED(31)
-#undef TUNE_MED
-        }
+        launch_bits_seg(med_of[m], probs, d_out_off, d_word_off, R, K, words, ThresholdList{d_thr + first[m], (int)thr_of[m].size()},
+                        track_words, d_bits + (size_t)first[m] * track_words, s);
         SED_LAUNCH_CHECK("tune_bits");
     }
     tune_refblocks_k<<<(unsigned)((long)R * K), 64, 0, s>>>(d_out_off, d_blk_off, K, block, ref_off, ref_onset, ref_offset, d_P);

@@ -17,6 +17,7 @@ reads one int — the event count — and nothing else.
 import ctypes as C
 from dataclasses import dataclass
 
+import numpy as np
 import torch
 
 from . import feature
@@ -25,6 +26,46 @@ from .data import SEQ_LEN_IN
 from .model import HipCRNN
 
 _EVENT_KEYS = ("cls", "onset", "offset", "peak", "peak_frame")
+
+
+def _event_tensors(keys, cap, device):
+    """event buffers for ``cap`` events: one device tensor per key (``peak`` float32, every other int32), rows of one allocation"""
+    buf = torch.empty(len(keys), cap, dtype=torch.int32, device=device)
+    return {k: buf[i].view(torch.float32) if k == "peak" else buf[i] for i, k in enumerate(keys)}
+
+
+def _intervals(events, frame_seconds, k):
+    """[(start_s, end_s, peak), ...] of class ``k`` among ``events``, on the host (seconds = frame * tf * hop_length / sr)"""
+    ev = {n: events[n].cpu().numpy() for n in ("cls", "onset", "offset", "peak")}
+    sel = ev["cls"] == int(k)
+    fs = frame_seconds
+    return [(int(a) * fs, int(b) * fs, float(p)) for a, b, p in zip(ev["onset"][sel], ev["offset"][sel], ev["peak"][sel])]
+
+
+def _timed(marks, name, fn):
+    """run ``fn``; with a list ``marks``, between two hip events that go to it as (name, start, end), for per-phase timing"""
+    if marks is None:
+        return fn()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    out = fn()
+    b.record()
+    marks.append((name, a, b))
+    return out
+
+
+def _window_jobs(logits, groups, tf, K):
+    """``_forward_windows`` jobs for ``groups`` = [(win_len, window starts), ...] (empty ones are skipped) whose logits fill the
+    flat buffer ``logits`` back to back: the starts go to the device as int32, every group gets its [n, win_len // tf, K] view"""
+    jobs, at = [], 0
+    for Lw, starts in groups:
+        n, wo = len(starts), Lw // tf
+        if n == 0:
+            continue
+        st = torch.from_numpy(np.asarray(starts, dtype=np.int32)).to(logits.device, non_blocking=True)
+        jobs.append((st, Lw, logits[at:at + n * wo * K].view(n, wo, K)))
+        at += n * wo * K
+    return jobs
 
 
 @dataclass(frozen=True)
@@ -95,7 +136,6 @@ class BatchPlan:
 
     def stitch_table(self):
         """[R][6] int64 {first logit, n_win, win_out, hop_out, last_start_out, n_out}: sed_detect_stitch_batch's table"""
-        import numpy as np
         return np.array([[o, p.n_win, p.win_out, p.hop_out, p.last_start_out, p.n_out] for o, p in zip(self.logit_off, self.plans)],
                         dtype=np.int64).reshape(-1, 6)
 
@@ -146,10 +186,7 @@ class DetectionResult:
 
     def intervals(self, k=0):
         """[(start_s, end_s, peak), ...] of class ``k`` on the host (seconds = frame * tf * hop_length / sr)."""
-        ev = {n: self.events[n].cpu().numpy() for n in ("cls", "onset", "offset", "peak")}
-        sel = ev["cls"] == int(k)
-        fs = self.frame_seconds
-        return [(int(a) * fs, int(b) * fs, float(p)) for a, b, p in zip(ev["onset"][sel], ev["offset"][sel], ev["peak"][sel])]
+        return _intervals(self.events, self.frame_seconds, k)
 
 
 class BatchDetectionResult:
@@ -211,6 +248,7 @@ class EventDetector:
         self.model = model
         self.seq_len, self.hop = int(seq_len), (int(seq_len) // 2 if hop is None else int(hop))
         self.combine, self.trim = combine, int(trim)
+        self._combine_id = ("mean", "max").index(combine)                  # as the stitch entries take it
         self.hi, self.lo = float(threshold), lo
         self.median, self.min_gap, self.min_len = int(median), int(min_gap), int(min_len)
         self.mean = None if mean is None else torch.as_tensor(mean, dtype=torch.float64)      # numpy or device tensors
@@ -317,8 +355,7 @@ class EventDetector:
         m = self.model
         self._check_model()
         logits = torch.empty(plan.n_win, plan.win_out, m.dense[-1], device=mel.device)
-        starts = torch.tensor(plan.starts, dtype=torch.int32).to(mel.device, non_blocking=True)
-        self._forward_windows(mel, [(starts, plan.win_len, logits)], marks)
+        self._forward_windows(mel, _window_jobs(logits.view(-1), [(plan.win_len, plan.starts)], m.time_factor, m.dense[-1]), marks)
         return logits
 
     def _forward_windows(self, mel, jobs, marks=None):
@@ -341,15 +378,6 @@ class EventDetector:
         ws = m._workspace(cfgs[max(range(len(cfgs)), key=need.__getitem__)], False)
         cap = ws.numel() * 4
 
-        def mark(name, fn):
-            if marks is None:
-                return fn()
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            marks.append((name, a, b))
-
         for (starts, Lw, logits), (bmax, _), cfg in zip(jobs, shapes, cfgs):
             nw = starts.numel()
             x = xbuf[:bmax * CF * Lw].view(bmax, m.in_channels, m.n_mels, Lw)
@@ -360,10 +388,10 @@ class EventDetector:
                     cfg = m._cfg(b, Lw, training=False)
                     if lib().sed_net_workspace_bytes(C.byref(cfg), 0) > cap:
                         check(-1, "sed_net_workspace_bytes (a smaller chunk needs a larger workspace)")
-                mark("gather", lambda: check(lib().sed_window_batch(
+                _timed(marks, "gather", lambda: check(lib().sed_window_batch(
                     ptr(mel), ptr(self._zlab), N, m.in_channels, m.n_mels, 1, ptr(starts[b0:b0 + b]), None, None, 0, 0, 0,
                     ptr(x), ptr(y), b, Lw, Lw, stream_ptr()), "sed_window_batch"))
-                mark("forward", lambda: check(lib().sed_net_forward(
+                _timed(marks, "forward", lambda: check(lib().sed_net_forward(
                     C.byref(cfg), C.byref(P), ptr(x), ptr(logits[b0:b0 + b]), ptr(ws), 0, 0, None, stream_ptr()),
                     "sed_net_forward"))
 
@@ -372,7 +400,7 @@ class EventDetector:
         K = logits.shape[2]
         probs = torch.empty(plan.n_out, K, device=logits.device)
         check(lib().sed_detect_stitch(ptr(logits), plan.n_win, plan.win_out, K, plan.hop_out, plan.last_start_out,
-                                      plan.n_out, {"mean": 0, "max": 1}[self.combine], self.trim, ptr(probs), stream_ptr()),
+                                      plan.n_out, self._combine_id, self.trim, ptr(probs), stream_ptr()),
               "sed_detect_stitch")
         return probs
 
@@ -388,16 +416,22 @@ class EventDetector:
         if self._dws is None or self._dws.numel() < need or self._dws.device != dev:
             self._dws = torch.empty(need, dtype=torch.uint8, device=dev)
         count = torch.empty(1, dtype=torch.int32, device=dev)
+        return self._decode_growing(_EVENT_KEYS, count, lambda cap, out: check(lib().sed_detect_events(
+            ptr(probs), n_out, K, self.median, self.lo, self.hi, self.min_gap, self.min_len, cap, ptr(self._dws), self._dws.numel(),
+            *(ptr(out[n]) for n in _EVENT_KEYS), ptr(count), stream_ptr()), "sed_detect_events"))[0]
+
+    def _decode_growing(self, keys, counts, launch):
+        """``launch(cap, out)`` decodes into event buffers of ``cap`` events and leaves its counts, the last one the total, in the
+        device tensor ``counts``: reading them is the one read.  When the total exceeds ``cap`` the buffers grow to it and the
+        decode runs again.  -> (events cut to the total, the counts as a host list)"""
         while True:
             cap = self.max_events
-            out = {n: torch.empty(cap, dtype=torch.float32 if n == "peak" else torch.int32, device=dev) for n in _EVENT_KEYS}
-            check(lib().sed_detect_events(ptr(probs), n_out, K, self.median, self.lo, self.hi, self.min_gap, self.min_len,
-                                          cap, ptr(self._dws), self._dws.numel(), *(ptr(out[n]) for n in _EVENT_KEYS),
-                                          ptr(count), stream_ptr()), "sed_detect_events")
-            n = int(count.item())
-            if n <= cap:
-                return {k: v[:n] for k, v in out.items()}
-            self.max_events = n
+            out = _event_tensors(keys, cap, counts.device)
+            launch(cap, out)
+            offs = counts.cpu().tolist()
+            if offs[-1] <= cap:
+                return {k: v[:offs[-1]] for k, v in out.items()}, offs
+            self.max_events = offs[-1]
 
     # ── batches: many recordings in one pass (DESIGN 5g) ──
     def detect_many(self, waveforms):
@@ -445,16 +479,12 @@ class EventDetector:
             return self._empty_batch()
         dev = m.flat_parameters().device
         with torch.no_grad():
-            if all(not x.is_cuda for x in mels):
-                mel = torch.cat([x.to(torch.float32) for x in mels]).to(dev)
-            else:
-                mel = torch.cat([x.to(dev, torch.float32) for x in mels])
-            return self._detect_packed(mel.contiguous(), bp)
+            return self._detect_packed(feature.cat_to_device(mels, dev).contiguous(), bp)
 
     def _empty_batch(self):
         m = self.model
         dev = m.flat_parameters().device
-        ev = {k: torch.empty(0, dtype=torch.float32 if k == "peak" else torch.int32, device=dev) for k in ("rec",) + _EVENT_KEYS}
+        ev = _event_tensors(("rec",) + _EVENT_KEYS, 0, dev)
         return BatchDetectionResult(torch.empty(0, m.dense[-1], device=dev), ev, self.frame_seconds, (), [0], [0])
 
     def _detect_packed(self, mel, bp):
@@ -468,18 +498,10 @@ class EventDetector:
         chunks of at most max_batch (one sed_window_batch gather each, absolute starts), then every group of short
         recordings, all on one workspace (``_forward_windows``).  ``marks`` as in ``window_logits``."""
         self._check_model()
-        m, dev = self.model, mel.device
-        K, tf = m.dense[-1], m.time_factor
-        logits = torch.empty(bp.n_logits, device=dev)
-        jobs, at = [], 0
-        for Lw, starts in ((self.seq_len, bp.full_starts),) + bp.groups:
-            if not starts:
-                continue
-            n, wo = len(starts), Lw // tf
-            st = torch.tensor(starts, dtype=torch.int32).to(dev, non_blocking=True)
-            jobs.append((st, Lw, logits[at:at + n * wo * K].view(n, wo, K)))
-            at += n * wo * K
-        self._forward_windows(mel, jobs, marks)
+        m = self.model
+        logits = torch.empty(bp.n_logits, device=mel.device)
+        self._forward_windows(mel, _window_jobs(logits, ((self.seq_len, bp.full_starts),) + bp.groups, m.time_factor, m.dense[-1]),
+                              marks)
         return logits
 
     def _batch_workspace(self, n_total, K, R):
@@ -498,7 +520,7 @@ class EventDetector:
         ws = self._batch_workspace(n, K, R)
         probs = torch.empty(n, K, device=logits.device)
         check(lib().sed_detect_stitch_batch(ptr(logits), logits.numel(), C.c_void_p(table.ctypes.data), R, K,
-                                            {"mean": 0, "max": 1}[self.combine], self.trim, ptr(probs), n, ptr(ws), ws.numel(),
+                                            self._combine_id, self.trim, ptr(probs), n, ptr(ws), ws.numel(),
                                             stream_ptr()), "sed_detect_stitch_batch")
         return probs
 
@@ -507,7 +529,6 @@ class EventDetector:
         batch; when the total exceeds the buffers, they grow and only the decode runs again.  Of ``bp`` only ``plans`` (its
         length, R) and ``out_off`` [R+1] are used: ``plan_batch([tf * n for n in n_out], tf, K)`` decodes a track that did
         not come from this detector's forward."""
-        import numpy as np
         n_total, K = probs.shape
         R = len(bp.plans)
         n_out = np.ascontiguousarray(np.diff(np.asarray(bp.out_off, dtype=np.int64)))
@@ -515,16 +536,9 @@ class EventDetector:
         dev = probs.device
         ev_off = torch.empty(R + 1, dtype=torch.int32, device=dev)
         keys = ("rec",) + _EVENT_KEYS
-        while True:
-            cap = self.max_events
-            out = {n: torch.empty(cap, dtype=torch.float32 if n == "peak" else torch.int32, device=dev) for n in keys}
-            check(lib().sed_detect_events_batch(ptr(probs), C.c_void_p(n_out.ctypes.data), R, K, self.median, self.lo, self.hi,
-                                                self.min_gap, self.min_len, cap, ptr(ws), ws.numel(),
-                                                *(ptr(out[n]) for n in keys), ptr(ev_off), stream_ptr()), "sed_detect_events_batch")
-            offs = ev_off.cpu().tolist()
-            if offs[-1] <= cap:
-                return {k: v[:offs[-1]] for k, v in out.items()}, offs
-            self.max_events = offs[-1]
+        return self._decode_growing(keys, ev_off, lambda cap, out: check(lib().sed_detect_events_batch(
+            ptr(probs), C.c_void_p(n_out.ctypes.data), R, K, self.median, self.lo, self.hi, self.min_gap, self.min_len, cap, ptr(ws),
+            ws.numel(), *(ptr(out[n]) for n in keys), ptr(ev_off), stream_ptr()), "sed_detect_events_batch"))
 
 
 def detect_events_many(model, xs, **kw):

@@ -89,6 +89,21 @@ def _validated_mels(tables):
     return n
 
 
+def _scaler(mean, std, device):
+    """the StandardScaler as the kernels take it: float32 (mean, 1/std), the reciprocal taken in float64; (None, None) without one"""
+    if mean is None:
+        return None, None
+    return mean.to(device).float().contiguous(), (1.0 / std.to(device).double()).float().contiguous()
+
+
+def cat_to_device(pieces, device):
+    """float32 ``torch.cat`` of the pieces on ``device``: host pieces are joined on the host and travel in ONE copy; with a device
+    piece among them, each is moved and they are joined on the device"""
+    if all(not p.is_cuda for p in pieces):
+        return torch.cat([p.to(torch.float32) for p in pieces]).to(device)
+    return torch.cat([p.to(device, torch.float32) for p in pieces])
+
+
 def mbe(y, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, pad_mode="constant", mean=None, std=None, tables=None):
     """y: mono float32 PCM CUDA tensor [N] -> [1 + N//hop, n_mels] log-mel energies (natural log, no eps).
     ``tables`` = build_tables(window, melfb, device) replaces librosa's default window / filterbank."""
@@ -103,10 +118,7 @@ def mbe(y, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, pad_mode="constant", mean=
         n_mels = _validated_mels(tables)
     frames = 1 + y.numel() // hop
     out = torch.empty(frames, n_mels, device=y.device)
-    inv = None
-    if mean is not None:
-        mean = mean.to(y.device).float().contiguous()
-        inv = (1.0 / std.to(y.device).double()).float().contiguous()
+    mean, inv = _scaler(mean, std, y.device)
     check(lib().sed_logmel(ptr(y), y.numel(), ptr(tables), tables.numel() * 4, ptr(mean), ptr(inv), ptr(out), n_fft, hop,
                            n_mels, {"constant": 0, "reflect": 1}[pad_mode], stream_ptr()), "sed_logmel")
     return out
@@ -137,10 +149,7 @@ def mbe_packed(pcm, clips, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, pad_mode="
     if rows[-1] >= 2 ** 31:
         raise ValueError(f"{rows[-1]} feature frames in one batch: at most 2^31 - 1")
     pcm = pcm.contiguous().float()
-    inv = None
-    if mean is not None:
-        mean = mean.to(pcm.device).float().contiguous()
-        inv = (1.0 / std.to(pcm.device).double()).float().contiguous()
+    mean, inv = _scaler(mean, std, pcm.device)
     ws = torch.empty(lib().sed_logmel_batch_workspace_bytes(R), dtype=torch.uint8, device=pcm.device)
     check(lib().sed_logmel_batch(ptr(pcm), pcm.numel(), C.c_void_p(table.ctypes.data), R, ptr(tables), tables.numel() * 4,
                                  ptr(mean), ptr(inv), ptr(out), rows[-1], n_fft, hop, n_mels,

@@ -24,7 +24,7 @@ import torch
 
 from . import feature
 from ._lib import SedHipError, check, lib, ptr, stream_ptr
-from .detect import EventDetector, plan_windows
+from .detect import EventDetector, _event_tensors, _intervals, _timed, _window_jobs, plan_windows
 
 _KEYS = ("stream", "cls", "onset", "offset", "peak", "peak_frame")
 
@@ -138,10 +138,7 @@ class StreamEvents:
     def intervals(self, stream, k=0):
         """[(start_s, end_s, peak), ...] of class ``k`` of one stream, on the host"""
         e0, e1 = self.event_offsets[int(stream)], self.event_offsets[int(stream) + 1]
-        ev = {n: self.events[n][e0:e1].cpu().numpy() for n in ("cls", "onset", "offset", "peak")}
-        sel = ev["cls"] == int(k)
-        fs = self.frame_seconds
-        return [(int(a) * fs, int(b) * fs, float(p)) for a, b, p in zip(ev["onset"][sel], ev["offset"][sel], ev["peak"][sel])]
+        return _intervals({n: v[e0:e1] for n, v in self.events.items()}, self.frame_seconds, k)
 
 
 class StreamDetector:
@@ -208,16 +205,6 @@ class StreamDetector:
             check(lib().sed_stream_init(ptr(self._state), self._state.numel(), *self._dims, stream_ptr()), "sed_stream_init")
         return self._state.device
 
-    def _mark(self, name, fn):
-        if self.marks is None:
-            return fn()
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        out = fn()
-        b.record()
-        self.marks.append((name, a, b))
-        return out
-
     # ── log-mel of a round: carry + new samples as one clip per stream ──
     def _logmel_round(self, fresh, takes, end):
         """``fresh``: the round's new samples packed (device, or None), ``takes`` [S] how many belong to each stream; the
@@ -257,16 +244,13 @@ class StreamDetector:
         if self._lm is None:
             m = det.model
             tables = feature._tables(dev.index or 0, det.sr, feature.NFFT, m.n_mels)
-            mean = inv = None
-            if det.mean is not None:
-                mean = det.mean.to(dev).float().contiguous()
-                inv = (1.0 / det.std.to(dev).double()).float().contiguous()
+            mean, inv = feature._scaler(det.mean, det.std, dev)
             ws = torch.empty(lib().sed_logmel_batch_workspace_bytes(S), dtype=torch.uint8, device=dev)
             self._lm = (tables, mean, inv, ws)
         tables, mean, inv, ws = self._lm
         ct = np.ascontiguousarray(np.stack([work_at[clip], total[clip]], 1))
         out = torch.empty(n_rows, det.model.n_mels, device=dev)
-        self._mark("logmel", lambda: check(lib().sed_logmel_batch(
+        _timed(self.marks, "logmel", lambda: check(lib().sed_logmel_batch(
             ptr(work), work.numel(), C.c_void_p(ct.ctypes.data), ct.shape[0], ptr(tables), tables.numel() * 4, ptr(mean), ptr(inv),
             ptr(out), n_rows, feature.NFFT, h, det.model.n_mels, 0, ptr(ws), ws.numel(), stream_ptr()), "sed_logmel_batch"))
         return out, row0, rows
@@ -320,16 +304,7 @@ class StreamDetector:
                                                _excl(prob_n)], 1))
         # 3. gather + forward, chunked exactly like the offline detector
         logits = torch.empty(max(n_logits, 1), device=dev)
-        jobs, used = [], 0
-        if n_full:
-            jobs.append((torch.from_numpy(full.astype(np.int32)).to(dev, non_blocking=True), L,
-                         logits[:n_full * self.win_out * K].view(n_full, self.win_out, K)))
-            used = n_full * self.win_out * K
-        for Lw, starts in groups:
-            n, wo = len(starts), Lw // tf
-            jobs.append((torch.from_numpy(starts.astype(np.int32)).to(dev, non_blocking=True), Lw,
-                         logits[used:used + n * wo * K].view(n, wo, K)))
-            used += n * wo * K
+        jobs = _window_jobs(logits, [(L, full)] + groups, tf, K)
         if jobs:
             with torch.no_grad():
                 det._forward_windows(self._feat, jobs, self.marks)
@@ -337,20 +312,19 @@ class StreamDetector:
         need = lib().sed_stream_step_workspace_bytes(S, K, dg_max)
         if self._sws is None or self._sws.numel() < need:
             self._sws = torch.empty(need, dtype=torch.uint8, device=dev)
-        ev = torch.empty(6, max(cap, 1), dtype=torch.int32, device=dev)
+        ev = _event_tensors(_KEYS, max(cap, 1), dev)
         ev_off = torch.empty(S + 1, dtype=torch.int32, device=dev)
         probs = torch.empty(n_probs, K, device=dev) if self.keep_probs else None
         give = probs is not None and n_probs > 0
-        self._mark("step", lambda: check(lib().sed_stream_step(
-            ptr(self._state), self._state.numel(), *self._dims, {"mean": 0, "max": 1}[det.combine], det.trim, det.lo, det.hi,
+        _timed(self.marks, "step", lambda: check(lib().sed_stream_step(
+            ptr(self._state), self._state.numel(), *self._dims, det._combine_id, det.trim, det.lo, det.hi,
             det.min_gap, det.min_len, ptr(logits) if n_logits else None, n_logits, C.c_void_p(table.ctypes.data), dg_max,
-            ptr(probs) if give else None, n_probs if give else 0, cap, *(ptr(ev[i]) for i in range(6)), ptr(ev_off), ptr(self._sws),
+            ptr(probs) if give else None, n_probs if give else 0, cap, *(ptr(ev[k]) for k in _KEYS), ptr(ev_off), ptr(self._sws),
             self._sws.numel(), stream_ptr()), "sed_stream_step"))
         offs = ev_off.cpu().tolist()                                        # the one blocking read of a step
         if offs[-1] > cap:
             raise SedHipError(f"sed_stream_step emitted {offs[-1]} events, more than the bound {cap}")
-        n = offs[-1]
-        events = {k: (ev[i, :n].view(torch.float32) if k == "peak" else ev[i, :n]) for i, k in enumerate(_KEYS)}
+        events = {k: v[:offs[-1]] for k, v in ev.items()}
         if end.any():
             self._reset_host(end)
         return events, offs, probs, prob_n, now_F
@@ -369,7 +343,7 @@ class StreamDetector:
             final = parts[-1][4]
         final = final.tolist()
         if not parts:
-            ev = {k: torch.empty(0, dtype=torch.float32 if k == "peak" else torch.int32, device=dev) for k in _KEYS}
+            ev = _event_tensors(_KEYS, 0, dev)
             probs = torch.empty(0, K, device=dev) if self.keep_probs else None
             return StreamEvents(ev, [0] * (S + 1), final, self.frame_seconds, probs, [0] * (S + 1) if self.keep_probs else None)
         if len(parts) == 1:
@@ -404,11 +378,9 @@ class StreamDetector:
         return pieces, lens
 
     def _pack(self, pieces, lens, done, takes, dev):
-        """the round's share of every piece, back to back on the device (host pieces travel in one copy)"""
-        parts = [pieces[s] if takes[s] == lens[s] else pieces[s][done[s]:done[s] + takes[s]] for s in np.nonzero(takes)[0]]
-        if all(not p.is_cuda for p in parts):
-            return torch.cat([p.to(torch.float32) for p in parts]).to(dev)
-        return torch.cat([p.to(dev, torch.float32) for p in parts])
+        """the round's share of every piece, back to back on the device (``feature.cat_to_device``)"""
+        return feature.cat_to_device([pieces[s] if takes[s] == lens[s] else pieces[s][done[s]:done[s] + takes[s]]
+                                      for s in np.nonzero(takes)[0]], dev)
 
     def push(self, chunks):
         """a list of S mono PCM pieces (1-D, host or device, any length >= 0; None = nothing new) -> StreamEvents"""

@@ -192,6 +192,16 @@ def test_step_kernel_is_exact_against_the_offline_kernels_and_the_per_step_refer
     assert _run_step_case(sed, rng, 32, 4, "mean", 0, 0.4, 0.6, 3, 1, 1, "K=32") > 50
 
 
+@pytest.mark.parametrize("median", range(1, 32, 2))
+def test_step_kernel_every_median_width(sed, median):
+    """every instantiation of the step's median (one per width the decoder accepts) against the per-step reference, the
+    offline stitch (bitwise) and the offline decoder; at least 10 events per width, so that no width passes on nothing"""
+    n = _run_step_case(sed, np.random.default_rng(11), K=2, hop_out=4, combine="mean", trim=0, lo=0.5, hi=0.5, median=median,
+                       min_gap=0, min_len=1, what=f"median {median}")
+    print(f"median {median}: {n} events")
+    assert n >= 10
+
+
 def test_step_kernel_pinned_timing_and_a_run_of_50000_frames(sed):
     """(10, 15) with min_gap 2 leaves in the step in which G first reaches 18; one run of 50 000 frames fed 4 at a time is ONE
     event, with the first arg-max, in the step the rule gives — the peak is a running value in the state"""
