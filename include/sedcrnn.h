@@ -448,6 +448,28 @@ int sed_logmel_batch(const float* pcm, long pcm_len, const long* clips_host, int
                      const float* mu, const float* inv_sigma, float* out, long out_rows, int n_fft, int hop, int n_mels,
                      int pad_mode, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ───────────── audio at any sample rate: rational-ratio polyphase resampler, format conversion and downmix ─────────────
+ * What the reference does with `ffmpeg -ac 1 -ar 44100` before feature.py:55.  L/M = sr_out/sr_in reduced; taps [L][2 half]
+ * (device float32, built by the caller in double: sed_crnn_amd/resample.py) weight, for output m of a clip (ABSOLUTE index,
+ * 64-bit), u = m M, i_c = u div L, p = u mod L:  y[m] = sum_k taps[p][k] x[i_c - half + 1 + k], x = 0 where the clip has
+ * nothing.  The sum is taken in fp32 in one fixed order that depends on (p, k) only, so a clip resampled in pieces (a stream)
+ * equals the clip resampled whole bit for bit.
+ * x: x_frames sample frames of `channels` interleaved samples, format 0 = float32, 1 = int16 (scaled by 1/32768); a frame
+ * becomes (sum_c x_c) * (1/channels), summed in channel order, while it is loaded.  rows_host [R][9] (HOST array, validated,
+ * then uploaded into `workspace` >= sed_resample_workspace_bytes(R) on the stream) = {first frame in x, n frames, absolute
+ * index of that first frame, absolute index of the first output, n outputs, first output sample in out (a multiple of 4:
+ * sed_logmel_batch's aligned clip starts; rows in increasing order), hist offset, n_hist, carry_dst}: hist[hist offset, +n_hist)
+ * holds the mono float32 samples that precede the frames (the carry of a stream; n_hist = 0 for a whole clip at base 0) and,
+ * unless carry_dst = -1, the last 2 half samples of (history | frames) are written to hist[carry_dst, +2 half) for the next
+ * call (zeros before the clip's sample 0; the two ranges must not overlap).  A row may have 0 outputs (only its carry moves).
+ * Limits: L (2 half + 1) <= 26 624 floats (the padded table stays in LDS) and a tile of 1024 outputs reads at most 8192
+ * samples (M/L below about 7.5); sed_resample_check_table runs every host check of sed_resample and makes no GPU call. */
+size_t sed_resample_workspace_bytes(int R);
+int sed_resample_check_table(const long* rows_host, int R, long x_frames, long hist_len, long out_len, int L, int M, int half);
+int sed_resample(const void* x, long x_frames, int format, int channels, float* hist, long hist_len, const float* taps,
+                 long taps_len, int L, int M, int half, const long* rows_host, int R, float* out, long out_len, void* workspace,
+                 size_t workspace_bytes, void* stream);
+
 /* ───────────── GPU-resident minibatch assembly (sed.py:64-79; decorte_datamodule.py:39-49,77-111; utils.py:15-41) ─────────────
  * mel [N][C*F] (a whole fold, device-resident; channel c = columns [c*F,(c+1)*F)), lab [N][K].
  * starts [B] window starts (clamped to [0, N-L] like the reference's fallback); tmask/fmask [B][n_masks] SpecAugment

@@ -14,6 +14,7 @@ from .lightning import CRNNLightning, fit_lightning  # noqa: F401
 from .losses import BCEWithLogitsLoss, FocalBCELoss  # noqa: F401
 from .model import (HipCRNN, LightningTimePooledCRNN, SEDNet, TimePooledCRNN,  # noqa: F401
                     get_model)
+from .resample import ResamplePlan, resample, resample_many  # noqa: F401
 from .stream import StreamDetector, StreamEvents, StreamSchedule, StreamSchedules  # noqa: F401
 from .tune import DecoderGrid, ReferenceEvents, SweepResult, tune_decoder  # noqa: F401
 from .optim import FusedAdam, clip_grad_norm_  # noqa: F401

@@ -274,7 +274,8 @@ class EventDetector:
             raise SedHipError("sed_crnn_amd: move the module to the GPU first (model.to('cuda')); there is no CPU fallback")
 
     def stream(self, n_streams, keep_probs=False, **kw):
-        """a ``stream.StreamDetector`` for ``n_streams`` live feeds with this detector's settings"""
+        """a ``stream.StreamDetector`` for ``n_streams`` live feeds with this detector's settings; ``input_sr`` /
+        ``input_channels``: what ``push`` receives"""
         from .stream import StreamDetector
         return StreamDetector(self.model, n_streams, keep_probs=keep_probs, _det=self, **kw)
 
@@ -312,11 +313,17 @@ class EventDetector:
                           block)
 
     # ── the whole path ──
-    def __call__(self, waveform):
-        """mono PCM (1-D tensor / ndarray) -> DetectionResult.  The log-mel front end is ``feature.mbe(..., mean, std)``."""
+    def __call__(self, waveform, sr=None, channels=1):
+        """mono PCM (1-D tensor / ndarray) -> DetectionResult.  The log-mel front end is ``feature.mbe(..., mean, std)``.
+        ``sr`` / ``channels``: the waveform is at that rate (default: the detector's), int16 or float, ``[N, channels]``
+        interleaved, and is converted, downmixed and resampled to the detector's rate on the device first; event
+        times need no change, they are in seconds at the detector's rate."""
         self._check_model()
         if self.model.in_channels != 1:
             raise ValueError(f"a mono waveform feeds a 1-channel net; this one has {self.model.in_channels} (use from_features)")
+        if feature._needs_front_end(waveform, sr, self.sr, channels):
+            from .resample import resample
+            waveform = resample(waveform, self.sr if sr is None else sr, self.sr, channels, self.model.flat_parameters().device)
         y = torch.as_tensor(waveform)
         if y.dim() != 1:
             raise ValueError(f"expected a mono 1-D waveform, got shape {tuple(y.shape)}")
@@ -434,10 +441,11 @@ class EventDetector:
             self.max_events = offs[-1]
 
     # ── batches: many recordings in one pass ──
-    def detect_many(self, waveforms):
+    def detect_many(self, waveforms, sr=None, channels=1):
         """A list of mono PCM clips (1-D, host or device, any lengths) -> BatchDetectionResult.  One log-mel launch for all
         (``feature.mbe_many``, fused scaler), then ``from_features_many``'s path.  A clip shorter than one output frame
-        raises ValueError naming its index before anything runs.
+        raises ValueError naming its index before anything runs.  ``sr`` (one rate, or one per clip) / ``channels``: as in
+        ``__call__``; the clips of one rate are resampled in one launch, straight into the buffer the log-mel launch reads.
 
         Memory, per input frame (hop_length samples): the packed PCM (4*hop_length B), the packed features (4*n_mels B),
         the flat logits (4*K*seq_len/hop/tf B: every frame is in seq_len/hop windows) and the track (4*K/tf B); the window
@@ -446,9 +454,17 @@ class EventDetector:
         if m.in_channels != 1:
             raise ValueError(f"a mono waveform feeds a 1-channel net; this one has {m.in_channels} (use from_features_many)")
         waves = list(waveforms)
+        front = sr is not None and np.ndim(sr) > 0 or any(feature._needs_front_end(w, sr, self.sr, channels) for w in waves)
+        if front:
+            from .resample import _rates, as_pcm, plan_for
+            waves = [as_pcm(w, channels, f"recording {i}") for i, w in enumerate(waves)]
+            rates = _rates(self.sr if sr is None else sr, len(waves))
+            lengths = [plan_for(r, self.sr).n_out(w.shape[0]) for r, w in zip(rates, waves)]
         n_frames = []
         for i, w in enumerate(waves):
             shape = tuple(w.shape) if hasattr(w, "shape") else (len(w),)
+            if front:
+                shape = (lengths[i],)
             if len(shape) != 1:
                 raise ValueError(f"recording {i}: expected a mono 1-D waveform, got shape {shape}")
             n_frames.append(1 + shape[0] // self.hop_length)
@@ -459,7 +475,7 @@ class EventDetector:
         dev = m.flat_parameters().device
         with torch.no_grad():
             mel, _ = feature.mbe_many(waves, sr=self.sr, hop=self.hop_length, n_mels=m.n_mels, mean=self.mean, std=self.std,
-                                      device=dev)
+                                      device=dev, **(dict(input_sr=rates, channels=channels) if front else {}))
             return self._detect_packed(mel, bp)
 
     def from_features_many(self, mels):
@@ -541,17 +557,23 @@ class EventDetector:
             ws.numel(), *(ptr(out[n]) for n in keys), ptr(ev_off), stream_ptr()), "sed_detect_events_batch"))
 
 
-def detect_events_many(model, xs, **kw):
+def detect_events_many(model, xs, input_sr=None, channels=1, **kw):
     """One shot over a list: ``EventDetector(model, **kw)`` on mono waveforms (all 1-D: ``detect_many``) or on scaled features
-    [N_r, C*F] (``from_features_many``) -> BatchDetectionResult."""
+    [N_r, C*F] (``from_features_many``) -> BatchDetectionResult.  With ``input_sr`` or ``channels`` > 1 the list holds
+    waveforms at that rate (``detect_many(xs, sr=input_sr, channels=channels)``; ``sr=`` stays the detector's own rate)."""
     det = EventDetector(model, **kw)
     xs = list(xs)
+    if input_sr is not None or int(channels) != 1:
+        return det.detect_many(xs, sr=input_sr, channels=channels)
     if xs and all(torch.as_tensor(x).dim() == 1 for x in xs):
         return det.detect_many(xs)
     return det.from_features_many(xs)
 
 
-def detect_events(model, x, **kw):
-    """One shot: ``EventDetector(model, **kw)`` on a mono waveform (1-D) or on scaled features [N, C*F] (2-D)."""
+def detect_events(model, x, input_sr=None, channels=1, **kw):
+    """One shot: ``EventDetector(model, **kw)`` on a mono waveform (1-D) or on scaled features [N, C*F] (2-D).  With
+    ``input_sr`` or ``channels`` > 1, ``x`` is a waveform at that rate (``det(x, sr=input_sr, channels=channels)``)."""
     det = EventDetector(model, **kw)
+    if input_sr is not None or int(channels) != 1:
+        return det(x, sr=input_sr, channels=channels)
     return det(x) if torch.as_tensor(x).dim() == 1 else det.from_features(x)

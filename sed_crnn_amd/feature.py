@@ -104,9 +104,21 @@ def cat_to_device(pieces, device):
     return torch.cat([p.to(device, torch.float32) for p in pieces])
 
 
-def mbe(y, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, pad_mode="constant", mean=None, std=None, tables=None):
+def _needs_front_end(w, input_sr, sr, channels):
+    """does this input go through resample.py first: another rate, interleaved channels or int16 samples"""
+    from .resample import is_plain
+    return (input_sr is not None and int(input_sr) != int(sr)) or not is_plain(w, channels)
+
+
+def mbe(y, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, pad_mode="constant", mean=None, std=None, tables=None, input_sr=None,
+        channels=1):
     """y: mono float32 PCM CUDA tensor [N] -> [1 + N//hop, n_mels] log-mel energies (natural log, no eps).
-    ``tables`` = build_tables(window, melfb, device) replaces librosa's default window / filterbank."""
+    ``tables`` = build_tables(window, melfb, device) replaces librosa's default window / filterbank.
+    ``input_sr`` / ``channels``: y is at that rate (default: ``sr``), int16 or float, ``[N, channels]`` interleaved when
+    channels > 1 (host or device), and is converted, downmixed and resampled to ``sr`` on the device first (resample.py)."""
+    if _needs_front_end(y, input_sr, sr, channels):
+        from .resample import resample
+        y = resample(y, sr if input_sr is None else input_sr, sr, channels)
     if not (isinstance(y, torch.Tensor) and y.is_cuda):
         raise RuntimeError("sed_crnn_amd.feature.mbe needs a CUDA(HIP) tensor; there is no CPU fallback")
     if pad_mode not in ("constant", "reflect"):
@@ -180,15 +192,20 @@ def pack_clips(waves, device):
 
 
 def mbe_many(waves, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, pad_mode="constant", mean=None, std=None, tables=None,
-             device=None):
+             device=None, input_sr=None, channels=1):
     """``mbe`` of every clip in a list of 1-D clips (host or device; ``device`` defaults to the first CUDA clip's, else
     cuda:current) in one launch -> (features [sum_r (1 + n_r//hop), n_mels] in clip order, row offsets [R+1] host list).
-    Bit for bit ``torch.cat([mbe(w) for w in waves])``."""
+    Bit for bit ``torch.cat([mbe(w) for w in waves])``.  ``input_sr`` (one rate, or one per clip) / ``channels``: as in
+    ``mbe``; the clips are resampled straight into the packed buffer the log-mel launch reads (``resample.resample_many``)."""
     waves = list(waves)
     if device is None:
         device = next((w.device for w in waves if isinstance(w, torch.Tensor) and w.is_cuda), None)
         device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
-    pcm, clips = pack_clips(waves, device)
+    if input_sr is not None and np.ndim(input_sr) > 0 or any(_needs_front_end(w, input_sr, sr, channels) for w in waves):
+        from .resample import resample_many
+        pcm, clips = resample_many(waves, sr if input_sr is None else input_sr, sr, channels, device)
+    else:
+        pcm, clips = pack_clips(waves, device)
     for i, (_, n) in enumerate(clips):
         if n < 1:
             raise ValueError(f"clip {i} is empty")

@@ -361,7 +361,9 @@ class HipCRNN(nn.Module):
 
     def inference_plan(self, B=1, T=None):
         """What the eval forward of a [B, Cin, F, T] batch runs in under the current settings:
-        ``{"conv": ["f32" | "bf16", ...] per conv block, "proj": "f32" | "bf16"}`` (the GRU layer-0 input projection)."""
+        ``{"conv": ["f32" | "bf16", ...] per conv block, "proj": "f32" | "bf16"}`` (the GRU layer-0 input projection).
+        In front of the net, always fp32 and outside this plan: the resampler fuses sample-format conversion and downmix into its
+        load (resample.py, only for input at another rate or format), the log-mel kernel fuses the StandardScaler (feature.py)."""
         T = int(T) if T is not None else 32 * self.time_factor
         cfg = self._cfg(int(B), T, training=False)
         cb, pj = (C.c_int * _lib.SED_MAX_CONV)(), C.c_int(0)

@@ -145,7 +145,7 @@ class StreamDetector:
     """``EventDetector`` for audio that is still arriving, S streams at once (module docstring).  The keyword arguments are
     ``EventDetector``'s, checked the same way; ``max_new_windows``: windows per stream and step (longer pushes are split)."""
 
-    def __init__(self, model, n_streams, keep_probs=False, max_new_windows=4, _det=None, **kw):
+    def __init__(self, model, n_streams, keep_probs=False, max_new_windows=4, _det=None, input_sr=None, input_channels=1, **kw):
         self.det = _det if _det is not None else EventDetector(model, **kw)
         det, m = self.det, self.det.model
         S = int(n_streams)
@@ -176,12 +176,27 @@ class StreamDetector:
         self._ar = np.arange(S, dtype=np.int64)
         self._none = np.zeros(S, bool)
         self.marks = None                                                  # a list here receives (phase, start, end) hip events
+        # the resampling stage in front of push: None when push receives mono float PCM at the detector's rate
+        self.input_sr = det.sr if input_sr is None else int(input_sr)
+        self.input_channels = int(input_channels)
+        self._rs = None
+        if self.input_sr != det.sr or self.input_channels != 1:
+            from .resample import plan_for
+            if not 1 <= self.input_channels <= 64:
+                raise ValueError(f"input_channels must be 1..64, got {input_channels}")
+            plan = plan_for(self.input_sr, det.sr)
+            self._rs = plan
+            self._rCR = 2 if plan.identity else plan.carry                 # carry samples per half (the copy filter has half = 1)
+            self._rn, self._rm, self._rpar = z(), z(), z()                 # input samples received, outputs emitted, carry half
+            self._rcarry = self._rws = None
+        self.keep_pcm = False                                              # True: pcm_log[s] collects the resampled pieces of feed s
+        self.pcm_log = [[] for _ in range(S)]
 
     # ── sizes ──
     @property
     def state_bytes(self):
         """device bytes held between calls: the step's rings and decoder states, the feature rows and the PCM carry"""
-        return self._core_bytes + 4 * self.S * 2 * (self.FC * self.CF + self.CC)
+        return self._core_bytes + 4 * self.S * 2 * (self.FC * self.CF + self.CC + (self._rCR if self._rs is not None else 0))
 
     @property
     def frame_seconds(self):
@@ -382,12 +397,68 @@ class StreamDetector:
         return feature.cat_to_device([pieces[s] if takes[s] == lens[s] else pieces[s][done[s]:done[s] + takes[s]]
                                       for s in np.nonzero(takes)[0]], dev)
 
+    # ── the resampling stage: pieces at the input rate -> mono float32 pieces at the detector's rate ──
+    def _resample_round(self, pieces, lens, end):
+        """``pieces``: per feed a tensor of ``lens[s]`` sample frames (int16 or float32, all one dtype) or None; the feeds in
+        the mask ``end`` end: everything up to ceil(n L / M) comes out, zeros to their right.  One launch: the outputs that
+        became final, per feed as a view of one packed device buffer (None = none), and the feeds' next carry.  The host
+        keeps the int64 counters and reads nothing back."""
+        from .resample import _device_taps, build_rows, launch, pack_pcm
+        plan, S, CR = self._rs, self.S, self._rCR
+        dev = self._state.device
+        if self._rcarry is None:
+            self._rcarry = torch.zeros(S * 2 * CR, device=dev)
+        taps, L, M, half = _device_taps(plan.sr_in, plan.sr_out, dev.index or 0)
+        n_new = self._rn + lens
+        if plan.identity:
+            done = np.where(end, n_new, np.maximum(0, n_new - 1))          # the copy filter reads x[m + 1] (times zero)
+        else:
+            done = np.where(end, plan.n_out_array(n_new), plan.n_final_array(n_new))
+        act = (lens > 0) | (done > self._rm)
+        idx = np.nonzero(act)[0]
+        if idx.size == 0:
+            return [None] * S
+        n_hist = np.minimum(CR, self._rn)
+        base = self._ar * (2 * CR)
+        live = [pieces[s] for s in idx if lens[s] > 0]
+        x = pack_pcm(live, dev) if live else None
+        is16 = bool(live) and live[0].dtype == torch.int16
+        rows, _, n_outbuf = build_rows(lens[idx], self._rn[idx], self._rm[idx], (done - self._rm)[idx], n_hist[idx],
+                                       (base + self._rpar * CR + CR - n_hist)[idx],
+                                       np.where(end, -1, base + (1 - self._rpar) * CR)[idx])
+        out = torch.empty(max(n_outbuf, 1), device=dev)
+        self._rws = _timed(self.marks, "resample", lambda: launch(x, int(is16), self.input_channels, self._rcarry, taps, L, M, half,
+                                                                  rows, out, self._rws))
+        res = [None] * S
+        for r, s in enumerate(idx.tolist()):
+            if rows[r, 4]:
+                res[s] = out[rows[r, 5]:rows[r, 5] + rows[r, 4]]
+                if self.keep_pcm:
+                    self.pcm_log[s].append(res[s])
+        moved = act & ~end
+        self._rpar = np.where(moved, 1 - self._rpar, self._rpar)
+        self._rn, self._rm = np.where(act, n_new, self._rn), np.where(act, done, self._rm)
+        self._rn[end], self._rm[end], self._rpar[end] = 0, 0, 0
+        return res
+
     def push(self, chunks):
-        """a list of S mono PCM pieces (1-D, host or device, any length >= 0; None = nothing new) -> StreamEvents"""
+        """a list of S mono PCM pieces (1-D, host or device, any length >= 0; None = nothing new) -> StreamEvents.  With
+        ``input_sr`` / ``input_channels`` the pieces are at that rate, int16 or float (one dtype per push), ``[n, channels]``
+        interleaved, and pass through the resampling stage first."""
         m = self.det.model
         if m.in_channels != 1:
             raise ValueError(f"a mono waveform feeds a 1-channel net; this one has {m.in_channels} (use push_features)")
+        if self._rs is not None:
+            from .resample import as_pcm
+            pieces, lens = self._pieces(chunks, "waveform pieces", lambda s, c: as_pcm(c, self.input_channels, f"stream {s}"))
+            if len({p.dtype for p in pieces if p is not None}) > 1:
+                raise ValueError("the pieces of one push must share a sample format (all int16 or all floating point)")
+            self._ready()
+            chunks = self._resample_round(pieces, lens, self._none)
+        return self._push_mono(chunks)
 
+    def _push_mono(self, chunks):
+        """``push`` at the detector's own rate"""
         def one(s, c):
             c = c if isinstance(c, torch.Tensor) else torch.as_tensor(np.asarray(c))
             if c.dim() != 1:
@@ -440,9 +511,13 @@ class StreamDetector:
             if not 0 <= s < self.S:
                 raise ValueError(f"stream {s} of {self.S}")
         h, sc = self.det.hop_length, self.sched
+        held = np.zeros(self.S, np.int64)                                   # samples the resampling stage still owes
+        if self._rs is not None:
+            held = (self._rn if self._rs.identity else self._rs.n_out_array(self._rn)) - self._rm
         end = np.zeros(self.S, bool)
         for s in sorted(set(which)):
-            N = int(sc.N[s]) + (int(1 + self._n[s] // h - self._fdone[s]) if self._n[s] else 0)
+            n = int(self._n[s] + held[s])
+            N = int(sc.N[s]) + (int(1 + n // h - self._fdone[s]) if n else 0)
             if N == 0:
                 continue
             try:
@@ -451,6 +526,9 @@ class StreamDetector:
                 raise ValueError(f"stream {s}: {e}") from None
             end[s] = True
         self._ready()
+        first = None
+        if (held[end] > 0).any():                                           # what the resampler holds comes out first (zeros to its right)
+            first = self._push_mono(self._resample_round([None] * self.S, np.zeros(self.S, np.int64), end & (held > 0)))
 
         def rounds():
             if not end.any():
@@ -461,7 +539,24 @@ class StreamDetector:
             else:
                 mel, row0, rows = None, zero, zero
             yield mel, row0, rows, end
-        return self._run(rounds())
+        last = self._run(rounds())
+        return last if first is None else self._joined(first, last)
+
+    def _joined(self, a, b):
+        """two StreamEvents of one call as one: per stream a's events (and rows), then b's"""
+        K, dev = self.K, self._state.device
+        ev = {k: torch.cat([a.events[k], b.events[k]]) for k in _KEYS}
+        order = torch.sort(ev["stream"].long() * K + ev["cls"].long(), stable=True).indices
+        ev = {k: v[order] for k, v in ev.items()}
+        offs = (np.asarray(a.event_offsets) + np.asarray(b.event_offsets)).tolist()
+        probs = poffs = None
+        if self.keep_probs:
+            na, nb = np.diff(a.prob_offsets), np.diff(b.prob_offsets)
+            owner = np.concatenate([np.repeat(self._ar, na), np.repeat(self._ar, nb)])
+            idx = np.argsort(owner, kind="stable")
+            probs = torch.cat([a.probs, b.probs])[torch.from_numpy(idx).to(dev)]
+            poffs = np.concatenate([[0], np.cumsum(na + nb)]).tolist()
+        return StreamEvents(ev, offs, b.final_frames, self.frame_seconds, probs, poffs)
 
     def reset(self, streams=None):
         """drop these streams (default: all) where they stand: nothing is emitted, they restart at frame 0"""
@@ -474,6 +569,8 @@ class StreamDetector:
             check(lib().sed_stream_reset(ptr(self._state), self._state.numel(), *self._dims, ids, which.size, stream_ptr()),
                   "sed_stream_reset")
             self._reset_host(which)
+            if self._rs is not None:
+                self._rn[which], self._rm[which], self._rpar[which] = 0, 0, 0
 
     def active(self):
         """[(stream, cls, onset), ...] of the events that are open right now: a run that is known to be kept and has not closed
