@@ -447,6 +447,18 @@ size_t sed_logmel_batch_workspace_bytes(int R);
 int sed_logmel_batch(const float* pcm, long pcm_len, const long* clips_host, int R, const void* tables, size_t tables_bytes,
                      const float* mu, const float* inv_sigma, float* out, long out_rows, int n_fft, int hop, int n_mels,
                      int pad_mode, void* workspace, size_t workspace_bytes, void* stream);
+/* sed_logmel_multi: R recordings of `channels` planar channels each, all R*channels clips packed in ONE pcm buffer
+ * -> out [sum_r (1 + n_r/hop)][channels*n_mels], the [N, C*F] layout the nets read: clip (r, c) = entry r*channels + c of
+ * clips_host [R*channels][2] = {first sample, n >= 1} writes the rows of recording r, columns [c*n_mels, (c+1)*n_mels).  The
+ * channels of a recording must have equal length (validated on the host, with every clip's bounds; the message names the
+ * recording); out_rows must equal the frame total.  mu/inv_sigma (may both be NULL) have channels*n_mels entries, column
+ * c*n_mels + m for channel c, band m; they are kept in LDS, so the waves per workgroup are chosen with their real size and a
+ * scaler beside which not even 2 waves fit is refused.  Every channel's columns are bit for bit sed_logmel on that channel with
+ * its slice of the scaler; channels = 1 is bit for bit sed_logmel_batch.  1 <= channels <= 64. */
+size_t sed_logmel_multi_workspace_bytes(int R, int channels);
+int sed_logmel_multi(const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const void* tables,
+                     size_t tables_bytes, const float* mu, const float* inv_sigma, float* out, long out_rows, int n_fft, int hop,
+                     int n_mels, int pad_mode, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ───────────── audio at any sample rate: rational-ratio polyphase resampler, format conversion and downmix ─────────────
  * What the reference does with `ffmpeg -ac 1 -ar 44100` before feature.py:55.  L/M = sr_out/sr_in reduced; taps [L][2 half]
@@ -469,6 +481,20 @@ int sed_resample_check_table(const long* rows_host, int R, long x_frames, long h
 int sed_resample(const void* x, long x_frames, int format, int channels, float* hist, long hist_len, const float* taps,
                  long taps_len, int L, int M, int half, const long* rows_host, int R, float* out, long out_len, void* workspace,
                  size_t workspace_bytes, void* stream);
+/* sed_resample_select: sed_resample whose rows may KEEP a channel instead of downmixing.  rows_host [R][10]: the
+ * nine columns above and `channel`: -1 = the downmix of sed_resample; c in [0, channels) = the row reads only channel c of the
+ * interleaved frames, as the converted sample itself (int16 * 1/32768; no multiplication by 1/channels), so that the row equals
+ * sed_resample on the de-interleaved channel bit for bit, at any tile boundary, with history and carry and at any absolute
+ * base.  History and carry stay mono float32 and belong to the row: a live feed has one per (feed, channel).  Several rows may
+ * read the same frames (one row per channel of a clip).  sed_resample is this entry with every channel -1.  The workspace
+ * (sed_resample_select_workspace_bytes(R)) also holds the R channels; sed_resample_select_check_table is the validator without
+ * a GPU call: every check of sed_resample_check_table, and a channel outside [-1, channels) is refused. */
+size_t sed_resample_select_workspace_bytes(int R);
+int sed_resample_select_check_table(const long* rows_host, int R, int channels, long x_frames, long hist_len, long out_len, int L,
+                                    int M, int half);
+int sed_resample_select(const void* x, long x_frames, int format, int channels, float* hist, long hist_len, const float* taps,
+                        long taps_len, int L, int M, int half, const long* rows_host, int R, float* out, long out_len,
+                        void* workspace, size_t workspace_bytes, void* stream);
 
 /* ───────────── GPU-resident minibatch assembly (sed.py:64-79; decorte_datamodule.py:39-49,77-111; utils.py:15-41) ─────────────
  * mel [N][C*F] (a whole fold, device-resident; channel c = columns [c*F,(c+1)*F)), lab [N][K].

@@ -16,7 +16,7 @@ SOURCES = ["api.cpp", "conv.hip", "conv_bf16.hip", "wino.hip", "conv1.hip", "bnp
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # per-file extras.  logmel: the SLP vectoriser packs the FFT's scalar adds into v_pk_add_f32 and pays for it with ~600
 # v_mov per frame pair to build the register pairs (packed f32 is no faster than scalar on gfx950)
-EXTRA_FLAGS = {"logmel.hip": ["-fno-slp-vectorize"],
+EXTRA_FLAGS = {"logmel.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"],
                "conv.hip": ["-Rpass-analysis=kernel-resource-usage"],
                "wino.hip": ["-Rpass-analysis=kernel-resource-usage"],
                "conv_bf16.hip": ["-Rpass-analysis=kernel-resource-usage"]}
@@ -32,7 +32,10 @@ NO_SPILL_KERNELS = {"conv.hip": ("conv3x3_mfma_fwd2_k", "conv3x3_mfma_fwd_bf16x3
 # hipcc: a spill there is not a correctness hazard, it is a performance cliff nobody would notice — scratch must stay 0.
 NO_SCRATCH_KERNELS = {"wino.hip": ("conv3x3_wino_k",),
                       # bf16 inference: hipcc's own waits (no hand counts), accumulators may sit in AGPRs; a spill would be a cliff
-                      "conv_bf16.hip": ("conv3x3_bf16_eval_k", "gemm_bf16_nt_k")}
+                      "conv_bf16.hip": ("conv3x3_bf16_eval_k", "gemm_bf16_nt_k"),
+                      # log-mel: every instantiation sits a few registers below its waves-per-CU budget (the 12-wave ones at
+                      # 163-167 of 168); two more live values in the pair loop spill, and nothing else would say so
+                      "logmel.hip": ("logmel_fft_k",)}
 
 
 def _hipcc():

@@ -174,9 +174,16 @@ __device__ __forceinline__ float pcm_at(const float* __restrict__ pcm, long n, l
 // Batched (SEG): R clips packed back to back in one PCM buffer; the launch walks the frame pairs of all of them, clip by clip.
 // Device tables (uploaded by sed_logmel_batch): pair_off [R+1] (first pair of each clip; the last entry is the total),
 // sample_off / n_samples / row_off [R] (the clip's first sample, its length and its first output row); n_pairs = pair_off[R].
-struct LmBatch { const long* pair_off; const long* sample_off; const long* n_samples; const long* row_off; int R; long n_pairs; };
-// where one frame pair lives: its clip's PCM, length and frame count, the pair's index in the clip and the clip's first row
-struct LmSeg { const float* pcm; long n_samples, n_frames, pair, row0; };
+// Multichannel (MC, sed_logmel_multi): the R clips are the planar channels of R / C recordings.  The C clips of a
+// recording share row_off, and col_off [R] says where in a row of row_stride = C n_mels floats the clip's bands go (c n_mels:
+// the [N, C F] layout the nets read); scaler_w = C n_mels coefficients of each kind are staged, column col_off + m is band m's.
+struct LmBatch {
+    const long* pair_off; const long* sample_off; const long* n_samples; const long* row_off; int R; long n_pairs;
+    const long* col_off; int row_stride; int scaler_w;
+};
+// where one frame pair lives: its clip's PCM, length and frame count, the pair's index in the clip, the clip's first row and
+// (MC) its first column
+struct LmSeg { const float* pcm; long n_samples, n_frames, pair, row0; int col0; };
 
 __device__ __forceinline__ long uniform_long(long v) {       // v is wave-uniform: say so, so that what it addresses stays scalar
     const unsigned long long u = (unsigned long long)v;
@@ -185,9 +192,9 @@ __device__ __forceinline__ long uniform_long(long v) {       // v is wave-unifor
 }
 
 // Both frames of a pair belong to one clip, so the lookup (a binary search over pair_off) is wave-uniform.
-template <bool SEG>
+template <bool SEG, bool MC>
 __device__ __forceinline__ LmSeg lm_locate(long pair, const float* pcm, long n_samples, long n_frames, const LmBatch& bt, int hop) {
-    if (!SEG) return LmSeg{pcm, n_samples, n_frames, pair, 0};
+    if (!SEG) return LmSeg{pcm, n_samples, n_frames, pair, 0, 0};
     pair = uniform_long(pair);
     int lo = 0, hi = bt.R - 1;                               // the last clip whose first pair is <= pair
     while (lo < hi) {
@@ -197,13 +204,15 @@ __device__ __forceinline__ LmSeg lm_locate(long pair, const float* pcm, long n_s
     }
     const int c = __builtin_amdgcn_readfirstlane(lo);
     const long ns = bt.n_samples[c];
-    return LmSeg{pcm + bt.sample_off[c], ns, 1 + ns / hop, pair - bt.pair_off[c], bt.row_off[c]};
+    return LmSeg{pcm + bt.sample_off[c], ns, 1 + ns / hop, pair - bt.pair_off[c], bt.row_off[c], MC ? __builtin_amdgcn_readfirstlane((int)bt.col_off[c]) : 0};
 }
 
 // DB: the next pair's PCM goes to a second register set one iteration ahead (needs the 256 registers of <= 8 waves per CU);
 // otherwise it is loaded into the FFT registers before the mel pass of the current pair (they are dead by then).
 // SEG: the batched launch (LmBatch above; n_samples / n_frames are then unused).  The FFT, mel and scaler code is the same.
-template <int WPB, bool SEG = false, bool DB = (WPB <= 8)>
+// MC (with SEG): the output addressing of sed_logmel_multi — a row stride and a per-clip column offset, and a scaler as wide as
+// the row.  A template parameter, so that the instantiations sed_logmel and sed_logmel_batch launch are the code they were.
+template <int WPB, bool SEG = false, bool DB = (WPB <= 8), bool MC = false>
 __global__ __launch_bounds__(WPB * 64) void logmel_fft_k(const float* __restrict__ pcm, long n_samples,
                                                          const uint32_t* __restrict__ tables, int table_words,
                                                          const float* __restrict__ mu, const float* __restrict__ inv_sigma,
@@ -217,11 +226,16 @@ __global__ __launch_bounds__(WPB * 64) void logmel_fft_k(const float* __restrict
         for (int i = tid; i < table_words / 4; i += WPB * 64) dst[i] = src[i];
     }
     // the fused scaler's coefficients go to LDS too: a global load inside the loop would have to retire IN ORDER behind the
-    // PCM prefetch of the next pair (vmcnt counts in order), i.e. wait for exactly the latency the prefetch is there to hide
+    // PCM prefetch of the next pair (vmcnt counts in order), i.e. wait for exactly the latency the prefetch is there to hide.
+    // That holds all the more for the C n_mels coefficients of a multichannel scaler: which slice a wave needs changes with
+    // the clip of its pair, so a register copy per wave would have to be reloaded from global memory inside the loop — the
+    // whole row of coefficients is staged instead (2 C n_mels floats, counted in the launch's LDS size).
     float* s_mu = lds + table_words + WPB * 2 * LM_FRAME_SCR;
-    float* s_is = s_mu + LM_MAX_MELS;
-    if (mu)
-        for (int i = tid; i < n_mels_out && i < LM_MAX_MELS; i += WPB * 64) { s_mu[i] = mu[i]; s_is[i] = inv_sigma[i]; }
+    float* s_is = s_mu + (MC ? bt.scaler_w : LM_MAX_MELS);
+    if (mu) {
+        if (MC) for (int i = tid; i < bt.scaler_w; i += WPB * 64) { s_mu[i] = mu[i]; s_is[i] = inv_sigma[i]; }
+        else for (int i = tid; i < n_mels_out && i < LM_MAX_MELS; i += WPB * 64) { s_mu[i] = mu[i]; s_is[i] = inv_sigma[i]; }
+    }
     __syncthreads();
     const uint32_t* hdr = reinterpret_cast<const uint32_t*>(lds);
     // the row length of `out` is the caller's n_mels; a blob built for more bands than that never writes past a row
@@ -263,7 +277,7 @@ __global__ __launch_bounds__(WPB * 64) void logmel_fft_k(const float* __restrict
     f2 zn[DB ? 32 : 1];
     const long stride = (long)gridDim.x * WPB;
     const long pair0 = (long)blockIdx.x * WPB + wave;
-    LmSeg cur = lm_locate<SEG>(pair0 < n_pairs ? pair0 : 0, pcm, n_samples, n_frames, bt, hop);
+    LmSeg cur = lm_locate<SEG, MC>(pair0 < n_pairs ? pair0 : 0, pcm, n_samples, n_frames, bt, hop);
     bool nloaded = DB && pair0 < n_pairs && fast_ok(cur);
     if (DB && nloaded) {
         const f2* src = reinterpret_cast<const f2*>(cur.pcm + (cur.pair * 2 + half) * hop - LM_NFFT / 2) + r;
@@ -272,7 +286,7 @@ __global__ __launch_bounds__(WPB * 64) void logmel_fft_k(const float* __restrict
     }
     for (long pair = pair0; pair < n_pairs; pair += stride) {
         // the next pair (its clip when batched): what the prefetch below loads, and this loop's state one iteration from now
-        const LmSeg nxt = lm_locate<SEG>(pair + stride < n_pairs ? pair + stride : pair, pcm, n_samples, n_frames, bt, hop);
+        const LmSeg nxt = lm_locate<SEG, MC>(pair + stride < n_pairs ? pair + stride : pair, pcm, n_samples, n_frames, bt, hop);
         long frame = cur.pair * 2 + half;
         const bool live = frame < cur.n_frames;
         if (!live) frame = cur.n_frames - 1;                 // odd tail: the upper half recomputes the last frame, stores nothing
@@ -425,8 +439,8 @@ __global__ __launch_bounds__(WPB * 64) void logmel_fft_k(const float* __restrict
                 v += part[l.w & 0xffffu];
                 v += part[l.w >> 16];
                 v = logf(v);
-                if (mu) v = (v - s_mu[m]) * s_is[m];
-                if (live) out[(cur.row0 + frame) * n_mels_out + m] = v;
+                if (mu) v = MC ? (v - s_mu[cur.col0 + m]) * s_is[cur.col0 + m] : (v - s_mu[m]) * s_is[m];
+                if (live) out[MC ? (cur.row0 + frame) * bt.row_stride + cur.col0 + m : (cur.row0 + frame) * n_mels_out + m] = v;
             }
         } else {
             // ── list plan: lane r walks entries [r*iters, (r+1)*iters) of the band-major list ──
@@ -447,13 +461,13 @@ __global__ __launch_bounds__(WPB * 64) void logmel_fft_k(const float* __restrict
             }
             wave_lds_fence();
             for (int m = r; m < n_mels; m += 32) {
-                const uint32_t bt = s_band[m];
-                const int f0 = (int)(bt & 0xffffu), cnt = (int)(bt >> 16);
+                const uint32_t bd = s_band[m];
+                const int f0 = (int)(bd & 0xffffu), cnt = (int)(bd >> 16);
                 float v = 0.f;
                 for (int j = 0; j < cnt; ++j) v += part[f0 + j];
                 v = logf(v);
-                if (mu) v = (v - s_mu[m]) * s_is[m];
-                if (live) out[(cur.row0 + frame) * n_mels_out + m] = v;
+                if (mu) v = MC ? (v - s_mu[cur.col0 + m]) * s_is[cur.col0 + m] : (v - s_mu[m]) * s_is[m];
+                if (live) out[MC ? (cur.row0 + frame) * bt.row_stride + cur.col0 + m : (cur.row0 + frame) * n_mels_out + m] = v;
             }
         }
         cur = nxt;
@@ -610,48 +624,56 @@ extern "C" int sed_logmel_build_tables(const float* window_host, const float* me
 // 12 waves per CU: the most that fit beside the tables (12 x 9.7 KB of exchange / power scratch + 38 KB of tables in 160 KB)
 #define LM_WPB 12
 #define LM_SCALER_BYTES ((size_t)2 * LM_MAX_MELS * sizeof(float))      // mean and 1/sigma of the fused scaler, behind the wave scratch
-template <int WPB, bool SEG>
+// scaler_bytes: the LDS behind the wave scratch that holds the scaler (LM_SCALER_BYTES for sed_logmel / sed_logmel_batch, the real
+// 2 C n_mels floats — nothing without a scaler — for sed_logmel_multi)
+template <int WPB, bool SEG, bool MC>
 static int launch_logmel(const float* pcm, long n_samples, const void* tables, int words, const float* mu, const float* inv_sigma,
-                         float* out, long frames, int hop, int n_mels, int pad_mode, const LmBatch& bt, hipStream_t s) {
-    const size_t lds = (size_t)words * 4 + (size_t)WPB * 2 * LM_FRAME_SCR * sizeof(float) + LM_SCALER_BYTES;
+                         float* out, long frames, int hop, int n_mels, int pad_mode, const LmBatch& bt, size_t scaler_bytes, hipStream_t s) {
+    const size_t lds = (size_t)words * 4 + (size_t)WPB * 2 * LM_FRAME_SCR * sizeof(float) + scaler_bytes;
     SED_REQUIRE(lds <= 160 * 1024, "logmel: tables + scratch (%zu B) exceed the 160 KiB LDS", lds);
-    hipError_t e = hipFuncSetAttribute((const void*)logmel_fft_k<WPB, SEG>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipError_t e = hipFuncSetAttribute((const void*)logmel_fft_k<WPB, SEG, (WPB <= 8), MC>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) { sed_set_error("logmel: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
     const long pairs = SEG ? bt.n_pairs : (frames + 1) / 2;
     long blocks = (pairs + WPB - 1) / WPB;
     const long resident = 256;                               // one persistent workgroup per CU: the tables are loaded once each
     if (blocks > resident) blocks = resident;
     SedProfScope prof(SED_K_LOGMEL, s, (double)frames * ((double)hop + n_mels) * 4.0);
-    logmel_fft_k<WPB, SEG><<<(unsigned)blocks, WPB * 64, lds, s>>>(pcm, n_samples, (const uint32_t*)tables, words, mu, inv_sigma,
-                                                                   out, frames, hop, pad_mode, n_mels, bt);
+    logmel_fft_k<WPB, SEG, (WPB <= 8), MC><<<(unsigned)blocks, WPB * 64, lds, s>>>(pcm, n_samples, (const uint32_t*)tables, words, mu,
+                                                                                   inv_sigma, out, frames, hop, pad_mode, n_mels, bt);
     SED_LAUNCH_CHECK("logmel");
     return 0;
 }
 
 // 12 waves per workgroup when the tables leave room for their scratch (the two-band plan of a Slaney bank: 38 KB); a large
 // list plan (up to 8 192 non-zeros = 67 KB of entries) runs with fewer waves per CU rather than being refused
-template <bool SEG>
+template <bool SEG, bool MC = false>
 static int launch_logmel_any(const float* pcm, long n_samples, const void* tables, int words, const float* mu, const float* inv_sigma,
-                             float* out, long frames, int hop, int n_mels, int pad_mode, const LmBatch& bt, hipStream_t s) {
-    const size_t per_wave = (size_t)2 * LM_FRAME_SCR * sizeof(float), room = (size_t)160 * 1024 - LM_SCALER_BYTES;
+                             float* out, long frames, int hop, int n_mels, int pad_mode, const LmBatch& bt, hipStream_t s,
+                             size_t scaler_bytes = LM_SCALER_BYTES) {
+    const size_t per_wave = (size_t)2 * LM_FRAME_SCR * sizeof(float), room = (size_t)160 * 1024 - scaler_bytes;
     const size_t tb = (size_t)words * 4;
-    if (tb + 12 * per_wave <= room) return launch_logmel<12, SEG>(pcm, n_samples, tables, words, mu, inv_sigma, out, frames, hop, n_mels, pad_mode, bt, s);
-    if (tb + 8 * per_wave <= room) return launch_logmel<8, SEG>(pcm, n_samples, tables, words, mu, inv_sigma, out, frames, hop, n_mels, pad_mode, bt, s);
-    if (tb + 4 * per_wave <= room) return launch_logmel<4, SEG>(pcm, n_samples, tables, words, mu, inv_sigma, out, frames, hop, n_mels, pad_mode, bt, s);
-    return launch_logmel<2, SEG>(pcm, n_samples, tables, words, mu, inv_sigma, out, frames, hop, n_mels, pad_mode, bt, s);
+    if (tb + 12 * per_wave <= room) return launch_logmel<12, SEG, MC>(pcm, n_samples, tables, words, mu, inv_sigma, out, frames, hop, n_mels, pad_mode, bt, scaler_bytes, s);
+    if (tb + 8 * per_wave <= room) return launch_logmel<8, SEG, MC>(pcm, n_samples, tables, words, mu, inv_sigma, out, frames, hop, n_mels, pad_mode, bt, scaler_bytes, s);
+    if (tb + 4 * per_wave <= room) return launch_logmel<4, SEG, MC>(pcm, n_samples, tables, words, mu, inv_sigma, out, frames, hop, n_mels, pad_mode, bt, scaler_bytes, s);
+    return launch_logmel<2, SEG, MC>(pcm, n_samples, tables, words, mu, inv_sigma, out, frames, hop, n_mels, pad_mode, bt, scaler_bytes, s);
 }
 
 // the argument checks both entries share
 static int logmel_check_args(const void* tables, size_t tables_bytes, const float* mu, const float* inv_sigma, int n_fft, int hop,
-                             int n_mels, int pad_mode) {
+                             int n_mels, int pad_mode, bool multi = false, size_t scaler_bytes = LM_SCALER_BYTES) {
     SED_REQUIRE(n_fft == LM_NFFT, "logmel: n_fft must be %d (got %d)", LM_NFFT, n_fft);
     SED_REQUIRE(hop > 0 && n_mels > 0 && n_mels <= LM_MAX_MELS, "logmel: bad sizes");
     SED_REQUIRE((mu == nullptr) == (inv_sigma == nullptr), "logmel: mu and inv_sigma go together");
     SED_REQUIRE(pad_mode == 0 || pad_mode == 1, "logmel: pad_mode must be 0 (constant) or 1 (reflect)");
     const int words = (int)(tables_bytes / 4);
     SED_REQUIRE(tables_bytes % 16 == 0 && words >= LM_OFF_ENT + 64 + n_mels, "logmel: table blob of %zu bytes is malformed", tables_bytes);
-    SED_REQUIRE((size_t)words * 4 + (size_t)2 * 2 * LM_FRAME_SCR * sizeof(float) + LM_SCALER_BYTES <= (size_t)160 * 1024,
-                "logmel: a table blob of %zu bytes leaves no room for the FFT scratch in the 160 KiB LDS", tables_bytes);
+    if (!multi)
+        SED_REQUIRE((size_t)words * 4 + (size_t)2 * 2 * LM_FRAME_SCR * sizeof(float) + LM_SCALER_BYTES <= (size_t)160 * 1024,
+                    "logmel: a table blob of %zu bytes leaves no room for the FFT scratch in the 160 KiB LDS", tables_bytes);
+    else                                                     // sed_logmel_multi: the scaler is as wide as the feature row
+        SED_REQUIRE((size_t)words * 4 + (size_t)2 * 2 * LM_FRAME_SCR * sizeof(float) + scaler_bytes <= (size_t)160 * 1024,
+                    "logmel_multi: a table blob of %zu bytes and a scaler of %zu bytes leave no room for the FFT scratch of even 2 "
+                    "waves (%zu bytes) in the 160 KiB LDS", tables_bytes, scaler_bytes, (size_t)2 * 2 * LM_FRAME_SCR * sizeof(float));
     return 0;
 }
 
@@ -702,4 +724,55 @@ extern "C" int sed_logmel_batch(const float* pcm, long pcm_len, const long* clip
     if (e != hipSuccess) { sed_set_error("logmel_batch: upload of the clip table: %s", hipGetErrorString(e)); return (int)e; }
     const LmBatch bt{dev, dev + R + 1, dev + 2 * R + 1, dev + 3 * R + 1, R, pairs};
     return launch_logmel_any<true>(pcm, pcm_len, tables, (int)(tables_bytes / 4), mu, inv_sigma, out, rows, hop, n_mels, pad_mode, bt, s);
+}
+
+// ───────────────────────── multichannel: R recordings x C planar channels -> one [rows][C n_mels] matrix, one launch ─────────────────────────
+// workspace: pair_off [RC+1], sample_off, n_samples, row_off, col_off [RC] (64-bit), uploaded from the validated host table
+extern "C" size_t sed_logmel_multi_workspace_bytes(int R, int channels) {
+    if (R < 1 || channels < 1 || channels > 64 || (long)R * channels > (1 << 26)) return 0;
+    return ((size_t)5 * R * channels + 1) * sizeof(long);
+}
+
+extern "C" int sed_logmel_multi(const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const void* tables,
+                                size_t tables_bytes, const float* mu, const float* inv_sigma, float* out, long out_rows, int n_fft, int hop,
+                                int n_mels, int pad_mode, void* workspace, size_t workspace_bytes, void* stream) {
+    SED_REQUIRE(channels >= 1 && channels <= 64, "logmel_multi: 1 to 64 channels, got %d", channels);
+    SED_REQUIRE(pcm && clips_host && tables && out && workspace, "logmel_multi: null pointer");
+    const size_t need = sed_logmel_multi_workspace_bytes(R, channels);
+    SED_REQUIRE(need > 0 && pcm_len > 0, "logmel_multi: bad sizes (R=%d, channels=%d, pcm_len=%ld)", R, channels, pcm_len);
+    SED_REQUIRE(workspace_bytes >= need, "logmel_multi: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    SED_REQUIRE(n_mels > 0 && n_mels <= LM_MAX_MELS, "logmel: bad sizes");
+    const size_t scaler_bytes = mu ? (size_t)2 * channels * n_mels * sizeof(float) : 0;
+    if (int rc = logmel_check_args(tables, tables_bytes, mu, inv_sigma, n_fft, hop, n_mels, pad_mode, true, scaler_bytes)) return rc;
+    const long RC = (long)R * channels;
+    std::vector<long> h((size_t)5 * RC + 1);
+    long* pair_off = h.data();
+    long *soff = pair_off + RC + 1, *slen = soff + RC, *roff = slen + RC, *coff = roff + RC;
+    long pairs = 0, rows = 0;
+    for (int r = 0; r < R; ++r) {
+        const long n0 = clips_host[2 * ((long)r * channels) + 1];
+        const long f = n0 >= 1 ? 1 + n0 / hop : 0;
+        for (int ch = 0; ch < channels; ++ch) {
+            const long c = (long)r * channels + ch, o = clips_host[2 * c], n = clips_host[2 * c + 1];
+            SED_REQUIRE(o >= 0 && n >= 1 && o <= pcm_len && n <= pcm_len - o,
+                        "logmel_multi: recording %d, channel %d (offset %ld, %ld samples) is not inside the PCM buffer of %ld samples", r, ch,
+                        o, n, pcm_len);
+            SED_REQUIRE(n == n0, "logmel_multi: recording %d: channel %d has %ld samples, channel 0 has %ld (the channels of a recording "
+                        "must have equal length)", r, ch, n, n0);
+            pair_off[c] = pairs; soff[c] = o; slen[c] = n; roff[c] = rows; coff[c] = (long)ch * n_mels;
+            pairs += (f + 1) / 2;
+        }
+        rows += f;
+        SED_REQUIRE(rows <= 0x7fffffffL, "logmel_multi: more than 2^31 - 1 feature frames in one batch");
+    }
+    pair_off[RC] = pairs;
+    SED_REQUIRE(out_rows == rows, "logmel_multi: out has %ld rows, the recordings make %ld", out_rows, rows);
+    hipStream_t s = as_stream(stream);
+    long* dev = (long*)workspace;
+    hipError_t e = hipMemcpyAsync(dev, h.data(), h.size() * sizeof(long), hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) { sed_set_error("logmel_multi: upload of the clip table: %s", hipGetErrorString(e)); return (int)e; }
+    const LmBatch bt{dev, dev + RC + 1, dev + 2 * RC + 1, dev + 3 * RC + 1, (int)RC, pairs, dev + 4 * RC + 1, channels * n_mels,
+                     channels * n_mels};
+    return launch_logmel_any<true, true>(pcm, pcm_len, tables, (int)(tables_bytes / 4), mu, inv_sigma, out, rows, hop, n_mels, pad_mode,
+                                         bt, s, scaler_bytes);
 }

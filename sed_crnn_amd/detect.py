@@ -226,7 +226,8 @@ class EventDetector:
     ``combine`` "mean" | "max" over overlapping windows; ``trim`` output frames dropped at interior window edges;
     ``threshold`` (hi) / ``low`` (lo, default = threshold): runs of p' > lo kept when max p' > hi; ``median`` odd filter width
     in output frames (1 = off); ``min_gap`` merge events separated by at most that many frames; ``min_len`` drop shorter
-    events; ``mean`` / ``std``: the float64 [F] scaler of ``data.standard_scaler_fit``, fused into the log-mel front end."""
+    events; ``mean`` / ``std``: the float64 [C*F] scaler of ``data.standard_scaler_fit`` (one entry per feature column: [F] for a
+    1-channel net), fused into the log-mel front end."""
 
     def __init__(self, model, seq_len=SEQ_LEN_IN, hop=None, combine="mean", trim=0, threshold=0.5, low=None, median=1,
                  min_gap=0, min_len=1, mean=None, std=None, sr=feature.SR, hop_length=feature.HOP, max_batch=1024):
@@ -253,6 +254,12 @@ class EventDetector:
         self.median, self.min_gap, self.min_len = int(median), int(min_gap), int(min_len)
         self.mean = None if mean is None else torch.as_tensor(mean, dtype=torch.float64)      # numpy or device tensors
         self.std = None if std is None else torch.as_tensor(std, dtype=torch.float64)
+        if self.mean is not None and model.in_channels > 1:
+            CF = model.in_channels * model.n_mels
+            if self.mean.numel() != CF or self.std.numel() != CF:
+                raise ValueError(f"a {model.in_channels}-channel net with {model.n_mels} mel bands needs mean / std of width "
+                                 f"{model.in_channels}*{model.n_mels} = {CF} (data.standard_scaler_fit on [N, C*F] features), got "
+                                 f"{self.mean.numel()} / {self.std.numel()}")
         self.sr, self.hop_length, self.max_batch = int(sr), int(hop_length), int(max_batch)
         plan_windows(4 * self.seq_len, model.time_factor, self.seq_len, self.hop, self.trim)     # validate the grid now
         self.max_events = 256                   # grows to the largest count seen
@@ -317,10 +324,18 @@ class EventDetector:
         """mono PCM (1-D tensor / ndarray) -> DetectionResult.  The log-mel front end is ``feature.mbe(..., mean, std)``.
         ``sr`` / ``channels``: the waveform is at that rate (default: the detector's), int16 or float, ``[N, channels]``
         interleaved, and is converted, downmixed and resampled to the detector's rate on the device first; event
-        times need no change, they are in seconds at the detector's rate."""
-        self._check_model()
+        times need no change, they are in seconds at the detector's rate.  A net with ``in_channels = C > 1`` takes
+        ``[N, C]`` interleaved PCM with ``channels=C``: the channels are kept, each resampled and turned into its own feature
+        columns; nothing is mixed down and a mono signal is not duplicated."""
         if self.model.in_channels != 1:
-            raise ValueError(f"a mono waveform feeds a 1-channel net; this one has {self.model.in_channels} (use from_features)")
+            self._check_channels(channels)
+            self._check_model()
+            dev = self.model.flat_parameters().device
+            with torch.no_grad():
+                mel = feature.mbe(waveform, sr=self.sr, hop=self.hop_length, n_mels=self.model.n_mels, mean=self.mean, std=self.std,
+                                  input_sr=sr, channels=channels, keep_channels=True, device=dev)
+            return self.from_features(mel)
+        self._check_model()
         if feature._needs_front_end(waveform, sr, self.sr, channels):
             from .resample import resample
             waveform = resample(waveform, self.sr if sr is None else sr, self.sr, channels, self.model.flat_parameters().device)
@@ -332,6 +347,14 @@ class EventDetector:
             mel = feature.mbe(y.to(dev, torch.float32), sr=self.sr, hop=self.hop_length, n_mels=self.model.n_mels,
                               mean=self.mean, std=self.std)
         return self.from_features(mel)
+
+    def _check_channels(self, channels):
+        """a multichannel net takes exactly its own channel count: no mix-down, no duplication of a mono signal"""
+        C_in = self.model.in_channels
+        if int(channels) != C_in:
+            raise ValueError(f"a {C_in}-channel net takes [N, {C_in}] interleaved PCM with channels={C_in}, got channels={int(channels)}: "
+                             f"there is no mix-down to fewer channels and no duplication of a mono signal (scaled features go "
+                             f"through from_features)")
 
     def from_features(self, mel):
         """Scaled features [N, C*F] (the .npz cache layout; channel c = columns [c*F, (c+1)*F)) -> DetectionResult."""
@@ -446,15 +469,18 @@ class EventDetector:
         (``feature.mbe_many``, fused scaler), then ``from_features_many``'s path.  A clip shorter than one output frame
         raises ValueError naming its index before anything runs.  ``sr`` (one rate, or one per clip) / ``channels``: as in
         ``__call__``; the clips of one rate are resampled in one launch, straight into the buffer the log-mel launch reads.
+        A net with ``in_channels = C > 1`` takes ``[N, C]`` clips with ``channels=C``: one launch per (rate, format) group writes
+        the planar channels of its clips, one ``sed_logmel_multi`` launch turns all of them into ``[sum N, C*F]``.
 
         Memory, per input frame (hop_length samples): the packed PCM (4*hop_length B), the packed features (4*n_mels B),
         the flat logits (4*K*seq_len/hop/tf B: every frame is in seq_len/hop windows) and the track (4*K/tf B); the window
         buffer is bounded by max_batch windows, the decoder's bit tracks take 2 bits per output frame and class."""
         m = self.model
-        if m.in_channels != 1:
-            raise ValueError(f"a mono waveform feeds a 1-channel net; this one has {m.in_channels} (use from_features_many)")
         waves = list(waveforms)
-        front = sr is not None and np.ndim(sr) > 0 or any(feature._needs_front_end(w, sr, self.sr, channels) for w in waves)
+        multi = m.in_channels != 1                                         # [N, C] clips, channels kept (DESIGN 5k)
+        if multi:
+            self._check_channels(channels)
+        front = multi or sr is not None and np.ndim(sr) > 0 or any(feature._needs_front_end(w, sr, self.sr, channels) for w in waves)
         if front:
             from .resample import _rates, as_pcm, plan_for
             waves = [as_pcm(w, channels, f"recording {i}") for i, w in enumerate(waves)]
@@ -475,7 +501,8 @@ class EventDetector:
         dev = m.flat_parameters().device
         with torch.no_grad():
             mel, _ = feature.mbe_many(waves, sr=self.sr, hop=self.hop_length, n_mels=m.n_mels, mean=self.mean, std=self.std,
-                                      device=dev, **(dict(input_sr=rates, channels=channels) if front else {}))
+                                      device=dev, **(dict(input_sr=rates, channels=channels) if front else {}),
+                                      **(dict(keep_channels=True) if multi else {}))
             return self._detect_packed(mel, bp)
 
     def from_features_many(self, mels):

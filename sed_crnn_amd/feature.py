@@ -111,14 +111,20 @@ def _needs_front_end(w, input_sr, sr, channels):
 
 
 def mbe(y, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, pad_mode="constant", mean=None, std=None, tables=None, input_sr=None,
-        channels=1):
+        channels=1, keep_channels=False, device=None):
     """y: mono float32 PCM CUDA tensor [N] -> [1 + N//hop, n_mels] log-mel energies (natural log, no eps).
     ``tables`` = build_tables(window, melfb, device) replaces librosa's default window / filterbank.
     ``input_sr`` / ``channels``: y is at that rate (default: ``sr``), int16 or float, ``[N, channels]`` interleaved when
-    channels > 1 (host or device), and is converted, downmixed and resampled to ``sr`` on the device first (resample.py)."""
+    channels > 1 (host or device), and is converted, downmixed and resampled to ``sr`` on the device first (resample.py).
+    ``keep_channels=True``: the channels are kept, not mixed -> ``[1 + N'//hop, channels*n_mels]``, channel c in columns
+    ``[c*n_mels, (c+1)*n_mels)`` (the layout the nets read), each bit for bit ``mbe(y[:, c])``; ``mean`` / ``std`` are then
+    ``channels*n_mels`` wide.  ``device``: where a host clip that goes through resample.py is put."""
+    if keep_channels:
+        return mbe_many([y], sr=sr, n_fft=n_fft, hop=hop, n_mels=n_mels, pad_mode=pad_mode, mean=mean, std=std, tables=tables,
+                        device=device, input_sr=input_sr, channels=channels, keep_channels=True)[0]
     if _needs_front_end(y, input_sr, sr, channels):
         from .resample import resample
-        y = resample(y, sr if input_sr is None else input_sr, sr, channels)
+        y = resample(y, sr if input_sr is None else input_sr, sr, channels, device)
     if not (isinstance(y, torch.Tensor) and y.is_cuda):
         raise RuntimeError("sed_crnn_amd.feature.mbe needs a CUDA(HIP) tensor; there is no CPU fallback")
     if pad_mode not in ("constant", "reflect"):
@@ -169,6 +175,54 @@ def mbe_packed(pcm, clips, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, pad_mode="
     return out, rows
 
 
+def mbe_planar(pcm, clips, channels, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, pad_mode="constant", mean=None, std=None,
+               tables=None):
+    """The multichannel twin of ``mbe_packed``: R recordings of ``channels`` planar channels each, all in ONE mono float32 CUDA
+    buffer ``pcm``; ``clips`` = [(first sample, n_samples >= 1), ...] has ``R * channels`` entries, recording r, channel c at
+    ``r * channels + c`` (what ``resample_many(..., keep_channels=True)`` returns), the channels of a recording equally long
+    -> (features [sum_r (1 + n_r//hop), channels*n_mels], row offsets [R+1] as a host list), in one launch
+    (``sed_logmel_multi``).  Columns ``[c*n_mels, (c+1)*n_mels)`` are bit for bit ``mbe`` of channel c with that slice of
+    ``mean`` / ``std`` (``channels*n_mels`` wide: ``data.standard_scaler_fit`` on such features)."""
+    import ctypes as C
+    if not (isinstance(pcm, torch.Tensor) and pcm.is_cuda and pcm.dim() == 1):
+        raise RuntimeError("sed_crnn_amd.feature.mbe_planar needs a 1-D CUDA(HIP) PCM buffer; there is no CPU fallback")
+    if pad_mode not in ("constant", "reflect"):
+        raise ValueError(f"pad_mode must be 'constant' or 'reflect', got {pad_mode!r}")
+    nc = int(channels)
+    if not 1 <= nc <= 64:
+        raise ValueError(f"channels must be 1..64, got {channels}")
+    table = np.ascontiguousarray(np.asarray(clips, dtype=np.int64).reshape(-1, 2))
+    if table.shape[0] % nc:
+        raise ValueError(f"{table.shape[0]} clips are not a whole number of recordings of {nc} channels")
+    R = table.shape[0] // nc
+    for i, (o, n) in enumerate(table.tolist()):
+        if n < 1 or o < 0 or o + n > pcm.numel():
+            raise ValueError(f"recording {i // nc}, channel {i % nc} (first sample {o}, {n} samples) is empty or not inside the "
+                             f"buffer of {pcm.numel()} samples")
+        if n != table[i - i % nc, 1]:
+            raise ValueError(f"recording {i // nc}: channel {i % nc} has {n} samples, channel 0 has {int(table[i - i % nc, 1])}")
+    if tables is None:
+        tables = _tables(pcm.device.index or 0, sr, n_fft, n_mels)
+    else:
+        n_mels = _validated_mels(tables)
+    if R == 0:
+        return torch.empty(0, nc * n_mels, device=pcm.device), [0]
+    rows = np.concatenate([[0], np.cumsum(1 + table[::nc, 1] // hop)]).tolist()
+    if rows[-1] >= 2 ** 31:
+        raise ValueError(f"{rows[-1]} feature frames in one batch: at most 2^31 - 1")
+    if mean is not None and (mean.numel() != nc * n_mels or std.numel() != nc * n_mels):
+        raise ValueError(f"mean / std must have {nc}*{n_mels} = {nc * n_mels} entries (channel c, band m at c*{n_mels} + m), got "
+                         f"{mean.numel()} / {std.numel()}")
+    out = torch.empty(rows[-1], nc * n_mels, device=pcm.device)
+    pcm = pcm.contiguous().float()
+    mean, inv = _scaler(mean, std, pcm.device)
+    ws = torch.empty(lib().sed_logmel_multi_workspace_bytes(R, nc), dtype=torch.uint8, device=pcm.device)
+    check(lib().sed_logmel_multi(ptr(pcm), pcm.numel(), C.c_void_p(table.ctypes.data), R, nc, ptr(tables), tables.numel() * 4,
+                                 ptr(mean), ptr(inv), ptr(out), rows[-1], n_fft, hop, n_mels,
+                                 {"constant": 0, "reflect": 1}[pad_mode], ptr(ws), ws.numel(), stream_ptr()), "sed_logmel_multi")
+    return out, rows
+
+
 def pack_clips(waves, device):
     """a list of 1-D clips (host arrays or tensors, any device) -> (one float32 buffer on ``device``, [(first sample, n), ...]);
     every clip starts on a 16-byte boundary.  Host clips travel in one copy, device clips are joined by one torch.cat."""
@@ -192,15 +246,25 @@ def pack_clips(waves, device):
 
 
 def mbe_many(waves, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, pad_mode="constant", mean=None, std=None, tables=None,
-             device=None, input_sr=None, channels=1):
+             device=None, input_sr=None, channels=1, keep_channels=False):
     """``mbe`` of every clip in a list of 1-D clips (host or device; ``device`` defaults to the first CUDA clip's, else
     cuda:current) in one launch -> (features [sum_r (1 + n_r//hop), n_mels] in clip order, row offsets [R+1] host list).
     Bit for bit ``torch.cat([mbe(w) for w in waves])``.  ``input_sr`` (one rate, or one per clip) / ``channels``: as in
-    ``mbe``; the clips are resampled straight into the packed buffer the log-mel launch reads (``resample.resample_many``)."""
+    ``mbe``; the clips are resampled straight into the packed buffer the log-mel launch reads (``resample.resample_many``).
+    ``keep_channels=True``: every clip is ``[N, channels]`` and its channels are kept -> features ``[.., channels*n_mels]``
+    (``mbe_planar``; the resampler writes the planar channels of every clip straight into the buffer that launch reads)."""
     waves = list(waves)
     if device is None:
         device = next((w.device for w in waves if isinstance(w, torch.Tensor) and w.is_cuda), None)
         device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    if keep_channels:
+        from .resample import resample_many
+        for i, w in enumerate(waves):
+            if len(w) < 1:
+                raise ValueError(f"clip {i} is empty")
+        pcm, clips = resample_many(waves, sr if input_sr is None else input_sr, sr, channels, device, keep_channels=True)
+        return mbe_planar(pcm, clips, channels, sr=sr, n_fft=n_fft, hop=hop, n_mels=n_mels, pad_mode=pad_mode, mean=mean, std=std,
+                          tables=tables)
     if input_sr is not None and np.ndim(input_sr) > 0 or any(_needs_front_end(w, input_sr, sr, channels) for w in waves):
         from .resample import resample_many
         pcm, clips = resample_many(waves, sr if input_sr is None else input_sr, sr, channels, device)

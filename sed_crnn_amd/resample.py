@@ -9,7 +9,9 @@ to float32.  Output ``m`` (absolute index) has ``u = m*M``, ``i_c = u // L``, ``
 
 summed in fp32 in one fixed order (``csrc/resample.hip``), so that a recording resampled in pieces equals the recording
 resampled whole, bit for bit.  int16 input (scaled by 1/32768) and interleaved channels ``[N, C]`` (downmixed as
-``(sum_c x_c) * (1/C)``) are converted while they are loaded.  There is no CPU fallback.
+``(sum_c x_c) * (1/C)``) are converted while they are loaded.  With ``keep_channels=True`` the channels are kept instead of
+mixed: one row of the launch per (clip, channel), planar mono clips out, each bit for bit the mono call on that
+channel.  There is no CPU fallback.
 """
 import ctypes as C
 import functools
@@ -25,6 +27,7 @@ TILE_OUT = 1024            # outputs per workgroup tile (resample.hip: RS_TILE)
 MAX_TABLE_FLOATS = 26_624  # L * (K + 1): the padded table must stay in LDS beside the input tile (resample.hip: RS_TAPS_MAX)
 MAX_TILE_SPAN = 8192       # input samples one tile may read (resample.hip: RS_SPAN_MAX)
 ROW = 9                    # int64 per row of sed_resample's host table
+ROW_SELECT = 10            # ... of sed_resample_select's: the tenth is the channel the row keeps (-1 = downmix)
 
 
 class ResamplePlan:
@@ -121,23 +124,51 @@ def build_rows(n_in, in_base, out_first, n_out, n_hist=None, hist_off=None, carr
     return np.ascontiguousarray(rows), int(n_in.sum()), int(padded.sum())
 
 
-def check_rows(rows, x_frames, hist_len, out_len, L, M, half):
-    """the library's host checks of a table (no GPU call); raises SedHipError with its message"""
+def with_channels(rows, channel):
+    """a [R][9] table and the channel every row keeps (int64 [R]; -1 = downmix) -> sed_resample_select's table [R][10]"""
+    rows = np.asarray(rows, np.int64).reshape(-1, ROW)
+    return np.ascontiguousarray(np.concatenate([rows, np.asarray(channel, np.int64).reshape(-1, 1)], 1))
+
+
+def build_keep_rows(n_in, n_out, channels):
+    """sed_resample_select's table [R*channels][10] for R whole clips whose channels are kept: one row per (clip, channel), the
+    rows of a clip all reading its frames, row ``r*channels + c`` keeping channel c; the planar outputs lie back to back,
+    every one on a 16-byte boundary -> (table, x frames, out samples)"""
+    nc = int(channels)
+    n_in = np.asarray(n_in, np.int64).reshape(-1)
+    rows, _, out_len = build_rows(np.repeat(n_in, nc), None, None, np.repeat(np.asarray(n_out, np.int64).reshape(-1), nc))
+    rows[:, 0] = np.repeat(np.cumsum(n_in) - n_in, nc)
+    return with_channels(rows, np.tile(np.arange(nc), n_in.shape[0])), int(n_in.sum()), out_len
+
+
+def check_rows(rows, x_frames, hist_len, out_len, L, M, half, channels=None):
+    """the library's host checks of a table (no GPU call); raises SedHipError with its message.  With ``channels`` the table
+    is sed_resample_select's [R][10]."""
+    if channels is not None:
+        rows = np.ascontiguousarray(rows, np.int64).reshape(-1, ROW_SELECT)
+        check(lib().sed_resample_select_check_table(C.c_void_p(rows.ctypes.data), rows.shape[0], int(channels), int(x_frames),
+                                                    int(hist_len), int(out_len), int(L), int(M), int(half)),
+              "sed_resample_select_check_table")
+        return
     rows = np.ascontiguousarray(rows, np.int64).reshape(-1, ROW)
     check(lib().sed_resample_check_table(C.c_void_p(rows.ctypes.data), rows.shape[0], int(x_frames), int(hist_len), int(out_len),
                                          int(L), int(M), int(half)), "sed_resample_check_table")
 
 
 def launch(x, fmt, channels, hist, taps, L, M, half, rows, out, ws=None):
-    """one sed_resample launch on torch's current stream; ``ws`` (optional) is a reusable workspace"""
-    rows = np.ascontiguousarray(rows, np.int64).reshape(-1, ROW)
+    """one sed_resample launch on torch's current stream (sed_resample_select when the table is [R][10], ``with_channels``);
+    ``ws`` (optional) is a reusable workspace"""
+    rows = np.asarray(rows, np.int64)
+    select = rows.ndim == 2 and rows.shape[1] == ROW_SELECT
+    rows = np.ascontiguousarray(rows).reshape(-1, ROW_SELECT if select else ROW)
     R = rows.shape[0]
-    need = lib().sed_resample_workspace_bytes(R)
+    name = "sed_resample_select" if select else "sed_resample"
+    need = getattr(lib(), name + "_workspace_bytes")(R)
     if ws is None or ws.numel() < need:
         ws = torch.empty(max(need, 1), dtype=torch.uint8, device=out.device)
-    check(lib().sed_resample(ptr(x), (x.numel() // channels) if x is not None else 0, fmt, channels, ptr(hist),
-                             hist.numel() if hist is not None else 0, ptr(taps), taps.numel(), L, M, half,
-                             C.c_void_p(rows.ctypes.data), R, ptr(out), out.numel(), ptr(ws), ws.numel(), stream_ptr()), "sed_resample")
+    check(getattr(lib(), name)(ptr(x), (x.numel() // channels) if x is not None else 0, fmt, channels, ptr(hist),
+                               hist.numel() if hist is not None else 0, ptr(taps), taps.numel(), L, M, half,
+                               C.c_void_p(rows.ctypes.data), R, ptr(out), out.numel(), ptr(ws), ws.numel(), stream_ptr()), name)
     return ws
 
 
@@ -185,12 +216,15 @@ def _rates(sr_in, R):
     return rates
 
 
-def resample_many(waves, sr_in, sr_out=SR, channels=1, device=None):
+def resample_many(waves, sr_in, sr_out=SR, channels=1, device=None, keep_channels=False):
     """Every clip of a list (host or device; int16 or float; [N], or [N, channels] interleaved) resampled to ``sr_out`` mono
     float32 -> (one packed buffer on the device, clips [(first sample, n), ...]): what ``feature.mbe_packed`` takes, every clip
     on a 16-byte boundary.  ``sr_in``: one rate, or one per clip; clips of one (rate, sample format) share a launch.  Clip r
-    is bit for bit ``resample(waves[r], sr_in[r])``; mono float clips already at ``sr_out`` are copied."""
+    is bit for bit ``resample(waves[r], sr_in[r])``; mono float clips already at ``sr_out`` are copied.
+    ``keep_channels=True``: nothing is mixed; R recordings give ``R * channels`` planar clips, recording r, channel c = clip
+    ``r * channels + c`` (what ``feature.mbe_planar`` takes), each bit for bit ``resample(waves[r][:, c], sr_in[r])``."""
     waves = list(waves)
+    Ck = int(channels) if keep_channels else 1                          # clips per recording
     rates = _rates(sr_in, len(waves))
     if device is None:
         device = next((w.device for w in waves if isinstance(w, torch.Tensor) and w.is_cuda), None)
@@ -200,7 +234,7 @@ def resample_many(waves, sr_in, sr_out=SR, channels=1, device=None):
         raise RuntimeError("sed_crnn_amd.resample needs a CUDA(HIP) device; there is no CPU fallback")
     pcs = [as_pcm(w, channels, f"clip {i}") for i, w in enumerate(waves)]
     plans = [plan_for(r, int(sr_out)) for r in rates]
-    n_out = np.array([pl.n_out(p.shape[0]) for pl, p in zip(plans, pcs)], np.int64)
+    n_out = np.repeat(np.array([pl.n_out(p.shape[0]) for pl, p in zip(plans, pcs)], np.int64), Ck)
     padded = (n_out + 3) & ~3
     out_off = np.cumsum(padded) - padded
     out = torch.empty(int(padded.sum()), device=device)
@@ -214,21 +248,31 @@ def resample_many(waves, sr_in, sr_out=SR, channels=1, device=None):
             continue
         if pl.identity and int(channels) == 1 and p.dtype == torch.float32:
             out[clips[i][0]:clips[i][0] + clips[i][1]] = p.to(device)      # the identity: the samples pass through untouched
-            continue
+            continue                                                       # (one channel: clip i is recording i either way)
         groups.setdefault((pl.sr_in, p.dtype == torch.int16), []).append(i)
     for (rate, is16), idx in groups.items():
         taps, L, M, half = _device_taps(rate, int(sr_out), device.index or 0)
         x = pack_pcm([pcs[i] for i in idx], device)
-        rows, _, _ = build_rows([pcs[i].shape[0] for i in idx], None, None, n_out[idx])
-        rows[:, 5] = out_off[idx]
+        if keep_channels:                                               # one row per (recording, channel), all reading the same frames
+            rows, _, _ = build_keep_rows([pcs[i].shape[0] for i in idx], n_out[np.asarray(idx) * Ck], Ck)
+            rows[:, 5] = out_off[(np.asarray(idx)[:, None] * Ck + np.arange(Ck)[None, :]).reshape(-1)]
+        else:
+            rows, _, _ = build_rows([pcs[i].shape[0] for i in idx], None, None, n_out[idx])
+            rows[:, 5] = out_off[idx]
         launch(x, int(is16), int(channels), None, taps, L, M, half, rows, out)
     return out, clips
 
 
-def resample(y, sr_in, sr_out=SR, channels=1, device=None):
+def resample(y, sr_in, sr_out=SR, channels=1, device=None, keep_channels=False):
     """One clip ([N], or [N, channels] interleaved; int16 or float; host or device) -> mono float32 [ceil(N*sr_out/sr_in)] on
-    the device.  ``sr_in == sr_out`` with mono float input is the identity: no kernel runs, the samples come back bit for bit."""
+    the device.  ``sr_in == sr_out`` with mono float input is the identity: no kernel runs, the samples come back bit for bit.
+    ``keep_channels=True``: planar float32 ``[channels, n_out]`` instead of the downmix, row c bit for bit
+    ``resample(y[:, c], sr_in)`` (at ``sr_in == sr_out`` the one-tap copy filter de-interleaves and converts)."""
     p = as_pcm(y, channels)
+    if keep_channels:
+        out, clips = resample_many([p], sr_in, sr_out, channels, device, keep_channels=True)
+        n = clips[0][1]
+        return out.as_strided((int(channels), n), ((n + 3) & ~3, 1))       # every channel starts on a 16-byte boundary
     if plan_for(int(sr_in), int(sr_out)).identity and int(channels) == 1 and p.dtype == torch.float32:
         if device is None:
             device = p.device if p.is_cuda else torch.device("cuda", torch.cuda.current_device())

@@ -16,6 +16,11 @@ the streams restart at frame 0.  Between calls everything lives on the device, i
 ``hop``, ``median``, ``max_new_windows`` and S only; a long push is split into steps of at most ``max_new_windows`` windows per
 stream.  The host keeps the counters of all streams as arrays, so a push costs no Python per stream beyond reading its list of
 pieces.  There is no CPU fallback.
+
+A net with ``in_channels = C > 1`` takes ``[n, C]`` interleaved pieces: the resampling stage is then always on (the
+one-tap copy filter at the detector's own rate) and emits C planar lanes per feed; lane ``s*C + c`` has its own resampler
+carry and its own log-mel PCM carry on the device, while the host counters stay per feed (the channels of a feed advance in
+lockstep), and a round's features come out of ``sed_logmel_multi`` as ``[rows, C*F]``, which is what the feature rows hold.
 """
 import ctypes as C
 
@@ -145,12 +150,19 @@ class StreamDetector:
     """``EventDetector`` for audio that is still arriving, S streams at once (module docstring).  The keyword arguments are
     ``EventDetector``'s, checked the same way; ``max_new_windows``: windows per stream and step (longer pushes are split)."""
 
-    def __init__(self, model, n_streams, keep_probs=False, max_new_windows=4, _det=None, input_sr=None, input_channels=1, **kw):
+    def __init__(self, model, n_streams, keep_probs=False, max_new_windows=4, _det=None, input_sr=None, input_channels=None, **kw):
         self.det = _det if _det is not None else EventDetector(model, **kw)
         det, m = self.det, self.det.model
         S = int(n_streams)
         if not 1 <= S <= 65535 or not 1 <= int(max_new_windows) <= 1024:
             raise ValueError(f"need 1 <= n_streams <= 65535 and 1 <= max_new_windows <= 1024, got {n_streams}, {max_new_windows}")
+        self.C = m.in_channels                                             # planar lanes per feed: lane s*C + c (DESIGN 5k)
+        input_channels = self.C if input_channels is None else int(input_channels)
+        if self.C > 1 and input_channels != self.C:
+            raise ValueError(f"a {self.C}-channel net takes [n, {self.C}] interleaved pieces: input_channels must be {self.C}, got "
+                             f"{input_channels} (there is no mix-down to fewer channels and no duplication of a mono signal)")
+        if S * self.C > 65535:
+            raise ValueError(f"{S} feeds of {self.C} channels are {S * self.C} lanes: sed_stream_append takes at most 65535")
         self.S, self.keep_probs, self.max_new = S, bool(keep_probs), int(max_new_windows)
         self.K, self.CF = m.dense[-1], m.in_channels * m.n_mels
         tf = m.time_factor
@@ -195,8 +207,9 @@ class StreamDetector:
     # ── sizes ──
     @property
     def state_bytes(self):
-        """device bytes held between calls: the step's rings and decoder states, the feature rows and the PCM carry"""
-        return self._core_bytes + 4 * self.S * 2 * (self.FC * self.CF + self.CC + (self._rCR if self._rs is not None else 0))
+        """device bytes held between calls: the step's rings and decoder states, the feature rows and, per lane, the PCM carry
+        and the resampler's carry"""
+        return self._core_bytes + 4 * self.S * 2 * (self.FC * self.CF + self.C * (self.CC + (self._rCR if self._rs is not None else 0)))
 
     @property
     def frame_seconds(self):
@@ -215,17 +228,17 @@ class StreamDetector:
             S = self.S
             self._state = torch.empty(self._core_bytes, dtype=torch.uint8, device=dev)
             self._feat = torch.empty(S * 2 * self.FC, self.CF, device=dev)
-            self._pcm = torch.empty(S * 2 * self.CC, device=dev)
-            self._aws = torch.empty(lib().sed_stream_append_workspace_bytes(S), dtype=torch.uint8, device=dev)
+            self._pcm = torch.empty(S * self.C * 2 * self.CC, device=dev)
+            self._aws = torch.empty(lib().sed_stream_append_workspace_bytes(S * self.C), dtype=torch.uint8, device=dev)
             check(lib().sed_stream_init(ptr(self._state), self._state.numel(), *self._dims, stream_ptr()), "sed_stream_init")
         return self._state.device
 
     # ── log-mel of a round: carry + new samples as one clip per stream ──
     def _logmel_round(self, fresh, takes, end):
-        """``fresh``: the round's new samples packed (device, or None), ``takes`` [S] how many belong to each stream; the
-        streams in the mask ``end`` also get their right-padded frames.  -> (features [rows, n_mels] or None, first row [S],
-        rows [S])"""
-        det, h, S, CC = self.det, self.det.hop_length, self.S, self.CC
+        """``fresh``: the round's new samples packed (device, or None; lane by lane: feed s, channel c at lane s*C + c),
+        ``takes`` [S] how many belong to each lane of a stream; the streams in the mask ``end`` also get their right-padded
+        frames.  -> (features [rows, C*n_mels] or None, first row [S], rows [S])"""
+        det, h, S, CC, NC = self.det, self.det.hop_length, self.S, self.CC, self.C
         dev = self._state.device
         takes, half = np.asarray(takes, np.int64), feature.NFFT // 2
         keep, done = self._clen, self._fdone
@@ -236,23 +249,26 @@ class StreamDetector:
         # the carry [cbase, n_prev) and the new samples are one clip; the next carry starts q frames before frame `upto`
         a_new = np.where(end, n, np.maximum(0, upto - self.q) * h)
         total = np.where(act, keep + takes, 0)
-        work_at = _excl((total + 3) & ~3)                                   # clips start 16-byte aligned (the fast load path)
-        base = self._ar * (2 * CC)
-        table = np.stack([base + self._cpar * CC, keep, _excl(takes), takes, work_at, base + (1 - self._cpar) * CC, n - a_new], 1)
-        table[~act] = 0                                                     # sed_stream_append: zeros = nothing moves
+        # per lane: the C lanes of a feed move the same counts, each in its own region of the carry and of `work`
+        lane = (lambda a: a) if NC == 1 else (lambda a: np.repeat(a, NC))
+        total_l, takes_l, cpar_l = lane(total), lane(takes), lane(self._cpar)
+        work_at = _excl((total_l + 3) & ~3)                                 # clips start 16-byte aligned (the fast load path)
+        base = np.arange(S * NC, dtype=np.int64) * (2 * CC)
+        table = np.stack([base + cpar_l * CC, lane(keep), _excl(takes_l), takes_l, work_at, base + (1 - cpar_l) * CC, lane(n - a_new)], 1)
+        table[~lane(act)] = 0                                               # sed_stream_append: zeros = nothing moves
         clip = act & (upto > done)
         clip_rows = np.where(clip, 1 + total // h, 0)
         row0 = np.where(clip, _excl(clip_rows) + done - self._cbase // h, 0)
         rows = np.where(clip, upto - done, 0)
-        n_rows, n_work = int(clip_rows.sum()), int(((total + 3) & ~3).sum())
+        n_rows, n_work = int(clip_rows.sum()), int(((total_l + 3) & ~3).sum())
         self._n, self._fdone = n, upto
         self._cbase, self._clen = np.where(act, a_new, self._cbase), np.where(act, n - a_new, self._clen)
         self._cpar = np.where(act, 1 - self._cpar, self._cpar)
         work = torch.empty(max(n_work, 1), device=dev) if n_rows else None
         if act.any():
             table = np.ascontiguousarray(table)
-            check(lib().sed_stream_append(ptr(self._pcm), self._pcm.numel(), 2 * CC, ptr(fresh), int(takes.sum()), ptr(work),
-                                          work.numel() if work is not None else 0, C.c_void_p(table.ctypes.data), S, ptr(self._aws),
+            check(lib().sed_stream_append(ptr(self._pcm), self._pcm.numel(), 2 * CC, ptr(fresh), int(takes_l.sum()), ptr(work),
+                                          work.numel() if work is not None else 0, C.c_void_p(table.ctypes.data), S * NC, ptr(self._aws),
                                           self._aws.numel(), stream_ptr()), "sed_stream_append")
         if not n_rows:
             return None, row0, rows
@@ -260,11 +276,17 @@ class StreamDetector:
             m = det.model
             tables = feature._tables(dev.index or 0, det.sr, feature.NFFT, m.n_mels)
             mean, inv = feature._scaler(det.mean, det.std, dev)
-            ws = torch.empty(lib().sed_logmel_batch_workspace_bytes(S), dtype=torch.uint8, device=dev)
+            need = lib().sed_logmel_batch_workspace_bytes(S) if NC == 1 else lib().sed_logmel_multi_workspace_bytes(S, NC)
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
             self._lm = (tables, mean, inv, ws)
         tables, mean, inv, ws = self._lm
-        ct = np.ascontiguousarray(np.stack([work_at[clip], total[clip]], 1))
-        out = torch.empty(n_rows, det.model.n_mels, device=dev)
+        ct = np.ascontiguousarray(np.stack([work_at[lane(clip)], total_l[lane(clip)]], 1))
+        out = torch.empty(n_rows, NC * det.model.n_mels, device=dev)
+        if NC > 1:                                                          # the C lanes of a feed -> its rows' C column blocks
+            _timed(self.marks, "logmel", lambda: check(lib().sed_logmel_multi(
+                ptr(work), work.numel(), C.c_void_p(ct.ctypes.data), ct.shape[0] // NC, NC, ptr(tables), tables.numel() * 4, ptr(mean),
+                ptr(inv), ptr(out), n_rows, feature.NFFT, h, det.model.n_mels, 0, ptr(ws), ws.numel(), stream_ptr()), "sed_logmel_multi"))
+            return out, row0, rows
         _timed(self.marks, "logmel", lambda: check(lib().sed_logmel_batch(
             ptr(work), work.numel(), C.c_void_p(ct.ctypes.data), ct.shape[0], ptr(tables), tables.numel() * 4, ptr(mean), ptr(inv),
             ptr(out), n_rows, feature.NFFT, h, det.model.n_mels, 0, ptr(ws), ws.numel(), stream_ptr()), "sed_logmel_batch"))
@@ -380,7 +402,7 @@ class StreamDetector:
             poffs = np.concatenate([[0], np.cumsum(np.sum([p[3] for p in parts], axis=0))]).tolist()
         return StreamEvents(ev, offs, final, self.frame_seconds, probs, poffs)
 
-    def _pieces(self, xs, what, check_one):
+    def _pieces(self, xs, what, check_one, axis=0):
         xs = list(xs)
         if len(xs) != self.S:
             raise ValueError(f"expected {self.S} {what} (one per stream, None = nothing new), got {len(xs)}")
@@ -388,12 +410,15 @@ class StreamDetector:
         for s, x in enumerate(xs):
             if x is not None:
                 x = check_one(s, x)
-                lens[s] = x.shape[0]
+                lens[s] = x.shape[axis]
             pieces.append(x)
         return pieces, lens
 
-    def _pack(self, pieces, lens, done, takes, dev):
-        """the round's share of every piece, back to back on the device (``feature.cat_to_device``)"""
+    def _pack(self, pieces, lens, done, takes, dev, planar=False):
+        """the round's share of every piece, back to back on the device (``feature.cat_to_device``); planar [C, n] pieces go
+        lane by lane (channel 0's share, then channel 1's, ...)"""
+        if planar:
+            return feature.cat_to_device([pieces[s][:, done[s]:done[s] + takes[s]].reshape(-1) for s in np.nonzero(takes)[0]], dev)
         return feature.cat_to_device([pieces[s] if takes[s] == lens[s] else pieces[s][done[s]:done[s] + takes[s]]
                                       for s in np.nonzero(takes)[0]], dev)
 
@@ -402,12 +427,13 @@ class StreamDetector:
         """``pieces``: per feed a tensor of ``lens[s]`` sample frames (int16 or float32, all one dtype) or None; the feeds in
         the mask ``end`` end: everything up to ceil(n L / M) comes out, zeros to their right.  One launch: the outputs that
         became final, per feed as a view of one packed device buffer (None = none), and the feeds' next carry.  The host
-        keeps the int64 counters and reads nothing back."""
-        from .resample import _device_taps, build_rows, launch, pack_pcm
-        plan, S, CR = self._rs, self.S, self._rCR
+        keeps the int64 counters and reads nothing back.  A multichannel net: one row per lane (feed, channel), each keeping
+        its channel of the feed's frames and its own carry; a feed's outputs are then a planar [C, n] view."""
+        from .resample import _device_taps, build_rows, launch, pack_pcm, with_channels
+        plan, S, CR, NC = self._rs, self.S, self._rCR, self.C
         dev = self._state.device
         if self._rcarry is None:
-            self._rcarry = torch.zeros(S * 2 * CR, device=dev)
+            self._rcarry = torch.zeros(S * NC * 2 * CR, device=dev)
         taps, L, M, half = _device_taps(plan.sr_in, plan.sr_out, dev.index or 0)
         n_new = self._rn + lens
         if plan.identity:
@@ -419,20 +445,25 @@ class StreamDetector:
         if idx.size == 0:
             return [None] * S
         n_hist = np.minimum(CR, self._rn)
-        base = self._ar * (2 * CR)
         live = [pieces[s] for s in idx if lens[s] > 0]
         x = pack_pcm(live, dev) if live else None
         is16 = bool(live) and live[0].dtype == torch.int16
-        rows, _, n_outbuf = build_rows(lens[idx], self._rn[idx], self._rm[idx], (done - self._rm)[idx], n_hist[idx],
-                                       (base + self._rpar * CR + CR - n_hist)[idx],
-                                       np.where(end, -1, base + (1 - self._rpar) * CR)[idx])
+        lane = (lambda a: a) if NC == 1 else (lambda a: np.repeat(a, NC))   # the C lanes of a feed share its counters
+        base = (lane(idx) * NC + np.tile(np.arange(NC), idx.size)) * (2 * CR)
+        rows, _, n_outbuf = build_rows(lane(lens[idx]), lane(self._rn[idx]), lane(self._rm[idx]), lane((done - self._rm)[idx]),
+                                       lane(n_hist[idx]), base + lane((self._rpar * CR + CR - n_hist)[idx]),
+                                       np.where(lane(end[idx]), -1, base + lane(((1 - self._rpar) * CR)[idx])))
+        if NC > 1:                                                          # ... and read the same frames, each its own channel
+            rows[:, 0] = lane(_excl(lens[idx]))
+            rows = with_channels(rows, np.tile(np.arange(NC), idx.size))
         out = torch.empty(max(n_outbuf, 1), device=dev)
         self._rws = _timed(self.marks, "resample", lambda: launch(x, int(is16), self.input_channels, self._rcarry, taps, L, M, half,
                                                                   rows, out, self._rws))
         res = [None] * S
         for r, s in enumerate(idx.tolist()):
-            if rows[r, 4]:
-                res[s] = out[rows[r, 5]:rows[r, 5] + rows[r, 4]]
+            n_r, at = int(rows[r * NC, 4]), int(rows[r * NC, 5])
+            if n_r:
+                res[s] = out[at:at + n_r] if NC == 1 else out.as_strided((NC, n_r), ((n_r + 3) & ~3, 1), at)
                 if self.keep_pcm:
                     self.pcm_log[s].append(res[s])
         moved = act & ~end
@@ -444,13 +475,20 @@ class StreamDetector:
     def push(self, chunks):
         """a list of S mono PCM pieces (1-D, host or device, any length >= 0; None = nothing new) -> StreamEvents.  With
         ``input_sr`` / ``input_channels`` the pieces are at that rate, int16 or float (one dtype per push), ``[n, channels]``
-        interleaved, and pass through the resampling stage first."""
-        m = self.det.model
-        if m.in_channels != 1:
-            raise ValueError(f"a mono waveform feeds a 1-channel net; this one has {m.in_channels} (use push_features)")
+        interleaved, and pass through the resampling stage first.  A net with C > 1 input channels takes ``[n, C]`` pieces and
+        keeps the channels (module docstring)."""
         if self._rs is not None:
             from .resample import as_pcm
-            pieces, lens = self._pieces(chunks, "waveform pieces", lambda s, c: as_pcm(c, self.input_channels, f"stream {s}"))
+
+            def one(s, c):
+                try:
+                    return as_pcm(c, self.input_channels, f"stream {s}")
+                except ValueError as e:
+                    if self.C == 1:
+                        raise
+                    raise ValueError(f"{e}: a {self.C}-channel net takes [n, {self.C}] interleaved PCM pieces (for scaled "
+                                     f"features use push_features)") from None
+            pieces, lens = self._pieces(chunks, "waveform pieces", one)
             if len({p.dtype for p in pieces if p is not None}) > 1:
                 raise ValueError("the pieces of one push must share a sample format (all int16 or all floating point)")
             self._ready()
@@ -458,13 +496,18 @@ class StreamDetector:
         return self._push_mono(chunks)
 
     def _push_mono(self, chunks):
-        """``push`` at the detector's own rate"""
+        """``push`` at the detector's own rate: mono pieces, or (a multichannel net) the resampling stage's planar [C, n] pieces"""
+        planar = self.C > 1
+
         def one(s, c):
             c = c if isinstance(c, torch.Tensor) else torch.as_tensor(np.asarray(c))
-            if c.dim() != 1:
+            if planar:
+                if c.dim() != 2 or c.shape[0] != self.C:
+                    raise ValueError(f"stream {s}: expected planar PCM [{self.C}, n], got shape {tuple(c.shape)}")
+            elif c.dim() != 1:
                 raise ValueError(f"stream {s}: expected a mono 1-D waveform, got shape {tuple(c.shape)}")
             return c
-        pieces, lens = self._pieces(chunks, "waveform pieces", one)
+        pieces, lens = self._pieces(chunks, "waveform pieces", one, axis=1 if planar else 0)
         dev = self._ready()
         per_round = (self.step_frames - 1) * self.det.hop_length
 
@@ -474,7 +517,7 @@ class StreamDetector:
                 takes = np.minimum(per_round, lens - done)
                 if not takes.any():
                     return
-                fresh = self._pack(pieces, lens, done, takes, dev)
+                fresh = self._pack(pieces, lens, done, takes, dev, planar)
                 done = done + takes
                 mel, row0, rows = self._logmel_round(fresh, takes, self._none)
                 yield mel, row0, rows, self._none
