@@ -151,8 +151,9 @@ int sed_conv3x3_dgrad_bnred(const float* dy, const float* wp_dgrad, float* dx, f
  * its zero padding from); either may be NULL.
  * wino_fwd = sed_conv3x3_fwd on channels-last x; wino_dgrad_bnred = sed_conv3x3_dgrad_bnred (same arguments and outputs). */
 int sed_conv3x3_wino_rows(int B, int Cin, int F, int T, int Cout);
-/* measurement only (tools/kprobe.py): buf = 4 device uint64 — prologue / main loop / epilogue ticks of the 100 MHz clock summed
- * over the workgroups of every following Winograd forward / data-gradient launch, and the workgroup count; NULL switches it off. */
+/* measurement only (tools/wino_probe.py): buf = 5 device uint64 — prologue / main loop / epilogue ticks of the 100 MHz clock summed
+ * over the workgroups of every following Winograd forward / data-gradient launch, the workgroup count, and (wino_dgrad_bnred[_rg]
+ * only) the part of the epilogue in front of its exchange barrier; NULL switches it off. */
 int sed_conv3x3_wino_phase_ticks(unsigned long long* buf);
 size_t sed_conv3x3_wino_packed_floats(int Cout, int Cin);
 int sed_conv3x3_wino_pack_weights(const float* w_oihw, float* uf, float* ud, int Cout, int Cin, void* stream);
@@ -170,7 +171,10 @@ int sed_conv3x3_wino_pack_weights_bn_folded(const float* w_oihw, const float* bi
                                             float* uf, float* bias_folded, int Cout, int Cin, void* stream);
 int sed_conv3x3_wino_bn_relu_pool_eval(const float* x, const float* uf_folded, const float* bias_folded, float* pooled,
                                        int B, int Cin, int F, int T, int Cout, void* stream);
-/* = sed_conv3x3_dgrad_bnred_rg (the first block's weight-gradient sums from the same epilogue); rows = sed_conv3x3_wino_rg_rows() */
+/* = sed_conv3x3_dgrad_bnred_rg (the first block's weight-gradient sums from the same epilogue); rows = sed_conv3x3_wino_rg_rows().
+ * dx may be NULL here: the data gradient itself is then not written (the training plan does so when the first block takes
+ * everything it needs from partials and rg_partials: a tensor of the size of the pooled output that nobody would read);
+ * partials and rg_partials are the same bit for bit with and without dx. */
 int sed_conv3x3_wino_rg_rows(int B, int C, int F, int T, int Cin, int Cin1);
 int sed_conv3x3_wino_dgrad_bnred_rg(const float* dy, const float* ud, float* dx, float* partials, const float* pooled,
                                     const float* gamma, const float* beta, const float* mean, const float* rstd, float drop_p,
@@ -723,7 +727,9 @@ int sed_net_backward_phases(const sed_net_cfg* cfg, const sed_net_params* p, con
  *   "mean" / "rstd" / "scale" / "shift"[l] the batch statistics and fused BatchNorm coefficients of block l ([C]);
  *   "gi"[i] / "gru_out"[i] input projections [M][2][3H] and outputs [M][2H] of GRU layer i;
  *   training only: "dconv"[l] gradient of block l's conv output, "dgru_out"[i], "grad_act"[0] the buffer that carries the
- *   gradient of the pooled output being back-propagated (reused from block to block), "bn_sums_bwd"[0] (sum g, sum g*xhat),
+ *   gradient of the pooled output being back-propagated (reused from block to block; when the first block's sums come out of
+ *   the Winograd data gradient of block 1, the gradient of block 0's pooled output is never written: after a backward the
+ *   buffer then holds the gradient of block 1's pooled output), "bn_sums_bwd"[0] (sum g, sum g*xhat),
  *   "wgrad_zero_row"[0|1] the zero-filled rows at the head of the weight-gradient scratch of the main / auxiliary stream
  *   (SED_WGRAD_ZERO_ROW_CLEAN: sed_net_backward re-clears them in every call that holds stage 0).
  * <0: unknown name / index for this plan. */

@@ -781,6 +781,42 @@ __global__ __launch_bounds__(256) void conv1_rgrad_mfma_k(
 // index of G(k, k2), k <= k2, in the moment vector [S1 (NK) | upper triangle row by row] of conv1_gram_k
 __device__ __forceinline__ int c1_gidx(int k, int k2, int NK) { return NK + k * NK - (k * (k - 1)) / 2 + (k2 - k); }
 
+// The row sums of conv1_wgrad_assemble_k for NVT = 1 + 9 Cin values per row.  A thread sums whole rows (the NVT values of
+// (workgroup r, channel co) are one 40..148-byte run), rows tid, tid + 256, ... in that order, in fp64.  The loads of RB rows are
+// all issued before the first of them is added: one memory round trip per RB rows instead of one per row (2560 rows at the
+// training shape: ten dependent round trips were most of the kernel).  Same values, same order of additions.
+template <int NVT, int RB>
+__device__ __forceinline__ void c1_assemble_row_sums(const float* __restrict__ part, int rows, int C, int co, double (*sw)[37]) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    double a[NVT];
+#pragma unroll
+    for (int v = 0; v < NVT; ++v) a[v] = 0.0;
+    for (int r0 = threadIdx.x; r0 < rows; r0 += 256 * RB) {
+        float pv[RB][NVT];
+#pragma unroll
+        for (int u = 0; u < RB; ++u) {
+            const int r = r0 + 256 * u;
+            if (r < rows) {
+                const float* pr = part + ((size_t)r * C + co) * NVT;
+#pragma unroll
+                for (int v = 0; v < NVT; ++v) pv[u][v] = pr[v];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < RB; ++u) {
+            if (r0 + 256 * u < rows) {
+#pragma unroll
+                for (int v = 0; v < NVT; ++v) a[v] += (double)pv[u][v];
+            }
+        }
+    }
+#pragma unroll
+    for (int v = 0; v < NVT; ++v) {
+        const double t = wave_sum_d(a[v]);
+        if (lane == 0) sw[wv][v] = t;
+    }
+}
+
 // one workgroup per output channel: R and sum g summed over the partial rows in fp64 (fixed order), then the closed form
 __global__ __launch_bounds__(256) void conv1_wgrad_assemble_k(
     const float* __restrict__ part, int rows, int Cin, int C, const double* __restrict__ gram, const float* __restrict__ wp,
@@ -791,24 +827,10 @@ __global__ __launch_bounds__(256) void conv1_wgrad_assemble_k(
     __shared__ double sv[37];                                 // [0] sum g, [1..NK] R_k
     __shared__ double sw[4][37];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    {   // a thread sums whole rows: the NV values of (workgroup r, channel co) are one 40..148-byte run
-        double a[37];
-#pragma unroll
-        for (int v = 0; v < 37; ++v) a[v] = 0.0;
-        for (int r = threadIdx.x; r < rows; r += 256) {
-            const float* pr = part + ((size_t)r * C + co) * NV;
-#pragma unroll
-            for (int v = 0; v < 37; ++v)
-                if (v < NV) a[v] += (double)pr[v];
-        }
-#pragma unroll
-        for (int v = 0; v < 37; ++v) {
-            if (v < NV) {
-                const double t = wave_sum_d(a[v]);
-                if (lane == 0) sw[wv][v] = t;
-            }
-        }
-    }
+    if (Cin == 1) c1_assemble_row_sums<10, 10>(part, rows, C, co, sw);
+    else if (Cin == 2) c1_assemble_row_sums<19, 5>(part, rows, C, co, sw);
+    else if (Cin == 3) c1_assemble_row_sums<28, 3>(part, rows, C, co, sw);
+    else c1_assemble_row_sums<37, 2>(part, rows, C, co, sw);
     __syncthreads();
     if (threadIdx.x < NV) sv[threadIdx.x] = (sw[0][threadIdx.x] + sw[1][threadIdx.x]) + (sw[2][threadIdx.x] + sw[3][threadIdx.x]);
     __syncthreads();

@@ -608,7 +608,8 @@ static int dgrad(const Layout& L, const sed_net_cfg* c, const sed_net_params* p,
     const ConvL& q = L.cv[l];
     const ConvL& u = L.cv[l - 1];
     if (u.rg_rows > 0 && q.wino_d)
-        return sed_conv3x3_wino_dgrad_bnred_rg(ws + L.dconv[l], ws + L.wp_d[l], ws + L.gradA, ws + L.bn_part, ws + L.pooled[l - 1],
+        // (dx: bn_backward of a first block that only assembles reads its sums from c1_ws and bn_part, nobody reads gradA: not written)
+        return sed_conv3x3_wino_dgrad_bnred_rg(ws + L.dconv[l], ws + L.wp_d[l], (u.fused && u.rgrad && u.rg_rows > 0) ? nullptr : ws + L.gradA, ws + L.bn_part, ws + L.pooled[l - 1],
                                                p->bn_g[l - 1], p->bn_b[l - 1], ws + L.mean[l - 1], ws + L.rstd[l - 1], u.drop,
                                                x, u.Cin, (const unsigned char*)(ws + L.c1_bits), ws + L.c1_ws, c->B, q.C, q.F, q.T, q.Cin, st);
     if (u.rg_rows > 0)

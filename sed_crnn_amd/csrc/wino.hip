@@ -245,8 +245,9 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_k(
         if (RG) xofftab[tid] = (unsigned)((fg0 + 2 * tf) * XT + 4 * (ty - ty0));
     }
     if (RG) {
+        const float invXT = 1.0f / (float)XT;
         for (int i = tid; i < (F + 2) * XT; i += 256) {
-            const int ff = i / XT, tt = i - ff * XT;
+            const int ff = sed_fdiv(i, invXT), tt = i - ff * XT;
             const int f = ff - 1, t = 4 * ty0 - 1 + tt;          // (all F + 2 mel columns: indexed by the absolute column)
             const bool in = f >= 0 && f < F && t >= 0 && t < br.Ty;
 #pragma unroll
@@ -311,6 +312,43 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_k(
         __builtin_amdgcn_global_load_lds((sed_gptr_t)(hp[u] + cc * 32), (sed_lptr_t)(buf + (u * 4 + wave) * 256), 16, 0, 0);
     };
 
+    // Epilogue state.  In the epilogue wave w finishes m-tile w >> 1, channel tile w & 1; lane = (row group rq, channels c4 .. c4+3).
+    // BNR: the pooled values (and RG: the arg-max bytes) of this lane's output positions come from a tensor that is streamed once
+    // (not L2-resident): requested behind the exchange tiles' parking they cost the workgroup a whole memory round trip with the
+    // matrix cores idle.  They ride in the slots of the LAST main-loop step instead, whose slots are otherwise empty and during
+    // which the staging registers (raw, up, the other operand parity, the patch pointers) are dead: a step plus the parking ahead of
+    // their first use.  Forward / inference: set up behind the parking, where it always was.
+    constexpr int PF = RGC == 2 ? 2 : 4;               // rows in flight (two input channels: 72 tap accumulators leave room for two)
+    int rq = 0, c4 = 0, cb = 0;
+    const char* qb = nullptr;
+    const unsigned char* bitq = nullptr;
+    unsigned rstride = 0, cstride = 0;
+    unsigned rov[4] = {0, 0, 0, 0};
+    f32x4 pqv[PF][BNR ? 4 : 1];
+    unsigned btv[PF][RG ? 4 : 1];
+    f32x4 q_beta = {0, 0, 0, 0}, gm = {0, 0, 0, 0};
+#define WN_EPI_LANE() do { rq = lane >> 3; c4 = (lane & 7) * 4; cb = co0 + nt * 32 + c4; } while (0)
+#define WN_EPI_STRIDES() do { rstride = (unsigned)(F * Cout) * 4u; cstride = (unsigned)Cout * 4u; } while (0)
+#define WN_EPI_ROWS() do { _Pragma("unroll") for (int k = 0; k < 4; ++k) rov[k] = rowtab[mt * 32 + rq + 8 * k]; } while (0)
+    auto epi_setup = [&]() {
+        const int mt = wave >> 1, nt = wave & 1;
+        WN_EPI_LANE();
+        qb = (const char*)(br.pooled + (size_t)b * T * F * Cout + cb);
+        bitq = RG ? br.bits + (size_t)b * T * F * (Cout >> 2) + (cb >> 2) : nullptr;
+        WN_EPI_STRIDES();
+        WN_EPI_ROWS();
+    };
+    // A lane without a tile in row k (rov[k] == ~0: the ragged end of a sequence) reads position 0 of its sequence instead, always
+    // inside the tensor, and never uses the value (the row is skipped below).  The guard is a select on the address and not a branch
+    // around the load: behind a branch hipcc can no longer count the loads in flight, and the waits for the weight fragments of
+    // this very step (s_waitcnt vmcnt) then wait for the pooled values too — the round trip would only move into the main loop.
+    auto prefetch_one = [&](int k, int n, f32x4* pqd, unsigned* btd) {      // position n = 2 jj + i of row k
+        if (!BNR) return;
+        const unsigned off = rov[k] != 0xFFFFFFFFu ? rov[k] + (n & 1) * rstride + (n >> 1) * cstride : 0u;
+        pqd[n] = *(const f32x4*)(qb + off);
+        if (RG) btd[n] = bitq[off >> 4];
+    };
+
 #pragma unroll
     for (int nu = 0; nu < 4; ++nu) load_b(nu, 0);
     __syncthreads();                                   // drains the DMA (vmcnt)
@@ -320,7 +358,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_k(
     for (int k = 0; k < 32; ++k) slot_xform(k, vp[0]);
     if (geo.dbg) tk1 = __builtin_amdgcn_s_memrealtime();
 #pragma unroll
-    for (int st = 0; st < NSTEP; ++st) {
+    for (int st = 0; st < (BNR ? NSTEP - 1 : NSTEP); ++st) {     // (BNR: the last step is written out below)
         const int cc = st >> 2, g = st & 3, par = st & 1;
         const bool more = cc + 1 < NCHUNK, nxt = st + 1 < NSTEP;
         const float* nbuf = smem + (((st + 1) >> 2) & 1) * HBUF;     // the next step's slice (the other buffer after step (cc, 3): complete since the barrier of (cc, 2))
@@ -345,6 +383,22 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_k(
         }
         if (g == 2 && more) __syncthreads();           // the next slice's patch is complete (DMA drained) and visible
     }
+    if (BNR) {
+        // the last step: 64 bare MFMAs, and in its slots the epilogue's loads — slots 0-15 (RGC == 2: 0-7) one output position each,
+        // 16 and 17 the BatchNorm parameters of the lane's channels
+        constexpr int par = (NSTEP - 1) & 1;
+        epi_setup();
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < 64; ++i) {
+            const int nu = i >> 4, j = (i >> 2) & 3, mt = (i >> 1) & 1, nt = i & 1;
+            acc[nu][mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(vp[par][mt][nu][j >> 1][j & 1], bq[nu][nt][j], acc[nu][mt][nt], 0, 0, 0);
+            if (i < 4 * (PF == 4 ? 4 : 2)) prefetch_one(i >> 2, i & 3, pqv[i >> 2], btv[i >> 2]);
+            else if (i == 16) q_beta = *(const f32x4*)(br.beta + cb);
+            else if (i == 17) gm = *(const f32x4*)(br.gamma + cb);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
     __syncthreads();                                   // every wave has read its last operands: the patch buffers are free
     if (geo.dbg) tk2 = __builtin_amdgcn_s_memrealtime();
 
@@ -354,6 +408,12 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_k(
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
+            if (BNR) {
+                // the pooled values are in flight: the finished accumulators stay where the MFMAs left them until their tile's turn
+                // (the register allocator copies all 256 out at once when nothing else wants the registers, and crowds the loads out)
+#pragma unroll
+                for (int nu = 0; nu < 4; ++nu) asm volatile("" : "+a"(acc[nu][mt][nt]));
+            }
             const f32x16 z0 = acc[0][mt][nt] + acc[1][mt][nt] + acc[2][mt][nt];
             const f32x16 z1 = acc[1][mt][nt] - acc[2][mt][nt] - acc[3][mt][nt];
             float* zb0 = smem + ((((wave * 2 + 0) * 2 + mt) * 2 + nt) << 10);
@@ -364,20 +424,17 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_k(
                 zb0[row * 32 + r] = z0[j];
                 zb1[row * 32 + r] = z1[j];
             }
+            if (BNR) __builtin_amdgcn_sched_barrier(0);
         }
     __builtin_amdgcn_sched_barrier(0);                 // (the exchange tiles are written: their registers are free for the pooled values)
-    // across xi: wave w finishes m-tile w >> 1, channel tile w & 1; lane = (row group rq, channels c4 .. c4+3)
+    // across xi (see "epilogue state" in front of the main loop)
     const int mt = wave >> 1, nt = wave & 1;
-    const int rq = lane >> 3, c4 = (lane & 7) * 4;
-    const int cb = co0 + nt * 32 + c4;
+    if (!BNR) WN_EPI_LANE();
     f32x4 bv = {0, 0, 0, 0};
     if (bias) bv = *(const f32x4*)(bias + cb);
     char* const yb = (char*)(y + (size_t)b * (EV ? T >> 1 : T) * F * Cout + cb);
-    const char* const qb = BNR ? (const char*)(br.pooled + (size_t)b * T * F * Cout + cb) : nullptr;
     f32x4 q_kr = {0, 0, 0, 0}, q_nb = {0, 0, 0, 0}, a1 = {0, 0, 0, 0}, a2 = {0, 0, 0, 0};
     if (BNR) {
-        const f32x4 q_beta = *(const f32x4*)(br.beta + cb);
-        const f32x4 gm = *(const f32x4*)(br.gamma + cb);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const bool zero = gm[e] == 0.f || (br.ybelow != nullptr && fabsf(gm[e]) * 64.f < fabsf(q_beta[e]));
@@ -386,50 +443,30 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_k(
             q_nb[e] = -q_beta[e] * rg;
         }
     }
-    const unsigned rstride = (unsigned)(F * Cout) * 4u, cstride = (unsigned)Cout * 4u;
+    if (!BNR) WN_EPI_STRIDES();
     f32x4 R[RG ? 9 * RGC : 1];
 #pragma unroll
     for (int k = 0; k < (RG ? 9 * RGC : 1); ++k) R[k] = (f32x4){0, 0, 0, 0};
-    const unsigned char* const bitq = RG ? br.bits + (size_t)b * T * F * (Cout >> 2) + (cb >> 2) : nullptr;
-    // BNR: the pooled values (and RG: the arg-max bytes) of this lane's output positions are requested ahead of their use — one
-    // dependent global load per position inside the loop below cost 8 us per workgroup, one row ahead still 4
-    unsigned rov[4], xov[4];
+    if (!BNR) WN_EPI_ROWS();
+    unsigned xov[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        rov[k] = rowtab[mt * 32 + rq + 8 * k];
-        xov[k] = RG ? xofftab[mt * 32 + rq + 8 * k] : 0u;
-    }
-    // (all four rows at once, in front of the exchange barrier: 16 loads in flight together instead of four dependent rounds;
-    // two input channels: 72 tap accumulators leave room for two rows only)
-    constexpr int PF = RGC == 2 ? 2 : 4;
-    f32x4 pqv[PF][BNR ? 4 : 1];
-    unsigned btv[PF][RG ? 4 : 1];
+    for (int k = 0; k < 4; ++k) xov[k] = RG ? xofftab[mt * 32 + rq + 8 * k] : 0u;
+    // (one dependent global load per position inside the loop below cost 8 us per workgroup, one row ahead still 4, all four rows in
+    // front of the exchange barrier one exposed round trip.  RGC == 2: rows 0 and 1 came with the last step, 2 and 3 roll below)
     auto prefetch = [&](int k, f32x4* pqd, unsigned* btd) {
-        if (!BNR) return;
 #pragma unroll
-        for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const unsigned off = rov[k] + i * rstride + jj * cstride;
-                pqd[jj * 2 + i] = (f32x4){0, 0, 0, 0};
-                if (RG) btd[jj * 2 + i] = 0u;
-                if (rov[k] != 0xFFFFFFFFu) {
-                    pqd[jj * 2 + i] = *(const f32x4*)(qb + off);
-                    if (RG) btd[jj * 2 + i] = bitq[off >> 4];
-                }
-            }
+        for (int n = 0; n < 4; ++n) prefetch_one(k, n, pqd, btd);
     };
-    if (PF == 4) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) prefetch(k, pqv[k], btv[k]);
-    } else prefetch(0, pqv[0], btv[0]);
+    const bool wr_y = !RG || y != nullptr;             // RG: dx is optional (nobody reads it when the block below only assembles)
 
     __syncthreads();
+    unsigned long long tkx = 0;
+    if (BNR && geo.dbg) tkx = __builtin_amdgcn_s_memrealtime();      // (behind the exchange barrier: parking + what is left of the loads' latency)
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int m = rq + 8 * k;
         const unsigned ro = rov[k];
-        if (PF == 2 && k + 1 < 4) prefetch(k + 1, pqv[(k + 1) & 1], btv[(k + 1) & 1]);
+        if (PF == 2 && k >= 1 && k + 1 < 4) prefetch(k + 1, pqv[(k + 1) & 1], btv[(k + 1) & 1]);
         if (ro == 0xFFFFFFFFu) continue;
         const unsigned xo = xov[k];
 #pragma unroll
@@ -449,7 +486,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_k(
             for (int i = 0; i < 2; ++i) {
                 const unsigned off = ro + i * rstride + jj * cstride;
                 const f32x4 v = o[i];
-                *(f32x4*)(yb + off) = v;
+                if (wr_y) *(f32x4*)(yb + off) = v;
                 if (BNR) {
                     const f32x4 pq = pqv[k & (PF - 1)][jj * 2 + i];
                     f32x4 g0;
@@ -530,8 +567,13 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_k(
         atomicAdd(geo.dbg + 1, tk2 - tk1);
         atomicAdd(geo.dbg + 2, tk3 - tk2);
         atomicAdd(geo.dbg + 3, 1ull);
+        if (BNR) atomicAdd(geo.dbg + 4, tkx - tk2);
     }
 }
+
+#undef WN_EPI_LANE
+#undef WN_EPI_STRIDES
+#undef WN_EPI_ROWS
 
 template <typename K>
 static int wino_set_lds(K kernel, size_t bytes) {
@@ -545,8 +587,10 @@ static unsigned long long* g_wino_dbg = nullptr;
 static int g_wino_abl = 0;
 extern "C" int sed_conv3x3_wino_ablate(int mask) { g_wino_abl = mask; return 0; }
 #endif
-// measurement only: buf = 4 device uint64 (prologue, main loop, epilogue ticks of the 100 MHz clock summed over workgroups, workgroup
-// count), accumulated by every Winograd forward / data-gradient launch until reset with NULL
+// measurement only: buf = 5 device uint64 (prologue, main loop, epilogue ticks of the 100 MHz clock summed over workgroups, workgroup
+// count, and — data gradient with the BatchNorm-backward epilogue only — the part of the epilogue in front of its exchange barrier:
+// parking the accumulators + waiting for the pooled values), accumulated by every Winograd forward / data-gradient launch until
+// reset with NULL
 extern "C" int sed_conv3x3_wino_phase_ticks(unsigned long long* buf) { g_wino_dbg = buf; return 0; }
 
 int sed_internal_wino_launch(const float* x, const float* uq, const float* bias, float* y, float* stat, const ConvBnRed* br,
@@ -624,7 +668,7 @@ extern "C" int sed_conv3x3_wino_dgrad_bnred_rg(const float* dy, const float* ud,
                                                const float* gamma, const float* beta, const float* mean, const float* rstd, float drop_p,
                                                const float* x1, int Cin1, const unsigned char* argmax_bits, float* rg_partials,
                                                int B, int C, int F, int T, int Cin, void* stream) {
-    SED_REQUIRE(dy && ud && dx && partials && pooled && gamma && beta && mean && rstd && x1 && argmax_bits && rg_partials, "conv3x3_wino_dgrad_bnred_rg: null pointer");
+    SED_REQUIRE(dy && ud && partials && pooled && gamma && beta && mean && rstd && x1 && argmax_bits && rg_partials, "conv3x3_wino_dgrad_bnred_rg: null pointer");       // dx may be NULL: not written
     SED_REQUIRE(drop_p >= 0.f && drop_p < 1.f && (Cin1 == 1 || Cin1 == 2), "conv3x3_wino_dgrad_bnred_rg: bad drop_p / input channels");
     hipStream_t s = as_stream(stream);
     SedProfScope prof(SED_K_CONV_MFMA_DGRAD, s, 2.0 * 9.0 * C * Cin * (double)B * T * F);
