@@ -628,6 +628,31 @@ size_t sed_stream_append_workspace_bytes(int S);
 int sed_stream_append(float* buf, long buf_len, long stride, const float* fresh, long fresh_len, float* work, long work_len,
                       const long* table_host, int S, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ───────────── class-wise decoder settings ─────────────
+ * The three decoding entries with one row of decoder values PER CLASS: classes_host [K] (a HOST array, K <= 32) takes the place
+ * of the scalar entries' median, lo, hi, min_gap, min_len; class k is decoded with row k — its own median width, thresholds, gap
+ * merge and minimum length — and peaks still read the unfiltered track.  Every row is checked like the scalar values and a
+ * refusal names the class ("...: class 3: need hi >= lo ..."); nothing is launched on a refusal.  The rows travel to the
+ * kernels by value: workspaces, state, tables and outputs are exactly those of the scalar entries, with the same size functions.
+ * Class k's events are bit for bit the class-k events of the scalar entry run with row k.
+ * sed_stream_step_classwise: `median` (here and in sed_stream_state_bytes / sed_stream_init / sed_stream_reset) must be the
+ * WIDEST median of the K classes.  There is one frontier per feed: filtered frame g of every class is decided once track frame
+ * g + median/2 is final; a pending event [a, b) of class k is emitted in the first step in which more than b + min_gap_k frames
+ * are decided and no run of class k that began at or before b + min_gap_k is still open. */
+typedef sed_tune_setting sed_decoder_setting;
+int sed_detect_events_classwise(const float* probs, long n_out, int K, const sed_decoder_setting* classes_host, int max_events,
+                                void* workspace, size_t workspace_bytes, int* cls, int* onset, int* offset, float* peak,
+                                int* peak_frame, int* count, void* stream);
+int sed_detect_events_batch_classwise(const float* probs, const long* n_out_host, int R, int K,
+                                      const sed_decoder_setting* classes_host, int max_events, void* workspace, size_t workspace_bytes,
+                                      int* rec, int* cls, int* onset, int* offset, float* peak, int* peak_frame, int* event_off,
+                                      void* stream);
+int sed_stream_step_classwise(void* state, size_t state_bytes, int S, int K, int win_out, int hop_out, int median, int max_new_windows,
+                              int combine, int trim, const sed_decoder_setting* classes_host, const float* logits, long logits_len,
+                              const long* table_host, int max_new_decided, float* probs, long probs_rows, int max_events,
+                              int* ev_stream, int* cls, int* onset, int* offset, float* peak, int* peak_frame, int* event_off,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
 /* ───────────── whole-network plan (TimePooledCRNN.forward sed.py:105-112 / crnn_lightning.py:66-73) ───────────── */
 typedef struct sed_net_cfg {
     int B, Cin, F, T;                 /* input x [B][Cin][F][T] */

@@ -45,7 +45,7 @@ class NetParams(C.Structure):
 
 
 class TuneSetting(C.Structure):
-    """sed_tune_setting: one decoder setting of sed_tune_sweep"""
+    """sed_tune_setting (= sed_decoder_setting): one decoder setting of sed_tune_sweep, one class's row of the class-wise entries"""
     _fields_ = [("median", C.c_int), ("lo", C.c_float), ("hi", C.c_float), ("min_gap", C.c_int), ("min_len", C.c_int)]
 
 
@@ -168,6 +168,10 @@ SIGNATURES = {
                              _fp, _fp, _fp, _fp, _fp, _sz, _stream]),
     "sed_stream_append_workspace_bytes": (_sz, [_i]),
     "sed_stream_append": (_i, [_fp, _l, _l, _fp, _l, _fp, _l, _fp, _i, _fp, _sz, _stream]),
+    "sed_detect_events_classwise": (_i, [_fp, _l, _i, _fp, _i, _fp, _sz, _fp, _fp, _fp, _fp, _fp, _fp, _stream]),
+    "sed_detect_events_batch_classwise": (_i, [_fp, _fp, _i, _i, _fp, _i, _fp, _sz, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _stream]),
+    "sed_stream_step_classwise": (_i, [_fp, _sz, _i, _i, _i, _i, _i, _i, _i, _i, _fp, _fp, _l, _fp, _i, _fp, _l, _i, _fp, _fp, _fp,
+                                       _fp, _fp, _fp, _fp, _fp, _sz, _stream]),
     "sed_prof_enable": (_i, [C.c_uint]),
     "sed_prof_read": (_i, [_i, C.POINTER(_d), C.POINTER(_l), C.POINTER(_d)]),
     "sed_prof_tag_name": (C.c_char_p, [_i]),

@@ -4,6 +4,10 @@
 // Frame arithmetic (output frames, tf input frames each): window w covers [start(w), start(w) + win_out) with
 // start(w) = min(w * hop_out, last_start_out) — the regular grid 0, hop, 2 hop, ... plus, where the last regular window stops
 // short of the end, one extra window aligned to the end (last_start_out + win_out == n_out).  The host planner builds that grid.
+//
+// The two decoding entries come twice: with one decoder setting for all classes (sed_detect_events, sed_detect_events_batch) and
+// with one row per class (…_classwise).  The class-wise ones launch their own bit-track and walk kernels around the
+// same device functions and share the peak, offset and scan kernels; the scalar ones launch what they always launched.
 #include <algorithm>
 #include <vector>
 #include "common.h"
@@ -83,6 +87,27 @@ __global__ __launch_bounds__(256) void detect_bits_k(const float* __restrict__ p
     }
 }
 
+// The class-wise form (sed_detect_events_classwise): grid y walks the classes of one median width, each compared with its own lo, hi
+template <int M>
+__global__ __launch_bounds__(256) void detect_bits_cw_k(const float* __restrict__ probs, int n_out, int K, long n_words, ClassList list,
+                                                        ClassTable tab, unsigned long long* __restrict__ on_bits,
+                                                        unsigned long long* __restrict__ hi_bits) {
+    const int k = list.k[blockIdx.y];
+    const long j = (long)blockIdx.x * 256 + threadIdx.x;
+    bool on = false, high = false;
+    if (j < n_out) {
+        const float p = median_nearest<M>(LinearRows{probs, K}, (int)j, k, n_out - 1);
+        on = p > tab.c[k].lo;
+        high = p > tab.c[k].hi;
+    }
+    const unsigned long long bo = __ballot(on), bh = __ballot(high);
+    const long w = j >> 6;
+    if ((threadIdx.x & 63) == 0 && w < n_words) {
+        on_bits[(size_t)k * n_words + w] = bo;
+        hi_bits[(size_t)k * n_words + w] = bh;
+    }
+}
+
 // Batched (SEG, sed_detect_events_batch): one wave per (recording r, class k), workgroup r*K + k; recording r's bit tracks
 // are [K][n_words_r] at word K*word_off[r] (detect_bits_seg_k), so no run, gap or event crosses recordings.
 // The walk itself is detect_walk_body of detect_shared.h (shared with the decoder sweep of tune.hip); here every finished event
@@ -119,6 +144,27 @@ __global__ __launch_bounds__(64) void detect_walk_k(const unsigned long long* __
     DetectEmit emit{write, max_events, k, r, write ? (long)offsets[blockIdx.x] : 0l, cls, onset, offset, SEG ? rec : nullptr, 0};
     detect_walk_body(on_bits + track0 + (size_t)k * n_words, hi_bits + track0 + (size_t)k * n_words, n_words, min_gap, min_len,
                      epos, eh, emit);
+    if (threadIdx.x == 0 && !write) counts[blockIdx.x] = emit.cnt;
+}
+
+// detect_walk_k with class k's own min_gap and min_len, read from the by-value table (k is workgroup-uniform)
+template <bool SEG = false>
+__global__ __launch_bounds__(64) void detect_walk_cw_k(const unsigned long long* __restrict__ on_bits,
+                                                       const unsigned long long* __restrict__ hi_bits, long n_words, ClassTable tab, int write,
+                                                       int max_events, int* __restrict__ counts, const int* __restrict__ offsets,
+                                                       int* __restrict__ cls, int* __restrict__ onset, int* __restrict__ offset,
+                                                       const int* __restrict__ word_off = nullptr, int K = 0, int* __restrict__ rec = nullptr) {
+    __shared__ int epos[DETECT_EDGE_CAP], eh[DETECT_EDGE_CAP];
+    const int r = SEG ? (int)blockIdx.x / K : 0;
+    const int k = SEG ? (int)blockIdx.x - r * K : (int)blockIdx.x;
+    size_t track0 = 0;
+    if (SEG) {
+        track0 = (size_t)K * word_off[r];
+        n_words = word_off[r + 1] - word_off[r];
+    }
+    DetectEmit emit{write, max_events, k, r, write ? (long)offsets[blockIdx.x] : 0l, cls, onset, offset, SEG ? rec : nullptr, 0};
+    detect_walk_body(on_bits + track0 + (size_t)k * n_words, hi_bits + track0 + (size_t)k * n_words, n_words, tab.c[k].min_gap,
+                     tab.c[k].min_len, epos, eh, emit);
     if (threadIdx.x == 0 && !write) counts[blockIdx.x] = emit.cnt;
 }
 
@@ -201,6 +247,42 @@ extern "C" int sed_detect_events(const float* probs, long n_out, int K, int medi
     if (max_events == 0) return 0;
     detect_walk_k<<<K, 64, 0, s>>>(ob, hb, nw, min_gap, min_len, 1, max_events, counts, offs, cls, onset, offset);
     SED_LAUNCH_CHECK("detect_walk(write)");
+    detect_peaks_k<<<max_events < 1024 ? max_events : 1024, 256, 0, s>>>(probs, K, count, max_events, cls, onset, offset, peak, peak_frame);
+    SED_LAUNCH_CHECK("detect_peaks");
+    return 0;
+}
+
+// Class-wise settings: classes_host [K] rows {median, lo, hi, min_gap, min_len}, class k decoded with row k.  The same
+// workspace, outputs and phases as sed_detect_events; the bit tracks are packed by one launch per distinct median width.
+extern "C" int sed_detect_events_classwise(const float* probs, long n_out, int K, const sed_tune_setting* classes_host, int max_events,
+                                           void* workspace, size_t workspace_bytes, int* cls, int* onset, int* offset, float* peak,
+                                           int* peak_frame, int* count, void* stream) {
+    SED_REQUIRE(probs && classes_host && workspace && count, "detect_events_classwise: null pointer");
+    const size_t need = sed_detect_workspace_bytes(n_out, K, max_events);
+    SED_REQUIRE(need > 0, "detect_events_classwise: bad sizes (n_out=%ld, K=%d in 1..32, max_events=%d >= 0)", n_out, K, max_events);
+    SED_REQUIRE(workspace_bytes >= need, "detect_events_classwise: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    ClassTable tab;
+    int widest;
+    SED_TRY(detect_class_table("detect_events_classwise", classes_host, K, tab, &widest));
+    SED_REQUIRE(max_events == 0 || (cls && onset && offset && peak && peak_frame), "detect_events_classwise: null output pointer");
+    hipStream_t s = as_stream(stream);
+    const long nw = detect_words(n_out);
+    unsigned long long* ob = (unsigned long long*)workspace;
+    unsigned long long* hb = ob + (size_t)K * nw;
+    int* counts = (int*)(hb + (size_t)K * nw);
+    int* offs = counts + K;
+    detect_for_widths(tab, K, [&](auto m, const ClassList& list) {
+        detect_bits_cw_k<decltype(m)::value><<<dim3((unsigned)cdiv(nw * 64, 256), (unsigned)list.n), 256, 0, s>>>(probs, (int)n_out, K, nw, list,
+                                                                                                           tab, ob, hb);
+    });
+    SED_LAUNCH_CHECK("detect_bits_classwise");
+    detect_walk_cw_k<<<K, 64, 0, s>>>(ob, hb, nw, tab, 0, max_events, counts, offs, cls, onset, offset);
+    SED_LAUNCH_CHECK("detect_walk_classwise(count)");
+    detect_offsets_k<<<1, 64, 0, s>>>(counts, K, offs, count);
+    SED_LAUNCH_CHECK("detect_offsets");
+    if (max_events == 0) return 0;
+    detect_walk_cw_k<<<K, 64, 0, s>>>(ob, hb, nw, tab, 1, max_events, counts, offs, cls, onset, offset);
+    SED_LAUNCH_CHECK("detect_walk_classwise(write)");
     detect_peaks_k<<<max_events < 1024 ? max_events : 1024, 256, 0, s>>>(probs, K, count, max_events, cls, onset, offset, peak, peak_frame);
     SED_LAUNCH_CHECK("detect_peaks");
     return 0;
@@ -312,6 +394,47 @@ extern "C" int sed_detect_events_batch(const float* probs, const long* n_out_hos
     detect_walk_k<true><<<groups, 64, 0, s>>>(w.ob, w.hb, 0, min_gap, min_len, 1, max_events, w.counts, w.offs, cls, onset, offset,
                                              w.word_off, K, rec);
     SED_LAUNCH_CHECK("detect_walk_batch(write)");
+    detect_peaks_k<true><<<max_events < 1024 ? max_events : 1024, 256, 0, s>>>(probs, K, event_off + R, max_events, cls, onset, offset,
+                                                                              peak, peak_frame, rec, w.out_off);
+    SED_LAUNCH_CHECK("detect_peaks_batch");
+    return 0;
+}
+
+// sed_detect_events_batch with class-wise settings (classes_host [K]): the same workspace, tables, outputs and phases
+extern "C" int sed_detect_events_batch_classwise(const float* probs, const long* n_out_host, int R, int K,
+                                                 const sed_tune_setting* classes_host, int max_events, void* workspace,
+                                                 size_t workspace_bytes, int* rec, int* cls, int* onset, int* offset, float* peak,
+                                                 int* peak_frame, int* event_off, void* stream) {
+    SED_REQUIRE(probs && n_out_host && classes_host && workspace && event_off, "detect_events_batch_classwise: null pointer");
+    SED_REQUIRE(R >= 1 && K >= 1 && K <= 32 && max_events >= 0,
+                "detect_events_batch_classwise: bad sizes (R=%d, K=%d in 1..32, max_events=%d)", R, K, max_events);
+    ClassTable tab;
+    int widest;
+    SED_TRY(detect_class_table("detect_events_batch_classwise", classes_host, K, tab, &widest));
+    SED_REQUIRE(max_events == 0 || (rec && cls && onset && offset && peak && peak_frame),
+                "detect_events_batch_classwise: null output pointer");
+    std::vector<int> h(2 * (size_t)(R + 1));                          // out_off [R+1] then word_off [R+1]
+    long rows, words;
+    SED_TRY(detect_seg_tables("detect_events_batch_classwise", n_out_host, R, K, h.data(), h.data() + R + 1, &rows, &words));
+    const size_t need = sed_detect_batch_workspace_bytes(rows, K, R, max_events);
+    SED_REQUIRE(need > 0, "detect_events_batch_classwise: bad sizes (R=%d, K=%d, %ld output frames)", R, K, rows);
+    SED_REQUIRE(workspace_bytes >= need, "detect_events_batch_classwise: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    hipStream_t s = as_stream(stream);
+    const DetBatchWs w = det_batch_layout(workspace, R, K, rows / 64 + R);
+    SED_TRY(detect_upload("detect_events_batch_classwise", w.out_off, h.data(), h.size() * 4, s));
+    detect_for_widths(tab, K, [&](auto m, const ClassList& list) {
+        detect_bits_seg_cw_k<decltype(m)::value><<<dim3((unsigned)cdiv(words, 4), (unsigned)list.n), 256, 0, s>>>(
+            probs, w.out_off, w.word_off, R, K, list, tab, (size_t)(w.hb - w.ob), w.ob);
+    });
+    SED_LAUNCH_CHECK("detect_bits_seg_classwise");
+    const unsigned groups = (unsigned)((long)R * K);
+    detect_walk_cw_k<true><<<groups, 64, 0, s>>>(w.ob, w.hb, 0, tab, 0, max_events, w.counts, w.offs, cls, onset, offset, w.word_off, K, rec);
+    SED_LAUNCH_CHECK("detect_walk_batch_classwise(count)");
+    detect_scan_k<<<1, 1024, 0, s>>>(w.counts, R * K, K, w.offs, event_off);
+    SED_LAUNCH_CHECK("detect_scan");
+    if (max_events == 0) return 0;
+    detect_walk_cw_k<true><<<groups, 64, 0, s>>>(w.ob, w.hb, 0, tab, 1, max_events, w.counts, w.offs, cls, onset, offset, w.word_off, K, rec);
+    SED_LAUNCH_CHECK("detect_walk_batch_classwise(write)");
     detect_peaks_k<true><<<max_events < 1024 ? max_events : 1024, 256, 0, s>>>(probs, K, event_off + R, max_events, cls, onset, offset,
                                                                               peak, peak_frame, rec, w.out_off);
     SED_LAUNCH_CHECK("detect_peaks_batch");

@@ -3,8 +3,9 @@
 // the edge walk of the event decoder and the exclusive scan of per-(segment, class) event counts.  The files call the SAME
 // functions, so a streamed track row is bit for bit the row sed_detect_stitch writes, a streamed filtered frame is the frame the
 // offline decoder thresholds, and the events a sweep scores are the events sed_detect_events_batch writes.  Host code: the
-// checks that several entries make (decoder settings, window grid, segment tables), the table upload and the dispatch from a
-// runtime median width to its instantiation.
+// checks that several entries make (decoder settings, window grid, segment tables), the table upload, the dispatch from a
+// runtime median width to its instantiation and, for the class-wise entries, the by-value table of per-class settings and the
+// lists of classes that share a width.
 #pragma once
 #include <type_traits>
 #include "common.h"
@@ -23,9 +24,10 @@ static const char* detect_who(const char* entry, const char* what, long i) {
     return i >= 0 ? s : entry;
 }
 
-// the decoder's settings; setting >= 0: the index of the setting in a sweep
-static int detect_check_decoder(const char* entry, long setting, int median, float lo, float hi, int min_gap, int min_len) {
-    const auto who = [&] { return detect_who(entry, "setting", setting); };
+// the decoder's settings; setting >= 0: the index of the setting in a sweep (or, what = "class", of the class in a class-wise table)
+static int detect_check_decoder(const char* entry, long setting, int median, float lo, float hi, int min_gap, int min_len,
+                                const char* what = "setting") {
+    const auto who = [&] { return detect_who(entry, what, setting); };
     SED_REQUIRE(median >= 1 && median <= 31 && (median & 1), "%s: median width must be odd, 1..31 (got %d)", who(), median);
     SED_REQUIRE(hi >= lo, "%s: need hi >= lo (got lo=%g, hi=%g)", who(), (double)lo, (double)hi);
     SED_REQUIRE(min_gap >= 0 && min_len >= 1, "%s: min_gap >= 0 and min_len >= 1 (got %d, %d)", who(), min_gap, min_len);
@@ -84,6 +86,37 @@ static void detect_with_median(int median, F&& f) {
         DETECT_MED(1) DETECT_MED(3) DETECT_MED(5) DETECT_MED(7) DETECT_MED(9) DETECT_MED(11) DETECT_MED(13) DETECT_MED(15)
         DETECT_MED(17) DETECT_MED(19) DETECT_MED(21) DETECT_MED(23) DETECT_MED(25) DETECT_MED(27) DETECT_MED(29) DETECT_MED(31)
 #undef DETECT_MED
+    }
+}
+
+// Class-wise decoder settings (the *_classwise entries).  K <= 32, so the K rows travel BY VALUE as a kernel
+// argument (640 bytes): no upload, no workspace.  The bit-track kernels are launched once per distinct median width over the
+// list of classes that have it, so the width stays a template argument and no wave ever chooses among instantiations.
+struct ClassTable { sed_tune_setting c[32]; };
+struct ClassList { int n; unsigned char k[32]; };                  // the classes that share one median width, ascending
+
+// classes_host [K] (K already checked to be 1..32) -> tab, every row checked like the scalar entry's five values;
+// *widest = the largest median width
+static int detect_class_table(const char* entry, const sed_tune_setting* classes_host, int K, ClassTable& tab, int* widest) {
+    tab = ClassTable{};
+    *widest = 1;
+    for (int k = 0; k < K; ++k) {
+        const sed_tune_setting c = classes_host[k];
+        SED_TRY(detect_check_decoder(entry, k, c.median, c.lo, c.hi, c.min_gap, c.min_len, "class"));
+        tab.c[k] = c;
+        *widest = c.median > *widest ? c.median : *widest;
+    }
+    return 0;
+}
+
+// f(std::integral_constant<int, M>, ClassList) for every median width M that a class has, in increasing width
+template <class F>
+static void detect_for_widths(const ClassTable& tab, int K, F&& f) {
+    for (int m = 1; m <= 31; m += 2) {
+        ClassList l{};
+        for (int k = 0; k < K; ++k)
+            if (tab.c[k].median == m) l.k[l.n++] = (unsigned char)k;
+        if (l.n) detect_with_median(m, [&](auto mm) { f(mm, l); });
     }
 }
 
@@ -165,6 +198,28 @@ __global__ __launch_bounds__(256) void detect_bits_seg_k(const float* __restrict
     for (int t = 0; t < thr.n(); ++t) {
         const unsigned long long b = __ballot(in && p > thr.at(t));
         if (lane == 0) bits[(size_t)t * track_stride + at] = b;
+    }
+}
+
+// The class-wise form (sed_detect_events_batch_classwise): grid y walks the classes of ONE median width (ClassList) and class k's
+// filtered value — the same median_nearest<M> call — is compared with its own lo (track 0) and hi (track 1), into the same words.
+template <int M>
+__global__ __launch_bounds__(256) void detect_bits_seg_cw_k(const float* __restrict__ probs, const int* __restrict__ out_off,
+                                                            const int* __restrict__ word_off, int R, int K, ClassList list, ClassTable tab,
+                                                            size_t track_stride, unsigned long long* __restrict__ bits) {
+    const int k = list.k[blockIdx.y], lane = threadIdx.x & 63;
+    const int gw = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (gw >= word_off[R]) return;                                    // wave-uniform
+    const int r = __builtin_amdgcn_readfirstlane(find_seg(word_off, R, gw));
+    const int n_out = out_off[r + 1] - out_off[r], nw = word_off[r + 1] - word_off[r], lw = gw - word_off[r];
+    const int j = lw * 64 + lane;
+    const bool in = j < n_out;
+    const float p = in ? median_nearest<M>(LinearRows{probs + (size_t)out_off[r] * K, K}, j, k, n_out - 1) : 0.f;
+    const size_t at = (size_t)K * word_off[r] + (size_t)k * nw + lw;
+    const unsigned long long bo = __ballot(in && p > tab.c[k].lo), bh = __ballot(in && p > tab.c[k].hi);
+    if (lane == 0) {
+        bits[at] = bo;
+        bits[track_stride + at] = bh;
     }
 }
 

@@ -7,6 +7,10 @@
 // complete, exists in the offline grid and does not touch the recording's end); filtered frame g is DECIDED iff track frame
 // g + median/2 is final.  At the end of a stream n_out is known: the offline grid's last window (end-aligned, or the single
 // short window of a stream shorter than win_out) arrives with the step and everything left becomes final.
+//
+// sed_stream_step_classwise is the same step with one row of decoder values per class.  `median` is then the WIDEST
+// class median: it sizes the rings and sets the ONE frontier of a feed (frame g of every class is decided once track frame
+// g + median/2 is final); class k filters with its own width and walks with its own lo, hi, min_gap and min_len.
 #include <vector>
 #include "common.h"
 #include "detect_shared.h"
@@ -190,16 +194,14 @@ __global__ __launch_bounds__(256) void stream_median_k(const StreamRec* __restri
 
 // one lane per (stream, class) walks its new decided frames.  WRITE = false counts the events this step emits; a scan turns
 // the counts into offsets; WRITE = true walks again from the same state, writes them and commits the state (once).
+// the walk of (stream s, class k), i = s*K + k, with that class's four decoder values
 template <bool WRITE>
-__global__ __launch_bounds__(256) void stream_walk_k(const StreamRec* __restrict__ recs, const float* __restrict__ filt,
-                                                     const float* __restrict__ track, int TR, int S, int K, int max_dg, float lo,
-                                                     float hi, int min_gap, int min_len, DecState* __restrict__ dec,
-                                                     int* __restrict__ counts, const int* __restrict__ offsets, int max_events,
-                                                     int* __restrict__ ev_stream, int* __restrict__ cls, int* __restrict__ onset,
-                                                     int* __restrict__ offset, float* __restrict__ peak, int* __restrict__ peak_frame) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= S * K) return;
-    const int s = i / K, k = i - s * K;
+__device__ __forceinline__ void stream_walk_one(const StreamRec* __restrict__ recs, const float* __restrict__ filt,
+                                                const float* __restrict__ track, int TR, int K, int max_dg, int i, int s, int k, float lo,
+                                                float hi, int min_gap, int min_len, DecState* __restrict__ dec, int* __restrict__ counts,
+                                                const int* __restrict__ offsets, int max_events, int* __restrict__ ev_stream,
+                                                int* __restrict__ cls, int* __restrict__ onset, int* __restrict__ offset,
+                                                float* __restrict__ peak, int* __restrict__ peak_frame) {
     const StreamRec r = recs[s];
     DecState st = dec[i];
     const int base = WRITE ? offsets[i] : 0;
@@ -252,6 +254,51 @@ __global__ __launch_bounds__(256) void stream_walk_k(const StreamRec* __restrict
     else counts[i] = cnt;
 }
 
+template <bool WRITE>
+__global__ __launch_bounds__(256) void stream_walk_k(const StreamRec* __restrict__ recs, const float* __restrict__ filt,
+                                                     const float* __restrict__ track, int TR, int S, int K, int max_dg, float lo,
+                                                     float hi, int min_gap, int min_len, DecState* __restrict__ dec,
+                                                     int* __restrict__ counts, const int* __restrict__ offsets, int max_events,
+                                                     int* __restrict__ ev_stream, int* __restrict__ cls, int* __restrict__ onset,
+                                                     int* __restrict__ offset, float* __restrict__ peak, int* __restrict__ peak_frame) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= S * K) return;
+    const int s = i / K, k = i - s * K;
+    stream_walk_one<WRITE>(recs, filt, track, TR, K, max_dg, i, s, k, lo, hi, min_gap, min_len, dec, counts, offsets, max_events,
+                           ev_stream, cls, onset, offset, peak, peak_frame);
+}
+
+// Class-wise settings (sed_stream_step_classwise): the lane of class k walks with row k of the by-value table.  The
+// frontier G is the feed's (decided once track frame g + widest/2 is final), so the walk is the scalar one with other constants.
+template <bool WRITE>
+__global__ __launch_bounds__(256) void stream_walk_cw_k(const StreamRec* __restrict__ recs, const float* __restrict__ filt,
+                                                        const float* __restrict__ track, int TR, int S, int K, int max_dg, ClassTable tab,
+                                                        DecState* __restrict__ dec, int* __restrict__ counts,
+                                                        const int* __restrict__ offsets, int max_events, int* __restrict__ ev_stream,
+                                                        int* __restrict__ cls, int* __restrict__ onset, int* __restrict__ offset,
+                                                        float* __restrict__ peak, int* __restrict__ peak_frame) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= S * K) return;
+    const int s = i / K, k = i - s * K;
+    const sed_tune_setting c = tab.c[k];
+    stream_walk_one<WRITE>(recs, filt, track, TR, K, max_dg, i, s, k, c.lo, c.hi, c.min_gap, c.min_len, dec, counts, offsets, max_events,
+                           ev_stream, cls, onset, offset, peak, peak_frame);
+}
+
+// stream_median_k for the classes of ONE median width (ClassList): one thread per (stream, newly decided frame, listed class)
+template <int M>
+__global__ __launch_bounds__(256) void stream_median_cw_k(const StreamRec* __restrict__ recs, const float* __restrict__ track, int TR,
+                                                          int K, int max_dg, ClassList list, float* __restrict__ filt) {
+    const StreamRec r = recs[blockIdx.y];
+    const long total = (long)(r.G_now - r.G_prev) * list.n;
+    const RingRows rows{track + (size_t)blockIdx.y * TR * K, TR, K};
+    const int last = r.end ? r.n_out - 1 : 0x7fffffff;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const int gg = (int)(i / list.n), k = list.k[i - (long)gg * list.n];
+        filt[((size_t)blockIdx.y * max_dg + gg) * K + k] = median_nearest<M>(rows, r.G_prev + gg, k, last);
+    }
+}
+
 static inline size_t st_al(size_t b) { return (b + 63) & ~(size_t)63; }
 
 extern "C" size_t sed_stream_step_workspace_bytes(int S, int K, int max_new_decided) {
@@ -261,39 +308,41 @@ extern "C" size_t sed_stream_step_workspace_bytes(int S, int K, int max_new_deci
 
 static inline long n_regular(long n_out, int win_out, int hop_out) { return n_out >= win_out ? (n_out - win_out) / hop_out + 1 : 0; }
 
-extern "C" int sed_stream_step(void* state, size_t state_bytes, int S, int K, int win_out, int hop_out, int median, int max_new_windows,
-                               int combine, int trim, float lo, float hi, int min_gap, int min_len, const float* logits,
-                               long logits_len, const long* table_host, int max_new_decided, float* probs, long probs_rows,
-                               int max_events, int* ev_stream, int* cls, int* onset, int* offset, float* peak, int* peak_frame,
-                               int* event_off, void* workspace, size_t workspace_bytes, void* stream) {
-    SED_REQUIRE(state && table_host && event_off && workspace, "stream_step: null pointer");
+// Both step entries.  `median` sizes the rings and sets the frontier; tab = nullptr: the scalar entry, one decoder setting
+// (median, lo, hi, min_gap, min_len) for every class; otherwise the class-wise entry (`median` = the widest class's width, the
+// four scalars unused).  `who` prefixes the messages.
+static int stream_step_impl(const char* who, const ClassTable* tab, void* state, size_t state_bytes, int S, int K, int win_out,
+                            int hop_out, int median, int max_new_windows, int combine, int trim, float lo, float hi, int min_gap,
+                            int min_len, const float* logits, long logits_len, const long* table_host, int max_new_decided, float* probs,
+                            long probs_rows, int max_events, int* ev_stream, int* cls, int* onset, int* offset, float* peak,
+                            int* peak_frame, int* event_off, void* workspace, size_t workspace_bytes, void* stream) {
     StreamDims d;
     SED_REQUIRE(stream_dims(S, K, win_out, hop_out, median, max_new_windows, d),
-                "stream_step: bad sizes (S=%d, K=%d in 1..32, win_out=%d, hop_out=%d, median=%d odd 1..31, max_new_windows=%d)", S, K,
+                "%s: bad sizes (S=%d, K=%d in 1..32, win_out=%d, hop_out=%d, median=%d odd 1..31, max_new_windows=%d)", who, S, K,
                 win_out, hop_out, median, max_new_windows);
-    SED_REQUIRE(state_bytes >= d.bytes, "stream_step: state of %zu bytes, %zu needed", state_bytes, d.bytes);
+    SED_REQUIRE(state_bytes >= d.bytes, "%s: state of %zu bytes, %zu needed", who, state_bytes, d.bytes);
     const size_t need = sed_stream_step_workspace_bytes(S, K, max_new_decided);
-    SED_REQUIRE(need > 0, "stream_step: bad max_new_decided=%d", max_new_decided);
-    SED_REQUIRE(workspace_bytes >= need, "stream_step: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-    SED_REQUIRE(combine == 0 || combine == 1, "stream_step: combine must be 0 (mean) or 1 (max), got %d", combine);
-    SED_TRY(detect_check_trim("stream_step", -1, 2, win_out, hop_out, trim));        // n_win = 2: a stream may always grow past one window
-    SED_TRY(detect_check_decoder("stream_step", -1, median, lo, hi, min_gap, min_len));
+    SED_REQUIRE(need > 0, "%s: bad max_new_decided=%d", who, max_new_decided);
+    SED_REQUIRE(workspace_bytes >= need, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
+    SED_REQUIRE(combine == 0 || combine == 1, "%s: combine must be 0 (mean) or 1 (max), got %d", who, combine);
+    SED_TRY(detect_check_trim(who, -1, 2, win_out, hop_out, trim));        // n_win = 2: a stream may always grow past one window
+    if (!tab) SED_TRY(detect_check_decoder(who, -1, median, lo, hi, min_gap, min_len));
     SED_REQUIRE(max_events >= 0 && (max_events == 0 || (ev_stream && cls && onset && offset && peak && peak_frame)),
-                "stream_step: null output pointer");
+                "%s: null output pointer", who);
     SED_REQUIRE(logits_len >= 0 && (logits || logits_len == 0) && probs_rows >= 0 && (probs || probs_rows == 0),
-                "stream_step: null buffer with a non-zero length");
+                "%s: null buffer with a non-zero length", who);
     const int r = median / 2;
     std::vector<StreamRec> h(S);
     long most_new = 0, most_df = 0, most_dg = 0;
     for (int s = 0; s < S; ++s) {
         const long* t = table_host + 8 * s;
         const long n_new = t[0], lg = t[1], w_first = t[2], prev = t[3], now = t[4], end = t[5], wos = t[6], poff = t[7];
-        SED_REQUIRE(prev >= 0 && now >= 0 && now <= 0x3fffffffL && (end == 0 || end == 1), "stream_step: stream %d: bad frame counts", s);
-        SED_REQUIRE(now >= prev, "stream_step: stream %d: n_out goes backwards (%ld after %ld)", s, now, prev);
-        SED_REQUIRE(w_first == n_regular(prev, win_out, hop_out), "stream_step: stream %d: %ld windows done do not match n_out=%ld", s, w_first, prev);
+        SED_REQUIRE(prev >= 0 && now >= 0 && now <= 0x3fffffffL && (end == 0 || end == 1), "%s: stream %d: bad frame counts", who, s);
+        SED_REQUIRE(now >= prev, "%s: stream %d: n_out goes backwards (%ld after %ld)", who, s, now, prev);
+        SED_REQUIRE(w_first == n_regular(prev, win_out, hop_out), "%s: stream %d: %ld windows done do not match n_out=%ld", who, s, w_first, prev);
         long n_win = n_regular(now, win_out, hop_out), want_wos = win_out, last_start = 0;
         if (end) {
-            SED_REQUIRE(now >= 1, "stream_step: stream %d ends without one output frame", s);
+            SED_REQUIRE(now >= 1, "%s: stream %d ends without one output frame", who, s);
             if (now >= win_out) {
                 last_start = now - win_out;
                 if ((n_win - 1) * hop_out != last_start) ++n_win;    // the end-aligned window
@@ -302,10 +351,10 @@ extern "C" int sed_stream_step(void* state, size_t state_bytes, int S, int K, in
             }
         }
         SED_REQUIRE(n_new == n_win - w_first && wos == want_wos && n_new <= max_new_windows + end,
-                    "stream_step: stream %d: %ld new windows of %ld frames, the grid has %ld of %ld (at most %d per step)", s, n_new, wos,
+                    "%s: stream %d: %ld new windows of %ld frames, the grid has %ld of %ld (at most %d per step)", who, s, n_new, wos,
                     n_win - w_first, want_wos, max_new_windows);
         SED_REQUIRE(n_new == 0 || (lg >= 0 && lg <= logits_len && n_new * wos * K <= logits_len - lg),
-                    "stream_step: stream %d: logits [%ld, +%ld x %ld x %d) leave the buffer of %ld floats", s, lg, n_new, wos, K, logits_len);
+                    "%s: stream %d: logits [%ld, +%ld x %ld x %d) leave the buffer of %ld floats", who, s, lg, n_new, wos, K, logits_len);
         StreamRec& q = h[s];
         q.logit_off = lg; q.n_new = (int)n_new; q.w_first = (int)w_first; q.win_out_s = (int)wos; q.end = (int)end;
         q.n_out = (int)now; q.n_win = (int)n_win; q.last_start = (int)last_start; q.prob_off = (int)poff;
@@ -315,13 +364,13 @@ extern "C" int sed_stream_step(void* state, size_t state_bytes, int S, int K, in
         q.G_now = end ? (int)now : (q.F_now > r ? q.F_now - r : 0);
         // everything still read is inside the rings
         const long w_lo = q.F_prev >= win_out ? (q.F_prev - win_out) / hop_out + 1 : 0;
-        SED_REQUIRE(w_first + n_new - w_lo <= d.WR, "stream_step: stream %d: %ld live windows, the ring holds %d", s, w_first + n_new - w_lo, d.WR);
-        SED_REQUIRE(q.F_now - (q.G_prev > r ? q.G_prev - r : 0) <= d.TR, "stream_step: stream %d: %d live track frames, the ring holds %d", s,
+        SED_REQUIRE(w_first + n_new - w_lo <= d.WR, "%s: stream %d: %ld live windows, the ring holds %d", who, s, w_first + n_new - w_lo, d.WR);
+        SED_REQUIRE(q.F_now - (q.G_prev > r ? q.G_prev - r : 0) <= d.TR, "%s: stream %d: %d live track frames, the ring holds %d", who, s,
                     q.F_now - (q.G_prev > r ? q.G_prev - r : 0), d.TR);
-        SED_REQUIRE(q.G_now - q.G_prev <= max_new_decided, "stream_step: stream %d decides %d frames, max_new_decided=%d", s,
+        SED_REQUIRE(q.G_now - q.G_prev <= max_new_decided, "%s: stream %d decides %d frames, max_new_decided=%d", who, s,
                     q.G_now - q.G_prev, max_new_decided);
         SED_REQUIRE(!probs || (poff >= 0 && poff + (q.F_now - q.F_prev) <= probs_rows && poff <= 0x7fffffffL),
-                    "stream_step: stream %d: its %d new rows at %ld leave probs [%ld]", s, q.F_now - q.F_prev, poff, probs_rows);
+                    "%s: stream %d: its %d new rows at %ld leave probs [%ld]", who, s, q.F_now - q.F_prev, poff, probs_rows);
         most_new = n_new * wos * K > most_new ? n_new * wos * K : most_new;
         most_df = (long)(q.F_now - q.F_prev) * K > most_df ? (long)(q.F_now - q.F_prev) * K : most_df;
         most_dg = (long)(q.G_now - q.G_prev) * K > most_dg ? (long)(q.G_now - q.G_prev) * K : most_dg;
@@ -332,7 +381,7 @@ extern "C" int sed_stream_step(void* state, size_t state_bytes, int S, int K, in
     int* counts = (int*)p; p += st_al((size_t)S * K * 4);
     int* offs = (int*)p; p += st_al((size_t)S * K * 4);
     float* filt = (float*)p;
-    SED_TRY(detect_upload("stream_step", recs, h.data(), (size_t)S * sizeof(StreamRec), st));
+    SED_TRY(detect_upload(who, recs, h.data(), (size_t)S * sizeof(StreamRec), st));
     float* ring = (float*)state;
     float* track = (float*)((char*)state + d.track_off);
     DecState* dec = (DecState*)((char*)state + d.dec_off);
@@ -348,19 +397,65 @@ extern "C" int sed_stream_step(void* state, size_t state_bytes, int S, int K, in
         SED_LAUNCH_CHECK("stream_stitch");
     }
     if (most_dg) {
-        detect_with_median(median, [&](auto m) {
-            stream_median_k<decltype(m)::value><<<dim3(blocks(most_dg), (unsigned)S), 256, 0, st>>>(recs, track, d.TR, K, max_new_decided, filt);
-        });
+        if (tab) {
+            detect_for_widths(*tab, K, [&](auto m, const ClassList& list) {
+                stream_median_cw_k<decltype(m)::value><<<dim3(blocks(most_dg / K * list.n), (unsigned)S), 256, 0, st>>>(
+                    recs, track, d.TR, K, max_new_decided, list, filt);
+            });
+        } else {
+            detect_with_median(median, [&](auto m) {
+                stream_median_k<decltype(m)::value><<<dim3(blocks(most_dg), (unsigned)S), 256, 0, st>>>(recs, track, d.TR, K, max_new_decided, filt);
+            });
+        }
         SED_LAUNCH_CHECK("stream_median");
     }
     const unsigned wb = (unsigned)cdiv((long)S * K, 256);
-    stream_walk_k<false><<<wb, 256, 0, st>>>(recs, filt, track, d.TR, S, K, max_new_decided, lo, hi, min_gap, min_len, dec, counts, offs,
-                                            max_events, ev_stream, cls, onset, offset, peak, peak_frame);
+    if (tab)
+        stream_walk_cw_k<false><<<wb, 256, 0, st>>>(recs, filt, track, d.TR, S, K, max_new_decided, *tab, dec, counts, offs, max_events,
+                                                   ev_stream, cls, onset, offset, peak, peak_frame);
+    else
+        stream_walk_k<false><<<wb, 256, 0, st>>>(recs, filt, track, d.TR, S, K, max_new_decided, lo, hi, min_gap, min_len, dec, counts, offs,
+                                                max_events, ev_stream, cls, onset, offset, peak, peak_frame);
     SED_LAUNCH_CHECK("stream_walk(count)");
     detect_scan_k<<<1, 1024, 0, st>>>(counts, S * K, K, offs, event_off);
     SED_LAUNCH_CHECK("stream_scan");
-    stream_walk_k<true><<<wb, 256, 0, st>>>(recs, filt, track, d.TR, S, K, max_new_decided, lo, hi, min_gap, min_len, dec, counts, offs,
-                                           max_events, ev_stream, cls, onset, offset, peak, peak_frame);
+    if (tab)
+        stream_walk_cw_k<true><<<wb, 256, 0, st>>>(recs, filt, track, d.TR, S, K, max_new_decided, *tab, dec, counts, offs, max_events,
+                                                  ev_stream, cls, onset, offset, peak, peak_frame);
+    else
+        stream_walk_k<true><<<wb, 256, 0, st>>>(recs, filt, track, d.TR, S, K, max_new_decided, lo, hi, min_gap, min_len, dec, counts, offs,
+                                               max_events, ev_stream, cls, onset, offset, peak, peak_frame);
     SED_LAUNCH_CHECK("stream_walk(write)");
     return 0;
+}
+
+extern "C" int sed_stream_step(void* state, size_t state_bytes, int S, int K, int win_out, int hop_out, int median, int max_new_windows,
+                               int combine, int trim, float lo, float hi, int min_gap, int min_len, const float* logits,
+                               long logits_len, const long* table_host, int max_new_decided, float* probs, long probs_rows,
+                               int max_events, int* ev_stream, int* cls, int* onset, int* offset, float* peak, int* peak_frame,
+                               int* event_off, void* workspace, size_t workspace_bytes, void* stream) {
+    SED_REQUIRE(state && table_host && event_off && workspace, "stream_step: null pointer");
+    return stream_step_impl("stream_step", nullptr, state, state_bytes, S, K, win_out, hop_out, median, max_new_windows, combine, trim, lo,
+                            hi, min_gap, min_len, logits, logits_len, table_host, max_new_decided, probs, probs_rows, max_events, ev_stream,
+                            cls, onset, offset, peak, peak_frame, event_off, workspace, workspace_bytes, stream);
+}
+
+// sed_stream_step with class-wise settings (classes_host [K]).  `median` is the width the state was sized with and must
+// be the widest of the K classes: ONE frontier per feed, filtered frame g of every class decided once track frame g + median/2 is
+// final.  A refusal (a bad class row included) comes before any launch, so the state is left as it was.
+extern "C" int sed_stream_step_classwise(void* state, size_t state_bytes, int S, int K, int win_out, int hop_out, int median,
+                                         int max_new_windows, int combine, int trim, const sed_tune_setting* classes_host,
+                                         const float* logits, long logits_len, const long* table_host, int max_new_decided, float* probs,
+                                         long probs_rows, int max_events, int* ev_stream, int* cls, int* onset, int* offset, float* peak,
+                                         int* peak_frame, int* event_off, void* workspace, size_t workspace_bytes, void* stream) {
+    SED_REQUIRE(state && classes_host && table_host && event_off && workspace, "stream_step_classwise: null pointer");
+    SED_REQUIRE(K >= 1 && K <= 32, "stream_step_classwise: bad sizes (K=%d in 1..32)", K);
+    ClassTable tab;
+    int widest;
+    SED_TRY(detect_class_table("stream_step_classwise", classes_host, K, tab, &widest));
+    SED_REQUIRE(median == widest, "stream_step_classwise: median=%d must be the widest median of the classes (%d): the state is sized with it",
+                median, widest);
+    return stream_step_impl("stream_step_classwise", &tab, state, state_bytes, S, K, win_out, hop_out, median, max_new_windows, combine,
+                            trim, 0.f, 0.f, 0, 1, logits, logits_len, table_host, max_new_decided, probs, probs_rows, max_events,
+                            ev_stream, cls, onset, offset, peak, peak_frame, event_off, workspace, workspace_bytes, stream);
 }

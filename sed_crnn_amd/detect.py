@@ -21,11 +21,53 @@ import numpy as np
 import torch
 
 from . import feature
-from ._lib import SedHipError, check, lib, ptr, stream_ptr
+from ._lib import SedHipError, TuneSetting, check, lib, ptr, stream_ptr
 from .data import SEQ_LEN_IN
 from .model import HipCRNN
 
 _EVENT_KEYS = ("cls", "onset", "offset", "peak", "peak_frame")
+
+
+def _is_per_class(v):
+    """a decoder argument given per class: a list, a tuple, an ndarray or a tensor with at least one axis"""
+    return isinstance(v, (list, tuple)) or (isinstance(v, (np.ndarray, torch.Tensor)) and v.ndim >= 1)
+
+
+def _class_settings(K, threshold, low, median, min_gap, min_len):
+    """The five decoder arguments, each a scalar or a length-K sequence -> (class-wise?, K dicts of scalars).  Scalars
+    broadcast; ``low=None`` means low_k = threshold_k.  ValueError names the class and the argument."""
+    given = dict(threshold=threshold, low=low, median=median, min_gap=min_gap, min_len=min_len)
+    classwise = any(_is_per_class(v) for v in given.values())
+    cols = {}
+    for name, v in given.items():
+        if _is_per_class(v):
+            v = v.detach().cpu().tolist() if isinstance(v, torch.Tensor) else np.asarray(v).tolist()
+            if len(v) != K or any(_is_per_class(x) for x in v):
+                raise ValueError(f"{name} has {len(v)} entries, the net has {K} classes (give a scalar or one value per class, "
+                                 f"as a list, tuple, ndarray or 1-D tensor)")
+            cols[name] = v
+        else:
+            cols[name] = [v] * K
+    rows = []
+    for k in range(K):
+        who = f"class {k}: " if classwise else ""
+        hi = float(cols["threshold"][k])
+        lo_k = cols["low"][k]
+        lo = hi if lo_k is None else float(lo_k)
+        if not lo <= hi:
+            raise ValueError(f"{who}low={lo_k} must not exceed threshold={cols['threshold'][k]}")
+        m, gap, ml = cols["median"][k], cols["min_gap"][k], cols["min_len"][k]
+        for name, x in (("median", m), ("min_gap", gap), ("min_len", ml)):
+            if classwise and int(x) != x:
+                raise ValueError(f"{who}{name} must be an integer, got {x}")
+        if not (1 <= int(m) <= 31 and int(m) % 2 == 1):
+            raise ValueError(f"{who}median must be odd, 1..31, got {m}")
+        if classwise and int(gap) < 0:
+            raise ValueError(f"{who}min_gap must be >= 0, got {gap}")
+        if classwise and int(ml) < 1:
+            raise ValueError(f"{who}min_len must be >= 1, got {ml}")
+        rows.append(dict(threshold=hi, low=lo, median=int(m), min_gap=int(gap), min_len=int(ml)))
+    return classwise, rows
 
 
 def _event_tensors(keys, cap, device):
@@ -226,7 +268,10 @@ class EventDetector:
     ``combine`` "mean" | "max" over overlapping windows; ``trim`` output frames dropped at interior window edges;
     ``threshold`` (hi) / ``low`` (lo, default = threshold): runs of p' > lo kept when max p' > hi; ``median`` odd filter width
     in output frames (1 = off); ``min_gap`` merge events separated by at most that many frames; ``min_len`` drop shorter
-    events; ``mean`` / ``std``: the float64 [C*F] scaler of ``data.standard_scaler_fit`` (one entry per feature column: [F] for a
+    events.  Each of these five is a scalar or a sequence of K = ``model.dense[-1]`` values, one per class (list, tuple,
+    ndarray or 1-D tensor): with any sequence the detector is CLASS-WISE (``det.classwise``; scalars broadcast, ``low=None``
+    means low_k = threshold_k) and every decode — single, batched, streamed — runs class k with its own five values
+    (DESIGN 5l).  ``mean`` / ``std``: the float64 [C*F] scaler of ``data.standard_scaler_fit`` (one entry per feature column: [F] for a
     1-channel net), fused into the log-mel front end."""
 
     def __init__(self, model, seq_len=SEQ_LEN_IN, hop=None, combine="mean", trim=0, threshold=0.5, low=None, median=1,
@@ -235,23 +280,24 @@ class EventDetector:
             raise TypeError(f"EventDetector needs a sed_crnn_amd net, got {type(model).__name__}")
         if combine not in ("mean", "max"):
             raise ValueError(f"combine must be 'mean' or 'max', got {combine!r}")
-        lo = float(threshold if low is None else low)
-        if not lo <= float(threshold):
-            raise ValueError(f"low={low} must not exceed threshold={threshold}")
-        if not (1 <= int(median) <= 31 and int(median) % 2 == 1):
-            raise ValueError(f"median must be odd, 1..31, got {median}")
-        if int(min_gap) < 0 or int(min_len) < 1 or int(max_batch) < 1:
+        K = model.dense[-1]
+        if K > 32:
+            raise ValueError(f"event decoding handles up to 32 classes, the net has {K}")
+        classwise, rows = _class_settings(K, threshold, low, median, min_gap, min_len)
+        if any(r["min_gap"] < 0 or r["min_len"] < 1 for r in rows) or int(max_batch) < 1:
             raise ValueError("need min_gap >= 0, min_len >= 1 and max_batch >= 1")
-        if model.dense[-1] > 32:
-            raise ValueError(f"event decoding handles up to 32 classes, the net has {model.dense[-1]}")
         if (mean is None) != (std is None):
             raise ValueError("give both mean and std (data.standard_scaler_fit) or neither")
         self.model = model
         self.seq_len, self.hop = int(seq_len), (int(seq_len) // 2 if hop is None else int(hop))
         self.combine, self.trim = combine, int(trim)
         self._combine_id = ("mean", "max").index(combine)                  # as the stitch entries take it
-        self.hi, self.lo = float(threshold), lo
-        self.median, self.min_gap, self.min_len = int(median), int(min_gap), int(min_len)
+        # scalars, or (class-wise) lists of K: a detector given any per-class argument decodes with the class-wise entries
+        self.classwise, self._classes, self._ctab = classwise, rows, None
+        col = (lambda n: [r[n] for r in rows]) if classwise else (lambda n: rows[0][n])
+        self.hi, self.lo = col("threshold"), col("low")
+        self.median, self.min_gap, self.min_len = col("median"), col("min_gap"), col("min_len")
+        self.median_max = max(r["median"] for r in rows)                   # what a stream's state is sized with
         self.mean = None if mean is None else torch.as_tensor(mean, dtype=torch.float64)      # numpy or device tensors
         self.std = None if std is None else torch.as_tensor(std, dtype=torch.float64)
         if self.mean is not None and model.in_channels > 1:
@@ -288,12 +334,29 @@ class EventDetector:
 
     # ── scoring and tuning the decoder (tune.py) ──
     def decoder_settings(self):
-        """this detector's decoder values, as ``DecoderGrid`` / ``with_decoder`` take them"""
-        return dict(threshold=self.hi, low=self.lo, median=self.median, min_gap=self.min_gap, min_len=self.min_len)
+        """this detector's decoder values, as ``with_decoder`` (and, for scalars, ``DecoderGrid``) takes them: scalars, or lists
+        of K when the detector is class-wise"""
+        g = (lambda v: list(v)) if self.classwise else (lambda v: v)
+        return dict(threshold=g(self.hi), low=g(self.lo), median=g(self.median), min_gap=g(self.min_gap), min_len=g(self.min_len))
+
+    def class_settings(self):
+        """K dicts of scalars (``threshold``, ``low``, ``median``, ``min_gap``, ``min_len``): what class k is decoded with; on a
+        scalar detector K copies of its one setting"""
+        return [dict(r) for r in self._classes]
+
+    def _class_table(self, K):
+        """the K rows as the class-wise entries take them (a host array of sed_decoder_setting)"""
+        if K != len(self._classes):
+            raise ValueError(f"the track has {K} classes, the detector has settings for {len(self._classes)}")
+        if self._ctab is None:
+            self._ctab = (TuneSetting * K)(*[TuneSetting(r["median"], r["low"], r["threshold"], r["min_gap"], r["min_len"])
+                                             for r in self._classes])
+        return C.cast(self._ctab, C.c_void_p)
 
     def with_decoder(self, **settings):
         """A new detector that shares the model, the scaler and the window grid and has the decoder values (``threshold``,
-        ``low``, ``median``, ``min_gap``, ``min_len``) replaced.  ``threshold`` without ``low`` means low = threshold."""
+        ``low``, ``median``, ``min_gap``, ``min_len``) replaced, each a scalar or one value per class (any sequence makes the
+        new detector class-wise).  ``threshold`` without ``low`` means low = threshold."""
         extra = set(settings) - {"threshold", "low", "median", "min_gap", "min_len"}
         if extra:
             raise TypeError(f"with_decoder takes decoder settings only, got {sorted(extra)}")
@@ -314,10 +377,22 @@ class EventDetector:
         return tune.sweep(track, ref, grid, collar, offset_collar, offset_percent, block, max_workspace_bytes, self._tune_cache)
 
     def score(self, result, ref, collar=1, offset_collar=None, offset_percent=None, block=None):
-        """the sweep with G = 1 and this detector's own decoder setting: how good are ``result``'s events against ``ref``"""
-        from .tune import DecoderGrid
-        return self.sweep(result, ref, DecoderGrid.from_settings([self.decoder_settings()]), collar, offset_collar, offset_percent,
-                          block)
+        """the sweep with G = 1 and this detector's own decoder setting: how good are ``result``'s events against ``ref``.  A
+        class-wise detector sweeps its distinct class settings (at most K) and takes class k's counts from class k's setting, on
+        the device: ``counts`` is still [1, K, 6] and ``grid[0]`` the detector's ``decoder_settings()``."""
+        from .tune import DecoderGrid, SweepResult
+        if not self.classwise:
+            return self.sweep(result, ref, DecoderGrid.from_settings([self.decoder_settings()]), collar, offset_collar,
+                              offset_percent, block)
+        distinct = []
+        for r in self._classes:
+            if r not in distinct:
+                distinct.append(r)
+        res = self.sweep(result, ref, DecoderGrid.from_settings(distinct), collar, offset_collar, offset_percent, block)
+        dev = res.counts.device
+        g = torch.tensor([distinct.index(r) for r in self._classes], device=dev)
+        row = res.counts[g, torch.arange(len(self._classes), device=dev)].unsqueeze(0).contiguous()
+        return SweepResult(row, [self.decoder_settings()], res.collar, res.block, res.n_slices, res.n_tracks, res.workspace_bytes)
 
     # ── the whole path ──
     def __call__(self, waveform, sr=None, channels=1):
@@ -446,6 +521,11 @@ class EventDetector:
         if self._dws is None or self._dws.numel() < need or self._dws.device != dev:
             self._dws = torch.empty(need, dtype=torch.uint8, device=dev)
         count = torch.empty(1, dtype=torch.int32, device=dev)
+        if self.classwise:
+            table = self._class_table(K)
+            return self._decode_growing(_EVENT_KEYS, count, lambda cap, out: check(lib().sed_detect_events_classwise(
+                ptr(probs), n_out, K, table, cap, ptr(self._dws), self._dws.numel(), *(ptr(out[n]) for n in _EVENT_KEYS), ptr(count),
+                stream_ptr()), "sed_detect_events_classwise"))[0]
         return self._decode_growing(_EVENT_KEYS, count, lambda cap, out: check(lib().sed_detect_events(
             ptr(probs), n_out, K, self.median, self.lo, self.hi, self.min_gap, self.min_len, cap, ptr(self._dws), self._dws.numel(),
             *(ptr(out[n]) for n in _EVENT_KEYS), ptr(count), stream_ptr()), "sed_detect_events"))[0]
@@ -579,6 +659,11 @@ class EventDetector:
         dev = probs.device
         ev_off = torch.empty(R + 1, dtype=torch.int32, device=dev)
         keys = ("rec",) + _EVENT_KEYS
+        if self.classwise:
+            table = self._class_table(K)
+            return self._decode_growing(keys, ev_off, lambda cap, out: check(lib().sed_detect_events_batch_classwise(
+                ptr(probs), C.c_void_p(n_out.ctypes.data), R, K, table, cap, ptr(ws), ws.numel(), *(ptr(out[n]) for n in keys),
+                ptr(ev_off), stream_ptr()), "sed_detect_events_batch_classwise"))
         return self._decode_growing(keys, ev_off, lambda cap, out: check(lib().sed_detect_events_batch(
             ptr(probs), C.c_void_p(n_out.ctypes.data), R, K, self.median, self.lo, self.hi, self.min_gap, self.min_len, cap, ptr(ws),
             ws.numel(), *(ptr(out[n]) for n in keys), ptr(ev_off), stream_ptr()), "sed_detect_events_batch"))

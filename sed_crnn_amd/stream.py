@@ -11,6 +11,17 @@ A stream gives exactly what the offline path gives on the concatenation of every
 * a pending event [a, b) is emitted in the first step in which more than ``b + min_gap`` frames are decided and no run that
   began at or before ``b + min_gap`` is still open.
 
+A class-wise detector (``EventDetector(..., median=[...])``) streams with ONE frontier per feed:
+
+* filtered frame g of EVERY class is decided once track frame ``g + R`` is final, ``R = max_k median_k // 2``: the state and the
+  schedule are sized with the widest median, and class k's filter (width ``median_k <= 2R + 1``) reads final frames only;
+* a pending event [a, b) of class k is emitted in the first step in which more than ``b + min_gap_k`` frames are decided and no
+  run of class k that began at or before ``b + min_gap_k`` is still open.
+
+A class with a narrow filter therefore becomes final ``R - median_k // 2`` output frames later than it strictly could: the
+price of per-feed state of constant size and a step that stays one kernel sequence.  Over a feed's life the events are exactly
+the offline class-wise decode of the whole track.
+
 ``flush`` ends streams: the offline grid's last window (end-aligned, or one short sequence) runs, everything left is emitted and
 the streams restart at frame 0.  Between calls everything lives on the device, in buffers whose size depends on ``seq_len``,
 ``hop``, ``median``, ``max_new_windows`` and S only; a long push is split into steps of at most ``max_new_windows`` windows per
@@ -166,7 +177,7 @@ class StreamDetector:
         self.S, self.keep_probs, self.max_new = S, bool(keep_probs), int(max_new_windows)
         self.K, self.CF = m.dense[-1], m.in_channels * m.n_mels
         tf = m.time_factor
-        self.sched = StreamSchedules(tf, det.seq_len, det.hop, det.trim, det.median, S)
+        self.sched = StreamSchedules(tf, det.seq_len, det.hop, det.trim, det.median_max, S)     # class-wise: the widest median
         self.win_out, self.hop_out = self.sched.win_out, self.sched.hop_out
         self.step_frames = self.max_new * det.hop                          # feature frames per stream and step
         self.FC = det.seq_len + tf + self.step_frames                      # rows per half of a stream's feature region
@@ -175,7 +186,7 @@ class StreamDetector:
         if self.q + 1 > self.step_frames:
             raise ValueError(f"hop_length={h} is too small: the {self.q + 1} frames of a flush exceed one step of {self.step_frames}")
         self.CC = (self.q + 1) * h + feature.NFFT // 2                     # samples per half of a stream's PCM carry (an upper bound)
-        self._dims = (S, self.K, self.win_out, self.hop_out, det.median, self.max_new)
+        self._dims = (S, self.K, self.win_out, self.hop_out, det.median_max, self.max_new)
         self._core_bytes = lib().sed_stream_state_bytes(*self._dims)
         if self._core_bytes == 0:
             check(-1, "sed_stream_state_bytes")
@@ -353,11 +364,16 @@ class StreamDetector:
         ev_off = torch.empty(S + 1, dtype=torch.int32, device=dev)
         probs = torch.empty(n_probs, K, device=dev) if self.keep_probs else None
         give = probs is not None and n_probs > 0
-        _timed(self.marks, "step", lambda: check(lib().sed_stream_step(
-            ptr(self._state), self._state.numel(), *self._dims, det._combine_id, det.trim, det.lo, det.hi,
-            det.min_gap, det.min_len, ptr(logits) if n_logits else None, n_logits, C.c_void_p(table.ctypes.data), dg_max,
-            ptr(probs) if give else None, n_probs if give else 0, cap, *(ptr(ev[k]) for k in _KEYS), ptr(ev_off), ptr(self._sws),
-            self._sws.numel(), stream_ptr()), "sed_stream_step"))
+        rest = (ptr(logits) if n_logits else None, n_logits, C.c_void_p(table.ctypes.data), dg_max, ptr(probs) if give else None,
+                n_probs if give else 0, cap, *(ptr(ev[k]) for k in _KEYS), ptr(ev_off), ptr(self._sws), self._sws.numel(), stream_ptr())
+        if det.classwise:
+            _timed(self.marks, "step", lambda: check(lib().sed_stream_step_classwise(
+                ptr(self._state), self._state.numel(), *self._dims, det._combine_id, det.trim, det._class_table(K), *rest),
+                "sed_stream_step_classwise"))
+        else:
+            _timed(self.marks, "step", lambda: check(lib().sed_stream_step(
+                ptr(self._state), self._state.numel(), *self._dims, det._combine_id, det.trim, det.lo, det.hi,
+                det.min_gap, det.min_len, *rest), "sed_stream_step"))
         offs = ev_off.cpu().tolist()                                        # the one blocking read of a step
         if offs[-1] > cap:
             raise SedHipError(f"sed_stream_step emitted {offs[-1]} events, more than the bound {cap}")
@@ -622,7 +638,8 @@ class StreamDetector:
         n = self.S * self.K
         d = self._state[self._core_bytes - 64 * n:].view(torch.int32).view(n, 16).cpu().numpy()
         out = []
+        gaps = [r["min_gap"] for r in self.det.class_settings()]          # class k merges across its own min_gap
         for i in np.nonzero((d[:, 0] != 0) & (d[:, 2] != 0))[0]:
-            merge = d[i, 5] != 0 and d[i, 1] - d[i, 7] <= self.det.min_gap
+            merge = d[i, 5] != 0 and d[i, 1] - d[i, 7] <= gaps[int(i) % self.K]
             out.append((int(i) // self.K, int(i) % self.K, int(d[i, 6] if merge else d[i, 1])))
         return out

@@ -333,6 +333,23 @@ class SweepResult:
         return g, self.grid[g], float(v[g])
 
 
+    def best_per_class(self, metric="f1_event"):
+        """(g [K] int array, settings dict of K-lists, scores [K]): for every class the setting with its highest class-wise
+        F1 / lowest class-wise ER, ties broken by the lowest g.  A NaN ER (a class without reference) counts as +inf, so such a
+        class takes g = 0.  The dict is what ``EventDetector.with_decoder`` takes to build the class-wise detector."""
+        if metric not in ("f1_event", "f1_segment", "er_segment"):
+            raise ValueError(f"metric must be 'f1_event', 'f1_segment' or 'er_segment', got {metric!r}")
+        if len(self.grid) == 0:
+            raise ValueError("an empty grid has no best setting")
+        cw, _ = getattr(self, metric)()
+        if metric == "er_segment":
+            g = np.argmin(np.where(np.isnan(cw), np.inf, cw), axis=0)
+        else:
+            g = np.argmax(cw, axis=0)
+        sets = [self.grid[int(i)] for i in g]
+        return g, {n: [s[n] for s in sets] for n in _SETTING_KEYS}, cw[g, np.arange(cw.shape[1])]
+
+
 # ───────────────────────── the sweep ─────────────────────────
 def _track(track):
     """BatchDetectionResult | DetectionResult | (probs, out_offsets) -> (probs [n_total, K], out_offsets list [R+1])"""
@@ -418,8 +435,12 @@ def sweep(track, ref, grid, collar=1, offset_collar=None, offset_percent=None, b
     return SweepResult(counts, grid, int(collar), int(block), len(slices), max(s[3] for s in slices), need)
 
 
-def tune_decoder(det, track, ref, grid, metric="f1_event", average="micro", **kw):
-    """One shot: ``det.sweep(track, ref, grid, **kw)``, then the detector with the best setting -> (detector, SweepResult)."""
+def tune_decoder(det, track, ref, grid, metric="f1_event", average="micro", per_class=False, **kw):
+    """One shot: ``det.sweep(track, ref, grid, **kw)``, then the detector with the best setting -> (detector, SweepResult).
+    ``per_class=True``: every class gets the setting that is best for it (``SweepResult.best_per_class(metric)``) and the
+    detector returned is class-wise; ``average`` is then ignored, there is nothing to average."""
     res = det.sweep(track, ref, grid, **kw)
+    if per_class:
+        return det.with_decoder(**res.best_per_class(metric)[1]), res
     _, best, _ = res.best(metric, average)
     return det.with_decoder(**best), res
