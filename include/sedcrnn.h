@@ -144,11 +144,12 @@ int sed_conv3x3_dgrad_bnred(const float* dy, const float* wp_dgrad, float* dx, f
 /* ---- Winograd F(2x2, 3x3) form of the 128-input-channel convolutions (wino.hip; reference sed.py:88,107, the same nn.Conv2d) ----
  * Exact-fp32 MFMA arithmetic on 16 transformed products per 2x2 output tile instead of 36 (2.25x fewer MFMAs); the transforms'
  * coefficients are 0, +-1 and 1/2, the result differs from the direct kernels' by a few ulp of the accumulated magnitude.
- * Shapes: Cin == 128, Cout % 64 == 0, F and T even, a tile-row patch that fits the LDS; sed_conv3x3_wino_rows() = the number of
+ * Shapes: Cin == 128, Cout % 64 == 0, F and T even, a tile-row patch that fits the LDS, a sequence (T x F x Cin floats) below
+ * 2 GiB; sed_conv3x3_wino_rows() = the number of
  * statistic / partial rows ([rows][2][Cout], as sed_conv3x3_fwd) or 0 when the shape is not taken.
  * pack_weights: w [Cout][Cin][3][3] -> uf (forward) and ud (data gradient: flipped taps, channel roles swapped), each
- * sed_conv3x3_wino_packed_floats() floats (16 Cin Cout transformed weights in MFMA fragment order + a zero tail the kernel reads
- * its zero padding from); either may be NULL.
+ * sed_conv3x3_wino_packed_floats() floats (16 Cin Cout transformed weights in MFMA fragment order + a zero tail, part of the layout: the
+ * kernel's zero padding came from it until the patch DMA's range check took that over); either may be NULL.
  * wino_fwd = sed_conv3x3_fwd on channels-last x; wino_dgrad_bnred = sed_conv3x3_dgrad_bnred (same arguments and outputs). */
 int sed_conv3x3_wino_rows(int B, int Cin, int F, int T, int Cout);
 /* measurement only (tools/wino_probe.py): buf = 5 device uint64 — prologue / main loop / epilogue ticks of the 100 MHz clock summed

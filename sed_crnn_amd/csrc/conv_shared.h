@@ -32,7 +32,7 @@ __host__ __device__ inline size_t wino_frag_index(int comp, int k, int n, int K,
 __host__ __device__ inline size_t bf16_eval_frag_index(int tap, int co, int ci, int Cout, int Cin) {
     return (((((size_t)tap * (Cin >> 4) + (ci >> 4)) * (Cout >> 5) + (co >> 5)) * 64) + (co & 31) + 32 * ((ci & 15) >> 3)) * 8 + (ci & 7);
 }
-#define WN_ZTAIL 256        // zero floats behind the packed weights: the source of the patch's zero padding (LDS-DMA cannot write a constant)
+#define WN_ZTAIL 256        // zero floats behind the packed weights (part of the packed layout; wino.hip's patch padding now comes from its buffer descriptor's range check)
 // one thread per (co, ci): U = G g G^T for the forward (g[a][c] = w[co][ci][kh = c][kw = a]: a runs along time, c along mel) and for
 // the data gradient (contraction over co, g'[a][c] = w[co][ci][2 - c][2 - a])
 // gamma / rv (may be NULL): the weights of output channel co are scaled by gamma[co] / sqrt(rv[co] + eps) first (inference: BatchNorm folded)

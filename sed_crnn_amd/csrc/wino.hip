@@ -16,7 +16,7 @@
 // any mel width fills the MFMA rows) x 64 output channels; wave xi holds the four components (xi, 0..3) of 2 x 2 MFMA tiles
 // (32 tiles x 32 channels each): 16 accumulators = 256 registers, ONE wave per SIMD.
 //   * input: the patch of the block's tile rows (2 TR + 2 time rows x F + 2 mel columns x 32 channels per slice) comes in by
-//     LDS-DMA (global_load_lds_dwordx4, no staging registers), double buffered, one barrier per 32-channel slice.  LDS image:
+//     LDS-DMA (buffer_load_dwordx4 ... lds, no staging registers), double buffered, one barrier per 32-channel slice.  LDS image:
 //     8 positions per KiB, quad-major inside ([quad][position]): a wave's DMA covers 8 whole positions (coalesced), a lane's
 //     ds_read_b128 of (position, quad) is conflict-free over consecutive positions, and the k-group g of a step is an
 //     immediate offset.  Mel columns are stored even ones first, so that the tiles of a row are consecutive positions.
@@ -85,6 +85,10 @@ extern "C" int sed_conv3x3_wino_pack_weights_bn_folded(const float* w, const flo
 static bool wino_geo(int B, int Cin, int F, int T, int Cout, WinoGeo* g) {
     if (B <= 0 || Cin != WN_CIN || Cout <= 0 || Cout % 64 != 0 || F < 2 || T < 2 || (F & 1) || (T & 1)) return false;
     if ((size_t)B * T * F * Cin >= ((size_t)1 << 32) || (size_t)T * F * Cout >= ((size_t)1 << 30)) return false;
+    // The patch DMA addresses a sequence through a buffer descriptor: num_records = its byte size (a positive int), lane offsets
+    // are 32-bit byte offsets, and padding lanes carry 0x80000000 (+ at most 384 for the channel slice), which has to lie beyond
+    // every valid offset and must not wrap.  So a sequence stays below 2 GiB: T x F x Cin x 4 < 2^31 (128 channels: T x F < 2^22)
+    if ((size_t)T * F * Cin * sizeof(float) >= ((size_t)1 << 31)) return false;
     g->Tw = T / 2;
     // 64 consecutive tiles of a column group: its tile rows' patch (2 TR + 2 time rows x 2 Fw + 2 mel columns) has to fit WN_NHMAX KiB
     // per wave and 32-channel slice.  Whole rows first (no column halo between workgroups); 128 mel bins: two groups of 32 tiles
@@ -189,12 +193,19 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_k(
     const float sg = wave == 1 ? 1.f : -1.f;
 
     // patch staging (LDS-DMA): item = KiB block k = 4 u + wave, lane = 8 quad + position-in-block.  Every lane of every block issues
-    // (no branch: the loads interleave with the MFMAs); a lane whose position is zero padding, or lies past the patch, reads the
-    // zero tail behind the packed weights instead.
-    const float* hp[NH];
+    // (no branch: the loads interleave with the MFMAs).  The loads go through a buffer descriptor of this workgroup's sequence
+    // (buffer_load_dwordx4 ... lds: wave-uniform base in scalar registers, one 32-bit byte offset per lane and block, the channel
+    // slice as the scalar offset), not through flat pointers: while a global_load_lds is in flight hipcc turns every counted
+    // wait for the weight fragments into vmcnt(0) and the matrix cores sit out the DMA's round trip five times per workgroup;
+    // a buffer load it counts exactly (tests/test_cpu_wino_waits.py).  A lane whose position is zero padding, or lies past the
+    // patch, gets WN_OOB: beyond num_records for every slice (wino_geo keeps a sequence below 2 GiB), so the range check
+    // answers 0 — into LDS too — and the lane can reach no neighbouring row or sequence.  (A select between two offsets, not a
+    // masked or branched load: behind a branch hipcc no longer counts the loads in flight.)
+    constexpr unsigned WN_OOB = 0x80000000u;
+    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)(x + (size_t)b * T * F * CIN), 0, T * F * CIN * 4, 0x00020000);
+    unsigned hp[NH];
     {
         const int Q = lane >> 3, pp = lane & 7;
-        const float* zrow = uq + (size_t)16 * CIN * Cout;
 #pragma unroll
         for (int u = 0; u < NH; ++u) {
             const int P = (u * 4 + wave) * 8 + pp;
@@ -202,13 +213,15 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_k(
             const int ff = cx < H2 ? 2 * cx : 2 * (cx - H2) + 1;
             const int t = 2 * ty0 - 1 + tt, f = fg0 + ff - 1;
             const bool in = P < geo.HR && t >= 0 && t < T && f >= 0 && f < F;
-            hp[u] = in ? x + ((((size_t)b * T + t) * F + f) * CIN + Q * 4) : zrow + Q * 4;
+            hp[u] = in ? (unsigned)((t * F + f) * CIN + Q * 4) * 4u : WN_OOB;
         }
     }
+    auto issue_one = [&](int cc, float* buf, int u) {
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (sed_lptr_t)(buf + (u * 4 + wave) * 256), 16, (int)hp[u], cc * 128, 0, 0);
+    };
     auto issue = [&](int cc, float* buf) {
 #pragma unroll
-        for (int u = 0; u < NH; ++u)
-            __builtin_amdgcn_global_load_lds((sed_gptr_t)(hp[u] + cc * 32), (sed_lptr_t)(buf + (u * 4 + wave) * 256), 16, 0, 0);
+        for (int u = 0; u < NH; ++u) issue_one(cc, buf, u);
     };
     // the first slice is requested before anything else is set up (its latency is the workgroup's prologue: 4.4 us)
     issue(0, smem);
@@ -282,7 +295,8 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_k(
     //   slots 16-47  its 32 transform instructions: per m-tile 8 x  u = d[ra] + sg d[rb]  then 8 x column combinations,
     //   slot 16 nu + 15  the next step's two weight fragments of component nu (its MFMAs of this step have all been issued),
     //   slots 1, 5, 9, ...  one patch DMA each in the first step of a slice
-    //   (measured alternatives, no better: the fragments one per slot at their last use, the DMA in the empty slots 49-62) —
+    //   (measured alternatives, no better: the fragments one per slot at their last use, the DMA in the empty slots 49-62, the DMA
+    //   split 7 + 7 over the first two steps of a slice) —
     // and a scheduling barrier after every slot keeps it that way.
     static_assert(NH <= 16, "the patch DMA of a slice rides in every fourth slot of its first step");
     f32x2 vp[2][2][4][2];
@@ -308,15 +322,11 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_k(
             else v[mt][3][hf] = wn_pk_sub(up[mt][1][hf], up[mt][3][hf]);
         }
     };
-    auto issue_one = [&](int cc, float* buf, int u) {
-        __builtin_amdgcn_global_load_lds((sed_gptr_t)(hp[u] + cc * 32), (sed_lptr_t)(buf + (u * 4 + wave) * 256), 16, 0, 0);
-    };
-
     // Epilogue state.  In the epilogue wave w finishes m-tile w >> 1, channel tile w & 1; lane = (row group rq, channels c4 .. c4+3).
     // BNR: the pooled values (and RG: the arg-max bytes) of this lane's output positions come from a tensor that is streamed once
     // (not L2-resident): requested behind the exchange tiles' parking they cost the workgroup a whole memory round trip with the
     // matrix cores idle.  They ride in the slots of the LAST main-loop step instead, whose slots are otherwise empty and during
-    // which the staging registers (raw, up, the other operand parity, the patch pointers) are dead: a step plus the parking ahead of
+    // which the staging registers (raw, up, the other operand parity, the patch offsets) are dead: a step plus the parking ahead of
     // their first use.  Forward / inference: set up behind the parking, where it always was.
     constexpr int PF = RGC == 2 ? 2 : 4;               // rows in flight (two input channels: 72 tap accumulators leave room for two)
     int rq = 0, c4 = 0, cb = 0;
@@ -351,7 +361,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_k(
 
 #pragma unroll
     for (int nu = 0; nu < 4; ++nu) load_b(nu, 0);
-    __syncthreads();                                   // drains the DMA (vmcnt)
+    __syncthreads();                                   // behind hipcc's counted wait for the 14 DMAs (the 8 fragment loads stay in flight)
 #pragma unroll
     for (int i = 0; i < 16; ++i) slot_read(smem, 0, i);
 #pragma unroll
@@ -381,7 +391,11 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_k(
 #pragma unroll
                 for (int c = 0; c < 4; ++c) { vp[par ^ 1][a][c][0] = vp[par][a][c][0]; vp[par ^ 1][a][c][1] = vp[par][a][c][1]; }
         }
-        if (g == 2 && more) __syncthreads();           // the next slice's patch is complete (DMA drained) and visible
+        // The next slice's patch is complete and visible behind this barrier.  Nothing drains here: vmcnt retires in order, the
+        // slice's DMAs were issued in step (cc, 0) before that step's last weight fragments (slot 63), and hipcc's counted wait
+        // for those fragments in front of MFMA 48 of step (cc, 1) therefore covers every DMA of this wave — a whole step before
+        // any wave arrives here
+        if (g == 2 && more) __syncthreads();
     }
     if (BNR) {
         // the last step: 64 bare MFMAs, and in its slots the epilogue's loads — slots 0-15 (RGC == 2: 0-7) one output position each,
