@@ -464,6 +464,21 @@ size_t sed_logmel_multi_workspace_bytes(int R, int channels);
 int sed_logmel_multi(const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const void* tables,
                      size_t tables_bytes, const float* mu, const float* inv_sigma, float* out, long out_rows, int n_fft, int hop,
                      int n_mels, int pad_mode, void* workspace, size_t workspace_bytes, void* stream);
+/* sed_logmel_gcc: the arguments of sed_logmel_multi plus n_lags -> out [rows][channels*n_mels + P*n_lags], P =
+ * channels*(channels-1)/2.  Columns [c*n_mels, (c+1)*n_mels) are bit for bit what sed_logmel_multi writes for channel c (it is
+ * that launch, with this row stride).  Columns [channels*n_mels + p*n_lags, .. + n_lags) hold the GCC-PHAT of microphone pair p
+ * = (i, j), i < j in lexicographic order, of the same frame: with X_c the 2048-point spectrum of the windowed frame of channel c,
+ * G = X_i conj X_j, Pk = G / |G| (0 where |G|^2 < 1e-30 in fp32: digital silence gives zeros, never NaN),
+ * cc[tau] = (1/2048) (Pk[0] + (-1)^tau Pk[1024] + 2 sum_{k=1..1023} Re(Pk[k] e^{+2 pi i k tau / 2048})) for tau = -n_lags/2 ..
+ * n_lags/2 - 1, in column tau + n_lags/2; values lie in [-1, 1]; channel j = channel i delayed by d samples peaks at tau = -d.
+ * mu/inv_sigma (may both be NULL) are as wide as a row; the GCC columns become (cc - mu)*inv_sigma.  2 <= channels <= 8, n_lags
+ * even and <= 128 (the feature path uses n_lags = n_mels).  Every value is summed in one fixed order that depends on the
+ * frame's samples alone.  Where |G|^2 overflows fp32 (samples of ~1e6 and more) the bin is written as 0 — G / sqrt(inf) for a
+ * finite G — never as inf * 0 = NaN.  workspace: 8-byte aligned, >= sed_logmel_gcc_workspace_bytes(R, channels) (0 = bad sizes). */
+size_t sed_logmel_gcc_workspace_bytes(int R, int channels);
+int sed_logmel_gcc(const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const void* tables,
+                   size_t tables_bytes, const float* mu, const float* inv_sigma, float* out, long out_rows, int n_fft, int hop,
+                   int n_mels, int n_lags, int pad_mode, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ───────────── audio at any sample rate: rational-ratio polyphase resampler, format conversion and downmix ─────────────
  * What the reference does with `ffmpeg -ac 1 -ar 44100` before feature.py:55.  L/M = sr_out/sr_in reduced; taps [L][2 half]

@@ -12,11 +12,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libsedcrnn.so")
-SOURCES = ["api.cpp", "conv.hip", "conv_bf16.hip", "wino.hip", "conv1.hip", "bnpool.hip", "gemm.hip", "gru.hip", "misc.hip", "logmel.hip", "resample.hip", "data.hip", "detect.hip", "tune.hip", "stream.hip", "net.hip"]
+SOURCES = ["api.cpp", "conv.hip", "conv_bf16.hip", "wino.hip", "conv1.hip", "bnpool.hip", "gemm.hip", "gru.hip", "misc.hip", "logmel.hip", "gcc.hip", "resample.hip", "data.hip", "detect.hip", "tune.hip", "stream.hip", "net.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # per-file extras.  logmel: the SLP vectoriser packs the FFT's scalar adds into v_pk_add_f32 and pays for it with ~600
 # v_mov per frame pair to build the register pairs (packed f32 is no faster than scalar on gfx950)
 EXTRA_FLAGS = {"logmel.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"],
+               "gcc.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"],
                "conv.hip": ["-Rpass-analysis=kernel-resource-usage"],
                "wino.hip": ["-Rpass-analysis=kernel-resource-usage"],
                "conv_bf16.hip": ["-Rpass-analysis=kernel-resource-usage"]}
@@ -35,7 +36,9 @@ NO_SCRATCH_KERNELS = {"wino.hip": ("conv3x3_wino_k",),
                       "conv_bf16.hip": ("conv3x3_bf16_eval_k", "gemm_bf16_nt_k"),
                       # log-mel: every instantiation sits a few registers below its waves-per-CU budget (the 12-wave ones at
                       # 163-167 of 168); two more live values in the pair loop spill, and nothing else would say so
-                      "logmel.hip": ("logmel_fft_k",)}
+                      "logmel.hip": ("logmel_fft_k",),
+                      # GCC-PHAT: one wave per SIMD with the FFT's 64 registers live; scratch there would be a silent cliff too
+                      "gcc.hip": ("gcc_phat_k",)}
 
 
 def _hipcc():
@@ -75,7 +78,7 @@ def check_no_spill(remarks, kernels, allow_agprs=False):
 def build(force=False, verbose=False):
     os.makedirs(OBJ, exist_ok=True)
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_shared.h"), os.path.join(CSRC, "detect_shared.h"), os.path.join(HERE, "..", "include", "sedcrnn.h")]
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_shared.h"), os.path.join(CSRC, "detect_shared.h"), os.path.join(CSRC, "fft2048.h"), os.path.join(HERE, "..", "include", "sedcrnn.h")]
     jobs = []
     objs = []
     for src in SOURCES:

@@ -72,6 +72,12 @@ int sed_internal_conv3x3_wgrad_workgroups(int B, int Cin, int F, int T, int Cout
 // it on `stream` then moves in BESIDE that kernel instead of taking its CUs (see sed_net_backward).
 int sed_internal_stream_gate(const unsigned* counter, unsigned target, int timeout_us, void* stream);
 
+// internal (logmel.hip): sed_logmel_multi with the output row stride as an argument (>= channels * n_mels; the scaler stays
+// channels * n_mels wide) — what sed_logmel_gcc (gcc.hip) fills the mel columns of its [rows][C n_mels + P n_lags] matrix with
+int sed_internal_logmel_multi(const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const void* tables,
+                              size_t tables_bytes, const float* mu, const float* inv_sigma, float* out, long out_rows, int n_fft, int hop,
+                              int n_mels, int pad_mode, int row_stride, void* workspace, size_t workspace_bytes, void* stream);
+
 static inline hipStream_t as_stream(void* s) { return (hipStream_t)s; }
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 

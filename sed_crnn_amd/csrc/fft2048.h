@@ -1,0 +1,157 @@
+// fft2048.h — the register-resident 2048-point real FFT that logmel.hip and gcc.hip share: the layout of the constant blob
+// (window, inter-pass and pairing twiddles), complex points in VGPR pairs, the 32-point transform, the half-wave exchange
+// through LDS and the guarded PCM load.  Everything is force-inlined into the kernels that use it.
+#pragma once
+#include "common.h"
+
+#define LM_NFFT 2048
+#define LM_N 1024                     // complex points
+#define LM_TSTRIDE 33                 // floats per row of the 32x32 transpose (conflict-free both ways)
+#define LM_SCR (32 * LM_TSTRIDE)      // 1056 floats >= 1025 power bins
+#define LM_MAX_MELS 128
+#define LM_PART (32 + LM_MAX_MELS)    // partial-sum slots per frame (plan 1: 2 per stored pair + the zero slot)
+#define LM_TRI_BINS 33
+#define LM_FRAME_SCR (LM_SCR + LM_PART)
+#define LM_HDR 8                      // table header words
+
+// table blob (32-bit words):  [0] magic  [1] n_mels  [2] iters  [3] n_slots  [4] total words  [5] plan (0 list, 1 two-band)  [6..7] 0
+//   win  [2048]            window, natural order
+//   tw   [32][32] float2   tw[q][r] = exp(-2 pi i r q / 1024)
+//   pw   [513]   float2    exp(-2 pi i k / 2048), k = 0..512 (+ 1 pad float2)
+//  plan 0 (any sparse bank): band-major list of the non-zeros, 1/32 of it per lane
+//   ent  [iters][32] {float weight*0.25, u32 meta}    meta = k | emit << 11 | slot << 12
+//   band [n_mels] u32      first_slot | count << 16
+//  plan 1 (every bin feeds at most two ADJACENT bands — triangular banks such as librosa's): lane r owns the 33
+//  consecutive bins 33r .. 33r+32, keeps one accumulator for the lower and one for the upper band of the current bin and
+//  stores the pair whenever the band pair changes (iters = 33)
+//   ent  [33][32] {float w_lower*0.25, float w_upper*0.25, u32 pair_slot (float index into part, even) or ~0, 0}
+//   band [n_mels][8] u16   float indices into part of the partial sums of the band (unused = the always-zero slot)
+#define LM_MAGIC 0x4C4D3332u
+#define LM_OFF_WIN LM_HDR
+#define LM_OFF_TW (LM_OFF_WIN + 2048)
+#define LM_OFF_PW (LM_OFF_TW + 2048)
+#define LM_OFF_ENT (LM_OFF_PW + 1028)
+
+namespace {
+
+__device__ __forceinline__ constexpr int brev5(int k) {
+    return ((k & 1) << 4) | ((k & 2) << 2) | (k & 4) | ((k & 8) >> 2) | ((k & 16) >> 4);
+}
+
+// A complex point lives in ONE aligned VGPR pair (re, im): the butterfly's u + v / u - v are one v_pk_add_f32 each and a twiddle
+// multiply (dr C + di S, di C - dr S) = d * (C, C) + swap(d) * (S, -S) is v_pk_mul_f32 + v_pk_fma_f32 — hipcc folds the swap into the
+// instruction's op_sel bits, so there is no register shuffling: 259 vector instructions per 32-point transform instead of 456
+// with separate re[] / im[] arrays (round 2 found the SLP vectoriser's packing of those arrays useless: it paid for every packed
+// add with moves that built the pairs; here the pairs are how the data is loaded — global_load_dwordx2 of (x[2n], x[2n+1])).
+typedef float f2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f2 swp(f2 a) { return __builtin_shufflevector(a, a, 1, 0); }
+// The forms hipcc does not find by itself (it negates and moves halves with v_xor / v_mov instead) are written with the VOP3P
+// modifiers spelled out: op_sel[i] = 1 takes the HIGH half of source i for the low result, op_sel_hi[i] = 0 the LOW half for the
+// high result; neg_lo / neg_hi negate source i for the low / high result.  Plain (non-volatile) asm: free to be scheduled.
+__device__ __forceinline__ f2 cmul(f2 x, f2 w) {               // x * w (complex): (xr wr - xi wi, xr wi + xi wr)
+    f2 t, d;
+    asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(t) : "v"(x), "v"(w));                                   // (xr wr, xi wr)
+    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_lo:[0,1,0]" : "=v"(d) : "v"(x), "v"(w), "v"(t));   // + (-xi wi, xr wi)
+    return d;
+}
+__device__ __forceinline__ f2 sub_rot(f2 a, f2 b) {            // -i (a - b) = (a.y - b.y, b.x - a.x)
+    f2 d;
+    asm("v_pk_add_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[0,0] neg_lo:[0,1] neg_hi:[1,0]" : "=v"(d) : "v"(a), "v"(b));
+    return d;
+}
+__device__ __forceinline__ f2 add_conj(f2 a, f2 b) {           // a + conj(b) = (a.x + b.x, a.y - b.y)
+    f2 d;
+    asm("v_pk_add_f32 %0, %1, %2 neg_hi:[0,1]" : "=v"(d) : "v"(a), "v"(b));
+    return d;
+}
+__device__ __forceinline__ f2 rot_sub_conj(f2 a, f2 b) {       // -i (a - conj(b)) = (a.y + b.y, b.x - a.x)
+    f2 d;
+    asm("v_pk_add_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[0,0] neg_hi:[1,0]" : "=v"(d) : "v"(a), "v"(b));
+    return d;
+}
+
+// 32-point DIF FFT in registers, forward sign; result X[k] = z[brev5(k)].  All indices are compile-time constants.
+__device__ __forceinline__ void fft32(f2 (&z)[32]) {
+    constexpr float C32[16] = {1.0f, 0.98078528040323044913f, 0.92387953251128675613f, 0.83146961230254523708f,
+                               0.70710678118654752440f, 0.55557023301960222474f, 0.38268343236508977173f,
+                               0.19509032201612826785f, 0.0f, -0.19509032201612826785f, -0.38268343236508977173f,
+                               -0.55557023301960222474f, -0.70710678118654752440f, -0.83146961230254523708f,
+                               -0.92387953251128675613f, -0.98078528040323044913f};
+    constexpr float S32[16] = {0.0f, 0.19509032201612826785f, 0.38268343236508977173f, 0.55557023301960222474f,
+                               0.70710678118654752440f, 0.83146961230254523708f, 0.92387953251128675613f,
+                               0.98078528040323044913f, 1.0f, 0.98078528040323044913f, 0.92387953251128675613f,
+                               0.83146961230254523708f, 0.70710678118654752440f, 0.55557023301960222474f,
+                               0.38268343236508977173f, 0.19509032201612826785f};
+#pragma unroll
+    for (int h = 16; h >= 1; h >>= 1) {
+#pragma unroll
+        for (int blk = 0; blk < 32; blk += 2 * h) {
+#pragma unroll
+            for (int j = 0; j < h; ++j) {
+                const int i0 = blk + j, i1 = i0 + h;
+                const int m = j * (16 / h);                 // twiddle W_32^m = C32[m] - i S32[m]
+                const f2 u = z[i0], v = z[i1];
+                z[i0] = u + v;
+                if (m == 0) z[i1] = u - v;
+                else if (m == 8) z[i1] = sub_rot(u, v);      // W_32^8 = -i
+                else { const f2 d = u - v; z[i1] = d * (f2){C32[m], C32[m]} + swp(d) * (f2){S32[m], -S32[m]}; }
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ void wave_lds_fence() {
+    // LDS operations of ONE wave are executed in order by the hardware; this only stops the compiler from moving
+    // them across the point where another lane of the same wave takes over the data
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// Eight rows of the pass-1 -> pass-2 exchange in one statement: ds_write_addtid_b32 stores 4 B per lane at
+// M0 + offset + 4*lane without an address register and at twice the rate of ds_write_b32 (MI355X_MICROARCH.md, LDS).  Row k
+// of the wave's 32 x 65-float exchange buffer starts at byte 260*k (the odd row stride makes the column reads of pass 2
+// conflict-free).  M0 is compiler-reserved: saved and restored inside the statement; the s_nop covers the
+// SALU-writes-M0 -> LDS-add-TID wait state.  No VGPR is written, so the statement needs no completion count of its own
+// (LDS operations of one wave complete in order).
+#define LM_ROW_BYTES 260
+template <int K0>
+__device__ __forceinline__ void addtid_store8(unsigned base, float a0, float a1, float a2, float a3, float a4, float a5,
+                                              float a6, float a7) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %9\n\ts_nop 0\n\t"
+                 "ds_write_addtid_b32 %1 offset:%10\n\tds_write_addtid_b32 %2 offset:%11\n\t"
+                 "ds_write_addtid_b32 %3 offset:%12\n\tds_write_addtid_b32 %4 offset:%13\n\t"
+                 "ds_write_addtid_b32 %5 offset:%14\n\tds_write_addtid_b32 %6 offset:%15\n\t"
+                 "ds_write_addtid_b32 %7 offset:%16\n\tds_write_addtid_b32 %8 offset:%17\n\t"
+                 "s_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(a0), "v"(a1), "v"(a2), "v"(a3), "v"(a4), "v"(a5), "v"(a6), "v"(a7), "s"(base),
+                   "i"((K0 + 0) * LM_ROW_BYTES), "i"((K0 + 1) * LM_ROW_BYTES), "i"((K0 + 2) * LM_ROW_BYTES),
+                   "i"((K0 + 3) * LM_ROW_BYTES), "i"((K0 + 4) * LM_ROW_BYTES), "i"((K0 + 5) * LM_ROW_BYTES),
+                   "i"((K0 + 6) * LM_ROW_BYTES), "i"((K0 + 7) * LM_ROW_BYTES)
+                 : "memory");
+}
+// rows k1 = 0..31 of one component (IMAG = 0: real parts, 1: imaginary parts): row k1 holds X[k1] = z[brev5(k1)] of every lane
+template <int IMAG>
+__device__ __forceinline__ void exchange_store(unsigned base, const f2 (&z)[32]) {
+#define LM_C(k) (IMAG ? z[brev5(k)].y : z[brev5(k)].x)
+    addtid_store8<0>(base, LM_C(0), LM_C(1), LM_C(2), LM_C(3), LM_C(4), LM_C(5), LM_C(6), LM_C(7));
+    addtid_store8<8>(base, LM_C(8), LM_C(9), LM_C(10), LM_C(11), LM_C(12), LM_C(13), LM_C(14), LM_C(15));
+    addtid_store8<16>(base, LM_C(16), LM_C(17), LM_C(18), LM_C(19), LM_C(20), LM_C(21), LM_C(22), LM_C(23));
+    addtid_store8<24>(base, LM_C(24), LM_C(25), LM_C(26), LM_C(27), LM_C(28), LM_C(29), LM_C(30), LM_C(31));
+#undef LM_C
+}
+
+__device__ __forceinline__ float pcm_at(const float* __restrict__ pcm, long n, long n_samples, int pad_mode) {
+    if (n >= 0 && n < n_samples) return pcm[n];
+    if (pad_mode == 1 && n_samples > 1) {                    // numpy 'reflect' (no edge repeat)
+        const long period = 2 * (n_samples - 1);
+        long r = n % period;
+        if (r < 0) r += period;
+        if (r >= n_samples) r = period - r;
+        return pcm[r];
+    }
+    return 0.f;
+}
+
+}  // namespace

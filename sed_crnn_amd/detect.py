@@ -272,12 +272,27 @@ class EventDetector:
     ndarray or 1-D tensor): with any sequence the detector is CLASS-WISE (``det.classwise``; scalars broadcast, ``low=None``
     means low_k = threshold_k) and every decode — single, batched, streamed — runs class k with its own five values
     (DESIGN 5l).  ``mean`` / ``std``: the float64 [C*F] scaler of ``data.standard_scaler_fit`` (one entry per feature column: [F] for a
-    1-channel net), fused into the log-mel front end."""
+    1-channel net), fused into the log-mel front end.  ``spatial="gcc_phat"``: the net reads spatial features — C
+    mel images and one GCC-PHAT image per microphone pair, ``model.in_channels = C + C(C-1)/2`` for C = 2..8 audio channels —
+    and every waveform entry point (``det(wave, sr=, channels=C)``, ``detect_many``, ``stream``) takes ``[N, C]`` PCM and makes
+    them on the device; ``mean`` / ``std`` are ``in_channels * n_mels`` wide."""
 
     def __init__(self, model, seq_len=SEQ_LEN_IN, hop=None, combine="mean", trim=0, threshold=0.5, low=None, median=1,
-                 min_gap=0, min_len=1, mean=None, std=None, sr=feature.SR, hop_length=feature.HOP, max_batch=1024):
+                 min_gap=0, min_len=1, mean=None, std=None, sr=feature.SR, hop_length=feature.HOP, max_batch=1024, spatial=None):
         if not isinstance(model, HipCRNN):
             raise TypeError(f"EventDetector needs a sed_crnn_amd net, got {type(model).__name__}")
+        # spatial features (DESIGN 5m): the net reads C mel images and one GCC-PHAT image per microphone pair of C audio channels
+        self.spatial, self.audio_channels = spatial, model.in_channels
+        if spatial is not None:
+            if spatial not in feature.SPATIAL:
+                raise ValueError(f"spatial must be None or 'gcc_phat', got {spatial!r}")
+            self.audio_channels = feature.audio_channels_of(model.in_channels)
+            if self.audio_channels is None:
+                raise ValueError(f"spatial={spatial!r} needs a net with in_channels = C + C(C-1)/2 for C = 2..{feature.GCC_MAX_CHANNELS} audio "
+                                 f"channels ({', '.join(str(feature.spatial_channels(c)) for c in range(2, feature.GCC_MAX_CHANNELS + 1))}), "
+                                 f"the net has in_channels={model.in_channels}")
+            if model.n_mels % 2:
+                raise ValueError(f"spatial={spatial!r} writes n_mels lags per pair and needs an even count, the net has n_mels={model.n_mels}")
         if combine not in ("mean", "max"):
             raise ValueError(f"combine must be 'mean' or 'max', got {combine!r}")
         K = model.dense[-1]
@@ -302,6 +317,10 @@ class EventDetector:
         self.std = None if std is None else torch.as_tensor(std, dtype=torch.float64)
         if self.mean is not None and model.in_channels > 1:
             CF = model.in_channels * model.n_mels
+            if (self.mean.numel() != CF or self.std.numel() != CF) and spatial is not None:
+                raise ValueError(f"spatial={spatial!r}: a net with in_channels={model.in_channels} ({self.audio_channels} audio channels) and "
+                                 f"{model.n_mels} mel bands needs mean / std of width (C+P)*n_mels = {model.in_channels}*{model.n_mels} = "
+                                 f"{CF}, got {self.mean.numel()} / {self.std.numel()}")
             if self.mean.numel() != CF or self.std.numel() != CF:
                 raise ValueError(f"a {model.in_channels}-channel net with {model.n_mels} mel bands needs mean / std of width "
                                  f"{model.in_channels}*{model.n_mels} = {CF} (data.standard_scaler_fit on [N, C*F] features), got "
@@ -365,7 +384,8 @@ class EventDetector:
             kw["low"] = None
         kw.update(settings)
         return EventDetector(self.model, seq_len=self.seq_len, hop=self.hop, combine=self.combine, trim=self.trim, mean=self.mean,
-                             std=self.std, sr=self.sr, hop_length=self.hop_length, max_batch=self.max_batch, **kw)
+                             std=self.std, sr=self.sr, hop_length=self.hop_length, max_batch=self.max_batch, spatial=self.spatial,
+                             **kw)
 
     def sweep(self, track, ref, grid, collar=1, offset_collar=None, offset_percent=None, block=None, max_workspace_bytes=1 << 30):
         """Score every decoder setting of ``grid`` (a ``DecoderGrid``) on a track against ``ref`` (a ``ReferenceEvents``) on
@@ -408,7 +428,7 @@ class EventDetector:
             dev = self.model.flat_parameters().device
             with torch.no_grad():
                 mel = feature.mbe(waveform, sr=self.sr, hop=self.hop_length, n_mels=self.model.n_mels, mean=self.mean, std=self.std,
-                                  input_sr=sr, channels=channels, keep_channels=True, device=dev)
+                                  input_sr=sr, channels=channels, keep_channels=True, device=dev, spatial=self.spatial)
             return self.from_features(mel)
         self._check_model()
         if feature._needs_front_end(waveform, sr, self.sr, channels):
@@ -425,7 +445,11 @@ class EventDetector:
 
     def _check_channels(self, channels):
         """a multichannel net takes exactly its own channel count: no mix-down, no duplication of a mono signal"""
-        C_in = self.model.in_channels
+        C_in = self.audio_channels
+        if self.spatial is not None and int(channels) != C_in:
+            raise ValueError(f"spatial={self.spatial!r}: a net with in_channels={self.model.in_channels} reads {C_in} audio channels "
+                             f"({C_in} mel images + {C_in * (C_in - 1) // 2} microphone pairs) and takes [N, {C_in}] interleaved PCM "
+                             f"with channels={C_in}, got channels={int(channels)}")
         if int(channels) != C_in:
             raise ValueError(f"a {C_in}-channel net takes [N, {C_in}] interleaved PCM with channels={C_in}, got channels={int(channels)}: "
                              f"there is no mix-down to fewer channels and no duplication of a mono signal (scaled features go "
@@ -582,7 +606,7 @@ class EventDetector:
         with torch.no_grad():
             mel, _ = feature.mbe_many(waves, sr=self.sr, hop=self.hop_length, n_mels=m.n_mels, mean=self.mean, std=self.std,
                                       device=dev, **(dict(input_sr=rates, channels=channels) if front else {}),
-                                      **(dict(keep_channels=True) if multi else {}))
+                                      **(dict(keep_channels=True, spatial=self.spatial) if multi else {}))
             return self._detect_packed(mel, bp)
 
     def from_features_many(self, mels):

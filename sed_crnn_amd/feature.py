@@ -110,18 +110,52 @@ def _needs_front_end(w, input_sr, sr, channels):
     return (input_sr is not None and int(input_sr) != int(sr)) or not is_plain(w, channels)
 
 
+SPATIAL = ("gcc_phat",)
+GCC_MAX_CHANNELS = 8      # gcc.hip: GC_MAX_CH
+
+
+def spatial_channels(channels):
+    """input channels of a net that reads the spatial features of ``channels`` audio channels: the C mel images and one
+    GCC-PHAT image per microphone pair, C + C(C-1)/2 (2 -> 3, 3 -> 6, 4 -> 10)"""
+    c = int(channels)
+    return c + c * (c - 1) // 2
+
+
+def audio_channels_of(in_channels):
+    """the audio channel count C in 2..8 with ``spatial_channels(C) == in_channels``, or None"""
+    return next((c for c in range(2, GCC_MAX_CHANNELS + 1) if spatial_channels(c) == int(in_channels)), None)
+
+
+def _check_spatial(spatial, keep_channels, channels, n_mels=None):
+    if spatial is None:
+        return
+    if spatial not in SPATIAL:
+        raise ValueError(f"spatial must be None or 'gcc_phat', got {spatial!r}")
+    if not keep_channels:
+        raise ValueError("spatial='gcc_phat' needs keep_channels=True: the cross-correlations are taken between the channels "
+                         "that a mix-down would remove")
+    if not 2 <= int(channels) <= GCC_MAX_CHANNELS:
+        raise ValueError(f"spatial='gcc_phat' needs 2 to {GCC_MAX_CHANNELS} audio channels (one image per microphone pair), got "
+                         f"channels={int(channels)}")
+    if n_mels is not None and n_mels % 2:
+        raise ValueError(f"spatial='gcc_phat' writes n_lags = n_mels lags per pair and needs an even count, got n_mels={n_mels}")
+
+
 def mbe(y, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, pad_mode="constant", mean=None, std=None, tables=None, input_sr=None,
-        channels=1, keep_channels=False, device=None):
+        channels=1, keep_channels=False, device=None, spatial=None):
     """y: mono float32 PCM CUDA tensor [N] -> [1 + N//hop, n_mels] log-mel energies (natural log, no eps).
     ``tables`` = build_tables(window, melfb, device) replaces librosa's default window / filterbank.
     ``input_sr`` / ``channels``: y is at that rate (default: ``sr``), int16 or float, ``[N, channels]`` interleaved when
     channels > 1 (host or device), and is converted, downmixed and resampled to ``sr`` on the device first (resample.py).
     ``keep_channels=True``: the channels are kept, not mixed -> ``[1 + N'//hop, channels*n_mels]``, channel c in columns
     ``[c*n_mels, (c+1)*n_mels)`` (the layout the nets read), each bit for bit ``mbe(y[:, c])``; ``mean`` / ``std`` are then
-    ``channels*n_mels`` wide.  ``device``: where a host clip that goes through resample.py is put."""
+    ``channels*n_mels`` wide.  ``device``: where a host clip that goes through resample.py is put.
+    ``spatial="gcc_phat"`` (with ``keep_channels=True``, 2..8 channels): one GCC-PHAT image per microphone pair
+    behind the mel images -> ``[.., (C+P)*n_mels]``, P = C(C-1)/2; ``mean`` / ``std`` are then that wide."""
+    _check_spatial(spatial, keep_channels, channels)
     if keep_channels:
         return mbe_many([y], sr=sr, n_fft=n_fft, hop=hop, n_mels=n_mels, pad_mode=pad_mode, mean=mean, std=std, tables=tables,
-                        device=device, input_sr=input_sr, channels=channels, keep_channels=True)[0]
+                        device=device, input_sr=input_sr, channels=channels, keep_channels=True, spatial=spatial)[0]
     if _needs_front_end(y, input_sr, sr, channels):
         from .resample import resample
         y = resample(y, sr if input_sr is None else input_sr, sr, channels, device)
@@ -176,14 +210,19 @@ def mbe_packed(pcm, clips, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, pad_mode="
 
 
 def mbe_planar(pcm, clips, channels, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, pad_mode="constant", mean=None, std=None,
-               tables=None):
+               tables=None, spatial=None):
     """The multichannel twin of ``mbe_packed``: R recordings of ``channels`` planar channels each, all in ONE mono float32 CUDA
     buffer ``pcm``; ``clips`` = [(first sample, n_samples >= 1), ...] has ``R * channels`` entries, recording r, channel c at
     ``r * channels + c`` (what ``resample_many(..., keep_channels=True)`` returns), the channels of a recording equally long
     -> (features [sum_r (1 + n_r//hop), channels*n_mels], row offsets [R+1] as a host list), in one launch
     (``sed_logmel_multi``).  Columns ``[c*n_mels, (c+1)*n_mels)`` are bit for bit ``mbe`` of channel c with that slice of
-    ``mean`` / ``std`` (``channels*n_mels`` wide: ``data.standard_scaler_fit`` on such features)."""
+    ``mean`` / ``std`` (``channels*n_mels`` wide: ``data.standard_scaler_fit`` on such features).
+    ``spatial="gcc_phat"`` (2..8 channels, even ``n_mels``; ``sed_logmel_gcc``): the P = C(C-1)/2 microphone pairs
+    (i, j), i < j in lexicographic order, follow as columns ``[(C+p)*n_mels, (C+p+1)*n_mels)``: the GCC-PHAT of the frame at
+    lags -n_mels/2 .. n_mels/2 - 1 (channel j = channel i delayed by d samples peaks at column n_mels/2 - d); the mel columns
+    are bit for bit those without ``spatial``, and ``mean`` / ``std`` are ``(C+P)*n_mels`` wide."""
     import ctypes as C
+    _check_spatial(spatial, True, channels)
     if not (isinstance(pcm, torch.Tensor) and pcm.is_cuda and pcm.dim() == 1):
         raise RuntimeError("sed_crnn_amd.feature.mbe_planar needs a 1-D CUDA(HIP) PCM buffer; there is no CPU fallback")
     if pad_mode not in ("constant", "reflect"):
@@ -205,17 +244,29 @@ def mbe_planar(pcm, clips, channels, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, 
         tables = _tables(pcm.device.index or 0, sr, n_fft, n_mels)
     else:
         n_mels = _validated_mels(tables)
+    _check_spatial(spatial, True, nc, n_mels)
+    width = (spatial_channels(nc) if spatial else nc) * n_mels
     if R == 0:
-        return torch.empty(0, nc * n_mels, device=pcm.device), [0]
+        return torch.empty(0, width, device=pcm.device), [0]
     rows = np.concatenate([[0], np.cumsum(1 + table[::nc, 1] // hop)]).tolist()
     if rows[-1] >= 2 ** 31:
         raise ValueError(f"{rows[-1]} feature frames in one batch: at most 2^31 - 1")
-    if mean is not None and (mean.numel() != nc * n_mels or std.numel() != nc * n_mels):
+    if mean is not None and (mean.numel() != width or std.numel() != width):
+        if spatial:
+            raise ValueError(f"mean / std must have (C+P)*n_mels = ({nc}+{nc * (nc - 1) // 2})*{n_mels} = {width} entries with "
+                             f"spatial={spatial!r} (the {nc} mel images, then one GCC image per microphone pair), got "
+                             f"{mean.numel()} / {std.numel()}")
         raise ValueError(f"mean / std must have {nc}*{n_mels} = {nc * n_mels} entries (channel c, band m at c*{n_mels} + m), got "
                          f"{mean.numel()} / {std.numel()}")
-    out = torch.empty(rows[-1], nc * n_mels, device=pcm.device)
+    out = torch.empty(rows[-1], width, device=pcm.device)
     pcm = pcm.contiguous().float()
     mean, inv = _scaler(mean, std, pcm.device)
+    if spatial:
+        ws = torch.empty(lib().sed_logmel_gcc_workspace_bytes(R, nc), dtype=torch.uint8, device=pcm.device)
+        check(lib().sed_logmel_gcc(ptr(pcm), pcm.numel(), C.c_void_p(table.ctypes.data), R, nc, ptr(tables), tables.numel() * 4,
+                                   ptr(mean), ptr(inv), ptr(out), rows[-1], n_fft, hop, n_mels, n_mels,
+                                   {"constant": 0, "reflect": 1}[pad_mode], ptr(ws), ws.numel(), stream_ptr()), "sed_logmel_gcc")
+        return out, rows
     ws = torch.empty(lib().sed_logmel_multi_workspace_bytes(R, nc), dtype=torch.uint8, device=pcm.device)
     check(lib().sed_logmel_multi(ptr(pcm), pcm.numel(), C.c_void_p(table.ctypes.data), R, nc, ptr(tables), tables.numel() * 4,
                                  ptr(mean), ptr(inv), ptr(out), rows[-1], n_fft, hop, n_mels,
@@ -246,13 +297,15 @@ def pack_clips(waves, device):
 
 
 def mbe_many(waves, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, pad_mode="constant", mean=None, std=None, tables=None,
-             device=None, input_sr=None, channels=1, keep_channels=False):
+             device=None, input_sr=None, channels=1, keep_channels=False, spatial=None):
     """``mbe`` of every clip in a list of 1-D clips (host or device; ``device`` defaults to the first CUDA clip's, else
     cuda:current) in one launch -> (features [sum_r (1 + n_r//hop), n_mels] in clip order, row offsets [R+1] host list).
     Bit for bit ``torch.cat([mbe(w) for w in waves])``.  ``input_sr`` (one rate, or one per clip) / ``channels``: as in
     ``mbe``; the clips are resampled straight into the packed buffer the log-mel launch reads (``resample.resample_many``).
     ``keep_channels=True``: every clip is ``[N, channels]`` and its channels are kept -> features ``[.., channels*n_mels]``
-    (``mbe_planar``; the resampler writes the planar channels of every clip straight into the buffer that launch reads)."""
+    (``mbe_planar``; the resampler writes the planar channels of every clip straight into the buffer that launch reads).
+    ``spatial="gcc_phat"``: as in ``mbe_planar`` — bit for bit the per-recording calls."""
+    _check_spatial(spatial, keep_channels, channels)
     waves = list(waves)
     if device is None:
         device = next((w.device for w in waves if isinstance(w, torch.Tensor) and w.is_cuda), None)
@@ -264,7 +317,7 @@ def mbe_many(waves, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, pad_mode="constan
                 raise ValueError(f"clip {i} is empty")
         pcm, clips = resample_many(waves, sr if input_sr is None else input_sr, sr, channels, device, keep_channels=True)
         return mbe_planar(pcm, clips, channels, sr=sr, n_fft=n_fft, hop=hop, n_mels=n_mels, pad_mode=pad_mode, mean=mean, std=std,
-                          tables=tables)
+                          tables=tables, spatial=spatial)
     if input_sr is not None and np.ndim(input_sr) > 0 or any(_needs_front_end(w, input_sr, sr, channels) for w in waves):
         from .resample import resample_many
         pcm, clips = resample_many(waves, sr if input_sr is None else input_sr, sr, channels, device)

@@ -32,6 +32,8 @@ A net with ``in_channels = C > 1`` takes ``[n, C]`` interleaved piec
 one-tap copy filter at the detector's own rate) and emits C planar lanes per feed; lane ``s*C + c`` has its own resampler
 carry and its own log-mel PCM carry on the device, while the host counters stay per feed (the channels of a feed advance in
 lockstep), and a round's features come out of ``sed_logmel_multi`` as ``[rows, C*F]``, which is what the feature rows hold.
+A spatial detector (``EventDetector(..., spatial="gcc_phat")``) keeps the same C lanes per feed and calls
+``sed_logmel_gcc`` instead: ``[rows, (C+P)*F]`` with one GCC-PHAT block per microphone pair, and no further state.
 """
 import ctypes as C
 
@@ -167,7 +169,8 @@ class StreamDetector:
         S = int(n_streams)
         if not 1 <= S <= 65535 or not 1 <= int(max_new_windows) <= 1024:
             raise ValueError(f"need 1 <= n_streams <= 65535 and 1 <= max_new_windows <= 1024, got {n_streams}, {max_new_windows}")
-        self.C = m.in_channels                                             # planar lanes per feed: lane s*C + c
+        # planar lanes per feed: lane s*C + c; a spatial detector's net reads C + C(C-1)/2 images of C audio channels
+        self.C = det.audio_channels
         input_channels = self.C if input_channels is None else int(input_channels)
         if self.C > 1 and input_channels != self.C:
             raise ValueError(f"a {self.C}-channel net takes [n, {self.C}] interleaved pieces: input_channels must be {self.C}, got "
@@ -287,12 +290,19 @@ class StreamDetector:
             m = det.model
             tables = feature._tables(dev.index or 0, det.sr, feature.NFFT, m.n_mels)
             mean, inv = feature._scaler(det.mean, det.std, dev)
-            need = lib().sed_logmel_batch_workspace_bytes(S) if NC == 1 else lib().sed_logmel_multi_workspace_bytes(S, NC)
+            need = (lib().sed_logmel_batch_workspace_bytes(S) if NC == 1 else lib().sed_logmel_gcc_workspace_bytes(S, NC) if det.spatial
+                    else lib().sed_logmel_multi_workspace_bytes(S, NC))
             ws = torch.empty(need, dtype=torch.uint8, device=dev)
             self._lm = (tables, mean, inv, ws)
         tables, mean, inv, ws = self._lm
         ct = np.ascontiguousarray(np.stack([work_at[lane(clip)], total_l[lane(clip)]], 1))
-        out = torch.empty(n_rows, NC * det.model.n_mels, device=dev)
+        out = torch.empty(n_rows, self.CF, device=dev)
+        if det.spatial:                                                     # the C lanes of a feed -> C mel blocks and one GCC-PHAT block per
+            _timed(self.marks, "logmel", lambda: check(lib().sed_logmel_gcc(   # pair: a frame's GCC needs that frame's samples only
+                ptr(work), work.numel(), C.c_void_p(ct.ctypes.data), ct.shape[0] // NC, NC, ptr(tables), tables.numel() * 4, ptr(mean),
+                ptr(inv), ptr(out), n_rows, feature.NFFT, h, det.model.n_mels, det.model.n_mels, 0, ptr(ws), ws.numel(), stream_ptr()),
+                "sed_logmel_gcc"))
+            return out, row0, rows
         if NC > 1:                                                          # the C lanes of a feed -> its rows' C column blocks
             _timed(self.marks, "logmel", lambda: check(lib().sed_logmel_multi(
                 ptr(work), work.numel(), C.c_void_p(ct.ctypes.data), ct.shape[0] // NC, NC, ptr(tables), tables.numel() * 4, ptr(mean),
@@ -545,7 +555,7 @@ class StreamDetector:
             x = torch.as_tensor(x)
             if x.dim() != 2 or x.shape[1] != self.CF:
                 m = self.det.model
-                raise ValueError(f"stream {s}: expected features [N, {self.CF}] (C*F = {m.in_channels}*{m.n_mels}), got {tuple(x.shape)}")
+                raise ValueError(f"stream {s}: expected features [N, {self.CF}] (in_channels*n_mels = {m.in_channels}*{m.n_mels}), got {tuple(x.shape)}")
             return x
         pieces, lens = self._pieces(mels, "feature pieces", one)
         dev = self._ready()
