@@ -480,6 +480,26 @@ int sed_logmel_gcc(const float* pcm, long pcm_len, const long* clips_host, int R
                    size_t tables_bytes, const float* mu, const float* inv_sigma, float* out, long out_rows, int n_fft, int hop,
                    int n_mels, int n_lags, int pad_mode, void* workspace, size_t workspace_bytes, void* stream);
 
+/* sed_pcen: per-channel energy normalisation, IN PLACE, of the columns [col0, col0 + W) of x [rows][stride], which
+ * hold log-mel values (natural log, as sed_logmel* write them without a scaler); the other columns are not touched.  Every column
+ * of a recording is one chain: E[t] = scale * exp(x[t]); M[t] = (1 - smooth_b) M[t-1] + smooth_b E[t] with M[0] = E[0] (librosa's
+ * lfilter_zi start); pcen[t] = (E[t] (eps + M[t])^-gain + bias)^power - bias^power; with a scaler (mu / inv_sigma: both NULL, or
+ * both W wide, entry c for column col0 + c) the value written is (pcen - mu) * inv_sigma.  x = -inf (E = 0) gives pcen = 0, never NaN.
+ * recs_host [R][3] = {first row, n rows, absolute index of the first frame}: a HOST table, validated on the host before anything
+ * is enqueued; the recordings lie inside the matrix, are disjoint and in increasing order; n rows may be 0 (nothing is read or
+ * written for it).  state: a device buffer of R*W chains x 2 floats (recording r, column c at 2 (r W + c)), or NULL when every
+ * recording starts at frame 0.  It is read for a recording whose absolute index is > 0, IGNORED for index 0 (a feed that restarts
+ * needs no reset call) and written back after the call, so that the next call continues with index + n rows.  The fp32
+ * operations behind M[t] depend on the absolute frame t and on the data only (blocks of 64 frames aligned to t; pcen.hip): a
+ * recording processed in pieces of any sizes gives bit for bit the rows of one call.  smooth_b in (0, 1] (the powers of
+ * 1 - smooth_b that the kernels use are taken in double here); gain > 0, bias >= 0, power > 0, eps > 0, scale > 0.  workspace:
+ * 8-byte aligned, >= sed_pcen_workspace_bytes(rows, R, W) (0 = bad sizes: rows < 2^31, R <= 2^24, 1 <= W <= 65536).  Three plain
+ * launches; no workgroup waits on another. */
+size_t sed_pcen_workspace_bytes(long rows, int R, int W);
+int sed_pcen(float* x, long rows, int stride, int col0, int W, const long* recs_host, int R, float* state, double smooth_b,
+             float gain, float bias, float power, float eps, float scale, const float* mu, const float* inv_sigma,
+             void* workspace, size_t workspace_bytes, void* stream);
+
 /* ───────────── audio at any sample rate: rational-ratio polyphase resampler, format conversion and downmix ─────────────
  * What the reference does with `ffmpeg -ac 1 -ar 44100` before feature.py:55.  L/M = sr_out/sr_in reduced; taps [L][2 half]
  * (device float32, built by the caller in double: sed_crnn_amd/resample.py) weight, for output m of a clip (ABSOLUTE index,

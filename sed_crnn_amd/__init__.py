@@ -9,6 +9,7 @@ from . import metrics  # noqa: F401
 from ._lib import LIB_PATH, SedHipError, lib  # noqa: F401
 from .detect import (BatchDetectionResult, BatchPlan, DetectionResult, EventDetector, detect_events,  # noqa: F401
                      detect_events_many, plan_batch, plan_windows)
+from .feature import PCEN  # noqa: F401
 from .fit import EpochTally, fit, fit_folds, run_epoch, run_epoch_device  # noqa: F401
 from .lightning import CRNNLightning, fit_lightning  # noqa: F401
 from .losses import BCEWithLogitsLoss, FocalBCELoss  # noqa: F401

@@ -142,6 +142,8 @@ SIGNATURES = {
     "sed_logmel_multi": (_i, [_fp, _l, _fp, _i, _i, _fp, _sz, _fp, _fp, _fp, _l, _i, _i, _i, _i, _fp, _sz, _stream]),
     "sed_logmel_gcc_workspace_bytes": (_sz, [_i, _i]),
     "sed_logmel_gcc": (_i, [_fp, _l, _fp, _i, _i, _fp, _sz, _fp, _fp, _fp, _l, _i, _i, _i, _i, _i, _fp, _sz, _stream]),
+    "sed_pcen_workspace_bytes": (_sz, [_l, _i, _i]),
+    "sed_pcen": (_i, [_fp, _l, _i, _i, _i, _fp, _i, _fp, _d, _f, _f, _f, _f, _f, _fp, _fp, _fp, _sz, _stream]),
     "sed_resample_workspace_bytes": (_sz, [_i]),
     "sed_resample_check_table": (_i, [_fp, _i, _l, _l, _l, _i, _i, _i]),
     "sed_resample": (_i, [_fp, _l, _i, _i, _fp, _l, _fp, _l, _i, _i, _i, _fp, _i, _fp, _l, _fp, _sz, _stream]),

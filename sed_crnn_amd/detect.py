@@ -275,12 +275,18 @@ class EventDetector:
     1-channel net), fused into the log-mel front end.  ``spatial="gcc_phat"``: the net reads spatial features — C
     mel images and one GCC-PHAT image per microphone pair, ``model.in_channels = C + C(C-1)/2`` for C = 2..8 audio channels —
     and every waveform entry point (``det(wave, sr=, channels=C)``, ``detect_many``, ``stream``) takes ``[N, C]`` PCM and makes
-    them on the device; ``mean`` / ``std`` are ``in_channels * n_mels`` wide."""
+    them on the device; ``mean`` / ``std`` are ``in_channels * n_mels`` wide.  ``compress=sed.PCEN(...)``: the net
+    was trained on PCEN features — every waveform entry point (``det(...)``, ``detect_many``, ``stream``) makes the mel columns
+    with ``feature.mbe(..., compress=)`` and ``mean`` / ``std`` are the scaler of such features; ``from_features*`` and
+    ``push_features`` take finished features and apply nothing."""
 
     def __init__(self, model, seq_len=SEQ_LEN_IN, hop=None, combine="mean", trim=0, threshold=0.5, low=None, median=1,
-                 min_gap=0, min_len=1, mean=None, std=None, sr=feature.SR, hop_length=feature.HOP, max_batch=1024, spatial=None):
+                 min_gap=0, min_len=1, mean=None, std=None, sr=feature.SR, hop_length=feature.HOP, max_batch=1024, spatial=None,
+                 compress=None):
         if not isinstance(model, HipCRNN):
             raise TypeError(f"EventDetector needs a sed_crnn_amd net, got {type(model).__name__}")
+        feature._check_compress(compress)
+        self.compress = compress                # PCEN instead of the log on the mel columns of every waveform entry point (DESIGN 5n)
         # spatial features (DESIGN 5m): the net reads C mel images and one GCC-PHAT image per microphone pair of C audio channels
         self.spatial, self.audio_channels = spatial, model.in_channels
         if spatial is not None:
@@ -385,7 +391,7 @@ class EventDetector:
         kw.update(settings)
         return EventDetector(self.model, seq_len=self.seq_len, hop=self.hop, combine=self.combine, trim=self.trim, mean=self.mean,
                              std=self.std, sr=self.sr, hop_length=self.hop_length, max_batch=self.max_batch, spatial=self.spatial,
-                             **kw)
+                             compress=self.compress, **kw)
 
     def sweep(self, track, ref, grid, collar=1, offset_collar=None, offset_percent=None, block=None, max_workspace_bytes=1 << 30):
         """Score every decoder setting of ``grid`` (a ``DecoderGrid``) on a track against ``ref`` (a ``ReferenceEvents``) on
@@ -428,7 +434,8 @@ class EventDetector:
             dev = self.model.flat_parameters().device
             with torch.no_grad():
                 mel = feature.mbe(waveform, sr=self.sr, hop=self.hop_length, n_mels=self.model.n_mels, mean=self.mean, std=self.std,
-                                  input_sr=sr, channels=channels, keep_channels=True, device=dev, spatial=self.spatial)
+                                  input_sr=sr, channels=channels, keep_channels=True, device=dev, spatial=self.spatial,
+                                  compress=self.compress)
             return self.from_features(mel)
         self._check_model()
         if feature._needs_front_end(waveform, sr, self.sr, channels):
@@ -440,7 +447,7 @@ class EventDetector:
         dev = self.model.flat_parameters().device
         with torch.no_grad():
             mel = feature.mbe(y.to(dev, torch.float32), sr=self.sr, hop=self.hop_length, n_mels=self.model.n_mels,
-                              mean=self.mean, std=self.std)
+                              mean=self.mean, std=self.std, compress=self.compress)
         return self.from_features(mel)
 
     def _check_channels(self, channels):
@@ -605,7 +612,7 @@ class EventDetector:
         dev = m.flat_parameters().device
         with torch.no_grad():
             mel, _ = feature.mbe_many(waves, sr=self.sr, hop=self.hop_length, n_mels=m.n_mels, mean=self.mean, std=self.std,
-                                      device=dev, **(dict(input_sr=rates, channels=channels) if front else {}),
+                                      device=dev, compress=self.compress, **(dict(input_sr=rates, channels=channels) if front else {}),
                                       **(dict(keep_channels=True, spatial=self.spatial) if multi else {}))
             return self._detect_packed(mel, bp)
 

@@ -6,6 +6,7 @@ edge padding from 'reflect' to 'constant' in 0.10, so ``pad_mode`` is explicit. 
 (window, FFT twiddles, mel basis) are computed once on the host in float64 and cached per device.
 feature.py:127-129's StandardScaler can be fused in through ``mean``/``std``.
 """
+import dataclasses
 import functools
 
 import numpy as np
@@ -141,8 +142,127 @@ def _check_spatial(spatial, keep_channels, channels, n_mels=None):
         raise ValueError(f"spatial='gcc_phat' writes n_lags = n_mels lags per pair and needs an even count, got n_mels={n_mels}")
 
 
+PCEN_BLOCK = 64          # pcen.hip: PC_L, the frames per block of the smoother (aligned to the absolute frame index)
+
+
+@dataclasses.dataclass(frozen=True)
+class PCEN:
+    """Per-channel energy normalisation (librosa.pcen's definition with max_size = 1) of the mel energies
+    ``E = scale * exp(log-mel)``: ``M[t] = (1 - b) M[t-1] + b E[t]``, ``M[0] = E[0]``;
+    ``pcen = (E (eps + M)^-gain + bias)^power - bias^power``.  ``time_constant`` in seconds sets b (``smoothing``).
+    ``compress=PCEN(...)`` on ``feature.mbe*`` and on ``EventDetector`` replaces the log compression by it."""
+    gain: float = 0.98
+    bias: float = 2.0
+    power: float = 0.5
+    time_constant: float = 0.4
+    eps: float = 1e-6
+    scale: float = 1.0
+
+    def __post_init__(self):
+        for name in ("gain", "bias", "power", "time_constant", "eps", "scale"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+                raise ValueError(f"PCEN: {name} must be a finite number, got {v!r}")
+            object.__setattr__(self, name, float(v))
+        if not self.gain > 0 or not self.power > 0 or not self.eps > 0 or not self.time_constant > 0 or not self.scale > 0:
+            raise ValueError(f"PCEN needs gain > 0, power > 0, eps > 0, time_constant > 0 and scale > 0, got gain={self.gain}, "
+                             f"power={self.power}, eps={self.eps}, time_constant={self.time_constant}, scale={self.scale}")
+        if self.bias < 0:
+            raise ValueError(f"PCEN needs bias >= 0, got {self.bias}")
+
+    def smoothing(self, sr=SR, hop=HOP):
+        """b of the smoother for frames ``hop`` samples apart at rate ``sr`` (librosa's: T = time_constant * sr / hop frames,
+        b = (sqrt(1 + 4 T^2) - 1) / (2 T^2)); 0.056389 for the defaults"""
+        if not sr > 0 or not hop > 0:
+            raise ValueError(f"PCEN.smoothing needs sr > 0 and hop > 0, got {sr}, {hop}")
+        t = self.time_constant * float(sr) / float(hop)
+        return float((np.sqrt(1.0 + 4.0 * t * t) - 1.0) / (2.0 * t * t))
+
+
+def _check_compress(compress):
+    if compress is not None and not isinstance(compress, PCEN):
+        raise TypeError(f"compress must be None or a PCEN(...) settings object, got {type(compress).__name__}")
+
+
+def _pcen_launch(x, settings, b, recs, col0, width, mean32, inv32, state, ws=None):
+    """``sed_pcen`` in place on the columns [col0, col0 + width) of the device matrix ``x``; ``recs`` [R, 3] int64 host rows
+    (first row, n rows, absolute index of the first frame); ``mean32`` / ``inv32``: ``_scaler``'s pair, ``width`` wide, or None"""
+    import ctypes as C
+    recs = np.ascontiguousarray(np.asarray(recs, dtype=np.int64).reshape(-1, 3))
+    R = recs.shape[0]
+    need = lib().sed_pcen_workspace_bytes(x.shape[0], R, width)
+    if need == 0:
+        raise ValueError(f"sed_pcen takes fewer than 2^31 rows, at most 2^24 recordings and 1..65536 columns, got {x.shape[0]} rows, "
+                         f"{R} recordings, {width} columns")
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    check(lib().sed_pcen(ptr(x), x.shape[0], x.stride(0), col0, width, C.c_void_p(recs.ctypes.data), R, ptr(state), b,
+                         settings.gain, settings.bias, settings.power, settings.eps, settings.scale, ptr(mean32), ptr(inv32),
+                         ptr(ws), ws.numel(), stream_ptr()), "sed_pcen")
+    return ws
+
+
+def _rows_table(rows, n, start=None):
+    """row offsets [R+1] (what ``mbe_many`` returns; None: one recording of all n rows) and absolute start indices -> recs [R, 3]"""
+    off = np.asarray([0, n] if rows is None else rows, dtype=np.int64).reshape(-1)
+    if off.size < 1 or off[0] < 0 or (np.diff(off) < 0).any() or off[-1] > n:
+        raise ValueError(f"rows must be non-decreasing row offsets inside the {n} rows of the features, got {off.tolist()}")
+    R = off.size - 1
+    t0 = np.zeros(R, np.int64) if start is None else np.asarray(start, dtype=np.int64).reshape(-1)
+    if t0.size != R or (t0 < 0).any():
+        raise ValueError(f"start must hold one absolute frame index >= 0 per recording ({R}), got {t0.tolist()}")
+    return np.stack([off[:-1], np.diff(off), t0], 1)
+
+
+def pcen(logmel, settings=PCEN(), sr=SR, hop=HOP, rows=None, mean=None, std=None, columns=None, state=None, start=None):
+    """PCEN of log-mel features that are already on the device (``mbe`` / ``mbe_many`` without a scaler, or stored features):
+    ``logmel`` [N, width] float32 CUDA -> a new tensor of the same shape (``sed_pcen``).  ``rows``: the row offsets
+    [R+1] that ``mbe_many`` returns — every recording starts its own smoother; default: one recording.  ``mean`` / ``std``:
+    the StandardScaler (fitted on PCEN features) of the processed columns, fused in.  ``columns`` = (first, count): only those
+    columns are processed (each its own chain), the others are copied — ``(0, C*n_mels)`` for spatial features, whose GCC
+    columns stay as they are.  ``state`` / ``start``: for features that arrive in pieces — ``start`` holds the absolute frame
+    index of every recording's first row and ``state`` a float32 CUDA tensor ``[R, count, 2]`` that is read where start > 0 and
+    updated; pieces of any sizes give bit for bit the rows of one call."""
+    _check_compress(settings)
+    if settings is None:
+        raise TypeError("pcen needs a PCEN(...) settings object")
+    if not (isinstance(logmel, torch.Tensor) and logmel.is_cuda and logmel.dim() == 2):
+        raise RuntimeError("sed_crnn_amd.feature.pcen needs a 2-D CUDA(HIP) tensor; there is no CPU fallback")
+    if (mean is None) != (std is None):
+        raise ValueError("give both mean and std or neither")
+    n, width = logmel.shape
+    col0, cnt = (0, width) if columns is None else (int(columns[0]), int(columns[1]))
+    if col0 < 0 or cnt < 1 or col0 + cnt > width:
+        raise ValueError(f"columns = (first, count) must lie inside the {width} feature columns, got {(col0, cnt)}")
+    if mean is not None and (mean.numel() != cnt or std.numel() != cnt):
+        raise ValueError(f"mean / std must have one entry per processed column ({cnt}), got {mean.numel()} / {std.numel()}")
+    recs = _rows_table(rows, n, start)
+    if state is not None and not (isinstance(state, torch.Tensor) and state.is_cuda and state.dtype == torch.float32 and
+                                  state.is_contiguous() and state.numel() == recs.shape[0] * cnt * 2):
+        raise ValueError(f"state must be a contiguous float32 CUDA tensor [R, count, 2] = [{recs.shape[0]}, {cnt}, 2]")
+    if state is None and (recs[:, 2] > 0).any():
+        raise ValueError("a recording that continues (start > 0) needs the state of the call before it")
+    out = logmel.float().clone(memory_format=torch.contiguous_format)
+    if n == 0:
+        return out
+    m32, i32 = _scaler(mean, std, out.device)
+    _pcen_launch(out, settings, settings.smoothing(sr, hop), recs, col0, cnt, m32, i32, state)
+    return out
+
+
+def _mel_identity(m32, i32, n_cols):
+    """the scaler a spatial log-mel launch gets when PCEN follows: identity on the first ``n_cols`` (mel) columns, whose real
+    entries go to the PCEN launch (returned second)"""
+    if m32 is None:
+        return (None, None), (None, None)
+    g_m, g_i = m32.clone(), i32.clone()
+    g_m[:n_cols] = 0.0
+    g_i[:n_cols] = 1.0
+    return (g_m, g_i), (m32[:n_cols].contiguous(), i32[:n_cols].contiguous())
+
+
 def mbe(y, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, pad_mode="constant", mean=None, std=None, tables=None, input_sr=None,
-        channels=1, keep_channels=False, device=None, spatial=None):
+        channels=1, keep_channels=False, device=None, spatial=None, compress=None):
     """y: mono float32 PCM CUDA tensor [N] -> [1 + N//hop, n_mels] log-mel energies (natural log, no eps).
     ``tables`` = build_tables(window, melfb, device) replaces librosa's default window / filterbank.
     ``input_sr`` / ``channels``: y is at that rate (default: ``sr``), int16 or float, ``[N, channels]`` interleaved when
@@ -151,11 +271,15 @@ def mbe(y, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, pad_mode="constant", mean=
     ``[c*n_mels, (c+1)*n_mels)`` (the layout the nets read), each bit for bit ``mbe(y[:, c])``; ``mean`` / ``std`` are then
     ``channels*n_mels`` wide.  ``device``: where a host clip that goes through resample.py is put.
     ``spatial="gcc_phat"`` (with ``keep_channels=True``, 2..8 channels): one GCC-PHAT image per microphone pair
-    behind the mel images -> ``[.., (C+P)*n_mels]``, P = C(C-1)/2; ``mean`` / ``std`` are then that wide."""
+    behind the mel images -> ``[.., (C+P)*n_mels]``, P = C(C-1)/2; ``mean`` / ``std`` are then that wide.
+    ``compress=PCEN(...)``: the mel columns hold PCEN instead of the log — the front end as before without the
+    scaler on them, then ``sed_pcen`` with it, bit for bit ``pcen(mbe(y), compress, ...)``; every mel column (of every kept
+    channel) is its own chain, GCC columns are what they are without ``compress``; ``mean`` / ``std`` keep their width."""
     _check_spatial(spatial, keep_channels, channels)
+    _check_compress(compress)
     if keep_channels:
         return mbe_many([y], sr=sr, n_fft=n_fft, hop=hop, n_mels=n_mels, pad_mode=pad_mode, mean=mean, std=std, tables=tables,
-                        device=device, input_sr=input_sr, channels=channels, keep_channels=True, spatial=spatial)[0]
+                        device=device, input_sr=input_sr, channels=channels, keep_channels=True, spatial=spatial, compress=compress)[0]
     if _needs_front_end(y, input_sr, sr, channels):
         from .resample import resample
         y = resample(y, sr if input_sr is None else input_sr, sr, channels, device)
@@ -171,16 +295,26 @@ def mbe(y, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, pad_mode="constant", mean=
     frames = 1 + y.numel() // hop
     out = torch.empty(frames, n_mels, device=y.device)
     mean, inv = _scaler(mean, std, y.device)
+    if compress is not None:
+        if mean is not None and (mean.numel() != n_mels or inv.numel() != n_mels):
+            raise ValueError(f"mean / std must have n_mels = {n_mels} entries, got {mean.numel()} / {inv.numel()}")
+        check(lib().sed_logmel(ptr(y), y.numel(), ptr(tables), tables.numel() * 4, None, None, ptr(out), n_fft, hop,
+                               n_mels, {"constant": 0, "reflect": 1}[pad_mode], stream_ptr()), "sed_logmel")
+        _pcen_launch(out, compress, compress.smoothing(sr, hop), [(0, frames, 0)], 0, n_mels, mean, inv, None)
+        return out
     check(lib().sed_logmel(ptr(y), y.numel(), ptr(tables), tables.numel() * 4, ptr(mean), ptr(inv), ptr(out), n_fft, hop,
                            n_mels, {"constant": 0, "reflect": 1}[pad_mode], stream_ptr()), "sed_logmel")
     return out
 
 
-def mbe_packed(pcm, clips, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, pad_mode="constant", mean=None, std=None, tables=None):
+def mbe_packed(pcm, clips, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, pad_mode="constant", mean=None, std=None, tables=None,
+               compress=None):
     """R clips that lie in ONE mono float32 CUDA buffer ``pcm``, ``clips`` = [(first sample, n_samples >= 1), ...] -> (features
     [sum_r (1 + n_r//hop), n_mels] in clip order, row offsets [R+1] as a host list), in one launch (``sed_logmel_batch``).
-    Each clip's rows are bit for bit ``mbe(clip)`` with the same options (its own centre padding at its own ends)."""
+    Each clip's rows are bit for bit ``mbe(clip)`` with the same options (its own centre padding at its own ends).
+    ``compress=PCEN(...)``: as in ``mbe`` — one ``sed_pcen`` call over all clips, every clip its own smoother."""
     import ctypes as C
+    _check_compress(compress)
     if not (isinstance(pcm, torch.Tensor) and pcm.is_cuda and pcm.dim() == 1):
         raise RuntimeError("sed_crnn_amd.feature.mbe_packed needs a 1-D CUDA(HIP) PCM buffer; there is no CPU fallback")
     if pad_mode not in ("constant", "reflect"):
@@ -203,14 +337,19 @@ def mbe_packed(pcm, clips, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, pad_mode="
     pcm = pcm.contiguous().float()
     mean, inv = _scaler(mean, std, pcm.device)
     ws = torch.empty(lib().sed_logmel_batch_workspace_bytes(R), dtype=torch.uint8, device=pcm.device)
+    if compress is not None and mean is not None and (mean.numel() != n_mels or inv.numel() != n_mels):
+        raise ValueError(f"mean / std must have n_mels = {n_mels} entries, got {mean.numel()} / {inv.numel()}")
+    lm_mean, lm_inv = (None, None) if compress is not None else (mean, inv)
     check(lib().sed_logmel_batch(ptr(pcm), pcm.numel(), C.c_void_p(table.ctypes.data), R, ptr(tables), tables.numel() * 4,
-                                 ptr(mean), ptr(inv), ptr(out), rows[-1], n_fft, hop, n_mels,
+                                 ptr(lm_mean), ptr(lm_inv), ptr(out), rows[-1], n_fft, hop, n_mels,
                                  {"constant": 0, "reflect": 1}[pad_mode], ptr(ws), ws.numel(), stream_ptr()), "sed_logmel_batch")
+    if compress is not None:
+        _pcen_launch(out, compress, compress.smoothing(sr, hop), _rows_table(rows, rows[-1]), 0, n_mels, mean, inv, None)
     return out, rows
 
 
 def mbe_planar(pcm, clips, channels, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, pad_mode="constant", mean=None, std=None,
-               tables=None, spatial=None):
+               tables=None, spatial=None, compress=None):
     """The multichannel twin of ``mbe_packed``: R recordings of ``channels`` planar channels each, all in ONE mono float32 CUDA
     buffer ``pcm``; ``clips`` = [(first sample, n_samples >= 1), ...] has ``R * channels`` entries, recording r, channel c at
     ``r * channels + c`` (what ``resample_many(..., keep_channels=True)`` returns), the channels of a recording equally long
@@ -220,9 +359,12 @@ def mbe_planar(pcm, clips, channels, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, 
     ``spatial="gcc_phat"`` (2..8 channels, even ``n_mels``; ``sed_logmel_gcc``): the P = C(C-1)/2 microphone pairs
     (i, j), i < j in lexicographic order, follow as columns ``[(C+p)*n_mels, (C+p+1)*n_mels)``: the GCC-PHAT of the frame at
     lags -n_mels/2 .. n_mels/2 - 1 (channel j = channel i delayed by d samples peaks at column n_mels/2 - d); the mel columns
-    are bit for bit those without ``spatial``, and ``mean`` / ``std`` are ``(C+P)*n_mels`` wide."""
+    are bit for bit those without ``spatial``, and ``mean`` / ``std`` are ``(C+P)*n_mels`` wide.
+    ``compress=PCEN(...)``: the ``channels*n_mels`` mel columns, each its own chain, hold PCEN (``sed_pcen`` with their
+    part of the scaler, after a front-end launch that leaves them unscaled); GCC columns are bit for bit those without it."""
     import ctypes as C
     _check_spatial(spatial, True, channels)
+    _check_compress(compress)
     if not (isinstance(pcm, torch.Tensor) and pcm.is_cuda and pcm.dim() == 1):
         raise RuntimeError("sed_crnn_amd.feature.mbe_planar needs a 1-D CUDA(HIP) PCM buffer; there is no CPU fallback")
     if pad_mode not in ("constant", "reflect"):
@@ -261,16 +403,22 @@ def mbe_planar(pcm, clips, channels, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, 
     out = torch.empty(rows[-1], width, device=pcm.device)
     pcm = pcm.contiguous().float()
     mean, inv = _scaler(mean, std, pcm.device)
+    if compress is not None:                                     # the mel columns leave the front end unscaled; PCEN scales them
+        (mean, inv), pc_scaler = _mel_identity(mean, inv, nc * n_mels) if spatial else ((None, None), (mean, inv))
     if spatial:
         ws = torch.empty(lib().sed_logmel_gcc_workspace_bytes(R, nc), dtype=torch.uint8, device=pcm.device)
         check(lib().sed_logmel_gcc(ptr(pcm), pcm.numel(), C.c_void_p(table.ctypes.data), R, nc, ptr(tables), tables.numel() * 4,
                                    ptr(mean), ptr(inv), ptr(out), rows[-1], n_fft, hop, n_mels, n_mels,
                                    {"constant": 0, "reflect": 1}[pad_mode], ptr(ws), ws.numel(), stream_ptr()), "sed_logmel_gcc")
+        if compress is not None:
+            _pcen_launch(out, compress, compress.smoothing(sr, hop), _rows_table(rows, rows[-1]), 0, nc * n_mels, *pc_scaler, None)
         return out, rows
     ws = torch.empty(lib().sed_logmel_multi_workspace_bytes(R, nc), dtype=torch.uint8, device=pcm.device)
     check(lib().sed_logmel_multi(ptr(pcm), pcm.numel(), C.c_void_p(table.ctypes.data), R, nc, ptr(tables), tables.numel() * 4,
                                  ptr(mean), ptr(inv), ptr(out), rows[-1], n_fft, hop, n_mels,
                                  {"constant": 0, "reflect": 1}[pad_mode], ptr(ws), ws.numel(), stream_ptr()), "sed_logmel_multi")
+    if compress is not None:
+        _pcen_launch(out, compress, compress.smoothing(sr, hop), _rows_table(rows, rows[-1]), 0, nc * n_mels, *pc_scaler, None)
     return out, rows
 
 
@@ -297,15 +445,17 @@ def pack_clips(waves, device):
 
 
 def mbe_many(waves, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, pad_mode="constant", mean=None, std=None, tables=None,
-             device=None, input_sr=None, channels=1, keep_channels=False, spatial=None):
+             device=None, input_sr=None, channels=1, keep_channels=False, spatial=None, compress=None):
     """``mbe`` of every clip in a list of 1-D clips (host or device; ``device`` defaults to the first CUDA clip's, else
     cuda:current) in one launch -> (features [sum_r (1 + n_r//hop), n_mels] in clip order, row offsets [R+1] host list).
     Bit for bit ``torch.cat([mbe(w) for w in waves])``.  ``input_sr`` (one rate, or one per clip) / ``channels``: as in
     ``mbe``; the clips are resampled straight into the packed buffer the log-mel launch reads (``resample.resample_many``).
     ``keep_channels=True``: every clip is ``[N, channels]`` and its channels are kept -> features ``[.., channels*n_mels]``
     (``mbe_planar``; the resampler writes the planar channels of every clip straight into the buffer that launch reads).
-    ``spatial="gcc_phat"``: as in ``mbe_planar`` — bit for bit the per-recording calls."""
+    ``spatial="gcc_phat"``: as in ``mbe_planar`` — bit for bit the per-recording calls.  ``compress=PCEN(...)``: as in ``mbe``;
+    one ``sed_pcen`` call for all clips, bit for bit the per-clip calls."""
     _check_spatial(spatial, keep_channels, channels)
+    _check_compress(compress)
     waves = list(waves)
     if device is None:
         device = next((w.device for w in waves if isinstance(w, torch.Tensor) and w.is_cuda), None)
@@ -317,7 +467,7 @@ def mbe_many(waves, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, pad_mode="constan
                 raise ValueError(f"clip {i} is empty")
         pcm, clips = resample_many(waves, sr if input_sr is None else input_sr, sr, channels, device, keep_channels=True)
         return mbe_planar(pcm, clips, channels, sr=sr, n_fft=n_fft, hop=hop, n_mels=n_mels, pad_mode=pad_mode, mean=mean, std=std,
-                          tables=tables, spatial=spatial)
+                          tables=tables, spatial=spatial, compress=compress)
     if input_sr is not None and np.ndim(input_sr) > 0 or any(_needs_front_end(w, input_sr, sr, channels) for w in waves):
         from .resample import resample_many
         pcm, clips = resample_many(waves, sr if input_sr is None else input_sr, sr, channels, device)
@@ -327,7 +477,7 @@ def mbe_many(waves, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, pad_mode="constan
         if n < 1:
             raise ValueError(f"clip {i} is empty")
     return mbe_packed(pcm, clips, sr=sr, n_fft=n_fft, hop=hop, n_mels=n_mels, pad_mode=pad_mode, mean=mean, std=std,
-                      tables=tables)
+                      tables=tables, compress=compress)
 
 
 # ───────────────────────── feature.py's on-disk formats ─────────────────────────

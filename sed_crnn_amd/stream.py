@@ -34,6 +34,9 @@ carry and its own log-mel PCM carry on the device, while the host counters stay 
 lockstep), and a round's features come out of ``sed_logmel_multi`` as ``[rows, C*F]``, which is what the feature rows hold.
 A spatial detector (``EventDetector(..., spatial="gcc_phat")``) keeps the same C lanes per feed and calls
 ``sed_logmel_gcc`` instead: ``[rows, (C+P)*F]`` with one GCC-PHAT block per microphone pair, and no further state.
+A detector with ``compress=PCEN(...)`` adds one ``sed_pcen`` call per round over the new rows of all feeds, with
+the feed's feature-frame counter as the absolute frame index; the smoother's state, two floats per feed and mel column, stays
+on the device and is simply ignored when a feed's counter is back at 0 (``flush`` / ``reset`` need nothing more).
 """
 import ctypes as C
 
@@ -179,6 +182,7 @@ class StreamDetector:
             raise ValueError(f"{S} feeds of {self.C} channels are {S * self.C} lanes: sed_stream_append takes at most 65535")
         self.S, self.keep_probs, self.max_new = S, bool(keep_probs), int(max_new_windows)
         self.K, self.CF = m.dense[-1], m.in_channels * m.n_mels
+        self.PW = self.C * m.n_mels                                        # mel columns = PCEN chains per feed (with det.compress)
         tf = m.time_factor
         self.sched = StreamSchedules(tf, det.seq_len, det.hop, det.trim, det.median_max, S)     # class-wise: the widest median
         self.win_out, self.hop_out = self.sched.win_out, self.sched.hop_out
@@ -195,6 +199,7 @@ class StreamDetector:
             check(-1, "sed_stream_state_bytes")
         self._state = self._feat = self._pcm = None                        # allocated by the first call that runs
         self._aws = self._sws = self._lm = None
+        self._pcen_state = self._pws = self._pc_scaler = None
         z = lambda: np.zeros(S, np.int64)                                   # noqa: E731
         self._n, self._fdone = z(), z()                                    # samples received, feature frames made from them
         self._cbase, self._clen, self._cpar = z(), z(), z()                # the PCM carry: first sample, length, which half
@@ -221,9 +226,10 @@ class StreamDetector:
     # ── sizes ──
     @property
     def state_bytes(self):
-        """device bytes held between calls: the step's rings and decoder states, the feature rows and, per lane, the PCM carry
-        and the resampler's carry"""
-        return self._core_bytes + 4 * self.S * 2 * (self.FC * self.CF + self.C * (self.CC + (self._rCR if self._rs is not None else 0)))
+        """device bytes held between calls: the step's rings and decoder states, the feature rows, per lane the PCM carry
+        and the resampler's carry and, with ``compress``, the PCEN smoother's two floats per feed and mel column"""
+        pcen = 8 * self.S * self.PW if self.det.compress is not None else 0                 # (C_k, loc) per chain
+        return self._core_bytes + pcen + 4 * self.S * 2 * (self.FC * self.CF + self.C * (self.CC + (self._rCR if self._rs is not None else 0)))
 
     @property
     def frame_seconds(self):
@@ -244,6 +250,8 @@ class StreamDetector:
             self._feat = torch.empty(S * 2 * self.FC, self.CF, device=dev)
             self._pcm = torch.empty(S * self.C * 2 * self.CC, device=dev)
             self._aws = torch.empty(lib().sed_stream_append_workspace_bytes(S * self.C), dtype=torch.uint8, device=dev)
+            if self.det.compress is not None:
+                self._pcen_state = torch.zeros(S, self.PW, 2, device=dev)
             check(lib().sed_stream_init(ptr(self._state), self._state.numel(), *self._dims, stream_ptr()), "sed_stream_init")
         return self._state.device
 
@@ -290,6 +298,9 @@ class StreamDetector:
             m = det.model
             tables = feature._tables(dev.index or 0, det.sr, feature.NFFT, m.n_mels)
             mean, inv = feature._scaler(det.mean, det.std, dev)
+            if det.compress is not None:                                    # the mel columns leave the front end unscaled
+                (mean, inv), self._pc_scaler = (feature._mel_identity(mean, inv, self.PW) if det.spatial
+                                                else ((None, None), (mean, inv)))
             need = (lib().sed_logmel_batch_workspace_bytes(S) if NC == 1 else lib().sed_logmel_gcc_workspace_bytes(S, NC) if det.spatial
                     else lib().sed_logmel_multi_workspace_bytes(S, NC))
             ws = torch.empty(need, dtype=torch.uint8, device=dev)
@@ -302,16 +313,30 @@ class StreamDetector:
                 ptr(work), work.numel(), C.c_void_p(ct.ctypes.data), ct.shape[0] // NC, NC, ptr(tables), tables.numel() * 4, ptr(mean),
                 ptr(inv), ptr(out), n_rows, feature.NFFT, h, det.model.n_mels, det.model.n_mels, 0, ptr(ws), ws.numel(), stream_ptr()),
                 "sed_logmel_gcc"))
-            return out, row0, rows
+            return self._pcen_round(out, row0, rows, done), row0, rows
         if NC > 1:                                                          # the C lanes of a feed -> its rows' C column blocks
             _timed(self.marks, "logmel", lambda: check(lib().sed_logmel_multi(
                 ptr(work), work.numel(), C.c_void_p(ct.ctypes.data), ct.shape[0] // NC, NC, ptr(tables), tables.numel() * 4, ptr(mean),
                 ptr(inv), ptr(out), n_rows, feature.NFFT, h, det.model.n_mels, 0, ptr(ws), ws.numel(), stream_ptr()), "sed_logmel_multi"))
-            return out, row0, rows
+            return self._pcen_round(out, row0, rows, done), row0, rows
         _timed(self.marks, "logmel", lambda: check(lib().sed_logmel_batch(
             ptr(work), work.numel(), C.c_void_p(ct.ctypes.data), ct.shape[0], ptr(tables), tables.numel() * 4, ptr(mean), ptr(inv),
             ptr(out), n_rows, feature.NFFT, h, det.model.n_mels, 0, ptr(ws), ws.numel(), stream_ptr()), "sed_logmel_batch"))
-        return out, row0, rows
+        return self._pcen_round(out, row0, rows, done), row0, rows
+
+    def _pcen_round(self, out, row0, rows, done):
+        """with ``compress``: PCEN, in place, of the mel columns of the round's NEW rows — feed s owns ``rows[s]`` rows from
+        ``row0[s]``, the first of them its feature frame ``done[s]`` — in one ``sed_pcen`` call over all feeds.  The smoother's
+        state (S x C*n_mels chains) stays on the device; a feed whose counter is back at 0 starts afresh without a reset."""
+        det = self.det
+        if det.compress is None:
+            return out
+        recs = np.stack([row0, rows, np.where(rows > 0, done, 0)], 1)
+        def run():
+            self._pws = feature._pcen_launch(out, det.compress, det.compress.smoothing(det.sr, det.hop_length), recs, 0, self.PW,
+                                             *self._pc_scaler, self._pcen_state, self._pws)
+        _timed(self.marks, "logmel", run)
+        return out
 
     # ── one step: new feature rows in, events out ──
     def _step(self, fresh, row0, rows, end):
