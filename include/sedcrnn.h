@@ -479,6 +479,33 @@ size_t sed_logmel_gcc_workspace_bytes(int R, int channels);
 int sed_logmel_gcc(const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const void* tables,
                    size_t tables_bytes, const float* mu, const float* inv_sigma, float* out, long out_rows, int n_fft, int hop,
                    int n_mels, int n_lags, int pad_mode, void* workspace, size_t workspace_bytes, void* stream);
+/* sed_event_tdoa: for each of E detected events and each microphone pair p = (i, j), i < j in lexicographic order, the
+ * time difference of arrival in samples and how coherent it is, from the GCC-PHAT of the event's frames accumulated in the
+ * frequency domain.  The recordings are given as for sed_logmel_gcc (planar channels, equal lengths; clips_host is a HOST table
+ * that is validated before anything is enqueued).  ev_rec / ev_onset / ev_offset / ev_peak_frame: DEVICE int32 [E], in output
+ * frames of time_factor feature frames, offset exclusive (what the decoders write); ev_rec may be NULL when R == 1.  With n_feat =
+ * 1 + n/hop feature frames in the event's recording, a = onset*time_factor and b = min(offset*time_factor, n_feat), the event is
+ * located on the frames [f0, f1): [a, b) when b - a <= max_frames, else the max_frames frames f0 = clamp(peak_frame*time_factor +
+ * time_factor/2 - max_frames/2, a, b - max_frames); the single frame a when b <= a.  With Pk_f the whitened cross spectrum of
+ * frame f as sed_logmel_gcc defines it, S = sum_f Pk_f and acc[tau] = (1/2048) (S[0] + (-1)^tau S[1024] + 2 sum_{k=1..1023}
+ * Re(S[k] e^{+2 pi i k tau / 2048})), |tau| <= max_lag + 1: t* is the first maximum of acc over |tau| <= max_lag in ascending
+ * order, lag = t* + 0.5 (l - r) / (l - 2m + r) with (l, m, r) = acc[t*-1 .. t*+1] where that denominator is < 0, else t*;
+ * strength = m / (f1 - f0) in [-1, 1].  Channel j = channel i delayed by d samples gives lag = -d.  Digital silence gives acc = 0,
+ * lag = 0, strength = 0, never NaN.  lag_out / strength_out: device float [E][P]; frames_out: device int32 [E] = f1 - f0; acc_out
+ * (may be NULL): device float [E][P][2 max_lag + 3], acc[tau] at tau + max_lag + 1.  The event entries are checked on the device:
+ * an event whose rec is outside [0, R) or whose onset is negative or beyond its recording's last frame gets 0 frames, lag 0 and
+ * strength 0, and reads no memory.  Every output is summed in one fixed order that depends on the event's own samples and frame
+ * range alone (frames in ascending order within chunks of 32 counted from f0, the chunks in ascending order): not on the other
+ * events, the clip's place in the buffer or the workspace size.  workspace: 16-byte aligned;
+ * sed_event_tdoa_workspace_bytes(R, channels, E, longest recording in samples, hop, max_frames) holds all E events at once (0 =
+ * bad sizes); with less — at least the size for E = 1 — the event table is processed in slices, with the same bits.  The host
+ * reads nothing back.  2 <= channels <= 8, 1 <= max_lag <= 127, max_frames >= 1, the 2048-point tables of sed_logmel_build_tables;
+ * E = 0 launches nothing. */
+size_t sed_event_tdoa_workspace_bytes(int R, int channels, long E, long max_n_samples, int hop, int max_frames);
+int sed_event_tdoa(const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const void* tables,
+                   size_t tables_bytes, const int* ev_rec, const int* ev_onset, const int* ev_offset, const int* ev_peak_frame,
+                   long E, int time_factor, int hop, int pad_mode, int max_lag, int max_frames, float* lag_out, float* strength_out,
+                   int* frames_out, float* acc_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* sed_pcen: per-channel energy normalisation, IN PLACE, of the columns [col0, col0 + W) of x [rows][stride], which
  * hold log-mel values (natural log, as sed_logmel* write them without a scaler); the other columns are not touched.  Every column

@@ -1,0 +1,428 @@
+// tdoa.hip — per-event time difference of arrival from accumulated GCC-PHAT: sed_event_tdoa.
+//
+// For a detected event (rec, onset, offset, peak_frame in output frames), the frames [f0, f1) it is located on
+// (td_event_range below; sed_crnn_amd/localize.py states the same rule on the host) and microphone pair (i, j), i < j:
+//   Pk_f[k] = G_f[k] / |G_f[k]|, G_f = X_i conj X_j of frame f     (gcc.hip's definition, thresholds and real DC / Nyquist bins)
+//   S[k]    = sum_{f = f0}^{f1 - 1} Pk_f[k]
+//   acc[tau] = (1/2048) (S[0] + (-1)^tau S[1024] + 2 sum_{k=1..1023} Re(S[k] e^{+2 pi i k tau / 2048})),  |tau| <= max_lag + 1
+//   t* = first maximum of acc over |tau| <= max_lag;  lag = t* + 0.5 (l - r) / (l - 2 m + r) where that denominator is < 0;
+//   strength = m / (f1 - f0).
+// The inverse transform is linear, so the lags are synthesised once per (event, pair) from the summed cross spectra instead of
+// once per frame.
+//
+// Shape (gfx950), two plain launches per slice of the event table; no workgroup waits on another and there are no atomics:
+//   tdoa_accum_k   one workgroup of 8 waves owns one CHUNK: TD_CHUNK consecutive frames of one event, counted from the event's
+//                  f0.  Per frame: the FFT of the C channels into LDS and the whitening of every pair (steps 1 and 2 of
+//                  gcc_phat_k, the same code), added into a per-pair accumulator [pairs of the batch][1026] float2 in LDS in
+//                  ascending frame order; every accumulator entry belongs to one lane.  Where the spectra fit LDS twice
+//                  (C <= 4) the transforming waves run one frame ahead of the whitening waves.  The chunk's partial sums go
+//                  to the workspace.  Where the P accumulators do not fit beside the spectra (C >= 5) the pairs go in batches and the
+//                  chunk's frames are transformed again for every batch.
+//   tdoa_finish_k  per (event, pair): the chunk partials added in ascending chunk order, the 2 max_lag + 3 lags by the
+//                  8-lanes-per-(pair, tau) direct sum against the exact 2048-entry (cos, sin) table, peak and parabola.
+// Every output is therefore summed in ONE order that depends on the event's own samples and frame range alone: not on the
+// other events, the slice, the clip's place in the buffer, the load path or the launch shape.
+#include <math.h>
+#include <string.h>
+#include <vector>
+#include "common.h"
+#include "fft2048.h"
+
+#define TD_CHUNK 32                               // frames per workgroup of the accumulate launch
+#define TD_WAVES 8
+#define TD_THREADS (TD_WAVES * 64)
+#define TD_MAX_CH 8
+#define TD_MAX_LAG 127
+#define TD_SPEC 1026                              // float2 per spectrum / accumulator row (1025 bins + 1 pad)
+#define TD_TAB_WORDS LM_OFF_ENT                   // of the log-mel blob: header, window, inter-pass and pairing twiddles
+#define TD_FFT_SCR (2 * LM_SCR)                   // floats of exchange scratch per transforming wave
+#define TD_LDS_MAX ((size_t)160 * 1024)
+#define TD_FIN_THREADS 256
+#define TD_ROW_BYTES ((size_t)TD_SPEC * sizeof(float2))
+
+namespace {
+
+struct TdArgs {
+    const long* sample_off;     // [R*C] first sample of every planar channel
+    const long* n_samples;      // [R]   samples per channel
+    const int *ev_rec, *ev_onset, *ev_offset, *ev_peak;          // [E] (ev_rec may be null: one recording)
+    int R, C, P, pairs_per_batch;
+    int tf, hop, max_frames, max_lag;
+    int cpe;                    // chunk slots per event in the workspace
+    int pipelined;              // two spectra buffers: the FFT of frame f+1 runs beside the whitening of frame f
+    long e0;                    // first event of the slice
+    int n_ev;                   // events of the slice
+};
+
+// The frames [f0, f0 + nf) an event is located on; nf = 0: the event names no recording or lies beyond its end (nothing is read).
+__device__ __forceinline__ void td_event_range(const TdArgs& a, long e, int& rec, long& f0, int& nf) {
+    rec = a.ev_rec ? a.ev_rec[e] : 0;
+    f0 = 0; nf = 0;
+    if (rec < 0 || rec >= a.R) return;
+    const long n_feat = 1 + a.n_samples[rec] / a.hop;
+    const long on = a.ev_onset[e], off = a.ev_offset[e];
+    const long lo = on * a.tf;
+    long hi = off * a.tf;
+    if (hi > n_feat) hi = n_feat;
+    if (on < 0 || lo >= n_feat) return;
+    if (hi <= lo) { f0 = lo; nf = 1; return; }
+    if (hi - lo <= a.max_frames) { f0 = lo; nf = (int)(hi - lo); return; }
+    long c = (long)a.ev_peak[e] * a.tf + a.tf / 2 - a.max_frames / 2;
+    if (c < lo) c = lo;
+    if (c > hi - a.max_frames) c = hi - a.max_frames;
+    f0 = c; nf = a.max_frames;
+}
+
+__global__ __launch_bounds__(TD_THREADS) void tdoa_accum_k(const float* __restrict__ pcm, const uint32_t* __restrict__ tables,
+                                                           float2* __restrict__ ws, int pad_mode, TdArgs ta) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x;
+    const long e = ta.e0 + blockIdx.y;
+    int rec, nf;
+    long f0;
+    td_event_range(ta, e, rec, f0, nf);
+    const int fc0 = blockIdx.x * TD_CHUNK;                       // the chunk's first frame, counted from f0
+    if (fc0 >= nf) return;                                       // (block-uniform: before any barrier)
+    const int fc1 = fc0 + TD_CHUNK < nf ? fc0 + TD_CHUNK : nf;
+    {   // window + twiddles of the log-mel blob: global -> LDS
+        const f32x4* src = reinterpret_cast<const f32x4*>(tables);
+        f32x4* dst = reinterpret_cast<f32x4*>(lds);
+        for (int i = tid; i < TD_TAB_WORDS / 4; i += TD_THREADS) dst[i] = src[i];
+    }
+    const f2* s_win = reinterpret_cast<const f2*>(lds + LM_OFF_WIN);
+    const f2* s_tw = reinterpret_cast<const f2*>(lds + LM_OFF_TW);
+    const f2* s_pw = reinterpret_cast<const f2*>(lds + LM_OFF_PW);
+    const int C = ta.C, P = ta.P;
+    const int nfw = (C + 1) >> 1;                                // waves that transform
+    const bool pipe = ta.pipelined != 0;
+    float2* s_spec = reinterpret_cast<float2*>(lds + TD_TAB_WORDS);                              // [1 or 2][C][TD_SPEC]
+    float* s_scr = lds + TD_TAB_WORDS + (pipe ? 2 : 1) * C * TD_SPEC * 2;                        // [nfw][TD_FFT_SCR]
+    float2* s_acc = reinterpret_cast<float2*>(s_scr + nfw * TD_FFT_SCR);                         // [batch][TD_SPEC]
+
+    const int lane = tid & 63, wave = tid >> 6, half = lane >> 5, r = lane & 31;
+    float* wscr = s_scr + (wave < nfw ? wave : 0) * TD_FFT_SCR;  // (only used by waves < nfw)
+    float* scr = wscr + half * LM_SCR;
+    const unsigned xbase = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(wscr - lds) * 4u +
+                                                          (unsigned)__builtin_amdgcn_groupstaticsize());
+    const int partner = (lane & 32) | ((32 - r) & 31);
+    const long ns = ta.n_samples[rec];
+    float2* wrow = ws + ((long)blockIdx.y * ta.cpe + blockIdx.x) * P * TD_SPEC;
+    // Pipelined (the spectra fit twice, C <= 4): in step s the transforming waves fill buffer s & 1 with frame s while the other
+    // waves whiten frame s - 1 from the other buffer; one barrier per step.  Otherwise every wave whitens, between two barriers.
+    // Either way an accumulator entry belongs to one lane and receives the frames in ascending order: the same sums.
+    const int wt0 = pipe ? nfw * 64 : 0, wstride = TD_THREADS - wt0;
+    const int n_fr = fc1 - fc0;
+
+    for (int p0 = 0; p0 < P; p0 += ta.pairs_per_batch) {
+        const int nb = (P - p0 < ta.pairs_per_batch) ? P - p0 : ta.pairs_per_batch;
+        for (int idx = tid; idx < nb * TD_SPEC; idx += TD_THREADS) s_acc[idx] = make_float2(0.f, 0.f);
+        __syncthreads();                                         // the tables are in LDS (first batch); the spectra are free
+        for (int step = 0; step < n_fr + (pipe ? 1 : 0); ++step) {
+            const long frame = f0 + fc0 + step;
+            if (wave < nfw && step < n_fr) {
+                // ── the frame of channel 2 wave + half (an odd C: the last half wave repeats channel C-1 and stores the same values) ──
+                const int ch = (2 * wave + half < C) ? 2 * wave + half : C - 1;
+                const float* cpcm = pcm + ta.sample_off[(long)rec * C + ch];
+                const long start = frame * ta.hop - LM_NFFT / 2;
+                const bool fast = (ta.hop & 1) == 0 && (reinterpret_cast<uintptr_t>(cpcm) & 7) == 0 && start >= 0 && start + LM_NFFT <= ns;
+                f2 z[32];                                        // z[n] = (x[2n], x[2n+1]): one complex point per VGPR pair
+                if (__all(fast)) {
+                    const f2* src = reinterpret_cast<const f2*>(cpcm + start) + r;
+#pragma unroll
+                    for (int n1 = 0; n1 < 32; ++n1) z[n1] = src[32 * n1];
+                } else {                                         // edge frames / odd hop / unaligned clips: guarded loads through LDS
+                    wave_lds_fence();
+#pragma unroll 1
+                    for (int n1 = 0; n1 < 32; ++n1) scr[n1 * 32 + r] = pcm_at(cpcm, start + 64 * n1 + 2 * r, ns, pad_mode);
+                    wave_lds_fence();
+#pragma unroll
+                    for (int n1 = 0; n1 < 32; ++n1) z[n1].x = scr[n1 * 32 + r];
+                    wave_lds_fence();
+#pragma unroll 1
+                    for (int n1 = 0; n1 < 32; ++n1) scr[n1 * 32 + r] = pcm_at(cpcm, start + 64 * n1 + 2 * r + 1, ns, pad_mode);
+                    wave_lds_fence();
+#pragma unroll
+                    for (int n1 = 0; n1 < 32; ++n1) z[n1].y = scr[n1 * 32 + r];
+                }
+#pragma unroll
+                for (int n1 = 0; n1 < 32; ++n1) z[n1] *= s_win[32 * n1 + r];
+                // ── pass 1 over n1, twiddle W_1024^{r k1}, exchange through the wave's 32 x 65 buffer, pass 2 over n2 (gcc.hip) ──
+                fft32(z);
+#pragma unroll
+                for (int k1 = 1; k1 < 32; ++k1) {
+                    const int b = brev5(k1);
+                    z[b] = cmul(z[b], s_tw[k1 * 32 + r]);
+                }
+                wave_lds_fence();
+                exchange_store<0>(xbase, z);
+                wave_lds_fence();
+                const unsigned xaddr = xbase + (unsigned)(r * LM_ROW_BYTES + 128 * half);
+#define TD_XREAD(H)                                                                                              \
+    _Pragma("unroll") for (int n2 = 0; n2 < 32; ++n2) {                                                           \
+        float t_;                                                                                                \
+        asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(t_) : "v"(xaddr), "i"(n2 * 4));                       \
+        z[n2].H = t_;                                                                                            \
+    }                                                                                                            \
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                           \
+    _Pragma("unroll") for (int n2 = 0; n2 < 32; ++n2) asm volatile("" : "+v"(z[n2]));
+                TD_XREAD(x)
+                wave_lds_fence();
+                exchange_store<1>(xbase, z);
+                wave_lds_fence();
+                TD_XREAD(y)
+#undef TD_XREAD
+                wave_lds_fence();
+                fft32(z);                                        // Z[r + 32 k2] = z[brev5(k2)]
+                // ── pairing: 2 X[k] = (Z[k] + conj Z[N-k]) - i W_2048^k (Z[k] - conj Z[N-k]) = e + t, and 2 X[N-k] = conj(e - t) ──
+                float2* spec = s_spec + ((pipe ? (step & 1) : 0) * C + ch) * TD_SPEC;
+#pragma unroll
+                for (int k2 = 0; k2 < 16; ++k2) {
+                    const int bp = brev5(31 - k2), b0 = brev5((32 - k2) & 31);
+                    f2 pp = {__shfl(z[bp].x, partner, 64), __shfl(z[bp].y, partner, 64)};
+                    if (r == 0) pp = z[b0];
+                    const f2 zz = z[brev5(k2)];
+                    const int k = r + 32 * k2;
+                    const f2 ee = add_conj(zz, pp);
+                    const f2 q = rot_sub_conj(zz, pp);
+                    const f2 t = cmul(q, s_pw[k]);
+                    const f2 a = ee + t, bb = ee - t;
+                    spec[k] = make_float2(0.5f * a.x, 0.5f * a.y);
+                    spec[LM_N - k] = make_float2(0.5f * bb.x, -0.5f * bb.y);
+                }
+                if (r == 0) { const f2 zz = z[brev5(16)]; spec[512] = make_float2(zz.x, -zz.y); }      // X[512] = conj Z[512]
+            }
+            if (!pipe) __syncthreads();
+            // ── Pk of the batch's pairs, added to the accumulators; Pk[0] is halved (the synthesis counts every bin twice) and the
+            //    DC and Nyquist bins are real.  Entry idx is read and written by this lane alone, frame after frame. ──
+            const int wf = pipe ? step - 1 : step;               // the frame of the chunk whose spectra are whitened now
+            const float2* wspec = s_spec + (pipe ? (wf & 1) : 0) * C * TD_SPEC;
+            for (int idx = wf >= 0 && tid >= wt0 ? tid - wt0 : nb * 1025; idx < nb * 1025; idx += wstride) {
+                const int pb = idx / 1025, k = idx - pb * 1025;
+                int i = 0, rem = p0 + pb;                        // pair p -> (i, j), lexicographic
+                while (rem >= C - 1 - i) { rem -= C - 1 - i; ++i; }
+                const int j = i + 1 + rem;
+                const float2 a = wspec[i * TD_SPEC + k], b = wspec[j * TD_SPEC + k];
+                const float gr = a.x * b.x + a.y * b.y, gi = a.y * b.x - a.x * b.y;
+                const float m2 = gr * gr + gi * gi;
+                // (m2 beyond the float range is inf: those bins are 0 by the definition, never inf * 0 = NaN — gcc.hip)
+                const float inv = (m2 >= 1e-30f && m2 <= 3.0e38f) ? rsqrtf(m2) : 0.f;
+                float pr = gr * inv, pi = gi * inv;
+                if (k == 0) { pr *= 0.5f; pi = 0.f; }
+                if (k == LM_N) pi = 0.f;
+                float2 s = s_acc[pb * TD_SPEC + k];
+                s.x += pr; s.y += pi;
+                s_acc[pb * TD_SPEC + k] = s;
+            }
+            __syncthreads();                                     // the spectra (of this buffer) may be overwritten
+        }
+        for (int idx = tid; idx < nb * 1025; idx += TD_THREADS) {
+            const int pb = idx / 1025, k = idx - pb * 1025;
+            wrow[(long)(p0 + pb) * TD_SPEC + k] = s_acc[pb * TD_SPEC + k];
+        }
+        __syncthreads();                                         // the accumulators are zeroed for the next batch
+    }
+}
+
+// One (persistent) workgroup per event at a time: every pair of the event in turn.
+__global__ __launch_bounds__(TD_FIN_THREADS) void tdoa_finish_k(const uint32_t* __restrict__ tables, const float2* __restrict__ ws,
+                                                                float* __restrict__ lag_out, float* __restrict__ strength_out,
+                                                                int* __restrict__ frames_out, float* __restrict__ acc_out, TdArgs ta) {
+    __shared__ __attribute__((aligned(16))) float2 s_lag[LM_NFFT];
+    __shared__ __attribute__((aligned(16))) float2 s_S[TD_SPEC];
+    __shared__ float s_cc[2 * TD_MAX_LAG + 3];
+    const int tid = threadIdx.x;
+    {   // the lag table (cos, sin)(2 pi m / 2048), m = 0..2047, unfolded from the blob's pairing twiddles pw[k] = (cos, -sin)
+        // (2 pi k / 2048), k = 0..512 (float64 values rounded once), as gcc_phat_k does it
+        const float2* pw = reinterpret_cast<const float2*>(tables + LM_OFF_PW);
+        for (int m = tid; m < LM_NFFT; m += TD_FIN_THREADS) {
+            const int mm = m <= LM_N ? m : LM_NFFT - m;
+            const int k = mm <= LM_N / 2 ? mm : LM_N - mm;
+            const float2 w = pw[k];
+            s_lag[m] = make_float2(mm <= LM_N / 2 ? w.x : -w.x, m <= LM_N ? -w.y : w.y);
+        }
+    }
+    __syncthreads();
+    const int P = ta.P, ML = ta.max_lag, T = ML + 2, W = 2 * ML + 3;
+    for (int el = blockIdx.x; el < ta.n_ev; el += gridDim.x) {
+        const long e = ta.e0 + el;
+        int rec, nf;
+        long f0;
+        td_event_range(ta, e, rec, f0, nf);
+        if (tid == 0) frames_out[e] = nf;
+        if (nf == 0) {                                           // (block-uniform)
+            for (int p = tid; p < P; p += TD_FIN_THREADS) { lag_out[e * P + p] = 0.f; strength_out[e * P + p] = 0.f; }
+            if (acc_out)
+                for (int i = tid; i < P * W; i += TD_FIN_THREADS) acc_out[e * P * W + i] = 0.f;
+            continue;
+        }
+        const int nch = (nf + TD_CHUNK - 1) / TD_CHUNK;
+        const float2* wev = ws + (long)el * ta.cpe * P * TD_SPEC;
+        for (int p = 0; p < P; ++p) {
+            // ── S = the chunk partials in ascending chunk order ──
+            for (int k = tid; k < 1025; k += TD_FIN_THREADS) {
+                float2 s = wev[(long)p * TD_SPEC + k];
+                for (int c = 1; c < nch; ++c) {
+                    const float2 v = wev[((long)c * P + p) * TD_SPEC + k];
+                    s.x += v.x; s.y += v.y;
+                }
+                s_S[k] = s;
+            }
+            __syncthreads();
+            // ── lag synthesis: item = tau = 0..max_lag+1, 8 lanes per item; cc[+tau] = A - B, cc[-tau] = A + B ──
+            const int grp = tid >> 3, j8 = tid & 7;
+            for (int it0 = 0; it0 < T; it0 += TD_FIN_THREADS / 8) {
+                const bool valid = it0 + grp < T;
+                const int tau = valid ? it0 + grp : 0;
+                float A = 0.f, B = 0.f;
+                int m = (j8 * tau) & (LM_NFFT - 1);
+                const int step = (8 * tau) & (LM_NFFT - 1);
+#pragma unroll 8
+                for (int i = 0; i < LM_N / 8; ++i) {             // bins k = j8 + 8 i, ascending
+                    const float2 q = s_S[j8 + 8 * i], t = s_lag[m];
+                    A = fmaf(q.x, t.x, A);
+                    B = fmaf(q.y, t.y, B);
+                    m = (m + step) & (LM_NFFT - 1);
+                }
+                A += __shfl_xor(A, 1, 64); B += __shfl_xor(B, 1, 64);
+                A += __shfl_xor(A, 2, 64); B += __shfl_xor(B, 2, 64);
+                A += __shfl_xor(A, 4, 64); B += __shfl_xor(B, 4, 64);
+                if (valid && j8 < 2) {
+                    const float ny = s_S[LM_N].x, sgn = (tau & 1) ? -ny : ny;
+                    const bool plus = j8 == 0;
+                    if (plus || tau > 0) s_cc[plus ? ML + 1 + tau : ML + 1 - tau] = (2.f * (plus ? A - B : A + B) + sgn) * (1.f / LM_NFFT);
+                }
+            }
+            __syncthreads();
+            if (acc_out)
+                for (int i = tid; i < W; i += TD_FIN_THREADS) acc_out[(e * P + p) * W + i] = s_cc[i];
+            if (tid < 64) {
+                // ── the first maximum over |tau| <= max_lag (entries 1 .. 2 max_lag + 1 of s_cc), ascending ──
+                float best = -INFINITY, low = INFINITY;
+                int at = 0x7fffffff;
+                for (int i = 1 + tid; i <= 2 * ML + 1; i += 64) {
+                    const float v = s_cc[i];
+                    if (v > best) { best = v; at = i; }
+                    low = fminf(low, v);
+                }
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) {
+                    const float ob = __shfl_xor(best, o, 64), ol = __shfl_xor(low, o, 64);
+                    const int oa = __shfl_xor(at, o, 64);
+                    if (ob > best || (ob == best && oa < at)) { best = ob; at = oa; }
+                    low = fminf(low, ol);
+                }
+                if (tid == 0) {
+                    // digital silence: every lag is 0, the answer is lag 0 (and NaN samples, which compare with nothing, stay in range)
+                    if ((best == 0.f && low == 0.f) || at > 2 * ML + 1) at = ML + 1;
+                    const double l = s_cc[at - 1], m = s_cc[at], rr = s_cc[at + 1];
+                    const double den = l - 2.0 * m + rr;
+                    double lag = (double)(at - ML - 1);
+                    if (den < 0.0) lag += 0.5 * (l - rr) / den;
+                    lag_out[e * P + p] = (float)lag;
+                    strength_out[e * P + p] = (float)(m / (double)nf);
+                }
+            }
+            __syncthreads();                                     // S and the lags may be overwritten by the next pair
+        }
+    }
+}
+
+// LDS of the accumulate kernel for C channels with `batch` pairs of accumulators resident and 1 or 2 spectra buffers
+size_t tdoa_lds_bytes(int C, int batch, int buffers) {
+    return ((size_t)TD_TAB_WORDS + (size_t)buffers * C * TD_SPEC * 2 + (size_t)((C + 1) / 2) * TD_FFT_SCR + (size_t)batch * TD_SPEC * 2) * sizeof(float);
+}
+
+// bytes of sample_off [R*C] and n_samples [R] (64-bit), rounded to 16
+size_t tdoa_table_bytes(int R, int channels) { return (((size_t)R * channels + R) * sizeof(long) + 15) & ~(size_t)15; }
+
+// chunk slots per event: no event is located on more than min(max_frames, the longest recording's frames) frames
+long tdoa_chunks_per_event(long max_rec_frames, int max_frames) {
+    const long f = max_rec_frames < max_frames ? max_rec_frames : max_frames;
+    return (f + TD_CHUNK - 1) / TD_CHUNK;
+}
+
+}  // namespace
+
+// workspace: sample_off [R*C] and n_samples [R], then, for every event, chunks_per_event x P rows of 1026 float2
+extern "C" size_t sed_event_tdoa_workspace_bytes(int R, int channels, long E, long max_n_samples, int hop, int max_frames) {
+    if (R < 1 || channels < 2 || channels > TD_MAX_CH || E < 0 || max_n_samples < 1 || hop < 1 || max_frames < 1) return 0;
+    const int P = channels * (channels - 1) / 2;
+    const long cpe = tdoa_chunks_per_event(1 + max_n_samples / hop, max_frames);
+    return tdoa_table_bytes(R, channels) + (size_t)E * cpe * P * TD_ROW_BYTES;
+}
+
+extern "C" int sed_event_tdoa(const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const void* tables,
+                              size_t tables_bytes, const int* ev_rec, const int* ev_onset, const int* ev_offset,
+                              const int* ev_peak_frame, long E, int time_factor, int hop, int pad_mode, int max_lag, int max_frames,
+                              float* lag_out, float* strength_out, int* frames_out, float* acc_out, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    SED_REQUIRE(channels >= 2 && channels <= TD_MAX_CH, "event_tdoa: 2 to %d channels, got %d", TD_MAX_CH, channels);
+    SED_REQUIRE(max_lag >= 1 && max_lag <= TD_MAX_LAG, "event_tdoa: max_lag must be in [1,%d], got %d", TD_MAX_LAG, max_lag);
+    SED_REQUIRE(max_frames >= 1, "event_tdoa: max_frames must be >= 1, got %d", max_frames);
+    SED_REQUIRE(time_factor >= 1 && hop >= 1 && R >= 1 && E >= 0, "event_tdoa: bad sizes (time_factor=%d, hop=%d, R=%d, E=%ld)",
+                time_factor, hop, R, E);
+    SED_REQUIRE(pad_mode == 0 || pad_mode == 1, "event_tdoa: pad_mode must be 0 (constant) or 1 (reflect), got %d", pad_mode);
+    SED_REQUIRE(pcm && clips_host && tables && pcm_len > 0, "event_tdoa: null pointer");
+    SED_REQUIRE(tables_bytes % 16 == 0 && tables_bytes / 4 >= (size_t)TD_TAB_WORDS, "event_tdoa: table blob of %zu bytes is malformed", tables_bytes);
+    const int P = channels * (channels - 1) / 2;
+
+    // the recordings: bounds and equal channel lengths, on the host, before anything is enqueued
+    std::vector<long> h((size_t)R * channels + R);
+    long *soff = h.data(), *slen = soff + (size_t)R * channels, longest = 0;
+    for (int r = 0; r < R; ++r) {
+        const long n0 = clips_host[2 * ((long)r * channels) + 1];
+        for (int ch = 0; ch < channels; ++ch) {
+            const long c = (long)r * channels + ch, o = clips_host[2 * c], n = clips_host[2 * c + 1];
+            SED_REQUIRE(o >= 0 && n >= 1 && o <= pcm_len && n <= pcm_len - o,
+                        "event_tdoa: recording %d, channel %d (offset %ld, %ld samples) is not inside the PCM buffer of %ld samples", r, ch,
+                        o, n, pcm_len);
+            SED_REQUIRE(n == n0, "event_tdoa: recording %d: channel %d has %ld samples, channel 0 has %ld (the channels of a recording "
+                        "must have equal length)", r, ch, n, n0);
+            soff[c] = o;
+        }
+        slen[r] = n0;
+        SED_REQUIRE(1 + n0 / hop <= 0x7fffffffL, "event_tdoa: recording %d has more than 2^31 - 1 feature frames", r);
+        if (n0 > longest) longest = n0;
+    }
+    if (E == 0) return 0;                                        // nothing to launch
+    SED_REQUIRE(ev_onset && ev_offset && ev_peak_frame && lag_out && strength_out && frames_out && workspace,
+                "event_tdoa: null pointer");
+    SED_REQUIRE(ev_rec || R == 1, "event_tdoa: %d recordings need ev_rec", R);
+    SED_REQUIRE(((uintptr_t)workspace & 15) == 0, "event_tdoa: workspace must be 16-byte aligned");
+    const size_t tab = tdoa_table_bytes(R, channels);
+    const long cpe = tdoa_chunks_per_event(1 + longest / hop, max_frames);
+    SED_REQUIRE(cpe <= 0x7fffffffL, "event_tdoa: too many chunks per event");      // (gridDim.x and TdArgs.cpe; frames are < 2^31)
+    const size_t per_event = (size_t)cpe * P * TD_ROW_BYTES;
+    SED_REQUIRE(workspace_bytes >= tab + per_event, "event_tdoa: workspace of %zu bytes, at least %zu needed (one event)", workspace_bytes,
+                tab + per_event);
+    long slice = (long)((workspace_bytes - tab) / per_event);
+    if (slice > E) slice = E;
+    if (slice > 65535) slice = 65535;                            // gridDim.y; the events of a slice (n_ev below) therefore fit an int
+
+    // every pair's accumulator beside two spectra buffers where that fits (C <= 4); else one buffer and as many pairs of
+    // accumulators at a time as LDS holds beside the tables, the C spectra and the FFT scratch
+    const int pipelined = tdoa_lds_bytes(channels, P, 2) <= TD_LDS_MAX;
+    int batch = P;
+    while (!pipelined && batch > 1 && tdoa_lds_bytes(channels, batch, 1) > TD_LDS_MAX) --batch;
+    const size_t lds = tdoa_lds_bytes(channels, batch, pipelined ? 2 : 1);
+    SED_REQUIRE(lds <= TD_LDS_MAX, "event_tdoa: %d spectra and the tables (%zu B) exceed the 160 KiB LDS", channels, lds);
+
+    hipStream_t s = as_stream(stream);
+    hipError_t err = hipMemcpyAsync(workspace, h.data(), h.size() * sizeof(long), hipMemcpyHostToDevice, s);
+    if (err != hipSuccess) { sed_set_error("event_tdoa: upload of the recording table: %s", hipGetErrorString(err)); return (int)err; }
+    err = hipFuncSetAttribute((const void*)tdoa_accum_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TD_LDS_MAX);
+    if (err != hipSuccess) { sed_set_error("event_tdoa: hipFuncSetAttribute: %s", hipGetErrorString(err)); return (int)err; }
+    const long* dl = (const long*)workspace;
+    float2* part = (float2*)((char*)workspace + tab);
+    for (long e0 = 0; e0 < E; e0 += slice) {
+        const int n_ev = (int)(E - e0 < slice ? E - e0 : slice);
+        TdArgs ta{dl, dl + (size_t)R * channels, ev_rec, ev_onset, ev_offset, ev_peak_frame, R, channels, P, batch,
+                  time_factor, hop, max_frames, max_lag, (int)cpe, pipelined, e0, n_ev};
+        tdoa_accum_k<<<dim3((unsigned)cpe, (unsigned)n_ev), TD_THREADS, lds, s>>>(pcm, (const uint32_t*)tables, part, pad_mode, ta);
+        SED_LAUNCH_CHECK("event_tdoa (accumulate)");
+        const int blocks = n_ev < 2048 ? n_ev : 2048;
+        tdoa_finish_k<<<blocks, TD_FIN_THREADS, 0, s>>>((const uint32_t*)tables, part, lag_out, strength_out, frames_out, acc_out, ta);
+        SED_LAUNCH_CHECK("event_tdoa (finish)");
+    }
+    return 0;
+}

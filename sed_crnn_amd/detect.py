@@ -26,6 +26,7 @@ from .data import SEQ_LEN_IN
 from .model import HipCRNN
 
 _EVENT_KEYS = ("cls", "onset", "offset", "peak", "peak_frame")
+_TDOA_KEYS = ("lag", "strength", "loc_frames")          # added to the events of a localising detector
 
 
 def _is_per_class(v):
@@ -220,8 +221,9 @@ class DetectionResult:
     """``probs`` [n_out, K] device track; ``events`` dict of device tensors (``cls``, ``onset``, ``offset``, ``peak_frame``
     int32 output frames, offset exclusive; ``peak`` float32), sorted by (class, onset); ``frame_seconds`` = tf*hop_length/sr."""
 
-    def __init__(self, probs, events, frame_seconds, plan):
+    def __init__(self, probs, events, frame_seconds, plan, sr=None):
         self.probs, self.events, self.frame_seconds, self.plan = probs, events, frame_seconds, plan
+        self.sr = sr                            # the detector's rate: set on located results (lags are in samples at that rate)
 
     def __len__(self):
         return int(self.events["cls"].numel())
@@ -230,6 +232,16 @@ class DetectionResult:
         """[(start_s, end_s, peak), ...] of class ``k`` on the host (seconds = frame * tf * hop_length / sr)."""
         return _intervals(self.events, self.frame_seconds, k)
 
+    def tdoa(self, k=None):
+        """time differences of arrival in seconds, a host array [E_k, P] (events of class ``k``; None: all events, in event
+        order), one column per microphone pair (i, j), i < j in lexicographic order; channel j hearing the sound ``d`` seconds
+        after channel i gives ``-d``.  Only on the result of a localising detector (``EventDetector(..., localize=TDOA())``)."""
+        if "lag" not in self.events or self.sr is None:
+            raise ValueError("this result holds no lags: detect with EventDetector(..., localize=sed.TDOA(...)) or pass it through "
+                             "det.localize(result, waveform, ...)")
+        lag = self.events["lag"].cpu().numpy().astype(np.float64) / float(self.sr)
+        return lag if k is None else lag[self.events["cls"].cpu().numpy() == int(k)]
+
 
 class BatchDetectionResult:
     """R recordings detected together.  ``len()`` = R; ``res[i]`` = a DetectionResult view of recording i (its slice of the
@@ -237,9 +249,10 @@ class BatchDetectionResult:
     ``events`` dict of device tensors with ``rec`` (sorted by recording, class, onset), and the host lists ``out_offsets``
     [R+1] (recording i = rows [out_offsets[i], out_offsets[i+1])) and ``event_offsets`` [R+1]."""
 
-    def __init__(self, probs, events, frame_seconds, plans, out_offsets, event_offsets):
+    def __init__(self, probs, events, frame_seconds, plans, out_offsets, event_offsets, sr=None):
         self.probs, self.events, self.frame_seconds, self.plans = probs, events, frame_seconds, tuple(plans)
         self.out_offsets, self.event_offsets = list(out_offsets), list(event_offsets)
+        self.sr = sr                            # as in DetectionResult
 
     def __len__(self):
         return len(self.plans)
@@ -251,8 +264,8 @@ class BatchDetectionResult:
         i = int(i) % R
         o0, o1 = self.out_offsets[i], self.out_offsets[i + 1]
         e0, e1 = self.event_offsets[i], self.event_offsets[i + 1]
-        return DetectionResult(self.probs[o0:o1], {k: self.events[k][e0:e1] for k in _EVENT_KEYS}, self.frame_seconds,
-                               self.plans[i])
+        keys = _EVENT_KEYS + tuple(k for k in _TDOA_KEYS if k in self.events)
+        return DetectionResult(self.probs[o0:o1], {k: self.events[k][e0:e1] for k in keys}, self.frame_seconds, self.plans[i], self.sr)
 
     def __iter__(self):
         return (self[i] for i in range(len(self)))
@@ -278,11 +291,15 @@ class EventDetector:
     them on the device; ``mean`` / ``std`` are ``in_channels * n_mels`` wide.  ``compress=sed.PCEN(...)``: the net
     was trained on PCEN features — every waveform entry point (``det(...)``, ``detect_many``, ``stream``) makes the mel columns
     with ``feature.mbe(..., compress=)`` and ``mean`` / ``std`` are the scaler of such features; ``from_features*`` and
-    ``push_features`` take finished features and apply nothing."""
+    ``push_features`` take finished features and apply nothing.  ``localize=sed.TDOA(max_lag, max_frames)``: for a
+    net that reads at least 2 audio channels, ``det(wave, sr=, channels=C)`` and ``detect_many`` keep the resampled planar PCM
+    until the decode is done and return events that also hold ``lag`` [E, P] (samples at the detector's rate, one column per
+    microphone pair; ``result.tdoa()`` in seconds), ``strength`` [E, P] and ``loc_frames`` [E] (``feature.event_tdoa``);
+    ``from_features*`` has no audio and returns un-located events, which ``det.localize(result, waveform, ...)`` locates."""
 
     def __init__(self, model, seq_len=SEQ_LEN_IN, hop=None, combine="mean", trim=0, threshold=0.5, low=None, median=1,
                  min_gap=0, min_len=1, mean=None, std=None, sr=feature.SR, hop_length=feature.HOP, max_batch=1024, spatial=None,
-                 compress=None):
+                 compress=None, localize=None):
         if not isinstance(model, HipCRNN):
             raise TypeError(f"EventDetector needs a sed_crnn_amd net, got {type(model).__name__}")
         feature._check_compress(compress)
@@ -299,6 +316,13 @@ class EventDetector:
                                  f"the net has in_channels={model.in_channels}")
             if model.n_mels % 2:
                 raise ValueError(f"spatial={spatial!r} writes n_mels lags per pair and needs an even count, the net has n_mels={model.n_mels}")
+        from .localize import TDOA
+        if localize is not None and not isinstance(localize, TDOA):
+            raise TypeError(f"localize must be None or a TDOA(...) settings object, got {type(localize).__name__}")
+        if localize is not None and not 2 <= self.audio_channels <= feature.GCC_MAX_CHANNELS:
+            raise ValueError(f"localize= needs a net that reads 2 to {feature.GCC_MAX_CHANNELS} audio channels (one time difference per "
+                             f"microphone pair), this one reads {self.audio_channels}")
+        self.localize_settings = localize                    # per-event TDOA settings of the waveform entry points, or None
         if combine not in ("mean", "max"):
             raise ValueError(f"combine must be 'mean' or 'max', got {combine!r}")
         K = model.dense[-1]
@@ -354,6 +378,9 @@ class EventDetector:
     def stream(self, n_streams, keep_probs=False, **kw):
         """a ``stream.StreamDetector`` for ``n_streams`` live feeds with this detector's settings; ``input_sr`` /
         ``input_channels``: what ``push`` receives"""
+        if self.localize_settings is not None:
+            raise NotImplementedError("live feeds are not localised: when a stream's event becomes final the PCM of its frames is "
+                                      "gone (DESIGN 5o); use a detector without localize= for det.stream(...)")
         from .stream import StreamDetector
         return StreamDetector(self.model, n_streams, keep_probs=keep_probs, _det=self, **kw)
 
@@ -391,7 +418,7 @@ class EventDetector:
         kw.update(settings)
         return EventDetector(self.model, seq_len=self.seq_len, hop=self.hop, combine=self.combine, trim=self.trim, mean=self.mean,
                              std=self.std, sr=self.sr, hop_length=self.hop_length, max_batch=self.max_batch, spatial=self.spatial,
-                             compress=self.compress, **kw)
+                             compress=self.compress, localize=self.localize_settings, **kw)
 
     def sweep(self, track, ref, grid, collar=1, offset_collar=None, offset_percent=None, block=None, max_workspace_bytes=1 << 30):
         """Score every decoder setting of ``grid`` (a ``DecoderGrid``) on a track against ``ref`` (a ``ReferenceEvents``) on
@@ -433,6 +460,11 @@ class EventDetector:
             self._check_model()
             dev = self.model.flat_parameters().device
             with torch.no_grad():
+                if self.localize_settings is not None:       # the same front end, whose planar PCM is kept until the events are decoded
+                    mel, _, pcm, clips = feature.mbe_many([waveform], sr=self.sr, hop=self.hop_length, n_mels=self.model.n_mels,
+                                                          mean=self.mean, std=self.std, input_sr=sr, channels=channels, keep_channels=True,
+                                                          device=dev, spatial=self.spatial, compress=self.compress, return_pcm=True)
+                    return self._located(self.from_features(mel), pcm, clips)
                 mel = feature.mbe(waveform, sr=self.sr, hop=self.hop_length, n_mels=self.model.n_mels, mean=self.mean, std=self.std,
                                   input_sr=sr, channels=channels, keep_channels=True, device=dev, spatial=self.spatial,
                                   compress=self.compress)
@@ -462,8 +494,53 @@ class EventDetector:
                              f"there is no mix-down to fewer channels and no duplication of a mono signal (scaled features go "
                              f"through from_features)")
 
+    # ── where the events came from ──
+    def _located(self, result, pcm, clips):
+        """``result``, MODIFIED IN PLACE and returned, with ``lag``, ``strength`` and ``loc_frames`` added to its events (a new dict)
+        and ``sr`` set: ``feature.event_tdoa`` on the planar PCM at the detector's rate that the events were detected in"""
+        t = self.localize_settings
+        with torch.no_grad():
+            loc = feature.event_tdoa(pcm, clips, self.audio_channels, result.events, self.model.time_factor, max_lag=t.max_lag,
+                                     max_frames=t.max_frames, hop=self.hop_length)
+        result.events = {**{k: v for k, v in result.events.items() if k not in _TDOA_KEYS}, **loc}
+        result.sr = self.sr
+        return result
+
+    def localize(self, result, waveforms, sr=None, channels=None):
+        """Locate events that were detected without their audio at hand (``from_features*``): ``result`` — a DetectionResult with
+        the ``[N, C]`` waveform it came from, or a BatchDetectionResult with the list of them — gets ``lag``, ``strength`` and
+        ``loc_frames`` (class docstring): the object that was passed in is modified (its ``events`` becomes a new dict with the
+        three keys, its ``sr`` is set) and returned.  ``sr`` / ``channels``: as in ``__call__``; the audio is resampled to
+        the detector's rate exactly as the waveform entry points do it, so the result equals theirs bit for bit.  Needs a
+        detector made with ``localize=sed.TDOA(...)``."""
+        if self.localize_settings is None:
+            raise ValueError("this detector has no localisation settings: make it with EventDetector(..., localize=sed.TDOA(...))")
+        channels = self.audio_channels if channels is None else channels
+        self._check_channels(channels)
+        self._check_model()
+        batch = isinstance(result, BatchDetectionResult)
+        if not batch and not isinstance(result, DetectionResult):
+            raise TypeError(f"localize takes a DetectionResult or a BatchDetectionResult, got {type(result).__name__}")
+        waves = list(waveforms) if batch else [waveforms]
+        if len(waves) != (len(result) if batch else 1):
+            raise ValueError(f"the result holds {len(result)} recordings, {len(waves)} waveforms were given")
+        if not waves:
+            result.events = {**result.events, **self._no_lags()}
+            result.sr = self.sr
+            return result
+        from .resample import resample_many
+        pcm, clips = resample_many(waves, self.sr if sr is None else sr, self.sr, channels, self.model.flat_parameters().device,
+                                   keep_channels=True)
+        plans = result.plans if batch else (result.plan,)
+        for i, p in enumerate(plans):
+            n_feat = 1 + clips[i * int(channels)][1] // self.hop_length
+            if n_feat != p.n_frames:
+                raise ValueError(f"recording {i}: the waveform makes {n_feat} feature frames, the result was detected in {p.n_frames}")
+        return self._located(result, pcm, clips)
+
     def from_features(self, mel):
-        """Scaled features [N, C*F] (the .npz cache layout; channel c = columns [c*F, (c+1)*F)) -> DetectionResult."""
+        """Scaled features [N, C*F] (the .npz cache layout; channel c = columns [c*F, (c+1)*F)) -> DetectionResult.  There is no
+        audio here: the events of a localising detector come back un-located (``det.localize`` adds the lags)."""
         self._check_model()
         with torch.no_grad():
             mel, plan = self._prepare(mel)
@@ -611,14 +688,16 @@ class EventDetector:
             return self._empty_batch()
         dev = m.flat_parameters().device
         with torch.no_grad():
-            mel, _ = feature.mbe_many(waves, sr=self.sr, hop=self.hop_length, n_mels=m.n_mels, mean=self.mean, std=self.std,
-                                      device=dev, compress=self.compress, **(dict(input_sr=rates, channels=channels) if front else {}),
-                                      **(dict(keep_channels=True, spatial=self.spatial) if multi else {}))
-            return self._detect_packed(mel, bp)
+            mel, _, *kept = feature.mbe_many(waves, sr=self.sr, hop=self.hop_length, n_mels=m.n_mels, mean=self.mean, std=self.std,
+                                             device=dev, compress=self.compress, **(dict(input_sr=rates, channels=channels) if front else {}),
+                                             **(dict(keep_channels=True, spatial=self.spatial) if multi else {}),
+                                             **(dict(return_pcm=True) if self.localize_settings is not None else {}))
+            res = self._detect_packed(mel, bp)
+            return self._located(res, *kept) if self.localize_settings is not None else res
 
     def from_features_many(self, mels):
-        """A list of scaled features [N_r, C*F] (any channel count, host or device) -> BatchDetectionResult.  The features
-        are packed back to back; every window of every recording goes through the chunked eval forward, then ONE stitch
+        """A list of scaled features [N_r, C*F] (any channel count, host or device) -> BatchDetectionResult (un-located, as
+        ``from_features``).  The features are packed back to back; every window of every recording goes through the chunked eval forward, then ONE stitch
         launch and ONE decode; the host reads the R+1 event offsets once at the end (see ``detect_many`` for the memory)."""
         m = self.model
         CF = m.in_channels * m.n_mels
@@ -639,7 +718,16 @@ class EventDetector:
         m = self.model
         dev = m.flat_parameters().device
         ev = _event_tensors(("rec",) + _EVENT_KEYS, 0, dev)
-        return BatchDetectionResult(torch.empty(0, m.dense[-1], device=dev), ev, self.frame_seconds, (), [0], [0])
+        if self.localize_settings is not None:
+            ev.update(self._no_lags())
+        return BatchDetectionResult(torch.empty(0, m.dense[-1], device=dev), ev, self.frame_seconds, (), [0], [0],
+                                    self.sr if self.localize_settings is not None else None)
+
+    def _no_lags(self):
+        """the three localisation columns of an empty event table"""
+        dev, P = self.model.flat_parameters().device, self.audio_channels * (self.audio_channels - 1) // 2
+        return {"lag": torch.empty(0, P, device=dev), "strength": torch.empty(0, P, device=dev),
+                "loc_frames": torch.empty(0, dtype=torch.int32, device=dev)}
 
     def _detect_packed(self, mel, bp):
         logits = self.window_logits_many(mel, bp)

@@ -422,6 +422,76 @@ def mbe_planar(pcm, clips, channels, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, 
     return out, rows
 
 
+def event_tdoa(pcm, clips, channels, events, time_factor, max_lag=24, max_frames=256, hop=HOP, pad_mode="constant",
+               return_curve=False, max_workspace_bytes=128 << 20):
+    """Per-event time difference of arrival (``sed_event_tdoa``).  ``pcm`` / ``clips`` / ``channels``: R recordings of
+    2..8 planar channels in one float32 CUDA buffer, as ``mbe_planar`` takes them.  ``events``: a dict of int32 device tensors
+    ``onset``, ``offset`` (exclusive), ``peak_frame`` in output frames of ``time_factor`` feature frames, as the decoders return
+    them, with ``rec`` when R > 1.  For every event and microphone pair p = (i, j), i < j in lexicographic order, the GCC-PHAT of
+    the event's frames (``localize.event_frames``: all of them up to ``max_frames``, else ``max_frames`` around the peak) is
+    accumulated and searched over ``|tau| <= max_lag`` -> a dict of device tensors: ``lag`` float32 [E, P] in samples at the
+    PCM's rate (channel j = channel i delayed by d samples gives -d; seconds = lag / sr), ``strength`` float32 [E, P] in [-1, 1]
+    (the accumulated correlation at the peak per frame), ``loc_frames`` int32 [E] (0: the event names no recording or lies
+    beyond its end; its lag and strength are 0), and with ``return_curve=True`` ``acc`` float32 [E, P, 2*max_lag + 3], the
+    accumulated correlation at lags -(max_lag+1) .. max_lag+1.  The partial sums of at most ``max_workspace_bytes`` worth of
+    events are held at a time; the slicing changes no bit, and neither do the other events, the batch or the clip's place in
+    the buffer.  The host reads nothing back.  The cost is per located frame (every event transforms its own frames: 21 ns per
+    frame at 4 channels on an MI355X): for an event table that covers its recordings more than about five times over — many
+    long, heavily overlapping events — ``mbe_planar(..., spatial="gcc_phat")`` with ``n_mels = 2 * (max_lag + 2)`` followed by sums
+    of the GCC columns over each event's rows is the cheaper route."""
+    import ctypes as C
+    from .localize import MAX_LAG_LIMIT
+    if not (isinstance(pcm, torch.Tensor) and pcm.is_cuda and pcm.dim() == 1):
+        raise RuntimeError("sed_crnn_amd.feature.event_tdoa needs a 1-D CUDA(HIP) PCM buffer; there is no CPU fallback")
+    if pad_mode not in ("constant", "reflect"):
+        raise ValueError(f"pad_mode must be 'constant' or 'reflect', got {pad_mode!r}")
+    nc, tf, max_lag, max_frames, hop = int(channels), int(time_factor), int(max_lag), int(max_frames), int(hop)
+    if not 2 <= nc <= GCC_MAX_CHANNELS:
+        raise ValueError(f"event_tdoa needs 2 to {GCC_MAX_CHANNELS} audio channels (one estimate per microphone pair), got channels={nc}")
+    if not 1 <= max_lag <= MAX_LAG_LIMIT or max_frames < 1 or tf < 1 or hop < 1:
+        raise ValueError(f"event_tdoa needs 1 <= max_lag <= {MAX_LAG_LIMIT}, max_frames >= 1, time_factor >= 1 and hop >= 1, got "
+                         f"max_lag={max_lag}, max_frames={max_frames}, time_factor={tf}, hop={hop}")
+    table = np.ascontiguousarray(np.asarray(clips, dtype=np.int64).reshape(-1, 2))
+    if table.shape[0] == 0 or table.shape[0] % nc:
+        raise ValueError(f"{table.shape[0]} clips are not a whole number (>= 1) of recordings of {nc} channels")
+    R = table.shape[0] // nc
+    for i, (o, n) in enumerate(table.tolist()):
+        if n < 1 or o < 0 or o + n > pcm.numel():
+            raise ValueError(f"recording {i // nc}, channel {i % nc} (first sample {o}, {n} samples) is empty or not inside the "
+                             f"buffer of {pcm.numel()} samples")
+        if n != table[i - i % nc, 1]:
+            raise ValueError(f"recording {i // nc}: channel {i % nc} has {n} samples, channel 0 has {int(table[i - i % nc, 1])}")
+    dev = pcm.device
+    col = {}
+    for k in ("onset", "offset", "peak_frame") + (("rec",) if R > 1 else ()):
+        if k not in events:
+            raise ValueError(f"events has no {k!r}" + (f" ({R} recordings need one)" if k == "rec" else ""))
+        col[k] = events[k].to(dev, torch.int32).contiguous()
+    E = col["onset"].numel()
+    if any(v.dim() != 1 or v.numel() != E for v in col.values()):
+        raise ValueError("the event columns must be 1-D and equally long")
+    P, W = nc * (nc - 1) // 2, 2 * max_lag + 3
+    out = {"lag": torch.empty(E, P, device=dev), "strength": torch.empty(E, P, device=dev),
+           "loc_frames": torch.empty(E, dtype=torch.int32, device=dev)}
+    if return_curve:
+        out["acc"] = torch.empty(E, P, W, device=dev)
+    if E == 0:
+        return out
+    pcm = pcm.contiguous().float()
+    tables = _tables(dev.index or 0, SR, NFFT, NB_MEL)                # the window and the twiddles; the mel plan is not read
+    longest = int(table[:, 1].max())
+    need_one = lib().sed_event_tdoa_workspace_bytes(R, nc, 1, longest, hop, max_frames)
+    need_all = lib().sed_event_tdoa_workspace_bytes(R, nc, E, longest, hop, max_frames)
+    if need_one == 0:
+        raise ValueError(f"sed_event_tdoa_workspace_bytes refuses R={R}, channels={nc}, hop={hop}, max_frames={max_frames}")
+    ws = torch.empty(min(need_all, max(need_one, int(max_workspace_bytes))), dtype=torch.uint8, device=dev)
+    check(lib().sed_event_tdoa(ptr(pcm), pcm.numel(), C.c_void_p(table.ctypes.data), R, nc, ptr(tables), tables.numel() * 4,
+                               ptr(col.get("rec")), ptr(col["onset"]), ptr(col["offset"]), ptr(col["peak_frame"]), E, tf, hop,
+                               {"constant": 0, "reflect": 1}[pad_mode], max_lag, max_frames, ptr(out["lag"]), ptr(out["strength"]),
+                               ptr(out["loc_frames"]), ptr(out.get("acc")), ptr(ws), ws.numel(), stream_ptr()), "sed_event_tdoa")
+    return out
+
+
 def pack_clips(waves, device):
     """a list of 1-D clips (host arrays or tensors, any device) -> (one float32 buffer on ``device``, [(first sample, n), ...]);
     every clip starts on a 16-byte boundary.  Host clips travel in one copy, device clips are joined by one torch.cat."""
@@ -445,7 +515,7 @@ def pack_clips(waves, device):
 
 
 def mbe_many(waves, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, pad_mode="constant", mean=None, std=None, tables=None,
-             device=None, input_sr=None, channels=1, keep_channels=False, spatial=None, compress=None):
+             device=None, input_sr=None, channels=1, keep_channels=False, spatial=None, compress=None, return_pcm=False):
     """``mbe`` of every clip in a list of 1-D clips (host or device; ``device`` defaults to the first CUDA clip's, else
     cuda:current) in one launch -> (features [sum_r (1 + n_r//hop), n_mels] in clip order, row offsets [R+1] host list).
     Bit for bit ``torch.cat([mbe(w) for w in waves])``.  ``input_sr`` (one rate, or one per clip) / ``channels``: as in
@@ -453,9 +523,12 @@ def mbe_many(waves, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, pad_mode="constan
     ``keep_channels=True``: every clip is ``[N, channels]`` and its channels are kept -> features ``[.., channels*n_mels]``
     (``mbe_planar``; the resampler writes the planar channels of every clip straight into the buffer that launch reads).
     ``spatial="gcc_phat"``: as in ``mbe_planar`` — bit for bit the per-recording calls.  ``compress=PCEN(...)``: as in ``mbe``;
-    one ``sed_pcen`` call for all clips, bit for bit the per-clip calls."""
+    one ``sed_pcen`` call for all clips, bit for bit the per-clip calls.  ``return_pcm=True`` (with ``keep_channels=True``): also
+    the resampled planar PCM the features were made from -> (features, row offsets, pcm, clips), what ``event_tdoa`` reads."""
     _check_spatial(spatial, keep_channels, channels)
     _check_compress(compress)
+    if return_pcm and not keep_channels:
+        raise ValueError("return_pcm=True needs keep_channels=True: it returns the planar channels of every recording")
     waves = list(waves)
     if device is None:
         device = next((w.device for w in waves if isinstance(w, torch.Tensor) and w.is_cuda), None)
@@ -466,8 +539,9 @@ def mbe_many(waves, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, pad_mode="constan
             if len(w) < 1:
                 raise ValueError(f"clip {i} is empty")
         pcm, clips = resample_many(waves, sr if input_sr is None else input_sr, sr, channels, device, keep_channels=True)
-        return mbe_planar(pcm, clips, channels, sr=sr, n_fft=n_fft, hop=hop, n_mels=n_mels, pad_mode=pad_mode, mean=mean, std=std,
-                          tables=tables, spatial=spatial, compress=compress)
+        out = mbe_planar(pcm, clips, channels, sr=sr, n_fft=n_fft, hop=hop, n_mels=n_mels, pad_mode=pad_mode, mean=mean, std=std,
+                         tables=tables, spatial=spatial, compress=compress)
+        return out + (pcm, clips) if return_pcm else out
     if input_sr is not None and np.ndim(input_sr) > 0 or any(_needs_front_end(w, input_sr, sr, channels) for w in waves):
         from .resample import resample_many
         pcm, clips = resample_many(waves, sr if input_sr is None else input_sr, sr, channels, device)

@@ -169,6 +169,9 @@ class StreamDetector:
     def __init__(self, model, n_streams, keep_probs=False, max_new_windows=4, _det=None, input_sr=None, input_channels=None, **kw):
         self.det = _det if _det is not None else EventDetector(model, **kw)
         det, m = self.det, self.det.model
+        if det.localize_settings is not None:
+            raise NotImplementedError("live feeds are not localised: when a stream's event becomes final the PCM of its frames is "
+                                      "gone (DESIGN 5o); make the StreamDetector without localize=")
         S = int(n_streams)
         if not 1 <= S <= 65535 or not 1 <= int(max_new_windows) <= 1024:
             raise ValueError(f"need 1 <= n_streams <= 65535 and 1 <= max_new_windows <= 1024, got {n_streams}, {max_new_windows}")
