@@ -506,6 +506,32 @@ int sed_event_tdoa(const float* pcm, long pcm_len, const long* clips_host, int R
                    size_t tables_bytes, const int* ev_rec, const int* ev_onset, const int* ev_offset, const int* ev_peak_frame,
                    long E, int time_factor, int hop, int pad_mode, int max_lag, int max_frames, float* lag_out, float* strength_out,
                    int* frames_out, float* acc_out, void* workspace, size_t workspace_bytes, void* stream);
+/* Live feeds: every planar lane of a stream keeps its last cap samples in a ring, ring [lanes][cap] float, sample i
+ * of the lane (counted from the start of the feed) at ring[lane*cap + i % cap].
+ * sed_stream_ring_write scatters a round's new samples into the rings in one launch.  table_host: HOST long [lanes][3] = {first
+ * sample in src, count, absolute index of the first sample}, validated before anything is enqueued: 0 <= count <= cap (so no
+ * entry is written twice), the source range inside src [src_len], cap a multiple of 4 (the lanes stay 16-byte aligned),
+ * lanes * cap <= ring_len.  All counts 0: nothing is launched.  workspace: >= sed_stream_ring_write_workspace_bytes(lanes)
+ * (0 = lanes outside 1..65535).  The host reads nothing back.
+ * sed_event_tdoa_ring is sed_event_tdoa with recording r = feed r, its channels the rings (r*channels + ch) of cap >= 2048
+ * samples, and n_host: HOST long [R], the samples feed r has received so far.  Absolute sample i reads ring[.. + i % cap] when
+ * max(0, n - cap) <= i < n and 0 otherwise (constant padding).  The event's frames [f0, f1) are sed_event_tdoa's with n_feat =
+ * 1 + n/hop; the event gets 0 frames, lag 0 and strength 0, and reads nothing, when in addition
+ *   offset*time_factor + lat_frames - f0 > history_frames   (the stream's rule: it depends on the event and the settings alone), or
+ *   max(0, f0*hop - 1024) < n - cap                         (its first sample has left the ring).
+ * Everything else — the sums and their order, lag, strength, acc, the slicing by workspace size — is sed_event_tdoa's: an event
+ * whose samples are all in the ring gets the bits sed_event_tdoa gives on the linear recording x[0, n), wherever the ring wraps.
+ * ring: 16-byte aligned, R * channels * cap <= ring_len.  workspace: 16-byte aligned, sed_event_tdoa_ring_workspace_bytes(R,
+ * channels, E, cap, hop, max_frames) for all E events at once (0 = bad sizes), at least that of E = 1.  E = 0 launches nothing. */
+size_t sed_stream_ring_write_workspace_bytes(int lanes);
+int sed_stream_ring_write(float* ring, long ring_len, int lanes, long cap, const float* src, long src_len, const long* table_host,
+                          void* workspace, size_t workspace_bytes, void* stream);
+size_t sed_event_tdoa_ring_workspace_bytes(int R, int channels, long E, long cap, int hop, int max_frames);
+int sed_event_tdoa_ring(const float* ring, long ring_len, long cap, const long* n_host, int R, int channels, const void* tables,
+                        size_t tables_bytes, const int* ev_rec, const int* ev_onset, const int* ev_offset, const int* ev_peak_frame,
+                        long E, int time_factor, int hop, int max_lag, int max_frames, int lat_frames, int history_frames,
+                        float* lag_out, float* strength_out, int* frames_out, float* acc_out, void* workspace,
+                        size_t workspace_bytes, void* stream);
 
 /* sed_pcen: per-channel energy normalisation, IN PLACE, of the columns [col0, col0 + W) of x [rows][stride], which
  * hold log-mel values (natural log, as sed_logmel* write them without a scaler); the other columns are not touched.  Every column

@@ -22,6 +22,10 @@
 //                  8-lanes-per-(pair, tau) direct sum against the exact 2048-entry (cos, sin) table, peak and parabola.
 // Every output is therefore summed in ONE order that depends on the event's own samples and frame range alone: not on the
 // other events, the slice, the clip's place in the buffer, the load path or the launch shape.
+//
+// Live feeds: sed_stream_ring_write keeps every lane's last cap samples in a ring, and sed_event_tdoa_ring is the same
+// two launches with tdoa_accum_k<true>, which loads a frame from the ring — directly where it does not wrap, through the guarded
+// loads where it does — and with td_event_range also refusing what the stream's rule or the ring's depth refuses.
 #include <math.h>
 #include <string.h>
 #include <vector>
@@ -52,10 +56,12 @@ struct TdArgs {
     int pipelined;              // two spectra buffers: the FFT of frame f+1 runs beside the whitening of frame f
     long e0;                    // first event of the slice
     int n_ev;                   // events of the slice
+    long cap;                   // > 0: recording r is a live feed, its channel ch the ring of cap samples at (r*C + ch)*cap
+    int lat, hist;              // ... and the stream's latency and history, in feature frames
 };
 
 // The frames [f0, f0 + nf) an event is located on; nf = 0: the event names no recording or lies beyond its end (nothing is read).
-__device__ __forceinline__ void td_event_range(const TdArgs& a, long e, int& rec, long& f0, int& nf) {
+__device__ __forceinline__ void td_linear_range(const TdArgs& a, long e, int& rec, long& f0, int& nf) {
     rec = a.ev_rec ? a.ev_rec[e] : 0;
     f0 = 0; nf = 0;
     if (rec < 0 || rec >= a.R) return;
@@ -73,6 +79,18 @@ __device__ __forceinline__ void td_event_range(const TdArgs& a, long e, int& rec
     f0 = c; nf = a.max_frames;
 }
 
+// ... of a live feed (a.cap > 0, n_samples = the samples received so far): the same range, and no frames either where the
+// stream's rule b*tf + lat - f0 <= history does not hold or where the first sample read is no longer in the ring
+__device__ __forceinline__ void td_event_range(const TdArgs& a, long e, int& rec, long& f0, int& nf) {
+    td_linear_range(a, e, rec, f0, nf);
+    if (a.cap <= 0 || nf == 0) return;
+    const long first = f0 * a.hop - LM_NFFT / 2;
+    if ((long)a.ev_offset[e] * a.tf + a.lat - f0 > a.hist || (first > 0 ? first : 0) < a.n_samples[rec] - a.cap) { f0 = 0; nf = 0; }
+}
+
+// RING: the channels are rings (TdArgs.cap); a frame that does not wrap takes the same 8-byte loads, one that does goes through
+// the guarded loads, and either way the registers hold the same samples: everything after the loads is one code.
+template <bool RING>
 __global__ __launch_bounds__(TD_THREADS) void tdoa_accum_k(const float* __restrict__ pcm, const uint32_t* __restrict__ tables,
                                                            float2* __restrict__ ws, int pad_mode, TdArgs ta) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -122,24 +140,34 @@ __global__ __launch_bounds__(TD_THREADS) void tdoa_accum_k(const float* __restri
             if (wave < nfw && step < n_fr) {
                 // ── the frame of channel 2 wave + half (an odd C: the last half wave repeats channel C-1 and stores the same values) ──
                 const int ch = (2 * wave + half < C) ? 2 * wave + half : C - 1;
-                const float* cpcm = pcm + ta.sample_off[(long)rec * C + ch];
+                const float* cpcm = pcm + (RING ? ((long)rec * C + ch) * ta.cap : ta.sample_off[(long)rec * C + ch]);
                 const long start = frame * ta.hop - LM_NFFT / 2;
-                const bool fast = (ta.hop & 1) == 0 && (reinterpret_cast<uintptr_t>(cpcm) & 7) == 0 && start >= 0 && start + LM_NFFT <= ns;
+                // RING: sample i lives at i % cap while max(0, ns - cap) <= i < ns; `pos` is the frame's first sample in the ring
+                const long kept = RING && ns > ta.cap ? ns - ta.cap : 0;
+                long pos = 0;
+                if (RING) { pos = start % ta.cap; if (pos < 0) pos += ta.cap; }
+                const bool fast = (ta.hop & 1) == 0 && (reinterpret_cast<uintptr_t>(cpcm) & 7) == 0 && start >= kept && start + LM_NFFT <= ns &&
+                                  (!RING || pos + LM_NFFT <= ta.cap);
+                auto sample = [&](int off) -> float {            // sample start + off of the channel, 0 <= off < 2048
+                    if (!RING) return pcm_at(cpcm, start + off, ns, pad_mode);
+                    const long i = start + off, p = pos + off;   // (cap >= 2048: p < 2 cap)
+                    return i >= kept && i < ns ? cpcm[p >= ta.cap ? p - ta.cap : p] : 0.f;
+                };
                 f2 z[32];                                        // z[n] = (x[2n], x[2n+1]): one complex point per VGPR pair
                 if (__all(fast)) {
-                    const f2* src = reinterpret_cast<const f2*>(cpcm + start) + r;
+                    const f2* src = reinterpret_cast<const f2*>(cpcm + (RING ? pos : start)) + r;
 #pragma unroll
                     for (int n1 = 0; n1 < 32; ++n1) z[n1] = src[32 * n1];
-                } else {                                         // edge frames / odd hop / unaligned clips: guarded loads through LDS
+                } else {                                         // edge frames / odd hop / unaligned clips / a frame that wraps: guarded loads through LDS
                     wave_lds_fence();
 #pragma unroll 1
-                    for (int n1 = 0; n1 < 32; ++n1) scr[n1 * 32 + r] = pcm_at(cpcm, start + 64 * n1 + 2 * r, ns, pad_mode);
+                    for (int n1 = 0; n1 < 32; ++n1) scr[n1 * 32 + r] = sample(64 * n1 + 2 * r);
                     wave_lds_fence();
 #pragma unroll
                     for (int n1 = 0; n1 < 32; ++n1) z[n1].x = scr[n1 * 32 + r];
                     wave_lds_fence();
 #pragma unroll 1
-                    for (int n1 = 0; n1 < 32; ++n1) scr[n1 * 32 + r] = pcm_at(cpcm, start + 64 * n1 + 2 * r + 1, ns, pad_mode);
+                    for (int n1 = 0; n1 < 32; ++n1) scr[n1 * 32 + r] = sample(64 * n1 + 2 * r + 1);
                     wave_lds_fence();
 #pragma unroll
                     for (int n1 = 0; n1 < 32; ++n1) z[n1].y = scr[n1 * 32 + r];
@@ -341,6 +369,74 @@ long tdoa_chunks_per_event(long max_rec_frames, int max_frames) {
     return (f + TD_CHUNK - 1) / TD_CHUNK;
 }
 
+// a live feed's table: n [R] (64-bit), rounded to 16 — the rings need no offsets
+size_t tdoa_ring_table_bytes(int R) { return ((size_t)R * sizeof(long) + 15) & ~(size_t)15; }
+
+// What both entries share once their recordings are checked: the argument checks, the upload of the host table `h` (tab bytes
+// of the workspace; linear: sample_off then n_samples, ring: n), and the two launches per slice of the event table.
+// `longest`: samples of the longest recording (ring: the ring's capacity — no located event has more than 1 + cap / hop frames).
+template <bool RING>
+int tdoa_run(const char* who, const float* pcm, const std::vector<long>& h, size_t tab, long longest, long cap, int lat, int hist, int R,
+             int channels, const void* tables, const int* ev_rec, const int* ev_onset, const int* ev_offset, const int* ev_peak_frame,
+             long E, int time_factor, int hop, int pad_mode, int max_lag, int max_frames, float* lag_out, float* strength_out,
+             int* frames_out, float* acc_out, void* workspace, size_t workspace_bytes, void* stream) {
+    const int P = channels * (channels - 1) / 2;
+    SED_REQUIRE(ev_onset && ev_offset && ev_peak_frame && lag_out && strength_out && frames_out && workspace, "%s: null pointer", who);
+    SED_REQUIRE(ev_rec || R == 1, "%s: %d recordings need ev_rec", who, R);
+    SED_REQUIRE(((uintptr_t)workspace & 15) == 0, "%s: workspace must be 16-byte aligned", who);
+    const long cpe = tdoa_chunks_per_event(1 + longest / hop, max_frames);
+    SED_REQUIRE(cpe <= 0x7fffffffL, "%s: too many chunks per event", who);         // (gridDim.x and TdArgs.cpe; frames are < 2^31)
+    const size_t per_event = (size_t)cpe * P * TD_ROW_BYTES;
+    SED_REQUIRE(workspace_bytes >= tab + per_event, "%s: workspace of %zu bytes, at least %zu needed (one event)", who, workspace_bytes,
+                tab + per_event);
+    long slice = (long)((workspace_bytes - tab) / per_event);
+    if (slice > E) slice = E;
+    if (slice > 65535) slice = 65535;                            // gridDim.y; the events of a slice (n_ev below) therefore fit an int
+
+    // every pair's accumulator beside two spectra buffers where that fits (C <= 4); else one buffer and as many pairs of
+    // accumulators at a time as LDS holds beside the tables, the C spectra and the FFT scratch
+    const int pipelined = tdoa_lds_bytes(channels, P, 2) <= TD_LDS_MAX;
+    int batch = P;
+    while (!pipelined && batch > 1 && tdoa_lds_bytes(channels, batch, 1) > TD_LDS_MAX) --batch;
+    const size_t lds = tdoa_lds_bytes(channels, batch, pipelined ? 2 : 1);
+    SED_REQUIRE(lds <= TD_LDS_MAX, "%s: %d spectra and the tables (%zu B) exceed the 160 KiB LDS", who, channels, lds);
+
+    hipStream_t s = as_stream(stream);
+    hipError_t err = hipMemcpyAsync(workspace, h.data(), h.size() * sizeof(long), hipMemcpyHostToDevice, s);
+    if (err != hipSuccess) { sed_set_error("%s: upload of the recording table: %s", who, hipGetErrorString(err)); return (int)err; }
+    err = hipFuncSetAttribute((const void*)tdoa_accum_k<RING>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TD_LDS_MAX);
+    if (err != hipSuccess) { sed_set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(err)); return (int)err; }
+    const long* dl = (const long*)workspace;
+    float2* part = (float2*)((char*)workspace + tab);
+    for (long e0 = 0; e0 < E; e0 += slice) {
+        const int n_ev = (int)(E - e0 < slice ? E - e0 : slice);
+        TdArgs ta{RING ? nullptr : dl, RING ? dl : dl + (size_t)R * channels, ev_rec, ev_onset, ev_offset, ev_peak_frame, R, channels, P,
+                  batch, time_factor, hop, max_frames, max_lag, (int)cpe, pipelined, e0, n_ev, RING ? cap : 0, lat, hist};
+        tdoa_accum_k<RING><<<dim3((unsigned)cpe, (unsigned)n_ev), TD_THREADS, lds, s>>>(pcm, (const uint32_t*)tables, part, pad_mode, ta);
+        SED_LAUNCH_CHECK(RING ? "event_tdoa_ring (accumulate)" : "event_tdoa (accumulate)");
+        const int blocks = n_ev < 2048 ? n_ev : 2048;
+        tdoa_finish_k<<<blocks, TD_FIN_THREADS, 0, s>>>((const uint32_t*)tables, part, lag_out, strength_out, frames_out, acc_out, ta);
+        SED_LAUNCH_CHECK(RING ? "event_tdoa_ring (finish)" : "event_tdoa (finish)");
+    }
+    return 0;
+}
+
+// ───────────────────────── a live feed's PCM ring ─────────────────────────
+// Lane l keeps its last cap samples: sample i (counted from the start of the feed) at ring[l*cap + i % cap].  A round's new
+// samples are at most cap per lane, so no entry is written twice and no thread reads what another writes.
+struct RingRec { long src, count, abs; };
+
+__global__ __launch_bounds__(256) void tdoa_ring_write_k(float* __restrict__ ring, long cap, const float* __restrict__ src,
+                                                         const RingRec* __restrict__ recs) {
+    const RingRec r = recs[blockIdx.y];
+    float* lane = ring + (long)blockIdx.y * cap;
+    const long p0 = r.abs % cap;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < r.count; i += (long)gridDim.x * 256) {
+        const long p = p0 + i;                                   // (count <= cap: p < 2 cap)
+        lane[p >= cap ? p - cap : p] = src[r.src + i];
+    }
+}
+
 }  // namespace
 
 // workspace: sample_off [R*C] and n_samples [R], then, for every event, chunks_per_event x P rows of 1026 float2
@@ -364,7 +460,6 @@ extern "C" int sed_event_tdoa(const float* pcm, long pcm_len, const long* clips_
     SED_REQUIRE(pad_mode == 0 || pad_mode == 1, "event_tdoa: pad_mode must be 0 (constant) or 1 (reflect), got %d", pad_mode);
     SED_REQUIRE(pcm && clips_host && tables && pcm_len > 0, "event_tdoa: null pointer");
     SED_REQUIRE(tables_bytes % 16 == 0 && tables_bytes / 4 >= (size_t)TD_TAB_WORDS, "event_tdoa: table blob of %zu bytes is malformed", tables_bytes);
-    const int P = channels * (channels - 1) / 2;
 
     // the recordings: bounds and equal channel lengths, on the host, before anything is enqueued
     std::vector<long> h((size_t)R * channels + R);
@@ -385,44 +480,82 @@ extern "C" int sed_event_tdoa(const float* pcm, long pcm_len, const long* clips_
         if (n0 > longest) longest = n0;
     }
     if (E == 0) return 0;                                        // nothing to launch
-    SED_REQUIRE(ev_onset && ev_offset && ev_peak_frame && lag_out && strength_out && frames_out && workspace,
-                "event_tdoa: null pointer");
-    SED_REQUIRE(ev_rec || R == 1, "event_tdoa: %d recordings need ev_rec", R);
-    SED_REQUIRE(((uintptr_t)workspace & 15) == 0, "event_tdoa: workspace must be 16-byte aligned");
-    const size_t tab = tdoa_table_bytes(R, channels);
-    const long cpe = tdoa_chunks_per_event(1 + longest / hop, max_frames);
-    SED_REQUIRE(cpe <= 0x7fffffffL, "event_tdoa: too many chunks per event");      // (gridDim.x and TdArgs.cpe; frames are < 2^31)
-    const size_t per_event = (size_t)cpe * P * TD_ROW_BYTES;
-    SED_REQUIRE(workspace_bytes >= tab + per_event, "event_tdoa: workspace of %zu bytes, at least %zu needed (one event)", workspace_bytes,
-                tab + per_event);
-    long slice = (long)((workspace_bytes - tab) / per_event);
-    if (slice > E) slice = E;
-    if (slice > 65535) slice = 65535;                            // gridDim.y; the events of a slice (n_ev below) therefore fit an int
+    return tdoa_run<false>("event_tdoa", pcm, h, tdoa_table_bytes(R, channels), longest, 0, 0, 0, R, channels, tables, ev_rec, ev_onset,
+                           ev_offset, ev_peak_frame, E, time_factor, hop, pad_mode, max_lag, max_frames, lag_out, strength_out,
+                           frames_out, acc_out, workspace, workspace_bytes, stream);
+}
 
-    // every pair's accumulator beside two spectra buffers where that fits (C <= 4); else one buffer and as many pairs of
-    // accumulators at a time as LDS holds beside the tables, the C spectra and the FFT scratch
-    const int pipelined = tdoa_lds_bytes(channels, P, 2) <= TD_LDS_MAX;
-    int batch = P;
-    while (!pipelined && batch > 1 && tdoa_lds_bytes(channels, batch, 1) > TD_LDS_MAX) --batch;
-    const size_t lds = tdoa_lds_bytes(channels, batch, pipelined ? 2 : 1);
-    SED_REQUIRE(lds <= TD_LDS_MAX, "event_tdoa: %d spectra and the tables (%zu B) exceed the 160 KiB LDS", channels, lds);
+// ───────────────────────── live feeds ─────────────────────────
+extern "C" size_t sed_stream_ring_write_workspace_bytes(int lanes) {
+    return lanes < 1 || lanes > 65535 ? 0 : (size_t)lanes * sizeof(RingRec);
+}
 
-    hipStream_t s = as_stream(stream);
-    hipError_t err = hipMemcpyAsync(workspace, h.data(), h.size() * sizeof(long), hipMemcpyHostToDevice, s);
-    if (err != hipSuccess) { sed_set_error("event_tdoa: upload of the recording table: %s", hipGetErrorString(err)); return (int)err; }
-    err = hipFuncSetAttribute((const void*)tdoa_accum_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TD_LDS_MAX);
-    if (err != hipSuccess) { sed_set_error("event_tdoa: hipFuncSetAttribute: %s", hipGetErrorString(err)); return (int)err; }
-    const long* dl = (const long*)workspace;
-    float2* part = (float2*)((char*)workspace + tab);
-    for (long e0 = 0; e0 < E; e0 += slice) {
-        const int n_ev = (int)(E - e0 < slice ? E - e0 : slice);
-        TdArgs ta{dl, dl + (size_t)R * channels, ev_rec, ev_onset, ev_offset, ev_peak_frame, R, channels, P, batch,
-                  time_factor, hop, max_frames, max_lag, (int)cpe, pipelined, e0, n_ev};
-        tdoa_accum_k<<<dim3((unsigned)cpe, (unsigned)n_ev), TD_THREADS, lds, s>>>(pcm, (const uint32_t*)tables, part, pad_mode, ta);
-        SED_LAUNCH_CHECK("event_tdoa (accumulate)");
-        const int blocks = n_ev < 2048 ? n_ev : 2048;
-        tdoa_finish_k<<<blocks, TD_FIN_THREADS, 0, s>>>((const uint32_t*)tables, part, lag_out, strength_out, frames_out, acc_out, ta);
-        SED_LAUNCH_CHECK("event_tdoa (finish)");
+extern "C" int sed_stream_ring_write(float* ring, long ring_len, int lanes, long cap, const float* src, long src_len,
+                                     const long* table_host, void* workspace, size_t workspace_bytes, void* stream) {
+    SED_REQUIRE(ring && table_host && workspace, "stream_ring_write: null pointer");
+    const size_t need = sed_stream_ring_write_workspace_bytes(lanes);
+    SED_REQUIRE(need > 0 && cap >= 4 && cap % 4 == 0 && ring_len >= 0 && cap <= ring_len / lanes && src_len >= 0,
+                "stream_ring_write: bad sizes (lanes=%d in 1..65535, cap=%ld a multiple of 4, ring_len=%ld)", lanes, cap, ring_len);
+    SED_REQUIRE(workspace_bytes >= need, "stream_ring_write: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    SED_REQUIRE(src || src_len == 0, "stream_ring_write: null buffer with a non-zero length");
+    std::vector<RingRec> h(lanes);
+    long longest = 0;
+    for (int l = 0; l < lanes; ++l) {
+        const RingRec r{table_host[3 * l], table_host[3 * l + 1], table_host[3 * l + 2]};
+        SED_REQUIRE(r.count >= 0 && r.count <= cap, "stream_ring_write: lane %d: %ld new samples, the ring holds %ld", l, r.count, cap);
+        SED_REQUIRE(r.count == 0 || (r.src >= 0 && r.src <= src_len && r.count <= src_len - r.src),
+                    "stream_ring_write: lane %d: its samples [%ld, +%ld) leave the buffer of %ld", l, r.src, r.count, src_len);
+        SED_REQUIRE(r.abs >= 0 && r.abs <= 0x7fffffffffffffffL - r.count, "stream_ring_write: lane %d: bad first sample index %ld", l, r.abs);
+        h[l] = r;
+        if (r.count > longest) longest = r.count;
     }
+    if (longest == 0) return 0;
+    hipStream_t st = as_stream(stream);
+    const hipError_t err = hipMemcpyAsync(workspace, h.data(), need, hipMemcpyHostToDevice, st);
+    if (err != hipSuccess) { sed_set_error("stream_ring_write: upload of the lane table: %s", hipGetErrorString(err)); return (int)err; }
+    const long nb = (longest + 255) / 256;
+    tdoa_ring_write_k<<<dim3((unsigned)(nb < 1024 ? nb : 1024), (unsigned)lanes), 256, 0, st>>>(ring, cap, src, (const RingRec*)workspace);
+    SED_LAUNCH_CHECK("stream_ring_write");
     return 0;
 }
+
+// workspace: n [R], then, for every event, chunks_per_event x P rows of 1026 float2 (no located event has more than
+// 1 + cap / hop frames: its first sample is still in the ring and its last frame's centre is a sample received)
+extern "C" size_t sed_event_tdoa_ring_workspace_bytes(int R, int channels, long E, long cap, int hop, int max_frames) {
+    if (R < 1 || channels < 2 || channels > TD_MAX_CH || E < 0 || cap < LM_NFFT || cap % 4 || hop < 1 || max_frames < 1) return 0;
+    const int P = channels * (channels - 1) / 2;
+    const long cpe = tdoa_chunks_per_event(1 + cap / hop, max_frames);
+    return tdoa_ring_table_bytes(R) + (size_t)E * cpe * P * TD_ROW_BYTES;
+}
+
+extern "C" int sed_event_tdoa_ring(const float* ring, long ring_len, long cap, const long* n_host, int R, int channels,
+                                   const void* tables, size_t tables_bytes, const int* ev_rec, const int* ev_onset,
+                                   const int* ev_offset, const int* ev_peak_frame, long E, int time_factor, int hop, int max_lag,
+                                   int max_frames, int lat_frames, int history_frames, float* lag_out, float* strength_out,
+                                   int* frames_out, float* acc_out, void* workspace, size_t workspace_bytes, void* stream) {
+    SED_REQUIRE(channels >= 2 && channels <= TD_MAX_CH, "event_tdoa_ring: 2 to %d channels, got %d", TD_MAX_CH, channels);
+    SED_REQUIRE(max_lag >= 1 && max_lag <= TD_MAX_LAG, "event_tdoa_ring: max_lag must be in [1,%d], got %d", TD_MAX_LAG, max_lag);
+    SED_REQUIRE(max_frames >= 1, "event_tdoa_ring: max_frames must be >= 1, got %d", max_frames);
+    SED_REQUIRE(time_factor >= 1 && hop >= 1 && R >= 1 && E >= 0, "event_tdoa_ring: bad sizes (time_factor=%d, hop=%d, R=%d, E=%ld)",
+                time_factor, hop, R, E);
+    SED_REQUIRE(lat_frames >= 0 && history_frames >= 1, "event_tdoa_ring: need lat_frames >= 0 and history_frames >= 1, got %d, %d",
+                lat_frames, history_frames);
+    SED_REQUIRE(ring && n_host && tables, "event_tdoa_ring: null pointer");
+    SED_REQUIRE(cap >= LM_NFFT && cap % 4 == 0, "event_tdoa_ring: a ring holds a multiple of 4 samples and at least one frame of %d, got "
+                "cap=%ld", LM_NFFT, cap);
+    SED_REQUIRE(ring_len >= 0 && cap <= ring_len / ((long)R * channels), "event_tdoa_ring: %d feeds of %d rings of %ld samples leave "
+                "the buffer of %ld", R, channels, cap, ring_len);
+    SED_REQUIRE(((uintptr_t)ring & 15) == 0, "event_tdoa_ring: the rings must be 16-byte aligned");
+    SED_REQUIRE(tables_bytes % 16 == 0 && tables_bytes / 4 >= (size_t)TD_TAB_WORDS, "event_tdoa_ring: table blob of %zu bytes is malformed", tables_bytes);
+    std::vector<long> h(R);
+    for (int r = 0; r < R; ++r) {
+        h[r] = n_host[r];
+        SED_REQUIRE(h[r] >= 0 && 1 + h[r] / hop <= 0x7fffffffL, "event_tdoa_ring: feed %d: %ld samples received (negative, or more than "
+                    "2^31 - 1 feature frames)", r, h[r]);
+    }
+    if (E == 0) return 0;                                        // nothing to launch
+    return tdoa_run<true>("event_tdoa_ring", ring, h, tdoa_ring_table_bytes(R), cap, cap, lat_frames, history_frames, R, channels, tables,
+                          ev_rec, ev_onset, ev_offset, ev_peak_frame, E, time_factor, hop, 0, max_lag, max_frames, lag_out, strength_out,
+                          frames_out, acc_out, workspace, workspace_bytes, stream);
+}
+

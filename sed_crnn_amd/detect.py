@@ -377,10 +377,8 @@ class EventDetector:
 
     def stream(self, n_streams, keep_probs=False, **kw):
         """a ``stream.StreamDetector`` for ``n_streams`` live feeds with this detector's settings; ``input_sr`` /
-        ``input_channels``: what ``push`` receives"""
-        if self.localize_settings is not None:
-            raise NotImplementedError("live feeds are not localised: when a stream's event becomes final the PCM of its frames is "
-                                      "gone (DESIGN 5o); use a detector without localize= for det.stream(...)")
+        ``input_channels``: what ``push`` receives.  A localising detector streams with ``history_frames="min"`` or a
+        number of feature frames: the audio every feed keeps for its emitted events; without it, NotImplementedError."""
         from .stream import StreamDetector
         return StreamDetector(self.model, n_streams, keep_probs=keep_probs, _det=self, **kw)
 

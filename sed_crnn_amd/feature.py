@@ -422,6 +422,25 @@ def mbe_planar(pcm, clips, channels, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, 
     return out, rows
 
 
+def _tdoa_io(events, R, rec_key, nc, max_lag, return_curve, dev):
+    """the event columns of ``event_tdoa`` / ``event_tdoa_ring`` as contiguous int32 device tensors (``rec_key`` names the
+    recording column, needed when R > 1) and the empty outputs -> (columns with the recording under "rec", E, outputs)"""
+    col = {}
+    for k in ("onset", "offset", "peak_frame") + ((rec_key,) if R > 1 else ()):
+        if k not in events:
+            raise ValueError(f"events has no {k!r}" + (f" ({R} recordings need one)" if k == rec_key else ""))
+        col["rec" if k == rec_key else k] = events[k].to(dev, torch.int32).contiguous()
+    E = col["onset"].numel()
+    if any(v.dim() != 1 or v.numel() != E for v in col.values()):
+        raise ValueError("the event columns must be 1-D and equally long")
+    P, W = nc * (nc - 1) // 2, 2 * max_lag + 3
+    out = {"lag": torch.empty(E, P, device=dev), "strength": torch.empty(E, P, device=dev),
+           "loc_frames": torch.empty(E, dtype=torch.int32, device=dev)}
+    if return_curve:
+        out["acc"] = torch.empty(E, P, W, device=dev)
+    return col, E, out
+
+
 def event_tdoa(pcm, clips, channels, events, time_factor, max_lag=24, max_frames=256, hop=HOP, pad_mode="constant",
                return_curve=False, max_workspace_bytes=128 << 20):
     """Per-event time difference of arrival (``sed_event_tdoa``).  ``pcm`` / ``clips`` / ``channels``: R recordings of
@@ -462,19 +481,7 @@ def event_tdoa(pcm, clips, channels, events, time_factor, max_lag=24, max_frames
         if n != table[i - i % nc, 1]:
             raise ValueError(f"recording {i // nc}: channel {i % nc} has {n} samples, channel 0 has {int(table[i - i % nc, 1])}")
     dev = pcm.device
-    col = {}
-    for k in ("onset", "offset", "peak_frame") + (("rec",) if R > 1 else ()):
-        if k not in events:
-            raise ValueError(f"events has no {k!r}" + (f" ({R} recordings need one)" if k == "rec" else ""))
-        col[k] = events[k].to(dev, torch.int32).contiguous()
-    E = col["onset"].numel()
-    if any(v.dim() != 1 or v.numel() != E for v in col.values()):
-        raise ValueError("the event columns must be 1-D and equally long")
-    P, W = nc * (nc - 1) // 2, 2 * max_lag + 3
-    out = {"lag": torch.empty(E, P, device=dev), "strength": torch.empty(E, P, device=dev),
-           "loc_frames": torch.empty(E, dtype=torch.int32, device=dev)}
-    if return_curve:
-        out["acc"] = torch.empty(E, P, W, device=dev)
+    col, E, out = _tdoa_io(events, R, "rec", nc, max_lag, return_curve, dev)
     if E == 0:
         return out
     pcm = pcm.contiguous().float()
@@ -489,6 +496,84 @@ def event_tdoa(pcm, clips, channels, events, time_factor, max_lag=24, max_frames
                                ptr(col.get("rec")), ptr(col["onset"]), ptr(col["offset"]), ptr(col["peak_frame"]), E, tf, hop,
                                {"constant": 0, "reflect": 1}[pad_mode], max_lag, max_frames, ptr(out["lag"]), ptr(out["strength"]),
                                ptr(out["loc_frames"]), ptr(out.get("acc")), ptr(ws), ws.numel(), stream_ptr()), "sed_event_tdoa")
+    return out
+
+
+def ring_write(ring, cap, src, table, workspace=None):
+    """A round's new samples into the PCM rings of live feeds (``sed_stream_ring_write``).  ``ring``: float32 CUDA
+    buffer of ``lanes * cap`` samples, lane l (feed s, channel c: ``s*C + c``) keeps its last ``cap`` samples, sample i of the
+    lane at ``ring[l*cap + i % cap]``; ``src``: the new samples, packed (float32 CUDA, or None when every count is 0);
+    ``table`` [lanes, 3] host ints ``{first sample in src, count <= cap, absolute index of the first sample}``.  One launch;
+    the host reads nothing back.  -> the workspace, for the next call."""
+    import ctypes as C
+    if not (isinstance(ring, torch.Tensor) and ring.is_cuda and ring.dim() == 1 and ring.dtype == torch.float32 and ring.is_contiguous()):
+        raise RuntimeError("sed_crnn_amd.feature.ring_write needs a contiguous 1-D float32 CUDA(HIP) ring buffer; there is no CPU fallback")
+    table = np.ascontiguousarray(np.asarray(table, dtype=np.int64).reshape(-1, 3))
+    lanes, cap = table.shape[0], int(cap)
+    if lanes < 1 or cap < 4 or cap % 4 or lanes * cap > ring.numel():
+        raise ValueError(f"{lanes} lanes of cap={cap} samples (a multiple of 4) do not fit the ring buffer of {ring.numel()} samples")
+    if (table[:, 1] < 0).any() or (table[:, 1] > cap).any():
+        raise ValueError(f"a lane takes 0 to cap={cap} new samples per call, got {int(table[:, 1].min())} .. {int(table[:, 1].max())}")
+    if src is not None:
+        if not (isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.float32):
+            raise RuntimeError("sed_crnn_amd.feature.ring_write needs the new samples as a float32 CUDA(HIP) tensor")
+        src = src.contiguous().view(-1)
+    need = lib().sed_stream_ring_write_workspace_bytes(lanes)
+    if need == 0:
+        raise ValueError(f"sed_stream_ring_write takes 1..65535 lanes, got {lanes}")
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=ring.device)
+    check(lib().sed_stream_ring_write(ptr(ring), ring.numel(), lanes, cap, ptr(src), src.numel() if src is not None else 0,
+                                      C.c_void_p(table.ctypes.data), ptr(workspace), workspace.numel(), stream_ptr()),
+          "sed_stream_ring_write")
+    return workspace
+
+
+def event_tdoa_ring(ring, cap, n, channels, events, time_factor, max_lag=24, max_frames=256, hop=HOP, lat_frames=0,
+                    history_frames=0x7fffffff, return_curve=False, max_workspace_bytes=128 << 20):
+    """``event_tdoa`` on the PCM rings of live feeds (``sed_event_tdoa_ring``).  ``ring`` / ``cap`` as ``ring_write``
+    fills them: feed r's ``channels`` lanes are the rings ``r*channels + c``; ``n`` [R] host ints: the samples feed r has
+    received.  ``events`` as ``event_tdoa`` takes them; the feed of an event is its ``rec`` — or ``stream`` — column (needed
+    when R > 1).  An event is located on ``localize.event_frames`` with ``n_feat = 1 + n // hop`` unless
+    ``offset*tf + lat_frames - f0 > history_frames`` (``localize.stream_locates``: the stream's rule) or its first sample has
+    left the ring (``max(0, f0*hop - 1024) < n - cap``): then ``loc_frames = 0``, ``lag = 0``, ``strength = 0`` and nothing is
+    read.  Samples before the start of the feed and beyond ``n`` read as 0 (constant padding).  A located event gets, bit for
+    bit, what ``event_tdoa`` gives on the feed's samples ``[0, n)`` laid out linearly, wherever the ring wraps.  Returns the
+    dict ``event_tdoa`` returns; the host reads nothing back."""
+    import ctypes as C
+    from .localize import MAX_LAG_LIMIT
+    if not (isinstance(ring, torch.Tensor) and ring.is_cuda and ring.dim() == 1 and ring.dtype == torch.float32 and ring.is_contiguous()):
+        raise RuntimeError("sed_crnn_amd.feature.event_tdoa_ring needs a contiguous 1-D float32 CUDA(HIP) ring buffer; there is no CPU fallback")
+    nc, tf, max_lag, max_frames, hop, cap = int(channels), int(time_factor), int(max_lag), int(max_frames), int(hop), int(cap)
+    lat, hist = int(lat_frames), int(history_frames)
+    if not 2 <= nc <= GCC_MAX_CHANNELS:
+        raise ValueError(f"event_tdoa_ring needs 2 to {GCC_MAX_CHANNELS} audio channels (one estimate per microphone pair), got channels={nc}")
+    if not 1 <= max_lag <= MAX_LAG_LIMIT or max_frames < 1 or tf < 1 or hop < 1 or lat < 0 or hist < 1:
+        raise ValueError(f"event_tdoa_ring needs 1 <= max_lag <= {MAX_LAG_LIMIT}, max_frames >= 1, time_factor >= 1, hop >= 1, lat_frames >= 0 "
+                         f"and history_frames >= 1, got max_lag={max_lag}, max_frames={max_frames}, time_factor={tf}, hop={hop}, "
+                         f"lat_frames={lat}, history_frames={hist}")
+    n = np.ascontiguousarray(np.asarray(n, dtype=np.int64).reshape(-1))
+    R = n.shape[0]
+    if R < 1 or (n < 0).any():
+        raise ValueError(f"n must hold one sample count >= 0 per feed, got {n.tolist()[:8]}")
+    if cap < NFFT or cap % 4 or R * nc * cap > ring.numel():
+        raise ValueError(f"{R} feeds of {nc} rings of cap={cap} samples (a multiple of 4, at least {NFFT}) do not fit the ring buffer of "
+                         f"{ring.numel()} samples")
+    dev = ring.device
+    rec_key = "stream" if "stream" in events and "rec" not in events else "rec"
+    col, E, out = _tdoa_io(events, R, rec_key, nc, max_lag, return_curve, dev)
+    if E == 0:
+        return out
+    tables = _tables(dev.index or 0, SR, NFFT, NB_MEL)                # the window and the twiddles; the mel plan is not read
+    need_one = lib().sed_event_tdoa_ring_workspace_bytes(R, nc, 1, cap, hop, max_frames)
+    need_all = lib().sed_event_tdoa_ring_workspace_bytes(R, nc, E, cap, hop, max_frames)
+    if need_one == 0:
+        raise ValueError(f"sed_event_tdoa_ring_workspace_bytes refuses R={R}, channels={nc}, cap={cap}, hop={hop}, max_frames={max_frames}")
+    ws = torch.empty(min(need_all, max(need_one, int(max_workspace_bytes))), dtype=torch.uint8, device=dev)
+    check(lib().sed_event_tdoa_ring(ptr(ring), ring.numel(), cap, C.c_void_p(n.ctypes.data), R, nc, ptr(tables), tables.numel() * 4,
+                                    ptr(col.get("rec")), ptr(col["onset"]), ptr(col["offset"]), ptr(col["peak_frame"]), E, tf, hop,
+                                    max_lag, max_frames, lat, hist, ptr(out["lag"]), ptr(out["strength"]), ptr(out["loc_frames"]),
+                                    ptr(out.get("acc")), ptr(ws), ws.numel(), stream_ptr()), "sed_event_tdoa_ring")
     return out
 
 

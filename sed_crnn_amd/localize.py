@@ -2,8 +2,10 @@
 entry ``feature.event_tdoa``).
 
 ``event_frames`` is the rule that picks the feature frames an event is located on — the kernels apply the same rule on the
-device.  ``TDOA`` holds the two settings of ``EventDetector(..., localize=TDOA(...))``.  ``max_lag_for`` and ``tdoa_to_azimuth``
-are the far-field geometry of ONE microphone pair; combining pairs into a direction for a given array is left to the caller.
+device.  ``stream_latency_frames``, ``stream_ring_samples`` and ``stream_locates`` are the arithmetic of a localising live
+stream: how late an event is emitted, how many samples a lane keeps, and which events are located.  ``TDOA`` holds
+the two settings of ``EventDetector(..., localize=TDOA(...))``.  ``max_lag_for`` and ``tdoa_to_azimuth`` are the far-field
+geometry of ONE microphone pair; combining pairs into a direction for a given array is left to the caller.
 """
 import dataclasses
 import math
@@ -34,6 +36,35 @@ def event_frames(onset, offset, peak_frame, time_factor, n_feat, max_frames=256)
     c = int(peak_frame) * tf + tf // 2 - max_frames // 2
     f0 = min(max(c, a), b - max_frames)
     return f0, f0 + max_frames
+
+
+# ── live feeds: how long an emitted event's audio must be kept ──
+def stream_latency_frames(time_factor, seq_len, median_max, min_gap_max):
+    """``lat``: the step of a stream that emits the event ``[a, b)`` runs with fewer than ``b*tf + lat + step_frames`` final
+    feature frames, ``lat = (max_k min_gap_k + median_max // 2 + seq_len // tf + 1) * tf`` (more than ``b + min_gap`` decided
+    frames need ``b + min_gap + 1 + median // 2 + seq_len // tf`` output frames)"""
+    tf = int(time_factor)
+    if tf < 1 or int(seq_len) < tf or int(median_max) < 1 or int(min_gap_max) < 0:
+        raise ValueError(f"stream_latency_frames needs time_factor >= 1, seq_len >= time_factor, median_max >= 1 and min_gap_max >= 0, "
+                         f"got {time_factor}, {seq_len}, {median_max}, {min_gap_max}")
+    return (int(min_gap_max) + int(median_max) // 2 + int(seq_len) // tf + 1) * tf
+
+
+def stream_ring_samples(history_frames, step_frames, hop_length, n_fft=2048):
+    """``cap``: samples per lane of a stream's PCM ring, ``roundup4((history_frames + step_frames) * hop_length + n_fft)``: enough
+    for every event that ``stream_locates`` accepts, in any chunking (DESIGN 5p has the proof)"""
+    if int(history_frames) < 1 or int(step_frames) < 1 or int(hop_length) < 1:
+        raise ValueError(f"stream_ring_samples needs history_frames, step_frames and hop_length >= 1, got {history_frames}, "
+                         f"{step_frames}, {hop_length}")
+    return ((int(history_frames) + int(step_frames)) * int(hop_length) + int(n_fft) + 3) & ~3
+
+
+def stream_locates(onset, offset, peak_frame, time_factor, n_feat, max_frames, lat, history_frames):
+    """whether a stream with ``history_frames`` of audio locates this event: it has frames ``[f0, f1) = event_frames(...)`` and
+    ``offset*tf + lat - f0 <= history_frames``.  The rule reads the event and the settings only, never the chunking; an event
+    it refuses comes back with ``loc_frames = 0``, ``lag = 0`` and ``strength = 0``."""
+    f0, f1 = event_frames(onset, offset, peak_frame, time_factor, n_feat, max_frames)
+    return f1 > f0 and int(offset) * int(time_factor) + int(lat) - f0 <= int(history_frames)
 
 
 @dataclasses.dataclass(frozen=True)

@@ -37,6 +37,10 @@ A spatial detector (``EventDetector(..., spatial="gcc_phat")``) keeps
 A detector with ``compress=PCEN(...)`` adds one ``sed_pcen`` call per round over the new rows of all feeds, with
 the feed's feature-frame counter as the absolute frame index; the smoother's state, two floats per feed and mel column, stays
 on the device and is simply ignored when a feed's counter is back at 0 (``flush`` / ``reset`` need nothing more).
+A detector with ``localize=sed.TDOA(...)`` streams when given ``history_frames``: every lane then also keeps its
+last ``cap`` samples in a ring on the device (``sed_stream_ring_write``, one launch per round), and a step that emits events
+locates them from the rings in one ``sed_event_tdoa_ring`` call — an event ``[a, b)`` with frames from ``f0`` iff ``b*tf + lat - f0
+<= history_frames`` (``localize.stream_locates``), with the bits of the offline call; ``flush`` / ``reset`` need no ring work either.
 """
 import ctypes as C
 
@@ -45,7 +49,7 @@ import torch
 
 from . import feature
 from ._lib import SedHipError, check, lib, ptr, stream_ptr
-from .detect import EventDetector, _event_tensors, _intervals, _timed, _window_jobs, plan_windows
+from .detect import _TDOA_KEYS, EventDetector, _event_tensors, _intervals, _timed, _window_jobs, plan_windows
 
 _KEYS = ("stream", "cls", "onset", "offset", "peak", "peak_frame")
 
@@ -149,9 +153,10 @@ class StreamEvents:
     event_offsets[s+1])); ``final_frames`` [S] host list: output frames of each stream that are final after this call; with
     ``keep_probs``, ``probs`` [sum, K] = the newly final track rows, packed by stream, and ``prob_offsets`` [S+1]."""
 
-    def __init__(self, events, event_offsets, final_frames, frame_seconds, probs=None, prob_offsets=None):
+    def __init__(self, events, event_offsets, final_frames, frame_seconds, probs=None, prob_offsets=None, sr=None):
         self.events, self.event_offsets, self.final_frames = events, list(event_offsets), list(final_frames)
         self.frame_seconds, self.probs, self.prob_offsets = frame_seconds, probs, prob_offsets
+        self.sr = sr                            # the detector's rate: set by a localising stream (lags are in samples at that rate)
 
     def __len__(self):
         return self.event_offsets[-1]
@@ -161,17 +166,36 @@ class StreamEvents:
         e0, e1 = self.event_offsets[int(stream)], self.event_offsets[int(stream) + 1]
         return _intervals({n: v[e0:e1] for n, v in self.events.items()}, self.frame_seconds, k)
 
+    def tdoa(self, stream=None):
+        """time differences of arrival in seconds, a host array [E, P] (the events of one stream; None: all events, in event
+        order), one column per microphone pair, as ``DetectionResult.tdoa``; an event that was not located (``loc_frames``
+        0) has 0.  Only on what a localising stream returns (``det.stream(S, history_frames=...)``)."""
+        if "lag" not in self.events or self.sr is None:
+            raise ValueError("these events hold no lags: make the stream from EventDetector(..., localize=sed.TDOA(...)) with "
+                             "det.stream(S, history_frames=...)")
+        lag = self.events["lag"].cpu().numpy().astype(np.float64) / float(self.sr)
+        return lag if stream is None else lag[self.event_offsets[int(stream)]:self.event_offsets[int(stream) + 1]]
+
 
 class StreamDetector:
     """``EventDetector`` for audio that is still arriving, S streams at once (module docstring).  The keyword arguments are
-    ``EventDetector``'s, checked the same way; ``max_new_windows``: windows per stream and step (longer pushes are split)."""
+    ``EventDetector``'s, checked the same way; ``max_new_windows``: windows per stream and step (longer pushes are split).
+    ``history_frames`` (a detector with ``localize=``): every lane also keeps its last samples in a ring, and an
+    emitted event ``[a, b)`` whose frames ``[f0, f1)`` (``localize.event_frames``) satisfy ``b*tf + lat - f0 <= history_frames``
+    (``localize.stream_locates``) comes with the ``lag``, ``strength`` and ``loc_frames`` of the offline call, bit for bit; the
+    others with zeros.  ``"min"`` = ``max_frames + lat``, the least that is accepted: every event of at most ``max_frames``
+    feature frames is located.  The ring costs ``4 * C * localize.stream_ring_samples(...)`` bytes per feed."""
 
-    def __init__(self, model, n_streams, keep_probs=False, max_new_windows=4, _det=None, input_sr=None, input_channels=None, **kw):
+    def __init__(self, model, n_streams, keep_probs=False, max_new_windows=4, _det=None, input_sr=None, input_channels=None,
+                 history_frames=None, **kw):
         self.det = _det if _det is not None else EventDetector(model, **kw)
         det, m = self.det, self.det.model
-        if det.localize_settings is not None:
+        if det.localize_settings is not None and history_frames is None:
             raise NotImplementedError("live feeds are not localised: when a stream's event becomes final the PCM of its frames is "
-                                      "gone (DESIGN 5o); make the StreamDetector without localize=")
+                                      "gone (DESIGN 5o); make the StreamDetector without localize=, or give it history_frames= "
+                                      "(\"min\" or a number of feature frames) to keep the audio in a ring (DESIGN 5p)")
+        if det.localize_settings is None and history_frames is not None:
+            raise ValueError("history_frames is the audio a localising stream keeps: the detector has no localize=sed.TDOA(...)")
         S = int(n_streams)
         if not 1 <= S <= 65535 or not 1 <= int(max_new_windows) <= 1024:
             raise ValueError(f"need 1 <= n_streams <= 65535 and 1 <= max_new_windows <= 1024, got {n_streams}, {max_new_windows}")
@@ -196,6 +220,27 @@ class StreamDetector:
         if self.q + 1 > self.step_frames:
             raise ValueError(f"hop_length={h} is too small: the {self.q + 1} frames of a flush exceed one step of {self.step_frames}")
         self.CC = (self.q + 1) * h + feature.NFFT // 2                     # samples per half of a stream's PCM carry (an upper bound)
+        # the PCM ring of a localising stream: lat, the history and the samples per lane
+        self.lat = self.history_frames = None
+        self.cap, self._ring, self._rws_ring = 0, None, None
+        self._ev_keys = _KEYS
+        if history_frames is not None:
+            from .localize import stream_latency_frames, stream_ring_samples
+            rows = det.class_settings()
+            if any(r["low"] < r["threshold"] for r in rows):
+                raise ValueError("a localising stream needs low == threshold in every class: below the threshold a run that began "
+                                 "within min_gap of a pending event holds that event back for as long as the run lasts, longer than "
+                                 "any ring keeps its audio (DESIGN 5p)")
+            self.lat = stream_latency_frames(tf, det.seq_len, det.median_max, max(r["min_gap"] for r in rows))
+            least = det.localize_settings.max_frames + self.lat
+            if not (history_frames == "min" or (isinstance(history_frames, (int, np.integer)) and not isinstance(history_frames, bool))):
+                raise ValueError(f"history_frames must be \"min\" or an integer number of feature frames, got {history_frames!r}")
+            self.history_frames = least if isinstance(history_frames, str) else int(history_frames)
+            if not least <= self.history_frames <= 0x7fffffff:
+                raise ValueError(f"history_frames={self.history_frames} is less than the minimum max_frames + lat = "
+                                 f"{det.localize_settings.max_frames} + {self.lat} = {least} feature frames (\"min\")")
+            self.cap = stream_ring_samples(self.history_frames, self.step_frames, h, feature.NFFT)
+            self._ev_keys = _KEYS + _TDOA_KEYS
         self._dims = (S, self.K, self.win_out, self.hop_out, det.median_max, self.max_new)
         self._core_bytes = lib().sed_stream_state_bytes(*self._dims)
         if self._core_bytes == 0:
@@ -230,9 +275,10 @@ class StreamDetector:
     @property
     def state_bytes(self):
         """device bytes held between calls: the step's rings and decoder states, the feature rows, per lane the PCM carry
-        and the resampler's carry and, with ``compress``, the PCEN smoother's two floats per feed and mel column"""
+        and the resampler's carry, with ``compress`` the PCEN smoother's two floats per feed and mel column and, with
+        ``history_frames``, the PCM ring of every lane"""
         pcen = 8 * self.S * self.PW if self.det.compress is not None else 0                 # (C_k, loc) per chain
-        return self._core_bytes + pcen + 4 * self.S * 2 * (self.FC * self.CF + self.C * (self.CC + (self._rCR if self._rs is not None else 0)))
+        return self._core_bytes + pcen + 4 * self.S * self.C * self.cap + 4 * self.S * 2 * (self.FC * self.CF + self.C * (self.CC + (self._rCR if self._rs is not None else 0)))
 
     @property
     def frame_seconds(self):
@@ -255,6 +301,8 @@ class StreamDetector:
             self._aws = torch.empty(lib().sed_stream_append_workspace_bytes(S * self.C), dtype=torch.uint8, device=dev)
             if self.det.compress is not None:
                 self._pcen_state = torch.zeros(S, self.PW, 2, device=dev)
+            if self.cap:                                                   # (read only where the feed's counter says it was written)
+                self._ring = torch.empty(S * self.C * self.cap, device=dev)
             check(lib().sed_stream_init(ptr(self._state), self._state.numel(), *self._dims, stream_ptr()), "sed_stream_init")
         return self._state.device
 
@@ -286,6 +334,9 @@ class StreamDetector:
         row0 = np.where(clip, _excl(clip_rows) + done - self._cbase // h, 0)
         rows = np.where(clip, upto - done, 0)
         n_rows, n_work = int(clip_rows.sum()), int(((total_l + 3) & ~3).sum())
+        if self._ring is not None and takes.any():                         # the new samples also go to the rings, from sample _n on
+            self._rws_ring = feature.ring_write(self._ring, self.cap, fresh, np.stack([_excl(takes_l), takes_l, lane(self._n)], 1),
+                                                self._rws_ring)
         self._n, self._fdone = n, upto
         self._cbase, self._clen = np.where(act, a_new, self._cbase), np.where(act, n - a_new, self._clen)
         self._cpar = np.where(act, 1 - self._cpar, self._cpar)
@@ -416,9 +467,24 @@ class StreamDetector:
         if offs[-1] > cap:
             raise SedHipError(f"sed_stream_step emitted {offs[-1]} events, more than the bound {cap}")
         events = {k: v[:offs[-1]] for k, v in ev.items()}
+        if self._ring is not None:
+            events.update(self._locate(events, end))
         if end.any():
             self._reset_host(end)
         return events, offs, probs, prob_n, now_F
+
+    def _locate(self, events, end):
+        """the step's events on the rings, with the samples received so far (before a feed that ends is reset): one
+        ``event_tdoa_ring`` call"""
+        det, t, h = self.det, self.det.localize_settings, self.det.hop_length
+        # every frame of an emitted event is final: its samples were received, so nothing is read beyond them — except in a feed
+        # that ends, whose count is final and whose last frames are right-padded with zeros as offline
+        live = ~end & (self._fdone > 0)
+        if (live & ((self._fdone - 1) * h + feature.NFFT // 2 > self._n)).any() or (self.sched.N > self._fdone).any():
+            raise SedHipError("a stream holds final feature frames whose samples it has not received")
+        return _timed(self.marks, "locate", lambda: feature.event_tdoa_ring(
+            self._ring, self.cap, self._n, self.C, events, det.model.time_factor, max_lag=t.max_lag, max_frames=t.max_frames, hop=h,
+            lat_frames=self.lat, history_frames=self.history_frames))
 
     # ── rounds: a push of any size as steps of bounded size ──
     def _run(self, rounds):
@@ -434,15 +500,15 @@ class StreamDetector:
             final = parts[-1][4]
         final = final.tolist()
         if not parts:
-            ev = _event_tensors(_KEYS, 0, dev)
+            ev = self._no_events(dev)
             probs = torch.empty(0, K, device=dev) if self.keep_probs else None
-            return StreamEvents(ev, [0] * (S + 1), final, self.frame_seconds, probs, [0] * (S + 1) if self.keep_probs else None)
+            return self._events(ev, [0] * (S + 1), final, probs, [0] * (S + 1) if self.keep_probs else None)
         if len(parts) == 1:
             ev, offs, probs, prob_n, _ = parts[0]
             poffs = np.concatenate([[0], np.cumsum(prob_n)]).tolist() if self.keep_probs else None
-            return StreamEvents(ev, offs, final, self.frame_seconds, probs, poffs)
+            return self._events(ev, offs, final, probs, poffs)
         # several steps: a stream's events (and rows) of step 1, then of step 2, ...: one stable sort by (stream, class)
-        ev = {k: torch.cat([p[0][k] for p in parts]) for k in _KEYS}
+        ev = {k: torch.cat([p[0][k] for p in parts]) for k in self._ev_keys}
         order = torch.sort(ev["stream"].long() * K + ev["cls"].long(), stable=True).indices
         ev = {k: v[order] for k, v in ev.items()}
         counts = np.sum([np.diff(p[1]) for p in parts], axis=0)
@@ -454,7 +520,18 @@ class StreamDetector:
             allp = torch.cat([p[2] for p in parts])
             probs = allp[torch.from_numpy(idx).to(dev)]
             poffs = np.concatenate([[0], np.cumsum(np.sum([p[3] for p in parts], axis=0))]).tolist()
-        return StreamEvents(ev, offs, final, self.frame_seconds, probs, poffs)
+        return self._events(ev, offs, final, probs, poffs)
+
+    def _no_events(self, dev):
+        ev = _event_tensors(_KEYS, 0, dev)
+        if self._ring is not None:
+            P = self.C * (self.C - 1) // 2
+            ev.update(lag=torch.empty(0, P, device=dev), strength=torch.empty(0, P, device=dev),
+                      loc_frames=torch.empty(0, dtype=torch.int32, device=dev))
+        return ev
+
+    def _events(self, ev, offs, final, probs, poffs):
+        return StreamEvents(ev, offs, final, self.frame_seconds, probs, poffs, self.det.sr if self.cap else None)
 
     def _pieces(self, xs, what, check_one, axis=0):
         xs = list(xs)
@@ -579,6 +656,9 @@ class StreamDetector:
 
     def push_features(self, mels):
         """a list of S scaled feature pieces [n_s, C*F] (any channel count, host or device; None = nothing new) -> StreamEvents"""
+        if self.cap:
+            raise ValueError("a localising stream (history_frames=) takes audio: features carry no samples to locate an event on; "
+                             "use push, or a stream without history_frames")
         def one(s, x):
             x = torch.as_tensor(x)
             if x.dim() != 2 or x.shape[1] != self.CF:
@@ -642,7 +722,7 @@ class StreamDetector:
     def _joined(self, a, b):
         """two StreamEvents of one call as one: per stream a's events (and rows), then b's"""
         K, dev = self.K, self._state.device
-        ev = {k: torch.cat([a.events[k], b.events[k]]) for k in _KEYS}
+        ev = {k: torch.cat([a.events[k], b.events[k]]) for k in self._ev_keys}
         order = torch.sort(ev["stream"].long() * K + ev["cls"].long(), stable=True).indices
         ev = {k: v[order] for k, v in ev.items()}
         offs = (np.asarray(a.event_offsets) + np.asarray(b.event_offsets)).tolist()
@@ -653,7 +733,7 @@ class StreamDetector:
             idx = np.argsort(owner, kind="stable")
             probs = torch.cat([a.probs, b.probs])[torch.from_numpy(idx).to(dev)]
             poffs = np.concatenate([[0], np.cumsum(na + nb)]).tolist()
-        return StreamEvents(ev, offs, b.final_frames, self.frame_seconds, probs, poffs)
+        return self._events(ev, offs, b.final_frames, probs, poffs)
 
     def reset(self, streams=None):
         """drop these streams (default: all) where they stand: nothing is emitted, they restart at frame 0"""
