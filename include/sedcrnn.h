@@ -343,7 +343,7 @@ int sed_conv1_bwd_wgrad_assemble(const float* partials, int rows, const double* 
 /* ───────────── dense GEMM on fp32 MFMA (aten::mm/addmm under nn.GRU / nn.Linear, sed.py:101-103) ─────────────
  * C[i][j] = sum_k A(i,k) * B(k,j) (+ bias[j]) (+ beta*C[i][j]), C row-major with leading dim ldc.
  * A(i,k) = A[i*a_si + k*a_sk], B(k,j) = B[k*b_sk + j*b_sj]; for each operand one of the
- * two strides must be 1.  Exact fp32 (v_mfma_f32_32x32x2_f32: a k-ordered fmaf chain). */
+ * two strides must be 1.  Exact fp32 (v_mfma_f32_32x32x2_f32: one fixed order of summation whatever the tile or layout). */
 int sed_gemm_f32(const float* A, long a_si, long a_sk, const float* B, long b_sk, long b_sj,
                  float* C, long ldc, const float* bias, float beta, int M, int N, int K, void* stream);
 /* Same product (optional bias, beta = 0) with a scratch buffer: small-output / long-K shapes (the GRU weight
@@ -365,6 +365,10 @@ int sed_gemm_bf16_nt(const void* A, const void* B, const float* bias, float* C, 
  * gives at most one tile per CU (two co-resident workgroups per CU instead of one).  Deterministic for given (M,N,K). */
 int sed_gemm_f32_wgrad(const float* A, long a_si, long a_sk, const float* B, long b_sk, long b_sj,
                        float* C, long ldc, int M, int N, int K, void* workspace, void* stream);
+/* Which plan a call of the three entries above runs (host only, the launches read the same rule).  policy 0: sed_gemm_f32,
+ * 1: sed_gemm_f32_ws, 2: sed_gemm_f32_wgrad (the latter two given a workspace).  *bm x *bn = the block tile; *splits = number of
+ * K-slices (1: not split); *k_len = k extent of a slice (K when not split; the last slice may be shorter). */
+int sed_gemm_f32_plan(int M, int N, int K, int policy, int* bm, int* bn, int* splits, int* k_len);
 
 /* Small dense layer y = act(x W^T + b) for the time-distributed head (sed.py:103,112;
  * crnn_lightning.py:63-64,72-73). x [M][K], W [N][K], y [M][N]; relu=1 applies ReLU. */

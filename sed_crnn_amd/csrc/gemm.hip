@@ -3,7 +3,10 @@
 // Replaces aten::mm / addmm under nn.GRU's input projections and nn.Linear (reference
 // sed.py:101-103,111-112; crnn_lightning.py:61-64,71-73) and their autograd transposes.
 // The GRU input projection (M=B*T', K=C*F, N=3H) is the one genuine dense GEMM of the path, hence MFMA.
-// fp32 in / fp32 accumulate: bit-for-bit a k-ordered fmaf chain, no reduced precision.
+// fp32 in / fp32 accumulate, no reduced precision.  The chain of an output element is NOT k-ordered: within each group of 8
+// the MFMA takes k = 8g+j from lanes 0-31 and k = 8g+4+j from lanes 32-63 (j = 0..3).  What holds is one fixed order of
+// summation, the same for every tile, layout and FULL / guarded path, so a row's bits do not depend on the plan its call got
+// (tests/test_gpu_gemm_tiles.py: test_one_summation_order_whatever_the_tile).
 #include <type_traits>
 #include "common.h"
 
@@ -348,6 +351,17 @@ extern "C" size_t sed_gemm_f32_workspace_bytes(int M, int N, int K) {
         if (b > best) best = b;
     }
     return best;
+}
+
+// What gemm_impl would use for (M, N, K) under a policy (0: sed_gemm_f32, 1: sed_gemm_f32_ws, 2: sed_gemm_f32_wgrad), from the
+// gemm_plan and the kCands the launches read, so the report and the dispatch cannot drift apart.  Host only.
+extern "C" int sed_gemm_f32_plan(int M, int N, int K, int policy, int* bm, int* bn, int* splits, int* k_len) {
+    SED_REQUIRE(bm && bn && splits && k_len, "gemm_f32_plan: null pointer");
+    SED_REQUIRE(M > 0 && N > 0 && K > 0, "gemm_f32_plan: bad sizes M=%d N=%d K=%d", M, N, K);
+    SED_REQUIRE(policy >= 0 && policy <= 2, "gemm_f32_plan: policy %d is not 0 (gemm_f32), 1 (gemm_f32_ws) or 2 (gemm_f32_wgrad)", policy);
+    const GemmPlan p = gemm_plan(M, N, K, policy);
+    *bm = kCands[p.cand].bm; *bn = kCands[p.cand].bn; *splits = p.splits; *k_len = p.k_len;
+    return 0;
 }
 
 static int gemm_impl(const float* A, long a_si, long a_sk, const float* B, long b_sk, long b_sj, float* C,

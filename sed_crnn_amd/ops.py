@@ -270,6 +270,13 @@ def gemm_ws(A, B, out=None, bias=None, wgrad=False):
     return out
 
 
+def gemm_plan(M, N, K, policy=0):
+    """-> (bm, bn, splits, k_len): the block tile and the K-slices gemm (policy 0), gemm_ws (1) or gemm_ws(wgrad=True) (2) use"""
+    bm, bn, splits, k_len = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    check(lib().sed_gemm_f32_plan(M, N, K, policy, C.byref(bm), C.byref(bn), C.byref(splits), C.byref(k_len)), "gemm_f32_plan")
+    return bm.value, bn.value, splits.value, k_len.value
+
+
 def linear_fwd(x, W, b, relu=False):
     M, K = x.shape
     N = W.shape[0]
