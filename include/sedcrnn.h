@@ -59,6 +59,14 @@ int sed_conv3x3_pack_weights(const float* w_oihw, float* wp_fwd, float* wp_dgrad
  * ([rows][2][Cout]: sum and sum of squares of the outputs, pre-BN, bias included). */
 int sed_conv3x3_stat_rows(int B, int Cin, int F, int T, int Cout, int x_is_nchw);
 
+/* How a shape would run, read from the plan the launches read (host only, works without a GPU).  which = 0: the plan of
+ * sed_conv3x3_fwd_ex and of the data gradients; which = 1: the plan of sed_conv3x3_bn_relu_pool_eval (x_is_nchw must be 0).
+ * out[8] = {kind (0 small-channel kernel, 1 MFMA kernel, -1 none; the rest is 0 then), TT, FT (time rows x mel columns of a
+ * block tile), nft (mel tiles), nct (32-wide output-channel tiles per workgroup; 0 on the small path), tblocks (= ceil(T/TT)),
+ * rows (statistic partial rows = B * tblocks * nft; the tile (b, tb, fi) writes row (b * tblocks + tb) * nft + fi),
+ * xcd_order (1: the MFMA kernel walks its tiles in the XCD-aware order, i.e. B % 8 == 0)}. */
+int sed_conv3x3_plan(int B, int Cin, int F, int T, int Cout, int x_is_nchw, int which, int* out);
+
 /* y[b][t][f][co] = bias[co] + sum_{kh,kw,ci} w[co][ci][kh][kw] x[.. f+kh-1, t+kw-1 ..]
  * x_is_nchw=1: x is the network input [B][Cin][F][T]; 0: x is channels-last [B][T][F][Cin].
  * wp = wp_fwd from sed_conv3x3_pack_weights ([9][Cout][Cin]).

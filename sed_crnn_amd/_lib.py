@@ -58,6 +58,7 @@ SIGNATURES = {
     "sed_last_error_string": (C.c_char_p, []),
     "sed_conv3x3_pack_weights": (_i, [_fp, _fp, _fp, _i, _i, _stream]),
     "sed_conv3x3_stat_rows": (_i, [_i, _i, _i, _i, _i, _i]),
+    "sed_conv3x3_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, C.POINTER(_i)]),
     "sed_conv3x3_fwd": (_i, [_fp, _i, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _stream]),
     "sed_conv3x3_pack_weights_ex": (_i, [_fp, _fp, _fp, _i, _i, _i, _stream]),
     "sed_conv3x3_fwd_ex": (_i, [_fp, _i, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _stream]),

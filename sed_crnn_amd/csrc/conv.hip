@@ -1245,6 +1245,23 @@ static ConvPlan conv_eval_plan(int B, int Cin, int F, int T, int Cout) {
     }
     return conv_eval_lds(p) <= 80 * 1024 ? p : none;
 }
+// What the launches would use for a shape, from the conv_plan (which = 0: sed_conv3x3_fwd_ex and the data gradients) or the
+// conv_eval_plan (which = 1: sed_conv3x3_bn_relu_pool_eval) they read, so the report and the dispatch cannot drift apart.
+// out = {kind, TT, FT, nft, nct, tblocks, rows, xcd_order}; kind = -1 (and zeros) where the plan takes no kernel.  Host only.
+extern "C" int sed_conv3x3_plan(int B, int Cin, int F, int T, int Cout, int x_is_nchw, int which, int* out) {
+    SED_REQUIRE(out, "conv3x3_plan: null pointer");
+    SED_REQUIRE(B > 0 && Cin > 0 && F > 0 && T > 0 && Cout > 0, "conv3x3_plan: bad shape B=%d Cin=%d F=%d T=%d Cout=%d", B, Cin, F, T, Cout);
+    SED_REQUIRE(which == 0 || which == 1, "conv3x3_plan: which = %d is not 0 (conv_plan) or 1 (the pooled inference plan)", which);
+    SED_REQUIRE(which == 0 || !x_is_nchw, "conv3x3_plan: the pooled inference kernel reads channels-last input");
+    const ConvPlan p = which ? conv_eval_plan(B, Cin, F, T, Cout) : conv_plan(B, Cin, F, T, Cout, x_is_nchw);
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    out[0] = p.kind;
+    if (p.kind < 0) return 0;
+    out[1] = p.TT; out[2] = p.FT; out[3] = p.nft; out[4] = p.nct; out[5] = p.tblocks; out[6] = p.rows;
+    out[7] = (p.kind == 1 && B % 8 == 0) ? 1 : 0;          // the kernels' `(gridDim.y & 7) == 0`, gridDim.y = B
+    return 0;
+}
+
 extern "C" int sed_conv3x3_bn_relu_pool_eval_supported(int B, int Cin, int F, int T, int Cout) {
     if (B <= 0 || Cin <= 0 || F <= 0 || T < 2 || Cout <= 0) return 0;
     if ((size_t)B * T * F * Cin >= ((size_t)1 << 32) || (size_t)T * F * Cout >= ((size_t)1 << 30)) return 0;

@@ -41,6 +41,17 @@ def conv3x3_fwd(x, wp, bias, x_is_nchw, want_stats=True, mode=0):
     return y, stat
 
 
+CONV_PLAN_FIELDS = ("kind", "TT", "FT", "nft", "nct", "tblocks", "rows", "xcd_order")
+
+
+def conv3x3_plan(B, Cin, F, T, Cout, x_is_nchw=False, which=0):
+    """-> dict of CONV_PLAN_FIELDS: the block tile conv3x3_fwd / the data gradients (which 0) or conv3x3_bn_relu_pool_eval
+    (which 1) run a shape on, from the plan the launches read; kind -1 = no kernel takes it.  Needs no GPU."""
+    out = (C.c_int * 8)()
+    check(lib().sed_conv3x3_plan(B, Cin, F, T, Cout, int(x_is_nchw), which, out), "conv3x3_plan")
+    return dict(zip(CONV_PLAN_FIELDS, out))
+
+
 def conv3x3_wino_pack(w):
     """w [Cout,Cin,3,3] -> (uf, ud): the Winograd F(2x2,3x3) transformed weights of the forward and of the data gradient"""
     Cout, Cin = w.shape[:2]

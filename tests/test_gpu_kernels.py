@@ -37,6 +37,8 @@ CONV_CASES = [  # B, Cin, F, T, Cout, nchw
     (2, 128, 8, 44, 128, False), (1, 128, 4, 75, 128, False), (2, 128, 2, 9, 128, False), (1, 128, 8, 3, 128, False),
     # channel counts off the MFMA path and too wide for one LDS image: the chunked fallback (several launches adding to y)
     (2, 100, 10, 6, 100, False), (1, 36, 12, 5, 132, False), (1, 200, 8, 4, 68, False), (2, 6, 40, 5, 200, True),
+    # a batch that is a multiple of 8: the MFMA kernel walks its tiles in the XCD-aware order (every tile: test_gpu_conv_tiles.py)
+    (8, 128, 40, 12, 128, False),
 ]
 
 
@@ -230,7 +232,8 @@ def test_conv1_stats_from_input_moments_vs_float64_sums(ops, cin, mu, sd):
 
 
 @pytest.mark.parametrize("B,Ty,Fy,pf,pt,p", [(3, 16, 40, 1, 2, 0.5), (2, 12, 40, 1, 2, 0.0), (2, 9, 40, 1, 2, 0.5), (1, 8, 41, 2, 2, 0.3),
-                                              (2, 6, 128, 1, 2, 0.5), (1, 20, 8, 2, 1, 0.25)])
+                                              (2, 6, 128, 1, 2, 0.5), (1, 20, 8, 2, 1, 0.25),
+                                              (8, 16, 40, 1, 2, 0.5)])                      # B = 8: the XCD-aware workgroup order
 def test_dgrad_with_fused_bn_backward_reduction_matches_the_two_pass_form(ops, B, Ty, Fy, pf, pt, p):
     """sed_conv3x3_dgrad_bnred: the data gradient of a 128-channel block whose epilogue also forms (sum g, sum g*xhat) of the
     block below from that block's pooled OUTPUT, against the separate passes (sed_conv3x3_fwd_ex on the dgrad weights +
@@ -429,7 +432,8 @@ def test_bn_backward_sums_of_the_gru_feeding_block_from_its_pooled_output(ops, B
 
 
 @pytest.mark.parametrize("B,F,T,p,cin", [(3, 40, 32, 0.5, 1), (2, 40, 20, 0.0, 1), (1, 40, 36, 0.5, 1), (2, 24, 12, 0.3, 1), (2, 128, 16, 0.5, 1),
-                                          (3, 40, 32, 0.5, 2), (1, 40, 36, 0.0, 2), (2, 24, 12, 0.3, 2)])
+                                          (3, 40, 32, 0.5, 2), (1, 40, 36, 0.0, 2), (2, 24, 12, 0.3, 2),
+                                          (8, 40, 32, 0.5, 1)])                             # B = 8: the XCD-aware workgroup order
 def test_first_block_weight_gradient_sums_from_the_data_gradient_epilogue(ops, B, F, T, p, cin):
     """sed_conv3x3_dgrad_bnred_rg + sed_conv1_bwd_wgrad_assemble against sed_conv3x3_dgrad_bnred + sed_conv1_bwd_wgrad: the
     data gradient of block 2 whose epilogue also forms the 1- or 2-channel first block's weight-gradient sums (sum g, R_k) from
@@ -643,7 +647,8 @@ def test_routing_codes_of_the_recomputed_first_block(ops, cin, pf, pt):
 
 @pytest.mark.parametrize("B,T,Fm,Cin,Cout", [(2, 16, 40, 128, 128), (3, 15, 40, 32, 128), (1, 8, 64, 64, 256), (2, 23, 13, 32, 128),
                                             (1, 4, 41, 128, 128), (2, 64, 20, 128, 128), (1, 31, 56, 32, 128), (2, 17, 70, 32, 128),
-                                            (1, 33, 8, 32, 128), (3, 9, 40, 32, 128)])
+                                            (1, 33, 8, 32, 128), (3, 9, 40, 32, 128),
+                                            (8, 16, 40, 32, 128)])                          # B = 8: the XCD-aware workgroup order
 def test_inference_conv_with_folded_batchnorm_relu_and_pool_in_the_epilogue(ops, B, T, Fm, Cin, Cout):
     """sed_conv3x3_bn_relu_pool_eval (the eval-mode plan's conv blocks >= 1: `pool(relu(bn(conv(x))))` of sed.py:107 under
     model.eval()) against torch: BatchNorm on running statistics folded into weights and bias, ReLU + (1,2) pool in the
