@@ -544,6 +544,35 @@ int sed_event_tdoa_ring(const float* ring, long ring_len, long cap, const long* 
                         long E, int time_factor, int hop, int max_lag, int max_frames, int lat_frames, int history_frames,
                         float* lag_out, float* strength_out, int* frames_out, float* acc_out, void* workspace,
                         size_t workspace_bytes, void* stream);
+/* sed_event_doa: sed_event_tdoa, and for every event one direction out of a grid of D, by steered response power
+ * (SRP-PHAT) for a known array.  Every argument it shares with sed_event_tdoa means what it means there, and lag_out,
+ * strength_out, frames_out and acc_out receive the bits that call writes.  With S the accumulated whitened cross spectrum of
+ * the event and pair p that acc is made from, Q = oversample in {1, 2, 4, 8, 16} and F = Q max_lag:
+ *   fine_p[j] = (1/2048) (S[0] + Re S[1024] cos(pi j / Q) + 2 sum_{k=1..1023} Re(S[k] e^{+2 pi i k j / (2048 Q)})),  |j| <= F:
+ * the band-limited correlation at the lag j / Q samples (at Q = 1, acc[j] bit for bit);
+ *   srp[d] = sum_p fine_p[steer_lags[d][p]], fp32 adds in ascending p; dir = the first maximum of srp in ascending d; power =
+ * srp[dir] / (P (f1 - f0)) in [-1, 1].  An event without frames and digital silence (every srp value 0) give dir = -1 and
+ * power = 0; no NaN is written to either.  steer_lags: DEVICE int32 [D][P], the fine lag Q sr (r_j - r_i) . u_d / c of direction
+ * d and pair p rounded to an integer (a value outside [-F, F] is read as the nearer end); trig: DEVICE float [512 Q + 1][2],
+ * (cos, sin)(2 pi k / (2048 Q)) (float64 values rounded once), 8-byte aligned; dir_out: device int32 [E]; power_out: device
+ * float [E]; srp_out (may be NULL): device float [E][D].  1 <= D <= 16384.  One more launch per slice of the event table; the
+ * workspace is sed_event_tdoa's (sed_event_doa_workspace_bytes returns the same size) and the slicing changes no bit.  Every
+ * output depends on the event's own samples, its frame range and these settings alone.  The host reads nothing back; every
+ * argument is checked before anything is enqueued.
+ * sed_event_doa_ring is the same on the rings of live feeds: sed_event_tdoa_ring's arguments, rules and bits. */
+size_t sed_event_doa_workspace_bytes(int R, int channels, long E, long max_n_samples, int hop, int max_frames);
+int sed_event_doa(const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const void* tables,
+                  size_t tables_bytes, const int* ev_rec, const int* ev_onset, const int* ev_offset, const int* ev_peak_frame,
+                  long E, int time_factor, int hop, int pad_mode, int max_lag, int max_frames, float* lag_out, float* strength_out,
+                  int* frames_out, float* acc_out, const int* steer_lags, int D, int Q, const float* trig, int* dir_out,
+                  float* power_out, float* srp_out, void* workspace, size_t workspace_bytes, void* stream);
+size_t sed_event_doa_ring_workspace_bytes(int R, int channels, long E, long cap, int hop, int max_frames);
+int sed_event_doa_ring(const float* ring, long ring_len, long cap, const long* n_host, int R, int channels, const void* tables,
+                       size_t tables_bytes, const int* ev_rec, const int* ev_onset, const int* ev_offset, const int* ev_peak_frame,
+                       long E, int time_factor, int hop, int max_lag, int max_frames, int lat_frames, int history_frames,
+                       float* lag_out, float* strength_out, int* frames_out, float* acc_out, const int* steer_lags, int D, int Q,
+                       const float* trig, int* dir_out, float* power_out, float* srp_out, void* workspace, size_t workspace_bytes,
+                       void* stream);
 
 /* sed_pcen: per-channel energy normalisation, IN PLACE, of the columns [col0, col0 + W) of x [rows][stride], which
  * hold log-mel values (natural log, as sed_logmel* write them without a scaler); the other columns are not touched.  Every column

@@ -152,6 +152,12 @@ SIGNATURES = {
     "sed_event_tdoa_ring_workspace_bytes": (_sz, [_i, _i, _l, _l, _i, _i]),
     "sed_event_tdoa_ring": (_i, [_fp, _l, _l, _fp, _i, _i, _fp, _sz, _fp, _fp, _fp, _fp, _l, _i, _i, _i, _i, _i, _i, _fp, _fp, _fp, _fp,
                                  _fp, _sz, _stream]),
+    "sed_event_doa_workspace_bytes": (_sz, [_i, _i, _l, _l, _i, _i]),
+    "sed_event_doa": (_i, [_fp, _l, _fp, _i, _i, _fp, _sz, _fp, _fp, _fp, _fp, _l, _i, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _i, _i,
+                           _fp, _fp, _fp, _fp, _fp, _sz, _stream]),
+    "sed_event_doa_ring_workspace_bytes": (_sz, [_i, _i, _l, _l, _i, _i]),
+    "sed_event_doa_ring": (_i, [_fp, _l, _l, _fp, _i, _i, _fp, _sz, _fp, _fp, _fp, _fp, _l, _i, _i, _i, _i, _i, _i, _fp, _fp, _fp, _fp,
+                                _fp, _i, _i, _fp, _fp, _fp, _fp, _fp, _sz, _stream]),
     "sed_pcen_workspace_bytes": (_sz, [_l, _i, _i]),
     "sed_pcen": (_i, [_fp, _l, _i, _i, _i, _fp, _i, _fp, _d, _f, _f, _f, _f, _f, _fp, _fp, _fp, _sz, _stream]),
     "sed_resample_workspace_bytes": (_sz, [_i]),

@@ -12,13 +12,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libsedcrnn.so")
-SOURCES = ["api.cpp", "conv.hip", "conv_bf16.hip", "wino.hip", "conv1.hip", "bnpool.hip", "gemm.hip", "gru.hip", "misc.hip", "logmel.hip", "gcc.hip", "tdoa.hip", "pcen.hip", "resample.hip", "data.hip", "detect.hip", "tune.hip", "stream.hip", "net.hip"]
+SOURCES = ["api.cpp", "conv.hip", "conv_bf16.hip", "wino.hip", "conv1.hip", "bnpool.hip", "gemm.hip", "gru.hip", "misc.hip", "logmel.hip", "gcc.hip", "tdoa.hip", "doa.hip", "pcen.hip", "resample.hip", "data.hip", "detect.hip", "tune.hip", "stream.hip", "net.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # per-file extras.  logmel: the SLP vectoriser packs the FFT's scalar adds into v_pk_add_f32 and pays for it with ~600
 # v_mov per frame pair to build the register pairs (packed f32 is no faster than scalar on gfx950)
 EXTRA_FLAGS = {"logmel.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"],
                "gcc.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"],
                "tdoa.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"],
+               "doa.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"],
                "pcen.hip": ["-Rpass-analysis=kernel-resource-usage"],
                "conv.hip": ["-Rpass-analysis=kernel-resource-usage"],
                "wino.hip": ["-Rpass-analysis=kernel-resource-usage"],
@@ -44,6 +45,9 @@ NO_SCRATCH_KERNELS = {"wino.hip": ("conv3x3_wino_k",),
                       # per-event TDOA: the accumulate kernel runs the same FFT beside LDS accumulators, the finish kernel's lag
                       # loop is all LDS reads and fma: scratch in either would be as silent
                       "tdoa.hip": ("tdoa_accum_k", "tdoa_finish_k"),
+                      # per-event direction: the fine-lag loop is tdoa_finish_k's with an index unfolding per read; scratch in it
+                      # would multiply the cost of the one loop the launch consists of
+                      "doa.hip": ("doa_steer_k",),
                       # PCEN: the powers of (1-b) travel by value and are indexed in a loop; a copy of them in scratch, or a spilled
                       # powf, would turn a bandwidth-bound pass into a latency-bound one without failing any test
                       "pcen.hip": ("pcen_pass_k", "pcen_carry_k")}
@@ -86,7 +90,7 @@ def check_no_spill(remarks, kernels, allow_agprs=False):
 def build(force=False, verbose=False):
     os.makedirs(OBJ, exist_ok=True)
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_shared.h"), os.path.join(CSRC, "detect_shared.h"), os.path.join(CSRC, "fft2048.h"), os.path.join(HERE, "..", "include", "sedcrnn.h")]
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_shared.h"), os.path.join(CSRC, "detect_shared.h"), os.path.join(CSRC, "fft2048.h"), os.path.join(CSRC, "tdoa_shared.h"), os.path.join(HERE, "..", "include", "sedcrnn.h")]
     jobs = []
     objs = []
     for src in SOURCES:

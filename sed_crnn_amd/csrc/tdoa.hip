@@ -26,67 +26,25 @@
 // Live feeds: sed_stream_ring_write keeps every lane's last cap samples in a ring, and sed_event_tdoa_ring is the same
 // two launches with tdoa_accum_k<true>, which loads a frame from the ring — directly where it does not wrap, through the guarded
 // loads where it does — and with td_event_range also refusing what the stream's rule or the ring's depth refuses.
+//
+// The host side of both entries is behind tdoa_linear_entry / tdoa_ring_entry (tdoa_shared.h), which doa.hip calls with a hook
+// that steers every slice while its partials are in the workspace; the entries here pass none.
 #include <math.h>
 #include <string.h>
 #include <vector>
 #include "common.h"
 #include "fft2048.h"
+#include "tdoa_shared.h"
 
-#define TD_CHUNK 32                               // frames per workgroup of the accumulate launch
 #define TD_WAVES 8
 #define TD_THREADS (TD_WAVES * 64)
-#define TD_MAX_CH 8
-#define TD_MAX_LAG 127
-#define TD_SPEC 1026                              // float2 per spectrum / accumulator row (1025 bins + 1 pad)
 #define TD_TAB_WORDS LM_OFF_ENT                   // of the log-mel blob: header, window, inter-pass and pairing twiddles
 #define TD_FFT_SCR (2 * LM_SCR)                   // floats of exchange scratch per transforming wave
 #define TD_LDS_MAX ((size_t)160 * 1024)
 #define TD_FIN_THREADS 256
-#define TD_ROW_BYTES ((size_t)TD_SPEC * sizeof(float2))
 
+// (TdArgs, td_event_range and the workspace's row layout: tdoa_shared.h, shared with doa.hip)
 namespace {
-
-struct TdArgs {
-    const long* sample_off;     // [R*C] first sample of every planar channel
-    const long* n_samples;      // [R]   samples per channel
-    const int *ev_rec, *ev_onset, *ev_offset, *ev_peak;          // [E] (ev_rec may be null: one recording)
-    int R, C, P, pairs_per_batch;
-    int tf, hop, max_frames, max_lag;
-    int cpe;                    // chunk slots per event in the workspace
-    int pipelined;              // two spectra buffers: the FFT of frame f+1 runs beside the whitening of frame f
-    long e0;                    // first event of the slice
-    int n_ev;                   // events of the slice
-    long cap;                   // > 0: recording r is a live feed, its channel ch the ring of cap samples at (r*C + ch)*cap
-    int lat, hist;              // ... and the stream's latency and history, in feature frames
-};
-
-// The frames [f0, f0 + nf) an event is located on; nf = 0: the event names no recording or lies beyond its end (nothing is read).
-__device__ __forceinline__ void td_linear_range(const TdArgs& a, long e, int& rec, long& f0, int& nf) {
-    rec = a.ev_rec ? a.ev_rec[e] : 0;
-    f0 = 0; nf = 0;
-    if (rec < 0 || rec >= a.R) return;
-    const long n_feat = 1 + a.n_samples[rec] / a.hop;
-    const long on = a.ev_onset[e], off = a.ev_offset[e];
-    const long lo = on * a.tf;
-    long hi = off * a.tf;
-    if (hi > n_feat) hi = n_feat;
-    if (on < 0 || lo >= n_feat) return;
-    if (hi <= lo) { f0 = lo; nf = 1; return; }
-    if (hi - lo <= a.max_frames) { f0 = lo; nf = (int)(hi - lo); return; }
-    long c = (long)a.ev_peak[e] * a.tf + a.tf / 2 - a.max_frames / 2;
-    if (c < lo) c = lo;
-    if (c > hi - a.max_frames) c = hi - a.max_frames;
-    f0 = c; nf = a.max_frames;
-}
-
-// ... of a live feed (a.cap > 0, n_samples = the samples received so far): the same range, and no frames either where the
-// stream's rule b*tf + lat - f0 <= history does not hold or where the first sample read is no longer in the ring
-__device__ __forceinline__ void td_event_range(const TdArgs& a, long e, int& rec, long& f0, int& nf) {
-    td_linear_range(a, e, rec, f0, nf);
-    if (a.cap <= 0 || nf == 0) return;
-    const long first = f0 * a.hop - LM_NFFT / 2;
-    if ((long)a.ev_offset[e] * a.tf + a.lat - f0 > a.hist || (first > 0 ? first : 0) < a.n_samples[rec] - a.cap) { f0 = 0; nf = 0; }
-}
 
 // RING: the channels are rings (TdArgs.cap); a frame that does not wrap takes the same 8-byte loads, one that does goes through
 // the guarded loads, and either way the registers hold the same samples: everything after the loads is one code.
@@ -379,7 +337,7 @@ template <bool RING>
 int tdoa_run(const char* who, const float* pcm, const std::vector<long>& h, size_t tab, long longest, long cap, int lat, int hist, int R,
              int channels, const void* tables, const int* ev_rec, const int* ev_onset, const int* ev_offset, const int* ev_peak_frame,
              long E, int time_factor, int hop, int pad_mode, int max_lag, int max_frames, float* lag_out, float* strength_out,
-             int* frames_out, float* acc_out, void* workspace, size_t workspace_bytes, void* stream) {
+             int* frames_out, float* acc_out, void* workspace, size_t workspace_bytes, void* stream, TdSliceHook hook, void* hook_ctx) {
     const int P = channels * (channels - 1) / 2;
     SED_REQUIRE(ev_onset && ev_offset && ev_peak_frame && lag_out && strength_out && frames_out && workspace, "%s: null pointer", who);
     SED_REQUIRE(ev_rec || R == 1, "%s: %d recordings need ev_rec", who, R);
@@ -417,6 +375,10 @@ int tdoa_run(const char* who, const float* pcm, const std::vector<long>& h, size
         const int blocks = n_ev < 2048 ? n_ev : 2048;
         tdoa_finish_k<<<blocks, TD_FIN_THREADS, 0, s>>>((const uint32_t*)tables, part, lag_out, strength_out, frames_out, acc_out, ta);
         SED_LAUNCH_CHECK(RING ? "event_tdoa_ring (finish)" : "event_tdoa (finish)");
+        if (hook) {                                              // (doa.hip: the slice's partials are still in the workspace)
+            const int rc = hook(hook_ctx, ta, part, s);
+            if (rc != 0) return rc;
+        }
     }
     return 0;
 }
@@ -447,19 +409,19 @@ extern "C" size_t sed_event_tdoa_workspace_bytes(int R, int channels, long E, lo
     return tdoa_table_bytes(R, channels) + (size_t)E * cpe * P * TD_ROW_BYTES;
 }
 
-extern "C" int sed_event_tdoa(const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const void* tables,
-                              size_t tables_bytes, const int* ev_rec, const int* ev_onset, const int* ev_offset,
-                              const int* ev_peak_frame, long E, int time_factor, int hop, int pad_mode, int max_lag, int max_frames,
-                              float* lag_out, float* strength_out, int* frames_out, float* acc_out, void* workspace,
-                              size_t workspace_bytes, void* stream) {
-    SED_REQUIRE(channels >= 2 && channels <= TD_MAX_CH, "event_tdoa: 2 to %d channels, got %d", TD_MAX_CH, channels);
-    SED_REQUIRE(max_lag >= 1 && max_lag <= TD_MAX_LAG, "event_tdoa: max_lag must be in [1,%d], got %d", TD_MAX_LAG, max_lag);
-    SED_REQUIRE(max_frames >= 1, "event_tdoa: max_frames must be >= 1, got %d", max_frames);
-    SED_REQUIRE(time_factor >= 1 && hop >= 1 && R >= 1 && E >= 0, "event_tdoa: bad sizes (time_factor=%d, hop=%d, R=%d, E=%ld)",
+int tdoa_linear_entry(const char* who, const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const void* tables,
+                      size_t tables_bytes, const int* ev_rec, const int* ev_onset, const int* ev_offset, const int* ev_peak_frame,
+                      long E, int time_factor, int hop, int pad_mode, int max_lag, int max_frames, float* lag_out, float* strength_out,
+                      int* frames_out, float* acc_out, void* workspace, size_t workspace_bytes, void* stream, TdSliceHook hook,
+                      void* hook_ctx) {
+    SED_REQUIRE(channels >= 2 && channels <= TD_MAX_CH, "%s: 2 to %d channels, got %d", who, TD_MAX_CH, channels);
+    SED_REQUIRE(max_lag >= 1 && max_lag <= TD_MAX_LAG, "%s: max_lag must be in [1,%d], got %d", who, TD_MAX_LAG, max_lag);
+    SED_REQUIRE(max_frames >= 1, "%s: max_frames must be >= 1, got %d", who, max_frames);
+    SED_REQUIRE(time_factor >= 1 && hop >= 1 && R >= 1 && E >= 0, "%s: bad sizes (time_factor=%d, hop=%d, R=%d, E=%ld)", who,
                 time_factor, hop, R, E);
-    SED_REQUIRE(pad_mode == 0 || pad_mode == 1, "event_tdoa: pad_mode must be 0 (constant) or 1 (reflect), got %d", pad_mode);
-    SED_REQUIRE(pcm && clips_host && tables && pcm_len > 0, "event_tdoa: null pointer");
-    SED_REQUIRE(tables_bytes % 16 == 0 && tables_bytes / 4 >= (size_t)TD_TAB_WORDS, "event_tdoa: table blob of %zu bytes is malformed", tables_bytes);
+    SED_REQUIRE(pad_mode == 0 || pad_mode == 1, "%s: pad_mode must be 0 (constant) or 1 (reflect), got %d", who, pad_mode);
+    SED_REQUIRE(pcm && clips_host && tables && pcm_len > 0, "%s: null pointer", who);
+    SED_REQUIRE(tables_bytes % 16 == 0 && tables_bytes / 4 >= (size_t)TD_TAB_WORDS, "%s: table blob of %zu bytes is malformed", who, tables_bytes);
 
     // the recordings: bounds and equal channel lengths, on the host, before anything is enqueued
     std::vector<long> h((size_t)R * channels + R);
@@ -469,20 +431,30 @@ extern "C" int sed_event_tdoa(const float* pcm, long pcm_len, const long* clips_
         for (int ch = 0; ch < channels; ++ch) {
             const long c = (long)r * channels + ch, o = clips_host[2 * c], n = clips_host[2 * c + 1];
             SED_REQUIRE(o >= 0 && n >= 1 && o <= pcm_len && n <= pcm_len - o,
-                        "event_tdoa: recording %d, channel %d (offset %ld, %ld samples) is not inside the PCM buffer of %ld samples", r, ch,
+                        "%s: recording %d, channel %d (offset %ld, %ld samples) is not inside the PCM buffer of %ld samples", who, r, ch,
                         o, n, pcm_len);
-            SED_REQUIRE(n == n0, "event_tdoa: recording %d: channel %d has %ld samples, channel 0 has %ld (the channels of a recording "
-                        "must have equal length)", r, ch, n, n0);
+            SED_REQUIRE(n == n0, "%s: recording %d: channel %d has %ld samples, channel 0 has %ld (the channels of a recording "
+                        "must have equal length)", who, r, ch, n, n0);
             soff[c] = o;
         }
         slen[r] = n0;
-        SED_REQUIRE(1 + n0 / hop <= 0x7fffffffL, "event_tdoa: recording %d has more than 2^31 - 1 feature frames", r);
+        SED_REQUIRE(1 + n0 / hop <= 0x7fffffffL, "%s: recording %d has more than 2^31 - 1 feature frames", who, r);
         if (n0 > longest) longest = n0;
     }
     if (E == 0) return 0;                                        // nothing to launch
-    return tdoa_run<false>("event_tdoa", pcm, h, tdoa_table_bytes(R, channels), longest, 0, 0, 0, R, channels, tables, ev_rec, ev_onset,
+    return tdoa_run<false>(who, pcm, h, tdoa_table_bytes(R, channels), longest, 0, 0, 0, R, channels, tables, ev_rec, ev_onset,
                            ev_offset, ev_peak_frame, E, time_factor, hop, pad_mode, max_lag, max_frames, lag_out, strength_out,
-                           frames_out, acc_out, workspace, workspace_bytes, stream);
+                           frames_out, acc_out, workspace, workspace_bytes, stream, hook, hook_ctx);
+}
+
+extern "C" int sed_event_tdoa(const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const void* tables,
+                              size_t tables_bytes, const int* ev_rec, const int* ev_onset, const int* ev_offset,
+                              const int* ev_peak_frame, long E, int time_factor, int hop, int pad_mode, int max_lag, int max_frames,
+                              float* lag_out, float* strength_out, int* frames_out, float* acc_out, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    return tdoa_linear_entry("event_tdoa", pcm, pcm_len, clips_host, R, channels, tables, tables_bytes, ev_rec, ev_onset, ev_offset,
+                             ev_peak_frame, E, time_factor, hop, pad_mode, max_lag, max_frames, lag_out, strength_out, frames_out, acc_out,
+                             workspace, workspace_bytes, stream, nullptr, nullptr);
 }
 
 // ───────────────────────── live feeds ─────────────────────────
@@ -528,34 +500,43 @@ extern "C" size_t sed_event_tdoa_ring_workspace_bytes(int R, int channels, long 
     return tdoa_ring_table_bytes(R) + (size_t)E * cpe * P * TD_ROW_BYTES;
 }
 
+int tdoa_ring_entry(const char* who, const float* ring, long ring_len, long cap, const long* n_host, int R, int channels,
+                    const void* tables, size_t tables_bytes, const int* ev_rec, const int* ev_onset, const int* ev_offset,
+                    const int* ev_peak_frame, long E, int time_factor, int hop, int max_lag, int max_frames, int lat_frames,
+                    int history_frames, float* lag_out, float* strength_out, int* frames_out, float* acc_out, void* workspace,
+                    size_t workspace_bytes, void* stream, TdSliceHook hook, void* hook_ctx) {
+    SED_REQUIRE(channels >= 2 && channels <= TD_MAX_CH, "%s: 2 to %d channels, got %d", who, TD_MAX_CH, channels);
+    SED_REQUIRE(max_lag >= 1 && max_lag <= TD_MAX_LAG, "%s: max_lag must be in [1,%d], got %d", who, TD_MAX_LAG, max_lag);
+    SED_REQUIRE(max_frames >= 1, "%s: max_frames must be >= 1, got %d", who, max_frames);
+    SED_REQUIRE(time_factor >= 1 && hop >= 1 && R >= 1 && E >= 0, "%s: bad sizes (time_factor=%d, hop=%d, R=%d, E=%ld)", who,
+                time_factor, hop, R, E);
+    SED_REQUIRE(lat_frames >= 0 && history_frames >= 1, "%s: need lat_frames >= 0 and history_frames >= 1, got %d, %d", who,
+                lat_frames, history_frames);
+    SED_REQUIRE(ring && n_host && tables, "%s: null pointer", who);
+    SED_REQUIRE(cap >= LM_NFFT && cap % 4 == 0, "%s: a ring holds a multiple of 4 samples and at least one frame of %d, got "
+                "cap=%ld", who, LM_NFFT, cap);
+    SED_REQUIRE(ring_len >= 0 && cap <= ring_len / ((long)R * channels), "%s: %d feeds of %d rings of %ld samples leave "
+                "the buffer of %ld", who, R, channels, cap, ring_len);
+    SED_REQUIRE(((uintptr_t)ring & 15) == 0, "%s: the rings must be 16-byte aligned", who);
+    SED_REQUIRE(tables_bytes % 16 == 0 && tables_bytes / 4 >= (size_t)TD_TAB_WORDS, "%s: table blob of %zu bytes is malformed", who, tables_bytes);
+    std::vector<long> h(R);
+    for (int r = 0; r < R; ++r) {
+        h[r] = n_host[r];
+        SED_REQUIRE(h[r] >= 0 && 1 + h[r] / hop <= 0x7fffffffL, "%s: feed %d: %ld samples received (negative, or more than "
+                    "2^31 - 1 feature frames)", who, r, h[r]);
+    }
+    if (E == 0) return 0;                                        // nothing to launch
+    return tdoa_run<true>(who, ring, h, tdoa_ring_table_bytes(R), cap, cap, lat_frames, history_frames, R, channels, tables,
+                          ev_rec, ev_onset, ev_offset, ev_peak_frame, E, time_factor, hop, 0, max_lag, max_frames, lag_out, strength_out,
+                          frames_out, acc_out, workspace, workspace_bytes, stream, hook, hook_ctx);
+}
+
 extern "C" int sed_event_tdoa_ring(const float* ring, long ring_len, long cap, const long* n_host, int R, int channels,
                                    const void* tables, size_t tables_bytes, const int* ev_rec, const int* ev_onset,
                                    const int* ev_offset, const int* ev_peak_frame, long E, int time_factor, int hop, int max_lag,
                                    int max_frames, int lat_frames, int history_frames, float* lag_out, float* strength_out,
                                    int* frames_out, float* acc_out, void* workspace, size_t workspace_bytes, void* stream) {
-    SED_REQUIRE(channels >= 2 && channels <= TD_MAX_CH, "event_tdoa_ring: 2 to %d channels, got %d", TD_MAX_CH, channels);
-    SED_REQUIRE(max_lag >= 1 && max_lag <= TD_MAX_LAG, "event_tdoa_ring: max_lag must be in [1,%d], got %d", TD_MAX_LAG, max_lag);
-    SED_REQUIRE(max_frames >= 1, "event_tdoa_ring: max_frames must be >= 1, got %d", max_frames);
-    SED_REQUIRE(time_factor >= 1 && hop >= 1 && R >= 1 && E >= 0, "event_tdoa_ring: bad sizes (time_factor=%d, hop=%d, R=%d, E=%ld)",
-                time_factor, hop, R, E);
-    SED_REQUIRE(lat_frames >= 0 && history_frames >= 1, "event_tdoa_ring: need lat_frames >= 0 and history_frames >= 1, got %d, %d",
-                lat_frames, history_frames);
-    SED_REQUIRE(ring && n_host && tables, "event_tdoa_ring: null pointer");
-    SED_REQUIRE(cap >= LM_NFFT && cap % 4 == 0, "event_tdoa_ring: a ring holds a multiple of 4 samples and at least one frame of %d, got "
-                "cap=%ld", LM_NFFT, cap);
-    SED_REQUIRE(ring_len >= 0 && cap <= ring_len / ((long)R * channels), "event_tdoa_ring: %d feeds of %d rings of %ld samples leave "
-                "the buffer of %ld", R, channels, cap, ring_len);
-    SED_REQUIRE(((uintptr_t)ring & 15) == 0, "event_tdoa_ring: the rings must be 16-byte aligned");
-    SED_REQUIRE(tables_bytes % 16 == 0 && tables_bytes / 4 >= (size_t)TD_TAB_WORDS, "event_tdoa_ring: table blob of %zu bytes is malformed", tables_bytes);
-    std::vector<long> h(R);
-    for (int r = 0; r < R; ++r) {
-        h[r] = n_host[r];
-        SED_REQUIRE(h[r] >= 0 && 1 + h[r] / hop <= 0x7fffffffL, "event_tdoa_ring: feed %d: %ld samples received (negative, or more than "
-                    "2^31 - 1 feature frames)", r, h[r]);
-    }
-    if (E == 0) return 0;                                        // nothing to launch
-    return tdoa_run<true>("event_tdoa_ring", ring, h, tdoa_ring_table_bytes(R), cap, cap, lat_frames, history_frames, R, channels, tables,
-                          ev_rec, ev_onset, ev_offset, ev_peak_frame, E, time_factor, hop, 0, max_lag, max_frames, lag_out, strength_out,
-                          frames_out, acc_out, workspace, workspace_bytes, stream);
+    return tdoa_ring_entry("event_tdoa_ring", ring, ring_len, cap, n_host, R, channels, tables, tables_bytes, ev_rec, ev_onset, ev_offset,
+                           ev_peak_frame, E, time_factor, hop, max_lag, max_frames, lat_frames, history_frames, lag_out, strength_out,
+                           frames_out, acc_out, workspace, workspace_bytes, stream, nullptr, nullptr);
 }
-

@@ -27,6 +27,18 @@ from .model import HipCRNN
 
 _EVENT_KEYS = ("cls", "onset", "offset", "peak", "peak_frame")
 _TDOA_KEYS = ("lag", "strength", "loc_frames")          # added to the events of a localising detector (DESIGN 5o)
+_DOA_KEYS = ("dir", "doa_power")                        # ... and, with localize=DOA(...), a direction per event (DESIGN 5q)
+
+
+def _doa_angles(events, grid, k):
+    """[E_k, 3] host float64: azimuth, elevation (radians) and power of the events of class ``k`` (None: all); NaN rows where
+    an event was not located (``dir`` = -1)"""
+    d = events["dir"].cpu().numpy().astype(np.int64)
+    out = np.full((d.shape[0], 3), np.nan)
+    ok = d >= 0
+    out[ok, 0], out[ok, 1] = grid.azimuth[d[ok]], grid.elevation[d[ok]]
+    out[ok, 2] = events["doa_power"].cpu().numpy().astype(np.float64)[ok]
+    return out if k is None else out[events["cls"].cpu().numpy() == int(k)]
 
 
 def _is_per_class(v):
@@ -221,9 +233,10 @@ class DetectionResult:
     """``probs`` [n_out, K] device track; ``events`` dict of device tensors (``cls``, ``onset``, ``offset``, ``peak_frame``
     int32 output frames, offset exclusive; ``peak`` float32), sorted by (class, onset); ``frame_seconds`` = tf*hop_length/sr."""
 
-    def __init__(self, probs, events, frame_seconds, plan, sr=None):
+    def __init__(self, probs, events, frame_seconds, plan, sr=None, grid=None):
         self.probs, self.events, self.frame_seconds, self.plan = probs, events, frame_seconds, plan
         self.sr = sr                            # the detector's rate: set on located results (lags are in samples at that rate)
+        self.grid = grid                        # the DirectionGrid that ``dir`` indexes: set on results located with DOA settings
 
     def __len__(self):
         return int(self.events["cls"].numel())
@@ -242,6 +255,16 @@ class DetectionResult:
         lag = self.events["lag"].cpu().numpy().astype(np.float64) / float(self.sr)
         return lag if k is None else lag[self.events["cls"].cpu().numpy() == int(k)]
 
+    def doa(self, k=None):
+        """directions of arrival, a host array [E_k, 3] (events of class ``k``; None: all events, in event order): azimuth and
+        elevation in radians (``u = (cos el cos az, cos el sin az, sin el)`` points from the array to the source) and the
+        steered response power per pair and frame, in [-1, 1]; NaN where an event was not located.  Only on the result of a
+        detector with ``localize=DOA(...)``."""
+        if "dir" not in self.events or self.grid is None:
+            raise ValueError("this result holds no directions: detect with EventDetector(..., localize=sed.DOA(...)) or pass it "
+                             "through det.localize(result, waveform, ...)")
+        return _doa_angles(self.events, self.grid, k)
+
 
 class BatchDetectionResult:
     """R recordings detected together.  ``len()`` = R; ``res[i]`` = a DetectionResult view of recording i (its slice of the
@@ -249,10 +272,10 @@ class BatchDetectionResult:
     ``events`` dict of device tensors with ``rec`` (sorted by recording, class, onset), and the host lists ``out_offsets``
     [R+1] (recording i = rows [out_offsets[i], out_offsets[i+1])) and ``event_offsets`` [R+1]."""
 
-    def __init__(self, probs, events, frame_seconds, plans, out_offsets, event_offsets, sr=None):
+    def __init__(self, probs, events, frame_seconds, plans, out_offsets, event_offsets, sr=None, grid=None):
         self.probs, self.events, self.frame_seconds, self.plans = probs, events, frame_seconds, tuple(plans)
         self.out_offsets, self.event_offsets = list(out_offsets), list(event_offsets)
-        self.sr = sr                            # as in DetectionResult
+        self.sr, self.grid = sr, grid           # as in DetectionResult
 
     def __len__(self):
         return len(self.plans)
@@ -264,8 +287,9 @@ class BatchDetectionResult:
         i = int(i) % R
         o0, o1 = self.out_offsets[i], self.out_offsets[i + 1]
         e0, e1 = self.event_offsets[i], self.event_offsets[i + 1]
-        keys = _EVENT_KEYS + tuple(k for k in _TDOA_KEYS if k in self.events)
-        return DetectionResult(self.probs[o0:o1], {k: self.events[k][e0:e1] for k in keys}, self.frame_seconds, self.plans[i], self.sr)
+        keys = _EVENT_KEYS + tuple(k for k in _TDOA_KEYS + _DOA_KEYS if k in self.events)
+        return DetectionResult(self.probs[o0:o1], {k: self.events[k][e0:e1] for k in keys}, self.frame_seconds, self.plans[i], self.sr,
+                               self.grid)
 
     def __iter__(self):
         return (self[i] for i in range(len(self)))
@@ -295,7 +319,10 @@ class EventDetector:
     net that reads at least 2 audio channels, ``det(wave, sr=, channels=C)`` and ``detect_many`` keep the resampled planar PCM
     until the decode is done and return events that also hold ``lag`` [E, P] (samples at the detector's rate, one column per
     microphone pair; ``result.tdoa()`` in seconds), ``strength`` [E, P] and ``loc_frames`` [E] (``feature.event_tdoa``);
-    ``from_features*`` has no audio and returns un-located events, which ``det.localize(result, waveform, ...)`` locates."""
+    ``from_features*`` has no audio and returns un-located events, which ``det.localize(result, waveform, ...)`` locates.
+    ``localize=sed.DOA(positions, grid, ...)`` for a known array: the same three keys, with ``max_lag`` taken from the
+    array's aperture, and ``dir`` [E] (a row of ``grid``, -1: not located) and ``doa_power`` [E] (``feature.event_doa``;
+    ``result.doa()`` in radians)."""
 
     def __init__(self, model, seq_len=SEQ_LEN_IN, hop=None, combine="mean", trim=0, threshold=0.5, low=None, median=1,
                  min_gap=0, min_len=1, mean=None, std=None, sr=feature.SR, hop_length=feature.HOP, max_batch=1024, spatial=None,
@@ -316,13 +343,21 @@ class EventDetector:
                                  f"the net has in_channels={model.in_channels}")
             if model.n_mels % 2:
                 raise ValueError(f"spatial={spatial!r} writes n_mels lags per pair and needs an even count, the net has n_mels={model.n_mels}")
-        from .localize import TDOA
-        if localize is not None and not isinstance(localize, TDOA):
-            raise TypeError(f"localize must be None or a TDOA(...) settings object, got {type(localize).__name__}")
+        from .localize import DOA, TDOA
+        if localize is not None and not isinstance(localize, (TDOA, DOA)):
+            raise TypeError(f"localize must be None, a TDOA(...) or a DOA(...) settings object, got {type(localize).__name__}")
         if localize is not None and not 2 <= self.audio_channels <= feature.GCC_MAX_CHANNELS:
             raise ValueError(f"localize= needs a net that reads 2 to {feature.GCC_MAX_CHANNELS} audio channels (one time difference per "
                              f"microphone pair), this one reads {self.audio_channels}")
-        self.localize_settings = localize                    # per-event TDOA settings of the waveform entry points, or None
+        if isinstance(localize, DOA):
+            if localize.channels != self.audio_channels:
+                raise ValueError(f"localize=DOA(...) holds {localize.channels} microphone positions, the net reads {self.audio_channels} "
+                                 f"audio channels")
+            localize.plan(sr)                                # (an aperture of more than 127 samples at this rate is refused here)
+        # per-event TDOA or DOA (5q) settings of the waveform entry points, or None; ``localize_tdoa``: the TDOA
+        # settings either of them means
+        self.localize_settings = localize
+        self.localize_tdoa = localize.tdoa(sr) if isinstance(localize, DOA) else localize
         if combine not in ("mean", "max"):
             raise ValueError(f"combine must be 'mean' or 'max', got {combine!r}")
         K = model.dense[-1]
@@ -498,11 +533,22 @@ class EventDetector:
         and ``sr`` set: ``feature.event_tdoa`` on the planar PCM at the detector's rate that the events were detected in"""
         t = self.localize_settings
         with torch.no_grad():
-            loc = feature.event_tdoa(pcm, clips, self.audio_channels, result.events, self.model.time_factor, max_lag=t.max_lag,
-                                     max_frames=t.max_frames, hop=self.hop_length)
-        result.events = {**{k: v for k, v in result.events.items() if k not in _TDOA_KEYS}, **loc}
+            if self.locates_directions:
+                loc = feature.event_doa(pcm, clips, self.audio_channels, result.events, self.model.time_factor, t, sr=self.sr,
+                                        hop=self.hop_length)
+                result.grid = t.grid
+            else:
+                loc = feature.event_tdoa(pcm, clips, self.audio_channels, result.events, self.model.time_factor, max_lag=t.max_lag,
+                                         max_frames=t.max_frames, hop=self.hop_length)
+        result.events = {**{k: v for k, v in result.events.items() if k not in _TDOA_KEYS + _DOA_KEYS}, **loc}
         result.sr = self.sr
         return result
+
+    @property
+    def locates_directions(self):
+        """whether the localisation settings are ``DOA(...)``: the events also hold ``dir`` and ``doa_power``"""
+        from .localize import DOA
+        return isinstance(self.localize_settings, DOA)
 
     def localize(self, result, waveforms, sr=None, channels=None):
         """Locate events that were detected without their audio at hand (``from_features*``): ``result`` — a DetectionResult with
@@ -525,6 +571,7 @@ class EventDetector:
         if not waves:
             result.events = {**result.events, **self._no_lags()}
             result.sr = self.sr
+            result.grid = self.localize_settings.grid if self.locates_directions else None
             return result
         from .resample import resample_many
         pcm, clips = resample_many(waves, self.sr if sr is None else sr, self.sr, channels, self.model.flat_parameters().device,
@@ -719,13 +766,17 @@ class EventDetector:
         if self.localize_settings is not None:
             ev.update(self._no_lags())
         return BatchDetectionResult(torch.empty(0, m.dense[-1], device=dev), ev, self.frame_seconds, (), [0], [0],
-                                    self.sr if self.localize_settings is not None else None)
+                                    self.sr if self.localize_settings is not None else None,
+                                    self.localize_settings.grid if self.locates_directions else None)
 
     def _no_lags(self):
-        """the three localisation columns of an empty event table"""
+        """the localisation columns of an empty event table"""
         dev, P = self.model.flat_parameters().device, self.audio_channels * (self.audio_channels - 1) // 2
-        return {"lag": torch.empty(0, P, device=dev), "strength": torch.empty(0, P, device=dev),
-                "loc_frames": torch.empty(0, dtype=torch.int32, device=dev)}
+        out = {"lag": torch.empty(0, P, device=dev), "strength": torch.empty(0, P, device=dev),
+               "loc_frames": torch.empty(0, dtype=torch.int32, device=dev)}
+        if self.locates_directions:
+            out.update(dir=torch.empty(0, dtype=torch.int32, device=dev), doa_power=torch.empty(0, device=dev))
+        return out
 
     def _detect_packed(self, mel, bp):
         logits = self.window_logits_many(mel, bp)

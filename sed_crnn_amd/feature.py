@@ -441,8 +441,59 @@ def _tdoa_io(events, R, rec_key, nc, max_lag, return_curve, dev):
     return col, E, out
 
 
+def _doa_plan(doa, nc, sr):
+    """checks the settings of a DOA call (a ``localize.DOA`` for ``nc`` channels) -> its max_lag at rate ``sr``"""
+    from .localize import DOA
+    if not isinstance(doa, DOA):
+        raise TypeError(f"event_doa takes the settings as a sed.DOA(...) object, got {type(doa).__name__}")
+    if doa.channels != nc:
+        raise ValueError(f"the DOA settings hold {doa.channels} microphone positions, the audio has {nc} channels")
+    return doa.plan(sr)[0]
+
+
+def _doa_io(doa, sr, E, dev, out, return_map):
+    """the steering tables of ``doa`` at rate ``sr`` on ``dev`` (uploaded once per device and rate) and, added to ``out``, the
+    outputs a DOA call adds -> [J, D, Q, trig, dir, doa_power, srp or None] as the C entries take them (None without events)"""
+    _, J, trig = doa.plan(sr)
+    out["dir"] = torch.empty(E, dtype=torch.int32, device=dev)
+    out["doa_power"] = torch.empty(E, device=dev)
+    if return_map:
+        out["srp"] = torch.empty(E, J.shape[0], device=dev)
+    if E == 0:
+        return None
+    key = (dev.index or 0, float(sr))
+    if key not in doa._device:
+        doa._device[key] = (torch.from_numpy(J).to(dev), torch.from_numpy(trig).to(dev))
+    Jd, td = doa._device[key]
+    return [ptr(Jd), J.shape[0], doa.oversample, ptr(td), ptr(out["dir"]), ptr(out["doa_power"]), ptr(out.get("srp"))]
+
+
+def event_doa(pcm, clips, channels, events, time_factor, doa, sr=SR, hop=HOP, pad_mode="constant", return_curve=False,
+              return_map=False, max_workspace_bytes=128 << 20):
+    """Per-event direction of arrival for a known array (``sed_event_doa``): ``event_tdoa`` with ``max_lag`` and
+    ``max_frames`` taken from ``doa`` (a ``sed.DOA(positions, grid, ...)``; ``sr``: the rate of the PCM), and for every event
+    the direction of ``doa.grid`` with the largest steered response power, summed over all microphone pairs at lags of
+    ``1 / doa.oversample`` sample.  Returns the dict of ``event_tdoa`` — the same bits — with ``dir`` int32 [E] (a row of the
+    grid; -1: the event has no frames, or digital silence) and ``doa_power`` float32 [E] (the response per pair and frame at
+    that direction, in [-1, 1]; 0 where ``dir`` is -1); ``return_map=True`` adds ``srp`` float32 [E, D], the response at every
+    direction (secondary peaks are other sources or reflections).  One more launch per slice; the host reads nothing back."""
+    return event_tdoa(pcm, clips, channels, events, time_factor, max_frames=getattr(doa, "max_frames", 256),
+                      hop=hop, pad_mode=pad_mode, return_curve=return_curve, max_workspace_bytes=max_workspace_bytes,
+                      _doa=(doa, sr, return_map))
+
+
+def event_doa_ring(ring, cap, n, channels, events, time_factor, doa, sr=SR, hop=HOP, lat_frames=0, history_frames=0x7fffffff,
+                   return_curve=False, return_map=False, max_workspace_bytes=128 << 20):
+    """``event_doa`` on the PCM rings of live feeds (``sed_event_doa_ring``): the arguments and rules of
+    ``event_tdoa_ring``, the outputs of ``event_doa``; an event the stream's rule or the ring's depth refuses has ``dir = -1``
+    and ``doa_power = 0``.  A located event gets, bit for bit, what ``event_doa`` gives on the feed's samples laid out linearly."""
+    return event_tdoa_ring(ring, cap, n, channels, events, time_factor, max_frames=getattr(doa, "max_frames", 256),
+                           hop=hop, lat_frames=lat_frames, history_frames=history_frames, return_curve=return_curve,
+                           max_workspace_bytes=max_workspace_bytes, _doa=(doa, sr, return_map))
+
+
 def event_tdoa(pcm, clips, channels, events, time_factor, max_lag=24, max_frames=256, hop=HOP, pad_mode="constant",
-               return_curve=False, max_workspace_bytes=128 << 20):
+               return_curve=False, max_workspace_bytes=128 << 20, _doa=None):
     """Per-event time difference of arrival (``sed_event_tdoa``).  ``pcm`` / ``clips`` / ``channels``: R recordings of
     2..8 planar channels in one float32 CUDA buffer, as ``mbe_planar`` takes them.  ``events``: a dict of int32 device tensors
     ``onset``, ``offset`` (exclusive), ``peak_frame`` in output frames of ``time_factor`` feature frames, as the decoders return
@@ -465,6 +516,8 @@ def event_tdoa(pcm, clips, channels, events, time_factor, max_lag=24, max_frames
     if pad_mode not in ("constant", "reflect"):
         raise ValueError(f"pad_mode must be 'constant' or 'reflect', got {pad_mode!r}")
     nc, tf, max_lag, max_frames, hop = int(channels), int(time_factor), int(max_lag), int(max_frames), int(hop)
+    if _doa is not None:                                              # (doa, sr, return_map) of event_doa: its max_lag
+        max_lag = _doa_plan(_doa[0], nc, _doa[1])
     if not 2 <= nc <= GCC_MAX_CHANNELS:
         raise ValueError(f"event_tdoa needs 2 to {GCC_MAX_CHANNELS} audio channels (one estimate per microphone pair), got channels={nc}")
     if not 1 <= max_lag <= MAX_LAG_LIMIT or max_frames < 1 or tf < 1 or hop < 1:
@@ -482,6 +535,7 @@ def event_tdoa(pcm, clips, channels, events, time_factor, max_lag=24, max_frames
             raise ValueError(f"recording {i // nc}: channel {i % nc} has {n} samples, channel 0 has {int(table[i - i % nc, 1])}")
     dev = pcm.device
     col, E, out = _tdoa_io(events, R, "rec", nc, max_lag, return_curve, dev)
+    extra = _doa_io(_doa[0], _doa[1], E, dev, out, _doa[2]) if _doa is not None else None
     if E == 0:
         return out
     pcm = pcm.contiguous().float()
@@ -492,10 +546,13 @@ def event_tdoa(pcm, clips, channels, events, time_factor, max_lag=24, max_frames
     if need_one == 0:
         raise ValueError(f"sed_event_tdoa_workspace_bytes refuses R={R}, channels={nc}, hop={hop}, max_frames={max_frames}")
     ws = torch.empty(min(need_all, max(need_one, int(max_workspace_bytes))), dtype=torch.uint8, device=dev)
-    check(lib().sed_event_tdoa(ptr(pcm), pcm.numel(), C.c_void_p(table.ctypes.data), R, nc, ptr(tables), tables.numel() * 4,
-                               ptr(col.get("rec")), ptr(col["onset"]), ptr(col["offset"]), ptr(col["peak_frame"]), E, tf, hop,
-                               {"constant": 0, "reflect": 1}[pad_mode], max_lag, max_frames, ptr(out["lag"]), ptr(out["strength"]),
-                               ptr(out["loc_frames"]), ptr(out.get("acc")), ptr(ws), ws.numel(), stream_ptr()), "sed_event_tdoa")
+    args = [ptr(pcm), pcm.numel(), C.c_void_p(table.ctypes.data), R, nc, ptr(tables), tables.numel() * 4, ptr(col.get("rec")),
+            ptr(col["onset"]), ptr(col["offset"]), ptr(col["peak_frame"]), E, tf, hop, {"constant": 0, "reflect": 1}[pad_mode], max_lag,
+            max_frames, ptr(out["lag"]), ptr(out["strength"]), ptr(out["loc_frames"]), ptr(out.get("acc"))]
+    if _doa is None:
+        check(lib().sed_event_tdoa(*args, ptr(ws), ws.numel(), stream_ptr()), "sed_event_tdoa")
+    else:                                                             # the same launches and one more
+        check(lib().sed_event_doa(*args, *extra, ptr(ws), ws.numel(), stream_ptr()), "sed_event_doa")
     return out
 
 
@@ -530,7 +587,7 @@ def ring_write(ring, cap, src, table, workspace=None):
 
 
 def event_tdoa_ring(ring, cap, n, channels, events, time_factor, max_lag=24, max_frames=256, hop=HOP, lat_frames=0,
-                    history_frames=0x7fffffff, return_curve=False, max_workspace_bytes=128 << 20):
+                    history_frames=0x7fffffff, return_curve=False, max_workspace_bytes=128 << 20, _doa=None):
     """``event_tdoa`` on the PCM rings of live feeds (``sed_event_tdoa_ring``).  ``ring`` / ``cap`` as ``ring_write``
     fills them: feed r's ``channels`` lanes are the rings ``r*channels + c``; ``n`` [R] host ints: the samples feed r has
     received.  ``events`` as ``event_tdoa`` takes them; the feed of an event is its ``rec`` — or ``stream`` — column (needed
@@ -546,6 +603,8 @@ def event_tdoa_ring(ring, cap, n, channels, events, time_factor, max_lag=24, max
         raise RuntimeError("sed_crnn_amd.feature.event_tdoa_ring needs a contiguous 1-D float32 CUDA(HIP) ring buffer; there is no CPU fallback")
     nc, tf, max_lag, max_frames, hop, cap = int(channels), int(time_factor), int(max_lag), int(max_frames), int(hop), int(cap)
     lat, hist = int(lat_frames), int(history_frames)
+    if _doa is not None:                                              # (doa, sr, return_map) of event_doa_ring: its max_lag
+        max_lag = _doa_plan(_doa[0], nc, _doa[1])
     if not 2 <= nc <= GCC_MAX_CHANNELS:
         raise ValueError(f"event_tdoa_ring needs 2 to {GCC_MAX_CHANNELS} audio channels (one estimate per microphone pair), got channels={nc}")
     if not 1 <= max_lag <= MAX_LAG_LIMIT or max_frames < 1 or tf < 1 or hop < 1 or lat < 0 or hist < 1:
@@ -562,6 +621,7 @@ def event_tdoa_ring(ring, cap, n, channels, events, time_factor, max_lag=24, max
     dev = ring.device
     rec_key = "stream" if "stream" in events and "rec" not in events else "rec"
     col, E, out = _tdoa_io(events, R, rec_key, nc, max_lag, return_curve, dev)
+    extra = _doa_io(_doa[0], _doa[1], E, dev, out, _doa[2]) if _doa is not None else None
     if E == 0:
         return out
     tables = _tables(dev.index or 0, SR, NFFT, NB_MEL)                # the window and the twiddles; the mel plan is not read
@@ -570,10 +630,13 @@ def event_tdoa_ring(ring, cap, n, channels, events, time_factor, max_lag=24, max
     if need_one == 0:
         raise ValueError(f"sed_event_tdoa_ring_workspace_bytes refuses R={R}, channels={nc}, cap={cap}, hop={hop}, max_frames={max_frames}")
     ws = torch.empty(min(need_all, max(need_one, int(max_workspace_bytes))), dtype=torch.uint8, device=dev)
-    check(lib().sed_event_tdoa_ring(ptr(ring), ring.numel(), cap, C.c_void_p(n.ctypes.data), R, nc, ptr(tables), tables.numel() * 4,
-                                    ptr(col.get("rec")), ptr(col["onset"]), ptr(col["offset"]), ptr(col["peak_frame"]), E, tf, hop,
-                                    max_lag, max_frames, lat, hist, ptr(out["lag"]), ptr(out["strength"]), ptr(out["loc_frames"]),
-                                    ptr(out.get("acc")), ptr(ws), ws.numel(), stream_ptr()), "sed_event_tdoa_ring")
+    args = [ptr(ring), ring.numel(), cap, C.c_void_p(n.ctypes.data), R, nc, ptr(tables), tables.numel() * 4, ptr(col.get("rec")),
+            ptr(col["onset"]), ptr(col["offset"]), ptr(col["peak_frame"]), E, tf, hop, max_lag, max_frames, lat, hist, ptr(out["lag"]),
+            ptr(out["strength"]), ptr(out["loc_frames"]), ptr(out.get("acc"))]
+    if _doa is None:
+        check(lib().sed_event_tdoa_ring(*args, ptr(ws), ws.numel(), stream_ptr()), "sed_event_tdoa_ring")
+    else:
+        check(lib().sed_event_doa_ring(*args, *extra, ptr(ws), ws.numel(), stream_ptr()), "sed_event_doa_ring")
     return out
 
 

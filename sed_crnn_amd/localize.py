@@ -5,7 +5,10 @@ entry ``feature.event_tdoa``).
 device.  ``stream_latency_frames``, ``stream_ring_samples`` and ``stream_locates`` are the arithmetic of a localising live
 stream: how late an event is emitted, how many samples a lane keeps, and which events are located.  ``TDOA`` holds
 the two settings of ``EventDetector(..., localize=TDOA(...))``.  ``max_lag_for`` and ``tdoa_to_azimuth`` are the far-field
-geometry of ONE microphone pair; combining pairs into a direction for a given array is left to the caller.
+geometry of ONE microphone pair.  ``DirectionGrid``, ``steering_lags`` and ``DOA`` are the host side of per-event direction of
+arrival for a known array (the kernel is csrc/doa.hip, the device entry ``feature.event_doa``): the directions that
+are searched, the time difference every direction means for every microphone pair, and the settings of
+``EventDetector(..., localize=DOA(positions, grid))``.
 """
 import dataclasses
 import math
@@ -14,6 +17,9 @@ import numpy as np
 
 MAX_LAG_LIMIT = 127        # tdoa.hip: TD_MAX_LAG
 SPEED_OF_SOUND = 343.0     # m/s in air at 20 degrees C
+MAX_CHANNELS = 8           # tdoa.hip: TD_MAX_CH
+MAX_DIRECTIONS = 16384     # doa.hip: DOA_MAX_DIRS
+OVERSAMPLE_CHOICES = (1, 2, 4, 8, 16)
 
 
 def event_frames(onset, offset, peak_frame, time_factor, n_feat, max_frames=256):
@@ -103,3 +109,147 @@ def tdoa_to_azimuth(tdoa_seconds, spacing_m, c=SPEED_OF_SOUND):
     if not spacing_m > 0 or not c > 0:
         raise ValueError(f"tdoa_to_azimuth needs spacing_m > 0 and c > 0, got {spacing_m}, {c}")
     return np.arcsin(np.clip(np.asarray(tdoa_seconds, dtype=np.float64) * (float(c) / float(spacing_m)), -1.0, 1.0))
+
+
+# ── direction of arrival for a known array ──
+class DirectionGrid:
+    """The directions a ``DOA`` searches: ``unit_vectors`` [D, 3], each pointing from the array towards a source,
+    ``u = (cos el cos az, cos el sin az, sin el)``; 1 <= D <= 16384.  ``.azimuth`` (in (-pi, pi]) and ``.elevation`` [D] are the
+    angles of the rows in radians.  ``ring`` and ``sphere`` build the two usual grids."""
+
+    def __init__(self, unit_vectors):
+        u = np.array(unit_vectors, dtype=np.float64)
+        if u.ndim != 2 or u.shape[1] != 3 or not 1 <= u.shape[0] <= MAX_DIRECTIONS:
+            raise ValueError(f"DirectionGrid: unit_vectors must be [D, 3] with 1 <= D <= {MAX_DIRECTIONS}, got shape {u.shape}")
+        if not np.isfinite(u).all():
+            raise ValueError("DirectionGrid: unit_vectors must be finite")
+        norm = np.sqrt((u * u).sum(1))
+        if np.abs(norm - 1.0).max() > 1e-6:
+            raise ValueError(f"DirectionGrid: every row must have unit norm (within 1e-6), got norms {norm.min():.6g} .. {norm.max():.6g}")
+        u.setflags(write=False)
+        self.unit_vectors = u
+        self.azimuth = np.arctan2(u[:, 1], u[:, 0])
+        self.elevation = np.arcsin(np.clip(u[:, 2], -1.0, 1.0))
+
+    def __len__(self):
+        return self.unit_vectors.shape[0]
+
+    @classmethod
+    def ring(cls, n_az, elevation=0.0):
+        """``n_az`` directions at one elevation (radians), azimuth ``2 pi i / n_az``: what a planar array can tell apart"""
+        n_az, el = int(n_az), float(elevation)
+        if not 1 <= n_az <= MAX_DIRECTIONS or not abs(el) <= math.pi / 2:
+            raise ValueError(f"DirectionGrid.ring needs 1 <= n_az <= {MAX_DIRECTIONS} and |elevation| <= pi/2, got {n_az}, {elevation}")
+        az = 2.0 * math.pi * np.arange(n_az) / n_az
+        return cls(np.stack([math.cos(el) * np.cos(az), math.cos(el) * np.sin(az), np.full(n_az, math.sin(el))], 1))
+
+    @classmethod
+    def sphere(cls, n):
+        """``n`` directions spread evenly over the whole sphere: the Fibonacci lattice ``z_i = 1 - (2 i + 1) / n``,
+        ``az_i = i pi (3 - sqrt 5)``"""
+        n = int(n)
+        if not 1 <= n <= MAX_DIRECTIONS:
+            raise ValueError(f"DirectionGrid.sphere needs 1 <= n <= {MAX_DIRECTIONS}, got {n}")
+        i = np.arange(n)
+        z = 1.0 - (2.0 * i + 1.0) / n
+        az = i * (math.pi * (3.0 - math.sqrt(5.0)))
+        rho = np.sqrt(np.maximum(0.0, 1.0 - z * z))
+        return cls(np.stack([rho * np.cos(az), rho * np.sin(az), z], 1))
+
+
+def _positions(positions, who):
+    r = np.array(positions, dtype=np.float64)
+    if r.ndim != 2 or r.shape[1] != 3 or not 2 <= r.shape[0] <= MAX_CHANNELS:
+        raise ValueError(f"{who}: positions must be [C, 3] metres with 2 <= C <= {MAX_CHANNELS} microphones, got shape {r.shape}")
+    if not np.isfinite(r).all():
+        raise ValueError(f"{who}: positions must be finite")
+    return r
+
+
+def _pairs(C):
+    return [(i, j) for i in range(C) for j in range(i + 1, C)]
+
+
+def steering_lags(positions, grid, sr, c=SPEED_OF_SOUND):
+    """``tau`` float64 [D, P]: the lag, in samples at rate ``sr`` and in the sign of ``event_tdoa`` (channel j delayed by n
+    samples gives -n), that a far-field source in direction ``grid.unit_vectors[d]`` produces in the pair p = (i, j), i < j in
+    lexicographic order, of microphones at ``positions`` [C, 3] (metres): ``sr (r_j - r_i) . u_d / c``"""
+    r = _positions(positions, "steering_lags")
+    if not isinstance(grid, DirectionGrid):
+        raise TypeError(f"steering_lags: grid must be a DirectionGrid, got {type(grid).__name__}")
+    if not float(sr) > 0 or not float(c) > 0 or not math.isfinite(float(sr)) or not math.isfinite(float(c)):
+        raise ValueError(f"steering_lags needs sr > 0 and c > 0, got {sr}, {c}")
+    base = np.stack([r[j] - r[i] for i, j in _pairs(r.shape[0])])                  # [P, 3]
+    return float(sr) * (grid.unit_vectors @ base.T) / float(c)
+
+
+def trig_table(oversample):
+    """float32 [512 Q + 1, 2]: ``(cos, sin)(2 pi k / (2048 Q))``, the quarter wave doa.hip unfolds; float64 values rounded once,
+    by the expression that makes the pairing twiddles of the log-mel tables (at Q = 1 the same values)"""
+    n = 2048 * int(oversample)
+    two_pi = 6.283185307179586476925286766559
+    a = [two_pi * float(k) / float(n) for k in range(n // 4 + 1)]
+    return np.array([[math.cos(x), math.sin(x)] for x in a], dtype=np.float64).astype(np.float32)
+
+
+class DOA:
+    """Settings of per-event direction of arrival (``EventDetector(model, ..., localize=DOA(positions, grid))``):
+    steered response power (SRP-PHAT) over ``grid`` for the microphones at ``positions`` [C, 3] (metres, in the order of the
+    audio channels).  ``oversample`` Q in {1, 2, 4, 8, 16}: the correlation of every pair is evaluated at lags of 1/Q sample,
+    exactly.  ``max_frames`` as in ``TDOA``; ``max_lag`` follows from the array: ``max_lag_for`` of its largest spacing at the
+    detector's rate, which must not exceed 127 samples.  ``c``: the speed of sound in m/s.  A detector with these settings
+    also returns everything a ``TDOA(max_lag, max_frames)`` detector returns."""
+
+    def __init__(self, positions, grid, max_frames=256, oversample=8, c=SPEED_OF_SOUND):
+        r = _positions(positions, "DOA")
+        if not isinstance(grid, DirectionGrid):
+            raise TypeError(f"DOA: grid must be a DirectionGrid, got {type(grid).__name__}")
+        for name, v in (("max_frames", max_frames), ("oversample", oversample)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"DOA: {name} must be an integer, got {v!r}")
+        if int(max_frames) < 1:
+            raise ValueError(f"DOA: max_frames must be >= 1, got {max_frames}")
+        if int(oversample) not in OVERSAMPLE_CHOICES:
+            raise ValueError(f"DOA: oversample must be one of {OVERSAMPLE_CHOICES}, got {oversample}")
+        if not (isinstance(c, (int, float, np.floating, np.integer)) and math.isfinite(float(c)) and float(c) > 0):
+            raise ValueError(f"DOA: the speed of sound c must be a positive number, got {c!r}")
+        dist = np.array([np.linalg.norm(r[j] - r[i]) for i, j in _pairs(r.shape[0])])
+        if dist.min() <= 0.0:
+            i, j = _pairs(r.shape[0])[int(dist.argmin())]
+            raise ValueError(f"DOA: microphones {i} and {j} are at the same position")
+        r.setflags(write=False)
+        self.positions, self.grid = r, grid
+        self.max_frames, self.oversample, self.c = int(max_frames), int(oversample), float(c)
+        self.aperture = float(dist.max())
+        self._plans, self._device = {}, {}                   # per rate: (max_lag, J, table); per (device, rate): their device copies
+
+    @property
+    def channels(self):
+        return self.positions.shape[0]
+
+    def max_lag(self, sr):
+        """``max_lag_for`` of the largest spacing at rate ``sr``; more than 127 samples is refused"""
+        ml = max_lag_for(self.aperture, sr, self.c)
+        if ml > MAX_LAG_LIMIT:
+            raise ValueError(f"DOA: an aperture of {self.aperture:.4g} m is {ml} samples at {sr} Hz (c = {self.c:g} m/s): more than the "
+                             f"{MAX_LAG_LIMIT} that are searched; use a smaller array or a lower rate")
+        return ml
+
+    def plan(self, sr):
+        """-> (max_lag, J int32 [D, P], trig float32 [512 Q + 1, 2]) at rate ``sr``: ``J = round_half_even(tau Q)``, every
+        ``|J| <= max_lag Q`` by construction"""
+        key = float(sr)
+        if key not in self._plans:
+            ml = self.max_lag(sr)
+            J = np.rint(steering_lags(self.positions, self.grid, sr, self.c) * self.oversample).astype(np.int32)
+            assert np.abs(J).max() <= ml * self.oversample
+            self._plans[key] = (ml, np.ascontiguousarray(J), trig_table(self.oversample))
+        return self._plans[key]
+
+    def tdoa(self, sr):
+        """the ``TDOA`` settings whose outputs a detector with these settings also returns"""
+        return TDOA(self.max_lag(sr), self.max_frames)
+
+    def __repr__(self):
+        return (f"DOA({self.channels} microphones, aperture {self.aperture:.4g} m, {len(self.grid)} directions, max_frames={self.max_frames}, "
+                f"oversample={self.oversample}, c={self.c:g})")

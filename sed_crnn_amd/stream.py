@@ -41,6 +41,8 @@ A detector with ``localize=sed.TDOA(...)`` streams when given ``hist
 last ``cap`` samples in a ring on the device (``sed_stream_ring_write``, one launch per round), and a step that emits events
 locates them from the rings in one ``sed_event_tdoa_ring`` call — an event ``[a, b)`` with frames from ``f0`` iff ``b*tf + lat - f0
 <= history_frames`` (``localize.stream_locates``), with the bits of the offline call; ``flush`` / ``reset`` need no ring work either.
+With ``localize=sed.DOA(...)`` that call is ``sed_event_doa_ring`` and the events also carry ``dir`` and ``doa_power``
+(``StreamEvents.doa()``); an event the rule refuses has ``dir = -1``.
 """
 import ctypes as C
 
@@ -49,7 +51,7 @@ import torch
 
 from . import feature
 from ._lib import SedHipError, check, lib, ptr, stream_ptr
-from .detect import _TDOA_KEYS, EventDetector, _event_tensors, _intervals, _timed, _window_jobs, plan_windows
+from .detect import _DOA_KEYS, _TDOA_KEYS, EventDetector, _doa_angles, _event_tensors, _intervals, _timed, _window_jobs, plan_windows
 
 _KEYS = ("stream", "cls", "onset", "offset", "peak", "peak_frame")
 
@@ -153,10 +155,11 @@ class StreamEvents:
     event_offsets[s+1])); ``final_frames`` [S] host list: output frames of each stream that are final after this call; with
     ``keep_probs``, ``probs`` [sum, K] = the newly final track rows, packed by stream, and ``prob_offsets`` [S+1]."""
 
-    def __init__(self, events, event_offsets, final_frames, frame_seconds, probs=None, prob_offsets=None, sr=None):
+    def __init__(self, events, event_offsets, final_frames, frame_seconds, probs=None, prob_offsets=None, sr=None, grid=None):
         self.events, self.event_offsets, self.final_frames = events, list(event_offsets), list(final_frames)
         self.frame_seconds, self.probs, self.prob_offsets = frame_seconds, probs, prob_offsets
         self.sr = sr                            # the detector's rate: set by a localising stream (lags are in samples at that rate)
+        self.grid = grid                        # the DirectionGrid that ``dir`` indexes: set by a stream with DOA settings
 
     def __len__(self):
         return self.event_offsets[-1]
@@ -175,6 +178,16 @@ class StreamEvents:
                              "det.stream(S, history_frames=...)")
         lag = self.events["lag"].cpu().numpy().astype(np.float64) / float(self.sr)
         return lag if stream is None else lag[self.event_offsets[int(stream)]:self.event_offsets[int(stream) + 1]]
+
+    def doa(self, stream=None):
+        """directions of arrival, a host array [E, 3] (the events of one stream; None: all events, in event order): azimuth,
+        elevation (radians) and power, as ``DetectionResult.doa``; NaN where an event was not located.  Only on what a stream
+        with ``localize=sed.DOA(...)`` returns."""
+        if "dir" not in self.events or self.grid is None:
+            raise ValueError("these events hold no directions: make the stream from EventDetector(..., localize=sed.DOA(...)) with "
+                             "det.stream(S, history_frames=...)")
+        out = _doa_angles(self.events, self.grid, None)
+        return out if stream is None else out[self.event_offsets[int(stream)]:self.event_offsets[int(stream) + 1]]
 
 
 class StreamDetector:
@@ -240,7 +253,7 @@ class StreamDetector:
                 raise ValueError(f"history_frames={self.history_frames} is less than the minimum max_frames + lat = "
                                  f"{det.localize_settings.max_frames} + {self.lat} = {least} feature frames (\"min\")")
             self.cap = stream_ring_samples(self.history_frames, self.step_frames, h, feature.NFFT)
-            self._ev_keys = _KEYS + _TDOA_KEYS
+            self._ev_keys = _KEYS + _TDOA_KEYS + (_DOA_KEYS if det.locates_directions else ())
         self._dims = (S, self.K, self.win_out, self.hop_out, det.median_max, self.max_new)
         self._core_bytes = lib().sed_stream_state_bytes(*self._dims)
         if self._core_bytes == 0:
@@ -476,12 +489,16 @@ class StreamDetector:
     def _locate(self, events, end):
         """the step's events on the rings, with the samples received so far (before a feed that ends is reset): one
         ``event_tdoa_ring`` call"""
-        det, t, h = self.det, self.det.localize_settings, self.det.hop_length
+        det, t, h = self.det, self.det.localize_tdoa, self.det.hop_length
         # every frame of an emitted event is final: its samples were received, so nothing is read beyond them — except in a feed
         # that ends, whose count is final and whose last frames are right-padded with zeros as offline
         live = ~end & (self._fdone > 0)
         if (live & ((self._fdone - 1) * h + feature.NFFT // 2 > self._n)).any() or (self.sched.N > self._fdone).any():
             raise SedHipError("a stream holds final feature frames whose samples it has not received")
+        if det.locates_directions:                                          # the same call with the steering launch (DESIGN 5q)
+            return _timed(self.marks, "locate", lambda: feature.event_doa_ring(
+                self._ring, self.cap, self._n, self.C, events, det.model.time_factor, det.localize_settings, sr=det.sr, hop=h,
+                lat_frames=self.lat, history_frames=self.history_frames))
         return _timed(self.marks, "locate", lambda: feature.event_tdoa_ring(
             self._ring, self.cap, self._n, self.C, events, det.model.time_factor, max_lag=t.max_lag, max_frames=t.max_frames, hop=h,
             lat_frames=self.lat, history_frames=self.history_frames))
@@ -528,10 +545,13 @@ class StreamDetector:
             P = self.C * (self.C - 1) // 2
             ev.update(lag=torch.empty(0, P, device=dev), strength=torch.empty(0, P, device=dev),
                       loc_frames=torch.empty(0, dtype=torch.int32, device=dev))
+            if self.det.locates_directions:
+                ev.update(dir=torch.empty(0, dtype=torch.int32, device=dev), doa_power=torch.empty(0, device=dev))
         return ev
 
     def _events(self, ev, offs, final, probs, poffs):
-        return StreamEvents(ev, offs, final, self.frame_seconds, probs, poffs, self.det.sr if self.cap else None)
+        return StreamEvents(ev, offs, final, self.frame_seconds, probs, poffs, self.det.sr if self.cap else None,
+                            self.det.localize_settings.grid if self.cap and self.det.locates_directions else None)
 
     def _pieces(self, xs, what, check_one, axis=0):
         xs = list(xs)
