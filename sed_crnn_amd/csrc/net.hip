@@ -282,6 +282,14 @@ static int forward_impl(const sed_net_cfg* c, const sed_net_params* p, const flo
     // (conv_mode 2: the same plan with the bf16 blocks / projection of build_layout; it has no phases)
     SED_REQUIRE(c->conv_mode != 2 || (pb == 0 && pe == 2 * L.n_conv + 1), "net_forward: the bf16 inference plan (conv_mode 2) runs whole, not in phases");
     const bool eval_plan = !training && (c->conv_mode == 0 || c->conv_mode == 2) && pb == 0 && pe == 2 * L.n_conv + 1;
+    // Only the eval plan runs a block whose conv output is never stored (.ev: pooled in the conv epilogue, .bf: bf16): the
+    // phased path below writes B*T*F*C floats to conv_out, for which such a block's layout holds one 64-float granule.  An
+    // inference layout with such a block therefore runs whole or not at all — refused here, before anything is packed or launched.
+    if (!eval_plan)
+        for (int l = 0; l < L.n_conv; ++l)
+            SED_REQUIRE(!(L.cv[l].ev || L.cv[l].bf),
+                        "net_forward: phases [%d,%d) of an inference layout whose conv block %d keeps no conv output (pooled in the conv epilogue); "
+                        "run inference whole: sed_net_forward, or phases [0,%d)", pb, pe, l, 2 * L.n_conv + 1);
     const ConvL& qtop = L.cv[L.n_conv - 1];
     const bool wih_permuted = eval_plan && (qtop.ev || L.proj_bf) && L.wih_perm != 0;
     if (eval_plan) {

@@ -340,13 +340,15 @@ def _wino_sweep_cases(n=28, seed=20260405):
 
 @pytest.mark.parametrize("B,Fm,T,Cout", _wino_sweep_cases())
 def test_conv3x3_winograd_seeded_shape_sweep(ops, B, Fm, T, Cout):
-    """28 seeded shapes through sed_conv3x3_wino_fwd (every shape the geometry takes must be right; the rest must say so): tile
+    """28 seeded shapes through sed_conv3x3_wino_fwd, all of them shapes the geometry takes (it refuses an even (F, T) whose tile
+    row does not fit a block's patch and cannot be halved, such as (70, 8): test_cpu_wino_geo.py pins which, test_gpu_wino_eval.py
+    what becomes of them): tile
     rows of 1 to 64 tiles, blocks that straddle tile rows at every phase, column groups (mel 128 and 70: 35 tiles in one group),
     a ragged last block, batch sizes on and off the XCD-aware order, 64 / 128 / 192 output channels — against torch in float64
     with the bound of the fixed-shape test (the direct kernel's own error on the same inputs x 4 + an ulp term)."""
     from sed_crnn_amd._lib import lib
     rows = lib().sed_conv3x3_wino_rows(B, 128, Fm, T, Cout)
-    assert rows > 0, "every even (F, T) with 128 input channels and 64-multiples of output channels is taken"
+    assert rows > 0, "the seeded list holds only shapes the Winograd geometry takes (sed_conv3x3_wino_rows > 0)"
     gen = torch.Generator().manual_seed(B * 131 + Fm * 17 + T)
     x = torch.randn(B, T, Fm, 128, generator=gen)
     w = torch.randn(Cout, 128, 3, 3, generator=gen) / 34.0
