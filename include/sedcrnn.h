@@ -573,6 +573,49 @@ int sed_event_doa_ring(const float* ring, long ring_len, long cap, const long* n
                        float* lag_out, float* strength_out, int* frames_out, float* acc_out, const int* steer_lags, int D, int Q,
                        const float* trig, int* dir_out, float* power_out, float* srp_out, void* workspace, size_t workspace_bytes,
                        void* stream);
+/* sed_event_beam_spans / sed_event_beamform: the audio of every located event, with the array pointed at it by a
+ * steered delay-and-sum beam.  The event columns, clips_host, R, channels, time_factor, hop and max_frames are sed_event_doa's;
+ * ev_dir and ev_loc_frames are the dir_out and frames_out it wrote.  An event is extracted iff 0 <= dir < D; its samples are
+ * [s0, s1) = [f0 hop, min((f0 + loc_frames) hop, n)) with f0 the first frame sed_event_tdoa locates it on (loc_frames is read
+ * as at most that range).
+ *   sed_event_beam_spans: len_out int32 [E] = max(0, s1 - s0) (0: not extracted), start_out int64 [E] = the exclusive prefix sum
+ * of len_out in event order, total_out int64 [1] = its sum; one launch, nothing else is read.  max_frames * hop <= 2^31 - 1.
+ *   sed_event_beamform: audio [audio_total] (the caller reads total_out, 8 bytes, to size it), event e at
+ * [audio_start[e], + audio_len[e]).  delays: DEVICE int32 [D][C], M[d][c] = round(Q sr (r_c - rbar) . u_d / c), the delay of
+ * channel c for direction d in 1/Q samples; taps: DEVICE float [Q][2H], row p evaluates a channel at m + p/Q:
+ * x(m + p/Q) = sum_k taps[p][k] x[m + k - H + 1]; Q = oversample in {1, 2, 4, .., 64}, H = half_width in 1..32.  With
+ * q = -M[dir][c], i = floor(q / Q), p = q - Q i, output sample j of the event (n = s0 + j):
+ *   a_c = sum_{k=0}^{2H-1} taps[p][k] x_c[n + i + k - H + 1]   (an fp32 fma chain from 0 in ascending k)
+ *   y   = (((0 + a_0) + a_1) + ... + a_{C-1}) * float32(1 / C)
+ * and samples outside [0, n) of the recording read as 0.  Every value depends on the event's own samples, its frames and these
+ * tables alone.  audio_len / audio_start must be what sed_event_beam_spans wrote for the same events: an event whose entries
+ * disagree with its own span, or leave [0, audio_total), is skipped.  pcm must be 16-byte aligned.  workspace: at least
+ * sed_event_beam_workspace_bytes(R, channels), 16-byte aligned (the recording table; each call uploads its own).  Every argument
+ * is checked before anything is enqueued; E = 0 or audio_total = 0 launches nothing.
+ * The _ring forms read the rings of live feeds as sed_event_tdoa_ring does (ring, ring_len, cap, n_host [R] = samples received):
+ * sample s of feed r, channel c at ring[(r C + c) cap + s % cap]; samples before max(0, n - cap) read as 0 (no event that
+ * sed_event_doa_ring located reaches them).  An extracted event gets, bit for bit, what the linear call gives on the feed's
+ * samples [0, n).  workspace: sed_event_beam_ring_workspace_bytes(R). */
+size_t sed_event_beam_workspace_bytes(int R, int channels);
+size_t sed_event_beam_ring_workspace_bytes(int R);
+int sed_event_beam_spans(long pcm_len, const long* clips_host, int R, int channels, const int* ev_rec, const int* ev_onset,
+                         const int* ev_offset, const int* ev_peak_frame, const int* ev_dir, const int* ev_loc_frames, long E,
+                         int time_factor, int hop, int max_frames, int D, int* len_out, long* start_out, long* total_out,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int sed_event_beam_spans_ring(const long* n_host, int R, int channels, const int* ev_rec, const int* ev_onset, const int* ev_offset,
+                              const int* ev_peak_frame, const int* ev_dir, const int* ev_loc_frames, long E, int time_factor, int hop,
+                              int max_frames, int D, int* len_out, long* start_out, long* total_out, void* workspace,
+                              size_t workspace_bytes, void* stream);
+int sed_event_beamform(const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const int* ev_rec,
+                       const int* ev_onset, const int* ev_offset, const int* ev_peak_frame, const int* ev_dir,
+                       const int* ev_loc_frames, long E, int time_factor, int hop, int max_frames, const int* delays, int D, int Q,
+                       int H, const float* taps, const int* audio_len, const long* audio_start, float* audio, long audio_total,
+                       void* workspace, size_t workspace_bytes, void* stream);
+int sed_event_beamform_ring(const float* ring, long ring_len, long cap, const long* n_host, int R, int channels, const int* ev_rec,
+                            const int* ev_onset, const int* ev_offset, const int* ev_peak_frame, const int* ev_dir,
+                            const int* ev_loc_frames, long E, int time_factor, int hop, int max_frames, const int* delays, int D,
+                            int Q, int H, const float* taps, const int* audio_len, const long* audio_start, float* audio,
+                            long audio_total, void* workspace, size_t workspace_bytes, void* stream);
 
 /* sed_pcen: per-channel energy normalisation, IN PLACE, of the columns [col0, col0 + W) of x [rows][stride], which
  * hold log-mel values (natural log, as sed_logmel* write them without a scaler); the other columns are not touched.  Every column

@@ -28,6 +28,7 @@ from .model import HipCRNN
 _EVENT_KEYS = ("cls", "onset", "offset", "peak", "peak_frame")
 _TDOA_KEYS = ("lag", "strength", "loc_frames")          # added to the events of a localising detector
 _DOA_KEYS = ("dir", "doa_power")                        # ... and, with localize=DOA(...), a direction per event
+_BEAM_KEYS = ("audio_start", "audio_len")               # ... and, with extract=DelaySum(...), its place in result.audio
 
 
 def _doa_angles(events, grid, k):
@@ -233,10 +234,13 @@ class DetectionResult:
     """``probs`` [n_out, K] device track; ``events`` dict of device tensors (``cls``, ``onset``, ``offset``, ``peak_frame``
     int32 output frames, offset exclusive; ``peak`` float32), sorted by (class, onset); ``frame_seconds`` = tf*hop_length/sr."""
 
-    def __init__(self, probs, events, frame_seconds, plan, sr=None, grid=None):
+    def __init__(self, probs, events, frame_seconds, plan, sr=None, grid=None, audio=None):
         self.probs, self.events, self.frame_seconds, self.plan = probs, events, frame_seconds, plan
         self.sr = sr                            # the detector's rate: set on located results (lags are in samples at that rate)
         self.grid = grid                        # the DirectionGrid that ``dir`` indexes: set on results located with DOA settings
+        # the packed beamformed audio that ``audio_start`` / ``audio_len`` index (DESIGN 5r): set by a detector with extract=; a
+        # ``res[i]`` view of a batch shares the batch's buffer
+        self.audio = audio
 
     def __len__(self):
         return int(self.events["cls"].numel())
@@ -265,6 +269,23 @@ class DetectionResult:
                              "through det.localize(result, waveform, ...)")
         return _doa_angles(self.events, self.grid, k)
 
+    def event_audio(self, e):
+        """the beamformed audio of event ``e``: a float32 device slice of ``audio`` at the detector's rate, empty
+        where the event was not located.  Only on the result of a detector with ``extract=sed.DelaySum(...)``; the host reads
+        the event's two integers."""
+        return _event_audio(self, e)
+
+
+def _event_audio(result, e):
+    if result.audio is None or "audio_start" not in result.events:
+        raise ValueError("this result holds no audio: detect with EventDetector(..., localize=sed.DOA(...), extract=sed.DelaySum(...)) "
+                         "or pass it through det.localize(result, waveform, ...)")
+    E = int(result.events["audio_start"].numel())
+    if not -E <= int(e) < E:
+        raise IndexError(f"event {e} of {E}")
+    start, n = int(result.events["audio_start"][int(e)]), int(result.events["audio_len"][int(e)])
+    return result.audio[start:start + n]
+
 
 class BatchDetectionResult:
     """R recordings detected together.  ``len()`` = R; ``res[i]`` = a DetectionResult view of recording i (its slice of the
@@ -272,10 +293,10 @@ class BatchDetectionResult:
     ``events`` dict of device tensors with ``rec`` (sorted by recording, class, onset), and the host lists ``out_offsets``
     [R+1] (recording i = rows [out_offsets[i], out_offsets[i+1])) and ``event_offsets`` [R+1]."""
 
-    def __init__(self, probs, events, frame_seconds, plans, out_offsets, event_offsets, sr=None, grid=None):
+    def __init__(self, probs, events, frame_seconds, plans, out_offsets, event_offsets, sr=None, grid=None, audio=None):
         self.probs, self.events, self.frame_seconds, self.plans = probs, events, frame_seconds, tuple(plans)
         self.out_offsets, self.event_offsets = list(out_offsets), list(event_offsets)
-        self.sr, self.grid = sr, grid           # as in DetectionResult
+        self.sr, self.grid, self.audio = sr, grid, audio         # as in DetectionResult
 
     def __len__(self):
         return len(self.plans)
@@ -287,9 +308,13 @@ class BatchDetectionResult:
         i = int(i) % R
         o0, o1 = self.out_offsets[i], self.out_offsets[i + 1]
         e0, e1 = self.event_offsets[i], self.event_offsets[i + 1]
-        keys = _EVENT_KEYS + tuple(k for k in _TDOA_KEYS + _DOA_KEYS if k in self.events)
+        keys = _EVENT_KEYS + tuple(k for k in _TDOA_KEYS + _DOA_KEYS + _BEAM_KEYS if k in self.events)
         return DetectionResult(self.probs[o0:o1], {k: self.events[k][e0:e1] for k in keys}, self.frame_seconds, self.plans[i], self.sr,
-                               self.grid)
+                               self.grid, self.audio)
+
+    def event_audio(self, e):
+        """the beamformed audio of event ``e`` of the packed table (``DetectionResult.event_audio``)"""
+        return _event_audio(self, e)
 
     def __iter__(self):
         return (self[i] for i in range(len(self)))
@@ -322,11 +347,15 @@ class EventDetector:
     ``from_features*`` has no audio and returns un-located events, which ``det.localize(result, waveform, ...)`` locates.
     ``localize=sed.DOA(positions, grid, ...)`` for a known array: the same three keys, with ``max_lag`` taken from the
     array's aperture, and ``dir`` [E] (a row of ``grid``, -1: not located) and ``doa_power`` [E] (``feature.event_doa``;
-    ``result.doa()`` in radians)."""
+    ``result.doa()`` in radians).  ``extract=sed.DelaySum(...)`` (needs ``localize=sed.DOA(...)``): every located event
+    also comes with its audio, the array pointed at ``dir`` by a delay-and-sum beam (``feature.event_beamform`` on the PCM that
+    is kept anyway): ``audio_start`` / ``audio_len`` [E] in the events, the packed float32 buffer ``result.audio`` and
+    ``result.event_audio(e)``; ``from_features*`` returns events without audio, ``det.localize`` adds it, ``det.stream`` of such a
+    detector is not implemented."""
 
     def __init__(self, model, seq_len=SEQ_LEN_IN, hop=None, combine="mean", trim=0, threshold=0.5, low=None, median=1,
                  min_gap=0, min_len=1, mean=None, std=None, sr=feature.SR, hop_length=feature.HOP, max_batch=1024, spatial=None,
-                 compress=None, localize=None):
+                 compress=None, localize=None, extract=None):
         if not isinstance(model, HipCRNN):
             raise TypeError(f"EventDetector needs a sed_crnn_amd net, got {type(model).__name__}")
         feature._check_compress(compress)
@@ -343,7 +372,13 @@ class EventDetector:
                                  f"the net has in_channels={model.in_channels}")
             if model.n_mels % 2:
                 raise ValueError(f"spatial={spatial!r} writes n_mels lags per pair and needs an even count, the net has n_mels={model.n_mels}")
-        from .localize import DOA, TDOA
+        from .localize import DOA, TDOA, DelaySum
+        if extract is not None and not isinstance(extract, DelaySum):
+            raise TypeError(f"extract must be None or a DelaySum(...) settings object, got {type(extract).__name__}")
+        if extract is not None and not isinstance(localize, DOA):
+            raise ValueError("extract=DelaySum(...) points the array at every event's direction and needs localize=sed.DOA(positions, grid), "
+                             f"got localize={localize!r}")
+        self.extract_settings = extract         # per-event delay-and-sum audio, or None
         if localize is not None and not isinstance(localize, (TDOA, DOA)):
             raise TypeError(f"localize must be None, a TDOA(...) or a DOA(...) settings object, got {type(localize).__name__}")
         if localize is not None and not 2 <= self.audio_channels <= feature.GCC_MAX_CHANNELS:
@@ -413,7 +448,8 @@ class EventDetector:
     def stream(self, n_streams, keep_probs=False, **kw):
         """a ``stream.StreamDetector`` for ``n_streams`` live feeds with this detector's settings; ``input_sr`` /
         ``input_channels``: what ``push`` receives.  A localising detector streams with ``history_frames="min"`` or a
-        number of feature frames: the audio every feed keeps for its emitted events; without it, NotImplementedError."""
+        number of feature frames: the audio every feed keeps for its emitted events; without it, NotImplementedError.  A detector with
+        ``extract=`` does not stream yet: NotImplementedError."""
         from .stream import StreamDetector
         return StreamDetector(self.model, n_streams, keep_probs=keep_probs, _det=self, **kw)
 
@@ -451,7 +487,7 @@ class EventDetector:
         kw.update(settings)
         return EventDetector(self.model, seq_len=self.seq_len, hop=self.hop, combine=self.combine, trim=self.trim, mean=self.mean,
                              std=self.std, sr=self.sr, hop_length=self.hop_length, max_batch=self.max_batch, spatial=self.spatial,
-                             compress=self.compress, localize=self.localize_settings, **kw)
+                             compress=self.compress, localize=self.localize_settings, extract=self.extract_settings, **kw)
 
     def sweep(self, track, ref, grid, collar=1, offset_collar=None, offset_percent=None, block=None, max_workspace_bytes=1 << 30):
         """Score every decoder setting of ``grid`` (a ``DecoderGrid``) on a track against ``ref`` (a ``ReferenceEvents``) on
@@ -540,7 +576,12 @@ class EventDetector:
             else:
                 loc = feature.event_tdoa(pcm, clips, self.audio_channels, result.events, self.model.time_factor, max_lag=t.max_lag,
                                          max_frames=t.max_frames, hop=self.hop_length)
-        result.events = {**{k: v for k, v in result.events.items() if k not in _TDOA_KEYS + _DOA_KEYS}, **loc}
+            if self.extract_settings is not None:            # the audio of the located events, from the same PCM
+                beam = feature.event_beamform(pcm, clips, self.audio_channels, {**result.events, **loc}, self.model.time_factor, t,
+                                              self.extract_settings, sr=self.sr, hop=self.hop_length)
+                result.audio = beam.pop("audio")
+                loc.update(beam)
+        result.events = {**{k: v for k, v in result.events.items() if k not in _TDOA_KEYS + _DOA_KEYS + _BEAM_KEYS}, **loc}
         result.sr = self.sr
         return result
 
@@ -571,6 +612,8 @@ class EventDetector:
         if not waves:
             result.events = {**result.events, **self._no_lags()}
             result.sr = self.sr
+            if self.extract_settings is not None:
+                result.audio = torch.empty(0, device=self.model.flat_parameters().device)
             result.grid = self.localize_settings.grid if self.locates_directions else None
             return result
         from .resample import resample_many
@@ -767,7 +810,8 @@ class EventDetector:
             ev.update(self._no_lags())
         return BatchDetectionResult(torch.empty(0, m.dense[-1], device=dev), ev, self.frame_seconds, (), [0], [0],
                                     self.sr if self.localize_settings is not None else None,
-                                    self.localize_settings.grid if self.locates_directions else None)
+                                    self.localize_settings.grid if self.locates_directions else None,
+                                    torch.empty(0, device=dev) if self.extract_settings is not None else None)
 
     def _no_lags(self):
         """the localisation columns of an empty event table"""
@@ -776,6 +820,8 @@ class EventDetector:
                "loc_frames": torch.empty(0, dtype=torch.int32, device=dev)}
         if self.locates_directions:
             out.update(dir=torch.empty(0, dtype=torch.int32, device=dev), doa_power=torch.empty(0, device=dev))
+        if self.extract_settings is not None:
+            out.update(audio_start=torch.empty(0, dtype=torch.int64, device=dev), audio_len=torch.empty(0, dtype=torch.int32, device=dev))
         return out
 
     def _detect_packed(self, mel, bp):

@@ -640,6 +640,129 @@ def event_tdoa_ring(ring, cap, n, channels, events, time_factor, max_lag=24, max
     return out
 
 
+def _beam_io(who, events, R, rec_key, nc, doa, beam, sr, dev):
+    """checks the settings of a beam call and gathers what both entries pass on -> (event columns as the C entries take them, E,
+    [max_frames, M, D, Q, H, taps] with M and the taps on ``dev``: uploaded once per device, rate and filter)"""
+    from .localize import DelaySum
+    _doa_plan(doa, nc, sr)
+    if not isinstance(beam, DelaySum):
+        raise TypeError(f"{who} takes the beam settings as a sed.DelaySum(...) object, got {type(beam).__name__}")
+    col = {}
+    for k in ("onset", "offset", "peak_frame", "dir", "loc_frames") + ((rec_key,) if R > 1 else ()):
+        if k not in events:
+            raise ValueError(f"events has no {k!r}" + (f" ({R} recordings need one)" if k == rec_key else
+                                                       " (the events must be located: feature.event_doa)" if k in ("dir", "loc_frames") else ""))
+        col["rec" if k == rec_key else k] = events[k].to(dev, torch.int32).contiguous()
+    E = col["onset"].numel()
+    if any(v.dim() != 1 or v.numel() != E for v in col.values()):
+        raise ValueError("the event columns must be 1-D and equally long")
+    key = (dev.index or 0, float(sr), beam.oversample)
+    if key not in doa._beam_device:
+        doa._beam_device[key] = torch.from_numpy(doa.delays(sr, beam.oversample)).to(dev)
+    tkey = (dev.index or 0, beam)
+    if tkey not in _BEAM_TAPS:
+        _BEAM_TAPS[tkey] = torch.from_numpy(beam.taps.copy()).to(dev)                # (the cached table is read-only)
+    M = doa._beam_device[key]
+    cols = [ptr(col.get("rec")), ptr(col["onset"]), ptr(col["offset"]), ptr(col["peak_frame"]), ptr(col["dir"]), ptr(col["loc_frames"])]
+    return cols, E, [doa.max_frames, ptr(M), M.shape[0], beam.oversample, beam.half_width, ptr(_BEAM_TAPS[tkey])]
+
+
+_BEAM_TAPS = {}              # (device, DelaySum) -> the filter on the device
+
+
+def _beam_empty(dev):
+    return {"audio": torch.empty(0, device=dev), "audio_start": torch.empty(0, dtype=torch.int64, device=dev),
+            "audio_len": torch.empty(0, dtype=torch.int32, device=dev)}
+
+
+def _beam_run(names, head, cols, E, tf, hop, plan, need, dev):
+    """the two calls of a beam entry: the spans, ONE blocking read of the total (8 bytes) to size ``audio``, the beam"""
+    max_frames, M, D, Q, H, taps = plan
+    out = {"audio_start": torch.empty(E, dtype=torch.int64, device=dev), "audio_len": torch.empty(E, dtype=torch.int32, device=dev)}
+    total = torch.empty(1, dtype=torch.int64, device=dev)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    check(getattr(lib(), names[0])(*head[1], *cols, E, tf, hop, max_frames, D, ptr(out["audio_len"]), ptr(out["audio_start"]), ptr(total),
+                                   ptr(ws), ws.numel(), stream_ptr()), names[0])
+    n_total = int(total.item())
+    out["audio"] = torch.empty(n_total, device=dev)
+    check(getattr(lib(), names[1])(*head[0], *head[1], *cols, E, tf, hop, max_frames, M, D, Q, H, taps, ptr(out["audio_len"]),
+                                   ptr(out["audio_start"]), ptr(out["audio"]), n_total, ptr(ws), ws.numel(), stream_ptr()), names[1])
+    return out
+
+
+def event_beamform(pcm, clips, channels, events, time_factor, doa, beam, sr=SR, hop=HOP):
+    """The audio of every located event with the array pointed at it (``sed_event_beam_spans`` + ``sed_event_beamform``, DESIGN
+    5r): a steered delay-and-sum beam.  ``pcm`` / ``clips`` / ``channels`` / ``events`` / ``time_factor`` as ``event_doa`` takes
+    them; the events must also hold ``dir`` and ``loc_frames`` as ``event_doa`` (with the same ``doa``, a ``sed.DOA``) returns
+    them; ``beam``: a ``sed.DelaySum(oversample, half_width, beta)``; ``sr``: the rate of the PCM.  An event with ``dir >= 0``
+    is extracted: its samples are ``localize.event_samples`` — the frames it was located on — and every output sample is the
+    mean over the channels of the channel evaluated ``doa.delays(sr, Q)[dir][c] / Q`` samples earlier, through the 2H-tap filter
+    ``beam.taps`` (samples outside the recording read as 0).  Returns device tensors ``{"audio": float32 [total], "audio_start":
+    int64 [E], "audio_len": int32 [E]}``: event e is ``audio[audio_start[e] : audio_start[e] + audio_len[e]]``, the events packed
+    in event order; events that are not extracted have length 0.  The host does ONE blocking read, the 8 bytes of the total,
+    to size ``audio``; nothing else is read back.  ``E == 0`` returns empty tensors without a launch.  Every sample depends on
+    its event's own samples alone: the batch, the order of the table, the other events and the clip's place in the buffer
+    change no bit."""
+    import ctypes as C
+    if not (isinstance(pcm, torch.Tensor) and pcm.is_cuda and pcm.dim() == 1):
+        raise RuntimeError("sed_crnn_amd.feature.event_beamform needs a 1-D CUDA(HIP) PCM buffer; there is no CPU fallback")
+    nc, tf, hop = int(channels), int(time_factor), int(hop)
+    if not 2 <= nc <= GCC_MAX_CHANNELS or tf < 1 or hop < 1:
+        raise ValueError(f"event_beamform needs 2 to {GCC_MAX_CHANNELS} audio channels, time_factor >= 1 and hop >= 1, got channels={nc}, "
+                         f"time_factor={tf}, hop={hop}")
+    table = np.ascontiguousarray(np.asarray(clips, dtype=np.int64).reshape(-1, 2))
+    if table.shape[0] == 0 or table.shape[0] % nc:
+        raise ValueError(f"{table.shape[0]} clips are not a whole number (>= 1) of recordings of {nc} channels")
+    R = table.shape[0] // nc
+    for i, (o, n) in enumerate(table.tolist()):
+        if n < 1 or o < 0 or o + n > pcm.numel():
+            raise ValueError(f"recording {i // nc}, channel {i % nc} (first sample {o}, {n} samples) is empty or not inside the "
+                             f"buffer of {pcm.numel()} samples")
+        if n != table[i - i % nc, 1]:
+            raise ValueError(f"recording {i // nc}: channel {i % nc} has {n} samples, channel 0 has {int(table[i - i % nc, 1])}")
+    dev = pcm.device
+    cols, E, plan = _beam_io("event_beamform", events, R, "rec", nc, doa, beam, sr, dev)
+    if E == 0:
+        return _beam_empty(dev)
+    pcm = pcm.contiguous().float()
+    if pcm.data_ptr() % 16:                                           # (a view into a larger buffer: the kernel loads 16 bytes at a time)
+        pcm = pcm.clone()
+    head = ([ptr(pcm)], [pcm.numel(), C.c_void_p(table.ctypes.data), R, nc])
+    return _beam_run(("sed_event_beam_spans", "sed_event_beamform"), head, cols, E, tf, hop, plan,
+                     lib().sed_event_beam_workspace_bytes(R, nc), dev)
+
+
+def event_beamform_ring(ring, cap, n, channels, events, time_factor, doa, beam, sr=SR, hop=HOP):
+    """``event_beamform`` on the PCM rings of live feeds (``sed_event_beam_spans_ring`` + ``sed_event_beamform_ring``):
+    ``ring`` / ``cap`` / ``n`` as ``event_doa_ring`` takes them, the events with the ``dir`` and ``loc_frames`` it returned (an
+    event the stream's rule or the ring's depth refused has ``dir = -1`` and length 0 here); the feed of an event is its
+    ``rec`` — or ``stream`` — column.  An extracted event gets, bit for bit, what ``event_beamform`` gives on the feed's samples
+    ``[0, n)`` laid out linearly, wherever the ring wraps.  Returns what ``event_beamform`` returns, with the same single
+    8-byte read."""
+    import ctypes as C
+    if not (isinstance(ring, torch.Tensor) and ring.is_cuda and ring.dim() == 1 and ring.dtype == torch.float32 and ring.is_contiguous()):
+        raise RuntimeError("sed_crnn_amd.feature.event_beamform_ring needs a contiguous 1-D float32 CUDA(HIP) ring buffer; there is no CPU fallback")
+    nc, tf, hop, cap = int(channels), int(time_factor), int(hop), int(cap)
+    if not 2 <= nc <= GCC_MAX_CHANNELS or tf < 1 or hop < 1:
+        raise ValueError(f"event_beamform_ring needs 2 to {GCC_MAX_CHANNELS} audio channels, time_factor >= 1 and hop >= 1, got "
+                         f"channels={nc}, time_factor={tf}, hop={hop}")
+    n = np.ascontiguousarray(np.asarray(n, dtype=np.int64).reshape(-1))
+    R = n.shape[0]
+    if R < 1 or (n < 0).any():
+        raise ValueError(f"n must hold one sample count >= 0 per feed, got {n.tolist()[:8]}")
+    if cap < NFFT or cap % 4 or R * nc * cap > ring.numel() or ring.data_ptr() % 16:
+        raise ValueError(f"{R} feeds of {nc} rings of cap={cap} samples (a multiple of 4, at least {NFFT}, 16-byte aligned) do not fit the "
+                         f"ring buffer of {ring.numel()} samples")
+    dev = ring.device
+    rec_key = "stream" if "stream" in events and "rec" not in events else "rec"
+    cols, E, plan = _beam_io("event_beamform_ring", events, R, rec_key, nc, doa, beam, sr, dev)
+    if E == 0:
+        return _beam_empty(dev)
+    head = ([ptr(ring), ring.numel(), cap], [C.c_void_p(n.ctypes.data), R, nc])
+    return _beam_run(("sed_event_beam_spans_ring", "sed_event_beamform_ring"), head, cols, E, tf, hop, plan,
+                     lib().sed_event_beam_ring_workspace_bytes(R), dev)
+
+
 def pack_clips(waves, device):
     """a list of 1-D clips (host arrays or tensors, any device) -> (one float32 buffer on ``device``, [(first sample, n), ...]);
     every clip starts on a 16-byte boundary.  Host clips travel in one copy, device clips are joined by one torch.cat."""

@@ -8,9 +8,13 @@ the two settings of ``EventDetector(..., localize=TDOA(...))``.  ``max_lag_for``
 geometry of ONE microphone pair.  ``DirectionGrid``, ``steering_lags`` and ``DOA`` are the host side of per-event direction of
 arrival for a known array (the kernel is csrc/doa.hip, the device entry ``feature.event_doa``): the directions that
 are searched, the time difference every direction means for every microphone pair, and the settings of
-``EventDetector(..., localize=DOA(positions, grid))``.
+``EventDetector(..., localize=DOA(positions, grid))``.  ``DelaySum``, ``beam_taps``, ``steering_delays`` and ``event_samples`` are
+the host side of per-event audio extraction by a steered delay-and-sum beam (the kernels are csrc/beam.hip, the device
+entry ``feature.event_beamform``): the settings of ``EventDetector(..., localize=DOA(...), extract=DelaySum())``, the
+fractional-delay filter, the delay every direction means for every microphone, and the samples an event's audio consists of.
 """
 import dataclasses
+import functools
 import math
 
 import numpy as np
@@ -222,6 +226,7 @@ class DOA:
         self.max_frames, self.oversample, self.c = int(max_frames), int(oversample), float(c)
         self.aperture = float(dist.max())
         self._plans, self._device = {}, {}                   # per rate: (max_lag, J, table); per (device, rate): their device copies
+        self._delays, self._beam_device = {}, {}             # per (rate, Q): M of steering_delays; per (device, rate, Q): its device copy
 
     @property
     def channels(self):
@@ -246,6 +251,17 @@ class DOA:
             self._plans[key] = (ml, np.ascontiguousarray(J), trig_table(self.oversample))
         return self._plans[key]
 
+    def delays(self, sr, oversample):
+        """``M`` int32 [D, C] at rate ``sr``: ``round_half_even(steering_delays * oversample)``, the delay of every microphone
+        for every direction in 1/oversample samples; every ``|M| <= max_lag * oversample`` by construction"""
+        key = (float(sr), int(oversample))
+        if key not in self._delays:
+            ml = self.max_lag(sr)
+            M = np.rint(steering_delays(self.positions, self.grid, sr, self.c) * int(oversample)).astype(np.int32)
+            assert np.abs(M).max() <= ml * int(oversample)
+            self._delays[key] = np.ascontiguousarray(M)
+        return self._delays[key]
+
     def tdoa(self, sr):
         """the ``TDOA`` settings whose outputs a detector with these settings also returns"""
         return TDOA(self.max_lag(sr), self.max_frames)
@@ -253,3 +269,85 @@ class DOA:
     def __repr__(self):
         return (f"DOA({self.channels} microphones, aperture {self.aperture:.4g} m, {len(self.grid)} directions, max_frames={self.max_frames}, "
                 f"oversample={self.oversample}, c={self.c:g})")
+
+
+# ── the audio of a located event: a steered delay-and-sum beam ──
+BEAM_OVERSAMPLE_CHOICES = (1, 2, 4, 8, 16, 32, 64)
+BEAM_MAX_HALF_WIDTH = 32   # beam.hip: BM_MAX_H
+
+
+@dataclasses.dataclass(frozen=True)
+class DelaySum:
+    """Settings of per-event audio extraction (``EventDetector(model, ..., localize=DOA(...), extract=DelaySum(...))``):
+    every located event's samples with the array pointed at the event's direction, each channel shifted by its delay and the
+    channels averaged.  ``oversample`` Q in {1, 2, 4, 8, 16, 32, 64}: delays are applied in steps of 1/Q sample.
+    ``half_width`` H in 1..32: the fractional-delay filter has 2H taps.  ``beta >= 0``: its Kaiser window."""
+    oversample: int = 16
+    half_width: int = 16
+    beta: float = 10.0
+
+    def __post_init__(self):
+        for name in ("oversample", "half_width"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"DelaySum: {name} must be an integer, got {v!r}")
+            object.__setattr__(self, name, int(v))
+        if self.oversample not in BEAM_OVERSAMPLE_CHOICES:
+            raise ValueError(f"DelaySum: oversample must be one of {BEAM_OVERSAMPLE_CHOICES}, got {self.oversample}")
+        if not 1 <= self.half_width <= BEAM_MAX_HALF_WIDTH:
+            raise ValueError(f"DelaySum: half_width must be in 1..{BEAM_MAX_HALF_WIDTH}, got {self.half_width}")
+        b = self.beta
+        if isinstance(b, bool) or not isinstance(b, (int, float, np.floating, np.integer)) or not math.isfinite(float(b)) or float(b) < 0:
+            raise ValueError(f"DelaySum: beta must be a finite number >= 0, got {b!r}")
+        object.__setattr__(self, "beta", float(b))
+
+    @property
+    def taps(self):
+        """``beam_taps`` of these settings: float32 [Q, 2H], read-only"""
+        return beam_taps(self.oversample, self.half_width, self.beta)
+
+
+@functools.lru_cache(maxsize=32)
+def beam_taps(oversample, half_width, beta):
+    """float32 [Q, 2H]: row p evaluates a channel at ``m + p/Q``, ``x(m + p/Q) = sum_k taps[p][k] x[m + k - H + 1]``.
+    ``resample.design_taps(Q, H, 1.0, beta)`` in float64 (a Kaiser-windowed sinc); row 0 is replaced by the exact unit impulse
+    (1 at column H - 1), every other row is divided by its float64 sum (unit gain at DC), and the table is rounded once."""
+    from .resample import design_taps
+    Q, H = int(oversample), int(half_width)
+    t = design_taps(Q, H, 1.0, float(beta))
+    t[0] = 0.0
+    t[0, H - 1] = 1.0
+    t[1:] /= t[1:].sum(1, keepdims=True)
+    t = np.ascontiguousarray(t.astype(np.float32))
+    t.setflags(write=False)
+    return t
+
+
+def steering_delays(positions, grid, sr, c=SPEED_OF_SOUND):
+    """``tau`` float64 [D, C]: channel c hears a far-field source in direction ``grid.unit_vectors[d]`` as ``s[n + tau[d][c]]``,
+    ``tau = sr (r_c - rbar) . u_d / c`` in samples at rate ``sr``, ``rbar`` the centroid of the microphones (the delays of a
+    direction sum to 0); ``tau[d][j] - tau[d][i]`` is ``steering_lags`` of the pair (i, j)"""
+    r = _positions(positions, "steering_delays")
+    if not isinstance(grid, DirectionGrid):
+        raise TypeError(f"steering_delays: grid must be a DirectionGrid, got {type(grid).__name__}")
+    if not float(sr) > 0 or not float(c) > 0 or not math.isfinite(float(sr)) or not math.isfinite(float(c)):
+        raise ValueError(f"steering_delays needs sr > 0 and c > 0, got {sr}, {c}")
+    return float(sr) * (grid.unit_vectors @ (r - r.mean(0)).T) / float(c)
+
+
+def event_samples(onset, offset, peak_frame, time_factor, n, hop, max_frames, direction, loc_frames):
+    """The samples ``[s0, s1)`` of a recording of ``n`` samples that the audio of an event consists of (the kernels of
+    beam.hip apply the same rule).  An event is extracted iff ``direction >= 0`` (``dir`` of ``feature.event_doa``); it was then
+    located on the frames ``[f0, f0 + loc_frames)`` with ``f0`` from ``event_frames`` (``n_feat = 1 + n // hop``;
+    ``loc_frames`` is read as at most that range), and ``[s0, s1) = [f0 * hop, min((f0 + loc_frames) * hop, n))``.  An event
+    that is not extracted — unlocated, beyond its recording, digital silence, refused by a stream's ring rule — and one whose
+    frames start at or beyond sample ``n`` have no samples: ``(0, 0)``."""
+    n, hop = int(n), int(hop)
+    if n < 0 or hop < 1:
+        raise ValueError(f"event_samples needs n >= 0 and hop >= 1, got {n}, {hop}")
+    if int(direction) < 0:
+        return 0, 0
+    f0, f1 = event_frames(onset, offset, peak_frame, time_factor, 1 + n // hop, max_frames)
+    nf = min(max(int(loc_frames), 0), f1 - f0)
+    s0, s1 = f0 * hop, min((f0 + nf) * hop, n)
+    return (s0, s1) if s1 > s0 else (0, 0)
