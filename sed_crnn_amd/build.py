@@ -24,7 +24,8 @@ EXTRA_FLAGS = {"logmel.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-reso
                "pcen.hip": ["-Rpass-analysis=kernel-resource-usage"],
                "conv.hip": ["-Rpass-analysis=kernel-resource-usage"],
                "wino.hip": ["-Rpass-analysis=kernel-resource-usage"],
-               "conv_bf16.hip": ["-Rpass-analysis=kernel-resource-usage"]}
+               "conv_bf16.hip": ["-Rpass-analysis=kernel-resource-usage"],
+               "gemm.hip": ["-Rpass-analysis=kernel-resource-usage"]}
 # Kernels whose inline-asm loads are consumed after HAND-COUNTED s_waitcnt vmcnt(N) immediates (conv.hip: the fp32 and the
 # bf16x3 conv forward).  The counts are only right while hipcc keeps the load destinations in registers between the asm load
 # and its use: a spill (scratch store/reload) would insert memory operations the counts do not know about and the MFMAs
@@ -54,7 +55,11 @@ NO_SCRATCH_KERNELS = {"wino.hip": ("conv3x3_wino_k",),
                       "beam.hip": ("beam_sum_k", "beam_spans_k"),
                       # PCEN: the powers of (1-b) travel by value and are indexed in a loop; a copy of them in scratch, or a spilled
                       # powf, would turn a bandwidth-bound pass into a latency-bound one without failing any test
-                      "pcen.hip": ("pcen_pass_k", "pcen_carry_k")}
+                      "pcen.hip": ("pcen_pass_k", "pcen_carry_k"),
+                      # fp32 GEMM: a staged K-step lives in registers for a whole MFMA block beside 64 accumulators (128 x 128 tile,
+                      # two workgroups per CU); the 4 x 4 block staging regroups 16 of them per operand.  A spill would put a
+                      # scratch round trip in front of every LDS store of the K loop and fail no test
+                      "gemm.hip": ("gemm_f32_k",)}
 
 
 def _hipcc():

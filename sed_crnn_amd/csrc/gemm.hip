@@ -11,24 +11,68 @@
 #include "common.h"
 
 #define GM_BK 32
-#define GM_LDK 36   // k-contiguous LDS row: 32 + 4 pad floats (16-B slot stride 9) -> conflict-free ds_read_b128
+#define GM_LDK 36   // LDS row of one m (or n): 32 k + 4 pad floats (16-B slot stride 9) -> conflict-free ds_read_b128
 
-// A_KC / B_KC: operand is contiguous along k (true) or along m/n (false).
+// A_KC / B_KC: operand is contiguous along k (true) or along m/n (false).  The flag decides how a K-step is STAGED, nothing else:
+// either kind ends up in the same LDS image [row m or n][GM_LDK], k-contiguous, and every fragment is one ds_read_b128.
 // Block tile (32*WM*WVM) x (32*WN*WVN), 4 waves as WVM x WVN, each wave WM x WN tiles of 32x32 (v_mfma_f32_32x32x2_f32).
 // Three-stage pipeline per K-step of 32: registers hold step k+1 (global loads issued a whole step earlier), LDS buffer
-// `cur` holds step k.  Each iteration first writes the registers to the other LDS buffer and issues the loads of step
-// k+2, then runs the MFMA block of step k, so the LDS writes and the global latency are covered by MFMA work and the one
-// barrier per step has nothing outstanding.  Inside a step the fragments of k-group g+1 are read while the MFMAs of
-// group g issue.  FULL = interior tile with aligned operands and K a multiple of 32: loads without range tests (the
-// guarded variant costs ~1000 scalar/branch instructions per step, which a lone wave per SIMD cannot hide).
+// `cur` holds step k, and one barrier per step has nothing outstanding.  FULL = interior tile with aligned operands and K a
+// multiple of 32: loads without range tests (the guarded variant costs ~1000 scalar/branch instructions per step, which a lone
+// wave per SIMD cannot hide).  The FULL steady state is issued in ONE pinned order (sched_group_barrier in `compute`): the
+// fragment reads of k-groups 0 and 1, group 0's MFMAs, the reads of group g + 2 one per MFMA behind the last MFMA of group g,
+// and behind the last read the LDS stores of step k+1 and the global loads of step k+2, one of each per MFMA.  A wave thus
+// issues everything that is not an MFMA under its own MFMAs; only the reads of groups 0 and 1 behind the barrier stand bare.
+// (Before, stores and loads stood in a block in front of the MFMAs that only the CU's other workgroup could cover, and how
+// well it did depended on details as small as the addressing form of one operand: 0.268 against 0.303 ms for the same loop.)
+// The guarded path and tiles too small for the interleave keep stores and loads in front of the MFMA block.
+//
+// Staging a k-contiguous operand: float4 i = tid + 256 u of the tile is (row i / 8, k-quad i % 8), TILE / 32 per thread, written
+// to the image as it was loaded.
+// Staging an m/n-contiguous operand (source [k][m]): the 32 x TILE step is cut into 4 x 4 blocks, block (bq, bk) = k rows
+// 4 bk .. 4 bk + 3 of m columns 4 bq .. 4 bq + 3, 8 x TILE / 4 of them.  A thread owns ONE block: four 16-byte loads, one per k
+// row, whose 16 registers regrouped by column are the four 16-byte image rows (m = 4 bq + c, k = 4 bk .. 4 bk + 3).  The regrouping
+// is NOT free: a load fills four consecutive registers and a ds_write_b128 takes four consecutive ones, so it costs up to 16
+// v_mov per operand and step (15 after coalescing) — but no LDS traffic, where the [k][m] image cost four 4-byte reads per fragment
+// (hipcc paired them: 2 ds_read2_b32).
+// A 128-wide tile has exactly 256 blocks; a 96-wide one has 192 and its last wave stages nothing.  A 64-wide tile would leave two
+// waves idle with the other two staging twice as much in front of 16 MFMAs (measured: the 64 x 64 weight gradients of the upper
+// GRU layers 19.1 -> 25.3 us), so there a thread owns HALF a block, 2 k rows x 4 columns: two loads, four ds_write_b64.
+// Lane -> block, wave w, lane l (96 and 128 wide):   bq = 8 w + (l & 3) + 4 ((l >> 3) & 1),   bk = ((l >> 2) & 1) + 2 (l >> 4).
+//  * global side: a wave covers m quads 8 w .. 8 w + 7 (128 bytes) of k blocks 0 .. 7, so each of its four loads (k row 4 bk + e) is
+//    eight whole 128-byte row segments, and the four lanes of a quad read 64 consecutive bytes;
+//  * LDS side: ds_write_b128 is served in 8 groups of 8 consecutive lanes on 32 banks, i.e. 8 slots of 16 B.  The slot of the
+//    store of column c is (4 bq + c) * 9 + bk, mod 8 = (4 (bq & 1) + bk + c) mod 8.  Inside a group bit 0 of bq and bit 0 of bk
+//    vary (4 slots) and so does bit 1 of bq, which the slot does not see: two-way, 16 LDS-array cycles against the 13 the
+//    instruction needs to hand over its data anyway.  (Conflict-free needs all four bk & 3 inside a group, i.e. pairs of
+//    lanes on 32-byte pieces of four different rows; measured equal: dX 0.303 / 0.302 ms, two-slice dW 0.272 / 0.270.)
+// 64 wide:   bq = 8 (w & 1) + (l & 3) + 4 ((l >> 4) & 1),   bk = (l >> 2 & 3) + 4 (l >> 5) + 8 (w >> 1)   (bk counts pairs of rows).
+//  * a wave covers 8 m quads (128 bytes) of 8 row pairs; ds_write_b64 is served in 4 groups of 16 consecutive lanes on 32
+//    banks: dword (4 bq + c) * 36 + 2 bk, mod 32 = 16 (bq & 1) + 2 bk + 4 c.  Inside a group bits 0, 1 of bk and bit 0 of bq vary
+//    (8 bank pairs) and bit 1 of bq, unseen: two-way, 8 LDS-array cycles against 6 for the data.
+#define gm_global __attribute__((address_space(1)))
+
+template <int TILE> constexpr int gm_rows() { return TILE >= 96 ? 4 : 2; }     // k rows of a thread's block
+template <int TILE>
+__device__ __forceinline__ bool gm_block(int wave, int lane, int& bq, int& bk) {
+    static_assert(TILE == 128 || TILE == 96 || TILE == 64, "tile widths of kCands");
+    if (TILE >= 96) {
+        bq = 8 * wave + (lane & 3) + 4 * ((lane >> 3) & 1);
+        bk = ((lane >> 2) & 1) + 2 * (lane >> 4);
+        return TILE >= 128 || wave < TILE / 32;        // wave-uniform
+    }
+    bq = 8 * (wave & 1) + (lane & 3) + 4 * ((lane >> 4) & 1);                // 64 wide: 2 x 4 half blocks, 16 x 16 of them
+    bk = ((lane >> 2) & 3) + 4 * (lane >> 5) + 8 * (wave >> 1);
+    return true;
+}
 template <bool KC, int NR, int TILE>
 __device__ __forceinline__ void gm_load(f32x4* reg, const float* __restrict__ P, long s_mn, long s_k, int mn0, int MN,
-                                        int K, int vec, int k0, int tid) {
+                                        int K, int vec, int k0, int tid, int wave) {
+    if (KC) {
 #pragma unroll
-    for (int u = 0; u < NR; ++u) {
-        int i = tid + u * 256;
-        f32x4 v = {0, 0, 0, 0};
-        if (KC) {
+        for (int u = 0; u < NR; ++u) {
+            int i = tid + u * 256;
+            f32x4 v = {0, 0, 0, 0};
             int row = i >> 3, kq = i & 7;
             int m = mn0 + row, k = k0 + kq * 4;
             const float* p = P + (long)m * s_mn + k;
@@ -38,27 +82,44 @@ __device__ __forceinline__ void gm_load(f32x4* reg, const float* __restrict__ P,
 #pragma unroll
                     for (int e = 0; e < 4; ++e) if (k + e < K) v[e] = p[e];
             }
-        } else {
-            int kk = i / (TILE / 4), mq = i - kk * (TILE / 4);
-            int m = mn0 + mq * 4, k = k0 + kk;
+            reg[u] = v;
+        }
+    } else {
+        int bq, bk;
+        const bool mine = gm_block<TILE>(wave, tid & 63, bq, bk);
+#pragma unroll
+        for (int e = 0; e < NR; ++e) {                 // NR == gm_rows<TILE>(): the block's k rows
+            f32x4 v = {0, 0, 0, 0};
+            int m = mn0 + bq * 4, k = k0 + bk * NR + e;
             const float* p = P + (long)k * s_k + m;
-            if (k < K) {
+            if (mine && k < K) {
                 if (vec && m + 3 < MN) v = *(const f32x4*)p;
                 else
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) if (m + e < MN) v[e] = p[e];
+                    for (int c = 0; c < 4; ++c) if (m + c < MN) v[c] = p[c];
             }
+            reg[e] = v;
         }
-        reg[u] = v;
     }
 }
 template <bool KC, int NR, int TILE>
-__device__ __forceinline__ void gm_store(const f32x4* reg, float* S, int tid) {
+__device__ __forceinline__ void gm_store(const f32x4* reg, float* S, int tid, int wave) {
+    if (KC) {
 #pragma unroll
-    for (int u = 0; u < NR; ++u) {
-        int i = tid + u * 256;
-        if (KC) { int row = i >> 3, kq = i & 7; *(f32x4*)(S + row * GM_LDK + kq * 4) = reg[u]; }
-        else { int kk = i / (TILE / 4), mq = i - kk * (TILE / 4); *(f32x4*)(S + kk * TILE + mq * 4) = reg[u]; }
+        for (int u = 0; u < NR; ++u) {
+            int i = tid + u * 256;
+            int row = i >> 3, kq = i & 7;
+            *(f32x4*)(S + row * GM_LDK + kq * 4) = reg[u];
+        }
+    } else {
+        int bq, bk;
+        if (!gm_block<TILE>(wave, tid & 63, bq, bk)) return;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            float* d = S + (bq * 4 + c) * GM_LDK + bk * NR;
+            if (NR == 4) { const f32x4 t = {reg[0][c], reg[1][c], reg[2][c], reg[3][c]}; *(f32x4*)d = t; }
+            else { const f32x2 t = {reg[0][c], reg[1][c]}; *(f32x2*)d = t; }
+        }
     }
 }
 
@@ -73,9 +134,9 @@ __global__ __launch_bounds__(256) void gemm_f32_k(
     const int kb = blockIdx.z * k_len;
     const int K = (kb + k_len < Kfull) ? kb + k_len : Kfull;
     C += (long)blockIdx.z * slab_stride;
-    constexpr int A_FLOATS = A_KC ? BM * GM_LDK : GM_BK * BM;
-    constexpr int B_FLOATS = B_KC ? BN * GM_LDK : GM_BK * BN;
-    constexpr int NA = BM / 32, NB = BN / 32;         // float4 per thread per K-step (BM*32 floats / 256 threads / 4)
+    constexpr int A_FLOATS = BM * GM_LDK, B_FLOATS = BN * GM_LDK;
+    // float4 per thread per K-step: BM*32 floats / 256 threads / 4 of a k-contiguous operand, the k rows of its block otherwise
+    constexpr int NA = A_KC ? BM / 32 : gm_rows<BM>(), NB = B_KC ? BN / 32 : gm_rows<BN>();
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* As0 = smem;                                // [2][A_FLOATS]
     float* Bs0 = smem + 2 * A_FLOATS;                 // [2][B_FLOATS]
@@ -106,19 +167,9 @@ __global__ __launch_bounds__(256) void gemm_f32_k(
 
     auto read_frags = [&](const float* As, const float* Bs, int g, f32x4* af, f32x4* bf) {
 #pragma unroll
-        for (int t = 0; t < WM; ++t) {
-            if (A_KC) af[t] = *(const f32x4*)(As + (wm0 + t * 32 + r) * GM_LDK + g * 8 + 4 * h);
-            else
+        for (int t = 0; t < WM; ++t) af[t] = *(const f32x4*)(As + (wm0 + t * 32 + r) * GM_LDK + g * 8 + 4 * h);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) af[t][j] = As[(g * 8 + 4 * h + j) * BM + wm0 + t * 32 + r];
-        }
-#pragma unroll
-        for (int u = 0; u < WN; ++u) {
-            if (B_KC) bf[u] = *(const f32x4*)(Bs + (wn0 + u * 32 + r) * GM_LDK + g * 8 + 4 * h);
-            else
-#pragma unroll
-                for (int j = 0; j < 4; ++j) bf[u][j] = Bs[(g * 8 + 4 * h + j) * BN + wn0 + u * 32 + r];
-        }
+        for (int u = 0; u < WN; ++u) bf[u] = *(const f32x4*)(Bs + (wn0 + u * 32 + r) * GM_LDK + g * 8 + 4 * h);
     };
     auto mfma_group = [&](const f32x4* af, const f32x4* bf) {
 #pragma unroll
@@ -133,40 +184,57 @@ __global__ __launch_bounds__(256) void gemm_f32_k(
     auto run = [&](auto full_tag) {
         constexpr bool FULL = decltype(full_tag)::value;
         f32x4 ra[NA], rb[NB];
-        // FULL: per-thread source pointers, advanced by one K-step per load (two VALU adds instead of the full index math)
-        const float* pa[NA];
-        const float* pb[NB];
-        const long a_step = A_KC ? GM_BK : GM_BK * a_sk, b_step = B_KC ? GM_BK : GM_BK * b_sk;
+        // FULL: the address of a load is a workgroup-uniform base (the tile's corner at the current K-step, in scalar registers,
+        // advanced once per step by scalar adds) plus a loop-invariant 32-bit byte offset per lane and load: the K loop carries no
+        // vector address arithmetic between its MFMAs (per-thread 64-bit pointers cost two vector adds per load and step).
+        // `full` below admits only tiles whose extent times the leading stride fits the 32-bit offset.
+        const char* ga = (const char*)(A + (A_KC ? (long)m0 * a_si + kb : (long)kb * a_sk + m0));
+        const char* gb = (const char*)(Bm + (B_KC ? (long)n0 * b_sj + kb : (long)kb * b_sk + n0));
+        const long a_step = (A_KC ? GM_BK : GM_BK * a_sk) * (long)sizeof(float), b_step = (B_KC ? GM_BK : GM_BK * b_sk) * (long)sizeof(float);
+        unsigned oa[NA], ob[NB];
+        int aq = 0, ak = 0, bq = 0, bk = 0;            // this thread's block of an m/n-contiguous A, B
+        const bool a_mine = A_KC || gm_block<BM>(wave, lane, aq, ak), b_mine = B_KC || gm_block<BN>(wave, lane, bq, bk);
         if (FULL) {
 #pragma unroll
             for (int u = 0; u < NA; ++u) {
                 int i = tid + u * 256;
-                if (A_KC) pa[u] = A + (long)(m0 + (i >> 3)) * a_si + kb + (i & 7) * 4;
-                else { int kk = i / (BM / 4), mq = i - kk * (BM / 4); pa[u] = A + (long)(kb + kk) * a_sk + m0 + mq * 4; }
+                oa[u] = (unsigned)((A_KC ? (long)(i >> 3) * a_si + (i & 7) * 4 : (long)(ak * NA + u) * a_sk + aq * 4) * (long)sizeof(float));
             }
 #pragma unroll
             for (int u = 0; u < NB; ++u) {
                 int i = tid + u * 256;
-                if (B_KC) pb[u] = Bm + (long)(n0 + (i >> 3)) * b_sj + kb + (i & 7) * 4;
-                else { int kk = i / (BN / 4), mq = i - kk * (BN / 4); pb[u] = Bm + (long)(kb + kk) * b_sk + n0 + mq * 4; }
+                ob[u] = (unsigned)((B_KC ? (long)(i >> 3) * b_sj + (i & 7) * 4 : (long)(bk * NB + u) * b_sk + bq * 4) * (long)sizeof(float));
             }
         }
         auto load = [&](int k0) {
             if (FULL) {
+                // opaque to the optimiser: left to itself, loop strength reduction folds base + offset back into one 64-bit
+                // vector pointer per load and advances each of them with a vector add.  (The constraint also hides that the
+                // pointer is to global memory, hence the explicit address space: a generic pointer would load with flat_load.  The
+                // offsets are hidden too: hoisted out of the loop as 64-bit values, they would no longer be seen as the
+                // zero-extended 32-bit register that the scalar-base form of global_load takes, and cost a vector add again.)
+                asm("" : "+s"(ga));
+                asm("" : "+s"(gb));
+                if (a_mine) {
 #pragma unroll
-                for (int u = 0; u < NA; ++u) { ra[u] = *(const f32x4*)pa[u]; pa[u] += a_step; }
+                    for (int u = 0; u < NA; ++u) { asm("" : "+v"(oa[u])); ra[u] = *(const gm_global f32x4*)((const gm_global char*)ga + oa[u]); }
+                }
+                if (b_mine) {
 #pragma unroll
-                for (int u = 0; u < NB; ++u) { rb[u] = *(const f32x4*)pb[u]; pb[u] += b_step; }
+                    for (int u = 0; u < NB; ++u) { asm("" : "+v"(ob[u])); rb[u] = *(const gm_global f32x4*)((const gm_global char*)gb + ob[u]); }
+                }
+                ga += a_step;
+                gb += b_step;
             } else {
-                gm_load<A_KC, NA, BM>(ra, A, a_si, a_sk, m0, M, K, a_vec, k0, tid);
-                gm_load<B_KC, NB, BN>(rb, Bm, b_sj, b_sk, n0, N, K, b_vec, k0, tid);
+                gm_load<A_KC, NA, BM>(ra, A, a_si, a_sk, m0, M, K, a_vec, k0, tid, wave);
+                gm_load<B_KC, NB, BN>(rb, Bm, b_sj, b_sk, n0, N, K, b_vec, k0, tid, wave);
             }
         };
         auto store = [&](int buf) {
-            gm_store<A_KC, NA, BM>(ra, As0 + buf * A_FLOATS, tid);
-            gm_store<B_KC, NB, BN>(rb, Bs0 + buf * B_FLOATS, tid);
+            gm_store<A_KC, NA, BM>(ra, As0 + buf * A_FLOATS, tid, wave);
+            gm_store<B_KC, NB, BN>(rb, Bs0 + buf * B_FLOATS, tid, wave);
         };
-        auto compute = [&](int buf) {
+        auto compute = [&](int buf, auto ilv_tag) {
             const float* As = As0 + buf * A_FLOATS;
             const float* Bs = Bs0 + buf * B_FLOATS;
             f32x4 af0[WM], bf0[WN], af1[WM], bf1[WN];
@@ -178,6 +246,38 @@ __global__ __launch_bounds__(256) void gemm_f32_k(
             read_frags(As, Bs, 3, af1, bf1);
             mfma_group(af0, bf0);
             mfma_group(af1, bf1);
+            // The order above, pinned.  Left alone hipcc moves the reads of groups 2 and 3 down to where their MFMAs start and
+            // waits for all of them there (seen in the 128 x 128 loops once every fragment was a b128 read): the LDS latency
+            // is then exposed in the middle of every step.  A group's reads reuse the registers of the group two back, so they
+            // follow its last MFMA, one per MFMA, and have the rest of a group (NM - NF MFMAs) to arrive.
+            // ILV (steady state of the FULL path): the LDS stores of step + 1 and the global loads of step + 2 follow this block in
+            // the source and are dealt out behind the MFMAs that follow the last fragment read, one store and one load per
+            // MFMA: a wave issues them under its own MFMAs instead of in a block that only the CU's other workgroup can cover.
+            // (Behind the reads, not in front: hipcc cannot tell that the stores go to the other buffer and keeps LDS order.)
+            constexpr bool ILV = decltype(ilv_tag)::value;
+            constexpr int NF = WM + WN, NM = 4 * WM * WN, NW = NA + NB;
+            __builtin_amdgcn_sched_group_barrier(0x100, 2 * NF, 0);          // groups 0 and 1: DS reads
+            __builtin_amdgcn_sched_group_barrier(0x008, NM, 0);              // group 0: MFMAs
+#pragma unroll
+            for (int g = 0; g < 2; ++g) {
+#pragma unroll
+                for (int i = 0; i < NF; ++i) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                }
+                if (g == 0 || !ILV) __builtin_amdgcn_sched_group_barrier(0x008, NM - NF, 0);
+            }
+            if (ILV) {
+#pragma unroll
+                for (int i = 0; i < NW; ++i) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);      // DS write
+                    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);      // global load
+                }
+                __builtin_amdgcn_sched_group_barrier(0x008, 2 * NM - NF - NW, 0);
+            } else {
+                __builtin_amdgcn_sched_group_barrier(0x008, NM, 0);          // group 3
+            }
         };
         const int nsteps = (K - kb + GM_BK - 1) / GM_BK;
         load(kb);
@@ -186,27 +286,39 @@ __global__ __launch_bounds__(256) void gemm_f32_k(
         __syncthreads();
         int cur = 0, step = 0;
         for (; step + 2 < nsteps; ++step) {           // steady state, branch-free
-            store(cur ^ 1);                            // step+1: registers -> the other LDS buffer
-            load(kb + (step + 2) * GM_BK);             // step+2: global -> registers
-            // The loads must LEAVE here, a whole MFMA block before the next iteration's LDS stores wait for them.  Left to itself
-            // hipcc sinks them below the MFMA block (shorter live ranges), to just in front of the barrier: the next iteration then
-            // waited for an L2 / HBM round trip at its first ds_write with nothing but the barrier in between (round 4, found
-            // in the ISA of every instantiation).  Measured: no change at the GRU shapes (dX 0.270 ms, two-slice dW 0.292 ms) —
-            // the second workgroup of the CU was hiding that wait — but this is the order the pipeline was designed around.
+            constexpr bool ILV = FULL && NA + NB <= 8 * WM * WN - (WM + WN);
+            if (ILV) {
+                compute(cur, std::true_type{});
+                store(cur ^ 1);                        // step+1: registers -> the other LDS buffer
+                load(kb + (step + 2) * GM_BK);         // step+2: global -> registers
+            } else {
+                store(cur ^ 1);
+                load(kb + (step + 2) * GM_BK);
+                // The loads must LEAVE here, a whole MFMA block before the next iteration's LDS stores wait for them.  Left to itself
+                // hipcc sinks them below the MFMA block (shorter live ranges), to just in front of the barrier: the next iteration
+                // then waited for an L2 / HBM round trip at its first ds_write with nothing but the barrier in between (round 4,
+                // found in the ISA of every instantiation).
+                __builtin_amdgcn_sched_barrier(0);
+                compute(cur, std::false_type{});
+            }
+            // ... and the barrier stays behind the MFMA block: hipcc waits for every outstanding LDS read in front of a barrier,
+            // and hoisted to the last read it would expose the latency of group 3's fragments
             __builtin_amdgcn_sched_barrier(0);
-            compute(cur);
             __syncthreads();
             cur ^= 1;
         }
         for (; step < nsteps; ++step) {                // last two steps
             if (step + 1 < nsteps) store(cur ^ 1);
-            compute(cur);
+            compute(cur, std::false_type{});
             __syncthreads();
             cur ^= 1;
         }
     };
     const bool full = a_vec && b_vec && m0 + BM <= M && n0 + BN <= N && ((K - kb) % GM_BK == 0);
-    if (full) run(std::true_type{});
+    // the FULL path's 32-bit lane offsets span a tile's rows: BM (BN) rows of a k-contiguous operand, GM_BK rows of the other kind.
+    // A leading stride of 4M floats and more (no caller has one) goes the guarded way, which indexes in 64 bits.
+    const bool fits = (A_KC ? BM * a_si : GM_BK * a_sk) < (1L << 29) && (B_KC ? BN * b_sj : GM_BK * b_sk) < (1L << 29);
+    if (full && fits) run(std::true_type{});
     else run(std::false_type{});
 
 #pragma unroll
@@ -234,7 +346,7 @@ static int launch_gemm2(dim3 grid, hipStream_t s, const float* A, long a_si, lon
                         long b_sj, float* C, long ldc, const float* bias, float beta, int M, int N, int K, int av, int bv,
                         int k_len, long slab) {
     constexpr int BM = 32 * WM * WVM, BN = 32 * WN * WVN;
-    constexpr size_t lds = 2 * ((AKC ? BM * GM_LDK : GM_BK * BM) + (BKC ? BN * GM_LDK : GM_BK * BN)) * sizeof(float);
+    constexpr size_t lds = 2 * (BM + BN) * GM_LDK * sizeof(float);         // 128 x 128: 72 KB, two workgroups per CU (147 of 160 KB)
     if (lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void*)gemm_f32_k<WVM, WVN, WM, WN, AKC, BKC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) { sed_set_error("gemm_f32: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
