@@ -99,7 +99,7 @@ def check_no_spill(remarks, kernels, allow_agprs=False):
 def build(force=False, verbose=False):
     os.makedirs(OBJ, exist_ok=True)
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_shared.h"), os.path.join(CSRC, "detect_shared.h"), os.path.join(CSRC, "fft2048.h"), os.path.join(CSRC, "tdoa_shared.h"), os.path.join(HERE, "..", "include", "sedcrnn.h")]
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_shared.h"), os.path.join(CSRC, "detect_shared.h"), os.path.join(CSRC, "fft2048.h"), os.path.join(CSRC, "tdoa_shared.h"), os.path.join(CSRC, "phat_shared.h"), os.path.join(HERE, "..", "include", "sedcrnn.h")]
     jobs = []
     objs = []
     for src in SOURCES:

@@ -13,10 +13,10 @@
 // hook of the shared runner), while the slice's chunk partials are in the workspace.  One persistent workgroup of 8 waves takes
 // one event at a time; per pair it re-forms S in LDS, synthesises the 2 F + 1 fine lags into LDS — item = lag j >= 0, 8 lanes
 // per item, bins j8 + 8 i in ascending order, the 8 partial sums joined by the xor-1, 2, 4 shuffle tree, +j and -j from the
-// same two sums: the loop of tdoa_finish_k with a table of 2048 Q angles — and every thread adds fine[J[d][p]] to the srp[d] it
-// owns (LDS).  At Q = 1 the table, the split, the fma order and the tree ARE those of tdoa_finish_k: fine[j] is acc[j] bit for bit.
+// same two sums: phat_lag_sum (phat_shared.h), which tdoa_finish_k calls too, with a table of 2048 Q angles — and every thread
+// adds fine[J[d][p]] to the srp[d] it owns (LDS).  At Q = 1 the table holds the values of tdoa_finish_k's: fine[j] is acc[j] bit for bit.
 // The angle table is the quarter wave (cos, sin)(2 pi k / (2048 Q)), k = 0 .. 512 Q (float64 values rounded once, made on the
-// host), unfolded by index at every read as tdoa_finish_k unfolds pw: 64 KiB at Q = 16, beside srp (64 KiB at D = 16384), S
+// host), unfolded by index at every read (phat_angle): 64 KiB at Q = 16, beside srp (64 KiB at D = 16384), S
 // (8 KiB) and one fine row (16 KiB at F = 2032) within the 160 KiB of LDS.  The fine row is contiguous floats: neighbouring j —
 // what neighbouring directions read — are neighbouring banks, and equal j is a broadcast.
 #include <math.h>
@@ -42,7 +42,7 @@ struct DoaArgs {
 };
 
 size_t doa_lds_bytes(int D, int Q, int max_lag) {
-    return ((size_t)2 * TD_SPEC + (size_t)2 * (512 * Q + 1) + (size_t)(2 * max_lag * Q + 1) + (size_t)D) * sizeof(float);
+    return ((size_t)2 * PHAT_SPEC + (size_t)2 * (512 * Q + 1) + (size_t)(2 * max_lag * Q + 1) + (size_t)D) * sizeof(float);
 }
 
 __global__ __launch_bounds__(DOA_THREADS) void doa_steer_k(const float2* __restrict__ ws, DoaArgs da, TdArgs ta) {
@@ -52,19 +52,13 @@ __global__ __launch_bounds__(DOA_THREADS) void doa_steer_k(const float2* __restr
     const int tid = threadIdx.x;
     const int Q = da.Q, D = da.D, P = ta.P, F = ta.max_lag * Q;
     const int NQ = 512 * Q, NH = 1024 * Q, N = 2048 * Q;         // a quarter, a half and the whole of the angle table
-    float2* s_S = reinterpret_cast<float2*>(lds);                // [TD_SPEC]
-    float2* s_trig = s_S + TD_SPEC;                              // [NQ + 1]
+    float2* s_S = reinterpret_cast<float2*>(lds);                // [PHAT_SPEC]
+    float2* s_trig = s_S + PHAT_SPEC;                            // [NQ + 1]
     float* s_fine = reinterpret_cast<float*>(s_trig + NQ + 1);   // [2 F + 1], lag j at F + j
     float* s_srp = s_fine + 2 * F + 1;                           // [D], entry d belongs to thread d % DOA_THREADS
     for (int k = tid; k <= NQ; k += DOA_THREADS) s_trig[k] = da.trig[k];
     __syncthreads();
-    // (cos, sin)(2 pi m / N), 0 <= m < N, from the quarter wave: the unfolding of tdoa_finish_k's lag table
-    auto angle = [&](int m) -> float2 {
-        const int mm = m <= NH ? m : N - m;
-        const int k = mm <= NQ ? mm : NH - mm;
-        const float2 w = s_trig[k];
-        return make_float2(mm <= NQ ? w.x : -w.x, m <= NH ? w.y : -w.y);
-    };
+    auto angle = [&](int m) -> float2 { return phat_angle<false>(s_trig, m, NQ, NH, N); };      // (cos, sin)(2 pi m / N), 0 <= m < N
     for (int el = blockIdx.x; el < ta.n_ev; el += gridDim.x) {
         const long e = ta.e0 + el;
         int rec, nf;
@@ -77,36 +71,17 @@ __global__ __launch_bounds__(DOA_THREADS) void doa_steer_k(const float2* __restr
             continue;
         }
         const int nch = (nf + TD_CHUNK - 1) / TD_CHUNK;
-        const float2* wev = ws + (long)el * ta.cpe * P * TD_SPEC;
+        const float2* wev = ws + (long)el * ta.cpe * P * PHAT_SPEC;
         for (int p = 0; p < P; ++p) {
-            // ── S = the chunk partials in ascending chunk order (tdoa_finish_k) ──
-            for (int k = tid; k < 1025; k += DOA_THREADS) {
-                float2 s = wev[(long)p * TD_SPEC + k];
-                for (int c = 1; c < nch; ++c) {
-                    const float2 v = wev[((long)c * P + p) * TD_SPEC + k];
-                    s.x += v.x; s.y += v.y;
-                }
-                s_S[k] = s;
-            }
+            phat_sum_chunks(s_S, wev, p, P, nch, tid, DOA_THREADS);
             __syncthreads();
             // ── fine lags: item = j = 0..F, 8 lanes per item; fine[+j] = A - B, fine[-j] = A + B ──
             const int grp = tid >> 3, j8 = tid & 7;
             for (int it0 = 0; it0 <= F; it0 += DOA_THREADS / 8) {
                 const bool valid = it0 + grp <= F;
                 const int j = valid ? it0 + grp : 0;
-                float A = 0.f, B = 0.f;
-                int m = (j8 * j) & (N - 1);
-                const int step = (8 * j) & (N - 1);
-#pragma unroll 8
-                for (int i = 0; i < LM_N / 8; ++i) {             // bins k = j8 + 8 i, ascending
-                    const float2 q = s_S[j8 + 8 * i], t = angle(m);
-                    A = fmaf(q.x, t.x, A);
-                    B = fmaf(q.y, t.y, B);
-                    m = (m + step) & (N - 1);
-                }
-                A += __shfl_xor(A, 1, 64); B += __shfl_xor(B, 1, 64);
-                A += __shfl_xor(A, 2, 64); B += __shfl_xor(B, 2, 64);
-                A += __shfl_xor(A, 4, 64); B += __shfl_xor(B, 4, 64);
+                const float2 ab = phat_lag_sum(s_S, j8, j, N, angle);
+                const float A = ab.x, B = ab.y;
                 if (valid && j8 < 2) {
                     const float ny = s_S[LM_N].x * angle((LM_N * j) & (N - 1)).x;        // Re S[1024] cos(pi j / Q): +-S[1024] at Q = 1
                     const bool plus = j8 == 0;
@@ -123,26 +98,21 @@ __global__ __launch_bounds__(DOA_THREADS) void doa_steer_k(const float2* __restr
             }
             __syncthreads();                                     // S and the fine row may be overwritten by the next pair
         }
-        // ── the first maximum of srp in ascending d (the tie rule of tdoa_finish_k) ──
-        float best = -INFINITY, low = INFINITY;
-        int at = 0x7fffffff;
+        // ── the first maximum of srp in ascending d ──
+        FirstMax fm{-INFINITY, INFINITY, 0x7fffffff};
         for (int d = tid; d < D; d += DOA_THREADS) {
             const float v = s_srp[d];
             if (da.srp_out) da.srp_out[e * D + d] = v;
-            if (v > best) { best = v; at = d; }
-            low = fminf(low, v);
+            if (v > fm.best) { fm.best = v; fm.at = d; }
+            fm.low = fminf(fm.low, v);
         }
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const float ob = __shfl_xor(best, o, 64), ol = __shfl_xor(low, o, 64);
-            const int oa = __shfl_xor(at, o, 64);
-            if (ob > best || (ob == best && oa < at)) { best = ob; at = oa; }
-            low = fminf(low, ol);
-        }
+        fm = first_max_wave(fm);
+        float best = fm.best, low = fm.low;
+        int at = fm.at;
         if ((tid & 63) == 0) { r_best[tid >> 6] = best; r_low[tid >> 6] = low; r_at[tid >> 6] = at; }
         __syncthreads();
         if (tid == 0) {
-            for (int w = 1; w < DOA_WAVES; ++w) {
+            for (int w = 1; w < DOA_WAVES; ++w) {                // (the tie rule of first_max_wave, across the waves)
                 const float ob = r_best[w];
                 const int oa = r_at[w];
                 if (ob > best || (ob == best && oa < at)) { best = ob; at = oa; }

@@ -1,6 +1,9 @@
-// fft2048.h — the register-resident 2048-point real FFT that logmel.hip and gcc.hip share: the layout of the constant blob
-// (window, inter-pass and pairing twiddles), complex points in VGPR pairs, the 32-point transform, the half-wave exchange
-// through LDS and the guarded PCM load.  Everything is force-inlined into the kernels that use it.
+// fft2048.h — the register-resident 2048-point real FFT of logmel.hip, gcc.hip and tdoa.hip: the layout of the constant blob
+// (window, inter-pass and pairing twiddles) and its staging into LDS, the lane geometry, complex points in VGPR pairs, the
+// 32-point transform, the half-wave exchange through LDS (store and read-back), the guarded frame load, the two passes from
+// samples to Z (fft2048_passes) and the pairing pass from Z to the complex half spectrum (fft2048_spectrum).  Everything is
+// force-inlined into the kernels that use it; what a kernel keeps for itself is its fast (unguarded) load path and, in
+// logmel.hip, a pairing pass of its own that produces power bins.
 #pragma once
 #include "common.h"
 
@@ -152,6 +155,129 @@ __device__ __forceinline__ float pcm_at(const float* __restrict__ pcm, long n, l
         return pcm[r];
     }
     return 0.f;
+}
+
+// ── what a kernel sets up once per workgroup ──
+// the constant blob (`words` 32-bit words, a multiple of 4): global -> LDS word 0; the caller's barrier makes it visible
+__device__ __forceinline__ void fft_stage_tables(float* lds, const uint32_t* __restrict__ tables, int words, int tid, int threads) {
+    const f32x4* src = reinterpret_cast<const f32x4*>(tables);
+    f32x4* dst = reinterpret_cast<f32x4*>(lds);
+    for (int i = tid; i < words / 4; i += threads) dst[i] = src[i];
+}
+// A half wave (32 lanes) transforms one frame.  Lane (half, r) holds column r of the frame's 32 x 32 points; `partner` is the
+// lane of the same half that holds column (32 - r) % 32, the mirror the pairing pass reads; `xbase` is the LDS byte address
+// (wave-uniform, in an SGPR) of the wave's 32 x 65-float exchange buffer, which starts `wscr_off` floats into the dynamic LDS
+// array.  (The caller subtracts the array itself, wscr - lds: behind a pointer parameter hipcc no longer folds the difference.)
+// half, r and partner are functions of `lane` and not stored values so that every function below that takes an FftLane
+// spells out r = lane & 31 in its own body: hipcc simplifies a function before it inlines it, and what it makes of an index
+// such as 1024 - (r + 32 k2) depends on whether it knows r < 32 at that point.
+struct FftLane {
+    int lane;
+    unsigned xbase;
+    __device__ __forceinline__ int half() const { return lane >> 5; }
+    __device__ __forceinline__ int r() const { return lane & 31; }
+    __device__ __forceinline__ int partner() const { return (lane & 32) | ((32 - r()) & 31); }
+};
+__device__ __forceinline__ FftLane fft_lane(int lane, ptrdiff_t wscr_off) {
+    const unsigned xbase = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)wscr_off * 4u +
+                                                          (unsigned)__builtin_amdgcn_groupstaticsize());
+    return FftLane{lane, xbase};
+}
+
+// The read-back of the exchange: z[n2].x (IMAG = 0) or .y (IMAG = 1) = column 32 half + n2 of row r, xaddr = its byte address.
+// Single-dword reads straight into the halves of the register pairs: left to hipcc these become ds_read2_b32 into scratch
+// pairs + 64 v_mov to split them — LDS issue slots are cheaper here than vector ones.
+// THE HAZARD.  To the compiler an asm output is valid the moment its statement ends, but a ds_read_b32's data arrives only
+// behind the s_waitcnt below, which hipcc does not know belongs to the reads.  Anything it places between a read and the wait
+// that touches a destination — a v_mov, a spill, a copy to an AGPR — captures stale data, and the returning read then lands
+// in a register that may have been given to something else.  What guards against it: every statement is volatile (kept in
+// order, nothing of them is duplicated or dropped), the empty "+v" statements behind the wait pin each destination pair as
+// live and in a VGPR there, the build refuses scratch in every kernel that uses this (build.py, NO_SCRATCH_KERNELS), and
+// tests/test_cpu_fft_exchange_isa.py asserts on the compiled code that nothing but the 32 reads stands between the first
+// read and the wait.  (One asm statement with 32 early-clobber outputs would make it structural; it changes register
+// allocation and is to be measured on its own.)
+template <int IMAG>
+__device__ __forceinline__ void exchange_load(unsigned xaddr, f2 (&z)[32]) {
+#pragma unroll
+    for (int n2 = 0; n2 < 32; ++n2) {
+        float t;
+        asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(t) : "v"(xaddr), "i"(n2 * 4));
+        if (IMAG) z[n2].y = t;
+        else z[n2].x = t;
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int n2 = 0; n2 < 32; ++n2) asm volatile("" : "+v"(z[n2]));
+}
+
+// The guarded frame load (edge frames, odd hop, unaligned clips, a ring that wraps): z[n1] = (x[64 n1 + 2r], x[64 n1 + 2r + 1])
+// with x[off] = sample(off), 0 <= off < 2048, staged through the half wave's 1024 floats `scr` so that this cold path costs
+// no registers (dynamic index, not unrolled).
+template <typename Sample>
+__device__ __forceinline__ void fft_load_guarded(f2 (&z)[32], float* scr, const FftLane& fl, Sample sample) {
+    const int r = fl.r();
+    wave_lds_fence();
+#pragma unroll 1
+    for (int n1 = 0; n1 < 32; ++n1) scr[n1 * 32 + r] = sample(64 * n1 + 2 * r);
+    wave_lds_fence();
+#pragma unroll
+    for (int n1 = 0; n1 < 32; ++n1) z[n1].x = scr[n1 * 32 + r];
+    wave_lds_fence();
+#pragma unroll 1
+    for (int n1 = 0; n1 < 32; ++n1) scr[n1 * 32 + r] = sample(64 * n1 + 2 * r + 1);
+    wave_lds_fence();
+#pragma unroll
+    for (int n1 = 0; n1 < 32; ++n1) z[n1].y = scr[n1 * 32 + r];
+}
+
+// Samples to Z: z[n1] = (x[64 n1 + 2r], x[64 n1 + 2r + 1]) on entry, Z[r + 32 k2] = z[brev5(k2)] on return.
+__device__ __forceinline__ void fft2048_passes(f2 (&z)[32], const FftLane& fl, const f2* s_win, const f2* s_tw) {
+    const int r = fl.r(), half = fl.half();
+#pragma unroll
+    for (int n1 = 0; n1 < 32; ++n1) z[n1] *= s_win[32 * n1 + r];
+    // ── pass 1: FFT over n1, twiddle W_1024^{r k1} ──
+    fft32(z);
+#pragma unroll
+    for (int k1 = 1; k1 < 32; ++k1) {
+        const int b = brev5(k1);
+        z[b] = cmul(z[b], s_tw[k1 * 32 + r]);
+    }
+    // ── exchange through LDS (real parts, then imaginary parts, the wave's 32 x 65 buffer): lane (half, r) holds
+    //    A[r][k1] and stores row k1 lane-linearly; lane (half, c) then needs A[n2][c] = row c, column 32*half + n2 ──
+    wave_lds_fence();                                        // whatever read the buffer before (a mel pass, a guarded load) is done
+    exchange_store<0>(fl.xbase, z);
+    wave_lds_fence();
+    const unsigned xaddr = fl.xbase + (unsigned)(r * LM_ROW_BYTES + 128 * half);
+    exchange_load<0>(xaddr, z);                              // (the .y halves — the imaginary parts — are still to be stored)
+    wave_lds_fence();
+    exchange_store<1>(fl.xbase, z);
+    wave_lds_fence();
+    exchange_load<1>(xaddr, z);
+    wave_lds_fence();
+    // ── pass 2: FFT over n2 ──
+    fft32(z);
+}
+
+// Z to the complex half spectrum spec[0..1024] of the real frame (LDS):
+// 2 X[k] = (Z[k] + conj Z[N-k]) - i W_2048^k (Z[k] - conj Z[N-k]) = e + t, and 2 X[N-k] = conj(e - t); lane r owns k = r + 32 k2,
+// k2 < 16, and its mirror N-k, whose Z lives in lane (32 - r) % 32, register 31 - k2 (lane 0: its own register 32 - k2).
+__device__ __forceinline__ void fft2048_spectrum(const f2 (&z)[32], const FftLane& fl, const f2* s_pw, float2* spec) {
+    const int r = fl.r(), partner = fl.partner();
+#pragma unroll
+    for (int k2 = 0; k2 < 16; ++k2) {
+        const int bp = brev5(31 - k2), b0 = brev5((32 - k2) & 31);
+        f2 pp = {__shfl(z[bp].x, partner, 64), __shfl(z[bp].y, partner, 64)};
+        if (r == 0) pp = z[b0];
+        const f2 zz = z[brev5(k2)];
+        const int k = r + 32 * k2;
+        const f2 e = add_conj(zz, pp);
+        const f2 q = rot_sub_conj(zz, pp);
+        const f2 t = cmul(q, s_pw[k]);
+        const f2 a = e + t, bb = e - t;
+        spec[k] = make_float2(0.5f * a.x, 0.5f * a.y);
+        spec[LM_N - k] = make_float2(0.5f * bb.x, -0.5f * bb.y);
+    }
+    if (r == 0) { const f2 zz = z[brev5(16)]; spec[512] = make_float2(zz.x, -zz.y); }      // X[512] = conj Z[512]
 }
 
 }  // namespace

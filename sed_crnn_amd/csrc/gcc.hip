@@ -16,6 +16,7 @@
 //      their products (A = sum Re Pk cos, B = sum Im Pk sin: cc[+-tau] = A -+ B).  Eight neighbouring lanes own one (pair, tau):
 //      lane j sums the bins k = j, j+8, ... in ascending order against a 2048-entry cos/sin table in LDS (exact table values at
 //      index k tau mod 2048: no recurrences), the eight partial sums are combined by three xor-shuffles.
+// Steps 2 and 3 are phat_bin and phat_lag_sum of phat_shared.h, which per-event TDOA and DOA call too.
 // Every output is therefore summed in one fixed order that depends on nothing but the frame's samples: not on the batch, the
 // clip's place in the buffer or the launch shape.
 #include <math.h>
@@ -23,11 +24,11 @@
 #include <vector>
 #include "common.h"
 #include "fft2048.h"
+#include "phat_shared.h"
 
 #define GC_WAVES 8                                // (4 waves: 27.2 ms instead of 24.8 for the hour of 4-channel audio of DESIGN 5m)
 #define GC_THREADS (GC_WAVES * 64)
 #define GC_MAX_CH 8
-#define GC_SPEC 1026                              // float2 per spectrum / per Pk row (1025 bins + 1 pad)
 #define GC_TAB_WORDS LM_OFF_ENT                   // of the log-mel blob: header, window, inter-pass and pairing twiddles
 #define GC_LAG_WORDS (2 * LM_NFFT)                // LDS floats of the lag table (cos, sin)(2 pi m / 2048), m = 0..2047
 #define GC_FFT_SCR (2 * LM_SCR)                   // floats of exchange scratch per transforming wave (>= 32 x 65)
@@ -49,40 +50,26 @@ __global__ __launch_bounds__(GC_THREADS) void gcc_phat_k(const float* __restrict
                                                          float* __restrict__ out, int hop, int pad_mode, GcArgs ga) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x;
-    {   // window + twiddles of the log-mel blob: global -> LDS, once per (persistent) workgroup
-        const f32x4* src = reinterpret_cast<const f32x4*>(tables);
-        f32x4* dst = reinterpret_cast<f32x4*>(lds);
-        for (int i = tid; i < GC_TAB_WORDS / 4; i += GC_THREADS) dst[i] = src[i];
-    }
+    fft_stage_tables(lds, tables, GC_TAB_WORDS, tid, GC_THREADS);     // once per (persistent) workgroup
     __syncthreads();
-    {   // the lag table (cos, sin)(2 pi m / 2048), m = 0..2047, unfolded from the blob's pairing twiddles pw[k] = (cos, -sin)
-        // (2 pi k / 2048), k = 0..512 (float64 values rounded once): nothing is computed or uploaded per call
-        const float2* pw = reinterpret_cast<const float2*>(lds + LM_OFF_PW);
-        float2* lag = reinterpret_cast<float2*>(lds + GC_TAB_WORDS);
-        for (int m = tid; m < LM_NFFT; m += GC_THREADS) {
-            const int mm = m <= LM_N ? m : LM_NFFT - m;          // cos(2 pi - a) = cos a, sin(2 pi - a) = -sin a
-            const int k = mm <= LM_N / 2 ? mm : LM_N - mm;       // cos(pi - a) = -cos a, sin(pi - a) = sin a
-            const float2 w = pw[k];
-            lag[m] = make_float2(mm <= LM_N / 2 ? w.x : -w.x, m <= LM_N ? -w.y : w.y);
-        }
-    }
+    // the lag table, unfolded from the blob's pairing twiddles: nothing is computed or uploaded per call
+    phat_lag_table(reinterpret_cast<float2*>(lds + GC_TAB_WORDS), reinterpret_cast<const float2*>(lds + LM_OFF_PW), tid, GC_THREADS);
     __syncthreads();
     const f2* s_win = reinterpret_cast<const f2*>(lds + LM_OFF_WIN);
     const f2* s_tw = reinterpret_cast<const f2*>(lds + LM_OFF_TW);
     const f2* s_pw = reinterpret_cast<const f2*>(lds + LM_OFF_PW);
     const float2* s_lag = reinterpret_cast<const float2*>(lds + GC_TAB_WORDS);
-    float2* s_spec = reinterpret_cast<float2*>(lds + GC_TAB_WORDS + GC_LAG_WORDS);           // [C][GC_SPEC]
-    float* s_uni = lds + GC_TAB_WORDS + GC_LAG_WORDS + ga.C * GC_SPEC * 2;                     // FFT scratch, then Pk [batch][GC_SPEC]
+    float2* s_spec = reinterpret_cast<float2*>(lds + GC_TAB_WORDS + GC_LAG_WORDS);           // [C][PHAT_SPEC]
+    float* s_uni = lds + GC_TAB_WORDS + GC_LAG_WORDS + ga.C * PHAT_SPEC * 2;                 // FFT scratch, then Pk [batch][PHAT_SPEC]
     float2* s_pk = reinterpret_cast<float2*>(s_uni);
 
     const int C = ga.C, P = ga.P, L = ga.n_lags, T = L / 2 + 1;
-    const int lane = tid & 63, wave = tid >> 6, half = lane >> 5, r = lane & 31;
+    const int wave = tid >> 6;
     const int nfw = (C + 1) >> 1;                                // waves that transform
     float* wscr = s_uni + wave * GC_FFT_SCR;                     // (only used by waves < nfw)
+    const FftLane fl = fft_lane(tid & 63, wscr - lds);
+    const int half = fl.half(), r = fl.r();
     float* scr = wscr + half * LM_SCR;
-    const unsigned xbase = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(wscr - lds) * 4u +
-                                                          (unsigned)__builtin_amdgcn_groupstaticsize());
-    const int partner = (lane & 32) | ((32 - r) & 31);
 
     for (long row = blockIdx.x; row < ga.rows; row += gridDim.x) {
         int lo = 0, hi = ga.R - 1;                               // the last recording whose first row is <= row (block-uniform)
@@ -106,87 +93,22 @@ __global__ __launch_bounds__(GC_THREADS) void gcc_phat_k(const float* __restrict
                 const f2* src = reinterpret_cast<const f2*>(cpcm + start) + r;
 #pragma unroll
                 for (int n1 = 0; n1 < 32; ++n1) z[n1] = src[32 * n1];
-            } else {                                             // edge frames / odd hop / unaligned clips: guarded loads through LDS
-                wave_lds_fence();
-#pragma unroll 1
-                for (int n1 = 0; n1 < 32; ++n1) scr[n1 * 32 + r] = pcm_at(cpcm, start + 64 * n1 + 2 * r, ns, pad_mode);
-                wave_lds_fence();
-#pragma unroll
-                for (int n1 = 0; n1 < 32; ++n1) z[n1].x = scr[n1 * 32 + r];
-                wave_lds_fence();
-#pragma unroll 1
-                for (int n1 = 0; n1 < 32; ++n1) scr[n1 * 32 + r] = pcm_at(cpcm, start + 64 * n1 + 2 * r + 1, ns, pad_mode);
-                wave_lds_fence();
-#pragma unroll
-                for (int n1 = 0; n1 < 32; ++n1) z[n1].y = scr[n1 * 32 + r];
+            } else {                                             // edge frames / odd hop / unaligned clips
+                fft_load_guarded(z, scr, fl, [&](int off) { return pcm_at(cpcm, start + off, ns, pad_mode); });
             }
-#pragma unroll
-            for (int n1 = 0; n1 < 32; ++n1) z[n1] *= s_win[32 * n1 + r];
-            // ── pass 1 over n1, twiddle W_1024^{r k1}, exchange through the wave's 32 x 65 buffer, pass 2 over n2 (logmel.hip) ──
-            fft32(z);
-#pragma unroll
-            for (int k1 = 1; k1 < 32; ++k1) {
-                const int b = brev5(k1);
-                z[b] = cmul(z[b], s_tw[k1 * 32 + r]);
-            }
-            wave_lds_fence();
-            exchange_store<0>(xbase, z);
-            wave_lds_fence();
-            const unsigned xaddr = xbase + (unsigned)(r * LM_ROW_BYTES + 128 * half);
-#define GC_XREAD(H)                                                                                              \
-    _Pragma("unroll") for (int n2 = 0; n2 < 32; ++n2) {                                                           \
-        float t_;                                                                                                \
-        asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(t_) : "v"(xaddr), "i"(n2 * 4));                       \
-        z[n2].H = t_;                                                                                            \
-    }                                                                                                            \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                           \
-    _Pragma("unroll") for (int n2 = 0; n2 < 32; ++n2) asm volatile("" : "+v"(z[n2]));
-            GC_XREAD(x)
-            wave_lds_fence();
-            exchange_store<1>(xbase, z);
-            wave_lds_fence();
-            GC_XREAD(y)
-#undef GC_XREAD
-            wave_lds_fence();
-            fft32(z);                                            // Z[r + 32 k2] = z[brev5(k2)]
-            // ── pairing: 2 X[k] = (Z[k] + conj Z[N-k]) - i W_2048^k (Z[k] - conj Z[N-k]) = e + t, and 2 X[N-k] = conj(e - t) ──
-            float2* spec = s_spec + ch * GC_SPEC;
-#pragma unroll
-            for (int k2 = 0; k2 < 16; ++k2) {
-                const int bp = brev5(31 - k2), b0 = brev5((32 - k2) & 31);
-                f2 pp = {__shfl(z[bp].x, partner, 64), __shfl(z[bp].y, partner, 64)};
-                if (r == 0) pp = z[b0];
-                const f2 zz = z[brev5(k2)];
-                const int k = r + 32 * k2;
-                const f2 e = add_conj(zz, pp);
-                const f2 q = rot_sub_conj(zz, pp);
-                const f2 t = cmul(q, s_pw[k]);
-                const f2 a = e + t, bb = e - t;
-                spec[k] = make_float2(0.5f * a.x, 0.5f * a.y);
-                spec[LM_N - k] = make_float2(0.5f * bb.x, -0.5f * bb.y);
-            }
-            if (r == 0) { const f2 zz = z[brev5(16)]; spec[512] = make_float2(zz.x, -zz.y); }      // X[512] = conj Z[512]
+            fft2048_passes(z, fl, s_win, s_tw);
+            fft2048_spectrum(z, fl, s_pw, s_spec + ch * PHAT_SPEC);
         }
         __syncthreads();
 
         for (int p0 = 0; p0 < P; p0 += ga.pairs_per_batch) {
             const int nb = (P - p0 < ga.pairs_per_batch) ? P - p0 : ga.pairs_per_batch;
-            // ── Pk of the batch's pairs; Pk[0] is stored halved (the sum below counts every bin twice), imaginary part 0 ──
+            // ── Pk of the batch's pairs ──
             for (int idx = tid; idx < nb * 1025; idx += GC_THREADS) {
                 const int pb = idx / 1025, k = idx - pb * 1025;
-                int i = 0, rem = p0 + pb;                        // pair p -> (i, j), lexicographic
-                while (rem >= C - 1 - i) { rem -= C - 1 - i; ++i; }
-                const int j = i + 1 + rem;
-                const float2 a = s_spec[i * GC_SPEC + k], b = s_spec[j * GC_SPEC + k];
-                const float gr = a.x * b.x + a.y * b.y, gi = a.y * b.x - a.x * b.y;
-                const float m2 = gr * gr + gi * gi;
-                // (m2 beyond the float range — samples of ~1e6 and more — is inf, and G / sqrt(inf) = 0 by the definition for a
-                // finite G; G * rsqrt(inf) with an infinite G would be NaN instead, so those bins are written as 0 explicitly)
-                const float inv = (m2 >= 1e-30f && m2 <= 3.0e38f) ? rsqrtf(m2) : 0.f;
-                float pr = gr * inv, pi = gi * inv;
-                if (k == 0) { pr *= 0.5f; pi = 0.f; }
-                if (k == LM_N) pi = 0.f;
-                s_pk[pb * GC_SPEC + k] = make_float2(pr, pi);
+                int i, j;
+                phat_pair(p0 + pb, C, i, j);
+                s_pk[pb * PHAT_SPEC + k] = phat_bin(s_spec[i * PHAT_SPEC + k], s_spec[j * PHAT_SPEC + k], k);
             }
             __syncthreads();
             // ── lag synthesis: item = (pair of the batch, tau = 0..L/2), 8 lanes per item ──
@@ -195,20 +117,9 @@ __global__ __launch_bounds__(GC_THREADS) void gcc_phat_k(const float* __restrict
                 const bool valid = it0 + grp < n_items;
                 const int item = valid ? it0 + grp : 0;
                 const int pb = item / T, tau = item - pb * T;
-                const float2* pk = s_pk + pb * GC_SPEC;
-                float A = 0.f, B = 0.f;
-                int m = (j8 * tau) & (LM_NFFT - 1);
-                const int step = (8 * tau) & (LM_NFFT - 1);
-#pragma unroll 8
-                for (int i = 0; i < LM_N / 8; ++i) {             // bins k = j8 + 8 i, ascending
-                    const float2 p = pk[j8 + 8 * i], t = s_lag[m];
-                    A = fmaf(p.x, t.x, A);
-                    B = fmaf(p.y, t.y, B);
-                    m = (m + step) & (LM_NFFT - 1);
-                }
-                A += __shfl_xor(A, 1, 64); B += __shfl_xor(B, 1, 64);
-                A += __shfl_xor(A, 2, 64); B += __shfl_xor(B, 2, 64);
-                A += __shfl_xor(A, 4, 64); B += __shfl_xor(B, 4, 64);
+                const float2* pk = s_pk + pb * PHAT_SPEC;
+                const float2 ab = phat_lag_sum(pk, j8, tau, LM_NFFT, [&](int m) { return s_lag[m]; });
+                const float A = ab.x, B = ab.y;
                 // lane 0 of the group stores cc[+tau] = A - B, lane 1 cc[-tau] = A + B
                 if (valid && j8 < 2) {
                     const float ny = pk[LM_N].x, sgn = (tau & 1) ? -ny : ny;
@@ -229,8 +140,8 @@ __global__ __launch_bounds__(GC_THREADS) void gcc_phat_k(const float* __restrict
 
 // LDS of the kernel for C channels with `batch` pairs of Pk resident
 size_t gcc_lds_bytes(int C, int batch) {
-    const size_t fft = (size_t)((C + 1) / 2) * GC_FFT_SCR, pk = (size_t)batch * GC_SPEC * 2;
-    return ((size_t)GC_TAB_WORDS + GC_LAG_WORDS + (size_t)C * GC_SPEC * 2 + (fft > pk ? fft : pk)) * sizeof(float);
+    const size_t fft = (size_t)((C + 1) / 2) * GC_FFT_SCR, pk = (size_t)batch * PHAT_SPEC * 2;
+    return ((size_t)GC_TAB_WORDS + GC_LAG_WORDS + (size_t)C * PHAT_SPEC * 2 + (fft > pk ? fft : pk)) * sizeof(float);
 }
 
 // 64-bit words of row_off [R+1], sample_off [R*C] and n_samples [R]

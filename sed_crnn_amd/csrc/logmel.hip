@@ -73,11 +73,7 @@ __global__ __launch_bounds__(WPB * 64) void logmel_fft_k(const float* __restrict
                                                          LmBatch bt = LmBatch{}) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x;
-    {   // tables: global -> LDS, once per workgroup (table_words is a multiple of 4)
-        const f32x4* src = reinterpret_cast<const f32x4*>(tables);
-        f32x4* dst = reinterpret_cast<f32x4*>(lds);
-        for (int i = tid; i < table_words / 4; i += WPB * 64) dst[i] = src[i];
-    }
+    fft_stage_tables(lds, tables, table_words, tid, WPB * 64);       // once per workgroup (table_words is a multiple of 4)
     // the fused scaler's coefficients go to LDS too: a global load inside the loop would have to retire IN ORDER behind the
     // PCM prefetch of the next pair (vmcnt counts in order), i.e. wait for exactly the latency the prefetch is there to hide.
     // That holds all the more for the C n_mels coefficients of a multichannel scaler: which slice a wave needs changes with
@@ -104,9 +100,9 @@ __global__ __launch_bounds__(WPB * 64) void logmel_fft_k(const float* __restrict
     float* scr = lds + table_words + (wave * 2 + half) * LM_FRAME_SCR;      // this half wave's transpose / power buffer
     float* part = scr + LM_SCR;
     float* wscr = lds + table_words + wave * 2 * LM_FRAME_SCR;               // the wave's whole scratch: the 32 x 65 exchange buffer
-    const unsigned xbase = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(wscr - lds) * 4u +
-                                                          (unsigned)__builtin_amdgcn_groupstaticsize());
-    const int partner = (lane & 32) | ((32 - r) & 31);
+    const FftLane fl = fft_lane(lane, wscr - lds);
+    const int partner = fl.partner();
+    const unsigned xbase = fl.xbase;
     const long n_pairs = SEG ? bt.n_pairs : (n_frames + 1) >> 1;
 
     // interior frame pairs with an even hop are read by plain 8-byte loads; the loads of the NEXT pair are issued before
@@ -147,6 +143,10 @@ __global__ __launch_bounds__(WPB * 64) void logmel_fft_k(const float* __restrict
         const float* cpcm = cur.pcm;
         const long cns = cur.n_samples;
         // ── z[32 n1 + r] = (x[64 n1 + 2r], x[64 n1 + 2r + 1]) * window ──
+        // (From here to pass 2 this is fft_load_guarded and fft2048_passes of fft2048.h, written out: called as functions they
+        // compute the same values, but hipcc simplifies a function before it inlines it and the instantiations then come out with
+        // other register assignments — the 12-wave one at 165 instead of 163 of its 168 VGPRs with the guarded load.  The kernel
+        // is kept as measured; a change to either copy belongs in both.)
         const bool loaded = nloaded;
         if (DB && loaded) {
 #pragma unroll
@@ -193,23 +193,12 @@ __global__ __launch_bounds__(WPB * 64) void logmel_fft_k(const float* __restrict
         wave_lds_fence();                                    // the previous frame's mel pass has finished reading the scratch
         exchange_store<0>(xbase, z);
         wave_lds_fence();
-        // (single-dword reads straight into the halves of the register pairs: left to hipcc these become ds_read2_b32 into
-        // scratch pairs + 64 v_mov to split them — LDS issue slots are cheaper here than vector ones)
         const unsigned xaddr = xbase + (unsigned)(r * LM_ROW_BYTES + 128 * half);          // LDS byte address of xrow
-#define LM_XREAD(H)                                                                                              \
-    _Pragma("unroll") for (int n2 = 0; n2 < 32; ++n2) {                                                           \
-        float t_;                                                                                                \
-        asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(t_) : "v"(xaddr), "i"(n2 * 4));                       \
-        z[n2].H = t_;                                                                                            \
-    }                                                                                                            \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                           \
-    _Pragma("unroll") for (int n2 = 0; n2 < 32; ++n2) asm volatile("" : "+v"(z[n2]));
-        LM_XREAD(x)                                          // (the .y halves — the imaginary parts — are still to be stored)
+        exchange_load<0>(xaddr, z);                          // (the .y halves — the imaginary parts — are still to be stored)
         wave_lds_fence();
         exchange_store<1>(xbase, z);
         wave_lds_fence();
-        LM_XREAD(y)
-#undef LM_XREAD
+        exchange_load<1>(xaddr, z);
         wave_lds_fence();
         // ── pass 2: FFT over n2 -> Z[r + 32 k2] = z[brev5(k2)] ──
         fft32(z);

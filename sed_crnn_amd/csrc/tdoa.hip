@@ -2,7 +2,7 @@
 //
 // For a detected event (rec, onset, offset, peak_frame in output frames), the frames [f0, f1) it is located on
 // (td_event_range below; sed_crnn_amd/localize.py states the same rule on the host) and microphone pair (i, j), i < j:
-//   Pk_f[k] = G_f[k] / |G_f[k]|, G_f = X_i conj X_j of frame f     (gcc.hip's definition, thresholds and real DC / Nyquist bins)
+//   Pk_f[k] = G_f[k] / |G_f[k]|, G_f = X_i conj X_j of frame f     (phat_bin of phat_shared.h: gcc.hip's Pk)
 //   S[k]    = sum_{f = f0}^{f1 - 1} Pk_f[k]
 //   acc[tau] = (1/2048) (S[0] + (-1)^tau S[1024] + 2 sum_{k=1..1023} Re(S[k] e^{+2 pi i k tau / 2048})),  |tau| <= max_lag + 1
 //   t* = first maximum of acc over |tau| <= max_lag;  lag = t* + 0.5 (l - r) / (l - 2 m + r) where that denominator is < 0;
@@ -13,13 +13,13 @@
 // Shape (gfx950), two plain launches per slice of the event table; no workgroup waits on another and there are no atomics:
 //   tdoa_accum_k   one workgroup of 8 waves owns one CHUNK: TD_CHUNK consecutive frames of one event, counted from the event's
 //                  f0.  Per frame: the FFT of the C channels into LDS and the whitening of every pair (steps 1 and 2 of
-//                  gcc_phat_k, the same code), added into a per-pair accumulator [pairs of the batch][1026] float2 in LDS in
+//                  gcc_phat_k: the functions it calls), added into a per-pair accumulator [pairs of the batch][1026] float2 in LDS in
 //                  ascending frame order; every accumulator entry belongs to one lane.  Where the spectra fit LDS twice
 //                  (C <= 4) the transforming waves run one frame ahead of the whitening waves.  The chunk's partial sums go
 //                  to the workspace.  Where the P accumulators do not fit beside the spectra (C >= 5) the pairs go in batches and the
 //                  chunk's frames are transformed again for every batch.
 //   tdoa_finish_k  per (event, pair): the chunk partials added in ascending chunk order, the 2 max_lag + 3 lags by the
-//                  8-lanes-per-(pair, tau) direct sum against the exact 2048-entry (cos, sin) table, peak and parabola.
+//                  8-lanes-per-(pair, tau) direct sum against the exact 2048-entry (cos, sin) table (phat_lag_sum), peak and parabola.
 // Every output is therefore summed in ONE order that depends on the event's own samples and frame range alone: not on the
 // other events, the slice, the clip's place in the buffer, the load path or the launch shape.
 //
@@ -60,29 +60,24 @@ __global__ __launch_bounds__(TD_THREADS) void tdoa_accum_k(const float* __restri
     const int fc0 = blockIdx.x * TD_CHUNK;                       // the chunk's first frame, counted from f0
     if (fc0 >= nf) return;                                       // (block-uniform: before any barrier)
     const int fc1 = fc0 + TD_CHUNK < nf ? fc0 + TD_CHUNK : nf;
-    {   // window + twiddles of the log-mel blob: global -> LDS
-        const f32x4* src = reinterpret_cast<const f32x4*>(tables);
-        f32x4* dst = reinterpret_cast<f32x4*>(lds);
-        for (int i = tid; i < TD_TAB_WORDS / 4; i += TD_THREADS) dst[i] = src[i];
-    }
+    fft_stage_tables(lds, tables, TD_TAB_WORDS, tid, TD_THREADS);
     const f2* s_win = reinterpret_cast<const f2*>(lds + LM_OFF_WIN);
     const f2* s_tw = reinterpret_cast<const f2*>(lds + LM_OFF_TW);
     const f2* s_pw = reinterpret_cast<const f2*>(lds + LM_OFF_PW);
     const int C = ta.C, P = ta.P;
     const int nfw = (C + 1) >> 1;                                // waves that transform
     const bool pipe = ta.pipelined != 0;
-    float2* s_spec = reinterpret_cast<float2*>(lds + TD_TAB_WORDS);                              // [1 or 2][C][TD_SPEC]
-    float* s_scr = lds + TD_TAB_WORDS + (pipe ? 2 : 1) * C * TD_SPEC * 2;                        // [nfw][TD_FFT_SCR]
-    float2* s_acc = reinterpret_cast<float2*>(s_scr + nfw * TD_FFT_SCR);                         // [batch][TD_SPEC]
+    float2* s_spec = reinterpret_cast<float2*>(lds + TD_TAB_WORDS);                              // [1 or 2][C][PHAT_SPEC]
+    float* s_scr = lds + TD_TAB_WORDS + (pipe ? 2 : 1) * C * PHAT_SPEC * 2;                      // [nfw][TD_FFT_SCR]
+    float2* s_acc = reinterpret_cast<float2*>(s_scr + nfw * TD_FFT_SCR);                         // [batch][PHAT_SPEC]
 
-    const int lane = tid & 63, wave = tid >> 6, half = lane >> 5, r = lane & 31;
+    const int wave = tid >> 6;
     float* wscr = s_scr + (wave < nfw ? wave : 0) * TD_FFT_SCR;  // (only used by waves < nfw)
+    const FftLane fl = fft_lane(tid & 63, wscr - lds);
+    const int half = fl.half(), r = fl.r();
     float* scr = wscr + half * LM_SCR;
-    const unsigned xbase = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(wscr - lds) * 4u +
-                                                          (unsigned)__builtin_amdgcn_groupstaticsize());
-    const int partner = (lane & 32) | ((32 - r) & 31);
     const long ns = ta.n_samples[rec];
-    float2* wrow = ws + ((long)blockIdx.y * ta.cpe + blockIdx.x) * P * TD_SPEC;
+    float2* wrow = ws + ((long)blockIdx.y * ta.cpe + blockIdx.x) * P * PHAT_SPEC;
     // Pipelined (the spectra fit twice, C <= 4): in step s the transforming waves fill buffer s & 1 with frame s while the other
     // waves whiten frame s - 1 from the other buffer; one barrier per step.  Otherwise every wave whitens, between two barriers.
     // Either way an accumulator entry belongs to one lane and receives the frames in ascending order: the same sums.
@@ -91,7 +86,7 @@ __global__ __launch_bounds__(TD_THREADS) void tdoa_accum_k(const float* __restri
 
     for (int p0 = 0; p0 < P; p0 += ta.pairs_per_batch) {
         const int nb = (P - p0 < ta.pairs_per_batch) ? P - p0 : ta.pairs_per_batch;
-        for (int idx = tid; idx < nb * TD_SPEC; idx += TD_THREADS) s_acc[idx] = make_float2(0.f, 0.f);
+        for (int idx = tid; idx < nb * PHAT_SPEC; idx += TD_THREADS) s_acc[idx] = make_float2(0.f, 0.f);
         __syncthreads();                                         // the tables are in LDS (first batch); the spectra are free
         for (int step = 0; step < n_fr + (pipe ? 1 : 0); ++step) {
             const long frame = f0 + fc0 + step;
@@ -116,94 +111,31 @@ __global__ __launch_bounds__(TD_THREADS) void tdoa_accum_k(const float* __restri
                     const f2* src = reinterpret_cast<const f2*>(cpcm + (RING ? pos : start)) + r;
 #pragma unroll
                     for (int n1 = 0; n1 < 32; ++n1) z[n1] = src[32 * n1];
-                } else {                                         // edge frames / odd hop / unaligned clips / a frame that wraps: guarded loads through LDS
-                    wave_lds_fence();
-#pragma unroll 1
-                    for (int n1 = 0; n1 < 32; ++n1) scr[n1 * 32 + r] = sample(64 * n1 + 2 * r);
-                    wave_lds_fence();
-#pragma unroll
-                    for (int n1 = 0; n1 < 32; ++n1) z[n1].x = scr[n1 * 32 + r];
-                    wave_lds_fence();
-#pragma unroll 1
-                    for (int n1 = 0; n1 < 32; ++n1) scr[n1 * 32 + r] = sample(64 * n1 + 2 * r + 1);
-                    wave_lds_fence();
-#pragma unroll
-                    for (int n1 = 0; n1 < 32; ++n1) z[n1].y = scr[n1 * 32 + r];
+                } else {                                         // edge frames / odd hop / unaligned clips / a frame that wraps
+                    fft_load_guarded(z, scr, fl, sample);
                 }
-#pragma unroll
-                for (int n1 = 0; n1 < 32; ++n1) z[n1] *= s_win[32 * n1 + r];
-                // ── pass 1 over n1, twiddle W_1024^{r k1}, exchange through the wave's 32 x 65 buffer, pass 2 over n2 (gcc.hip) ──
-                fft32(z);
-#pragma unroll
-                for (int k1 = 1; k1 < 32; ++k1) {
-                    const int b = brev5(k1);
-                    z[b] = cmul(z[b], s_tw[k1 * 32 + r]);
-                }
-                wave_lds_fence();
-                exchange_store<0>(xbase, z);
-                wave_lds_fence();
-                const unsigned xaddr = xbase + (unsigned)(r * LM_ROW_BYTES + 128 * half);
-#define TD_XREAD(H)                                                                                              \
-    _Pragma("unroll") for (int n2 = 0; n2 < 32; ++n2) {                                                           \
-        float t_;                                                                                                \
-        asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(t_) : "v"(xaddr), "i"(n2 * 4));                       \
-        z[n2].H = t_;                                                                                            \
-    }                                                                                                            \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                           \
-    _Pragma("unroll") for (int n2 = 0; n2 < 32; ++n2) asm volatile("" : "+v"(z[n2]));
-                TD_XREAD(x)
-                wave_lds_fence();
-                exchange_store<1>(xbase, z);
-                wave_lds_fence();
-                TD_XREAD(y)
-#undef TD_XREAD
-                wave_lds_fence();
-                fft32(z);                                        // Z[r + 32 k2] = z[brev5(k2)]
-                // ── pairing: 2 X[k] = (Z[k] + conj Z[N-k]) - i W_2048^k (Z[k] - conj Z[N-k]) = e + t, and 2 X[N-k] = conj(e - t) ──
-                float2* spec = s_spec + ((pipe ? (step & 1) : 0) * C + ch) * TD_SPEC;
-#pragma unroll
-                for (int k2 = 0; k2 < 16; ++k2) {
-                    const int bp = brev5(31 - k2), b0 = brev5((32 - k2) & 31);
-                    f2 pp = {__shfl(z[bp].x, partner, 64), __shfl(z[bp].y, partner, 64)};
-                    if (r == 0) pp = z[b0];
-                    const f2 zz = z[brev5(k2)];
-                    const int k = r + 32 * k2;
-                    const f2 ee = add_conj(zz, pp);
-                    const f2 q = rot_sub_conj(zz, pp);
-                    const f2 t = cmul(q, s_pw[k]);
-                    const f2 a = ee + t, bb = ee - t;
-                    spec[k] = make_float2(0.5f * a.x, 0.5f * a.y);
-                    spec[LM_N - k] = make_float2(0.5f * bb.x, -0.5f * bb.y);
-                }
-                if (r == 0) { const f2 zz = z[brev5(16)]; spec[512] = make_float2(zz.x, -zz.y); }      // X[512] = conj Z[512]
+                fft2048_passes(z, fl, s_win, s_tw);
+                fft2048_spectrum(z, fl, s_pw, s_spec + ((pipe ? (step & 1) : 0) * C + ch) * PHAT_SPEC);
             }
             if (!pipe) __syncthreads();
-            // ── Pk of the batch's pairs, added to the accumulators; Pk[0] is halved (the synthesis counts every bin twice) and the
-            //    DC and Nyquist bins are real.  Entry idx is read and written by this lane alone, frame after frame. ──
+            // ── Pk of the batch's pairs, added to the accumulators.  Entry idx is read and written by this lane alone, frame
+            //    after frame. ──
             const int wf = pipe ? step - 1 : step;               // the frame of the chunk whose spectra are whitened now
-            const float2* wspec = s_spec + (pipe ? (wf & 1) : 0) * C * TD_SPEC;
+            const float2* wspec = s_spec + (pipe ? (wf & 1) : 0) * C * PHAT_SPEC;
             for (int idx = wf >= 0 && tid >= wt0 ? tid - wt0 : nb * 1025; idx < nb * 1025; idx += wstride) {
                 const int pb = idx / 1025, k = idx - pb * 1025;
-                int i = 0, rem = p0 + pb;                        // pair p -> (i, j), lexicographic
-                while (rem >= C - 1 - i) { rem -= C - 1 - i; ++i; }
-                const int j = i + 1 + rem;
-                const float2 a = wspec[i * TD_SPEC + k], b = wspec[j * TD_SPEC + k];
-                const float gr = a.x * b.x + a.y * b.y, gi = a.y * b.x - a.x * b.y;
-                const float m2 = gr * gr + gi * gi;
-                // (m2 beyond the float range is inf: those bins are 0 by the definition, never inf * 0 = NaN — gcc.hip)
-                const float inv = (m2 >= 1e-30f && m2 <= 3.0e38f) ? rsqrtf(m2) : 0.f;
-                float pr = gr * inv, pi = gi * inv;
-                if (k == 0) { pr *= 0.5f; pi = 0.f; }
-                if (k == LM_N) pi = 0.f;
-                float2 s = s_acc[pb * TD_SPEC + k];
-                s.x += pr; s.y += pi;
-                s_acc[pb * TD_SPEC + k] = s;
+                int i, j;
+                phat_pair(p0 + pb, C, i, j);
+                const float2 pk = phat_bin(wspec[i * PHAT_SPEC + k], wspec[j * PHAT_SPEC + k], k);
+                float2 s = s_acc[pb * PHAT_SPEC + k];
+                s.x += pk.x; s.y += pk.y;
+                s_acc[pb * PHAT_SPEC + k] = s;
             }
             __syncthreads();                                     // the spectra (of this buffer) may be overwritten
         }
         for (int idx = tid; idx < nb * 1025; idx += TD_THREADS) {
             const int pb = idx / 1025, k = idx - pb * 1025;
-            wrow[(long)(p0 + pb) * TD_SPEC + k] = s_acc[pb * TD_SPEC + k];
+            wrow[(long)(p0 + pb) * PHAT_SPEC + k] = s_acc[pb * PHAT_SPEC + k];
         }
         __syncthreads();                                         // the accumulators are zeroed for the next batch
     }
@@ -214,19 +146,10 @@ __global__ __launch_bounds__(TD_FIN_THREADS) void tdoa_finish_k(const uint32_t* 
                                                                 float* __restrict__ lag_out, float* __restrict__ strength_out,
                                                                 int* __restrict__ frames_out, float* __restrict__ acc_out, TdArgs ta) {
     __shared__ __attribute__((aligned(16))) float2 s_lag[LM_NFFT];
-    __shared__ __attribute__((aligned(16))) float2 s_S[TD_SPEC];
+    __shared__ __attribute__((aligned(16))) float2 s_S[PHAT_SPEC];
     __shared__ float s_cc[2 * TD_MAX_LAG + 3];
     const int tid = threadIdx.x;
-    {   // the lag table (cos, sin)(2 pi m / 2048), m = 0..2047, unfolded from the blob's pairing twiddles pw[k] = (cos, -sin)
-        // (2 pi k / 2048), k = 0..512 (float64 values rounded once), as gcc_phat_k does it
-        const float2* pw = reinterpret_cast<const float2*>(tables + LM_OFF_PW);
-        for (int m = tid; m < LM_NFFT; m += TD_FIN_THREADS) {
-            const int mm = m <= LM_N ? m : LM_NFFT - m;
-            const int k = mm <= LM_N / 2 ? mm : LM_N - mm;
-            const float2 w = pw[k];
-            s_lag[m] = make_float2(mm <= LM_N / 2 ? w.x : -w.x, m <= LM_N ? -w.y : w.y);
-        }
-    }
+    phat_lag_table(s_lag, reinterpret_cast<const float2*>(tables + LM_OFF_PW), tid, TD_FIN_THREADS);
     __syncthreads();
     const int P = ta.P, ML = ta.max_lag, T = ML + 2, W = 2 * ML + 3;
     for (int el = blockIdx.x; el < ta.n_ev; el += gridDim.x) {
@@ -242,36 +165,17 @@ __global__ __launch_bounds__(TD_FIN_THREADS) void tdoa_finish_k(const uint32_t* 
             continue;
         }
         const int nch = (nf + TD_CHUNK - 1) / TD_CHUNK;
-        const float2* wev = ws + (long)el * ta.cpe * P * TD_SPEC;
+        const float2* wev = ws + (long)el * ta.cpe * P * PHAT_SPEC;
         for (int p = 0; p < P; ++p) {
-            // ── S = the chunk partials in ascending chunk order ──
-            for (int k = tid; k < 1025; k += TD_FIN_THREADS) {
-                float2 s = wev[(long)p * TD_SPEC + k];
-                for (int c = 1; c < nch; ++c) {
-                    const float2 v = wev[((long)c * P + p) * TD_SPEC + k];
-                    s.x += v.x; s.y += v.y;
-                }
-                s_S[k] = s;
-            }
+            phat_sum_chunks(s_S, wev, p, P, nch, tid, TD_FIN_THREADS);
             __syncthreads();
             // ── lag synthesis: item = tau = 0..max_lag+1, 8 lanes per item; cc[+tau] = A - B, cc[-tau] = A + B ──
             const int grp = tid >> 3, j8 = tid & 7;
             for (int it0 = 0; it0 < T; it0 += TD_FIN_THREADS / 8) {
                 const bool valid = it0 + grp < T;
                 const int tau = valid ? it0 + grp : 0;
-                float A = 0.f, B = 0.f;
-                int m = (j8 * tau) & (LM_NFFT - 1);
-                const int step = (8 * tau) & (LM_NFFT - 1);
-#pragma unroll 8
-                for (int i = 0; i < LM_N / 8; ++i) {             // bins k = j8 + 8 i, ascending
-                    const float2 q = s_S[j8 + 8 * i], t = s_lag[m];
-                    A = fmaf(q.x, t.x, A);
-                    B = fmaf(q.y, t.y, B);
-                    m = (m + step) & (LM_NFFT - 1);
-                }
-                A += __shfl_xor(A, 1, 64); B += __shfl_xor(B, 1, 64);
-                A += __shfl_xor(A, 2, 64); B += __shfl_xor(B, 2, 64);
-                A += __shfl_xor(A, 4, 64); B += __shfl_xor(B, 4, 64);
+                const float2 ab = phat_lag_sum(s_S, j8, tau, LM_NFFT, [&](int m) { return s_lag[m]; });
+                const float A = ab.x, B = ab.y;
                 if (valid && j8 < 2) {
                     const float ny = s_S[LM_N].x, sgn = (tau & 1) ? -ny : ny;
                     const bool plus = j8 == 0;
@@ -283,23 +187,16 @@ __global__ __launch_bounds__(TD_FIN_THREADS) void tdoa_finish_k(const uint32_t* 
                 for (int i = tid; i < W; i += TD_FIN_THREADS) acc_out[(e * P + p) * W + i] = s_cc[i];
             if (tid < 64) {
                 // ── the first maximum over |tau| <= max_lag (entries 1 .. 2 max_lag + 1 of s_cc), ascending ──
-                float best = -INFINITY, low = INFINITY;
-                int at = 0x7fffffff;
+                FirstMax fm{-INFINITY, INFINITY, 0x7fffffff};
                 for (int i = 1 + tid; i <= 2 * ML + 1; i += 64) {
                     const float v = s_cc[i];
-                    if (v > best) { best = v; at = i; }
-                    low = fminf(low, v);
+                    if (v > fm.best) { fm.best = v; fm.at = i; }
+                    fm.low = fminf(fm.low, v);
                 }
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const float ob = __shfl_xor(best, o, 64), ol = __shfl_xor(low, o, 64);
-                    const int oa = __shfl_xor(at, o, 64);
-                    if (ob > best || (ob == best && oa < at)) { best = ob; at = oa; }
-                    low = fminf(low, ol);
-                }
+                fm = first_max_wave(fm);
                 if (tid == 0) {
                     // digital silence: every lag is 0, the answer is lag 0 (and NaN samples, which compare with nothing, stay in range)
-                    if ((best == 0.f && low == 0.f) || at > 2 * ML + 1) at = ML + 1;
+                    const int at = (fm.best == 0.f && fm.low == 0.f) || fm.at > 2 * ML + 1 ? ML + 1 : fm.at;
                     const double l = s_cc[at - 1], m = s_cc[at], rr = s_cc[at + 1];
                     const double den = l - 2.0 * m + rr;
                     double lag = (double)(at - ML - 1);
@@ -315,7 +212,7 @@ __global__ __launch_bounds__(TD_FIN_THREADS) void tdoa_finish_k(const uint32_t* 
 
 // LDS of the accumulate kernel for C channels with `batch` pairs of accumulators resident and 1 or 2 spectra buffers
 size_t tdoa_lds_bytes(int C, int batch, int buffers) {
-    return ((size_t)TD_TAB_WORDS + (size_t)buffers * C * TD_SPEC * 2 + (size_t)((C + 1) / 2) * TD_FFT_SCR + (size_t)batch * TD_SPEC * 2) * sizeof(float);
+    return ((size_t)TD_TAB_WORDS + (size_t)buffers * C * PHAT_SPEC * 2 + (size_t)((C + 1) / 2) * TD_FFT_SCR + (size_t)batch * PHAT_SPEC * 2) * sizeof(float);
 }
 
 // bytes of sample_off [R*C] and n_samples [R] (64-bit), rounded to 16

@@ -8,12 +8,12 @@
 #pragma once
 #include "common.h"
 #include "fft2048.h"
+#include "phat_shared.h"
 
 #define TD_CHUNK 32                               // frames per workgroup of the accumulate launch
 #define TD_MAX_CH 8
 #define TD_MAX_LAG 127
-#define TD_SPEC 1026                              // float2 per spectrum / accumulator row (1025 bins + 1 pad)
-#define TD_ROW_BYTES ((size_t)TD_SPEC * sizeof(float2))
+#define TD_ROW_BYTES ((size_t)PHAT_SPEC * sizeof(float2))
 
 struct TdArgs {
     const long* sample_off;     // [R*C] first sample of every planar channel
@@ -58,7 +58,7 @@ __device__ __forceinline__ void td_event_range(const TdArgs& a, long e, int& rec
 }
 
 // Given every slice of the event table after its two launches, on the same stream: `part` holds the slice's chunk partials,
-// event el of the slice (ta.e0 + el of the table) at part + el * ta.cpe * ta.P * TD_SPEC, chunk c / pair p at row c * P + p.
+// event el of the slice (ta.e0 + el of the table) at part + el * ta.cpe * ta.P * PHAT_SPEC, chunk c / pair p at row c * P + p.
 // A non-zero return ends the call with that code.
 typedef int (*TdSliceHook)(void* ctx, const TdArgs& ta, const float2* part, hipStream_t stream);
 
