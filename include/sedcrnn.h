@@ -616,6 +616,29 @@ int sed_event_beamform_ring(const float* ring, long ring_len, long cap, const lo
                             const int* ev_loc_frames, long E, int time_factor, int hop, int max_frames, const int* delays, int D,
                             int Q, int H, const float* taps, const int* audio_len, const long* audio_start, float* audio,
                             long audio_total, void* workspace, size_t workspace_bytes, void* stream);
+/* sed_event_mvdr: the audio of every located event through an adaptive (MVDR) beam.  The arguments are
+ * sed_event_beamform's with, in place of the delays and the filter, tau: DEVICE float64 [D][C], the delay of channel c for
+ * direction d in samples (sr (r_c - rbar) . u_d / c, not rounded); loading in [1e-6, 1e6]; tables: a blob of
+ * sed_logmel_build_tables made with the window w[m] = sqrt(0.5 - 0.5 cos(2 pi m / 2048)), of which the header, the window and the
+ * twiddles are read.  The events, their samples [s0, s1) and audio_len / audio_start are sed_event_beam_spans'.  The transform grid
+ * is the event's own: N = 2048, B = 1024, len = s1 - s0, J = ceil(len / B); frame j = 0..J holds x_c[s0 + (j - 1) B + m] with every
+ * sample outside [s0, s1) read as 0.  Per bin k = 0..1024, with X_j the C spectra of frame j:
+ *   R = sum_j X_j X_j^H                                   (fp32, ascending j)
+ *   d_c = exp(+2 pi i k tau[dir][c] / 2048),  v = (R + loading trace(R) / C I)^-1 d,  w = v / (d^H v)   (float64; stored as fp32)
+ *   trace(R) not > 0: w = d / C
+ *   Y_j = sum_c conj(w_c) X_{c,j}                         (ascending c; the imaginary parts of Y[0] and Y[1024] are dropped)
+ * and with v_j the inverse real FFT of Y_j, output sample i = j B + m < len is w[m + B] v_j[m + B] + w[m] v_{j+1}[m].  An event's
+ * audio depends on its own samples, tau[dir] and loading alone.  workspace: 16-byte aligned, at least
+ * sed_event_mvdr_workspace_bytes(R, channels, max_frames, hop) — the recording table and ONE event's covariance partials and
+ * weights; with more, as many events as fit (at most 65535) go through the three launches at a time, which changes no bit.
+ * Every argument is checked before anything is enqueued; E = 0 or audio_total = 0 launches nothing; an event whose audio_len /
+ * audio_start disagree with its own span, or leave [0, audio_total), is skipped. */
+size_t sed_event_mvdr_workspace_bytes(int R, int channels, int max_frames, int hop);
+int sed_event_mvdr(const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const int* ev_rec, const int* ev_onset,
+                   const int* ev_offset, const int* ev_peak_frame, const int* ev_dir, const int* ev_loc_frames, long E,
+                   int time_factor, int hop, int max_frames, const double* tau, int D, double loading, const void* tables,
+                   size_t tables_bytes, const int* audio_len, const long* audio_start, float* audio, long audio_total,
+                   void* workspace, size_t workspace_bytes, void* stream);
 
 /* sed_pcen: per-channel energy normalisation, IN PLACE, of the columns [col0, col0 + W) of x [rows][stride], which
  * hold log-mel values (natural log, as sed_logmel* write them without a scaler); the other columns are not touched.  Every column

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libsedcrnn.so")
-SOURCES = ["api.cpp", "conv.hip", "conv_bf16.hip", "wino.hip", "conv1.hip", "bnpool.hip", "gemm.hip", "gru.hip", "misc.hip", "logmel.hip", "gcc.hip", "tdoa.hip", "doa.hip", "beam.hip", "pcen.hip", "resample.hip", "data.hip", "detect.hip", "tune.hip", "stream.hip", "net.hip"]
+SOURCES = ["api.cpp", "conv.hip", "conv_bf16.hip", "wino.hip", "conv1.hip", "bnpool.hip", "gemm.hip", "gru.hip", "misc.hip", "logmel.hip", "gcc.hip", "tdoa.hip", "doa.hip", "beam.hip", "mvdr.hip", "pcen.hip", "resample.hip", "data.hip", "detect.hip", "tune.hip", "stream.hip", "net.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # per-file extras.  logmel: the SLP vectoriser packs the FFT's scalar adds into v_pk_add_f32 and pays for it with ~600
 # v_mov per frame pair to build the register pairs (packed f32 is no faster than scalar on gfx950)
@@ -21,6 +21,7 @@ EXTRA_FLAGS = {"logmel.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-reso
                "tdoa.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"],
                "doa.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"],
                "beam.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"],
+               "mvdr.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"],
                "pcen.hip": ["-Rpass-analysis=kernel-resource-usage"],
                "conv.hip": ["-Rpass-analysis=kernel-resource-usage"],
                "wino.hip": ["-Rpass-analysis=kernel-resource-usage"],
@@ -53,6 +54,10 @@ NO_SCRATCH_KERNELS = {"wino.hip": ("conv3x3_wino_k",),
                       # delay-and-sum beam: 8 outputs, 8 channel sums and a 16-sample window live per thread, indexed by unrolled
                       # loops; one of them in scratch would put a memory round trip on every fma of the launch's one loop
                       "beam.hip": ("beam_sum_k", "beam_spans_k"),
+                      # MVDR beam: the covariance and the apply kernel run the FFT (and its inverse) with exchange_load's hand-placed
+                      # wait, which is only right while the read-back's destinations stay in registers (fft2048.h, THE HAZARD); the
+                      # weight kernel keeps its matrices in LDS so that its float64 solve needs no scratch either
+                      "mvdr.hip": ("mvdr_cov_k", "mvdr_weights_k", "mvdr_apply_k"),
                       # PCEN: the powers of (1-b) travel by value and are indexed in a loop; a copy of them in scratch, or a spilled
                       # powf, would turn a bandwidth-bound pass into a latency-bound one without failing any test
                       "pcen.hip": ("pcen_pass_k", "pcen_carry_k"),
@@ -99,7 +104,7 @@ def check_no_spill(remarks, kernels, allow_agprs=False):
 def build(force=False, verbose=False):
     os.makedirs(OBJ, exist_ok=True)
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_shared.h"), os.path.join(CSRC, "detect_shared.h"), os.path.join(CSRC, "fft2048.h"), os.path.join(CSRC, "tdoa_shared.h"), os.path.join(CSRC, "phat_shared.h"), os.path.join(HERE, "..", "include", "sedcrnn.h")]
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_shared.h"), os.path.join(CSRC, "detect_shared.h"), os.path.join(CSRC, "fft2048.h"), os.path.join(CSRC, "tdoa_shared.h"), os.path.join(CSRC, "phat_shared.h"), os.path.join(CSRC, "beam_shared.h"), os.path.join(HERE, "..", "include", "sedcrnn.h")]
     jobs = []
     objs = []
     for src in SOURCES:

@@ -1,7 +1,8 @@
 // fft2048.h — the register-resident 2048-point real FFT of logmel.hip, gcc.hip and tdoa.hip: the layout of the constant blob
 // (window, inter-pass and pairing twiddles) and its staging into LDS, the lane geometry, complex points in VGPR pairs, the
 // 32-point transform, the half-wave exchange through LDS (store and read-back), the guarded frame load, the two passes from
-// samples to Z (fft2048_passes) and the pairing pass from Z to the complex half spectrum (fft2048_spectrum).  Everything is
+// samples to Z (fft2048_passes) and the pairing pass from Z to the complex half spectrum (fft2048_spectrum) — and, for mvdr.hip,
+// the way back from a half spectrum to the windowed frame (ifft2048_unpair, ifft2048_passes).  Everything is
 // force-inlined into the kernels that use it; what a kernel keeps for itself is its fast (unguarded) load path and, in
 // logmel.hip, a pairing pass of its own that produces power bins.
 #pragma once
@@ -278,6 +279,56 @@ __device__ __forceinline__ void fft2048_spectrum(const f2 (&z)[32], const FftLan
         spec[LM_N - k] = make_float2(0.5f * bb.x, -0.5f * bb.y);
     }
     if (r == 0) { const f2 zz = z[brev5(16)]; spec[512] = make_float2(zz.x, -zz.y); }      // X[512] = conj Z[512]
+}
+
+// ── the inverse: a half spectrum back to its real frame (mvdr.hip), from the pieces above ──
+// The forward pairing read backwards.  With z[n] = x[2n] + i x[2n+1] and Z = FFT_1024(z), the half spectrum Y[0..1024] of the real
+// frame x gives 2 conj Z[k] = (a + b) - i W_2048^k (a - b) with a = conj Y[k], b = Y[N-k]; x is then conj(FFT_1024(2 conj Z)) / 2048:
+// the SAME two forward 32-point passes.  Lane r takes k = r + 32 n1 into register n1 — the order the passes read — and reads its own
+// 2 x 32 bins of `spec` (LDS): no shuffles.  W^k for k > 512 is -conj W^(1024-k), from the 513 pairing twiddles.  The imaginary
+// parts of Y[0] and Y[1024] must be 0 in `spec` (a real frame has none; the caller drops them).
+__device__ __forceinline__ void ifft2048_unpair(f2 (&z)[32], const FftLane& fl, const f2* s_pw, const float2* spec) {
+    const int r = fl.r();
+#pragma unroll
+    for (int n1 = 0; n1 < 32; ++n1) {
+        const int k = r + 32 * n1;
+        const float2 ya = spec[k], yb = spec[LM_N - k];
+        const f2 a = {ya.x, -ya.y}, b = {yb.x, yb.y};
+        f2 w;
+        if (n1 < 16) w = s_pw[k];                                // (k <= 511)
+        else { const f2 t = s_pw[LM_N - k]; w = (f2){-t.x, t.y}; }   // (k = 512: -conj W^512 = W^512)
+        const f2 e = a + b, u = cmul(a - b, w);
+        z[n1] = e + (f2){u.y, -u.x};                             // e - i u
+    }
+}
+
+// 2 conj Z (register n1 of lane r = point r + 32 n1) to the frame, windowed for the overlap-add: on return
+// z[brev5(k2)] = (win[2m] x[2m], win[2m+1] x[2m+1]), m = r + 32 k2.  fft2048_passes without its window on the way in; the scale
+// 1/2048 is a power of two, so every output is the transform's value times the window's, rounded once.
+__device__ __forceinline__ void ifft2048_passes(f2 (&z)[32], const FftLane& fl, const f2* s_win, const f2* s_tw) {
+    const int r = fl.r(), half = fl.half();
+    fft32(z);
+#pragma unroll
+    for (int k1 = 1; k1 < 32; ++k1) {
+        const int b = brev5(k1);
+        z[b] = cmul(z[b], s_tw[k1 * 32 + r]);
+    }
+    wave_lds_fence();                                        // whatever read the buffer before (the forward transform) is done
+    exchange_store<0>(fl.xbase, z);
+    wave_lds_fence();
+    const unsigned xaddr = fl.xbase + (unsigned)(r * LM_ROW_BYTES + 128 * half);
+    exchange_load<0>(xaddr, z);
+    wave_lds_fence();
+    exchange_store<1>(fl.xbase, z);
+    wave_lds_fence();
+    exchange_load<1>(xaddr, z);
+    wave_lds_fence();
+    fft32(z);
+#pragma unroll
+    for (int k2 = 0; k2 < 32; ++k2) {
+        const int b = brev5(k2);
+        z[b] = (z[b] * (f2){1.0f / LM_NFFT, -1.0f / LM_NFFT}) * s_win[r + 32 * k2];
+    }
 }
 
 }  // namespace

@@ -351,7 +351,8 @@ class EventDetector:
     also comes with its audio, the array pointed at ``dir`` by a delay-and-sum beam (``feature.event_beamform`` on the PCM that
     is kept anyway): ``audio_start`` / ``audio_len`` [E] in the events, the packed float32 buffer ``result.audio`` and
     ``result.event_audio(e)``; ``from_features*`` returns events without audio, ``det.localize`` adds it, ``det.stream`` of such a
-    detector is not implemented."""
+    detector is not implemented.  ``extract=sed.MVDR(loading)`` instead: the same events, samples and results through
+    an adaptive beam that suppresses what else the event's frames contain (``feature.event_mvdr``)."""
 
     def __init__(self, model, seq_len=SEQ_LEN_IN, hop=None, combine="mean", trim=0, threshold=0.5, low=None, median=1,
                  min_gap=0, min_len=1, mean=None, std=None, sr=feature.SR, hop_length=feature.HOP, max_batch=1024, spatial=None,
@@ -372,13 +373,13 @@ class EventDetector:
                                  f"the net has in_channels={model.in_channels}")
             if model.n_mels % 2:
                 raise ValueError(f"spatial={spatial!r} writes n_mels lags per pair and needs an even count, the net has n_mels={model.n_mels}")
-        from .localize import DOA, TDOA, DelaySum
-        if extract is not None and not isinstance(extract, DelaySum):
-            raise TypeError(f"extract must be None or a DelaySum(...) settings object, got {type(extract).__name__}")
+        from .localize import DOA, MVDR, TDOA, DelaySum
+        if extract is not None and not isinstance(extract, (DelaySum, MVDR)):
+            raise TypeError(f"extract must be None, a DelaySum(...) or an MVDR(...) settings object, got {type(extract).__name__}")
         if extract is not None and not isinstance(localize, DOA):
-            raise ValueError("extract=DelaySum(...) points the array at every event's direction and needs localize=sed.DOA(positions, grid), "
-                             f"got localize={localize!r}")
-        self.extract_settings = extract         # per-event delay-and-sum audio, or None
+            raise ValueError(f"extract={type(extract).__name__}(...) points the array at every event's direction and needs "
+                             f"localize=sed.DOA(positions, grid), got localize={localize!r}")
+        self.extract_settings = extract         # per-event audio: a delay-and-sum or an MVDR beam (5s), or None
         if localize is not None and not isinstance(localize, (TDOA, DOA)):
             raise TypeError(f"localize must be None, a TDOA(...) or a DOA(...) settings object, got {type(localize).__name__}")
         if localize is not None and not 2 <= self.audio_channels <= feature.GCC_MAX_CHANNELS:
@@ -576,9 +577,11 @@ class EventDetector:
             else:
                 loc = feature.event_tdoa(pcm, clips, self.audio_channels, result.events, self.model.time_factor, max_lag=t.max_lag,
                                          max_frames=t.max_frames, hop=self.hop_length)
-            if self.extract_settings is not None:            # the audio of the located events, from the same PCM (DESIGN 5r)
-                beam = feature.event_beamform(pcm, clips, self.audio_channels, {**result.events, **loc}, self.model.time_factor, t,
-                                              self.extract_settings, sr=self.sr, hop=self.hop_length)
+            if self.extract_settings is not None:            # the audio of the located events, from the same PCM (DESIGN 5r, 5s)
+                from .localize import MVDR
+                entry = feature.event_mvdr if isinstance(self.extract_settings, MVDR) else feature.event_beamform
+                beam = entry(pcm, clips, self.audio_channels, {**result.events, **loc}, self.model.time_factor, t,
+                             self.extract_settings, sr=self.sr, hop=self.hop_length)
                 result.audio = beam.pop("audio")
                 loc.update(beam)
         result.events = {**{k: v for k, v in result.events.items() if k not in _TDOA_KEYS + _DOA_KEYS + _BEAM_KEYS}, **loc}

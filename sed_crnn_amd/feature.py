@@ -640,13 +640,9 @@ def event_tdoa_ring(ring, cap, n, channels, events, time_factor, max_lag=24, max
     return out
 
 
-def _beam_io(who, events, R, rec_key, nc, doa, beam, sr, dev):
-    """checks the settings of a beam call and gathers what both entries pass on -> (event columns as the C entries take them, E,
-    [max_frames, M, D, Q, H, taps] with M and the taps on ``dev``: uploaded once per device, rate and filter)"""
-    from .localize import DelaySum
-    _doa_plan(doa, nc, sr)
-    if not isinstance(beam, DelaySum):
-        raise TypeError(f"{who} takes the beam settings as a sed.DelaySum(...) object, got {type(beam).__name__}")
+def _located_cols(events, R, rec_key, dev):
+    """the columns of located events as the C entries of both beams take them (``rec_key`` names the recording column, needed
+    when R > 1) -> ([rec, onset, offset, peak_frame, dir, loc_frames] as pointers to contiguous int32 device tensors, E)"""
     col = {}
     for k in ("onset", "offset", "peak_frame", "dir", "loc_frames") + ((rec_key,) if R > 1 else ()):
         if k not in events:
@@ -656,6 +652,26 @@ def _beam_io(who, events, R, rec_key, nc, doa, beam, sr, dev):
     E = col["onset"].numel()
     if any(v.dim() != 1 or v.numel() != E for v in col.values()):
         raise ValueError("the event columns must be 1-D and equally long")
+    cols = [ptr(col.get("rec")), ptr(col["onset"]), ptr(col["offset"]), ptr(col["peak_frame"]), ptr(col["dir"]), ptr(col["loc_frames"])]
+    return _Kept(cols, col), E
+
+
+class _Kept(list):
+    """a list of pointers that keeps the tensors they point into alive"""
+
+    def __init__(self, items, owner):
+        super().__init__(items)
+        self.owner = owner
+
+
+def _beam_io(who, events, R, rec_key, nc, doa, beam, sr, dev):
+    """checks the settings of a beam call and gathers what both entries pass on -> (event columns as the C entries take them, E,
+    [max_frames, M, D, Q, H, taps] with M and the taps on ``dev``: uploaded once per device, rate and filter)"""
+    from .localize import DelaySum
+    _doa_plan(doa, nc, sr)
+    if not isinstance(beam, DelaySum):
+        raise TypeError(f"{who} takes the beam settings as a sed.DelaySum(...) object, got {type(beam).__name__}")
+    cols, E = _located_cols(events, R, rec_key, dev)
     key = (dev.index or 0, float(sr), beam.oversample)
     if key not in doa._beam_device:
         doa._beam_device[key] = torch.from_numpy(doa.delays(sr, beam.oversample)).to(dev)
@@ -663,7 +679,6 @@ def _beam_io(who, events, R, rec_key, nc, doa, beam, sr, dev):
     if tkey not in _BEAM_TAPS:
         _BEAM_TAPS[tkey] = torch.from_numpy(beam.taps.copy()).to(dev)                # (the cached table is read-only)
     M = doa._beam_device[key]
-    cols = [ptr(col.get("rec")), ptr(col["onset"]), ptr(col["offset"]), ptr(col["peak_frame"]), ptr(col["dir"]), ptr(col["loc_frames"])]
     return cols, E, [doa.max_frames, ptr(M), M.shape[0], beam.oversample, beam.half_width, ptr(_BEAM_TAPS[tkey])]
 
 
@@ -690,6 +705,84 @@ def _beam_run(names, head, cols, E, tf, hop, plan, need, dev):
     return out
 
 
+def _planar_recordings(who, pcm, clips, channels, time_factor, hop):
+    """checks the PCM buffer and the clip table of ``event_beamform`` / ``event_mvdr`` -> (channels, time_factor, hop, the table as
+    int64 [R * channels, 2], R)"""
+    if not (isinstance(pcm, torch.Tensor) and pcm.is_cuda and pcm.dim() == 1):
+        raise RuntimeError(f"sed_crnn_amd.feature.{who} needs a 1-D CUDA(HIP) PCM buffer; there is no CPU fallback")
+    nc, tf, hop = int(channels), int(time_factor), int(hop)
+    if not 2 <= nc <= GCC_MAX_CHANNELS or tf < 1 or hop < 1:
+        raise ValueError(f"{who} needs 2 to {GCC_MAX_CHANNELS} audio channels, time_factor >= 1 and hop >= 1, got channels={nc}, "
+                         f"time_factor={tf}, hop={hop}")
+    table = np.ascontiguousarray(np.asarray(clips, dtype=np.int64).reshape(-1, 2))
+    if table.shape[0] == 0 or table.shape[0] % nc:
+        raise ValueError(f"{table.shape[0]} clips are not a whole number (>= 1) of recordings of {nc} channels")
+    for i, (o, n) in enumerate(table.tolist()):
+        if n < 1 or o < 0 or o + n > pcm.numel():
+            raise ValueError(f"recording {i // nc}, channel {i % nc} (first sample {o}, {n} samples) is empty or not inside the "
+                             f"buffer of {pcm.numel()} samples")
+        if n != table[i - i % nc, 1]:
+            raise ValueError(f"recording {i // nc}: channel {i % nc} has {n} samples, channel 0 has {int(table[i - i % nc, 1])}")
+    return nc, tf, hop, table, table.shape[0] // nc
+
+
+@functools.lru_cache(maxsize=8)
+def _mvdr_tables(device_index):
+    """the 2048-point tables with the MVDR beam's window (``localize.mvdr_window``): the header, window and twiddle sections of a
+    ``build_tables`` blob — the mel plan behind them is not read and not kept — cached per device"""
+    from .localize import mvdr_window
+    blob = build_tables(mvdr_window(), slaney_mel_basis(SR, NFFT, NB_MEL), torch.device("cuda", device_index))
+    return blob[:_LM_OFF_ENT].clone()
+
+
+def event_mvdr(pcm, clips, channels, events, time_factor, doa, mvdr, sr=SR, hop=HOP, max_workspace_bytes=128 << 20):
+    """The audio of every located event through an adaptive beam (``sed_event_beam_spans`` + ``sed_event_mvdr``):
+    the arguments, the events that are extracted, their samples and the returned dict — ``audio`` float32 [total],
+    ``audio_start`` int64 [E], ``audio_len`` int32 [E] — are ``event_beamform``'s; ``mvdr``: a ``sed.MVDR(loading)``.  On the
+    event's own grid of 2048-sample frames every 1024 samples (sqrt-Hann window; every sample outside the event read as 0) the
+    spatial covariance of every frequency bin is summed over the event's frames, the weights
+    ``w = (R + loading trace(R)/C I)^-1 d / (d^H (R + ...)^-1 d)`` for the steering vector ``d`` of ``doa.steering(sr)[dir]`` are
+    solved in float64 on the device, and the frames are combined, transformed back and overlap-added.  A source in the
+    event's direction passes unchanged; whatever else the event's frames contain — a second source, above all — is suppressed
+    as far as ``loading`` and the number of frames allow (DESIGN 5s has figures).  The covariance partials of at most
+    ``max_workspace_bytes`` worth of events are held at a time; the slicing changes no bit, and neither do the other events,
+    the batch, the clip's place in the buffer or the samples outside the event.  The host does ONE blocking read, the 8 bytes
+    of the total; ``E == 0`` returns empty tensors without a launch."""
+    import ctypes as C
+    from .localize import MVDR
+    nc, tf, hop, table, R = _planar_recordings("event_mvdr", pcm, clips, channels, time_factor, hop)
+    _doa_plan(doa, nc, sr)
+    if not isinstance(mvdr, MVDR):
+        raise TypeError(f"event_mvdr takes the beam settings as a sed.MVDR(...) object, got {type(mvdr).__name__}")
+    dev = pcm.device
+    cols, E = _located_cols(events, R, "rec", dev)
+    if E == 0:
+        return _beam_empty(dev)
+    key = (dev.index or 0, float(sr))
+    if key not in doa._steering_device:
+        doa._steering_device[key] = torch.from_numpy(doa.steering(sr)).to(dev)
+    tau = doa._steering_device[key]
+    tables = _mvdr_tables(dev.index or 0)
+    pcm = pcm.contiguous().float()
+    head = [pcm.numel(), C.c_void_p(table.ctypes.data), R, nc]
+    out = {"audio_start": torch.empty(E, dtype=torch.int64, device=dev), "audio_len": torch.empty(E, dtype=torch.int32, device=dev)}
+    total = torch.empty(1, dtype=torch.int64, device=dev)
+    need_tab = lib().sed_event_beam_workspace_bytes(R, nc)
+    need_one = lib().sed_event_mvdr_workspace_bytes(R, nc, doa.max_frames, hop)
+    if need_one == 0:
+        raise ValueError(f"sed_event_mvdr_workspace_bytes refuses R={R}, channels={nc}, max_frames={doa.max_frames}, hop={hop}")
+    per_event = need_one - need_tab
+    ws = torch.empty(min(need_tab + E * per_event, max(need_one, int(max_workspace_bytes))), dtype=torch.uint8, device=dev)
+    check(lib().sed_event_beam_spans(*head, *cols, E, tf, hop, doa.max_frames, tau.shape[0], ptr(out["audio_len"]),
+                                     ptr(out["audio_start"]), ptr(total), ptr(ws), ws.numel(), stream_ptr()), "sed_event_beam_spans")
+    n_total = int(total.item())                                       # the one blocking read
+    out["audio"] = torch.empty(n_total, device=dev)
+    check(lib().sed_event_mvdr(ptr(pcm), *head, *cols, E, tf, hop, doa.max_frames, ptr(tau), tau.shape[0], mvdr.loading, ptr(tables),
+                               tables.numel() * 4, ptr(out["audio_len"]), ptr(out["audio_start"]), ptr(out["audio"]), n_total, ptr(ws),
+                               ws.numel(), stream_ptr()), "sed_event_mvdr")
+    return out
+
+
 def event_beamform(pcm, clips, channels, events, time_factor, doa, beam, sr=SR, hop=HOP):
     """The audio of every located event with the array pointed at it (``sed_event_beam_spans`` + ``sed_event_beamform``, DESIGN
     5r): a steered delay-and-sum beam.  ``pcm`` / ``clips`` / ``channels`` / ``events`` / ``time_factor`` as ``event_doa`` takes
@@ -704,22 +797,7 @@ def event_beamform(pcm, clips, channels, events, time_factor, doa, beam, sr=SR, 
     its event's own samples alone: the batch, the order of the table, the other events and the clip's place in the buffer
     change no bit."""
     import ctypes as C
-    if not (isinstance(pcm, torch.Tensor) and pcm.is_cuda and pcm.dim() == 1):
-        raise RuntimeError("sed_crnn_amd.feature.event_beamform needs a 1-D CUDA(HIP) PCM buffer; there is no CPU fallback")
-    nc, tf, hop = int(channels), int(time_factor), int(hop)
-    if not 2 <= nc <= GCC_MAX_CHANNELS or tf < 1 or hop < 1:
-        raise ValueError(f"event_beamform needs 2 to {GCC_MAX_CHANNELS} audio channels, time_factor >= 1 and hop >= 1, got channels={nc}, "
-                         f"time_factor={tf}, hop={hop}")
-    table = np.ascontiguousarray(np.asarray(clips, dtype=np.int64).reshape(-1, 2))
-    if table.shape[0] == 0 or table.shape[0] % nc:
-        raise ValueError(f"{table.shape[0]} clips are not a whole number (>= 1) of recordings of {nc} channels")
-    R = table.shape[0] // nc
-    for i, (o, n) in enumerate(table.tolist()):
-        if n < 1 or o < 0 or o + n > pcm.numel():
-            raise ValueError(f"recording {i // nc}, channel {i % nc} (first sample {o}, {n} samples) is empty or not inside the "
-                             f"buffer of {pcm.numel()} samples")
-        if n != table[i - i % nc, 1]:
-            raise ValueError(f"recording {i // nc}: channel {i % nc} has {n} samples, channel 0 has {int(table[i - i % nc, 1])}")
+    nc, tf, hop, table, R = _planar_recordings("event_beamform", pcm, clips, channels, time_factor, hop)
     dev = pcm.device
     cols, E, plan = _beam_io("event_beamform", events, R, "rec", nc, doa, beam, sr, dev)
     if E == 0:

@@ -12,6 +12,8 @@ are searched, the time difference every direction means for every microphone pai
 the host side of per-event audio extraction by a steered delay-and-sum beam (the kernels are csrc/beam.hip, the device
 entry ``feature.event_beamform``): the settings of ``EventDetector(..., localize=DOA(...), extract=DelaySum())``, the
 fractional-delay filter, the delay every direction means for every microphone, and the samples an event's audio consists of.
+``MVDR`` and ``mvdr_window`` are the host side of the adaptive beam that extracts the same events (the kernels are
+csrc/mvdr.hip, the device entry ``feature.event_mvdr``).
 """
 import dataclasses
 import functools
@@ -227,6 +229,7 @@ class DOA:
         self.aperture = float(dist.max())
         self._plans, self._device = {}, {}                   # per rate: (max_lag, J, table); per (device, rate): their device copies
         self._delays, self._beam_device = {}, {}             # per (rate, Q): M of steering_delays; per (device, rate, Q): its device copy
+        self._steering, self._steering_device = {}, {}       # per rate: steering_delays in float64; per (device, rate): its device copy
 
     @property
     def channels(self):
@@ -261,6 +264,14 @@ class DOA:
             assert np.abs(M).max() <= ml * int(oversample)
             self._delays[key] = np.ascontiguousarray(M)
         return self._delays[key]
+
+    def steering(self, sr):
+        """``steering_delays`` of the array at rate ``sr``: float64 [D, C] in samples, not rounded, cached per rate"""
+        key = float(sr)
+        if key not in self._steering:
+            self.max_lag(sr)
+            self._steering[key] = np.ascontiguousarray(steering_delays(self.positions, self.grid, sr, self.c))
+        return self._steering[key]
 
     def tdoa(self, sr):
         """the ``TDOA`` settings whose outputs a detector with these settings also returns"""
@@ -321,6 +332,33 @@ def beam_taps(oversample, half_width, beta):
     t = np.ascontiguousarray(t.astype(np.float32))
     t.setflags(write=False)
     return t
+
+
+@dataclasses.dataclass(frozen=True)
+class MVDR:
+    """Settings of per-event audio extraction by an adaptive beam (``EventDetector(model, ..., localize=DOA(...), extract=MVDR(...))``;
+    DESIGN 5s): the events and samples of ``DelaySum``, but per frequency bin the channel weights that pass the event's direction
+    unchanged and let through the least of everything else the event's own frames contain (minimum variance distortionless
+    response).  ``loading`` in [1e-6, 1e6]: ``loading * trace(R) / C`` is added to the diagonal of every bin's covariance R before
+    the solve; small values adapt hard (and need more frames than microphones to estimate R), large ones approach the plain
+    average of the steered channels."""
+    loading: float = 1e-2
+
+    def __post_init__(self):
+        v = self.loading
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not 1e-6 <= float(v) <= 1e6:
+            raise ValueError(f"MVDR: loading must be a number in [1e-6, 1e6], got {v!r}")
+        object.__setattr__(self, "loading", float(v))
+
+
+@functools.lru_cache(maxsize=1)
+def mvdr_window():
+    """float32 [2048]: ``sqrt(0.5 - 0.5 cos(2 pi m / 2048))`` in float64, rounded once; analysis and synthesis window of the MVDR
+    beam (``w[m]^2 + w[m + 1024]^2 = 1``), read-only"""
+    m = np.arange(2048, dtype=np.float64)
+    w = np.sqrt(0.5 - 0.5 * np.cos(2.0 * np.pi * m / 2048.0)).astype(np.float32)
+    w.setflags(write=False)
+    return w
 
 
 def steering_delays(positions, grid, sr, c=SPEED_OF_SOUND):

@@ -204,9 +204,10 @@ class StreamDetector:
         self.det = _det if _det is not None else EventDetector(model, **kw)
         det, m = self.det, self.det.model
         if det.extract_settings is not None:
-            raise NotImplementedError("live feeds do not extract audio yet: a detector with extract=sed.DelaySum(...) does not stream "
-                                      "(feature.event_beamform_ring is the ring entry a StreamDetector would call; DESIGN 5r); make "
-                                      "the stream from a detector without extract=")
+            raise NotImplementedError("live feeds do not extract audio yet: a detector with extract=sed.DelaySum(...) or sed.MVDR(...) "
+                                      "does not stream (feature.event_beamform_ring is the ring entry a StreamDetector would call, "
+                                      "DESIGN 5r; the MVDR beam has no ring entry, DESIGN 5s); make the stream from a detector "
+                                      "without extract=")
         if det.localize_settings is not None and history_frames is None:
             raise NotImplementedError("live feeds are not localised: when a stream's event becomes final the PCM of its frames is "
                                       "gone (DESIGN 5o); make the StreamDetector without localize=, or give it history_frames= "
