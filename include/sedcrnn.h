@@ -291,7 +291,8 @@ int sed_conv1_fused_supported(int Cin, int F, int T, int C, int pool_f, int pool
 int sed_conv1_fused_rows(int B, int T);
 /* Statistics WITHOUT recomputing the convolution: sum y and sum y^2 of every output channel follow from the first and
  * second moments of the 9*Cin shifted inputs (one pass over x, fp64 quadratic form per channel).  Writes ONE partial
- * row [1][2][C]; workspace >= sed_conv1_stats_workspace_bytes(). */
+ * row [1][2][C]; workspace >= sed_conv1_stats_workspace_bytes().  With 1 or 2 input channels T may be any positive number
+ * of time rows (this pass has a ragged last tile; the multiple of 4 of sed_conv1_fused_supported belongs to the other passes). */
 size_t sed_conv1_stats_workspace_bytes(int B, int Cin, int T);
 /* moments (may be NULL): device array of sed_conv1_moments_doubles(Cin) doubles that receives the input moments themselves
  * ([9*Cin] first moments, then the upper triangle of the second moments row by row) for sed_conv1_bwd_wgrad. */

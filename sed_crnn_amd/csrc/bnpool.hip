@@ -46,23 +46,8 @@ __global__ __launch_bounds__(1024) void bn_finalize_train_k(
     const int c = blockIdx.x * 2 + (threadIdx.x & 1);
     double A, Q;
     bn_two_channel_sums(part, rows, C, c, c < C, sred, &A, &Q);
-    if (threadIdx.x < 2 && c < C) {
-        double m = A / count;
-        double var = Q / count - m * m;
-        if (var < 0.0) var = 0.0;
-        float rstd = (float)(1.0 / sqrt(var + (double)eps));
-        float g = gamma[c], bt = beta[c];
-        mean_o[c] = (float)m;
-        rstd_o[c] = rstd;
-        float sc = g * rstd;
-        scale_o[c] = sc;
-        shift_o[c] = bt - (float)m * sc;
-        if (rmean) {
-            double unb = count > 1.0 ? var * count / (count - 1.0) : var;
-            rmean[c] = (1.f - momentum) * rmean[c] + momentum * (float)m;
-            rvar[c] = (1.f - momentum) * rvar[c] + momentum * (float)unb;
-        }
-    }
+    if (threadIdx.x < 2 && c < C)
+        sed_bn_train_channel(A, Q, count, c, gamma, beta, rmean, rvar, momentum, eps, mean_o, rstd_o, scale_o, shift_o);
 }
 
 extern "C" int sed_bn_finalize_train(const float* part, int rows, int C, double count, const float* gamma,

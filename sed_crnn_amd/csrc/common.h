@@ -50,6 +50,30 @@ struct SedProfScope {
 // wino_f / wino_d (may be NULL): per layer, wf / wd receives the Winograd-transformed packing of wino.hip instead
 int sed_internal_conv_pack_multi(int n, const float* const* w, float* const* wf, float* const* wd, const int* Cout, const int* Cin,
                                  const int* wino_f, const int* wino_d, void* stream);
+// ... and, in the same launch, W_hh^T of n_gru GRU layers (whh[g][dir] [3H][H] -> whh_t[g] [2][H][3H], H[g] per layer): every
+// packing of a training forward is one launch at the head of the step, none stands between two layers of the chain
+int sed_internal_conv_pack_multi_gru(int n, const float* const* w, float* const* wf, float* const* wd, const int* Cout, const int* Cin,
+                                     const int* wino_f, const int* wino_d, int n_gru, const float* const* whh, float* const* whh_t,
+                                     const int* H, void* stream);
+
+// internal (gru.hip): sed_gru_seq_fwd on an already transposed W_hh (one launch), and sed_gru_seq_bwd in two halves — the
+// recurrence, which leaves its per-workgroup bias-gradient partial sums in bpart (NULL: none), and their reduction
+int sed_internal_gru_seq_fwd_packed(const float* gi, const float* wt, const float* const* bhh, float* out,
+                                    float* saved, int B, int T, int H, void* stream);
+int sed_internal_gru_seq_bwd_partials(const float* dout, const float* saved, const float* const* whh, float* dgi,
+                                      float* dgh, float* bpart, int B, int T, int H, void* stream);
+int sed_internal_gru_bias_grad(const float* bpart, float* const* dbih, float* const* dbhh, int B, int H, void* stream);
+
+// internal (gemm.hip): sed_linear_bwd in two halves — mask + data gradient, and the weight / bias gradient
+int sed_internal_linear_bwd_dx(const float* W, const float* y, float* dy, float* dx, int M, int K, int N, int relu, void* stream);
+int sed_internal_linear_bwd_dw(const float* x, const float* dy, float* dW, float* db, void* workspace, int M, int K, int N, void* stream);
+
+// internal (conv1.hip): sed_conv1_stats of a block with 1 or 2 input channels whose finalising kernel goes on to what
+// sed_bn_finalize_train makes of its one statistics row (same bits): one launch less on the head of the forward chain
+int sed_internal_conv1_stats_bn(const float* x, const float* wp, const float* bias, float* stat_partials, void* workspace,
+                                int B, int Cin, int F, int T, int C, double* gram_out, const float* gamma, const float* beta,
+                                float* running_mean, float* running_var, float momentum, float eps,
+                                float* mean, float* rstd, float* scale, float* shift, void* stream);
 
 // internal (conv.hip): the inference form of the packing launch — every layer's fragments, the BatchNorm coefficients on running
 // statistics, BatchNorm folded into weights + bias where fold[l], and (perm_src) the GRU input weights re-ordered to
@@ -119,4 +143,28 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     return v;
 }
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + __expf(-x)); }
+
+// Training BatchNorm of channel c from its sums A = sum y, Q = sum y^2 over `count` elements: mean, rstd, scale = gamma rstd,
+// shift = beta - mean scale, and the running statistics (unbiased variance).  One spelling for bn_finalize_train_k (bnpool.hip)
+// and for the first block's statistics kernel that ends in it (conv1.hip), so the two give the same bits.
+__device__ __forceinline__ void sed_bn_train_channel(double A, double Q, double count, int c, const float* __restrict__ gamma,
+                                                     const float* __restrict__ beta, float* __restrict__ rmean, float* __restrict__ rvar,
+                                                     float momentum, float eps, float* __restrict__ mean_o, float* __restrict__ rstd_o,
+                                                     float* __restrict__ scale_o, float* __restrict__ shift_o) {
+    double m = A / count;
+    double var = Q / count - m * m;
+    if (var < 0.0) var = 0.0;
+    float rstd = (float)(1.0 / sqrt(var + (double)eps));
+    float g = gamma[c], bt = beta[c];
+    mean_o[c] = (float)m;
+    rstd_o[c] = rstd;
+    float sc = g * rstd;
+    scale_o[c] = sc;
+    shift_o[c] = bt - (float)m * sc;
+    if (rmean) {
+        double unb = count > 1.0 ? var * count / (count - 1.0) : var;
+        rmean[c] = (1.f - momentum) * rmean[c] + momentum * (float)m;
+        rvar[c] = (1.f - momentum) * rvar[c] + momentum * (float)unb;
+    }
+}
 #endif

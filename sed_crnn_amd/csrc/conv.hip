@@ -152,10 +152,23 @@ struct ConvPackMulti {
     // bf16 inference plan (conv_mode 2): wb[l] != NULL receives the folded weights as bf16 fragments (conv_bf16.hip) instead of wf[l];
     // perm_bf16: perm_dst is a bf16 matrix
     __bf16* wb[SED_MAX_CONV]; int perm_bf16;
+    // the training plan: n_gru more slices of the grid (behind the layers and the permutation), slice g transposes W_hh of both
+    // directions of GRU layer g into gru_wt[g][dir][k][3H] — what gru_pack_whh_t_k (gru.hip) writes in front of a recurrence
+    const float* gru_w[SED_MAX_GRU][2]; float* gru_wt[SED_MAX_GRU]; int gru_H[SED_MAX_GRU]; int n_gru;
 };
 __global__ void conv_pack_w_multi_k(ConvPackMulti a, int n) {
     const int l = blockIdx.y;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int gru0 = n + (a.perm_src[0] ? 1 : 0);
+    if (l >= gru0) {
+        const int gl = l - gru0, H = a.gru_H[gl], nw = 3 * H * H;
+        for (int e2 = i; e2 < 2 * nw; e2 += gridDim.x * blockDim.x) {      // the copy of gru_pack_whh_t_k, element for element
+            const int dir = e2 / nw, e = e2 - dir * nw;
+            const int g = e / H, k = e - g * H;
+            a.gru_wt[gl][(size_t)dir * nw + (size_t)k * 3 * H + g] = a.gru_w[gl][dir][e];
+        }
+        return;
+    }
     if (l == n) {
         // one row per workgroup and round: read it as it lies (coalesced), write it re-ordered (coalesced) through LDS
         extern __shared__ __attribute__((aligned(16))) float prow[];
@@ -207,14 +220,25 @@ static int pack_multi_launch(const ConvPackMulti& a, int n, void* stream) {
     const size_t lds = a.perm_src[0] ? (size_t)a.perm_C * a.perm_Fp * sizeof(float) : 0;      // one row of the re-ordered matrix
     SED_REQUIRE(lds <= 64 * 1024, "conv_pack: a GRU input row of %zu bytes does not fit the re-ordering buffer", lds);
     if (lds > 48 * 1024) SED_TRY(set_lds_early(lds));
-    conv_pack_w_multi_k<<<dim3(gx, n + (a.perm_src[0] ? 1 : 0)), 256, lds, as_stream(stream)>>>(a, n);
+    conv_pack_w_multi_k<<<dim3(gx, n + (a.perm_src[0] ? 1 : 0) + a.n_gru), 256, lds, as_stream(stream)>>>(a, n);
     SED_LAUNCH_CHECK("conv_pack_w_multi");
     return 0;
 }
 int sed_internal_conv_pack_multi(int n, const float* const* w, float* const* wf, float* const* wd, const int* Cout, const int* Cin,
                                  const int* wino_f, const int* wino_d, void* stream) {
+    return sed_internal_conv_pack_multi_gru(n, w, wf, wd, Cout, Cin, wino_f, wino_d, 0, nullptr, nullptr, nullptr, stream);
+}
+int sed_internal_conv_pack_multi_gru(int n, const float* const* w, float* const* wf, float* const* wd, const int* Cout, const int* Cin,
+                                     const int* wino_f, const int* wino_d, int n_gru, const float* const* whh, float* const* whh_t,
+                                     const int* H, void* stream) {
     SED_REQUIRE(n > 0 && n <= SED_MAX_CONV && w && wf && wd && Cout && Cin, "conv_pack_multi: bad arguments");
+    SED_REQUIRE(n_gru >= 0 && n_gru <= SED_MAX_GRU && (n_gru == 0 || (whh && whh_t && H)), "conv_pack_multi: bad GRU arguments");
     ConvPackMulti a{};
+    a.n_gru = n_gru;
+    for (int g = 0; g < n_gru; ++g) {
+        SED_REQUIRE(whh[2 * g] && whh[2 * g + 1] && whh_t[g] && H[g] > 0, "conv_pack_multi: bad GRU layer %d", g);
+        a.gru_w[g][0] = whh[2 * g]; a.gru_w[g][1] = whh[2 * g + 1]; a.gru_wt[g] = whh_t[g]; a.gru_H[g] = H[g];
+    }
     for (int l = 0; l < n; ++l) {
         SED_REQUIRE(w[l] && Cout[l] > 0 && Cin[l] > 0, "conv_pack_multi: bad layer %d", l);
         a.w[l] = w[l]; a.wf[l] = wf[l]; a.wd[l] = wd[l]; a.Cout[l] = Cout[l]; a.Cin[l] = Cin[l];

@@ -5,7 +5,10 @@
 // their backward.  With Cin <= 2 one output costs 9..18 FMAs, far less than moving it through HBM, so none of the
 // four passes materialises it: each recomputes conv(x) from the L2-resident input tile in LDS.
 //   A  stats      : sum / sum^2 partials                         (reads x)
-//   B  fwd        : BN scale/shift + ReLU + max-pool + dropout    (reads x, writes pooled)
+//                   (1 or 2 input channels: from the input's moments, two launches — conv1_gram_k, then one workgroup that
+//                    turns the moments into the statistics row and, in the whole-network plan, goes straight on to the
+//                    BatchNorm coefficients and running statistics: sed_internal_conv1_stats_bn)
+//   B  fwd       : BN scale/shift + ReLU + max-pool + dropout    (reads x, writes pooled)
 //   C  bwd reduce : sum g, sum g*xhat                             (reads x, dpooled)
 //   D  bwd apply  : dy on the fly -> dW (9*Cin taps), dbias       (reads x, dpooled; dy is never written;
 //                                                                   the network input needs no data gradient)
@@ -324,27 +327,47 @@ __global__ __launch_bounds__(256) void conv1_gram_k(const float* __restrict__ x,
     for (int i = 0; i < NG; ++i) acc[i] = 0.f;
     // C1_GR tiles per round: all their halo loads are in flight together (one global latency per round, not per tile)
     const int hn = (C1_GT + 2) * F2 * CIN;
+    const float inv_F = 1.0f / (float)F;
+    // The positions a thread sums, and their order, are what they always were (p = tid, tid + 256, ... of a round's C1_GR x C1_GT x F),
+    // so every partial sum keeps its bits.  What changed is what a position costs besides its NG multiply-adds: no integer
+    // division is left in either loop (there were four per staged element and three per position, ~35 instructions each at one
+    // wave per SIMD with nothing to hide them behind: half of the kernel).  What is uniform — a tile's batch, its first time row,
+    // how many of its rows lie inside the recording — is worked out once per tile and round on the scalar unit.
     for (int tile0 = blockIdx.x * C1_GR; tile0 < ntiles; tile0 += gridDim.x * C1_GR) {
+        int t0[C1_GR], rows[C1_GR];                           // rows: 0 for a tile beyond the last one
+        size_t xb[C1_GR];
+#pragma unroll
+        for (int u = 0; u < C1_GR; ++u) {
+            const int tile = tile0 + u, b = tile < ntiles ? tile / tblocks : 0;
+            t0[u] = (tile - b * tblocks) * C1_GT;
+            rows[u] = tile < ntiles ? (T - t0[u] < C1_GT ? T - t0[u] : C1_GT) : 0;
+            xb[u] = (size_t)b * CIN * F * T;
+        }
         __syncthreads();
-        for (int i = tid; i < C1_GR * hn; i += 256) {         // time fastest: contiguous in the NCHW input
-            const int u = i / hn, j = i - u * hn;
-            const int tile = tile0 + u;
-            int tt = j % (C1_GT + 2), ff = (j / (C1_GT + 2)) % F2, ci = j / ((C1_GT + 2) * F2);
-            float v = 0.f;
-            if (tile < ntiles) {
-                const int b = tile / tblocks, t = (tile - b * tblocks) * C1_GT + tt - 1, f = ff - 1;
-                if (t >= 0 && t < T && f >= 0 && f < F) v = x[(((size_t)b * CIN + ci) * F + f) * T + t];
+        // an element of the halo image is decoded once (constant divisor, CIN <= 2) and fetched for all C1_GR tiles: their loads
+        // are in flight together (one global latency per round, not per tile); time fastest: contiguous in the NCHW input
+        for (int j = tid; j < hn; j += 256) {
+            const int r = j / (C1_GT + 2), tt = j - r * (C1_GT + 2);
+            const int ci = (CIN > 1 && r >= F2) ? 1 : 0, ff = r - ci * F2, f = ff - 1;
+            const bool f_in = f >= 0 && f < F;
+            const long src = ((long)ci * F + f) * T + tt - 1;
+            float v[C1_GR];
+#pragma unroll
+            for (int u = 0; u < C1_GR; ++u) {
+                const int t = t0[u] + tt - 1;
+                v[u] = (f_in && rows[u] > 0 && t >= 0 && t < T) ? x[xb[u] + (size_t)(src + t0[u])] : 0.f;
             }
-            halo[u * hn + (tt * F2 + ff) * CIN + ci] = v;
+#pragma unroll
+            for (int u = 0; u < C1_GR; ++u) halo[u * hn + (tt * F2 + ff) * CIN + ci] = v[u];
         }
         __syncthreads();
         for (int p = tid; p < C1_GR * C1_GT * F; p += 256) {
-            const int u = p / (C1_GT * F), q = p - u * (C1_GT * F);
-            const int tile = tile0 + u;
-            if (tile >= ntiles) break;
-            const int tl = q / F, f = q - tl * F;
-            const int b = tile / tblocks, t0 = (tile - b * tblocks) * C1_GT;
-            if (t0 + tl >= T) continue;
+            const int r = sed_fdiv(p, inv_F), f = p - r * F;  // r = tile of the round * C1_GT + time row of the tile
+            const int u = r / C1_GT, tl = r - u * C1_GT;
+            int live = rows[0];
+#pragma unroll
+            for (int k = 1; k < C1_GR; ++k) live = (u == k) ? rows[k] : live;
+            if (tl >= live) continue;
             const float* hb = halo + u * hn;
             float v[NK];
 #pragma unroll
@@ -366,10 +389,24 @@ __global__ __launch_bounds__(256) void conv1_gram_k(const float* __restrict__ x,
     __syncthreads();
     float* red = smem;                                         // [NG][4]
     const int lane = tid & 63, wave = tid >> 6;
+    // (wave_sum's butterfly, value for value — the same additions in the same order — but a chunk of values goes through each
+    // exchange step together: taken one value at a time, the NG x 6 cross-lane reads each waited out their own latency, a third
+    // of what was left of the kernel)
+    constexpr int CH = 27;                                     // divides 54 and 189
+    static_assert(NG % CH == 0, "chunked wave reduction");
 #pragma unroll
-    for (int i = 0; i < NG; ++i) {
-        const float sum = wave_sum(acc[i]);
-        if (lane == 0) red[i * 4 + wave] = sum;
+    for (int i0 = 0; i0 < NG; i0 += CH) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            float t[CH];
+#pragma unroll
+            for (int j = 0; j < CH; ++j) t[j] = __shfl_xor(acc[i0 + j], o, 64);
+#pragma unroll
+            for (int j = 0; j < CH; ++j) acc[i0 + j] += t[j];
+        }
+#pragma unroll
+        for (int j = 0; j < CH; ++j)
+            if (lane == 0) red[(i0 + j) * 4 + wave] = acc[i0 + j];
     }
     __syncthreads();
     for (int i = tid; i < NG; i += 256)
@@ -377,10 +414,14 @@ __global__ __launch_bounds__(256) void conv1_gram_k(const float* __restrict__ x,
 }
 
 // stat[0][c] = sum y, stat[1][c] = sum y^2 of channel c (one partial row in the format of the stored path's conv epilogue)
+// bn.gamma != NULL: the thread that holds a channel's two sums goes on to its training BatchNorm coefficients and running
+// statistics — what bn_finalize_train_k makes of this one-row `stat`, in the same arithmetic (sed_bn_train_channel), without
+// the launch in between: both are one workgroup's work and the second only ever read the first's row.
+struct Conv1BnOut { const float* gamma; const float* beta; float* rmean; float* rvar; float momentum, eps; float* mean; float* rstd; float* scale; float* shift; };
 template <int CIN>
 __global__ __launch_bounds__(256) void conv1_gram_finalize_k(const float* __restrict__ partials, int nblk, const float* __restrict__ wp,
                                                              const float* __restrict__ bias, double count, int C, float* __restrict__ stat,
-                                                             double* __restrict__ gram_out) {
+                                                             double* __restrict__ gram_out, Conv1BnOut bn) {
     constexpr int NK = 9 * CIN, NG = NK + NK * (NK + 1) / 2;
     __shared__ double G[NG];
     __shared__ double Gq[4][64];
@@ -416,8 +457,13 @@ __global__ __launch_bounds__(256) void conv1_gram_finalize_k(const float* __rest
 #pragma unroll
             for (int k2 = k; k2 < NK; ++k2) { q += (k2 == k ? 1.0 : 2.0) * w[k] * w[k2] * G[g]; ++g; }
         }
-        stat[c] = (float)(count * b + ws1);
-        stat[C + c] = (float)(q + 2.0 * b * ws1 + count * b * b);
+        const float sum_y = (float)(count * b + ws1), sum_y2 = (float)(q + 2.0 * b * ws1 + count * b * b);
+        stat[c] = sum_y;
+        stat[C + c] = sum_y2;
+        // (0.0 + : the sums of a one-row `stat` as bn_finalize_train_k forms them, a zero's sign included)
+        if (bn.gamma)
+            sed_bn_train_channel(0.0 + (double)sum_y, 0.0 + (double)sum_y2, count, c, bn.gamma, bn.beta, bn.rmean, bn.rvar, bn.momentum, bn.eps,
+                                 bn.mean, bn.rstd, bn.scale, bn.shift);
     }
 }
 
@@ -936,10 +982,33 @@ extern "C" size_t sed_conv1_stats_workspace_bytes(int B, int Cin, int T) {
     return (size_t)256 * (nk + nk * (nk + 1) / 2) * sizeof(float);      // at most 256 partial rows (one per workgroup)
 }
 
+static int conv1_stats_impl(const float* x, const float* wp, const float* bias, float* stat_partials, void* workspace,
+                            int B, int Cin, int F, int T, int C, double* gram_out, const Conv1BnOut& bn, void* stream);
+
 extern "C" int sed_conv1_stats(const float* x, const float* wp, const float* bias, float* stat_partials, void* workspace,
                                int B, int Cin, int F, int T, int C, double* gram_out, void* stream) {
+    return conv1_stats_impl(x, wp, bias, stat_partials, workspace, B, Cin, F, T, C, gram_out, Conv1BnOut{}, stream);
+}
+
+// sed_conv1_stats (1 or 2 input channels) followed by sed_bn_finalize_train on its one statistics row, in the two launches of
+// the former: the kernel that turns the moments into the row also writes the BatchNorm coefficients and running statistics
+int sed_internal_conv1_stats_bn(const float* x, const float* wp, const float* bias, float* stat_partials, void* workspace,
+                                int B, int Cin, int F, int T, int C, double* gram_out, const float* gamma, const float* beta,
+                                float* running_mean, float* running_var, float momentum, float eps,
+                                float* mean, float* rstd, float* scale, float* shift, void* stream) {
+    SED_REQUIRE(Cin >= 1 && Cin <= 2, "conv1_stats_bn: Cin=%d (the merged finalisation exists for 1 or 2 input channels)", Cin);
+    SED_REQUIRE(gamma && beta && mean && rstd && scale && shift, "conv1_stats_bn: null pointer");
+    return conv1_stats_impl(x, wp, bias, stat_partials, workspace, B, Cin, F, T, C, gram_out,
+                            Conv1BnOut{gamma, beta, running_mean, running_var, momentum, eps, mean, rstd, scale, shift}, stream);
+}
+
+static int conv1_stats_impl(const float* x, const float* wp, const float* bias, float* stat_partials, void* workspace,
+                            int B, int Cin, int F, int T, int C, double* gram_out, const Conv1BnOut& bn, void* stream) {
     SED_REQUIRE(x && wp && stat_partials && workspace, "conv1_stats: null pointer");
-    SED_REQUIRE(c1_shape_ok(Cin, F, T, C, 1, 1, 4), "conv1_stats: shape Cin=%d F=%d T=%d C=%d is not supported", Cin, F, T, C);
+    // 1 or 2 input channels: the moment pass walks C1_GT-row tiles with a ragged last one, so any number of time rows will do (the
+    // multiple of C1_TT the other passes of the block need is theirs, not this one's)
+    const int Tq = Cin <= 2 ? (T + C1_TT - 1) / C1_TT * C1_TT : T;
+    SED_REQUIRE(T >= 1 && c1_shape_ok(Cin, F, Tq, C, 1, 1, 4), "conv1_stats: shape Cin=%d F=%d T=%d C=%d is not supported", Cin, F, T, C);
     hipStream_t s = as_stream(stream);
     SedProfScope prof(SED_K_CONV_SMALL_FWD, s, 4.0 * B * Cin * (double)F * T);
     if (Cin > 2) {
@@ -964,9 +1033,7 @@ extern "C" int sed_conv1_stats(const float* x, const float* wp, const float* bia
         SED_LAUNCH_CHECK("conv1_moments");
         return 0;
     }
-    const int pf = 1, pt = 1;
-    C1_CHECK("conv1_stats");
-    int grid = (B * ((T + C1_GT - 1) / C1_GT) + C1_GR - 1) / C1_GR;
+    int grid =(B * ((T + C1_GT - 1) / C1_GT) + C1_GR - 1) / C1_GR;
     if (grid > 256) grid = 256;                              // one workgroup per CU; at most 256 partial rows for the finalisation
     const int nk = 9 * Cin, ng = nk + nk * (nk + 1) / 2;
     size_t lds = (size_t)C1_GR * (C1_GT + 2) * (F + 2) * Cin * sizeof(float), red = (size_t)ng * 4 * sizeof(float);
@@ -980,11 +1047,11 @@ extern "C" int sed_conv1_stats(const float* x, const float* wp, const float* bia
     if (Cin == 1) {
         conv1_gram_k<1><<<grid, 256, lds, s>>>(x, (float*)workspace, B, F, T);
         SED_LAUNCH_CHECK("conv1_gram");
-        conv1_gram_finalize_k<1><<<1, 256, 0, s>>>((const float*)workspace, grid, wp, bias, count, C, stat_partials, gram_out);
+        conv1_gram_finalize_k<1><<<1, 256, 0, s>>>((const float*)workspace, grid, wp, bias, count, C, stat_partials, gram_out, bn);
     } else {
         conv1_gram_k<2><<<grid, 256, lds, s>>>(x, (float*)workspace, B, F, T);
         SED_LAUNCH_CHECK("conv1_gram");
-        conv1_gram_finalize_k<2><<<1, 256, 0, s>>>((const float*)workspace, grid, wp, bias, count, C, stat_partials, gram_out);
+        conv1_gram_finalize_k<2><<<1, 256, 0, s>>>((const float*)workspace, grid, wp, bias, count, C, stat_partials, gram_out, bn);
     }
     SED_LAUNCH_CHECK("conv1_gram_finalize");
     return 0;

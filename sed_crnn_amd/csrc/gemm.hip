@@ -605,9 +605,11 @@ extern "C" size_t sed_linear_bwd_workspace_bytes(int M, int K, int N) {
     return (size_t)cdiv(M, LIN_CHUNK) * ((size_t)N * K + N) * sizeof(float);
 }
 
-extern "C" int sed_linear_bwd(const float* x, const float* W, const float* y, float* dy, float* dx, float* dW,
-                              float* db, void* workspace, int M, int K, int N, int relu, void* stream) {
-    SED_REQUIRE(x && W && dy && dW && workspace && M > 0 && K > 0 && N > 0, "linear_bwd: bad arguments");
+// sed_linear_bwd in its two halves.  _dx: what the layer below waits for (the ReLU mask on dy, then dx).  _dw: the weight and
+// bias gradient, which feed only the optimiser — the whole-network backward issues it on its auxiliary stream, behind an event
+// recorded after _dx (it reads the masked dy).
+int sed_internal_linear_bwd_dx(const float* W, const float* y, float* dy, float* dx, int M, int K, int N, int relu, void* stream) {
+    SED_REQUIRE(W && dy && M > 0 && K > 0 && N > 0, "linear_bwd: bad arguments");
     SED_REQUIRE(!relu || y, "linear_bwd: relu=1 needs the forward output y");
     hipStream_t s = as_stream(stream);
     if (relu) {
@@ -620,10 +622,22 @@ extern "C" int sed_linear_bwd(const float* x, const float* W, const float* y, fl
         linear_dx_k<<<cdiv(n, 256), 256, 0, s>>>(dy, W, dx, M, K, N);
         SED_LAUNCH_CHECK("linear_dx");
     }
+    return 0;
+}
+int sed_internal_linear_bwd_dw(const float* x, const float* dy, float* dW, float* db, void* workspace, int M, int K, int N, void* stream) {
+    SED_REQUIRE(x && dy && dW && workspace && M > 0 && K > 0 && N > 0, "linear_bwd: bad arguments");
+    hipStream_t s = as_stream(stream);
     int tot = N * K + N, chunks = cdiv(M, LIN_CHUNK);
     linear_dw_partial_k<<<dim3(cdiv(tot, 256), chunks), 256, 0, s>>>(dy, x, (float*)workspace, M, K, N);
     SED_LAUNCH_CHECK("linear_dw_partial");
     linear_dw_reduce_k<<<cdiv(tot, 256), 256, 0, s>>>((const float*)workspace, chunks, tot, N * K, dW, db);
     SED_LAUNCH_CHECK("linear_dw_reduce");
     return 0;
+}
+
+extern "C" int sed_linear_bwd(const float* x, const float* W, const float* y, float* dy, float* dx, float* dW,
+                              float* db, void* workspace, int M, int K, int N, int relu, void* stream) {
+    SED_REQUIRE(x && W && dy && dW && workspace && M > 0 && K > 0 && N > 0, "linear_bwd: bad arguments");
+    SED_TRY(sed_internal_linear_bwd_dx(W, y, dy, dx, M, K, N, relu, stream));
+    return sed_internal_linear_bwd_dw(x, dy, dW, db, workspace, M, K, N, stream);
 }

@@ -8,7 +8,14 @@
 // gfx950, so the per-step matvec is plain v_fma with a small batch tile (more workgroups in flight)
 // rather than a 32-wide MFMA tile.
 //
-// PyTorch gate convention (r,z,n):  r = s(gi_r+gh_r)  z = s(gi_z+gh_z)  n = tanh(gi_n + r*gh_n)
+// Launches.  The forward kernel reads W_hh transposed ([dir][k][3H]).  The public sed_gru_seq_fwd makes that copy itself
+// (gru_pack_whh_t_k, one launch in front of the recurrence); the whole-network plan writes it for every layer from the one packing
+// launch at the head of its forward (conv.hip, conv_pack_w_multi_k) and calls sed_internal_gru_seq_fwd_packed, which launches the
+// recurrence and nothing else.  The backward kernel leaves per-workgroup bias-gradient partial sums; sed_gru_seq_bwd reduces
+// them behind the recurrence (gru_bias_grad_k), the plan's backward issues that reduction on its auxiliary stream
+// (sed_internal_gru_seq_bwd_partials + sed_internal_gru_bias_grad): it feeds nothing but the optimiser.
+//
+// PyTorch gate convention (r,z,n): r = s(gi_r+gh_r)  z = s(gi_z+gh_z)  n = tanh(gi_n + r*gh_n)
 //                                   h' = (1-z)*n + z*h,  h0 = 0.
 #include "common.h"
 
@@ -368,15 +375,21 @@ extern "C" int sed_gru_seq_variant(int B, int H, int* bt, int* hreg, int* hlds) 
         default: GRU_BT3(0, KERNEL, __VA_ARGS__); break;                                      \
     }
 
-extern "C" int sed_gru_seq_fwd(const float* gi, const float* const* whh, const float* const* bhh, float* out,
-                               float* saved, void* workspace, int B, int T, int H, void* stream) {
-    SED_REQUIRE(gi && whh && bhh && out && workspace && whh[0] && whh[1] && bhh[0] && bhh[1], "gru_seq_fwd: null pointer");
-    SED_REQUIRE(B > 0 && T > 0 && H > 0 && H % 4 == 0 && 3 * H <= 1024, "gru_seq_fwd: H=%d must be a multiple of 4 and <= 341", H);
-    hipStream_t s = as_stream(stream);
-    float* wt = (float*)workspace;
+// W_hh^T of both directions of one layer into wt (sed_gru_seq_workspace_bytes(H)): the launch the public entry makes for itself.
+// The whole-network plan writes the same matrix from its up-front packing launch (sed_internal_conv_pack_multi_gru, conv.hip).
+static int gru_pack_whh(const float* const* whh, float* wt, int H, hipStream_t s) {
     int n = 2 * 3 * H * H;
     gru_pack_whh_t_k<<<cdiv(n, 256), 256, 0, s>>>(whh[0], whh[1], wt, H);
     SED_LAUNCH_CHECK("gru_pack_whh_t");
+    return 0;
+}
+
+// The recurrence alone: wt = W_hh^T of both directions, [2][H][3H], already packed.  One launch.
+int sed_internal_gru_seq_fwd_packed(const float* gi, const float* wt, const float* const* bhh, float* out,
+                                    float* saved, int B, int T, int H, void* stream) {
+    SED_REQUIRE(gi && wt && bhh && out && bhh[0] && bhh[1], "gru_seq_fwd: null pointer");
+    SED_REQUIRE(B > 0 && T > 0 && H > 0 && H % 4 == 0 && 3 * H <= 1024, "gru_seq_fwd: H=%d must be a multiple of 4 and <= 341", H);
+    hipStream_t s = as_stream(stream);
     const GruVariant v = gru_variant(H, B, GRU_HR_FWD);
     dim3 grid(cdiv(B, v.bt), 2);
     int nt = gru_threads(H);
@@ -391,15 +404,21 @@ extern "C" int sed_gru_seq_fwd(const float* gi, const float* const* whh, const f
     return 0;
 }
 
+extern "C" int sed_gru_seq_fwd(const float* gi, const float* const* whh, const float* const* bhh, float* out,
+                               float* saved, void* workspace, int B, int T, int H, void* stream) {
+    SED_REQUIRE(gi && whh && bhh && out && workspace && whh[0] && whh[1] && bhh[0] && bhh[1], "gru_seq_fwd: null pointer");
+    SED_REQUIRE(B > 0 && T > 0 && H > 0 && H % 4 == 0 && 3 * H <= 1024, "gru_seq_fwd: H=%d must be a multiple of 4 and <= 341", H);
+    SED_TRY(gru_pack_whh(whh, (float*)workspace, H, as_stream(stream)));
+    return sed_internal_gru_seq_fwd_packed(gi, (const float*)workspace, bhh, out, saved, B, T, H, stream);
+}
+
 extern "C" size_t sed_gru_seq_bwd_workspace_bytes(int B, int H) { return (size_t)cdiv(B, gru_bt(H, B)) * 2 * 4 * H * sizeof(float); }
 
-extern "C" int sed_gru_seq_bwd(const float* dout, const float* saved, const float* const* whh, float* dgi,
-                               float* dgh, float* const* dbih, float* const* dbhh, void* workspace, int B, int T,
-                               int H, void* stream) {
+// The recurrence's backward alone.  bpart (may be NULL: no bias gradients wanted): every workgroup's bias-gradient partial
+// sums, sed_gru_seq_bwd_workspace_bytes(B, H); sed_internal_gru_bias_grad reduces them, on whichever stream the caller likes.
+int sed_internal_gru_seq_bwd_partials(const float* dout, const float* saved, const float* const* whh, float* dgi,
+                                      float* dgh, float* bpart, int B, int T, int H, void* stream) {
     SED_REQUIRE(dout && saved && whh && whh[0] && whh[1] && dgi && dgh, "gru_seq_bwd: null pointer");
-    const bool want_bias = dbih && dbhh;
-    SED_REQUIRE(!want_bias || (workspace && dbih[0] && dbih[1] && dbhh[0] && dbhh[1]), "gru_seq_bwd: bias gradients need all four outputs and a workspace");
-    float* bpart = want_bias ? (float*)workspace : nullptr;
     SED_REQUIRE(B > 0 && T > 0 && H > 0 && H % 4 == 0 && 3 * H <= 1024, "gru_seq_bwd: H=%d must be a multiple of 4 and <= 341", H);
     hipStream_t s = as_stream(stream);
     const GruVariant v = gru_variant(H, B, GRU_HR);
@@ -413,9 +432,25 @@ extern "C" int sed_gru_seq_bwd(const float* dout, const float* saved, const floa
     GRU_DISPATCH(gru_seq_bwd_k, dout, saved, whh[0], whh[1], dgi, dgh, bpart, B, T, H);
 #undef GRU_HRX
     SED_LAUNCH_CHECK("gru_seq_bwd");
-    if (want_bias) {
-        gru_bias_grad_k<<<cdiv(8 * H, 256), 256, 0, s>>>(bpart, cdiv(B, v.bt), H, dbih[0], dbih[1], dbhh[0], dbhh[1]);
-        SED_LAUNCH_CHECK("gru_bias_grad");
-    }
+    return 0;
+}
+
+// db_ih / db_hh of both directions from the partial sums of sed_internal_gru_seq_bwd_partials (same B, H).  Feeds only the optimiser.
+int sed_internal_gru_bias_grad(const float* bpart, float* const* dbih, float* const* dbhh, int B, int H, void* stream) {
+    SED_REQUIRE(bpart && dbih && dbhh && dbih[0] && dbih[1] && dbhh[0] && dbhh[1], "gru_bias_grad: null pointer");
+    SED_REQUIRE(B > 0 && H > 0 && H % 4 == 0 && 3 * H <= 1024, "gru_bias_grad: H=%d must be a multiple of 4 and <= 341", H);
+    gru_bias_grad_k<<<cdiv(8 * H, 256), 256, 0, as_stream(stream)>>>(bpart, cdiv(B, gru_bt(H, B)), H, dbih[0], dbih[1], dbhh[0], dbhh[1]);
+    SED_LAUNCH_CHECK("gru_bias_grad");
+    return 0;
+}
+
+extern "C" int sed_gru_seq_bwd(const float* dout, const float* saved, const float* const* whh, float* dgi,
+                               float* dgh, float* const* dbih, float* const* dbhh, void* workspace, int B, int T,
+                               int H, void* stream) {
+    const bool want_bias = dbih && dbhh;
+    SED_REQUIRE(!want_bias || (workspace && dbih[0] && dbih[1] && dbhh[0] && dbhh[1]), "gru_seq_bwd: bias gradients need all four outputs and a workspace");
+    float* bpart = want_bias ? (float*)workspace : nullptr;
+    SED_TRY(sed_internal_gru_seq_bwd_partials(dout, saved, whh, dgi, dgh, bpart, B, T, H, stream));
+    if (want_bias) SED_TRY(sed_internal_gru_bias_grad(bpart, dbih, dbhh, B, H, stream));
     return 0;
 }

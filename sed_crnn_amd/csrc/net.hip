@@ -34,13 +34,16 @@ struct Layout {
     size_t bias_f[SED_MAX_CONV];   // inference: the BatchNorm-folded conv bias of a block whose epilogue pools
     size_t wih_perm;               // inference, last block pooled in its conv epilogue (output stays channels-last): weight_ih_l0 of both
                                    // directions [6H][F'*C] with the columns re-ordered from c*F'+f (sed.py:108-110) to f*C+c; 0 = not used
-    size_t gi[SED_MAX_GRU], gout[SED_MAX_GRU], saved[SED_MAX_GRU], gru_ws;
+    size_t gi[SED_MAX_GRU], gout[SED_MAX_GRU], saved[SED_MAX_GRU];
+    size_t gru_ws[SED_MAX_GRU];    // W_hh^T of layer i, [2][H][3H]: one region per layer, all written by the packing launch at the head of the forward
     size_t act[SED_MAX_DENSE];
     // backward only
     size_t wgrad_zrow;       // floats at the start of wgrad_ws / wgrad_ws_aux that the backward keeps zero (sed_conv3x3_wgrad_zero_row_bytes)
     size_t wg_arrive;        // one granule right in front of wgrad_ws (cleared by the same memset as its zero row): word 0 = arrival
                              // counter of the first deferred weight gradient's workgroups (sed_internal_stream_gate)
-    size_t bn_part, sum_g, sum_gx, dbias_part, dconv[SED_MAX_CONV], gradA, wgrad_ws, wgrad_ws_aux, c1_ws, dgi[SED_MAX_GRU], dgh[SED_MAX_GRU], gru_bws, dgout[SED_MAX_GRU];
+    size_t bn_part, sum_g, sum_gx, dbias_part, dconv[SED_MAX_CONV], gradA, wgrad_ws, wgrad_ws_aux, c1_ws, dgi[SED_MAX_GRU], dgh[SED_MAX_GRU], dgout[SED_MAX_GRU];
+    size_t gru_bws[SED_MAX_GRU];   // bias-gradient partial sums of layer i's recurrence: one region per layer (the auxiliary stream still
+                                   // reduces layer i's while the recurrence of layer i-1 writes its own)
     size_t dact[SED_MAX_DENSE], lin_ws, gemm_ws, gemm_ws_aux;
     size_t total;     // floats
 };
@@ -182,7 +185,7 @@ int build_layout(const sed_net_cfg* c, int training, Layout* L) {
     }
     L->proj_bf = L->cv[c->n_conv - 1].bf;
     L->wih_perm = ((L->cv[c->n_conv - 1].ev || L->proj_bf) && c->H[0] > 0) ? cv.take((size_t)6 * c->H[0] * L->feat / (L->proj_bf ? 2 : 1)) : 0;
-    int in = L->feat, maxH = 0, max2H = 0;
+    int in = L->feat, max2H = 0;
     for (int i = 0; i < c->n_gru; ++i) {
         int H = c->H[i];
         SED_REQUIRE(H > 0 && H % 4 == 0 && 3 * H <= 1024, "net: GRU hidden H[%d]=%d must be a multiple of 4 and <= 341", i, H);
@@ -190,11 +193,10 @@ int build_layout(const sed_net_cfg* c, int training, Layout* L) {
         L->gi[i] = cv.take(M * 6 * H);
         L->gout[i] = cv.take(M * 2 * H);
         L->saved[i] = training ? cv.take(M * 10 * H) : 0;
-        if (H > maxH) maxH = H;
         in = 2 * H;
         if (in > max2H) max2H = in;
     }
-    L->gru_ws = cv.take((size_t)6 * maxH * maxH);
+    for (int i = 0; i < c->n_gru; ++i) L->gru_ws[i] = cv.take((size_t)6 * c->H[i] * c->H[i]);
     size_t max_lin_ws = 0;
     for (int j = 0; j < c->n_dense; ++j) {
         SED_REQUIRE(c->D[j] > 0, "net: dense size D[%d]=%d", j, c->D[j]);
@@ -224,9 +226,10 @@ int build_layout(const sed_net_cfg* c, int training, Layout* L) {
             L->dgi[i] = cv.take(M * 6 * c->H[i]);
             L->dgh[i] = cv.take(M * 6 * c->H[i]);
         }
-        L->gru_bws = cv.take(sed_gru_seq_bwd_workspace_bytes(c->B, maxH) / sizeof(float));
+        for (int i = 0; i < c->n_gru; ++i) L->gru_bws[i] = cv.take(sed_gru_seq_bwd_workspace_bytes(c->B, c->H[i]) / sizeof(float));
         for (int i = 0; i < c->n_gru; ++i) L->dgout[i] = cv.take(M * 2 * c->H[i]);
         for (int j = 0; j < c->n_dense - 1; ++j) L->dact[j] = cv.take(M * c->D[j]);
+        // one region for every dense layer: their weight gradients are issued on ONE stream (main, or auxiliary), in order
         L->lin_ws = cv.take(max_lin_ws);
     }
     {   // split-K scratch of the GEMMs: forward input projections (small batches), and in training the weight gradients
@@ -333,6 +336,9 @@ static int forward_impl(const sed_net_cfg* c, const sed_net_params* p, const flo
         }
     }
     const bool packed_up_front = !eval_plan && pb == 0 && c->conv_mode == 0 && L.n_conv > 1;
+    // ... and, when this call also runs the GRU stack, W_hh^T of every GRU layer: the recurrences then launch nothing but
+    // themselves (a call that starts at a later phase, and the inference plan, pack in front of each recurrence as before)
+    const bool gru_packed_up_front = packed_up_front && pe > 2 * L.n_conv;
     if (packed_up_front) {
         const float* w[SED_MAX_CONV]; float* wf[SED_MAX_CONV]; float* wd[SED_MAX_CONV]; int co[SED_MAX_CONV], ci[SED_MAX_CONV];
         int wnf[SED_MAX_CONV], wnd[SED_MAX_CONV];
@@ -341,7 +347,12 @@ static int forward_impl(const sed_net_cfg* c, const sed_net_params* p, const flo
             w[l] = p->conv_w[l]; wf[l] = ws + L.wp_f[l]; wd[l] = (training && l > 0) ? ws + L.wp_d[l] : nullptr;
             co[l] = L.cv[l].C; ci[l] = L.cv[l].Cin; wnf[l] = L.cv[l].wino; wnd[l] = L.cv[l].wino_d;
         }
-        SED_TRY(sed_internal_conv_pack_multi(L.n_conv, w, wf, wd, co, ci, wnf, wnd, stream));
+        const float* whh[2 * SED_MAX_GRU]; float* whh_t[SED_MAX_GRU]; int gh[SED_MAX_GRU];
+        for (int i = 0; i < L.n_gru && gru_packed_up_front; ++i) {
+            SED_REQUIRE(p->gru_whh[i][0] && p->gru_whh[i][1], "net_forward: missing parameters of GRU layer %d", i);
+            whh[2 * i] = p->gru_whh[i][0]; whh[2 * i + 1] = p->gru_whh[i][1]; whh_t[i] = ws + L.gru_ws[i]; gh[i] = L.gr[i].H;
+        }
+        SED_TRY(sed_internal_conv_pack_multi_gru(L.n_conv, w, wf, wd, co, ci, wnf, wnd, gru_packed_up_front ? L.n_gru : 0, whh, whh_t, gh, stream));
     }
     for (int l = 0; l < L.n_conv && !eval_plan; ++l) {
         const ConvL& q = L.cv[l];
@@ -349,6 +360,9 @@ static int forward_impl(const sed_net_cfg* c, const sed_net_params* p, const flo
         const bool do_a = pb <= 2 * l && 2 * l < pe, do_b = pb <= 2 * l + 1 && 2 * l + 1 < pe;
         if (!do_a && !do_b) continue;
         const bool one_shot = do_a && do_b && count_scale == 1.f;      // unsynchronised: the fused finalise kernel
+        // a recomputed first block with 1 or 2 input channels: its statistics come as ONE row, and the single workgroup that
+        // forms it writes the BatchNorm coefficients and running statistics too (no bn_finalize_train launch behind it)
+        const bool stats_with_bn = training && one_shot && q.fused && q.Cin <= 2;
         SED_REQUIRE(p->conv_w[l] && p->conv_b[l] && p->bn_g[l] && p->bn_b[l] && p->bn_rm[l] && p->bn_rv[l],
                     "net_forward: missing parameters of conv block %d", l);
         if (do_a) {
@@ -361,8 +375,13 @@ static int forward_impl(const sed_net_cfg* c, const sed_net_params* p, const flo
                                                         q.C, q.Cin, (l > 0) ? c->conv_mode : 0, stream));
             }
             if (q.fused) {
-                if (training) SED_TRY(sed_conv1_stats(in, ws + L.wp_f[l], p->conv_b[l], ws + L.stat[l], ws + L.c1_stat_ws, B, q.Cin, q.F, q.T, q.C,
-                                                      q.rgrad ? (double*)(ws + L.c1_mom) : nullptr, stream));
+                if (training && stats_with_bn)
+                    SED_TRY(sed_internal_conv1_stats_bn(in, ws + L.wp_f[l], p->conv_b[l], ws + L.stat[l], ws + L.c1_stat_ws, B, q.Cin, q.F, q.T, q.C,
+                                                        q.rgrad ? (double*)(ws + L.c1_mom) : nullptr, p->bn_g[l], p->bn_b[l], p->bn_rm[l], p->bn_rv[l],
+                                                        c->bn_momentum, c->bn_eps, ws + L.mean[l], ws + L.rstd[l], ws + L.scale[l], ws + L.shift[l], stream));
+                else if (training)
+                    SED_TRY(sed_conv1_stats(in, ws + L.wp_f[l], p->conv_b[l], ws + L.stat[l], ws + L.c1_stat_ws, B, q.Cin, q.F, q.T, q.C,
+                                            q.rgrad ? (double*)(ws + L.c1_mom) : nullptr, stream));
             } else if (q.wino) {
                 SED_TRY(sed_conv3x3_wino_fwd(in, ws + L.wp_f[l], p->conv_b[l], ws + L.conv_out[l], training ? ws + L.stat[l] : nullptr,
                                              B, q.Cin, q.F, q.T, q.C, stream));
@@ -374,7 +393,9 @@ static int forward_impl(const sed_net_cfg* c, const sed_net_params* p, const flo
         }
         if (!do_b) continue;
         const double count = (double)B * q.T * q.F;
-        if (training && one_shot)
+        if (stats_with_bn) {
+            // (written by sed_internal_conv1_stats_bn above)
+        } else if (training && one_shot)
             SED_TRY(sed_bn_finalize_train(ws + L.stat[l], q.rows, q.C, count, p->bn_g[l], p->bn_b[l],
                                           p->bn_rm[l], p->bn_rv[l], c->bn_momentum, c->bn_eps, ws + L.mean[l],
                                           ws + L.rstd[l], ws + L.scale[l], ws + L.shift[l], stream));
@@ -428,8 +449,12 @@ static int forward_impl(const sed_net_cfg* c, const sed_net_params* p, const flo
         }
         const float* whh[2] = {p->gru_whh[i][0], p->gru_whh[i][1]};
         const float* bhh[2] = {p->gru_bhh[i][0], p->gru_bhh[i][1]};
-        SED_TRY(sed_gru_seq_fwd(ws + L.gi[i], whh, bhh, ws + L.gout[i], training ? ws + L.saved[i] : nullptr,
-                                ws + L.gru_ws, B, L.Tp, H, stream));
+        if (gru_packed_up_front)
+            SED_TRY(sed_internal_gru_seq_fwd_packed(ws + L.gi[i], ws + L.gru_ws[i], bhh, ws + L.gout[i], training ? ws + L.saved[i] : nullptr,
+                                                    B, L.Tp, H, stream));
+        else
+            SED_TRY(sed_gru_seq_fwd(ws + L.gi[i], whh, bhh, ws + L.gout[i], training ? ws + L.saved[i] : nullptr,
+                                    ws + L.gru_ws[i], B, L.Tp, H, stream));
         gin = ws + L.gout[i];
     }
     const float* din = gin;
@@ -492,6 +517,9 @@ extern "C" int sed_net_workspace_region(const sed_net_cfg* c, int training, cons
         if (is("gi")) { off = L.gi[index]; n = M * 6 * H; ok = true; }
         else if (is("gru_out")) { off = L.gout[index]; n = M * 2 * H; ok = true; }
         else if (is("dgru_out") && training) { off = L.dgout[index]; n = M * 2 * H; ok = true; }
+        // the per-layer scratch of the recurrences: W_hh^T of both directions, and the backward's bias-gradient partial sums
+        else if (is("gru_whh_t")) { off = L.gru_ws[index]; n = 6 * H * H; ok = true; }
+        else if (is("gru_bias_part") && training) { off = L.gru_bws[index]; n = sed_gru_seq_bwd_workspace_bytes(c->B, (int)H) / sizeof(float); ok = true; }
     }
     if (!ok && training && index == 0) {
         if (is("grad_act")) {           // the gradient w.r.t. the pooled output currently being back-propagated (reused per block)
@@ -649,8 +677,8 @@ extern "C" int sed_net_backward(const sed_net_cfg* c, const sed_net_params* p, c
     // [i]: recurrence of GRU layer i done (main); [SED_MAX_GRU]: the GRU weight gradients of the aux stream done;
     // [SED_MAX_GRU + 1]: data gradient of the top conv block issued (main); [SED_MAX_GRU + 2]: its weight gradient done (aux);
     // [SED_MAX_GRU + 3]: the zero rows of the weight-gradient workspaces cleared (aux); [SED_MAX_GRU + 4]: the fork of the
-    // auxiliary stream at the top of the call (main)
-    static thread_local hipEvent_t ev_gru_all[kMaxDev][SED_MAX_GRU + 5] = {};
+    // auxiliary stream at the top of the call (main); [SED_MAX_GRU + 5]: the data gradients of the dense head issued (main)
+    static thread_local hipEvent_t ev_gru_all[kMaxDev][SED_MAX_GRU + 6] = {};
     hipStream_t s_main = as_stream(stream), s_aux = as_stream(aux_stream);
     hipEvent_t* ev_dg = nullptr;
     hipEvent_t* ev_bn = nullptr;
@@ -664,7 +692,7 @@ extern "C" int sed_net_backward(const sed_net_cfg* c, const sed_net_params* p, c
         ev_dg = ev_all[dev][0];
         ev_bn = ev_all[dev][1];
         ev_gru = ev_gru_all[dev];
-        for (int i = 0; i < SED_MAX_GRU + 5; ++i)
+        for (int i = 0; i < SED_MAX_GRU + 6; ++i)
             if (!ev_gru[i] && hipEventCreateWithFlags(&ev_gru[i], hipEventDisableTiming) != hipSuccess) {
                 sed_set_error("net_backward: hipEventCreate failed");
                 return SED_EINVAL;
@@ -716,8 +744,24 @@ extern "C" int sed_net_backward(const sed_net_cfg* c, const sed_net_params* p, c
             float* dy = last ? const_cast<float*>(dlogits) : ws + L.dact[j];   // relu=0 on the last layer: not modified
             float* dx = (j == 0) ? ws + L.dgout[L.n_gru - 1] : ws + L.dact[j - 1];
             SED_REQUIRE(g->dense_w[j] && g->dense_b[j], "net_backward: missing gradient buffers of dense layer %d", j);
-            SED_TRY(sed_linear_bwd(xin, p->dense_w[j], last ? nullptr : ws + L.act[j], dy, dx, g->dense_w[j],
-                                   g->dense_b[j], ws + L.lin_ws, M, L.dK[j], L.dN[j], !last, stream));
+            if (s_aux)      // only the mask and the data gradient: the recurrence below waits for nothing else of the head
+                SED_TRY(sed_internal_linear_bwd_dx(p->dense_w[j], last ? nullptr : ws + L.act[j], dy, dx, M, L.dK[j], L.dN[j], !last, stream));
+            else
+                SED_TRY(sed_linear_bwd(xin, p->dense_w[j], last ? nullptr : ws + L.act[j], dy, dx, g->dense_w[j],
+                                       g->dense_b[j], ws + L.lin_ws, M, L.dK[j], L.dN[j], !last, stream));
+        }
+        if (s_aux) {
+            // The head's weight and bias gradients feed only the optimiser: on the auxiliary stream, behind the last mask of
+            // the chain above (they read the masked dy; nothing overwrites dy, the activations or lin_ws before the join at the
+            // end of this stage), beside the recurrence of the top GRU layer.  Same kernels, same order of summation.
+            (void)hipEventRecord(ev_gru[SED_MAX_GRU + 5], s_main);
+            (void)hipStreamWaitEvent(s_aux, ev_gru[SED_MAX_GRU + 5], 0);
+            for (int j = L.n_dense - 1; j >= 0; --j) {
+                const int last = (j == L.n_dense - 1);
+                const float* xin = (j == 0) ? gru_last : ws + L.act[j - 1];
+                const float* dy = last ? dlogits : ws + L.dact[j];
+                SED_TRY(sed_internal_linear_bwd_dw(xin, dy, g->dense_w[j], g->dense_b[j], ws + L.lin_ws, M, L.dK[j], L.dN[j], aux_stream));
+            }
         }
         // ── GRU stack ──
         for (int i = L.n_gru - 1; i >= 0; --i) {
@@ -732,7 +776,10 @@ extern "C" int sed_net_backward(const sed_net_cfg* c, const sed_net_params* p, c
                             "net_backward: missing gradient buffers of GRU layer %d dir %d", i, d);
             float* dbih[2] = {g->gru_bih[i][0], g->gru_bih[i][1]};
             float* dbhh[2] = {g->gru_bhh[i][0], g->gru_bhh[i][1]};
-            SED_TRY(sed_gru_seq_bwd(ws + L.dgout[i], ws + L.saved[i], whh, dgi, dgh, dbih, dbhh, ws + L.gru_bws, B, L.Tp, H, stream));
+            // with an auxiliary stream the recurrence only leaves its bias-gradient partial sums (its own region per layer);
+            // their reduction feeds nothing but the optimiser and runs there, see below
+            if (s_aux) SED_TRY(sed_internal_gru_seq_bwd_partials(ws + L.dgout[i], ws + L.saved[i], whh, dgi, dgh, ws + L.gru_bws[i], B, L.Tp, H, stream));
+            else SED_TRY(sed_gru_seq_bwd(ws + L.dgout[i], ws + L.saved[i], whh, dgi, dgh, dbih, dbhh, ws + L.gru_bws[i], B, L.Tp, H, stream));
             // Critical chain: recurrence(i) -> dX(i) -> recurrence(i-1) ...  The weight gradients hang off it: with an auxiliary
             // stream the small ones (dW_hh of every layer, dW_ih of the layers above the first) run there, beside the next
             // data-gradient GEMM / recurrence (which leaves most CUs idle), with their own split-K scratch.
@@ -741,9 +788,10 @@ extern "C" int sed_net_backward(const sed_net_cfg* c, const sed_net_params* p, c
             const bool on_aux = s_aux && i > 0;
             void* wst = on_aux ? aux_stream : stream;
             float* wws = ws + (on_aux ? L.gemm_ws_aux : L.gemm_ws);
-            if (on_aux) {
+            if (s_aux) {       // (layer 0 too: its bias gradients go to the auxiliary stream, its weight gradients do not)
                 (void)hipEventRecord(ev_gru[i], s_main);
                 (void)hipStreamWaitEvent(s_aux, ev_gru[i], 0);
+                SED_TRY(sed_internal_gru_bias_grad(ws + L.gru_bws[i], dbih, dbhh, B, H, aux_stream));
             }
             auto dw_hh = [&]() -> int {      // dW_hh = dgh^T h_prev (block-diagonal over the directions)
                 for (int d = 0; d < 2; ++d)

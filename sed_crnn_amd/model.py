@@ -474,7 +474,7 @@ class HipCRNN(nn.Module):
     def workspace_view(self, name, index=0):
         """A view of an intermediate of the LAST training forward / backward inside the plan's workspace
         (``sed_net_workspace_region``: "conv_out", "pooled", "mean", "rstd", "scale", "shift", "dconv", "gi", "gru_out",
-        "dgru_out", "grad_act", "bn_sums_bwd", "wgrad_zero_row").  Flat fp32; valid until the next forward of that shape.
+        "dgru_out", "gru_whh_t", "gru_bias_part", "grad_act", "bn_sums_bwd", "wgrad_zero_row").  Flat fp32; valid until the next forward of that shape.
         "grad_act" after a backward on the default plan holds the gradient of block 1's pooled output: the first block takes its
         sums from the epilogue of block 1's data gradient, which is then not written."""
         if self._last is None:
