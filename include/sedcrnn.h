@@ -640,6 +640,19 @@ int sed_event_mvdr(const float* pcm, long pcm_len, const long* clips_host, int R
                    int time_factor, int hop, int max_frames, const double* tau, int D, double loading, const void* tables,
                    size_t tables_bytes, const int* audio_len, const long* audio_start, float* audio, long audio_total,
                    void* workspace, size_t workspace_bytes, void* stream);
+/* sed_event_mvdr_ring: sed_event_mvdr on the PCM rings of live feeds, as sed_event_beamform_ring relates to
+ * sed_event_beamform: recording r is a feed that has received n_host[r] samples, its channel ch the ring of cap samples at
+ * (r*C + ch)*cap, sample i at i % cap while max(0, n - cap) <= i < n (sed_stream_ring_write); cap >= 2048, cap % 4 == 0,
+ * R*C*cap <= ring_len.  The spans are sed_event_beam_spans_ring's.  A sample outside what the ring still holds reads as 0.  An
+ * extracted event's audio is, bit for bit, what sed_event_mvdr gives on the feed's samples [0, n) laid out linearly, wherever
+ * the ring wraps.  workspace: at least sed_event_mvdr_ring_workspace_bytes(R, channels, max_frames, hop) — the table of the
+ * sample counts and one event's partials and weights. */
+size_t sed_event_mvdr_ring_workspace_bytes(int R, int channels, int max_frames, int hop);
+int sed_event_mvdr_ring(const float* ring, long ring_len, long cap, const long* n_host, int R, int channels, const int* ev_rec,
+                        const int* ev_onset, const int* ev_offset, const int* ev_peak_frame, const int* ev_dir,
+                        const int* ev_loc_frames, long E, int time_factor, int hop, int max_frames, const double* tau, int D,
+                        double loading, const void* tables, size_t tables_bytes, const int* audio_len, const long* audio_start,
+                        float* audio, long audio_total, void* workspace, size_t workspace_bytes, void* stream);
 
 /* sed_pcen: per-channel energy normalisation, IN PLACE, of the columns [col0, col0 + W) of x [rows][stride], which
  * hold log-mel values (natural log, as sed_logmel* write them without a scaler); the other columns are not touched.  Every column

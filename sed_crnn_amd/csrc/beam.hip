@@ -242,21 +242,6 @@ __global__ __launch_bounds__(BM_THREADS) void beam_sum_k(const float* __restrict
     for (int j = tid; j < cnt; j += BM_THREADS) dst[j] = lds[j];
 }
 
-size_t beam_ring_table_bytes(int R) { return ((size_t)R * sizeof(long) + 15) & ~(size_t)15; }
-
-int beam_ring_table(const char* who, const long* n_host, int R, int hop, std::vector<long>& h, long& longest) {
-    SED_REQUIRE(n_host, "%s: null pointer (the sample counts)", who);
-    h.assign((size_t)R, 0);
-    longest = 0;
-    for (int r = 0; r < R; ++r) {
-        h[r] = n_host[r];
-        SED_REQUIRE(h[r] >= 0 && 1 + h[r] / hop <= 0x7fffffffL, "%s: feed %d: %ld samples received (negative, or more than "
-                    "2^31 - 1 feature frames)", who, r, h[r]);
-        if (h[r] > longest) longest = h[r];
-    }
-    return 0;
-}
-
 int beam_spans(const char* who, bool ring, const std::vector<long>& h, size_t tab, int R, int channels, const int* ev_rec,
                const int* ev_onset, const int* ev_offset, const int* ev_peak, const int* ev_dir, const int* ev_loc, long E,
                int time_factor, int hop, int max_frames, int D, int* len_out, long* start_out, long* total_out, void* workspace,

@@ -1,7 +1,8 @@
 // beam_shared.h — what the two ways to extract a located event's audio share: the delay-and-sum beam (beam.hip) and the
 // adaptive MVDR beam (mvdr.hip).  Device code: the rule that gives an event its samples, so that both extract the SAME
 // samples and both agree with sed_event_beam_spans.  Host code: the checks of the event columns and of the recordings of a linear
-// call, the recording table (sample_off [R*C] and n_samples [R], 64-bit) at the head of the workspace and its upload.
+// call, the recording table (sample_off [R*C] and n_samples [R], 64-bit; a ring call: n_samples [R] alone) at the head of the
+// workspace and its upload.
 #pragma once
 #include <vector>
 #include "common.h"
@@ -66,6 +67,22 @@ int beam_linear_table(const char* who, long pcm_len, const long* clips_host, int
         slen[r] = n0;
         SED_REQUIRE(1 + n0 / hop <= 0x7fffffffL, "%s: recording %d has more than 2^31 - 1 feature frames", who, r);
         if (n0 > longest) longest = n0;
+    }
+    return 0;
+}
+
+// the recordings of a ring call (live feeds): h = n_samples [R], the samples every feed has received
+size_t beam_ring_table_bytes(int R) { return ((size_t)R * sizeof(long) + 15) & ~(size_t)15; }
+
+int beam_ring_table(const char* who, const long* n_host, int R, int hop, std::vector<long>& h, long& longest) {
+    SED_REQUIRE(n_host, "%s: null pointer (the sample counts)", who);
+    h.assign((size_t)R, 0);
+    longest = 0;
+    for (int r = 0; r < R; ++r) {
+        h[r] = n_host[r];
+        SED_REQUIRE(h[r] >= 0 && 1 + h[r] / hop <= 0x7fffffffL, "%s: feed %d: %ld samples received (negative, or more than "
+                    "2^31 - 1 feature frames)", who, r, h[r]);
+        if (h[r] > longest) longest = h[r];
     }
     return 0;
 }

@@ -1,4 +1,5 @@
-// mvdr.hip — the audio of every located event through an adaptive (MVDR) beam: sed_event_mvdr.
+// mvdr.hip — the audio of every located event through an adaptive (MVDR) beam: sed_event_mvdr, and on the PCM rings
+// of live feeds sed_event_mvdr_ring.
 //
 // The events, their samples [s0, s1) and the packed output (audio_len, audio_start) are sed_event_beam_spans' (beam_shared.h).  The
 // transform grid is the event's own: N = 2048, B = 1024, len = s1 - s0, J = ceil(len / B); frame j = 0..J holds
@@ -27,6 +28,11 @@
 //                   combines the new spectra with w from the workspace into the next Y.  Two barriers per frame.
 // A frame inside [s0, s1) on an 8-byte boundary takes tdoa_accum_k's direct loads; frames 0 and J, which reach outside the event,
 // and unaligned events go through fft_load_guarded: the same samples.
+//
+// Live feeds: sed_event_mvdr_ring is the same three launches with mvdr_ring_cov_k and mvdr_ring_apply_k, the same
+// bodies with the frame loaded from the feed's PCM rings (sed_stream_ring_write; TdArgs.cap) — directly where the frame does not
+// wrap, through the guarded loads with the index taken modulo cap where it does — so the registers hold the samples the linear
+// call loads and everything after the loads is one code: the same bits.  The weight kernel reads no PCM and has no ring form.
 #include <math.h>
 #include <vector>
 #include "common.h"
@@ -90,8 +96,47 @@ __device__ __forceinline__ void mv_load_frame(f2 (&z)[32], const float* __restri
     }
 }
 
-__global__ __launch_bounds__(MV_THREADS) void mvdr_cov_k(const float* __restrict__ pcm, const uint32_t* __restrict__ tables,
-                                                         float2* __restrict__ ws, TdArgs ta, MvArgs ma) {
+// ... of a live feed: lane = the channel's ring of cap samples, sample i of the feed at lane[i % cap] while kept <= i < n (the
+// event ends at or before n: bm_event_span).  A frame inside the event and inside what the ring holds that does not wrap and
+// starts on an 8-byte boundary takes the same 32 loads; every other frame — 0 and J, one that straddles the wrap point, an odd
+// s0 — the guarded ones, with the index taken modulo cap: the registers hold the same samples either way.
+__device__ __forceinline__ void mv_load_frame_ring(f2 (&z)[32], const float* __restrict__ lane, long cap, long kept, long s0, int len,
+                                                   int j, float* scr, const FftLane& fl) {
+    const long first = (long)(j - 1) * MV_B;
+    long pos = (s0 + first) % cap;                               // the frame's first sample in the ring (s0 + first >= -B)
+    if (pos < 0) pos += cap;
+    const bool fast = first >= 0 && first + LM_NFFT <= len && s0 + first >= kept && pos + LM_NFFT <= cap &&
+                      (reinterpret_cast<uintptr_t>(lane + pos) & 7) == 0;
+    if (__all(fast)) {
+        const f2* src = reinterpret_cast<const f2*>(lane + pos) + fl.r();
+#pragma unroll
+        for (int n1 = 0; n1 < 32; ++n1) z[n1] = src[32 * n1];
+    } else {
+        fft_load_guarded(z, scr, fl, [&](int off) -> float {
+            const long i = first + off, p = pos + off;           // (cap >= 2048: p < 2 cap)
+            return i >= 0 && i < len && s0 + i >= kept ? lane[p >= cap ? p - cap : p] : 0.f;
+        });
+    }
+}
+
+// frame j of channel ch of the event at s0 of recording rec: RING = false from the planar PCM, RING = true from the feed's rings
+template <bool RING>
+__device__ __forceinline__ void mv_load(f2 (&z)[32], const float* __restrict__ pcm, const TdArgs& ta, int rec, int ch, long s0, int len,
+                                        int j, float* scr, const FftLane& fl) {
+    if (RING) {
+        const long n = ta.n_samples[rec];
+        mv_load_frame_ring(z, pcm + ((long)rec * ta.C + ch) * ta.cap, ta.cap, n > ta.cap ? n - ta.cap : 0, s0, len, j, scr, fl);
+    } else {
+        mv_load_frame(z, pcm + ta.sample_off[(long)rec * ta.C + ch] + s0, len, j, scr, fl);
+    }
+}
+
+// The bodies of the covariance and the apply kernels, once for the planar PCM (mvdr_cov_k, mvdr_apply_k) and once for the rings
+// of live feeds (mvdr_ring_cov_k, mvdr_ring_apply_k): two kernels each, not one with a run-time branch, so that the linear
+// kernels compile to what they were before the rings existed; only mv_load differs.
+template <bool RING>
+__device__ __forceinline__ void mv_cov_body(const float* __restrict__ pcm, const uint32_t* __restrict__ tables, float2* __restrict__ ws,
+                                            TdArgs ta, MvArgs ma) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x;
     const long e = ta.e0 + blockIdx.y;
@@ -127,9 +172,8 @@ __global__ __launch_bounds__(MV_THREADS) void mvdr_cov_k(const float* __restrict
             if (wave < nfw) {
                 // the frame of channel 2 wave + half (an odd C: the last half wave repeats channel C-1 and stores the same values)
                 const int ch = (2 * wave + half < C) ? 2 * wave + half : C - 1;
-                const float* ev = pcm + ta.sample_off[(long)rec * C + ch] + s0;
                 f2 z[32];
-                mv_load_frame(z, ev, len, j, scr, fl);
+                mv_load<RING>(z, pcm, ta, rec, ch, s0, len, j, scr, fl);
                 fft2048_passes(z, fl, s_win, s_tw);
                 fft2048_spectrum(z, fl, s_pw, s_spec + ch * PHAT_SPEC);
             }
@@ -156,6 +200,16 @@ __global__ __launch_bounds__(MV_THREADS) void mvdr_cov_k(const float* __restrict
         }
         __syncthreads();                                         // the accumulators are zeroed for the next batch
     }
+}
+
+__global__ __launch_bounds__(MV_THREADS) void mvdr_cov_k(const float* __restrict__ pcm, const uint32_t* __restrict__ tables,
+                                                         float2* __restrict__ ws, TdArgs ta, MvArgs ma) {
+    mv_cov_body<false>(pcm, tables, ws, ta, ma);
+}
+
+__global__ __launch_bounds__(MV_THREADS) void mvdr_ring_cov_k(const float* __restrict__ ring, const uint32_t* __restrict__ tables,
+                                                              float2* __restrict__ ws, TdArgs ta, MvArgs ma) {
+    mv_cov_body<true>(ring, tables, ws, ta, ma);
 }
 
 // Every thread works in its own column of the three arrays: no thread reads what another writes, and there is no barrier.
@@ -262,8 +316,9 @@ __global__ __launch_bounds__(MV_WT) void mvdr_weights_k(float2* __restrict__ ws,
     for (int c = 0; c < C; ++c) wout[(long)c * PHAT_SPEC + k] = make_float2((float)(s_v[c][tid].x * scale), (float)(s_v[c][tid].y * scale));
 }
 
-__global__ __launch_bounds__(MV_THREADS) void mvdr_apply_k(const float* __restrict__ pcm, const uint32_t* __restrict__ tables,
-                                                           const float2* __restrict__ ws, float* __restrict__ audio, TdArgs ta, MvArgs ma) {
+template <bool RING>
+__device__ __forceinline__ void mv_apply_body(const float* __restrict__ pcm, const uint32_t* __restrict__ tables,
+                                              const float2* __restrict__ ws, float* __restrict__ audio, TdArgs ta, MvArgs ma) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x;
     const long e = ta.e0 + blockIdx.y;
@@ -301,9 +356,8 @@ __global__ __launch_bounds__(MV_THREADS) void mvdr_apply_k(const float* __restri
     for (int j = b0; j <= b1 + 1; ++j) {
         if (wave < nfw && j <= b1) {
             const int ch = (2 * wave + half < C) ? 2 * wave + half : C - 1;
-            const float* ev = pcm + ta.sample_off[(long)rec * C + ch] + s0;
             f2 z[32];
-            mv_load_frame(z, ev, len, j, scr, fl);
+            mv_load<RING>(z, pcm, ta, rec, ch, s0, len, j, scr, fl);
             fft2048_passes(z, fl, s_win, s_tw);
             fft2048_spectrum(z, fl, s_pw, s_spec + ch * PHAT_SPEC);
         } else if (wave == nfw && j > b0) {                      // (both halves transform the same Y_{j-1}; one stores)
@@ -339,6 +393,17 @@ __global__ __launch_bounds__(MV_THREADS) void mvdr_apply_k(const float* __restri
     }
 }
 
+__global__ __launch_bounds__(MV_THREADS) void mvdr_apply_k(const float* __restrict__ pcm, const uint32_t* __restrict__ tables,
+                                                           const float2* __restrict__ ws, float* __restrict__ audio, TdArgs ta, MvArgs ma) {
+    mv_apply_body<false>(pcm, tables, ws, audio, ta, ma);
+}
+
+__global__ __launch_bounds__(MV_THREADS) void mvdr_ring_apply_k(const float* __restrict__ ring, const uint32_t* __restrict__ tables,
+                                                                const float2* __restrict__ ws, float* __restrict__ audio, TdArgs ta,
+                                                                MvArgs ma) {
+    mv_apply_body<true>(ring, tables, ws, audio, ta, ma);
+}
+
 // rows of 1026 float2 per event: the chunk partials of every entry of the triangle, then w
 long mv_chunks(int max_frames, int hop) {
     const long J = ((long)max_frames * hop + MV_B - 1) / MV_B;   // no event has more output blocks
@@ -352,25 +417,18 @@ size_t mv_apply_lds(int C) {
     return ((size_t)MV_TAB_WORDS + (size_t)C * PHAT_SPEC * 2 + (size_t)((C + 1) / 2 + 1) * MV_FFT_SCR + PHAT_SPEC * 2 + LM_NFFT + MV_B) * sizeof(float);
 }
 
-}  // namespace
-
-extern "C" size_t sed_event_mvdr_workspace_bytes(int R, int channels, int max_frames, int hop) {
-    if (R < 1 || channels < 2 || channels > TD_MAX_CH || max_frames < 1 || hop < 1 || (long)max_frames * hop > 0x7fffffffL) return 0;
-    return beam_table_bytes(R, channels) + mv_event_bytes(channels, mv_chunks(max_frames, hop));
+bool mv_sizes_ok(int R, int channels, int max_frames, int hop) {
+    return R >= 1 && channels >= 2 && channels <= TD_MAX_CH && max_frames >= 1 && hop >= 1 && (long)max_frames * hop <= 0x7fffffffL;
 }
 
-extern "C" int sed_event_mvdr(const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const int* ev_rec,
-                              const int* ev_onset, const int* ev_offset, const int* ev_peak_frame, const int* ev_dir,
-                              const int* ev_loc_frames, long E, int time_factor, int hop, int max_frames, const double* tau, int D,
-                              double loading, const void* tables, size_t tables_bytes, const int* audio_len, const long* audio_start,
-                              float* audio, long audio_total, void* workspace, size_t workspace_bytes, void* stream) {
-    const char* who = "mvdr";
-    SED_TRY(beam_check_events(who, R, channels, ev_rec, ev_onset, ev_offset, ev_peak_frame, ev_dir, ev_loc_frames, E, time_factor, hop,
-                              max_frames, D));
-    SED_REQUIRE(pcm, "%s: null pointer (the samples)", who);
-    std::vector<long> h;
-    long longest;
-    SED_TRY(beam_linear_table(who, pcm_len, clips_host, R, channels, hop, h, longest));
+// what both entries do once the events and the recordings are checked: h = the recording table (tab bytes at the head of the
+// workspace), pcm = the planar PCM (RING: the rings, cap samples each)
+template <bool RING>
+int mv_run(const char* who, const float* pcm, const std::vector<long>& h, size_t tab, long longest, long cap, int R, int channels,
+           const int* ev_rec, const int* ev_onset, const int* ev_offset, const int* ev_peak_frame, const int* ev_dir,
+           const int* ev_loc_frames, long E, int time_factor, int hop, int max_frames, const double* tau, int D, double loading,
+           const void* tables, size_t tables_bytes, const int* audio_len, const long* audio_start, float* audio, long audio_total,
+           void* workspace, size_t workspace_bytes, void* stream) {
     SED_REQUIRE(loading >= 1e-6 && loading <= 1e6, "%s: loading must be in [1e-6, 1e6], got %g", who, loading);
     SED_REQUIRE(audio_total >= 0, "%s: a total of %ld samples", who, audio_total);
     SED_REQUIRE(E == 0 || (tau && audio_len && audio_start), "%s: null pointer (tau, audio_len or audio_start)", who);
@@ -380,7 +438,6 @@ extern "C" int sed_event_mvdr(const float* pcm, long pcm_len, const long* clips_
     SED_REQUIRE(((uintptr_t)pcm & 3) == 0, "%s: the samples must be 4-byte aligned", who);
     if (E == 0 || audio_total == 0) return 0;                    // nothing to launch
     const int C = channels, T = C * (C + 1) / 2;
-    const size_t tab = beam_table_bytes(R, C);
     const long cpe = mv_chunks(max_frames, hop);
     const size_t per_event = mv_event_bytes(C, cpe);
     SED_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0, "%s: the workspace must be a 16-byte aligned device buffer", who);
@@ -402,21 +459,74 @@ extern "C" int sed_event_mvdr(const float* pcm, long pcm_len, const long* clips_
 
     hipStream_t s = as_stream(stream);
     SED_TRY(beam_upload(who, h, tab, workspace, workspace_bytes, s));
-    hipError_t err = hipFuncSetAttribute((const void*)mvdr_cov_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MV_LDS_MAX);
-    if (err == hipSuccess) err = hipFuncSetAttribute((const void*)mvdr_apply_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MV_LDS_MAX);
+    const auto cov_k = RING ? mvdr_ring_cov_k : mvdr_cov_k;
+    const auto apply_k = RING ? mvdr_ring_apply_k : mvdr_apply_k;
+    hipError_t err = hipFuncSetAttribute((const void*)cov_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MV_LDS_MAX);
+    if (err == hipSuccess) err = hipFuncSetAttribute((const void*)apply_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MV_LDS_MAX);
     if (err != hipSuccess) { sed_set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(err)); return (int)err; }
-    TdArgs ta = beam_args(false, workspace, R, C, ev_rec, ev_onset, ev_offset, ev_peak_frame, time_factor, hop, max_frames, 0);
+    TdArgs ta = beam_args(RING, workspace, R, C, ev_rec, ev_onset, ev_offset, ev_peak_frame, time_factor, hop, max_frames, cap);
     const MvArgs ma{ev_dir, ev_loc_frames, D, audio_len, audio_start, audio_total, (int)cpe, (int)(cpe * T + C), batch};
     float2* part = (float2*)((char*)workspace + tab);
     for (long e0 = 0; e0 < E; e0 += slice) {
         ta.e0 = e0;
         ta.n_ev = (int)(E - e0 < slice ? E - e0 : slice);
-        mvdr_cov_k<<<dim3(chunks, (unsigned)ta.n_ev), MV_THREADS, lds_cov, s>>>(pcm, (const uint32_t*)tables, part, ta, ma);
+        cov_k<<<dim3(chunks, (unsigned)ta.n_ev), MV_THREADS, lds_cov, s>>>(pcm, (const uint32_t*)tables, part, ta, ma);
         SED_LAUNCH_CHECK("mvdr (covariance)");
         mvdr_weights_k<<<dim3((LM_N + MV_WT) / MV_WT, (unsigned)ta.n_ev), MV_WT, 0, s>>>(part, tau, loading, ta, ma);
         SED_LAUNCH_CHECK("mvdr (weights)");
-        mvdr_apply_k<<<dim3(runs, (unsigned)ta.n_ev), MV_THREADS, lds_apply, s>>>(pcm, (const uint32_t*)tables, part, audio, ta, ma);
+        apply_k<<<dim3(runs, (unsigned)ta.n_ev), MV_THREADS, lds_apply, s>>>(pcm, (const uint32_t*)tables, part, audio, ta, ma);
         SED_LAUNCH_CHECK("mvdr (apply)");
     }
     return 0;
+}
+
+}  // namespace
+
+extern "C" size_t sed_event_mvdr_workspace_bytes(int R, int channels, int max_frames, int hop) {
+    if (!mv_sizes_ok(R, channels, max_frames, hop)) return 0;
+    return beam_table_bytes(R, channels) + mv_event_bytes(channels, mv_chunks(max_frames, hop));
+}
+
+extern "C" size_t sed_event_mvdr_ring_workspace_bytes(int R, int channels, int max_frames, int hop) {
+    if (!mv_sizes_ok(R, channels, max_frames, hop)) return 0;
+    return beam_ring_table_bytes(R) + mv_event_bytes(channels, mv_chunks(max_frames, hop));
+}
+
+extern "C" int sed_event_mvdr(const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const int* ev_rec,
+                              const int* ev_onset, const int* ev_offset, const int* ev_peak_frame, const int* ev_dir,
+                              const int* ev_loc_frames, long E, int time_factor, int hop, int max_frames, const double* tau, int D,
+                              double loading, const void* tables, size_t tables_bytes, const int* audio_len, const long* audio_start,
+                              float* audio, long audio_total, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "mvdr";
+    SED_TRY(beam_check_events(who, R, channels, ev_rec, ev_onset, ev_offset, ev_peak_frame, ev_dir, ev_loc_frames, E, time_factor, hop,
+                              max_frames, D));
+    SED_REQUIRE(pcm, "%s: null pointer (the samples)", who);
+    std::vector<long> h;
+    long longest;
+    SED_TRY(beam_linear_table(who, pcm_len, clips_host, R, channels, hop, h, longest));
+    return mv_run<false>(who, pcm, h, beam_table_bytes(R, channels), longest, 0, R, channels, ev_rec, ev_onset, ev_offset, ev_peak_frame,
+                         ev_dir, ev_loc_frames, E, time_factor, hop, max_frames, tau, D, loading, tables, tables_bytes, audio_len,
+                         audio_start, audio, audio_total, workspace, workspace_bytes, stream);
+}
+
+extern "C" int sed_event_mvdr_ring(const float* ring, long ring_len, long cap, const long* n_host, int R, int channels, const int* ev_rec,
+                                   const int* ev_onset, const int* ev_offset, const int* ev_peak_frame, const int* ev_dir,
+                                   const int* ev_loc_frames, long E, int time_factor, int hop, int max_frames, const double* tau, int D,
+                                   double loading, const void* tables, size_t tables_bytes, const int* audio_len,
+                                   const long* audio_start, float* audio, long audio_total, void* workspace, size_t workspace_bytes,
+                                   void* stream) {
+    const char* who = "mvdr_ring";
+    SED_TRY(beam_check_events(who, R, channels, ev_rec, ev_onset, ev_offset, ev_peak_frame, ev_dir, ev_loc_frames, E, time_factor, hop,
+                              max_frames, D));
+    SED_REQUIRE(ring, "%s: null pointer (the rings)", who);
+    SED_REQUIRE(cap >= LM_NFFT && cap % 4 == 0, "%s: a ring holds a multiple of 4 samples and at least one frame of %d, got cap=%ld", who,
+                LM_NFFT, cap);
+    SED_REQUIRE(ring_len >= 0 && cap <= ring_len / ((long)R * channels), "%s: %d feeds of %d rings of %ld samples leave the buffer "
+                "of %ld", who, R, channels, cap, ring_len);
+    std::vector<long> h;
+    long longest;
+    SED_TRY(beam_ring_table(who, n_host, R, hop, h, longest));
+    return mv_run<true>(who, ring, h, beam_ring_table_bytes(R), longest, cap, R, channels, ev_rec, ev_onset, ev_offset, ev_peak_frame,
+                        ev_dir, ev_loc_frames, E, time_factor, hop, max_frames, tau, D, loading, tables, tables_bytes, audio_len,
+                        audio_start, audio, audio_total, workspace, workspace_bytes, stream);
 }

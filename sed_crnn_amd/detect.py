@@ -351,8 +351,9 @@ class EventDetector:
     also comes with its audio, the array pointed at ``dir`` by a delay-and-sum beam (``feature.event_beamform`` on the PCM that
     is kept anyway): ``audio_start`` / ``audio_len`` [E] in the events, the packed float32 buffer ``result.audio`` and
     ``result.event_audio(e)``; ``from_features*`` returns events without audio, ``det.localize`` adds it, ``det.stream`` of such a
-    detector is not implemented.  ``extract=sed.MVDR(loading)`` instead: the same events, samples and results through
-    an adaptive beam that suppresses what else the event's frames contain (``feature.event_mvdr``)."""
+    detector takes ``history_frames=`` and ``emit_audio=True`` and emits the same audio on live feeds.
+    ``extract=sed.MVDR(loading)`` instead: the same events, samples and results through an adaptive beam that
+    suppresses what else the event's frames contain (``feature.event_mvdr``; live feeds: ``feature.event_mvdr_ring``)."""
 
     def __init__(self, model, seq_len=SEQ_LEN_IN, hop=None, combine="mean", trim=0, threshold=0.5, low=None, median=1,
                  min_gap=0, min_len=1, mean=None, std=None, sr=feature.SR, hop_length=feature.HOP, max_batch=1024, spatial=None,
@@ -450,7 +451,10 @@ class EventDetector:
         """a ``stream.StreamDetector`` for ``n_streams`` live feeds with this detector's settings; ``input_sr`` /
         ``input_channels``: what ``push`` receives.  A localising detector streams with ``history_frames="min"`` or a
         number of feature frames: the audio every feed keeps for its emitted events; without it, NotImplementedError.  A detector with
-        ``extract=`` does not stream yet: NotImplementedError."""
+        ``extract=`` streams with ``emit_audio=True``: every located event comes with its audio, the offline call's
+        bit for bit (``StreamEvents.audio`` / ``event_audio``), for one more blocking 8-byte read and one device allocation per
+        step that emits events; without ``emit_audio=True`` it raises NotImplementedError, and ``emit_audio=True`` on a detector
+        without ``extract=`` ValueError."""
         from .stream import StreamDetector
         return StreamDetector(self.model, n_streams, keep_probs=keep_probs, _det=self, **kw)
 

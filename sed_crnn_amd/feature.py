@@ -758,28 +758,34 @@ def event_mvdr(pcm, clips, channels, events, time_factor, doa, mvdr, sr=SR, hop=
     cols, E = _located_cols(events, R, "rec", dev)
     if E == 0:
         return _beam_empty(dev)
+    pcm = pcm.contiguous().float()
+    need_one = lib().sed_event_mvdr_workspace_bytes(R, nc, doa.max_frames, hop)
+    if need_one == 0:
+        raise ValueError(f"sed_event_mvdr_workspace_bytes refuses R={R}, channels={nc}, max_frames={doa.max_frames}, hop={hop}")
+    head = ([ptr(pcm)], [pcm.numel(), C.c_void_p(table.ctypes.data), R, nc])
+    return _mvdr_run(("sed_event_beam_spans", "sed_event_mvdr"), head, cols, E, tf, hop, doa, mvdr, sr,
+                     lib().sed_event_beam_workspace_bytes(R, nc), need_one, max_workspace_bytes, dev)
+
+
+def _mvdr_run(names, head, cols, E, tf, hop, doa, mvdr, sr, need_tab, need_one, max_workspace_bytes, dev):
+    """the two calls of an MVDR entry, linear or ring: the spans, ONE blocking read of the total (8 bytes) to size ``audio``, the
+    beam; ``need_tab`` / ``need_one``: the workspace bytes of the recording table alone and with one event"""
     key = (dev.index or 0, float(sr))
     if key not in doa._steering_device:
         doa._steering_device[key] = torch.from_numpy(doa.steering(sr)).to(dev)
     tau = doa._steering_device[key]
     tables = _mvdr_tables(dev.index or 0)
-    pcm = pcm.contiguous().float()
-    head = [pcm.numel(), C.c_void_p(table.ctypes.data), R, nc]
     out = {"audio_start": torch.empty(E, dtype=torch.int64, device=dev), "audio_len": torch.empty(E, dtype=torch.int32, device=dev)}
     total = torch.empty(1, dtype=torch.int64, device=dev)
-    need_tab = lib().sed_event_beam_workspace_bytes(R, nc)
-    need_one = lib().sed_event_mvdr_workspace_bytes(R, nc, doa.max_frames, hop)
-    if need_one == 0:
-        raise ValueError(f"sed_event_mvdr_workspace_bytes refuses R={R}, channels={nc}, max_frames={doa.max_frames}, hop={hop}")
     per_event = need_one - need_tab
     ws = torch.empty(min(need_tab + E * per_event, max(need_one, int(max_workspace_bytes))), dtype=torch.uint8, device=dev)
-    check(lib().sed_event_beam_spans(*head, *cols, E, tf, hop, doa.max_frames, tau.shape[0], ptr(out["audio_len"]),
-                                     ptr(out["audio_start"]), ptr(total), ptr(ws), ws.numel(), stream_ptr()), "sed_event_beam_spans")
+    check(getattr(lib(), names[0])(*head[1], *cols, E, tf, hop, doa.max_frames, tau.shape[0], ptr(out["audio_len"]),
+                                   ptr(out["audio_start"]), ptr(total), ptr(ws), ws.numel(), stream_ptr()), names[0])
     n_total = int(total.item())                                       # the one blocking read
     out["audio"] = torch.empty(n_total, device=dev)
-    check(lib().sed_event_mvdr(ptr(pcm), *head, *cols, E, tf, hop, doa.max_frames, ptr(tau), tau.shape[0], mvdr.loading, ptr(tables),
-                               tables.numel() * 4, ptr(out["audio_len"]), ptr(out["audio_start"]), ptr(out["audio"]), n_total, ptr(ws),
-                               ws.numel(), stream_ptr()), "sed_event_mvdr")
+    check(getattr(lib(), names[1])(*head[0], *head[1], *cols, E, tf, hop, doa.max_frames, ptr(tau), tau.shape[0], mvdr.loading,
+                                   ptr(tables), tables.numel() * 4, ptr(out["audio_len"]), ptr(out["audio_start"]), ptr(out["audio"]),
+                                   n_total, ptr(ws), ws.numel(), stream_ptr()), names[1])
     return out
 
 
@@ -839,6 +845,45 @@ def event_beamform_ring(ring, cap, n, channels, events, time_factor, doa, beam, 
     head = ([ptr(ring), ring.numel(), cap], [C.c_void_p(n.ctypes.data), R, nc])
     return _beam_run(("sed_event_beam_spans_ring", "sed_event_beamform_ring"), head, cols, E, tf, hop, plan,
                      lib().sed_event_beam_ring_workspace_bytes(R), dev)
+
+
+def event_mvdr_ring(ring, cap, n, channels, events, time_factor, doa, mvdr, sr=SR, hop=HOP, max_workspace_bytes=128 << 20):
+    """``event_mvdr`` on the PCM rings of live feeds (``sed_event_beam_spans_ring`` + ``sed_event_mvdr_ring``): ``ring`` /
+    ``cap`` / ``n`` / ``events`` as ``event_beamform_ring`` takes them (an event the stream's rule or the ring's depth refused
+    has ``dir = -1`` and length 0 here; the feed of an event is its ``rec`` — or ``stream`` — column), ``mvdr`` and
+    ``max_workspace_bytes`` as ``event_mvdr``.  An extracted event gets, bit for bit, what ``event_mvdr`` gives on the feed's
+    samples ``[0, n)`` laid out linearly, wherever the ring wraps and whatever the slicing; a sample the ring no longer holds
+    reads as 0.  Returns what ``event_mvdr`` returns, with the same single 8-byte read; ``E == 0`` returns empty tensors without
+    a launch."""
+    import ctypes as C
+    from .localize import MVDR
+    if not (isinstance(ring, torch.Tensor) and ring.is_cuda and ring.dim() == 1 and ring.dtype == torch.float32 and ring.is_contiguous()):
+        raise RuntimeError("sed_crnn_amd.feature.event_mvdr_ring needs a contiguous 1-D float32 CUDA(HIP) ring buffer; there is no CPU fallback")
+    nc, tf, hop, cap = int(channels), int(time_factor), int(hop), int(cap)
+    if not 2 <= nc <= GCC_MAX_CHANNELS or tf < 1 or hop < 1:
+        raise ValueError(f"event_mvdr_ring needs 2 to {GCC_MAX_CHANNELS} audio channels, time_factor >= 1 and hop >= 1, got "
+                         f"channels={nc}, time_factor={tf}, hop={hop}")
+    n = np.ascontiguousarray(np.asarray(n, dtype=np.int64).reshape(-1))
+    R = n.shape[0]
+    if R < 1 or (n < 0).any():
+        raise ValueError(f"n must hold one sample count >= 0 per feed, got {n.tolist()[:8]}")
+    if cap < NFFT or cap % 4 or R * nc * cap > ring.numel():
+        raise ValueError(f"{R} feeds of {nc} rings of cap={cap} samples (a multiple of 4, at least {NFFT}) do not fit the ring buffer of "
+                         f"{ring.numel()} samples")
+    _doa_plan(doa, nc, sr)
+    if not isinstance(mvdr, MVDR):
+        raise TypeError(f"event_mvdr_ring takes the beam settings as a sed.MVDR(...) object, got {type(mvdr).__name__}")
+    dev = ring.device
+    rec_key = "stream" if "stream" in events and "rec" not in events else "rec"
+    cols, E = _located_cols(events, R, rec_key, dev)
+    if E == 0:
+        return _beam_empty(dev)
+    need_one = lib().sed_event_mvdr_ring_workspace_bytes(R, nc, doa.max_frames, hop)
+    if need_one == 0:
+        raise ValueError(f"sed_event_mvdr_ring_workspace_bytes refuses R={R}, channels={nc}, max_frames={doa.max_frames}, hop={hop}")
+    head = ([ptr(ring), ring.numel(), cap], [C.c_void_p(n.ctypes.data), R, nc])
+    return _mvdr_run(("sed_event_beam_spans_ring", "sed_event_mvdr_ring"), head, cols, E, tf, hop, doa, mvdr, sr,
+                     lib().sed_event_beam_ring_workspace_bytes(R), need_one, max_workspace_bytes, dev)
 
 
 def pack_clips(waves, device):

@@ -43,6 +43,10 @@ locates them from the rings in one ``sed_event_tdoa_ring`` call — an event ``[
 <= history_frames`` (``localize.stream_locates``), with the bits of the offline call; ``flush`` / ``reset`` need no ring work either.
 With ``localize=sed.DOA(...)`` that call is ``sed_event_doa_ring`` and the events also carry ``dir`` and ``doa_power``
 (``StreamEvents.doa()``); an event the rule refuses has ``dir = -1``.
+With ``extract=sed.DelaySum(...)`` or ``sed.MVDR(...)`` and ``emit_audio=True`` a step that emitted events makes one
+more call on the same rings, ``feature.event_beamform_ring`` or ``feature.event_mvdr_ring``: the events carry ``audio_start`` and
+``audio_len`` and the call's ``StreamEvents.audio`` holds every located event's audio, the offline call's bit for bit.  Nothing
+of it persists between calls: the steps of one push hand their buffers to ``merge_step_audio``.
 """
 import ctypes as C
 
@@ -51,7 +55,8 @@ import torch
 
 from . import feature
 from ._lib import SedHipError, check, lib, ptr, stream_ptr
-from .detect import _DOA_KEYS, _TDOA_KEYS, EventDetector, _doa_angles, _event_tensors, _intervals, _timed, _window_jobs, plan_windows
+from .detect import (_BEAM_KEYS, _DOA_KEYS, _TDOA_KEYS, EventDetector, _doa_angles, _event_audio, _event_tensors, _intervals, _timed,
+                     _window_jobs, plan_windows)
 
 _KEYS = ("stream", "cls", "onset", "offset", "peak", "peak_frame")
 
@@ -59,6 +64,17 @@ _KEYS = ("stream", "cls", "onset", "offset", "peak", "peak_frame")
 def _excl(x):
     """exclusive prefix sums"""
     return np.cumsum(x) - x
+
+
+def merge_step_audio(parts):
+    """The extracted audio of several steps of one call as one table.  ``parts``: per step, in step order,
+    ``(audio float32 [n_i], audio_start int64 [E_i], audio_len int32 [E_i])`` — tensors on one device, host or GPU — where the
+    slices of a step are disjoint and cover its ``audio``.  -> ``(audio, audio_start, audio_len)``: the buffers back to back and
+    every step's ``audio_start`` moved by the samples of the steps before it, so the slices stay disjoint and cover the joined
+    buffer; lengths, zero ones included, are unchanged.  The host knows every ``n_i`` already: nothing is read back."""
+    base = _excl(np.asarray([int(p[0].numel()) for p in parts], np.int64))
+    return (torch.cat([p[0] for p in parts]), torch.cat([p[1] + int(b) for p, b in zip(parts, base)]),
+            torch.cat([p[2] for p in parts]))
 
 
 class StreamSchedules:
@@ -153,13 +169,20 @@ class StreamEvents:
     ``onset``, ``offset`` (exclusive), ``peak_frame`` (int32 output frames from the start of the stream) and ``peak`` (float32),
     sorted by (stream, class, onset); ``event_offsets`` [S+1] host list (stream s = events [event_offsets[s],
     event_offsets[s+1])); ``final_frames`` [S] host list: output frames of each stream that are final after this call; with
-    ``keep_probs``, ``probs`` [sum, K] = the newly final track rows, packed by stream, and ``prob_offsets`` [S+1]."""
+    ``keep_probs``, ``probs`` [sum, K] = the newly final track rows, packed by stream, and ``prob_offsets`` [S+1].  From a stream
+    with ``emit_audio=True`` the events also hold ``audio_start`` (int64) and ``audio_len`` (int32), and ``audio`` is
+    the call's one packed float32 device buffer: event e is ``audio[audio_start[e] : audio_start[e] + audio_len[e]]``
+    (``event_audio(e)``), length 0 where the event was not located.  The slices of one StreamEvents are disjoint and cover
+    ``audio`` exactly; after a call that took several steps ``audio_start`` is NOT monotone in event order (the events are sorted
+    by stream and class, the buffer is in step order)."""
 
-    def __init__(self, events, event_offsets, final_frames, frame_seconds, probs=None, prob_offsets=None, sr=None, grid=None):
+    def __init__(self, events, event_offsets, final_frames, frame_seconds, probs=None, prob_offsets=None, sr=None, grid=None,
+                 audio=None):
         self.events, self.event_offsets, self.final_frames = events, list(event_offsets), list(final_frames)
         self.frame_seconds, self.probs, self.prob_offsets = frame_seconds, probs, prob_offsets
         self.sr = sr                            # the detector's rate: set by a localising stream (lags are in samples at that rate)
         self.grid = grid                        # the DirectionGrid that ``dir`` indexes: set by a stream with DOA settings
+        self.audio = audio                      # the packed extracted audio of this call: set by a stream with emit_audio=True
 
     def __len__(self):
         return self.event_offsets[-1]
@@ -189,6 +212,12 @@ class StreamEvents:
         out = _doa_angles(self.events, self.grid, None)
         return out if stream is None else out[self.event_offsets[int(stream)]:self.event_offsets[int(stream) + 1]]
 
+    def event_audio(self, e):
+        """the extracted audio of event ``e`` of this call (``DetectionResult.event_audio``): a float32 device slice of ``audio``
+        at the detector's rate, empty where the event was not located.  Only on what a stream with ``emit_audio=True`` returns
+        (DESIGN 5t); the host reads the event's two integers."""
+        return _event_audio(self, e)
+
 
 class StreamDetector:
     """``EventDetector`` for audio that is still arriving, S streams at once (module docstring).  The keyword arguments are
@@ -197,17 +226,26 @@ class StreamDetector:
     emitted event ``[a, b)`` whose frames ``[f0, f1)`` (``localize.event_frames``) satisfy ``b*tf + lat - f0 <= history_frames``
     (``localize.stream_locates``) comes with the ``lag``, ``strength`` and ``loc_frames`` of the offline call, bit for bit; the
     others with zeros.  ``"min"`` = ``max_frames + lat``, the least that is accepted: every event of at most ``max_frames``
-    feature frames is located.  The ring costs ``4 * C * localize.stream_ring_samples(...)`` bytes per feed."""
+    feature frames is located.  The ring costs ``4 * C * localize.stream_ring_samples(...)`` bytes per feed.
+    ``emit_audio=True`` (a detector with ``extract=sed.DelaySum(...)`` or ``sed.MVDR(...)``, which does not stream without it;
+    DESIGN 5t): a step that emits events also extracts their audio from the rings, ``feature.event_beamform_ring`` or
+    ``feature.event_mvdr_ring`` — every located event's audio is the offline call's, bit for bit, in any chunking; an event the
+    rule above refuses has ``dir = -1`` and length 0 (``StreamEvents.audio`` / ``event_audio``).  It costs one more blocking
+    8-byte read and one device allocation per step that emits events; ``state_bytes`` does not change."""
 
     def __init__(self, model, n_streams, keep_probs=False, max_new_windows=4, _det=None, input_sr=None, input_channels=None,
-                 history_frames=None, **kw):
+                 history_frames=None, emit_audio=False, **kw):
         self.det = _det if _det is not None else EventDetector(model, **kw)
         det, m = self.det, self.det.model
-        if det.extract_settings is not None:
-            raise NotImplementedError("live feeds do not extract audio yet: a detector with extract=sed.DelaySum(...) or sed.MVDR(...) "
-                                      "does not stream (feature.event_beamform_ring is the ring entry a StreamDetector would call, "
-                                      "DESIGN 5r; the MVDR beam has no ring entry, DESIGN 5s); make the stream from a detector "
-                                      "without extract=")
+        self.emit_audio = bool(emit_audio)
+        if det.extract_settings is not None and not self.emit_audio:
+            raise NotImplementedError("live feeds extract audio only when asked to: a detector with extract=sed.DelaySum(...) or "
+                                      "sed.MVDR(...) streams with emit_audio=True (and history_frames=), which costs one more "
+                                      "blocking read and one device allocation per step (DESIGN 5t); pass emit_audio=True, or make "
+                                      "the stream from a detector without extract=")
+        if self.emit_audio and det.extract_settings is None:
+            raise ValueError("emit_audio=True needs a detector that extracts audio: EventDetector(..., localize=sed.DOA(...), "
+                             "extract=sed.DelaySum(...) or sed.MVDR(...))")
         if det.localize_settings is not None and history_frames is None:
             raise NotImplementedError("live feeds are not localised: when a stream's event becomes final the PCM of its frames is "
                                       "gone (DESIGN 5o); make the StreamDetector without localize=, or give it history_frames= "
@@ -258,7 +296,7 @@ class StreamDetector:
                 raise ValueError(f"history_frames={self.history_frames} is less than the minimum max_frames + lat = "
                                  f"{det.localize_settings.max_frames} + {self.lat} = {least} feature frames (\"min\")")
             self.cap = stream_ring_samples(self.history_frames, self.step_frames, h, feature.NFFT)
-            self._ev_keys = _KEYS + _TDOA_KEYS + (_DOA_KEYS if det.locates_directions else ())
+            self._ev_keys = _KEYS + _TDOA_KEYS + (_DOA_KEYS if det.locates_directions else ()) + (_BEAM_KEYS if self.emit_audio else ())
         self._dims = (S, self.K, self.win_out, self.hop_out, det.median_max, self.max_new)
         self._core_bytes = lib().sed_stream_state_bytes(*self._dims)
         if self._core_bytes == 0:
@@ -413,7 +451,8 @@ class StreamDetector:
     # ── one step: new feature rows in, events out ──
     def _step(self, fresh, row0, rows, end):
         """``fresh`` [*, CF] device rows, stream s takes ``rows[s]`` of them from ``row0[s]`` (at most step_frames); the streams
-        in the mask ``end`` end after them.  -> (events dict, event offsets [S+1], probs or None, prob counts [S], final [S])"""
+        in the mask ``end`` end after them.  -> (events dict, event offsets [S+1], probs or None, prob counts [S], final [S], the
+        events' packed audio or None)"""
         det, S, K, CF, FC, sc = self.det, self.S, self.K, self.CF, self.FC, self.sched
         dev = self._state.device
         tf, L, ar = det.model.time_factor, det.seq_len, self._ar
@@ -485,11 +524,14 @@ class StreamDetector:
         if offs[-1] > cap:
             raise SedHipError(f"sed_stream_step emitted {offs[-1]} events, more than the bound {cap}")
         events = {k: v[:offs[-1]] for k, v in ev.items()}
+        audio = None
         if self._ring is not None:
             events.update(self._locate(events, end))
+            if self.emit_audio:
+                audio = self._extract(events, offs[-1])
         if end.any():
             self._reset_host(end)
-        return events, offs, probs, prob_n, now_F
+        return events, offs, probs, prob_n, now_F, audio
 
     def _locate(self, events, end):
         """the step's events on the rings, with the samples received so far (before a feed that ends is reset): one
@@ -508,6 +550,22 @@ class StreamDetector:
             self._ring, self.cap, self._n, self.C, events, det.model.time_factor, max_lag=t.max_lag, max_frames=t.max_frames, hop=h,
             lat_frames=self.lat, history_frames=self.history_frames))
 
+    def _extract(self, events, E):
+        """the audio of the step's located events from the rings, with the samples received so far, through the detector's
+        beam: one ``event_beamform_ring`` / ``event_mvdr_ring`` call when the step emitted events.  ``events`` gains
+        ``audio_start`` and ``audio_len``; -> the packed buffer"""
+        from .localize import MVDR
+        det, dev = self.det, self._state.device
+        if E == 0:                                                          # no launch, no read
+            events.update({k: v for k, v in feature._beam_empty(dev).items() if k != "audio"})
+            return torch.empty(0, device=dev)
+        entry = feature.event_mvdr_ring if isinstance(det.extract_settings, MVDR) else feature.event_beamform_ring
+        beam = _timed(self.marks, "extract", lambda: entry(self._ring, self.cap, self._n, self.C, events, det.model.time_factor,
+                                                           det.localize_settings, det.extract_settings, sr=det.sr, hop=det.hop_length))
+        audio = beam.pop("audio")
+        events.update(beam)
+        return audio
+
     # ── rounds: a push of any size as steps of bounded size ──
     def _run(self, rounds):
         """``rounds``: an iterator of (fresh, row0, rows, end mask) steps -> one StreamEvents for all of them"""
@@ -524,13 +582,17 @@ class StreamDetector:
         if not parts:
             ev = self._no_events(dev)
             probs = torch.empty(0, K, device=dev) if self.keep_probs else None
-            return self._events(ev, [0] * (S + 1), final, probs, [0] * (S + 1) if self.keep_probs else None)
+            return self._events(ev, [0] * (S + 1), final, probs, [0] * (S + 1) if self.keep_probs else None,
+                                torch.empty(0, device=dev) if self.emit_audio else None)
         if len(parts) == 1:
-            ev, offs, probs, prob_n, _ = parts[0]
+            ev, offs, probs, prob_n, _, audio = parts[0]
             poffs = np.concatenate([[0], np.cumsum(prob_n)]).tolist() if self.keep_probs else None
-            return self._events(ev, offs, final, probs, poffs)
+            return self._events(ev, offs, final, probs, poffs, audio)
         # several steps: a stream's events (and rows) of step 1, then of step 2, ...: one stable sort by (stream, class)
         ev = {k: torch.cat([p[0][k] for p in parts]) for k in self._ev_keys}
+        audio = None
+        if self.emit_audio:                                                 # the steps' buffers back to back, in step order
+            audio, ev["audio_start"], ev["audio_len"] = merge_step_audio([(p[5], p[0]["audio_start"], p[0]["audio_len"]) for p in parts])
         order = torch.sort(ev["stream"].long() * K + ev["cls"].long(), stable=True).indices
         ev = {k: v[order] for k, v in ev.items()}
         counts = np.sum([np.diff(p[1]) for p in parts], axis=0)
@@ -542,7 +604,7 @@ class StreamDetector:
             allp = torch.cat([p[2] for p in parts])
             probs = allp[torch.from_numpy(idx).to(dev)]
             poffs = np.concatenate([[0], np.cumsum(np.sum([p[3] for p in parts], axis=0))]).tolist()
-        return self._events(ev, offs, final, probs, poffs)
+        return self._events(ev, offs, final, probs, poffs, audio)
 
     def _no_events(self, dev):
         ev = _event_tensors(_KEYS, 0, dev)
@@ -552,11 +614,13 @@ class StreamDetector:
                       loc_frames=torch.empty(0, dtype=torch.int32, device=dev))
             if self.det.locates_directions:
                 ev.update(dir=torch.empty(0, dtype=torch.int32, device=dev), doa_power=torch.empty(0, device=dev))
+            if self.emit_audio:
+                ev.update({k: v for k, v in feature._beam_empty(dev).items() if k != "audio"})
         return ev
 
-    def _events(self, ev, offs, final, probs, poffs):
+    def _events(self, ev, offs, final, probs, poffs, audio=None):
         return StreamEvents(ev, offs, final, self.frame_seconds, probs, poffs, self.det.sr if self.cap else None,
-                            self.det.localize_settings.grid if self.cap and self.det.locates_directions else None)
+                            self.det.localize_settings.grid if self.cap and self.det.locates_directions else None, audio)
 
     def _pieces(self, xs, what, check_one, axis=0):
         xs = list(xs)
@@ -748,6 +812,10 @@ class StreamDetector:
         """two StreamEvents of one call as one: per stream a's events (and rows), then b's"""
         K, dev = self.K, self._state.device
         ev = {k: torch.cat([a.events[k], b.events[k]]) for k in self._ev_keys}
+        audio = None
+        if self.emit_audio:
+            audio, ev["audio_start"], ev["audio_len"] = merge_step_audio([(x.audio, x.events["audio_start"], x.events["audio_len"])
+                                                                          for x in (a, b)])
         order = torch.sort(ev["stream"].long() * K + ev["cls"].long(), stable=True).indices
         ev = {k: v[order] for k, v in ev.items()}
         offs = (np.asarray(a.event_offsets) + np.asarray(b.event_offsets)).tolist()
@@ -758,7 +826,7 @@ class StreamDetector:
             idx = np.argsort(owner, kind="stable")
             probs = torch.cat([a.probs, b.probs])[torch.from_numpy(idx).to(dev)]
             poffs = np.concatenate([[0], np.cumsum(na + nb)]).tolist()
-        return self._events(ev, offs, b.final_frames, probs, poffs)
+        return self._events(ev, offs, b.final_frames, probs, poffs, audio)
 
     def reset(self, streams=None):
         """drop these streams (default: all) where they stand: nothing is emitted, they restart at frame 0"""
