@@ -654,6 +654,33 @@ int sed_event_mvdr_ring(const float* ring, long ring_len, long cap, const long* 
                         double loading, const void* tables, size_t tables_bytes, const int* audio_len, const long* audio_start,
                         float* audio, long audio_total, void* workspace, size_t workspace_bytes, void* stream);
 
+/* sed_event_mvdr_noise / sed_event_mvdr_noise_ring: sed_event_mvdr / sed_event_mvdr_ring with the covariance taken from
+ * before the onset.  noise_blocks = Kn in [0, 256], noise_guard = G in [0, 64], in blocks of B = 1024 samples.  An extracted event
+ * [s0, s1) with s0 >= (G + Kn + 1) B gets its weights from Rn[k] = sum_q X_q X_q^H over the Kn frames q = 0..Kn-1 of 2048 samples
+ * that start at s0 - (G + Kn + 1 - q) B of its RECORDING (they cover [s0 - (G + Kn + 1) B, s0 - G B); fp32, ascending q, chunks
+ * of 32 frames added in ascending order), by sed_event_mvdr's formula with Rn in place of R; the frames that are combined and
+ * the output are unchanged.  Every other extracted event gets sed_event_mvdr's audio, bit for bit.  noise_frames_out: DEVICE int32
+ * [E], Kn for an event that used the noise covariance, 0 for every other one; it is written when something is launched (E = 0
+ * or audio_total = 0 launches nothing: no event is extracted).  Kn = 0 is sed_event_mvdr with noise_frames_out zeroed.  On a ring
+ * a noise sample the ring no longer holds reads as 0.  With Kn > 0 a recording (a feed) has fewer than 2^42 samples.  An event's audio is a function of those samples and [s0, s1) of its own
+ * recording, tau[dir] and the settings alone.  workspace: at least sed_event_mvdr_noise_workspace_bytes(R, channels, max_frames,
+ * hop, noise_blocks) (0: refused sizes) — per event max(the chunks of the own frames, ceil(Kn / 32)) chunk slots.  Every argument
+ * is checked on the host before anything is enqueued; messages begin with "mvdr_noise:" / "mvdr_noise_ring:". */
+size_t sed_event_mvdr_noise_workspace_bytes(int R, int channels, int max_frames, int hop, int noise_blocks);
+int sed_event_mvdr_noise(const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const int* ev_rec,
+                         const int* ev_onset, const int* ev_offset, const int* ev_peak_frame, const int* ev_dir,
+                         const int* ev_loc_frames, long E, int time_factor, int hop, int max_frames, const double* tau, int D,
+                         double loading, int noise_blocks, int noise_guard, const void* tables, size_t tables_bytes,
+                         const int* audio_len, const long* audio_start, float* audio, long audio_total, int* noise_frames_out,
+                         void* workspace, size_t workspace_bytes, void* stream);
+size_t sed_event_mvdr_noise_ring_workspace_bytes(int R, int channels, int max_frames, int hop, int noise_blocks);
+int sed_event_mvdr_noise_ring(const float* ring, long ring_len, long cap, const long* n_host, int R, int channels, const int* ev_rec,
+                              const int* ev_onset, const int* ev_offset, const int* ev_peak_frame, const int* ev_dir,
+                              const int* ev_loc_frames, long E, int time_factor, int hop, int max_frames, const double* tau, int D,
+                              double loading, int noise_blocks, int noise_guard, const void* tables, size_t tables_bytes,
+                              const int* audio_len, const long* audio_start, float* audio, long audio_total, int* noise_frames_out,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
 /* sed_pcen: per-channel energy normalisation, IN PLACE, of the columns [col0, col0 + W) of x [rows][stride], which
  * hold log-mel values (natural log, as sed_logmel* write them without a scaler); the other columns are not touched.  Every column
  * of a recording is one chain: E[t] = scale * exp(x[t]); M[t] = (1 - smooth_b) M[t-1] + smooth_b E[t] with M[0] = E[0] (librosa's

@@ -33,6 +33,14 @@
 // bodies with the frame loaded from the feed's PCM rings (sed_stream_ring_write; TdArgs.cap) — directly where the frame does not
 // wrap, through the guarded loads with the index taken modulo cap where it does — so the registers hold the samples the linear
 // call loads and everything after the loads is one code: the same bits.  The weight kernel reads no PCM and has no ring form.
+//
+// The covariance from before the onset: sed_event_mvdr_noise / sed_event_mvdr_noise_ring with Kn = noise_blocks >= 1
+// and G = noise_guard.  An extracted event with s0 >= (G + Kn + 1) B gets its weights from Rn[k] = sum_q X_q X_q^H over the Kn
+// frames q of 2048 samples that start at s0 - (G + Kn + 1 - q) B of its RECORDING (fp32, ascending q, chunks of MV_CHUNK added
+// in ascending order), by the formula above with Rn for R; every other event is the above, bit for bit.  mvdr_noise_k /
+// mvdr_ring_noise_k are the covariance body over those frames (mv_load_abs / mv_load_abs_ring: direct loads, or guarded ones
+// with every index checked against the recording); a slice is then four launches — own covariance, noise covariance, weights,
+// apply — and each covariance launch returns at once for the other's events.  noise_frames_out says which events used it.
 #include <math.h>
 #include <vector>
 #include "common.h"
@@ -62,7 +70,17 @@ struct MvArgs {
     int cpe;                                     // chunk slots per event in the workspace
     int rows;                                    // rows per event: cpe x C(C+1)/2 partials, then the C rows of w
     int batch;                                   // entries of the triangle that mvdr_cov_k holds at a time
+    int kn, guard;                               // Kn noise frames that end guard blocks before the onset (kn = 0: none)
+    int* noise_frames;                           // [E] kn where the event's weights come from the noise covariance, else 0 (kn > 0)
 };
+
+// whether the weights of an extracted event at s0 come from the covariance of the kn frames before its onset: the samples
+// [s0 - (guard + kn + 1) B, s0 - guard B) must exist: s0 >= (guard + kn + 1) B.  All or nothing, and a function of the event
+// and the settings alone.  Compared in whole blocks and in 32 bits (0 <= s0 < 2^42: mv_run refuses longer recordings with
+// kn > 0): the scalar unit has no 64-bit ordering compare, and a vector one would be new to mvdr_cov_k's prologue.
+__device__ __forceinline__ bool mv_uses_noise(const MvArgs& ma, long s0) {
+    return ma.kn > 0 && (unsigned)(s0 >> 10) >= (unsigned)(ma.guard + ma.kn + 1);
+}
 
 // event e: its recording, first sample and length.  len = 0: not extracted, or a span table that was not made from this event
 // table (nothing is read or written for it, as in beam_sum_k)
@@ -119,6 +137,54 @@ __device__ __forceinline__ void mv_load_frame_ring(f2 (&z)[32], const float* __r
     }
 }
 
+// 2048 samples of a recording of n samples from sample `first` on — a noise frame, which lies before the event:
+// chan = the channel's sample 0.  A frame inside [0, n) on an 8-byte boundary takes the direct loads; every other one the
+// guarded loads, each index checked against [0, n): whatever the event table says, nothing outside the channel is read.
+__device__ __forceinline__ void mv_load_abs(f2 (&z)[32], const float* __restrict__ chan, long n, long first, float* scr, const FftLane& fl) {
+    const bool fast = first >= 0 && first + LM_NFFT <= n && (reinterpret_cast<uintptr_t>(chan + first) & 7) == 0;
+    if (__all(fast)) {
+        const f2* src = reinterpret_cast<const f2*>(chan + first) + fl.r();
+#pragma unroll
+        for (int n1 = 0; n1 < 32; ++n1) z[n1] = src[32 * n1];
+    } else {
+        fft_load_guarded(z, scr, fl, [&](int off) -> float {
+            const long i = first + off;
+            return i >= 0 && i < n ? chan[i] : 0.f;
+        });
+    }
+}
+
+// ... of a live feed that has received n samples: mv_load_frame_ring's scheme — one remainder per frame; direct loads where the
+// frame does not wrap, is aligned and is at or after kept = max(0, n - cap); otherwise guarded loads with the index taken
+// modulo cap, and a sample outside [kept, n) reads as 0
+__device__ __forceinline__ void mv_load_abs_ring(f2 (&z)[32], const float* __restrict__ lane, long cap, long n, long first, float* scr,
+                                                 const FftLane& fl) {
+    const long kept = n > cap ? n - cap : 0;
+    long pos = first % cap;
+    if (pos < 0) pos += cap;
+    const bool fast = first >= kept && first + LM_NFFT <= n && pos + LM_NFFT <= cap && (reinterpret_cast<uintptr_t>(lane + pos) & 7) == 0;
+    if (__all(fast)) {
+        const f2* src = reinterpret_cast<const f2*>(lane + pos) + fl.r();
+#pragma unroll
+        for (int n1 = 0; n1 < 32; ++n1) z[n1] = src[32 * n1];
+    } else {
+        fft_load_guarded(z, scr, fl, [&](int off) -> float {
+            const long i = first + off, p = pos + off;           // (cap >= 2048: p < 2 cap)
+            return i >= kept && i < n ? lane[p >= cap ? p - cap : p] : 0.f;
+        });
+    }
+}
+
+// noise frame q of channel ch of the event at s0 of recording rec: the 2048 samples from s0 - (guard + kn + 1 - q) B
+// on, read from the recording
+template <bool RING>
+__device__ __forceinline__ void mv_load_noise(f2 (&z)[32], const float* __restrict__ pcm, const TdArgs& ta, const MvArgs& ma, int rec, int ch,
+                                              long s0, int q, float* scr, const FftLane& fl) {
+    const long n = ta.n_samples[rec], first = s0 - (long)(ma.guard + ma.kn + 1 - q) * MV_B;
+    if (RING) mv_load_abs_ring(z, pcm + ((long)rec * ta.C + ch) * ta.cap, ta.cap, n, first, scr, fl);
+    else mv_load_abs(z, pcm + ta.sample_off[(long)rec * ta.C + ch], n, first, scr, fl);
+}
+
 // frame j of channel ch of the event at s0 of recording rec: RING = false from the planar PCM, RING = true from the feed's rings
 template <bool RING>
 __device__ __forceinline__ void mv_load(f2 (&z)[32], const float* __restrict__ pcm, const TdArgs& ta, int rec, int ch, long s0, int len,
@@ -133,8 +199,10 @@ __device__ __forceinline__ void mv_load(f2 (&z)[32], const float* __restrict__ p
 
 // The bodies of the covariance and the apply kernels, once for the planar PCM (mvdr_cov_k, mvdr_apply_k) and once for the rings
 // of live feeds (mvdr_ring_cov_k, mvdr_ring_apply_k): two kernels each, not one with a run-time branch, so that the linear
-// kernels compile to what they were before the rings existed; only mv_load differs.
-template <bool RING>
+// kernels compile to what they were before the rings existed; only mv_load differs.  NOISE = true (mvdr_noise_k,
+// mvdr_ring_noise_k) is the same body over the kn frames before the onset of the events whose weights come from
+// them; with kn > 0 the two launches share the events between them and each leaves the other's alone.
+template <bool RING, bool NOISE>
 __device__ __forceinline__ void mv_cov_body(const float* __restrict__ pcm, const uint32_t* __restrict__ tables, float2* __restrict__ ws,
                                             TdArgs ta, MvArgs ma) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -143,8 +211,10 @@ __device__ __forceinline__ void mv_cov_body(const float* __restrict__ pcm, const
     int rec, len;
     long s0;
     mv_event(ta, ma, e, rec, s0, len);
-    if (len == 0) return;                                        // (block-uniform: before any barrier)
-    const int nfr = (len + MV_B - 1) / MV_B + 1;                 // frames 0 .. J
+    const bool noise = len != 0 && mv_uses_noise(ma, s0);
+    if (NOISE && blockIdx.x == 0 && tid == 0) ma.noise_frames[e] = noise ? ma.kn : 0;
+    if (len == 0 || noise != NOISE) return;                      // (block-uniform: before any barrier)
+    const int nfr = NOISE ? ma.kn : (len + MV_B - 1) / MV_B + 1; // the frames before the onset, or frames 0 .. J
     const int fc0 = blockIdx.x * MV_CHUNK;
     if (fc0 >= nfr) return;
     const int fc1 = fc0 + MV_CHUNK < nfr ? fc0 + MV_CHUNK : nfr;
@@ -173,7 +243,8 @@ __device__ __forceinline__ void mv_cov_body(const float* __restrict__ pcm, const
                 // the frame of channel 2 wave + half (an odd C: the last half wave repeats channel C-1 and stores the same values)
                 const int ch = (2 * wave + half < C) ? 2 * wave + half : C - 1;
                 f2 z[32];
-                mv_load<RING>(z, pcm, ta, rec, ch, s0, len, j, scr, fl);
+                if (NOISE) mv_load_noise<RING>(z, pcm, ta, ma, rec, ch, s0, j, scr, fl);
+                else mv_load<RING>(z, pcm, ta, rec, ch, s0, len, j, scr, fl);
                 fft2048_passes(z, fl, s_win, s_tw);
                 fft2048_spectrum(z, fl, s_pw, s_spec + ch * PHAT_SPEC);
             }
@@ -204,12 +275,22 @@ __device__ __forceinline__ void mv_cov_body(const float* __restrict__ pcm, const
 
 __global__ __launch_bounds__(MV_THREADS) void mvdr_cov_k(const float* __restrict__ pcm, const uint32_t* __restrict__ tables,
                                                          float2* __restrict__ ws, TdArgs ta, MvArgs ma) {
-    mv_cov_body<false>(pcm, tables, ws, ta, ma);
+    mv_cov_body<false, false>(pcm, tables, ws, ta, ma);
 }
 
 __global__ __launch_bounds__(MV_THREADS) void mvdr_ring_cov_k(const float* __restrict__ ring, const uint32_t* __restrict__ tables,
                                                               float2* __restrict__ ws, TdArgs ta, MvArgs ma) {
-    mv_cov_body<true>(ring, tables, ws, ta, ma);
+    mv_cov_body<true, false>(ring, tables, ws, ta, ma);
+}
+
+__global__ __launch_bounds__(MV_THREADS) void mvdr_noise_k(const float* __restrict__ pcm, const uint32_t* __restrict__ tables,
+                                                           float2* __restrict__ ws, TdArgs ta, MvArgs ma) {
+    mv_cov_body<false, true>(pcm, tables, ws, ta, ma);
+}
+
+__global__ __launch_bounds__(MV_THREADS) void mvdr_ring_noise_k(const float* __restrict__ ring, const uint32_t* __restrict__ tables,
+                                                                float2* __restrict__ ws, TdArgs ta, MvArgs ma) {
+    mv_cov_body<true, true>(ring, tables, ws, ta, ma);
 }
 
 // Every thread works in its own column of the three arrays: no thread reads what another writes, and there is no barrier.
@@ -226,7 +307,7 @@ __global__ __launch_bounds__(MV_WT) void mvdr_weights_k(float2* __restrict__ ws,
     mv_event(ta, ma, e, rec, s0, len);
     if (len == 0) return;
     const int C = ta.C, T = C * (C + 1) / 2;
-    const int nfr = (len + MV_B - 1) / MV_B + 1, nch = (nfr + MV_CHUNK - 1) / MV_CHUNK;
+    const int nfr = mv_uses_noise(ma, s0) ? ma.kn : (len + MV_B - 1) / MV_B + 1, nch = (nfr + MV_CHUNK - 1) / MV_CHUNK;
     float2* wev = ws + (long)blockIdx.y * ma.rows * PHAT_SPEC;
     float2* wout = wev + (long)ma.cpe * T * PHAT_SPEC;           // [C][PHAT_SPEC]
 #pragma unroll 1
@@ -409,6 +490,12 @@ long mv_chunks(int max_frames, int hop) {
     const long J = ((long)max_frames * hop + MV_B - 1) / MV_B;   // no event has more output blocks
     return (J + 1 + MV_CHUNK - 1) / MV_CHUNK;
 }
+long mv_noise_chunks(int kn) { return (kn + MV_CHUNK - 1) / MV_CHUNK; }
+// chunk slots per event: the own frames' or the noise frames', whichever are more (an event uses one kind)
+long mv_slots(int max_frames, int hop, int kn) {
+    const long own = mv_chunks(max_frames, hop), nz = mv_noise_chunks(kn);
+    return own > nz ? own : nz;
+}
 size_t mv_event_bytes(int C, long cpe) { return ((size_t)cpe * (C * (C + 1) / 2) + C) * TD_ROW_BYTES; }
 size_t mv_cov_lds(int C, int batch) {
     return ((size_t)MV_TAB_WORDS + (size_t)C * PHAT_SPEC * 2 + (size_t)((C + 1) / 2) * MV_FFT_SCR + (size_t)batch * PHAT_SPEC * 2) * sizeof(float);
@@ -421,14 +508,22 @@ bool mv_sizes_ok(int R, int channels, int max_frames, int hop) {
     return R >= 1 && channels >= 2 && channels <= TD_MAX_CH && max_frames >= 1 && hop >= 1 && (long)max_frames * hop <= 0x7fffffffL;
 }
 
-// what both entries do once the events and the recordings are checked: h = the recording table (tab bytes at the head of the
-// workspace), pcm = the planar PCM (RING: the rings, cap samples each)
+#define MV_MAX_NOISE 256                          // localize.MVDR: noise_blocks
+#define MV_MAX_GUARD 64                           //                noise_guard
+
+// what all entries do once the events and the recordings are checked: h = the recording table (tab bytes at the head of the
+// workspace), pcm = the planar PCM (RING: the rings, cap samples each); kn = 0 (sed_event_mvdr, sed_event_mvdr_ring, or a
+// noise entry asked for no noise frames): today's three launches, and noise_frames_out, where given, is zeroed
 template <bool RING>
 int mv_run(const char* who, const float* pcm, const std::vector<long>& h, size_t tab, long longest, long cap, int R, int channels,
            const int* ev_rec, const int* ev_onset, const int* ev_offset, const int* ev_peak_frame, const int* ev_dir,
            const int* ev_loc_frames, long E, int time_factor, int hop, int max_frames, const double* tau, int D, double loading,
            const void* tables, size_t tables_bytes, const int* audio_len, const long* audio_start, float* audio, long audio_total,
-           void* workspace, size_t workspace_bytes, void* stream) {
+           void* workspace, size_t workspace_bytes, void* stream, int kn = 0, int guard = 0, int* noise_frames_out = nullptr,
+           bool noise_entry = false) {
+    SED_REQUIRE(kn >= 0 && kn <= MV_MAX_NOISE, "%s: noise_blocks must be in [0, %d], got %d", who, MV_MAX_NOISE, kn);
+    SED_REQUIRE(guard >= 0 && guard <= MV_MAX_GUARD, "%s: noise_guard must be in [0, %d], got %d", who, MV_MAX_GUARD, guard);
+    SED_REQUIRE(!noise_entry || E == 0 || noise_frames_out, "%s: null pointer (noise_frames_out)", who);
     SED_REQUIRE(loading >= 1e-6 && loading <= 1e6, "%s: loading must be in [1e-6, 1e6], got %g", who, loading);
     SED_REQUIRE(audio_total >= 0, "%s: a total of %ld samples", who, audio_total);
     SED_REQUIRE(E == 0 || (tau && audio_len && audio_start), "%s: null pointer (tau, audio_len or audio_start)", who);
@@ -436,9 +531,11 @@ int mv_run(const char* who, const float* pcm, const std::vector<long>& h, size_t
     SED_REQUIRE(tables && tables_bytes % 16 == 0 && tables_bytes / 4 >= (size_t)MV_TAB_WORDS, "%s: table blob of %zu bytes is malformed", who,
                 tables_bytes);
     SED_REQUIRE(((uintptr_t)pcm & 3) == 0, "%s: the samples must be 4-byte aligned", who);
-    if (E == 0 || audio_total == 0) return 0;                    // nothing to launch
+    SED_REQUIRE(kn == 0 || longest < (1L << 42), "%s: a recording of %ld samples; with noise_blocks > 0 fewer than 2^42 are taken", who,
+                longest);
+    if (E == 0 || audio_total == 0) return 0;                    // nothing to launch (noise_frames_out is not written: no event is extracted)
     const int C = channels, T = C * (C + 1) / 2;
-    const long cpe = mv_chunks(max_frames, hop);
+    const long cpe = mv_slots(max_frames, hop, kn);
     const size_t per_event = mv_event_bytes(C, cpe);
     SED_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0, "%s: the workspace must be a 16-byte aligned device buffer", who);
     SED_REQUIRE(workspace_bytes >= tab + per_event, "%s: workspace of %zu bytes, at least %zu needed (one event)", who, workspace_bytes,
@@ -463,15 +560,25 @@ int mv_run(const char* who, const float* pcm, const std::vector<long>& h, size_t
     const auto apply_k = RING ? mvdr_ring_apply_k : mvdr_apply_k;
     hipError_t err = hipFuncSetAttribute((const void*)cov_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MV_LDS_MAX);
     if (err == hipSuccess) err = hipFuncSetAttribute((const void*)apply_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MV_LDS_MAX);
+    const auto noise_k = RING ? mvdr_ring_noise_k : mvdr_noise_k;
+    if (err == hipSuccess && kn > 0) err = hipFuncSetAttribute((const void*)noise_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MV_LDS_MAX);
     if (err != hipSuccess) { sed_set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(err)); return (int)err; }
+    if (kn == 0 && noise_frames_out) {
+        err = hipMemsetAsync(noise_frames_out, 0, (size_t)E * sizeof(int), s);
+        if (err != hipSuccess) { sed_set_error("%s: hipMemsetAsync: %s", who, hipGetErrorString(err)); return (int)err; }
+    }
     TdArgs ta = beam_args(RING, workspace, R, C, ev_rec, ev_onset, ev_offset, ev_peak_frame, time_factor, hop, max_frames, cap);
-    const MvArgs ma{ev_dir, ev_loc_frames, D, audio_len, audio_start, audio_total, (int)cpe, (int)(cpe * T + C), batch};
+    const MvArgs ma{ev_dir, ev_loc_frames, D, audio_len, audio_start, audio_total, (int)cpe, (int)(cpe * T + C), batch, kn, guard, noise_frames_out};
     float2* part = (float2*)((char*)workspace + tab);
     for (long e0 = 0; e0 < E; e0 += slice) {
         ta.e0 = e0;
         ta.n_ev = (int)(E - e0 < slice ? E - e0 : slice);
         cov_k<<<dim3(chunks, (unsigned)ta.n_ev), MV_THREADS, lds_cov, s>>>(pcm, (const uint32_t*)tables, part, ta, ma);
         SED_LAUNCH_CHECK("mvdr (covariance)");
+        if (kn > 0) {                                            // the host does not know which events use it: both launches run
+            noise_k<<<dim3((unsigned)mv_noise_chunks(kn), (unsigned)ta.n_ev), MV_THREADS, lds_cov, s>>>(pcm, (const uint32_t*)tables, part, ta, ma);
+            SED_LAUNCH_CHECK("mvdr (noise covariance)");
+        }
         mvdr_weights_k<<<dim3((LM_N + MV_WT) / MV_WT, (unsigned)ta.n_ev), MV_WT, 0, s>>>(part, tau, loading, ta, ma);
         SED_LAUNCH_CHECK("mvdr (weights)");
         apply_k<<<dim3(runs, (unsigned)ta.n_ev), MV_THREADS, lds_apply, s>>>(pcm, (const uint32_t*)tables, part, audio, ta, ma);
@@ -529,4 +636,57 @@ extern "C" int sed_event_mvdr_ring(const float* ring, long ring_len, long cap, c
     return mv_run<true>(who, ring, h, beam_ring_table_bytes(R), longest, cap, R, channels, ev_rec, ev_onset, ev_offset, ev_peak_frame,
                         ev_dir, ev_loc_frames, E, time_factor, hop, max_frames, tau, D, loading, tables, tables_bytes, audio_len,
                         audio_start, audio, audio_total, workspace, workspace_bytes, stream);
+}
+
+// ── DESIGN 5u: the weights from the covariance of the noise_blocks frames that end noise_guard blocks before the onset ──
+extern "C" size_t sed_event_mvdr_noise_workspace_bytes(int R, int channels, int max_frames, int hop, int noise_blocks) {
+    if (!mv_sizes_ok(R, channels, max_frames, hop) || noise_blocks < 0 || noise_blocks > MV_MAX_NOISE) return 0;
+    return beam_table_bytes(R, channels) + mv_event_bytes(channels, mv_slots(max_frames, hop, noise_blocks));
+}
+
+extern "C" size_t sed_event_mvdr_noise_ring_workspace_bytes(int R, int channels, int max_frames, int hop, int noise_blocks) {
+    if (!mv_sizes_ok(R, channels, max_frames, hop) || noise_blocks < 0 || noise_blocks > MV_MAX_NOISE) return 0;
+    return beam_ring_table_bytes(R) + mv_event_bytes(channels, mv_slots(max_frames, hop, noise_blocks));
+}
+
+extern "C" int sed_event_mvdr_noise(const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const int* ev_rec,
+                                    const int* ev_onset, const int* ev_offset, const int* ev_peak_frame, const int* ev_dir,
+                                    const int* ev_loc_frames, long E, int time_factor, int hop, int max_frames, const double* tau, int D,
+                                    double loading, int noise_blocks, int noise_guard, const void* tables, size_t tables_bytes,
+                                    const int* audio_len, const long* audio_start, float* audio, long audio_total, int* noise_frames_out,
+                                    void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "mvdr_noise";
+    SED_TRY(beam_check_events(who, R, channels, ev_rec, ev_onset, ev_offset, ev_peak_frame, ev_dir, ev_loc_frames, E, time_factor, hop,
+                              max_frames, D));
+    SED_REQUIRE(pcm, "%s: null pointer (the samples)", who);
+    std::vector<long> h;
+    long longest;
+    SED_TRY(beam_linear_table(who, pcm_len, clips_host, R, channels, hop, h, longest));
+    return mv_run<false>(who, pcm, h, beam_table_bytes(R, channels), longest, 0, R, channels, ev_rec, ev_onset, ev_offset, ev_peak_frame,
+                         ev_dir, ev_loc_frames, E, time_factor, hop, max_frames, tau, D, loading, tables, tables_bytes, audio_len,
+                         audio_start, audio, audio_total, workspace, workspace_bytes, stream, noise_blocks, noise_guard, noise_frames_out,
+                         true);
+}
+
+extern "C" int sed_event_mvdr_noise_ring(const float* ring, long ring_len, long cap, const long* n_host, int R, int channels,
+                                         const int* ev_rec, const int* ev_onset, const int* ev_offset, const int* ev_peak_frame,
+                                         const int* ev_dir, const int* ev_loc_frames, long E, int time_factor, int hop, int max_frames,
+                                         const double* tau, int D, double loading, int noise_blocks, int noise_guard, const void* tables,
+                                         size_t tables_bytes, const int* audio_len, const long* audio_start, float* audio,
+                                         long audio_total, int* noise_frames_out, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "mvdr_noise_ring";
+    SED_TRY(beam_check_events(who, R, channels, ev_rec, ev_onset, ev_offset, ev_peak_frame, ev_dir, ev_loc_frames, E, time_factor, hop,
+                              max_frames, D));
+    SED_REQUIRE(ring, "%s: null pointer (the rings)", who);
+    SED_REQUIRE(cap >= LM_NFFT && cap % 4 == 0, "%s: a ring holds a multiple of 4 samples and at least one frame of %d, got cap=%ld", who,
+                LM_NFFT, cap);
+    SED_REQUIRE(ring_len >= 0 && cap <= ring_len / ((long)R * channels), "%s: %d feeds of %d rings of %ld samples leave the buffer "
+                "of %ld", who, R, channels, cap, ring_len);
+    std::vector<long> h;
+    long longest;
+    SED_TRY(beam_ring_table(who, n_host, R, hop, h, longest));
+    return mv_run<true>(who, ring, h, beam_ring_table_bytes(R), longest, cap, R, channels, ev_rec, ev_onset, ev_offset, ev_peak_frame,
+                        ev_dir, ev_loc_frames, E, time_factor, hop, max_frames, tau, D, loading, tables, tables_bytes, audio_len,
+                        audio_start, audio, audio_total, workspace, workspace_bytes, stream, noise_blocks, noise_guard, noise_frames_out,
+                        true);
 }

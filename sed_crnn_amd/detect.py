@@ -29,6 +29,7 @@ _EVENT_KEYS = ("cls", "onset", "offset", "peak", "peak_frame")
 _TDOA_KEYS = ("lag", "strength", "loc_frames")          # added to the events of a localising detector
 _DOA_KEYS = ("dir", "doa_power")                        # ... and, with localize=DOA(...), a direction per event
 _BEAM_KEYS = ("audio_start", "audio_len")               # ... and, with extract=DelaySum(...), its place in result.audio
+_NOISE_KEYS = ("noise_frames",)                         # ... and, with extract=MVDR(noise_blocks >= 1), the pre-onset frames its weights used (5u)
 
 
 def _doa_angles(events, grid, k):
@@ -275,6 +276,20 @@ class DetectionResult:
         the event's two integers."""
         return _event_audio(self, e)
 
+    @property
+    def noise_frames(self):
+        """int32 [E] on the device: the pre-onset frames every event's MVDR weights were made from — ``noise_blocks``, or 0 for
+        an event that fell back to its own frames or was not extracted.  Only on the result of a detector with
+        ``extract=sed.MVDR(noise_blocks >= 1)``: otherwise AttributeError."""
+        return _noise_frames(self)
+
+
+def _noise_frames(result):
+    if "noise_frames" not in result.events:
+        raise AttributeError("this result holds no noise_frames: detect with EventDetector(..., localize=sed.DOA(...), "
+                             "extract=sed.MVDR(noise_blocks=...))")
+    return result.events["noise_frames"]
+
 
 def _event_audio(result, e):
     if result.audio is None or "audio_start" not in result.events:
@@ -308,13 +323,20 @@ class BatchDetectionResult:
         i = int(i) % R
         o0, o1 = self.out_offsets[i], self.out_offsets[i + 1]
         e0, e1 = self.event_offsets[i], self.event_offsets[i + 1]
-        keys = _EVENT_KEYS + tuple(k for k in _TDOA_KEYS + _DOA_KEYS + _BEAM_KEYS if k in self.events)
+        keys = _EVENT_KEYS + tuple(k for k in _TDOA_KEYS + _DOA_KEYS + _BEAM_KEYS + _NOISE_KEYS if k in self.events)
         return DetectionResult(self.probs[o0:o1], {k: self.events[k][e0:e1] for k in keys}, self.frame_seconds, self.plans[i], self.sr,
                                self.grid, self.audio)
 
     def event_audio(self, e):
         """the beamformed audio of event ``e`` of the packed table (``DetectionResult.event_audio``)"""
         return _event_audio(self, e)
+
+    @property
+    def noise_frames(self):
+        """int32 [E] on the device: the pre-onset frames every event's MVDR weights were made from — ``noise_blocks``, or 0 for
+        an event that fell back to its own frames or was not extracted.  Only on the result of a detector with
+        ``extract=sed.MVDR(noise_blocks >= 1)``: otherwise AttributeError."""
+        return _noise_frames(self)
 
     def __iter__(self):
         return (self[i] for i in range(len(self)))
@@ -353,7 +375,9 @@ class EventDetector:
     ``result.event_audio(e)``; ``from_features*`` returns events without audio, ``det.localize`` adds it, ``det.stream`` of such a
     detector takes ``history_frames=`` and ``emit_audio=True`` and emits the same audio on live feeds.
     ``extract=sed.MVDR(loading)`` instead: the same events, samples and results through an adaptive beam that
-    suppresses what else the event's frames contain (``feature.event_mvdr``; live feeds: ``feature.event_mvdr_ring``)."""
+    suppresses what else the event's frames contain (``feature.event_mvdr``; live feeds: ``feature.event_mvdr_ring``).  With
+    ``sed.MVDR(noise_blocks=Kn)``, ``Kn >= 1``, the weights come from the Kn frames before the onset where the
+    recording has them, and the events and ``result.noise_frames`` also hold ``noise_frames``."""
 
     def __init__(self, model, seq_len=SEQ_LEN_IN, hop=None, combine="mean", trim=0, threshold=0.5, low=None, median=1,
                  min_gap=0, min_len=1, mean=None, std=None, sr=feature.SR, hop_length=feature.HOP, max_batch=1024, spatial=None,
@@ -588,7 +612,7 @@ class EventDetector:
                              self.extract_settings, sr=self.sr, hop=self.hop_length)
                 result.audio = beam.pop("audio")
                 loc.update(beam)
-        result.events = {**{k: v for k, v in result.events.items() if k not in _TDOA_KEYS + _DOA_KEYS + _BEAM_KEYS}, **loc}
+        result.events = {**{k: v for k, v in result.events.items() if k not in _TDOA_KEYS + _DOA_KEYS + _BEAM_KEYS + _NOISE_KEYS}, **loc}
         result.sr = self.sr
         return result
 
@@ -829,6 +853,8 @@ class EventDetector:
             out.update(dir=torch.empty(0, dtype=torch.int32, device=dev), doa_power=torch.empty(0, device=dev))
         if self.extract_settings is not None:
             out.update(audio_start=torch.empty(0, dtype=torch.int64, device=dev), audio_len=torch.empty(0, dtype=torch.int32, device=dev))
+        if getattr(self.extract_settings, "noise_blocks", 0):
+            out.update(noise_frames=torch.empty(0, dtype=torch.int32, device=dev))
         return out
 
     def _detect_packed(self, mel, bp):

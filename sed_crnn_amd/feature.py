@@ -747,7 +747,13 @@ def event_mvdr(pcm, clips, channels, events, time_factor, doa, mvdr, sr=SR, hop=
     as far as ``loading`` and the number of frames allow (DESIGN 5s has figures).  The covariance partials of at most
     ``max_workspace_bytes`` worth of events are held at a time; the slicing changes no bit, and neither do the other events,
     the batch, the clip's place in the buffer or the samples outside the event.  The host does ONE blocking read, the 8 bytes
-    of the total; ``E == 0`` returns empty tensors without a launch."""
+    of the total; ``E == 0`` returns empty tensors without a launch.
+
+    ``sed.MVDR(loading, noise_blocks=Kn, noise_guard=G)`` with ``Kn >= 1`` (``sed_event_mvdr_noise``): an event with
+    ``s0 >= (G + Kn + 1) 1024`` gets its weights from the covariance of the Kn frames before its onset, the samples
+    ``[s0 - (G + Kn + 1) 1024, s0 - G 1024)`` of its recording, which do not hold the target: a steering error no longer makes
+    the beam cancel it.  Every other event gets what ``Kn = 0`` gives, bit for bit.  The dict gains ``noise_frames`` int32 [E]:
+    Kn where the noise covariance was used, else 0.  An event's audio then depends on those samples and its own alone."""
     import ctypes as C
     from .localize import MVDR
     nc, tf, hop, table, R = _planar_recordings("event_mvdr", pcm, clips, channels, time_factor, hop)
@@ -757,19 +763,38 @@ def event_mvdr(pcm, clips, channels, events, time_factor, doa, mvdr, sr=SR, hop=
     dev = pcm.device
     cols, E = _located_cols(events, R, "rec", dev)
     if E == 0:
-        return _beam_empty(dev)
+        return _mvdr_empty(dev, mvdr)
     pcm = pcm.contiguous().float()
-    need_one = lib().sed_event_mvdr_workspace_bytes(R, nc, doa.max_frames, hop)
-    if need_one == 0:
-        raise ValueError(f"sed_event_mvdr_workspace_bytes refuses R={R}, channels={nc}, max_frames={doa.max_frames}, hop={hop}")
+    need_one = _mvdr_workspace("sed_event_mvdr", R, nc, doa.max_frames, hop, mvdr)
     head = ([ptr(pcm)], [pcm.numel(), C.c_void_p(table.ctypes.data), R, nc])
     return _mvdr_run(("sed_event_beam_spans", "sed_event_mvdr"), head, cols, E, tf, hop, doa, mvdr, sr,
                      lib().sed_event_beam_workspace_bytes(R, nc), need_one, max_workspace_bytes, dev)
 
 
+def _mvdr_empty(dev, mvdr):
+    out = _beam_empty(dev)
+    if mvdr.noise_blocks:
+        out["noise_frames"] = torch.empty(0, dtype=torch.int32, device=dev)
+    return out
+
+
+def _mvdr_workspace(entry, R, nc, max_frames, hop, mvdr):
+    """the workspace bytes of the recording table and one event of ``entry`` (``sed_event_mvdr`` / ``sed_event_mvdr_ring``), or of
+    its noise form where ``mvdr.noise_blocks >= 1``"""
+    if mvdr.noise_blocks:
+        name, args = entry.replace("sed_event_mvdr", "sed_event_mvdr_noise") + "_workspace_bytes", (R, nc, max_frames, hop, mvdr.noise_blocks)
+    else:
+        name, args = entry + "_workspace_bytes", (R, nc, max_frames, hop)
+    need_one = getattr(lib(), name)(*args)
+    if need_one == 0:
+        raise ValueError(f"{name} refuses R={R}, channels={nc}, max_frames={max_frames}, hop={hop}")
+    return need_one
+
+
 def _mvdr_run(names, head, cols, E, tf, hop, doa, mvdr, sr, need_tab, need_one, max_workspace_bytes, dev):
     """the two calls of an MVDR entry, linear or ring: the spans, ONE blocking read of the total (8 bytes) to size ``audio``, the
-    beam; ``need_tab`` / ``need_one``: the workspace bytes of the recording table alone and with one event"""
+    beam; ``need_tab`` / ``need_one``: the workspace bytes of the recording table alone and with one event.  With
+    ``mvdr.noise_blocks >= 1`` the beam is the entry's noise form and the dict gains ``noise_frames`` int32 [E]"""
     key = (dev.index or 0, float(sr))
     if key not in doa._steering_device:
         doa._steering_device[key] = torch.from_numpy(doa.steering(sr)).to(dev)
@@ -783,6 +808,14 @@ def _mvdr_run(names, head, cols, E, tf, hop, doa, mvdr, sr, need_tab, need_one, 
                                    ptr(out["audio_start"]), ptr(total), ptr(ws), ws.numel(), stream_ptr()), names[0])
     n_total = int(total.item())                                       # the one blocking read
     out["audio"] = torch.empty(n_total, device=dev)
+    if mvdr.noise_blocks:
+        name = names[1].replace("sed_event_mvdr", "sed_event_mvdr_noise")
+        out["noise_frames"] = torch.zeros(E, dtype=torch.int32, device=dev)      # (a call that extracts nothing launches nothing)
+        check(getattr(lib(), name)(*head[0], *head[1], *cols, E, tf, hop, doa.max_frames, ptr(tau), tau.shape[0], mvdr.loading,
+                                   mvdr.noise_blocks, mvdr.noise_guard, ptr(tables), tables.numel() * 4, ptr(out["audio_len"]),
+                                   ptr(out["audio_start"]), ptr(out["audio"]), n_total, ptr(out["noise_frames"]), ptr(ws), ws.numel(),
+                                   stream_ptr()), name)
+        return out
     check(getattr(lib(), names[1])(*head[0], *head[1], *cols, E, tf, hop, doa.max_frames, ptr(tau), tau.shape[0], mvdr.loading,
                                    ptr(tables), tables.numel() * 4, ptr(out["audio_len"]), ptr(out["audio_start"]), ptr(out["audio"]),
                                    n_total, ptr(ws), ws.numel(), stream_ptr()), names[1])
@@ -877,10 +910,8 @@ def event_mvdr_ring(ring, cap, n, channels, events, time_factor, doa, mvdr, sr=S
     rec_key = "stream" if "stream" in events and "rec" not in events else "rec"
     cols, E = _located_cols(events, R, rec_key, dev)
     if E == 0:
-        return _beam_empty(dev)
-    need_one = lib().sed_event_mvdr_ring_workspace_bytes(R, nc, doa.max_frames, hop)
-    if need_one == 0:
-        raise ValueError(f"sed_event_mvdr_ring_workspace_bytes refuses R={R}, channels={nc}, max_frames={doa.max_frames}, hop={hop}")
+        return _mvdr_empty(dev, mvdr)
+    need_one = _mvdr_workspace("sed_event_mvdr_ring", R, nc, doa.max_frames, hop, mvdr)
     head = ([ptr(ring), ring.numel(), cap], [C.c_void_p(n.ctypes.data), R, nc])
     return _mvdr_run(("sed_event_beam_spans_ring", "sed_event_mvdr_ring"), head, cols, E, tf, hop, doa, mvdr, sr,
                      lib().sed_event_beam_ring_workspace_bytes(R), need_one, max_workspace_bytes, dev)

@@ -79,6 +79,32 @@ def stream_locates(onset, offset, peak_frame, time_factor, n_feat, max_frames, l
     return f1 > f0 and int(offset) * int(time_factor) + int(lat) - f0 <= int(history_frames)
 
 
+def stream_noise_frames(hop_length, noise_blocks, noise_guard=1):
+    """``nf``: the feature frames before an event's first that hold the samples its pre-onset noise covariance reads,
+    ``ceil((noise_guard + noise_blocks + 1) * 1024 / hop_length)``; 0 with ``noise_blocks = 0``"""
+    Kn, G, hop = int(noise_blocks), int(noise_guard), int(hop_length)
+    if hop < 1 or Kn < 0 or G < 0:
+        raise ValueError(f"stream_noise_frames needs hop_length >= 1, noise_blocks >= 0 and noise_guard >= 0, got {hop}, {Kn}, {G}")
+    return -(-(G + Kn + 1) * 1024 // hop) if Kn else 0
+
+
+def stream_extracts(onset, offset, peak_frame, time_factor, n_feat, max_frames, lat, history_frames, hop_length, noise_blocks=0,
+                    noise_guard=1):
+    """whether a stream with ``history_frames`` of audio emits this event's audio: ``stream_locates`` it, and —
+    where its weights come from the frames before its onset, ``f0 * hop_length >= (noise_guard + noise_blocks + 1) * 1024`` with
+    ``noise_blocks >= 1`` — the ring still holds those too: ``offset*tf + lat - f0 + nf <= history_frames``,
+    ``nf = stream_noise_frames(...)``.  An event near the feed's start, which falls back to its own frames, needs no more than
+    ``stream_locates`` asks.  The rule reads the event and the settings only; an event it refuses keeps its ``dir`` and comes
+    with ``audio_len = 0``.  (Whether the event is located at all — ``dir >= 0`` — is for the caller to know.)"""
+    if not stream_locates(onset, offset, peak_frame, time_factor, n_feat, max_frames, lat, history_frames):
+        return False
+    f0, _ = event_frames(onset, offset, peak_frame, time_factor, n_feat, max_frames)
+    Kn, G = int(noise_blocks), int(noise_guard)
+    if Kn < 1 or f0 * int(hop_length) < (G + Kn + 1) * 1024:
+        return True
+    return int(offset) * int(time_factor) + int(lat) - f0 + stream_noise_frames(hop_length, Kn, G) <= int(history_frames)
+
+
 @dataclasses.dataclass(frozen=True)
 class TDOA:
     """Settings of per-event localisation (``EventDetector(model, ..., localize=TDOA(...))``).  ``max_lag``: the
@@ -334,6 +360,11 @@ def beam_taps(oversample, half_width, beta):
     return t
 
 
+MVDR_BLOCK = 1024               # mvdr.hip: MV_B, the hop of an event's own transform grid
+MVDR_MAX_NOISE_BLOCKS = 256     # mvdr.hip: MV_MAX_NOISE
+MVDR_MAX_NOISE_GUARD = 64       # mvdr.hip: MV_MAX_GUARD
+
+
 @dataclasses.dataclass(frozen=True)
 class MVDR:
     """Settings of per-event audio extraction by an adaptive beam (``EventDetector(model, ..., localize=DOA(...), extract=MVDR(...))``;
@@ -341,14 +372,34 @@ class MVDR:
     unchanged and let through the least of everything else the event's own frames contain (minimum variance distortionless
     response).  ``loading`` in [1e-6, 1e6]: ``loading * trace(R) / C`` is added to the diagonal of every bin's covariance R before
     the solve; small values adapt hard (and need more frames than microphones to estimate R), large ones approach the plain
-    average of the steered channels."""
+    average of the steered channels.
+
+    ``noise_blocks`` Kn in 0..256 and ``noise_guard`` G in 0..64, in blocks of 1024 samples: with ``Kn >= 1`` the
+    covariance is not the event's own — which holds the target, so that any steering error makes the beam cancel part of it —
+    but that of the Kn frames of 2048 samples before the onset, ``[s0 - (G + Kn + 1) 1024, s0 - G 1024)`` of the recording.  An
+    event that starts earlier than ``(G + Kn + 1) 1024`` samples into its recording keeps its own covariance, wholly;
+    ``noise_frames`` in the results says which events used which (Kn or 0).  ``Kn = 0``: the own frames, for every event.  On
+    live feeds the ring keeps ``stream_noise_frames`` more feature frames."""
     loading: float = 1e-2
+    noise_blocks: int = 0
+    noise_guard: int = 1
 
     def __post_init__(self):
         v = self.loading
         if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not 1e-6 <= float(v) <= 1e6:
             raise ValueError(f"MVDR: loading must be a number in [1e-6, 1e6], got {v!r}")
         object.__setattr__(self, "loading", float(v))
+        for name, most in (("noise_blocks", MVDR_MAX_NOISE_BLOCKS), ("noise_guard", MVDR_MAX_NOISE_GUARD)):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= most:
+                raise ValueError(f"MVDR: {name} must be an integer in [0, {most}], got {v!r}")
+            object.__setattr__(self, name, int(v))
+
+    @property
+    def noise_lead_blocks(self):
+        """``G + Kn + 1``: an event uses the noise covariance iff it starts at least this many blocks of 1024 samples into its
+        recording; 0 with ``noise_blocks = 0``"""
+        return self.noise_guard + self.noise_blocks + 1 if self.noise_blocks else 0
 
 
 @functools.lru_cache(maxsize=1)
@@ -379,7 +430,9 @@ def event_samples(onset, offset, peak_frame, time_factor, n, hop, max_frames, di
     located on the frames ``[f0, f0 + loc_frames)`` with ``f0`` from ``event_frames`` (``n_feat = 1 + n // hop``;
     ``loc_frames`` is read as at most that range), and ``[s0, s1) = [f0 * hop, min((f0 + loc_frames) * hop, n))``.  An event
     that is not extracted — unlocated, beyond its recording, digital silence, refused by a stream's ring rule — and one whose
-    frames start at or beyond sample ``n`` have no samples: ``(0, 0)``."""
+    frames start at or beyond sample ``n`` have no samples: ``(0, 0)``.  These are the samples the audio consists of; an
+    ``MVDR`` beam with ``noise_blocks = Kn >= 1`` also READS ``[s0 - (G + Kn + 1) 1024, s0 - G 1024)`` of the recording for the
+    weights of an event with ``s0 >= (G + Kn + 1) 1024``, which adds no sample to its audio."""
     n, hop = int(n), int(hop)
     if n < 0 or hop < 1:
         raise ValueError(f"event_samples needs n >= 0 and hop >= 1, got {n}, {hop}")

@@ -45,7 +45,8 @@ With ``localize=sed.DOA(...)`` that call is ``sed_event_doa_ring`` a
 (``StreamEvents.doa()``); an event the rule refuses has ``dir = -1``.
 With ``extract=sed.DelaySum(...)`` or ``sed.MVDR(...)`` and ``emit_audio=True`` a step that emitted events makes one
 more call on the same rings, ``feature.event_beamform_ring`` or ``feature.event_mvdr_ring``: the events carry ``audio_start`` and
-``audio_len`` and the call's ``StreamEvents.audio`` holds every located event's audio, the offline call's bit for bit.  Nothing
+``audio_len`` (and, with ``sed.MVDR(noise_blocks >= 1)``, ``noise_frames``: DESIGN 5u) and the call's ``StreamEvents.audio`` holds
+every located event's audio, the offline call's bit for bit.  Nothing
 of it persists between calls: the steps of one push hand their buffers to ``merge_step_audio``.
 """
 import ctypes as C
@@ -55,8 +56,8 @@ import torch
 
 from . import feature
 from ._lib import SedHipError, check, lib, ptr, stream_ptr
-from .detect import (_BEAM_KEYS, _DOA_KEYS, _TDOA_KEYS, EventDetector, _doa_angles, _event_audio, _event_tensors, _intervals, _timed,
-                     _window_jobs, plan_windows)
+from .detect import (_BEAM_KEYS, _DOA_KEYS, _NOISE_KEYS, _TDOA_KEYS, EventDetector, _doa_angles, _event_audio, _event_tensors, _intervals,
+                     _noise_frames, _timed, _window_jobs, plan_windows)
 
 _KEYS = ("stream", "cls", "onset", "offset", "peak", "peak_frame")
 
@@ -218,6 +219,12 @@ class StreamEvents:
         (DESIGN 5t); the host reads the event's two integers."""
         return _event_audio(self, e)
 
+    @property
+    def noise_frames(self):
+        """int32 [E] on the device, as ``DetectionResult.noise_frames``: only on what a stream with
+        ``emit_audio=True`` of a detector with ``extract=sed.MVDR(noise_blocks >= 1)`` returns, otherwise AttributeError"""
+        return _noise_frames(self)
+
 
 class StreamDetector:
     """``EventDetector`` for audio that is still arriving, S streams at once (module docstring).  The keyword arguments are
@@ -230,7 +237,11 @@ class StreamDetector:
     ``emit_audio=True`` (a detector with ``extract=sed.DelaySum(...)`` or ``sed.MVDR(...)``, which does not stream without it;
     DESIGN 5t): a step that emits events also extracts their audio from the rings, ``feature.event_beamform_ring`` or
     ``feature.event_mvdr_ring`` — every located event's audio is the offline call's, bit for bit, in any chunking; an event the
-    rule above refuses has ``dir = -1`` and length 0 (``StreamEvents.audio`` / ``event_audio``).  It costs one more blocking
+    rule above refuses has ``dir = -1`` and length 0 (``StreamEvents.audio`` / ``event_audio``).  With
+    ``extract=sed.MVDR(noise_blocks=Kn)``, ``Kn >= 1``, ``history_frames="min"`` is ``max_frames + lat + nf``,
+    ``nf = localize.stream_noise_frames(...)`` feature frames more, and a located event whose weights come from the frames
+    before its onset gets its audio iff ``b*tf + lat - f0 + nf <= history_frames`` (``localize.stream_extracts``): otherwise it
+    keeps its ``dir`` and has length 0; the events also hold ``noise_frames``.  It costs one more blocking
     8-byte read and one device allocation per step that emits events; ``state_bytes`` does not change."""
 
     def __init__(self, model, n_streams, keep_probs=False, max_new_windows=4, _det=None, input_sr=None, input_channels=None,
@@ -278,10 +289,11 @@ class StreamDetector:
         self.CC = (self.q + 1) * h + feature.NFFT // 2                     # samples per half of a stream's PCM carry (an upper bound)
         # the PCM ring of a localising stream: lat, the history and the samples per lane
         self.lat = self.history_frames = None
+        self.noise_frames = 0
         self.cap, self._ring, self._rws_ring = 0, None, None
         self._ev_keys = _KEYS
         if history_frames is not None:
-            from .localize import stream_latency_frames, stream_ring_samples
+            from .localize import stream_latency_frames, stream_noise_frames, stream_ring_samples
             rows = det.class_settings()
             if any(r["low"] < r["threshold"] for r in rows):
                 raise ValueError("a localising stream needs low == threshold in every class: below the threshold a run that began "
@@ -289,14 +301,18 @@ class StreamDetector:
                                  "any ring keeps its audio (DESIGN 5p)")
             self.lat = stream_latency_frames(tf, det.seq_len, det.median_max, max(r["min_gap"] for r in rows))
             least = det.localize_settings.max_frames + self.lat
+            # the frames before an event's first that its pre-onset noise covariance reads: "min" keeps them too
+            mv = det.extract_settings if self.emit_audio else None
+            self.noise_frames = stream_noise_frames(h, mv.noise_blocks, mv.noise_guard) if getattr(mv, "noise_blocks", 0) else 0
             if not (history_frames == "min" or (isinstance(history_frames, (int, np.integer)) and not isinstance(history_frames, bool))):
                 raise ValueError(f"history_frames must be \"min\" or an integer number of feature frames, got {history_frames!r}")
-            self.history_frames = least if isinstance(history_frames, str) else int(history_frames)
+            self.history_frames = least + self.noise_frames if isinstance(history_frames, str) else int(history_frames)
             if not least <= self.history_frames <= 0x7fffffff:
                 raise ValueError(f"history_frames={self.history_frames} is less than the minimum max_frames + lat = "
                                  f"{det.localize_settings.max_frames} + {self.lat} = {least} feature frames (\"min\")")
             self.cap = stream_ring_samples(self.history_frames, self.step_frames, h, feature.NFFT)
-            self._ev_keys = _KEYS + _TDOA_KEYS + (_DOA_KEYS if det.locates_directions else ()) + (_BEAM_KEYS if self.emit_audio else ())
+            self._ev_keys = _KEYS + _TDOA_KEYS + (_DOA_KEYS if det.locates_directions else ()) + (_BEAM_KEYS if self.emit_audio else ()) + \
+                            (_NOISE_KEYS if self.noise_frames else ())
         self._dims = (S, self.K, self.win_out, self.hop_out, det.median_max, self.max_new)
         self._core_bytes = lib().sed_stream_state_bytes(*self._dims)
         if self._core_bytes == 0:
@@ -557,14 +573,39 @@ class StreamDetector:
         from .localize import MVDR
         det, dev = self.det, self._state.device
         if E == 0:                                                          # no launch, no read
-            events.update({k: v for k, v in feature._beam_empty(dev).items() if k != "audio"})
+            events.update({k: v for k, v in self._no_audio(dev).items() if k != "audio"})
             return torch.empty(0, device=dev)
         entry = feature.event_mvdr_ring if isinstance(det.extract_settings, MVDR) else feature.event_beamform_ring
-        beam = _timed(self.marks, "extract", lambda: entry(self._ring, self.cap, self._n, self.C, events, det.model.time_factor,
+        given = events
+        if self.noise_frames:
+            given = {**events, "dir": self._dir_with_noise_history(events)}
+        beam = _timed(self.marks, "extract", lambda: entry(self._ring, self.cap, self._n, self.C, given, det.model.time_factor,
                                                            det.localize_settings, det.extract_settings, sr=det.sr, hop=det.hop_length))
         audio = beam.pop("audio")
         events.update(beam)
         return audio
+
+    def _no_audio(self, dev):
+        """the extraction columns of an empty event table"""
+        if self.noise_frames:
+            return feature._mvdr_empty(dev, self.det.extract_settings)
+        return feature._beam_empty(dev)
+
+    def _dir_with_noise_history(self, events):
+        """``dir`` for the extraction alone, by device tensor ops (no host read): -1 where the event's weights come from the
+        frames before its onset (``f0 * hop >= (G + Kn + 1) 1024``) and the ring need not hold them any more,
+        ``offset*tf + lat - f0 + nf > history_frames`` (``localize.stream_extracts``).  ``f0`` is ``event_frames``'
+        with the frames the feed has now — an emitted event's frames are final, so it is the offline call's."""
+        det, dev = self.det, events["dir"].device
+        tf, h, mf, mv = det.model.time_factor, det.hop_length, det.localize_settings.max_frames, det.extract_settings
+        n_feat = torch.from_numpy(1 + self._n // h).to(dev)[events["stream"].long()]
+        a, off = events["onset"].long() * tf, events["offset"].long() * tf
+        b = torch.minimum(off, n_feat)
+        c = events["peak_frame"].long() * tf + tf // 2 - mf // 2
+        f0 = torch.where(b - a > mf, torch.minimum(torch.maximum(c, a), b - mf), a)
+        uses = f0 * h >= (mv.noise_guard + mv.noise_blocks + 1) * 1024
+        refused = uses & (off + self.lat - f0 + self.noise_frames > self.history_frames)
+        return torch.where(refused, torch.full_like(events["dir"], -1), events["dir"])
 
     # ── rounds: a push of any size as steps of bounded size ──
     def _run(self, rounds):
@@ -615,7 +656,7 @@ class StreamDetector:
             if self.det.locates_directions:
                 ev.update(dir=torch.empty(0, dtype=torch.int32, device=dev), doa_power=torch.empty(0, device=dev))
             if self.emit_audio:
-                ev.update({k: v for k, v in feature._beam_empty(dev).items() if k != "audio"})
+                ev.update({k: v for k, v in self._no_audio(dev).items() if k != "audio"})
         return ev
 
     def _events(self, ev, offs, final, probs, poffs, audio=None):
