@@ -827,6 +827,25 @@ int sed_tune_sweep(const float* probs, const long* n_out_host, int R, int K, con
                    const int* ref_off, const int* ref_onset, const int* ref_offset, const int* ref_tol, int collar, int block,
                    void* workspace, size_t workspace_bytes, long* counts, void* stream);
 
+/* ───────────── PSDS: intersection criteria over a grid of settings (sed_crnn_amd/tune.py) ─────────────
+ * The integer side of the polyphonic sound detection score: for G decoder settings at once, the events of
+ * sed_detect_events_batch are judged against reference events by how much of them intersects the reference, without writing an
+ * event and without a read back.  probs, n_out_host, settings_host and the reference arrays are those of sed_tune_sweep, with
+ * the same checks and limits.  Criteria in thousandths (dtc_milli, gtc_milli in 1..1000; cttc_milli in 1..1000, or 0 for no
+ * cross triggers); |x ∩ G_c| = the frames of x covered by reference events of class c; every comparison is a 64-bit integer
+ * one.  Per (setting, recording, class k), with D the system events: d in D is relevant iff 1000 |d ∩ G_k| >= dtc_milli |d|; a
+ * reference event t of class k is a true positive iff 1000 (sum over relevant d of |d ∩ t|) >= gtc_milli |t|; every other d is
+ * a false positive of class k and, when cttc_milli > 0, a cross trigger (k -> c) for every class c != k with
+ * 1000 |d ∩ G_c| >= cttc_milli |d|.  counts [G][K][4] (device, int64, cleared by the call) = tp, n_ref, n_sys, fp summed over
+ * recordings; ct [G][K][K] (device, int64; row k, column c = cross triggers of detections of class k on the reference of class
+ * c, the diagonal 0) is cleared and written only when cttc_milli > 0 and may be NULL otherwise.  The workspace is
+ * sed_tune_sweep's with a per-frame prefix: >= sed_psds_workspace_bytes(n_total, K, R, n_tracks, G) (0 = bad sizes).  G = 0 is a
+ * no-op that returns 0 once the recording table has been checked. */
+size_t sed_psds_workspace_bytes(long n_total, int K, int R, int n_tracks, int G);
+int sed_psds_sweep(const float* probs, const long* n_out_host, int R, int K, const sed_tune_setting* settings_host, int G,
+                   const int* ref_off, const int* ref_onset, const int* ref_offset, int dtc_milli, int gtc_milli, int cttc_milli,
+                   void* workspace, size_t workspace_bytes, long* counts, long* ct, void* stream);
+
 /* ───────────── live streams (sed_crnn_amd/stream.py) ─────────────
  * S feeds keep their state on the device between calls, in ONE caller-owned buffer of sed_stream_state_bytes(...) bytes (0 = bad
  * sizes: S in 1..65535, K in 1..32, 1 <= hop_out <= win_out, median odd 1..31, max_new_windows in 1..1024; the size depends on

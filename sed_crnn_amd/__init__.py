@@ -20,7 +20,7 @@ from .model import (HipCRNN, LightningTimePooledCRNN, SEDNet, TimePooledCRNN,  #
                     get_model)
 from .resample import ResamplePlan, resample, resample_many  # noqa: F401
 from .stream import StreamDetector, StreamEvents, StreamSchedule, StreamSchedules  # noqa: F401
-from .tune import DecoderGrid, ReferenceEvents, SweepResult, tune_decoder  # noqa: F401
+from .tune import DecoderGrid, PSDSCriteria, PSDSResult, ReferenceEvents, SweepResult, psds_sweep, tune_decoder  # noqa: F401
 from .optim import FusedAdam, clip_grad_norm_  # noqa: F401
 
 __version__ = "0.1.0"

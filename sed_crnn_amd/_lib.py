@@ -200,6 +200,8 @@ SIGNATURES = {
     "sed_detect_events_batch": (_i, [_fp, _fp, _i, _i, _i, _f, _f, _i, _i, _i, _fp, _sz, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _stream]),
     "sed_tune_workspace_bytes": (_sz, [_l, _i, _i, _i, _i]),
     "sed_tune_sweep": (_i, [_fp, _fp, _i, _i, _fp, _i, _fp, _fp, _fp, _fp, _i, _i, _fp, _sz, _fp, _stream]),
+    "sed_psds_workspace_bytes": (_sz, [_l, _i, _i, _i, _i]),
+    "sed_psds_sweep": (_i, [_fp, _fp, _i, _i, _fp, _i, _fp, _fp, _fp, _i, _i, _i, _fp, _sz, _fp, _fp, _stream]),
     "sed_stream_state_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "sed_stream_init": (_i, [_fp, _sz, _i, _i, _i, _i, _i, _i, _stream]),
     "sed_stream_reset": (_i, [_fp, _sz, _i, _i, _i, _i, _i, _i, _fp, _i, _stream]),

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libsedcrnn.so")
-SOURCES = ["api.cpp", "conv.hip", "conv_bf16.hip", "wino.hip", "conv1.hip", "bnpool.hip", "gemm.hip", "gru.hip", "misc.hip", "logmel.hip", "gcc.hip", "tdoa.hip", "doa.hip", "beam.hip", "mvdr.hip", "pcen.hip", "resample.hip", "data.hip", "detect.hip", "tune.hip", "stream.hip", "net.hip"]
+SOURCES = ["api.cpp", "conv.hip", "conv_bf16.hip", "wino.hip", "conv1.hip", "bnpool.hip", "gemm.hip", "gru.hip", "misc.hip", "logmel.hip", "gcc.hip", "tdoa.hip", "doa.hip", "beam.hip", "mvdr.hip", "pcen.hip", "resample.hip", "data.hip", "detect.hip", "tune.hip", "psds.hip", "stream.hip", "net.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # per-file extras.  logmel: the SLP vectoriser packs the FFT's scalar adds into v_pk_add_f32 and pays for it with ~600
 # v_mov per frame pair to build the register pairs (packed f32 is no faster than scalar on gfx950)
@@ -26,7 +26,8 @@ EXTRA_FLAGS = {"logmel.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-reso
                "conv.hip": ["-Rpass-analysis=kernel-resource-usage"],
                "wino.hip": ["-Rpass-analysis=kernel-resource-usage"],
                "conv_bf16.hip": ["-Rpass-analysis=kernel-resource-usage"],
-               "gemm.hip": ["-Rpass-analysis=kernel-resource-usage"]}
+               "gemm.hip": ["-Rpass-analysis=kernel-resource-usage"],
+               "psds.hip": ["-Rpass-analysis=kernel-resource-usage"]}
 # Kernels whose inline-asm loads are consumed after HAND-COUNTED s_waitcnt vmcnt(N) immediates (conv.hip: the fp32 and the
 # bf16x3 conv forward).  The counts are only right while hipcc keeps the load destinations in registers between the asm load
 # and its use: a spill (scratch store/reload) would insert memory operations the counts do not know about and the MFMAs
@@ -67,7 +68,10 @@ NO_SCRATCH_KERNELS = {"wino.hip": ("conv3x3_wino_k",),
                       # fp32 GEMM: a staged K-step lives in registers for a whole MFMA block beside 64 accumulators (128 x 128 tile,
                       # two workgroups per CU); the 4 x 4 block staging regroups 16 of them per operand.  A spill would put a
                       # scratch round trip in front of every LDS store of the K loop and fail no test
-                      "gemm.hip": ("gemm_f32_k",)}
+                      "gemm.hip": ("gemm_f32_k",),
+                      # PSDS sweep: lane 0 walks every event serially with a reference pointer, an open coverage sum and four
+                      # counters live; one of them in scratch would put a memory round trip on every step of that walk
+                      "psds.hip": ("psds_walk_k",)}
 
 
 def _hipcc():
@@ -107,7 +111,7 @@ def check_no_spill(remarks, kernels, allow_agprs=False):
 def build(force=False, verbose=False):
     os.makedirs(OBJ, exist_ok=True)
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_shared.h"), os.path.join(CSRC, "detect_shared.h"), os.path.join(CSRC, "fft2048.h"), os.path.join(CSRC, "tdoa_shared.h"), os.path.join(CSRC, "phat_shared.h"), os.path.join(CSRC, "beam_shared.h"), os.path.join(HERE, "..", "include", "sedcrnn.h")]
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_shared.h"), os.path.join(CSRC, "detect_shared.h"), os.path.join(CSRC, "tune_shared.h"), os.path.join(CSRC, "fft2048.h"), os.path.join(CSRC, "tdoa_shared.h"), os.path.join(CSRC, "phat_shared.h"), os.path.join(CSRC, "beam_shared.h"), os.path.join(HERE, "..", "include", "sedcrnn.h")]
     jobs = []
     objs = []
     for src in SOURCES:

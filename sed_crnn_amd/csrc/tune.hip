@@ -6,55 +6,15 @@
 //   1. detect_bits_seg_k<M> of detect_shared.h — the bit-track kernel of sed_detect_events_batch — with a list of thresholds,
 //      one launch per distinct median width: the track is filtered once per width and one bit track is packed per distinct
 //      (width, threshold value); lo and hi of every setting index into that pool.
-//   2. tune_refblocks_k: per (recording, class) the prefix count of reference-active blocks, P[b] = active blocks before block b.
+//   2. tune_refblocks_k of tune_shared.h: per (recording, class) the prefix count of reference-active blocks, P[b] = active
+//      blocks before block b.
 //   3. tune_walk_k, one wave per (setting, class, group of recordings): detect_walk_body of detect_shared.h — the walk of
 //      detect_walk_k — whose finished events go through the matcher and the block counter instead of being stored; the wave sums
 //      its recordings in registers and adds six integers to counts[g][k] at the end.
 #include <vector>
 #include "common.h"
 #include "detect_shared.h"
-
-// One wave per (recording, class).  Block b = frames [b block, (b+1) block) is reference-active when a reference event covers one
-// of its frames: the events are sorted and disjoint, so that is the first event whose offset lies beyond the block's start.
-// P [n_blk + 1] at K*blk_off[r] + k*(n_blk + 1): exclusive prefix counts, P[n_blk] = the number of active blocks.
-__global__ __launch_bounds__(64) void tune_refblocks_k(const int* __restrict__ out_off, const int* __restrict__ blk_off, int K, int block,
-                                                       const int* __restrict__ ref_off, const int* __restrict__ ref_onset,
-                                                       const int* __restrict__ ref_offset, int* __restrict__ P) {
-    const int lane = threadIdx.x, r = (int)blockIdx.x / K, k = (int)blockIdx.x - r * K;
-    const int n_out = out_off[r + 1] - out_off[r];
-    const int n_blk = blk_off[r + 1] - blk_off[r] - 1;
-    int* p = P + (size_t)K * blk_off[r] + (size_t)k * (n_blk + 1);
-    const int j0 = ref_off[blockIdx.x], j1 = ref_off[blockIdx.x + 1];
-    int carry = 0;
-    for (int b0 = 0; b0 < n_blk; b0 += 64) {
-        const int b = b0 + lane;
-        int act = 0;
-        if (b < n_blk) {
-            const long start = (long)b * block;
-            long end = start + block;
-            if (end > n_out) end = n_out;
-            int lo = j0, hi = j1;                                     // first event with offset > start
-            while (lo < hi) {
-                const int mid = lo + ((hi - lo) >> 1);
-                if (ref_offset[mid] > start) hi = mid;
-                else lo = mid + 1;
-            }
-            act = lo < j1 && ref_onset[lo] < end;
-        }
-        int x = act;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int y = __shfl_up(x, o, 64);
-            if (lane >= o) x += y;
-        }
-        if (b < n_blk) p[b] = carry + x - act;
-        carry += __shfl(x, 63, 64);
-    }
-    if (lane == 0) p[n_blk] = carry;
-}
-
-// a setting on the device: which bit tracks it reads and the constants of its walk
-struct TuneSet { int lo_track, hi_track, min_gap, min_len; };
+#include "tune_shared.h"
 
 // What lane 0 does with every finished event of one (setting, recording, class): the matcher and the block counter.  The first
 // TUNE_REF_LDS reference events and TUNE_P_LDS block prefix counts of the (recording, class) are staged in LDS by the whole wave
@@ -98,7 +58,6 @@ struct TuneEmit {
     }
 };
 
-#define TUNE_REC_PER_WAVE 8
 // workgroup (one wave) = (g, k, rs): recordings rs, rs + RS, ... of setting g and class k
 __global__ __launch_bounds__(64) void tune_walk_k(const unsigned long long* __restrict__ bits, size_t track_words,
                                                   const TuneSet* __restrict__ sets, const int* __restrict__ word_off,
@@ -146,18 +105,9 @@ __global__ __launch_bounds__(64) void tune_walk_k(const unsigned long long* __re
     }
 }
 
-// workspace (16-byte aligned regions): out_off, word_off, blk_off [R+1] each (one upload); the settings [G]; the thresholds
-// [n_tracks]; the block prefix counts, at most K (n_total + R) ints (block >= 1); then n_tracks bit tracks of K words each,
-// words <= n_total/64 + R
-#define TUNE_MAX_G (1 << 20)
-
+// the workspace is tune_shared.h's: the offset tables, the settings, the thresholds, the block prefix counts, the bit tracks
 extern "C" size_t sed_tune_workspace_bytes(long n_total, int K, int R, int n_tracks, int G) {
-    if (R < 1 || n_total < R || n_total > 0x7fffffffL || K < 1 || K > 32 || n_total * K > 0x7fffffffL) return 0;
-    if (G < 1 || G > TUNE_MAX_G || n_tracks < 1 || n_tracks > 2 * (long)G) return 0;
-    if (n_total / 64 + R > 0x7fffffffL) return 0;
-    const size_t words = (size_t)(n_total / 64 + R);
-    return al16((size_t)3 * (R + 1) * 4) + al16((size_t)G * sizeof(TuneSet)) + al16((size_t)n_tracks * 4) +
-           al16((size_t)K * ((size_t)n_total + R) * 4) + (size_t)n_tracks * K * words * sizeof(unsigned long long);
+    return tune_workspace_bytes(n_total, K, R, n_tracks, G);
 }
 
 extern "C" int sed_tune_sweep(const float* probs, const long* n_out_host, int R, int K, const sed_tune_setting* settings_host, int G,
@@ -179,36 +129,9 @@ extern "C" int sed_tune_sweep(const float* probs, const long* n_out_host, int R,
     blk_off[R] = (int)blks;
     if (G == 0) return 0;
     SED_REQUIRE(settings_host, "tune_sweep: null pointer (settings_host)");
-    // the pool of bit tracks: distinct (median, threshold value), grouped by median in order of first appearance
-    std::vector<int> med_of;                                          // distinct medians
-    std::vector<std::vector<float>> thr_of;                           // their distinct thresholds
-    std::vector<int> lo_m(G), lo_i(G), hi_i(G);
-    for (int g = 0; g < G; ++g) {
-        const sed_tune_setting& t = settings_host[g];
-        SED_TRY(detect_check_decoder("tune_sweep", g, t.median, t.lo, t.hi, t.min_gap, t.min_len));
-        size_t m = 0;
-        while (m < med_of.size() && med_of[m] != t.median) ++m;
-        if (m == med_of.size()) { med_of.push_back(t.median); thr_of.emplace_back(); }
-        auto slot = [&](float v) {
-            std::vector<float>& th = thr_of[m];
-            size_t i = 0;
-            while (i < th.size() && !(th[i] == v)) ++i;
-            if (i == th.size()) th.push_back(v);
-            return (int)i;
-        };
-        lo_m[g] = (int)m;
-        lo_i[g] = slot(t.lo);
-        hi_i[g] = slot(t.hi);
-    }
-    std::vector<int> first(med_of.size() + 1, 0);
-    for (size_t m = 0; m < med_of.size(); ++m) first[m + 1] = first[m] + (int)thr_of[m].size();
-    const int n_tracks = first.back();
-    std::vector<float> thr(n_tracks);
-    for (size_t m = 0; m < med_of.size(); ++m)
-        for (size_t i = 0; i < thr_of[m].size(); ++i) thr[first[m] + i] = thr_of[m][i];
-    std::vector<TuneSet> sets(G);
-    for (int g = 0; g < G; ++g)
-        sets[g] = TuneSet{first[lo_m[g]] + lo_i[g], first[lo_m[g]] + hi_i[g], settings_host[g].min_gap, settings_host[g].min_len};
+    TunePool pool;                                                    // distinct (median, threshold value) -> one bit track
+    SED_TRY(tune_track_pool("tune_sweep", settings_host, G, pool));
+    const int n_tracks = pool.n_tracks;
 
     const size_t need = sed_tune_workspace_bytes(rows, K, R, n_tracks, G);
     SED_REQUIRE(need > 0, "tune_sweep: bad sizes (R=%d, K=%d, %ld output frames, G=%d)", R, K, rows, G);
@@ -218,30 +141,24 @@ extern "C" int sed_tune_sweep(const float* probs, const long* n_out_host, int R,
     const int RS = (R + TUNE_REC_PER_WAVE - 1) / TUNE_REC_PER_WAVE;
     SED_REQUIRE((long)G * K * RS <= 0x7fffffffL, "tune_sweep: G*K*R = %d*%d*%d is too large for one call", G, K, R);
 
-    char* p = (char*)workspace;
-    int* d_off = (int*)p; p += al16((size_t)3 * (R + 1) * 4);
-    TuneSet* d_sets = (TuneSet*)p; p += al16((size_t)G * sizeof(TuneSet));
-    float* d_thr = (float*)p; p += al16((size_t)n_tracks * 4);
-    int* d_P = (int*)p; p += al16((size_t)K * ((size_t)rows + R) * 4);
-    unsigned long long* d_bits = (unsigned long long*)p;
-    const int *d_out_off = d_off, *d_word_off = d_off + R + 1, *d_blk_off = d_off + 2 * (R + 1);
+    const TuneWorkspace w = tune_carve(workspace, rows, K, R, n_tracks, G);
     const size_t track_words = (size_t)K * words;                     // words <= rows/64 + R: inside the workspace
 
     hipStream_t s = as_stream(stream);
-    SED_TRY(detect_upload("tune_sweep", d_off, h.data(), h.size() * 4, s));
-    SED_TRY(detect_upload("tune_sweep", d_sets, sets.data(), sets.size() * sizeof(TuneSet), s));
-    SED_TRY(detect_upload("tune_sweep", d_thr, thr.data(), thr.size() * 4, s));
+    SED_TRY(detect_upload("tune_sweep", w.out_off, h.data(), h.size() * 4, s));
+    SED_TRY(detect_upload("tune_sweep", w.sets, pool.sets.data(), pool.sets.size() * sizeof(TuneSet), s));
+    SED_TRY(detect_upload("tune_sweep", w.thr, pool.thr.data(), pool.thr.size() * 4, s));
     const hipError_t e = hipMemsetAsync(counts, 0, (size_t)G * K * 6 * sizeof(long), s);
     if (e != hipSuccess) { sed_set_error("tune_sweep: clearing counts: %s", hipGetErrorString(e)); return (int)e; }
-    for (size_t m = 0; m < med_of.size(); ++m) {
-        launch_bits_seg(med_of[m], probs, d_out_off, d_word_off, R, K, words, ThresholdList{d_thr + first[m], (int)thr_of[m].size()},
-                        track_words, d_bits + (size_t)first[m] * track_words, s);
+    for (size_t m = 0; m < pool.med_of.size(); ++m) {
+        launch_bits_seg(pool.med_of[m], probs, w.out_off, w.word_off, R, K, words, ThresholdList{w.thr + pool.first[m], pool.n_thr[m]},
+                        track_words, w.bits + (size_t)pool.first[m] * track_words, s);
         SED_LAUNCH_CHECK("tune_bits");
     }
-    tune_refblocks_k<<<(unsigned)((long)R * K), 64, 0, s>>>(d_out_off, d_blk_off, K, block, ref_off, ref_onset, ref_offset, d_P);
+    tune_refblocks_k<<<(unsigned)((long)R * K), 64, 0, s>>>(w.out_off, w.blk_off, K, block, ref_off, ref_onset, ref_offset, w.P);
     SED_LAUNCH_CHECK("tune_refblocks");
-    tune_walk_k<<<(unsigned)((long)G * K * RS), 64, 0, s>>>(d_bits, track_words, d_sets, d_word_off, d_blk_off, R, K, RS, ref_off,
-                                                           ref_onset, ref_offset, ref_tol, d_P, collar, block,
+    tune_walk_k<<<(unsigned)((long)G * K * RS), 64, 0, s>>>(w.bits, track_words, w.sets, w.word_off, w.blk_off, R, K, RS, ref_off,
+                                                           ref_onset, ref_offset, ref_tol, w.P, collar, block,
                                                            (unsigned long long*)counts);
     SED_LAUNCH_CHECK("tune_walk");
     return 0;

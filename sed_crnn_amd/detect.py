@@ -545,6 +545,23 @@ class EventDetector:
         row = res.counts[g, torch.arange(len(self._classes), device=dev)].unsqueeze(0).contiguous()
         return SweepResult(row, [self.decoder_settings()], res.collar, res.block, res.n_slices, res.n_tracks, res.workspace_bytes)
 
+    def psds(self, track, ref, thresholds=50, criteria=None, grid=None, max_workspace_bytes=1 << 30):
+        """The polyphonic sound detection score of a track against ``ref`` over a sweep of thresholds, on the device ->
+        ``PSDSResult`` (``tune.psds_sweep``): no threshold has to be picked to compare two nets, front ends or
+        decoders.  ``thresholds``: an int n for ``np.linspace(0.01, 0.99, n)``, or a sequence; each value is one setting with
+        this detector's median, min_gap and min_len and lo = hi = the value.  An explicit ``grid`` (a ``DecoderGrid``) overrides
+        ``thresholds``; a class-wise detector needs one, it has no single median to sweep around.  ``criteria``: a
+        ``PSDSCriteria``, default ``PSDSCriteria.scenario1()``.  Rates are per hour of ``frame_seconds``."""
+        from . import tune
+        if grid is None:
+            if self.classwise:
+                raise ValueError("a class-wise detector has no single median to sweep thresholds around: give an explicit grid")
+            values = np.linspace(0.01, 0.99, thresholds) if isinstance(thresholds, (int, np.integer)) else list(thresholds)
+            grid = tune.DecoderGrid.from_settings([dict(threshold=float(v), median=self.median, min_gap=self.min_gap, min_len=self.min_len)
+                                                   for v in values])
+        criteria = tune.PSDSCriteria.scenario1() if criteria is None else criteria
+        return tune.psds_sweep(track, ref, grid, criteria, self.frame_seconds, max_workspace_bytes, self._tune_cache)
+
     # ── the whole path ──
     def __call__(self, waveform, sr=None, channels=1):
         """mono PCM (1-D tensor / ndarray) -> DetectionResult.  The log-mel front end is ``feature.mbe(..., mean, std)``.

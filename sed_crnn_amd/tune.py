@@ -14,7 +14,11 @@ them (the partial last block is kept, blocks never straddle recordings); a block
 events covers one of its frames.
 
 ``counts`` [G, K, 6] int64 = (ev_tp, n_sys, n_ref, seg_tp, seg_sys, seg_ref) summed over recordings: integers, so exact and
-repeatable.  The sweep is one ``sed_tune_sweep`` call per slice of the grid: no event is written, nothing is read back."""
+repeatable.  The sweep is one ``sed_tune_sweep`` call per slice of the grid: no event is written, nothing is read back.
+
+The polyphonic sound detection score (the last section of this module) judges the same system events by how much of
+them intersects the reference instead of by a collar, over a sweep of thresholds: ``psds_sweep`` is one ``sed_psds_sweep``
+call per slice, ``PSDSResult`` the float64 score on its integer counts."""
 import ctypes as C
 import itertools
 
@@ -361,11 +365,10 @@ def _track(track):
     return probs, [int(o) for o in out_off]
 
 
-def sweep(track, ref, grid, collar=1, offset_collar=None, offset_percent=None, block=1, max_workspace_bytes=1 << 30, cache=None):
-    """Score every setting of ``grid`` on a packed track against ``ref`` (module docstring) -> SweepResult.  The grid is split
-    into consecutive slices whose workspace (it grows with the number of distinct bit tracks) fits ``max_workspace_bytes``; each
-    slice writes its own rows of ``counts``, so the result does not depend on the split.  ``cache``: a dict that keeps the
-    workspace between calls."""
+# what sweep and psds_sweep share: the checks of their three arguments, the device requirement, the slicing of the grid by
+# workspace, the workspace itself and the settings as the entries take them
+def _checked_types(track, ref, grid):
+    """-> (probs, out_off) of ``_track`` once ref, grid and the track have the right types"""
     probs, out_off = _track(track)
     if not isinstance(ref, ReferenceEvents):
         raise TypeError(f"ref must be a ReferenceEvents, got {type(ref).__name__}")
@@ -373,10 +376,11 @@ def sweep(track, ref, grid, collar=1, offset_collar=None, offset_percent=None, b
         raise TypeError(f"grid must be a DecoderGrid, got {type(grid).__name__}")
     if not (torch.is_tensor(probs) and probs.dim() == 2):
         raise ValueError("the track must be a [n_total, K] tensor of probabilities")
-    if not 0 <= int(collar) <= 31:
-        raise ValueError(f"collar must be in 0..31 output frames, got {collar}")
-    if int(block) < 1:
-        raise ValueError(f"block must be >= 1 output frame, got {block}")
+    return probs, out_off
+
+
+def _checked_sizes(probs, out_off, ref):
+    """-> (n_out int64 [R], R, K) once the reference fits the track recording by recording"""
     n_out = np.ascontiguousarray(np.diff(np.asarray(out_off, dtype=np.int64)))
     R, K = n_out.size, int(probs.shape[1])
     if out_off[0] != 0 or out_off[-1] != probs.shape[0]:
@@ -386,51 +390,85 @@ def sweep(track, ref, grid, collar=1, offset_collar=None, offset_percent=None, b
     for r in range(R):
         if ref.n_out[r] != int(n_out[r]):
             raise ValueError(f"recording {r}: the reference was built for {ref.n_out[r]} output frames, the track has {int(n_out[r])}")
-    tol = ref.tolerances(offset_collar, offset_percent)
+    return n_out, R, K
+
+
+def _on_gpu(probs):
     if not probs.is_cuda:
         raise SedHipError("sed_crnn_amd: the track must be on the GPU; there is no CPU fallback")
-    dev = probs.device
-    probs = probs.contiguous().float()
+    return probs.contiguous().float()
+
+
+def _grid_slices(grid, n_total, K, R, max_workspace_bytes, bytes_fn, fn_name):
+    """consecutive slices [(g0, g1, workspace bytes, bit tracks)] of the grid that fit the budget; ``bytes_fn(n_total, K, R,
+    n_tracks, G)`` is the entry's size query"""
     G = len(grid)
-    counts = torch.zeros(G, K, 6, dtype=torch.int64, device=dev)
-    if G == 0 or R == 0:
-        return SweepResult(counts, grid, int(collar), int(block), 0)
-    n_total = int(probs.shape[0])
-    L = lib()
-    # consecutive slices that fit the budget
     slices, g0 = [], 0
     while g0 < G:
         rest = grid.n_tracks(g0, G)                                   # the usual case: everything that is left fits, one query
-        b = L.sed_tune_workspace_bytes(n_total, K, R, rest, G - g0)
+        b = bytes_fn(n_total, K, R, rest, G - g0)
         if 0 < b <= max_workspace_bytes and (G - g0) * K * R < 2 ** 31:
             slices.append((g0, G, b, rest))
             break
         keys, g1, need = set(), g0, 0
         while g1 < G:
             k2 = keys.union(grid.track_keys(grid.settings[g1]))
-            b = L.sed_tune_workspace_bytes(n_total, K, R, len(k2), g1 + 1 - g0)
+            b = bytes_fn(n_total, K, R, len(k2), g1 + 1 - g0)
             if b == 0 and g1 == g0:
-                raise ValueError(f"sed_tune_workspace_bytes refuses {n_total} output frames of {K} classes in {R} recordings")
+                raise ValueError(f"{fn_name} refuses {n_total} output frames of {K} classes in {R} recordings")
             if b == 0 or b > max_workspace_bytes or (g1 + 1 - g0) * K * R >= 2 ** 31:
                 break
             keys, need, g1 = k2, b, g1 + 1
         if g1 == g0:
             raise ValueError(f"max_workspace_bytes={max_workspace_bytes} does not hold a single setting "
-                             f"({L.sed_tune_workspace_bytes(n_total, K, R, len(k2), 1)} bytes)")
+                             f"({bytes_fn(n_total, K, R, len(k2), 1)} bytes)")
         slices.append((g0, g1, need, len(keys)))
         g0 = g1
+    return slices
+
+
+def _workspace(slices, cache, dev):
+    """-> (uint8 tensor that holds the largest slice, its size); ``cache``: a dict that keeps it between calls"""
     need = max(s[2] for s in slices)
     cache = {} if cache is None else cache
     ws = cache.get("ws")
     if ws is None or ws.numel() < need or ws.device != dev:
         ws = cache["ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
+    return ws, need
+
+
+def _settings_array(grid, a, b):
+    return (TuneSetting * (b - a))(*[TuneSetting(s["median"], s["low"], s["threshold"], s["min_gap"], s["min_len"])
+                                     for s in grid.settings[a:b]])
+
+
+def sweep(track, ref, grid, collar=1, offset_collar=None, offset_percent=None, block=1, max_workspace_bytes=1 << 30, cache=None):
+    """Score every setting of ``grid`` on a packed track against ``ref`` (module docstring) -> SweepResult.  The grid is split
+    into consecutive slices whose workspace (it grows with the number of distinct bit tracks) fits ``max_workspace_bytes``; each
+    slice writes its own rows of ``counts``, so the result does not depend on the split.  ``cache``: a dict that keeps the
+    workspace between calls."""
+    probs, out_off = _checked_types(track, ref, grid)
+    if not 0 <= int(collar) <= 31:
+        raise ValueError(f"collar must be in 0..31 output frames, got {collar}")
+    if int(block) < 1:
+        raise ValueError(f"block must be >= 1 output frame, got {block}")
+    n_out, R, K = _checked_sizes(probs, out_off, ref)
+    tol = ref.tolerances(offset_collar, offset_percent)
+    probs = _on_gpu(probs)
+    dev = probs.device
+    G = len(grid)
+    counts = torch.zeros(G, K, 6, dtype=torch.int64, device=dev)
+    if G == 0 or R == 0:
+        return SweepResult(counts, grid, int(collar), int(block), 0)
+    L = lib()
+    slices = _grid_slices(grid, int(probs.shape[0]), K, R, max_workspace_bytes, L.sed_tune_workspace_bytes, "sed_tune_workspace_bytes")
+    ws, need = _workspace(slices, cache, dev)
     d_off, d_on, d_offs = ref.device(dev)
     d_tol = ref.device_tolerances(dev, offset_collar, offset_percent, tol)
     for a, b, _, _ in slices:
-        arr = (TuneSetting * (b - a))(*[TuneSetting(s["median"], s["low"], s["threshold"], s["min_gap"], s["min_len"])
-                                        for s in grid.settings[a:b]])
-        check(L.sed_tune_sweep(ptr(probs), C.c_void_p(n_out.ctypes.data), R, K, C.cast(arr, C.c_void_p), b - a, ptr(d_off), ptr(d_on),
-                               ptr(d_offs), ptr(d_tol), int(collar), int(block), ptr(ws), ws.numel(), ptr(counts[a:b]), stream_ptr()),
+        check(L.sed_tune_sweep(ptr(probs), C.c_void_p(n_out.ctypes.data), R, K, C.cast(_settings_array(grid, a, b), C.c_void_p), b - a,
+                               ptr(d_off), ptr(d_on), ptr(d_offs), ptr(d_tol), int(collar), int(block), ptr(ws), ws.numel(),
+                               ptr(counts[a:b]), stream_ptr()),
               "sed_tune_sweep")
     return SweepResult(counts, grid, int(collar), int(block), len(slices), max(s[3] for s in slices), need)
 
@@ -444,3 +482,173 @@ def tune_decoder(det, track, ref, grid, metric="f1_event", average="micro", per_
         return det.with_decoder(**res.best_per_class(metric)[1]), res
     _, best, _ = res.best(metric, average)
     return det.with_decoder(**best), res
+
+
+# ───────────────────────── PSDS: intersection criteria, threshold-free score ─────────────────────────
+PSDS_COUNT_NAMES = ("tp", "n_ref", "n_sys", "fp")
+
+
+def _milli(value, name, lowest=1):
+    """a criterion in 0..1 as integer thousandths; ValueError unless it is a multiple of 0.001 (to within 1e-9) in range"""
+    v = float(value)
+    if not np.isfinite(v):
+        raise ValueError(f"{name}={value} must be a number in {lowest / 1000:g}..1")
+    m = int(round(v * 1000.0))
+    if not abs(v - m / 1000.0) <= 1e-9:
+        raise ValueError(f"{name}={value} must be a multiple of 0.001")
+    if not lowest <= m <= 1000:
+        raise ValueError(f"{name}={value} must be in {lowest / 1000:g}..1")
+    return m
+
+
+class PSDSCriteria:
+    """The intersection criteria and the weights of the polyphonic sound detection score (module section above).
+    ``dtc`` / ``gtc`` / ``cttc``: fractions in (0, 1], multiples of 0.001 (the device compares integers in thousandths);
+    ``cttc=None``: no cross triggers.  ``alpha_ct`` weighs the cross-trigger rate in the effective false-positive rate,
+    ``alpha_st`` the standard deviation across classes; ``e_max`` is the largest effective FPR (per hour) of the area."""
+
+    def __init__(self, dtc=0.7, gtc=0.7, cttc=None, alpha_ct=0.0, alpha_st=1.0, e_max=100.0):
+        self.dtc_milli, self.gtc_milli = _milli(dtc, "dtc"), _milli(gtc, "gtc")
+        self.cttc_milli = 0 if cttc is None else _milli(cttc, "cttc")
+        self.dtc, self.gtc, self.cttc = self.dtc_milli / 1000.0, self.gtc_milli / 1000.0, None if cttc is None else self.cttc_milli / 1000.0
+        self.alpha_ct, self.alpha_st, self.e_max = float(alpha_ct), float(alpha_st), float(e_max)
+        if not self.alpha_ct >= 0.0 or not self.alpha_st >= 0.0:
+            raise ValueError(f"alpha_ct={alpha_ct} and alpha_st={alpha_st} must not be negative")
+        if self.alpha_ct > 0.0 and cttc is None:
+            raise ValueError(f"alpha_ct={alpha_ct} needs a cross-trigger criterion: give cttc")
+        if not (self.e_max > 0.0 and np.isfinite(self.e_max)):
+            raise ValueError(f"e_max={e_max} must be positive and finite")
+
+    @classmethod
+    def scenario1(cls):
+        """DCASE scenario 1: react fast, localise precisely (dtc = gtc = 0.7, no cross triggers, alpha_st = 1, e_max = 100)"""
+        return cls(0.7, 0.7, None, 0.0, 1.0, 100.0)
+
+    @classmethod
+    def scenario2(cls):
+        """DCASE scenario 2: do not confuse classes (dtc = gtc = 0.1, cttc = 0.3, alpha_ct = 0.5, alpha_st = 1, e_max = 100)"""
+        return cls(0.1, 0.1, 0.3, 0.5, 1.0, 100.0)
+
+    def __repr__(self):
+        return (f"PSDSCriteria(dtc={self.dtc}, gtc={self.gtc}, cttc={self.cttc}, alpha_ct={self.alpha_ct}, alpha_st={self.alpha_st}, "
+                f"e_max={self.e_max})")
+
+
+class PSDSResult:
+    """``counts`` [G, K, 4] int64 (PSDS_COUNT_NAMES) and ``ct`` [G, K, K] int64 (row k, column c: cross triggers of detections of
+    class k on the reference of class c; zeros without a cross-trigger criterion) on the device; ``table()`` is the one host
+    read (cached).  ``total_seconds`` = T, ``class_seconds`` [K] = T_c.  Everything else is float64 on those integers."""
+
+    def __init__(self, counts, ct, grid, criteria, total_seconds, class_seconds, n_slices=1, n_tracks=0, workspace_bytes=0):
+        self.counts, self.ct, self.grid, self.criteria = counts, ct, grid, criteria
+        self.total_seconds, self.class_seconds = float(total_seconds), np.asarray(class_seconds, np.float64)
+        self.n_slices, self.n_tracks, self.workspace_bytes = n_slices, n_tracks, workspace_bytes
+        self._table = None
+
+    def __len__(self):
+        return len(self.grid)
+
+    def table(self):
+        """(counts, ct) as numpy arrays"""
+        if self._table is None:
+            self._table = (self.counts.cpu().numpy(), self.ct.cpu().numpy())
+        return self._table
+
+    def rates(self):
+        """(TPR [G, K], FPR [G, K], CTR [G, K, K], eFPR [G, K]): TPR = tp / n_ref (NaN for a class without reference), FPR and
+        CTR per hour, eFPR = FPR + alpha_ct · the mean of CTR over the other classes that have reference time"""
+        counts, ct = self.table()
+        c = counts.astype(np.float64)
+        K = c.shape[1]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            tpr = c[..., 0] / c[..., 1]
+            fpr = c[..., 3] / (self.total_seconds / 3600.0)
+            ctr = ct.astype(np.float64) / (self.class_seconds / 3600.0)[None, None, :]
+        efpr = fpr.copy()
+        if self.criteria.cttc_milli and self.criteria.alpha_ct > 0.0:
+            for k in range(K):
+                others = [c2 for c2 in range(K) if c2 != k and self.class_seconds[c2] > 0.0]
+                if others:
+                    efpr[:, k] = fpr[:, k] + self.criteria.alpha_ct * ctr[:, k, others].mean(1)
+        return tpr, fpr, ctr, efpr
+
+    def kept_classes(self):
+        """the classes with a reference event: the ones the score averages over"""
+        counts, _ = self.table()
+        if counts.shape[0] == 0:
+            raise ValueError("an empty grid has no PSDS")
+        kept = np.flatnonzero(counts[0, :, 1] > 0)
+        if kept.size == 0:
+            raise ValueError("no class has a reference event: the PSDS is undefined")
+        return kept
+
+    def roc(self, k):
+        """class k's ROC as a step function: (e, tpr) with e the sorted distinct eFPR[:, k] and tpr[i] = max TPR[g, k] over the
+        settings with eFPR[g, k] <= e[i]"""
+        tpr, _, _, efpr = self.rates()
+        e = np.unique(efpr[:, k])
+        return e, np.array([tpr[efpr[:, k] <= x, k].max() for x in e], np.float64)
+
+    def _steps(self, e, k):
+        ek, tk = self.roc(k)
+        i = np.searchsorted(ek, e, side="right") - 1
+        return np.where(i >= 0, tk[np.maximum(i, 0)], 0.0)
+
+    def curve(self):
+        """(e, mean, std, eTPR): the e axis = the sorted distinct eFPR values <= e_max of the kept classes, then e_max; across
+        the kept classes the mean and population std of tpr_k(e), and eTPR = mean − alpha_st · std"""
+        kept = self.kept_classes()
+        efpr = self.rates()[3][:, kept]
+        e = np.unique(efpr[efpr <= self.criteria.e_max])
+        e = np.concatenate([e, [self.criteria.e_max]])
+        per = np.stack([self._steps(e, int(k)) for k in kept])
+        mean, std = per.mean(0), per.std(0)
+        return e, mean, std, mean - self.criteria.alpha_st * std
+
+    def psds(self):
+        """the area under eTPR over [0, e_max], left-constant, 0 before the first point, divided by e_max"""
+        e, _, _, etpr = self.curve()
+        return float(np.sum(etpr[:-1] * np.diff(e)) / self.criteria.e_max)
+
+    def per_class_auc(self):
+        """[K]: the same area under every class's own tpr_k(e) (NaN for a class without reference)"""
+        kept = self.kept_classes()
+        e = self.curve()[0]
+        out = np.full(self.table()[0].shape[1], np.nan)
+        for k in kept:
+            out[k] = np.sum(self._steps(e, int(k))[:-1] * np.diff(e)) / self.criteria.e_max
+        return out
+
+
+def psds_sweep(track, ref, grid, criteria, frame_seconds, max_workspace_bytes=1 << 30, cache=None):
+    """The PSDS counts of every setting of ``grid`` on a packed track against ``ref`` -> PSDSResult: one ``sed_psds_sweep`` call
+    per slice of the grid (sliced by workspace exactly like ``sweep``), no event written, nothing read back.  ``track``, ``ref``
+    and ``grid`` as in ``sweep``; ``criteria`` a PSDSCriteria; ``frame_seconds`` per output frame turns frames into the hours
+    of the rates."""
+    probs, out_off = _checked_types(track, ref, grid)
+    if not isinstance(criteria, PSDSCriteria):
+        raise TypeError(f"criteria must be a PSDSCriteria, got {type(criteria).__name__}")
+    fs = float(frame_seconds)
+    if not fs > 0:
+        raise ValueError(f"frame_seconds={frame_seconds} must be positive")
+    n_out, R, K = _checked_sizes(probs, out_off, ref)
+    probs = _on_gpu(probs)
+    dev = probs.device
+    G = len(grid)
+    cls_of = np.repeat(np.arange(R * K), np.diff(ref.off)) % K       # the class of every reference event
+    class_seconds = np.bincount(cls_of, weights=ref.offset.astype(np.float64) - ref.onset, minlength=K) * fs
+    counts = torch.zeros(G, K, 4, dtype=torch.int64, device=dev)
+    ct = torch.zeros(G, K, K, dtype=torch.int64, device=dev)
+    total = float(n_out.sum()) * fs
+    if G == 0 or R == 0:
+        return PSDSResult(counts, ct, grid, criteria, total, class_seconds, 0)
+    L = lib()
+    slices = _grid_slices(grid, int(probs.shape[0]), K, R, max_workspace_bytes, L.sed_psds_workspace_bytes, "sed_psds_workspace_bytes")
+    ws, need = _workspace(slices, cache, dev)
+    d_off, d_on, d_offs = ref.device(dev)
+    for a, b, _, _ in slices:
+        check(L.sed_psds_sweep(ptr(probs), C.c_void_p(n_out.ctypes.data), R, K, C.cast(_settings_array(grid, a, b), C.c_void_p), b - a,
+                               ptr(d_off), ptr(d_on), ptr(d_offs), criteria.dtc_milli, criteria.gtc_milli, criteria.cttc_milli,
+                               ptr(ws), ws.numel(), ptr(counts[a:b]), ptr(ct[a:b]) if criteria.cttc_milli else None, stream_ptr()),
+              "sed_psds_sweep")
+    return PSDSResult(counts, ct, grid, criteria, total, class_seconds, len(slices), max(s[3] for s in slices), need)
