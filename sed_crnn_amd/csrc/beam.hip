@@ -52,7 +52,8 @@ struct BmArgs {
     float inv_c;
 };
 
-// (bm_event_span — [s0, s0 + len) of an event — and the host's checks, recording table and upload: beam_shared.h, shared with mvdr.hip)
+// (bm_event_span — [s0, s0 + len) of an event — and the host's checks and upload: beam_shared.h, shared with mvdr.hip; the source,
+// the event table and the recording table: tdoa_shared.h)
 __global__ __launch_bounds__(BM_SCAN) void beam_spans_k(TdArgs ta, const int* __restrict__ ev_dir, const int* __restrict__ ev_loc, int D,
                                                         long E, int* __restrict__ len_out, long* __restrict__ start_out,
                                                         long* __restrict__ total_out) {
@@ -242,90 +243,97 @@ __global__ __launch_bounds__(BM_THREADS) void beam_sum_k(const float* __restrict
     for (int j = tid; j < cnt; j += BM_THREADS) dst[j] = lds[j];
 }
 
-int beam_spans(const char* who, bool ring, const std::vector<long>& h, size_t tab, int R, int channels, const int* ev_rec,
-               const int* ev_onset, const int* ev_offset, const int* ev_peak, const int* ev_dir, const int* ev_loc, long E,
-               int time_factor, int hop, int max_frames, int D, int* len_out, long* start_out, long* total_out, void* workspace,
-               size_t workspace_bytes, void* stream) {
-    SED_REQUIRE(total_out && (E == 0 || (len_out && start_out)), "%s: null pointer (an output)", who);
+int beam_spans(const char* who, const RecSource& src, const EvTable& ev, int* len_out, long* start_out, long* total_out,
+               void* workspace, size_t workspace_bytes, void* stream) {
+    SED_REQUIRE(total_out && (ev.E == 0 || (len_out && start_out)), "%s: null pointer (an output)", who);
     hipStream_t s = as_stream(stream);
-    SED_TRY(beam_upload(who, h, tab, workspace, workspace_bytes, s));
-    const TdArgs ta = beam_args(ring, workspace, R, channels, ev_rec, ev_onset, ev_offset, ev_peak, time_factor, hop, max_frames, 0);
-    beam_spans_k<<<1, BM_SCAN, 0, s>>>(ta, ev_dir, ev_loc, D, E, len_out, start_out, total_out);      // (E = 0: the total alone)
+    SED_TRY(beam_upload(who, src, workspace, workspace_bytes, s));
+    const TdArgs ta = td_args(src, ev, workspace);
+    beam_spans_k<<<1, BM_SCAN, 0, s>>>(ta, ev.dir, ev.loc, ev.D, ev.E, len_out, start_out, total_out);      // (E = 0: the total alone)
     SED_LAUNCH_CHECK(who);
     return 0;
 }
 
+// the delays [D][C] in 1/Q samples and the fractional-delay filter [Q][2H] (the host's tables)
+struct BmTables { const int* delays; int Q, H; const float* taps; };
+
 template <bool RING>
-int beam_run(const char* who, const float* x, const std::vector<long>& h, size_t tab, long longest, long cap, int R, int channels,
-             const int* ev_rec, const int* ev_onset, const int* ev_offset, const int* ev_peak, const int* ev_dir, const int* ev_loc,
-             long E, int time_factor, int hop, int max_frames, const int* delays, int D, int Q, int H, const float* taps,
-             const int* audio_len, const long* audio_start, float* audio, long total, void* workspace, size_t workspace_bytes,
-             void* stream) {
+int beam_run(const char* who, const RecSource& src, const EvTable& ev, const BmTables& bt, const BeamOut& out, void* workspace,
+             size_t workspace_bytes, void* stream) {
+    const int Q = bt.Q, H = bt.H;
+    const long E = ev.E;
     SED_REQUIRE(Q == 1 || Q == 2 || Q == 4 || Q == 8 || Q == 16 || Q == 32 || Q == 64, "%s: oversample must be a power of two up to 64, got %d",
                 who, Q);
     SED_REQUIRE(H >= 1 && H <= BM_MAX_H, "%s: half_width must be in [1,%d], got %d", who, BM_MAX_H, H);
-    SED_REQUIRE(total >= 0, "%s: a total of %ld samples", who, total);
-    SED_REQUIRE(E == 0 || (delays && taps && audio_len && audio_start), "%s: null pointer (delays, taps, audio_len or audio_start)", who);
-    SED_REQUIRE(audio || total == 0, "%s: null output buffer for %ld samples", who, total);
-    SED_REQUIRE(((uintptr_t)x & 15) == 0, "%s: the samples must be 16-byte aligned", who);
-    if (E == 0 || total == 0) return 0;                          // nothing to launch
+    SED_REQUIRE(out.total >= 0, "%s: a total of %ld samples", who, out.total);
+    SED_REQUIRE(E == 0 || (bt.delays && bt.taps && out.audio_len && out.audio_start), "%s: null pointer (delays, taps, audio_len or audio_start)",
+                who);
+    SED_REQUIRE(out.audio || out.total == 0, "%s: null output buffer for %ld samples", who, out.total);
+    SED_REQUIRE(((uintptr_t)src.x & 15) == 0, "%s: the samples must be 16-byte aligned", who);
+    if (E == 0 || out.total == 0) return 0;                      // nothing to launch
     hipStream_t s = as_stream(stream);
-    SED_TRY(beam_upload(who, h, tab, workspace, workspace_bytes, s));
-    const size_t lds = (size_t)channels * BM_SEG * sizeof(float);
+    SED_TRY(beam_upload(who, src, workspace, workspace_bytes, s));
+    const size_t lds = (size_t)src.C * BM_SEG * sizeof(float);
     const hipError_t err = hipFuncSetAttribute((const void*)beam_sum_k<RING>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                (int)(TD_MAX_CH * BM_SEG * sizeof(float)));
     if (err != hipSuccess) { sed_set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(err)); return (int)err; }
-    TdArgs ta = beam_args(RING, workspace, R, channels, ev_rec, ev_onset, ev_offset, ev_peak, time_factor, hop, max_frames, cap);
+    TdArgs ta = td_args(src, ev, workspace);
     int lq = 0;
     while ((1 << lq) < Q) ++lq;
-    const BmArgs ba{ev_dir, ev_loc, D, delays, Q, lq, H, taps, audio_len, audio_start, audio, total, (float)(1.0 / channels)};
-    long most = (long)max_frames * hop;                          // no event has more samples than this, or than its recording
-    if (most > longest) most = longest;
+    const BmArgs ba{ev.dir, ev.loc, ev.D, bt.delays, Q, lq, H, bt.taps, out.audio_len, out.audio_start, out.audio, out.total,
+                    (float)(1.0 / src.C)};
+    long most = (long)ev.max_frames * ev.hop;                    // no event has more samples than this, or than its recording
+    if (most > src.longest) most = src.longest;
     if (most < 1) return 0;
     const unsigned tiles = (unsigned)((most + BM_TILE - 1) / BM_TILE);
     for (long e0 = 0; e0 < E; e0 += 65535) {                     // gridDim.y
         ta.e0 = e0;
         ta.n_ev = (int)(E - e0 < 65535 ? E - e0 : 65535);
-        beam_sum_k<RING><<<dim3(tiles, (unsigned)ta.n_ev), BM_THREADS, lds, s>>>(x, ta, ba);
+        beam_sum_k<RING><<<dim3(tiles, (unsigned)ta.n_ev), BM_THREADS, lds, s>>>(src.x, ta, ba);
         SED_LAUNCH_CHECK(who);
     }
     return 0;
 }
 
+// an entry: the events and the recordings checked, then the launches
+template <bool RING>
+int beam_spans_entry(const char* who, RecSource src, const EvTable& ev, int* len_out, long* start_out, long* total_out, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+    SED_TRY((beam_source<RING, false>(who, src, ev)));
+    return beam_spans(who, src, ev, len_out, start_out, total_out, workspace, workspace_bytes, stream);
+}
+
+template <bool RING>
+int beam_entry(const char* who, RecSource src, const EvTable& ev, const BmTables& bt, const BeamOut& out, void* workspace,
+               size_t workspace_bytes, void* stream) {
+    SED_TRY(beam_source<RING>(who, src, ev));
+    return beam_run<RING>(who, src, ev, bt, out, workspace, workspace_bytes, stream);
+}
+
 }  // namespace
 
 extern "C" size_t sed_event_beam_workspace_bytes(int R, int channels) {
-    return R < 1 || channels < 2 || channels > TD_MAX_CH ? 0 : beam_table_bytes(R, channels);
+    return R < 1 || channels < 2 || channels > TD_MAX_CH ? 0 : rec_table_bytes(R, channels);
 }
 
-extern "C" size_t sed_event_beam_ring_workspace_bytes(int R) { return R < 1 ? 0 : beam_ring_table_bytes(R); }
+extern "C" size_t sed_event_beam_ring_workspace_bytes(int R) { return R < 1 ? 0 : rec_ring_table_bytes(R); }
 
 extern "C" int sed_event_beam_spans(long pcm_len, const long* clips_host, int R, int channels, const int* ev_rec, const int* ev_onset,
                                     const int* ev_offset, const int* ev_peak_frame, const int* ev_dir, const int* ev_loc_frames, long E,
                                     int time_factor, int hop, int max_frames, int D, int* len_out, long* start_out, long* total_out,
                                     void* workspace, size_t workspace_bytes, void* stream) {
-    const char* who = "event_beam_spans";
-    SED_TRY(beam_check_events(who, R, channels, ev_rec, ev_onset, ev_offset, ev_peak_frame, ev_dir, ev_loc_frames, E, time_factor, hop,
-                              max_frames, D));
-    std::vector<long> h;
-    long longest;
-    SED_TRY(beam_linear_table(who, pcm_len, clips_host, R, channels, hop, h, longest));
-    return beam_spans(who, false, h, beam_table_bytes(R, channels), R, channels, ev_rec, ev_onset, ev_offset, ev_peak_frame, ev_dir,
-                      ev_loc_frames, E, time_factor, hop, max_frames, D, len_out, start_out, total_out, workspace, workspace_bytes, stream);
+    return beam_spans_entry<false>("event_beam_spans", {nullptr, false, 0, pcm_len, R, channels, clips_host},
+                                   {ev_rec, ev_onset, ev_offset, ev_peak_frame, ev_dir, ev_loc_frames, E, time_factor, hop, max_frames, D},
+                                   len_out, start_out, total_out, workspace, workspace_bytes, stream);
 }
 
 extern "C" int sed_event_beam_spans_ring(const long* n_host, int R, int channels, const int* ev_rec, const int* ev_onset,
                                          const int* ev_offset, const int* ev_peak_frame, const int* ev_dir, const int* ev_loc_frames,
                                          long E, int time_factor, int hop, int max_frames, int D, int* len_out, long* start_out,
                                          long* total_out, void* workspace, size_t workspace_bytes, void* stream) {
-    const char* who = "event_beam_spans_ring";
-    SED_TRY(beam_check_events(who, R, channels, ev_rec, ev_onset, ev_offset, ev_peak_frame, ev_dir, ev_loc_frames, E, time_factor, hop,
-                              max_frames, D));
-    std::vector<long> h;
-    long longest;
-    SED_TRY(beam_ring_table(who, n_host, R, hop, h, longest));
-    return beam_spans(who, true, h, beam_ring_table_bytes(R), R, channels, ev_rec, ev_onset, ev_offset, ev_peak_frame, ev_dir,
-                      ev_loc_frames, E, time_factor, hop, max_frames, D, len_out, start_out, total_out, workspace, workspace_bytes, stream);
+    return beam_spans_entry<true>("event_beam_spans_ring", {nullptr, true, 0, 0, R, channels, n_host},
+                                  {ev_rec, ev_onset, ev_offset, ev_peak_frame, ev_dir, ev_loc_frames, E, time_factor, hop, max_frames, D},
+                                  len_out, start_out, total_out, workspace, workspace_bytes, stream);
 }
 
 extern "C" int sed_event_beamform(const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const int* ev_rec,
@@ -333,16 +341,9 @@ extern "C" int sed_event_beamform(const float* pcm, long pcm_len, const long* cl
                                   const int* ev_loc_frames, long E, int time_factor, int hop, int max_frames, const int* delays, int D,
                                   int Q, int H, const float* taps, const int* audio_len, const long* audio_start, float* audio,
                                   long audio_total, void* workspace, size_t workspace_bytes, void* stream) {
-    const char* who = "event_beamform";
-    SED_TRY(beam_check_events(who, R, channels, ev_rec, ev_onset, ev_offset, ev_peak_frame, ev_dir, ev_loc_frames, E, time_factor, hop,
-                              max_frames, D));
-    SED_REQUIRE(pcm, "%s: null pointer (the samples)", who);
-    std::vector<long> h;
-    long longest;
-    SED_TRY(beam_linear_table(who, pcm_len, clips_host, R, channels, hop, h, longest));
-    return beam_run<false>(who, pcm, h, beam_table_bytes(R, channels), longest, 0, R, channels, ev_rec, ev_onset, ev_offset, ev_peak_frame,
-                           ev_dir, ev_loc_frames, E, time_factor, hop, max_frames, delays, D, Q, H, taps, audio_len, audio_start, audio,
-                           audio_total, workspace, workspace_bytes, stream);
+    return beam_entry<false>("event_beamform", {pcm, false, 0, pcm_len, R, channels, clips_host},
+                             {ev_rec, ev_onset, ev_offset, ev_peak_frame, ev_dir, ev_loc_frames, E, time_factor, hop, max_frames, D},
+                             {delays, Q, H, taps}, {audio_len, audio_start, audio, audio_total}, workspace, workspace_bytes, stream);
 }
 
 extern "C" int sed_event_beamform_ring(const float* ring, long ring_len, long cap, const long* n_host, int R, int channels,
@@ -351,18 +352,7 @@ extern "C" int sed_event_beamform_ring(const float* ring, long ring_len, long ca
                                        const int* delays, int D, int Q, int H, const float* taps, const int* audio_len,
                                        const long* audio_start, float* audio, long audio_total, void* workspace, size_t workspace_bytes,
                                        void* stream) {
-    const char* who = "event_beamform_ring";
-    SED_TRY(beam_check_events(who, R, channels, ev_rec, ev_onset, ev_offset, ev_peak_frame, ev_dir, ev_loc_frames, E, time_factor, hop,
-                              max_frames, D));
-    SED_REQUIRE(ring, "%s: null pointer (the rings)", who);
-    SED_REQUIRE(cap >= LM_NFFT && cap % 4 == 0, "%s: a ring holds a multiple of 4 samples and at least one frame of %d, got cap=%ld", who,
-                LM_NFFT, cap);
-    SED_REQUIRE(ring_len >= 0 && cap <= ring_len / ((long)R * channels), "%s: %d feeds of %d rings of %ld samples leave the buffer "
-                "of %ld", who, R, channels, cap, ring_len);
-    std::vector<long> h;
-    long longest;
-    SED_TRY(beam_ring_table(who, n_host, R, hop, h, longest));
-    return beam_run<true>(who, ring, h, beam_ring_table_bytes(R), longest, cap, R, channels, ev_rec, ev_onset, ev_offset, ev_peak_frame,
-                          ev_dir, ev_loc_frames, E, time_factor, hop, max_frames, delays, D, Q, H, taps, audio_len, audio_start, audio,
-                          audio_total, workspace, workspace_bytes, stream);
+    return beam_entry<true>("event_beamform_ring", {ring, true, cap, ring_len, R, channels, n_host},
+                            {ev_rec, ev_onset, ev_offset, ev_peak_frame, ev_dir, ev_loc_frames, E, time_factor, hop, max_frames, D},
+                            {delays, Q, H, taps}, {audio_len, audio_start, audio, audio_total}, workspace, workspace_bytes, stream);
 }

@@ -169,9 +169,10 @@ extern "C" int sed_event_doa(const float* pcm, long pcm_len, const long* clips_h
                              size_t workspace_bytes, void* stream) {
     DoaArgs da;
     SED_TRY(doa_check("event_doa", steer_lags, D, Q, trig, max_lag, dir_out, power_out, srp_out, da));
-    return tdoa_linear_entry("event_doa", pcm, pcm_len, clips_host, R, channels, tables, tables_bytes, ev_rec, ev_onset, ev_offset,
-                             ev_peak_frame, E, time_factor, hop, pad_mode, max_lag, max_frames, lag_out, strength_out, frames_out, acc_out,
-                             workspace, workspace_bytes, stream, doa_hook, &da);
+    return tdoa_entry("event_doa", {pcm, false, 0, pcm_len, R, channels, clips_host},
+                             {ev_rec, ev_onset, ev_offset, ev_peak_frame, nullptr, nullptr, E, time_factor, hop, max_frames, 0},
+                             {tables, tables_bytes, pad_mode, max_lag, 0, 0}, {lag_out, strength_out, frames_out, acc_out}, workspace,
+                             workspace_bytes, stream, doa_hook, &da);
 }
 
 extern "C" size_t sed_event_doa_ring_workspace_bytes(int R, int channels, long E, long cap, int hop, int max_frames) {
@@ -186,7 +187,8 @@ extern "C" int sed_event_doa_ring(const float* ring, long ring_len, long cap, co
                                   float* power_out, float* srp_out, void* workspace, size_t workspace_bytes, void* stream) {
     DoaArgs da;
     SED_TRY(doa_check("event_doa_ring", steer_lags, D, Q, trig, max_lag, dir_out, power_out, srp_out, da));
-    return tdoa_ring_entry("event_doa_ring", ring, ring_len, cap, n_host, R, channels, tables, tables_bytes, ev_rec, ev_onset, ev_offset,
-                           ev_peak_frame, E, time_factor, hop, max_lag, max_frames, lat_frames, history_frames, lag_out, strength_out,
-                           frames_out, acc_out, workspace, workspace_bytes, stream, doa_hook, &da);
+    return tdoa_entry("event_doa_ring", {ring, true, cap, ring_len, R, channels, n_host},
+                           {ev_rec, ev_onset, ev_offset, ev_peak_frame, nullptr, nullptr, E, time_factor, hop, max_frames, 0},
+                           {tables, tables_bytes, 0, max_lag, lat_frames, history_frames}, {lag_out, strength_out, frames_out, acc_out},
+                           workspace, workspace_bytes, stream, doa_hook, &da);
 }

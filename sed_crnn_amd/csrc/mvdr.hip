@@ -42,7 +42,6 @@
 // with every index checked against the recording); a slice is then four launches — own covariance, noise covariance, weights,
 // apply — and each covariance launch returns at once for the other's events.  noise_frames_out says which events used it.
 #include <math.h>
-#include <vector>
 #include "common.h"
 #include "fft2048.h"
 #include "tdoa_shared.h"
@@ -511,31 +510,35 @@ bool mv_sizes_ok(int R, int channels, int max_frames, int hop) {
 #define MV_MAX_NOISE 256                          // localize.MVDR: noise_blocks
 #define MV_MAX_GUARD 64                           //                noise_guard
 
-// what all entries do once the events and the recordings are checked: h = the recording table (tab bytes at the head of the
-// workspace), pcm = the planar PCM (RING: the rings, cap samples each); kn = 0 (sed_event_mvdr, sed_event_mvdr_ring, or a
-// noise entry asked for no noise frames): today's three launches, and noise_frames_out, where given, is zeroed
+// the steering delays [D][C], the diagonal loading and the table blob
+struct MvTables { const double* tau; double loading; const void* tables; size_t tables_bytes; };
+// kn noise frames that end guard blocks before the onset, and which events used them; entry: one of the noise entries,
+// which must be given frames_out
+struct MvNoise { int kn, guard; int* frames_out; bool entry; };
+
+// what all entries do once the events and the recordings are checked.  kn = 0 (sed_event_mvdr, sed_event_mvdr_ring, or a noise
+// entry asked for no noise frames): three launches per slice, and the noise entries' frames_out is zeroed
 template <bool RING>
-int mv_run(const char* who, const float* pcm, const std::vector<long>& h, size_t tab, long longest, long cap, int R, int channels,
-           const int* ev_rec, const int* ev_onset, const int* ev_offset, const int* ev_peak_frame, const int* ev_dir,
-           const int* ev_loc_frames, long E, int time_factor, int hop, int max_frames, const double* tau, int D, double loading,
-           const void* tables, size_t tables_bytes, const int* audio_len, const long* audio_start, float* audio, long audio_total,
-           void* workspace, size_t workspace_bytes, void* stream, int kn = 0, int guard = 0, int* noise_frames_out = nullptr,
-           bool noise_entry = false) {
+int mv_run(const char* who, const RecSource& src, const EvTable& ev, const MvTables& mt, const MvNoise& nz, const BeamOut& out,
+           void* workspace, size_t workspace_bytes, void* stream) {
+    const int kn = nz.kn;
+    const long E = ev.E;
+    const size_t tab = src.tab;
     SED_REQUIRE(kn >= 0 && kn <= MV_MAX_NOISE, "%s: noise_blocks must be in [0, %d], got %d", who, MV_MAX_NOISE, kn);
-    SED_REQUIRE(guard >= 0 && guard <= MV_MAX_GUARD, "%s: noise_guard must be in [0, %d], got %d", who, MV_MAX_GUARD, guard);
-    SED_REQUIRE(!noise_entry || E == 0 || noise_frames_out, "%s: null pointer (noise_frames_out)", who);
-    SED_REQUIRE(loading >= 1e-6 && loading <= 1e6, "%s: loading must be in [1e-6, 1e6], got %g", who, loading);
-    SED_REQUIRE(audio_total >= 0, "%s: a total of %ld samples", who, audio_total);
-    SED_REQUIRE(E == 0 || (tau && audio_len && audio_start), "%s: null pointer (tau, audio_len or audio_start)", who);
-    SED_REQUIRE(audio || audio_total == 0, "%s: null output buffer for %ld samples", who, audio_total);
-    SED_REQUIRE(tables && tables_bytes % 16 == 0 && tables_bytes / 4 >= (size_t)MV_TAB_WORDS, "%s: table blob of %zu bytes is malformed", who,
-                tables_bytes);
-    SED_REQUIRE(((uintptr_t)pcm & 3) == 0, "%s: the samples must be 4-byte aligned", who);
-    SED_REQUIRE(kn == 0 || longest < (1L << 42), "%s: a recording of %ld samples; with noise_blocks > 0 fewer than 2^42 are taken", who,
-                longest);
-    if (E == 0 || audio_total == 0) return 0;                    // nothing to launch (noise_frames_out is not written: no event is extracted)
-    const int C = channels, T = C * (C + 1) / 2;
-    const long cpe = mv_slots(max_frames, hop, kn);
+    SED_REQUIRE(nz.guard >= 0 && nz.guard <= MV_MAX_GUARD, "%s: noise_guard must be in [0, %d], got %d", who, MV_MAX_GUARD, nz.guard);
+    SED_REQUIRE(!nz.entry || E == 0 || nz.frames_out, "%s: null pointer (noise_frames_out)", who);
+    SED_REQUIRE(mt.loading >= 1e-6 && mt.loading <= 1e6, "%s: loading must be in [1e-6, 1e6], got %g", who, mt.loading);
+    SED_REQUIRE(out.total >= 0, "%s: a total of %ld samples", who, out.total);
+    SED_REQUIRE(E == 0 || (mt.tau && out.audio_len && out.audio_start), "%s: null pointer (tau, audio_len or audio_start)", who);
+    SED_REQUIRE(out.audio || out.total == 0, "%s: null output buffer for %ld samples", who, out.total);
+    SED_REQUIRE(mt.tables && mt.tables_bytes % 16 == 0 && mt.tables_bytes / 4 >= (size_t)MV_TAB_WORDS, "%s: table blob of %zu bytes is malformed",
+                who, mt.tables_bytes);
+    SED_REQUIRE(((uintptr_t)src.x & 3) == 0, "%s: the samples must be 4-byte aligned", who);
+    SED_REQUIRE(kn == 0 || src.longest < (1L << 42), "%s: a recording of %ld samples; with noise_blocks > 0 fewer than 2^42 are taken", who,
+                src.longest);
+    if (E == 0 || out.total == 0) return 0;                      // nothing to launch (frames_out is not written: no event is extracted)
+    const int C = src.C, T = C * (C + 1) / 2;
+    const long cpe = mv_slots(ev.max_frames, ev.hop, kn);
     const size_t per_event = mv_event_bytes(C, cpe);
     SED_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0, "%s: the workspace must be a 16-byte aligned device buffer", who);
     SED_REQUIRE(workspace_bytes >= tab + per_event, "%s: workspace of %zu bytes, at least %zu needed (one event)", who, workspace_bytes,
@@ -548,14 +551,14 @@ int mv_run(const char* who, const float* pcm, const std::vector<long>& h, size_t
     const size_t lds_cov = mv_cov_lds(C, batch), lds_apply = mv_apply_lds(C);
     SED_REQUIRE(lds_cov <= MV_LDS_MAX && lds_apply <= MV_LDS_MAX, "%s: %d spectra and the tables (%zu B, %zu B) exceed the 160 KiB LDS", who,
                 C, lds_cov, lds_apply);
-    long most = (long)max_frames * hop;                          // no event has more samples than this, or than its recording
-    if (most > longest) most = longest;
+    long most = (long)ev.max_frames * ev.hop;                    // no event has more samples than this, or than its recording
+    if (most > src.longest) most = src.longest;
     const long blocks = (most + MV_B - 1) / MV_B;
     if (blocks < 1) return 0;
     const unsigned chunks = (unsigned)((blocks + 1 + MV_CHUNK - 1) / MV_CHUNK), runs = (unsigned)((blocks + MV_RUN - 1) / MV_RUN);
 
     hipStream_t s = as_stream(stream);
-    SED_TRY(beam_upload(who, h, tab, workspace, workspace_bytes, s));
+    SED_TRY(beam_upload(who, src, workspace, workspace_bytes, s));
     const auto cov_k = RING ? mvdr_ring_cov_k : mvdr_cov_k;
     const auto apply_k = RING ? mvdr_ring_apply_k : mvdr_apply_k;
     hipError_t err = hipFuncSetAttribute((const void*)cov_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MV_LDS_MAX);
@@ -563,40 +566,50 @@ int mv_run(const char* who, const float* pcm, const std::vector<long>& h, size_t
     const auto noise_k = RING ? mvdr_ring_noise_k : mvdr_noise_k;
     if (err == hipSuccess && kn > 0) err = hipFuncSetAttribute((const void*)noise_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MV_LDS_MAX);
     if (err != hipSuccess) { sed_set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(err)); return (int)err; }
-    if (kn == 0 && noise_frames_out) {
-        err = hipMemsetAsync(noise_frames_out, 0, (size_t)E * sizeof(int), s);
+    if (kn == 0 && nz.frames_out) {
+        err = hipMemsetAsync(nz.frames_out, 0, (size_t)E * sizeof(int), s);
         if (err != hipSuccess) { sed_set_error("%s: hipMemsetAsync: %s", who, hipGetErrorString(err)); return (int)err; }
     }
-    TdArgs ta = beam_args(RING, workspace, R, C, ev_rec, ev_onset, ev_offset, ev_peak_frame, time_factor, hop, max_frames, cap);
-    const MvArgs ma{ev_dir, ev_loc_frames, D, audio_len, audio_start, audio_total, (int)cpe, (int)(cpe * T + C), batch, kn, guard, noise_frames_out};
+    TdArgs ta = td_args(src, ev, workspace);
+    const MvArgs ma{ev.dir, ev.loc, ev.D, out.audio_len, out.audio_start, out.total, (int)cpe, (int)(cpe * T + C), batch, kn, nz.guard,
+                    nz.frames_out};
+    const uint32_t* tables = (const uint32_t*)mt.tables;
     float2* part = (float2*)((char*)workspace + tab);
     for (long e0 = 0; e0 < E; e0 += slice) {
         ta.e0 = e0;
         ta.n_ev = (int)(E - e0 < slice ? E - e0 : slice);
-        cov_k<<<dim3(chunks, (unsigned)ta.n_ev), MV_THREADS, lds_cov, s>>>(pcm, (const uint32_t*)tables, part, ta, ma);
+        cov_k<<<dim3(chunks, (unsigned)ta.n_ev), MV_THREADS, lds_cov, s>>>(src.x, tables, part, ta, ma);
         SED_LAUNCH_CHECK("mvdr (covariance)");
         if (kn > 0) {                                            // the host does not know which events use it: both launches run
-            noise_k<<<dim3((unsigned)mv_noise_chunks(kn), (unsigned)ta.n_ev), MV_THREADS, lds_cov, s>>>(pcm, (const uint32_t*)tables, part, ta, ma);
+            noise_k<<<dim3((unsigned)mv_noise_chunks(kn), (unsigned)ta.n_ev), MV_THREADS, lds_cov, s>>>(src.x, tables, part, ta, ma);
             SED_LAUNCH_CHECK("mvdr (noise covariance)");
         }
-        mvdr_weights_k<<<dim3((LM_N + MV_WT) / MV_WT, (unsigned)ta.n_ev), MV_WT, 0, s>>>(part, tau, loading, ta, ma);
+        mvdr_weights_k<<<dim3((LM_N + MV_WT) / MV_WT, (unsigned)ta.n_ev), MV_WT, 0, s>>>(part, mt.tau, mt.loading, ta, ma);
         SED_LAUNCH_CHECK("mvdr (weights)");
-        apply_k<<<dim3(runs, (unsigned)ta.n_ev), MV_THREADS, lds_apply, s>>>(pcm, (const uint32_t*)tables, part, audio, ta, ma);
+        apply_k<<<dim3(runs, (unsigned)ta.n_ev), MV_THREADS, lds_apply, s>>>(src.x, tables, part, out.audio, ta, ma);
         SED_LAUNCH_CHECK("mvdr (apply)");
     }
     return 0;
+}
+
+// an entry: the events and the recordings checked, then the launches
+template <bool RING>
+int mv_entry(const char* who, RecSource src, const EvTable& ev, const MvTables& mt, const MvNoise& nz, const BeamOut& out, void* workspace,
+             size_t workspace_bytes, void* stream) {
+    SED_TRY(beam_source<RING>(who, src, ev));
+    return mv_run<RING>(who, src, ev, mt, nz, out, workspace, workspace_bytes, stream);
 }
 
 }  // namespace
 
 extern "C" size_t sed_event_mvdr_workspace_bytes(int R, int channels, int max_frames, int hop) {
     if (!mv_sizes_ok(R, channels, max_frames, hop)) return 0;
-    return beam_table_bytes(R, channels) + mv_event_bytes(channels, mv_chunks(max_frames, hop));
+    return rec_table_bytes(R, channels) + mv_event_bytes(channels, mv_chunks(max_frames, hop));
 }
 
 extern "C" size_t sed_event_mvdr_ring_workspace_bytes(int R, int channels, int max_frames, int hop) {
     if (!mv_sizes_ok(R, channels, max_frames, hop)) return 0;
-    return beam_ring_table_bytes(R) + mv_event_bytes(channels, mv_chunks(max_frames, hop));
+    return rec_ring_table_bytes(R) + mv_event_bytes(channels, mv_chunks(max_frames, hop));
 }
 
 extern "C" int sed_event_mvdr(const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const int* ev_rec,
@@ -604,16 +617,10 @@ extern "C" int sed_event_mvdr(const float* pcm, long pcm_len, const long* clips_
                               const int* ev_loc_frames, long E, int time_factor, int hop, int max_frames, const double* tau, int D,
                               double loading, const void* tables, size_t tables_bytes, const int* audio_len, const long* audio_start,
                               float* audio, long audio_total, void* workspace, size_t workspace_bytes, void* stream) {
-    const char* who = "mvdr";
-    SED_TRY(beam_check_events(who, R, channels, ev_rec, ev_onset, ev_offset, ev_peak_frame, ev_dir, ev_loc_frames, E, time_factor, hop,
-                              max_frames, D));
-    SED_REQUIRE(pcm, "%s: null pointer (the samples)", who);
-    std::vector<long> h;
-    long longest;
-    SED_TRY(beam_linear_table(who, pcm_len, clips_host, R, channels, hop, h, longest));
-    return mv_run<false>(who, pcm, h, beam_table_bytes(R, channels), longest, 0, R, channels, ev_rec, ev_onset, ev_offset, ev_peak_frame,
-                         ev_dir, ev_loc_frames, E, time_factor, hop, max_frames, tau, D, loading, tables, tables_bytes, audio_len,
-                         audio_start, audio, audio_total, workspace, workspace_bytes, stream);
+    return mv_entry<false>("mvdr", {pcm, false, 0, pcm_len, R, channels, clips_host},
+                           {ev_rec, ev_onset, ev_offset, ev_peak_frame, ev_dir, ev_loc_frames, E, time_factor, hop, max_frames, D},
+                           {tau, loading, tables, tables_bytes}, {0, 0, nullptr, false}, {audio_len, audio_start, audio, audio_total},
+                           workspace, workspace_bytes, stream);
 }
 
 extern "C" int sed_event_mvdr_ring(const float* ring, long ring_len, long cap, const long* n_host, int R, int channels, const int* ev_rec,
@@ -622,31 +629,21 @@ extern "C" int sed_event_mvdr_ring(const float* ring, long ring_len, long cap, c
                                    double loading, const void* tables, size_t tables_bytes, const int* audio_len,
                                    const long* audio_start, float* audio, long audio_total, void* workspace, size_t workspace_bytes,
                                    void* stream) {
-    const char* who = "mvdr_ring";
-    SED_TRY(beam_check_events(who, R, channels, ev_rec, ev_onset, ev_offset, ev_peak_frame, ev_dir, ev_loc_frames, E, time_factor, hop,
-                              max_frames, D));
-    SED_REQUIRE(ring, "%s: null pointer (the rings)", who);
-    SED_REQUIRE(cap >= LM_NFFT && cap % 4 == 0, "%s: a ring holds a multiple of 4 samples and at least one frame of %d, got cap=%ld", who,
-                LM_NFFT, cap);
-    SED_REQUIRE(ring_len >= 0 && cap <= ring_len / ((long)R * channels), "%s: %d feeds of %d rings of %ld samples leave the buffer "
-                "of %ld", who, R, channels, cap, ring_len);
-    std::vector<long> h;
-    long longest;
-    SED_TRY(beam_ring_table(who, n_host, R, hop, h, longest));
-    return mv_run<true>(who, ring, h, beam_ring_table_bytes(R), longest, cap, R, channels, ev_rec, ev_onset, ev_offset, ev_peak_frame,
-                        ev_dir, ev_loc_frames, E, time_factor, hop, max_frames, tau, D, loading, tables, tables_bytes, audio_len,
-                        audio_start, audio, audio_total, workspace, workspace_bytes, stream);
+    return mv_entry<true>("mvdr_ring", {ring, true, cap, ring_len, R, channels, n_host},
+                          {ev_rec, ev_onset, ev_offset, ev_peak_frame, ev_dir, ev_loc_frames, E, time_factor, hop, max_frames, D},
+                          {tau, loading, tables, tables_bytes}, {0, 0, nullptr, false}, {audio_len, audio_start, audio, audio_total},
+                          workspace, workspace_bytes, stream);
 }
 
 // ── DESIGN 5u: the weights from the covariance of the noise_blocks frames that end noise_guard blocks before the onset ──
 extern "C" size_t sed_event_mvdr_noise_workspace_bytes(int R, int channels, int max_frames, int hop, int noise_blocks) {
     if (!mv_sizes_ok(R, channels, max_frames, hop) || noise_blocks < 0 || noise_blocks > MV_MAX_NOISE) return 0;
-    return beam_table_bytes(R, channels) + mv_event_bytes(channels, mv_slots(max_frames, hop, noise_blocks));
+    return rec_table_bytes(R, channels) + mv_event_bytes(channels, mv_slots(max_frames, hop, noise_blocks));
 }
 
 extern "C" size_t sed_event_mvdr_noise_ring_workspace_bytes(int R, int channels, int max_frames, int hop, int noise_blocks) {
     if (!mv_sizes_ok(R, channels, max_frames, hop) || noise_blocks < 0 || noise_blocks > MV_MAX_NOISE) return 0;
-    return beam_ring_table_bytes(R) + mv_event_bytes(channels, mv_slots(max_frames, hop, noise_blocks));
+    return rec_ring_table_bytes(R) + mv_event_bytes(channels, mv_slots(max_frames, hop, noise_blocks));
 }
 
 extern "C" int sed_event_mvdr_noise(const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const int* ev_rec,
@@ -655,17 +652,10 @@ extern "C" int sed_event_mvdr_noise(const float* pcm, long pcm_len, const long* 
                                     double loading, int noise_blocks, int noise_guard, const void* tables, size_t tables_bytes,
                                     const int* audio_len, const long* audio_start, float* audio, long audio_total, int* noise_frames_out,
                                     void* workspace, size_t workspace_bytes, void* stream) {
-    const char* who = "mvdr_noise";
-    SED_TRY(beam_check_events(who, R, channels, ev_rec, ev_onset, ev_offset, ev_peak_frame, ev_dir, ev_loc_frames, E, time_factor, hop,
-                              max_frames, D));
-    SED_REQUIRE(pcm, "%s: null pointer (the samples)", who);
-    std::vector<long> h;
-    long longest;
-    SED_TRY(beam_linear_table(who, pcm_len, clips_host, R, channels, hop, h, longest));
-    return mv_run<false>(who, pcm, h, beam_table_bytes(R, channels), longest, 0, R, channels, ev_rec, ev_onset, ev_offset, ev_peak_frame,
-                         ev_dir, ev_loc_frames, E, time_factor, hop, max_frames, tau, D, loading, tables, tables_bytes, audio_len,
-                         audio_start, audio, audio_total, workspace, workspace_bytes, stream, noise_blocks, noise_guard, noise_frames_out,
-                         true);
+    return mv_entry<false>("mvdr_noise", {pcm, false, 0, pcm_len, R, channels, clips_host},
+                           {ev_rec, ev_onset, ev_offset, ev_peak_frame, ev_dir, ev_loc_frames, E, time_factor, hop, max_frames, D},
+                           {tau, loading, tables, tables_bytes}, {noise_blocks, noise_guard, noise_frames_out, true},
+                           {audio_len, audio_start, audio, audio_total}, workspace, workspace_bytes, stream);
 }
 
 extern "C" int sed_event_mvdr_noise_ring(const float* ring, long ring_len, long cap, const long* n_host, int R, int channels,
@@ -674,19 +664,8 @@ extern "C" int sed_event_mvdr_noise_ring(const float* ring, long ring_len, long 
                                          const double* tau, int D, double loading, int noise_blocks, int noise_guard, const void* tables,
                                          size_t tables_bytes, const int* audio_len, const long* audio_start, float* audio,
                                          long audio_total, int* noise_frames_out, void* workspace, size_t workspace_bytes, void* stream) {
-    const char* who = "mvdr_noise_ring";
-    SED_TRY(beam_check_events(who, R, channels, ev_rec, ev_onset, ev_offset, ev_peak_frame, ev_dir, ev_loc_frames, E, time_factor, hop,
-                              max_frames, D));
-    SED_REQUIRE(ring, "%s: null pointer (the rings)", who);
-    SED_REQUIRE(cap >= LM_NFFT && cap % 4 == 0, "%s: a ring holds a multiple of 4 samples and at least one frame of %d, got cap=%ld", who,
-                LM_NFFT, cap);
-    SED_REQUIRE(ring_len >= 0 && cap <= ring_len / ((long)R * channels), "%s: %d feeds of %d rings of %ld samples leave the buffer "
-                "of %ld", who, R, channels, cap, ring_len);
-    std::vector<long> h;
-    long longest;
-    SED_TRY(beam_ring_table(who, n_host, R, hop, h, longest));
-    return mv_run<true>(who, ring, h, beam_ring_table_bytes(R), longest, cap, R, channels, ev_rec, ev_onset, ev_offset, ev_peak_frame,
-                        ev_dir, ev_loc_frames, E, time_factor, hop, max_frames, tau, D, loading, tables, tables_bytes, audio_len,
-                        audio_start, audio, audio_total, workspace, workspace_bytes, stream, noise_blocks, noise_guard, noise_frames_out,
-                        true);
+    return mv_entry<true>("mvdr_noise_ring", {ring, true, cap, ring_len, R, channels, n_host},
+                          {ev_rec, ev_onset, ev_offset, ev_peak_frame, ev_dir, ev_loc_frames, E, time_factor, hop, max_frames, D},
+                          {tau, loading, tables, tables_bytes}, {noise_blocks, noise_guard, noise_frames_out, true},
+                          {audio_len, audio_start, audio, audio_total}, workspace, workspace_bytes, stream);
 }

@@ -27,7 +27,7 @@
 // two launches with tdoa_accum_k<true>, which loads a frame from the ring — directly where it does not wrap, through the guarded
 // loads where it does — and with td_event_range also refusing what the stream's rule or the ring's depth refuses.
 //
-// The host side of both entries is behind tdoa_linear_entry / tdoa_ring_entry (tdoa_shared.h), which doa.hip calls with a hook
+// The host side of both entries is behind tdoa_entry (tdoa_shared.h), which doa.hip calls with a hook
 // that steers every slice while its partials are in the workspace; the entries here pass none.
 #include <math.h>
 #include <string.h>
@@ -215,31 +215,25 @@ size_t tdoa_lds_bytes(int C, int batch, int buffers) {
     return ((size_t)TD_TAB_WORDS + (size_t)buffers * C * PHAT_SPEC * 2 + (size_t)((C + 1) / 2) * TD_FFT_SCR + (size_t)batch * PHAT_SPEC * 2) * sizeof(float);
 }
 
-// bytes of sample_off [R*C] and n_samples [R] (64-bit), rounded to 16
-size_t tdoa_table_bytes(int R, int channels) { return (((size_t)R * channels + R) * sizeof(long) + 15) & ~(size_t)15; }
-
 // chunk slots per event: no event is located on more than min(max_frames, the longest recording's frames) frames
 long tdoa_chunks_per_event(long max_rec_frames, int max_frames) {
     const long f = max_rec_frames < max_frames ? max_rec_frames : max_frames;
     return (f + TD_CHUNK - 1) / TD_CHUNK;
 }
 
-// a live feed's table: n [R] (64-bit), rounded to 16 — the rings need no offsets
-size_t tdoa_ring_table_bytes(int R) { return ((size_t)R * sizeof(long) + 15) & ~(size_t)15; }
-
-// What both entries share once their recordings are checked: the argument checks, the upload of the host table `h` (tab bytes
-// of the workspace; linear: sample_off then n_samples, ring: n), and the two launches per slice of the event table.
-// `longest`: samples of the longest recording (ring: the ring's capacity — no located event has more than 1 + cap / hop frames).
+// What both entries share once their recordings are checked: the argument checks, the upload of the recording table and the
+// two launches per slice of the event table.  A ring's longest "recording" is its capacity: no located event has more than
+// 1 + cap / hop frames.
 template <bool RING>
-int tdoa_run(const char* who, const float* pcm, const std::vector<long>& h, size_t tab, long longest, long cap, int lat, int hist, int R,
-             int channels, const void* tables, const int* ev_rec, const int* ev_onset, const int* ev_offset, const int* ev_peak_frame,
-             long E, int time_factor, int hop, int pad_mode, int max_lag, int max_frames, float* lag_out, float* strength_out,
-             int* frames_out, float* acc_out, void* workspace, size_t workspace_bytes, void* stream, TdSliceHook hook, void* hook_ctx) {
-    const int P = channels * (channels - 1) / 2;
-    SED_REQUIRE(ev_onset && ev_offset && ev_peak_frame && lag_out && strength_out && frames_out && workspace, "%s: null pointer", who);
-    SED_REQUIRE(ev_rec || R == 1, "%s: %d recordings need ev_rec", who, R);
+int tdoa_run(const char* who, const RecSource& src, const EvTable& ev, const TdSettings& st, const TdOut& out, void* workspace,
+             size_t workspace_bytes, void* stream, TdSliceHook hook, void* hook_ctx) {
+    const int channels = src.C, P = channels * (channels - 1) / 2;
+    const long E = ev.E;
+    const size_t tab = src.tab;
+    SED_REQUIRE(ev.onset && ev.offset && ev.peak && out.lag && out.strength && out.frames && workspace, "%s: null pointer", who);
+    SED_REQUIRE(ev.rec || src.R == 1, "%s: %d recordings need ev_rec", who, src.R);
     SED_REQUIRE(((uintptr_t)workspace & 15) == 0, "%s: workspace must be 16-byte aligned", who);
-    const long cpe = tdoa_chunks_per_event(1 + longest / hop, max_frames);
+    const long cpe = tdoa_chunks_per_event(1 + (RING ? src.cap : src.longest) / ev.hop, ev.max_frames);
     SED_REQUIRE(cpe <= 0x7fffffffL, "%s: too many chunks per event", who);         // (gridDim.x and TdArgs.cpe; frames are < 2^31)
     const size_t per_event = (size_t)cpe * P * TD_ROW_BYTES;
     SED_REQUIRE(workspace_bytes >= tab + per_event, "%s: workspace of %zu bytes, at least %zu needed (one event)", who, workspace_bytes,
@@ -257,20 +251,21 @@ int tdoa_run(const char* who, const float* pcm, const std::vector<long>& h, size
     SED_REQUIRE(lds <= TD_LDS_MAX, "%s: %d spectra and the tables (%zu B) exceed the 160 KiB LDS", who, channels, lds);
 
     hipStream_t s = as_stream(stream);
-    hipError_t err = hipMemcpyAsync(workspace, h.data(), h.size() * sizeof(long), hipMemcpyHostToDevice, s);
-    if (err != hipSuccess) { sed_set_error("%s: upload of the recording table: %s", who, hipGetErrorString(err)); return (int)err; }
-    err = hipFuncSetAttribute((const void*)tdoa_accum_k<RING>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TD_LDS_MAX);
+    SED_TRY(rec_upload(who, src, workspace, s));
+    const hipError_t err = hipFuncSetAttribute((const void*)tdoa_accum_k<RING>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TD_LDS_MAX);
     if (err != hipSuccess) { sed_set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(err)); return (int)err; }
-    const long* dl = (const long*)workspace;
+    TdArgs ta = td_args(src, ev, workspace);
+    ta.pairs_per_batch = batch; ta.max_lag = st.max_lag; ta.cpe = (int)cpe; ta.pipelined = pipelined;
+    ta.lat = st.lat; ta.hist = st.hist;
+    const uint32_t* tables = (const uint32_t*)st.tables;
     float2* part = (float2*)((char*)workspace + tab);
     for (long e0 = 0; e0 < E; e0 += slice) {
-        const int n_ev = (int)(E - e0 < slice ? E - e0 : slice);
-        TdArgs ta{RING ? nullptr : dl, RING ? dl : dl + (size_t)R * channels, ev_rec, ev_onset, ev_offset, ev_peak_frame, R, channels, P,
-                  batch, time_factor, hop, max_frames, max_lag, (int)cpe, pipelined, e0, n_ev, RING ? cap : 0, lat, hist};
-        tdoa_accum_k<RING><<<dim3((unsigned)cpe, (unsigned)n_ev), TD_THREADS, lds, s>>>(pcm, (const uint32_t*)tables, part, pad_mode, ta);
+        ta.e0 = e0;
+        ta.n_ev = (int)(E - e0 < slice ? E - e0 : slice);
+        tdoa_accum_k<RING><<<dim3((unsigned)cpe, (unsigned)ta.n_ev), TD_THREADS, lds, s>>>(src.x, tables, part, st.pad_mode, ta);
         SED_LAUNCH_CHECK(RING ? "event_tdoa_ring (accumulate)" : "event_tdoa (accumulate)");
-        const int blocks = n_ev < 2048 ? n_ev : 2048;
-        tdoa_finish_k<<<blocks, TD_FIN_THREADS, 0, s>>>((const uint32_t*)tables, part, lag_out, strength_out, frames_out, acc_out, ta);
+        const int blocks = ta.n_ev < 2048 ? ta.n_ev : 2048;
+        tdoa_finish_k<<<blocks, TD_FIN_THREADS, 0, s>>>(tables, part, out.lag, out.strength, out.frames, out.acc, ta);
         SED_LAUNCH_CHECK(RING ? "event_tdoa_ring (finish)" : "event_tdoa (finish)");
         if (hook) {                                              // (doa.hip: the slice's partials are still in the workspace)
             const int rc = hook(hook_ctx, ta, part, s);
@@ -303,45 +298,33 @@ extern "C" size_t sed_event_tdoa_workspace_bytes(int R, int channels, long E, lo
     if (R < 1 || channels < 2 || channels > TD_MAX_CH || E < 0 || max_n_samples < 1 || hop < 1 || max_frames < 1) return 0;
     const int P = channels * (channels - 1) / 2;
     const long cpe = tdoa_chunks_per_event(1 + max_n_samples / hop, max_frames);
-    return tdoa_table_bytes(R, channels) + (size_t)E * cpe * P * TD_ROW_BYTES;
+    return rec_table_bytes(R, channels) + (size_t)E * cpe * P * TD_ROW_BYTES;
 }
 
-int tdoa_linear_entry(const char* who, const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const void* tables,
-                      size_t tables_bytes, const int* ev_rec, const int* ev_onset, const int* ev_offset, const int* ev_peak_frame,
-                      long E, int time_factor, int hop, int pad_mode, int max_lag, int max_frames, float* lag_out, float* strength_out,
-                      int* frames_out, float* acc_out, void* workspace, size_t workspace_bytes, void* stream, TdSliceHook hook,
-                      void* hook_ctx) {
-    SED_REQUIRE(channels >= 2 && channels <= TD_MAX_CH, "%s: 2 to %d channels, got %d", who, TD_MAX_CH, channels);
-    SED_REQUIRE(max_lag >= 1 && max_lag <= TD_MAX_LAG, "%s: max_lag must be in [1,%d], got %d", who, TD_MAX_LAG, max_lag);
-    SED_REQUIRE(max_frames >= 1, "%s: max_frames must be >= 1, got %d", who, max_frames);
-    SED_REQUIRE(time_factor >= 1 && hop >= 1 && R >= 1 && E >= 0, "%s: bad sizes (time_factor=%d, hop=%d, R=%d, E=%ld)", who,
-                time_factor, hop, R, E);
-    SED_REQUIRE(pad_mode == 0 || pad_mode == 1, "%s: pad_mode must be 0 (constant) or 1 (reflect), got %d", who, pad_mode);
-    SED_REQUIRE(pcm && clips_host && tables && pcm_len > 0, "%s: null pointer", who);
-    SED_REQUIRE(tables_bytes % 16 == 0 && tables_bytes / 4 >= (size_t)TD_TAB_WORDS, "%s: table blob of %zu bytes is malformed", who, tables_bytes);
-
-    // the recordings: bounds and equal channel lengths, on the host, before anything is enqueued
-    std::vector<long> h((size_t)R * channels + R);
-    long *soff = h.data(), *slen = soff + (size_t)R * channels, longest = 0;
-    for (int r = 0; r < R; ++r) {
-        const long n0 = clips_host[2 * ((long)r * channels) + 1];
-        for (int ch = 0; ch < channels; ++ch) {
-            const long c = (long)r * channels + ch, o = clips_host[2 * c], n = clips_host[2 * c + 1];
-            SED_REQUIRE(o >= 0 && n >= 1 && o <= pcm_len && n <= pcm_len - o,
-                        "%s: recording %d, channel %d (offset %ld, %ld samples) is not inside the PCM buffer of %ld samples", who, r, ch,
-                        o, n, pcm_len);
-            SED_REQUIRE(n == n0, "%s: recording %d: channel %d has %ld samples, channel 0 has %ld (the channels of a recording "
-                        "must have equal length)", who, r, ch, n, n0);
-            soff[c] = o;
-        }
-        slen[r] = n0;
-        SED_REQUIRE(1 + n0 / hop <= 0x7fffffffL, "%s: recording %d has more than 2^31 - 1 feature frames", who, r);
-        if (n0 > longest) longest = n0;
+// the host side of sed_event_tdoa / sed_event_tdoa_ring (src.ring) and, with a hook, of their DOA siblings: each form keeps its
+// own checks in its own order
+int tdoa_entry(const char* who, RecSource src, const EvTable& ev, const TdSettings& st, const TdOut& out, void* workspace,
+               size_t workspace_bytes, void* stream, TdSliceHook hook, void* hook_ctx) {
+    SED_REQUIRE(src.C >= 2 && src.C <= TD_MAX_CH, "%s: 2 to %d channels, got %d", who, TD_MAX_CH, src.C);
+    SED_REQUIRE(st.max_lag >= 1 && st.max_lag <= TD_MAX_LAG, "%s: max_lag must be in [1,%d], got %d", who, TD_MAX_LAG, st.max_lag);
+    SED_REQUIRE(ev.max_frames >= 1, "%s: max_frames must be >= 1, got %d", who, ev.max_frames);
+    SED_REQUIRE(ev.tf >= 1 && ev.hop >= 1 && src.R >= 1 && ev.E >= 0, "%s: bad sizes (time_factor=%d, hop=%d, R=%d, E=%ld)", who,
+                ev.tf, ev.hop, src.R, ev.E);
+    if (!src.ring) {
+        SED_REQUIRE(st.pad_mode == 0 || st.pad_mode == 1, "%s: pad_mode must be 0 (constant) or 1 (reflect), got %d", who, st.pad_mode);
+        SED_REQUIRE(src.x && src.host && st.tables && src.x_len > 0, "%s: null pointer", who);
+    } else {
+        SED_REQUIRE(st.lat >= 0 && st.hist >= 1, "%s: need lat_frames >= 0 and history_frames >= 1, got %d, %d", who, st.lat, st.hist);
+        SED_REQUIRE(src.x && src.host && st.tables, "%s: null pointer", who);
+        SED_TRY(rec_ring_check(who, src));
+        SED_REQUIRE(((uintptr_t)src.x & 15) == 0, "%s: the rings must be 16-byte aligned", who);
     }
-    if (E == 0) return 0;                                        // nothing to launch
-    return tdoa_run<false>(who, pcm, h, tdoa_table_bytes(R, channels), longest, 0, 0, 0, R, channels, tables, ev_rec, ev_onset,
-                           ev_offset, ev_peak_frame, E, time_factor, hop, pad_mode, max_lag, max_frames, lag_out, strength_out,
-                           frames_out, acc_out, workspace, workspace_bytes, stream, hook, hook_ctx);
+    SED_REQUIRE(st.tables_bytes % 16 == 0 && st.tables_bytes / 4 >= (size_t)TD_TAB_WORDS, "%s: table blob of %zu bytes is malformed", who,
+                st.tables_bytes);
+    SED_TRY(!src.ring ? rec_source_linear(who, src, ev.hop) : rec_source_ring(who, src, ev.hop));
+    if (ev.E == 0) return 0;                                     // nothing to launch
+    return !src.ring ? tdoa_run<false>(who, src, ev, st, out, workspace, workspace_bytes, stream, hook, hook_ctx)
+                     : tdoa_run<true>(who, src, ev, st, out, workspace, workspace_bytes, stream, hook, hook_ctx);
 }
 
 extern "C" int sed_event_tdoa(const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const void* tables,
@@ -349,9 +332,10 @@ extern "C" int sed_event_tdoa(const float* pcm, long pcm_len, const long* clips_
                               const int* ev_peak_frame, long E, int time_factor, int hop, int pad_mode, int max_lag, int max_frames,
                               float* lag_out, float* strength_out, int* frames_out, float* acc_out, void* workspace,
                               size_t workspace_bytes, void* stream) {
-    return tdoa_linear_entry("event_tdoa", pcm, pcm_len, clips_host, R, channels, tables, tables_bytes, ev_rec, ev_onset, ev_offset,
-                             ev_peak_frame, E, time_factor, hop, pad_mode, max_lag, max_frames, lag_out, strength_out, frames_out, acc_out,
-                             workspace, workspace_bytes, stream, nullptr, nullptr);
+    return tdoa_entry("event_tdoa", {pcm, false, 0, pcm_len, R, channels, clips_host},
+                             {ev_rec, ev_onset, ev_offset, ev_peak_frame, nullptr, nullptr, E, time_factor, hop, max_frames, 0},
+                             {tables, tables_bytes, pad_mode, max_lag, 0, 0}, {lag_out, strength_out, frames_out, acc_out}, workspace,
+                             workspace_bytes, stream, nullptr, nullptr);
 }
 
 // ───────────────────────── live feeds ─────────────────────────
@@ -394,38 +378,7 @@ extern "C" size_t sed_event_tdoa_ring_workspace_bytes(int R, int channels, long 
     if (R < 1 || channels < 2 || channels > TD_MAX_CH || E < 0 || cap < LM_NFFT || cap % 4 || hop < 1 || max_frames < 1) return 0;
     const int P = channels * (channels - 1) / 2;
     const long cpe = tdoa_chunks_per_event(1 + cap / hop, max_frames);
-    return tdoa_ring_table_bytes(R) + (size_t)E * cpe * P * TD_ROW_BYTES;
-}
-
-int tdoa_ring_entry(const char* who, const float* ring, long ring_len, long cap, const long* n_host, int R, int channels,
-                    const void* tables, size_t tables_bytes, const int* ev_rec, const int* ev_onset, const int* ev_offset,
-                    const int* ev_peak_frame, long E, int time_factor, int hop, int max_lag, int max_frames, int lat_frames,
-                    int history_frames, float* lag_out, float* strength_out, int* frames_out, float* acc_out, void* workspace,
-                    size_t workspace_bytes, void* stream, TdSliceHook hook, void* hook_ctx) {
-    SED_REQUIRE(channels >= 2 && channels <= TD_MAX_CH, "%s: 2 to %d channels, got %d", who, TD_MAX_CH, channels);
-    SED_REQUIRE(max_lag >= 1 && max_lag <= TD_MAX_LAG, "%s: max_lag must be in [1,%d], got %d", who, TD_MAX_LAG, max_lag);
-    SED_REQUIRE(max_frames >= 1, "%s: max_frames must be >= 1, got %d", who, max_frames);
-    SED_REQUIRE(time_factor >= 1 && hop >= 1 && R >= 1 && E >= 0, "%s: bad sizes (time_factor=%d, hop=%d, R=%d, E=%ld)", who,
-                time_factor, hop, R, E);
-    SED_REQUIRE(lat_frames >= 0 && history_frames >= 1, "%s: need lat_frames >= 0 and history_frames >= 1, got %d, %d", who,
-                lat_frames, history_frames);
-    SED_REQUIRE(ring && n_host && tables, "%s: null pointer", who);
-    SED_REQUIRE(cap >= LM_NFFT && cap % 4 == 0, "%s: a ring holds a multiple of 4 samples and at least one frame of %d, got "
-                "cap=%ld", who, LM_NFFT, cap);
-    SED_REQUIRE(ring_len >= 0 && cap <= ring_len / ((long)R * channels), "%s: %d feeds of %d rings of %ld samples leave "
-                "the buffer of %ld", who, R, channels, cap, ring_len);
-    SED_REQUIRE(((uintptr_t)ring & 15) == 0, "%s: the rings must be 16-byte aligned", who);
-    SED_REQUIRE(tables_bytes % 16 == 0 && tables_bytes / 4 >= (size_t)TD_TAB_WORDS, "%s: table blob of %zu bytes is malformed", who, tables_bytes);
-    std::vector<long> h(R);
-    for (int r = 0; r < R; ++r) {
-        h[r] = n_host[r];
-        SED_REQUIRE(h[r] >= 0 && 1 + h[r] / hop <= 0x7fffffffL, "%s: feed %d: %ld samples received (negative, or more than "
-                    "2^31 - 1 feature frames)", who, r, h[r]);
-    }
-    if (E == 0) return 0;                                        // nothing to launch
-    return tdoa_run<true>(who, ring, h, tdoa_ring_table_bytes(R), cap, cap, lat_frames, history_frames, R, channels, tables,
-                          ev_rec, ev_onset, ev_offset, ev_peak_frame, E, time_factor, hop, 0, max_lag, max_frames, lag_out, strength_out,
-                          frames_out, acc_out, workspace, workspace_bytes, stream, hook, hook_ctx);
+    return rec_ring_table_bytes(R) + (size_t)E * cpe * P * TD_ROW_BYTES;
 }
 
 extern "C" int sed_event_tdoa_ring(const float* ring, long ring_len, long cap, const long* n_host, int R, int channels,
@@ -433,7 +386,8 @@ extern "C" int sed_event_tdoa_ring(const float* ring, long ring_len, long cap, c
                                    const int* ev_offset, const int* ev_peak_frame, long E, int time_factor, int hop, int max_lag,
                                    int max_frames, int lat_frames, int history_frames, float* lag_out, float* strength_out,
                                    int* frames_out, float* acc_out, void* workspace, size_t workspace_bytes, void* stream) {
-    return tdoa_ring_entry("event_tdoa_ring", ring, ring_len, cap, n_host, R, channels, tables, tables_bytes, ev_rec, ev_onset, ev_offset,
-                           ev_peak_frame, E, time_factor, hop, max_lag, max_frames, lat_frames, history_frames, lag_out, strength_out,
-                           frames_out, acc_out, workspace, workspace_bytes, stream, nullptr, nullptr);
+    return tdoa_entry("event_tdoa_ring", {ring, true, cap, ring_len, R, channels, n_host},
+                           {ev_rec, ev_onset, ev_offset, ev_peak_frame, nullptr, nullptr, E, time_factor, hop, max_frames, 0},
+                           {tables, tables_bytes, 0, max_lag, lat_frames, history_frames}, {lag_out, strength_out, frames_out, acc_out},
+                           workspace, workspace_bytes, stream, nullptr, nullptr);
 }

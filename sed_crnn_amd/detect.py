@@ -23,6 +23,7 @@ import torch
 from . import feature
 from ._lib import SedHipError, TuneSetting, check, lib, ptr, stream_ptr
 from .data import SEQ_LEN_IN
+from .events import event_beamform, event_doa, event_mvdr, event_tdoa
 from .model import HipCRNN
 
 _EVENT_KEYS = ("cls", "onset", "offset", "peak", "peak_frame")
@@ -365,17 +366,17 @@ class EventDetector:
     ``push_features`` take finished features and apply nothing.  ``localize=sed.TDOA(max_lag, max_frames)``: for a
     net that reads at least 2 audio channels, ``det(wave, sr=, channels=C)`` and ``detect_many`` keep the resampled planar PCM
     until the decode is done and return events that also hold ``lag`` [E, P] (samples at the detector's rate, one column per
-    microphone pair; ``result.tdoa()`` in seconds), ``strength`` [E, P] and ``loc_frames`` [E] (``feature.event_tdoa``);
+    microphone pair; ``result.tdoa()`` in seconds), ``strength`` [E, P] and ``loc_frames`` [E] (``events.event_tdoa``);
     ``from_features*`` has no audio and returns un-located events, which ``det.localize(result, waveform, ...)`` locates.
     ``localize=sed.DOA(positions, grid, ...)`` for a known array: the same three keys, with ``max_lag`` taken from the
-    array's aperture, and ``dir`` [E] (a row of ``grid``, -1: not located) and ``doa_power`` [E] (``feature.event_doa``;
+    array's aperture, and ``dir`` [E] (a row of ``grid``, -1: not located) and ``doa_power`` [E] (``events.event_doa``;
     ``result.doa()`` in radians).  ``extract=sed.DelaySum(...)`` (needs ``localize=sed.DOA(...)``): every located event
-    also comes with its audio, the array pointed at ``dir`` by a delay-and-sum beam (``feature.event_beamform`` on the PCM that
+    also comes with its audio, the array pointed at ``dir`` by a delay-and-sum beam (``events.event_beamform`` on the PCM that
     is kept anyway): ``audio_start`` / ``audio_len`` [E] in the events, the packed float32 buffer ``result.audio`` and
     ``result.event_audio(e)``; ``from_features*`` returns events without audio, ``det.localize`` adds it, ``det.stream`` of such a
     detector takes ``history_frames=`` and ``emit_audio=True`` and emits the same audio on live feeds.
     ``extract=sed.MVDR(loading)`` instead: the same events, samples and results through an adaptive beam that
-    suppresses what else the event's frames contain (``feature.event_mvdr``; live feeds: ``feature.event_mvdr_ring``).  With
+    suppresses what else the event's frames contain (``events.event_mvdr``; live feeds: ``events.event_mvdr_ring``).  With
     ``sed.MVDR(noise_blocks=Kn)``, ``Kn >= 1``, the weights come from the Kn frames before the onset where the
     recording has them, and the events and ``result.noise_frames`` also hold ``noise_frames``."""
 
@@ -612,19 +613,19 @@ class EventDetector:
     # ── where the events came from ──
     def _located(self, result, pcm, clips):
         """``result``, MODIFIED IN PLACE and returned, with ``lag``, ``strength`` and ``loc_frames`` added to its events (a new dict)
-        and ``sr`` set: ``feature.event_tdoa`` on the planar PCM at the detector's rate that the events were detected in"""
+        and ``sr`` set: ``events.event_tdoa`` on the planar PCM at the detector's rate that the events were detected in"""
         t = self.localize_settings
         with torch.no_grad():
             if self.locates_directions:
-                loc = feature.event_doa(pcm, clips, self.audio_channels, result.events, self.model.time_factor, t, sr=self.sr,
+                loc = event_doa(pcm, clips, self.audio_channels, result.events, self.model.time_factor, t, sr=self.sr,
                                         hop=self.hop_length)
                 result.grid = t.grid
             else:
-                loc = feature.event_tdoa(pcm, clips, self.audio_channels, result.events, self.model.time_factor, max_lag=t.max_lag,
+                loc = event_tdoa(pcm, clips, self.audio_channels, result.events, self.model.time_factor, max_lag=t.max_lag,
                                          max_frames=t.max_frames, hop=self.hop_length)
             if self.extract_settings is not None:            # the audio of the located events, from the same PCM (DESIGN 5r, 5s)
                 from .localize import MVDR
-                entry = feature.event_mvdr if isinstance(self.extract_settings, MVDR) else feature.event_beamform
+                entry = event_mvdr if isinstance(self.extract_settings, MVDR) else event_beamform
                 beam = entry(pcm, clips, self.audio_channels, {**result.events, **loc}, self.model.time_factor, t,
                              self.extract_settings, sr=self.sr, hop=self.hop_length)
                 result.audio = beam.pop("audio")

@@ -1,0 +1,460 @@
+"""device entries over an event table: where every detected event came from (``event_tdoa``, ``event_doa``) and its audio with the
+array pointed at it (``event_beamform``, ``event_mvdr``), on planar PCM and, with ``_ring``, on the PCM rings of live feeds that
+``ring_write`` fills.  ``feature`` re-exports the public names.
+
+Every function is: check the arguments, describe where the samples are (``_Source``), run.  The TDOA / DOA entries share
+``_locate``, the two beams ``_extract``; the C entry of a call comes from ``_ENTRY``."""
+import ctypes as C
+import functools
+import typing
+
+import numpy as np
+import torch
+
+from ._lib import check, lib, ptr, stream_ptr
+from .feature import GCC_MAX_CHANNELS, HOP, NB_MEL, NFFT, SR, _LM_OFF_ENT, _clip_table, _tables, build_tables, slaney_mel_basis
+
+# (what is computed, on rings) -> the C entry; its workspace function is the name + "_workspace_bytes"
+_ENTRY = {("tdoa", False): "sed_event_tdoa", ("tdoa", True): "sed_event_tdoa_ring",
+          ("doa", False): "sed_event_doa", ("doa", True): "sed_event_doa_ring",
+          ("spans", False): "sed_event_beam_spans", ("spans", True): "sed_event_beam_spans_ring",
+          ("delay_sum", False): "sed_event_beamform", ("delay_sum", True): "sed_event_beamform_ring",
+          ("mvdr", False): "sed_event_mvdr", ("mvdr", True): "sed_event_mvdr_ring",
+          ("mvdr_noise", False): "sed_event_mvdr_noise", ("mvdr_noise", True): "sed_event_mvdr_noise_ring"}
+_LOCATED = ("onset", "offset", "peak_frame", "dir", "loc_frames")
+
+
+class _Source(typing.NamedTuple):
+    """where the samples of a call are.  Holds the tensor and the host table that its C arguments point into."""
+    x: torch.Tensor              # the planar PCM; ring: the rings
+    table: np.ndarray            # int64: (first sample, samples) per recording and channel; ring: the samples every feed has received
+    R: int
+    nc: int
+    ring: bool
+    extent: int                  # what bounds an event's frames: the longest recording's samples; ring: cap
+    spans_head: list             # the leading C arguments of the spans call, which reads no samples
+    head: list                   # ... of every other call
+
+
+def _pad_code(pad_mode):
+    if pad_mode not in ("constant", "reflect"):
+        raise ValueError(f"pad_mode must be 'constant' or 'reflect', got {pad_mode!r}")
+    return {"constant": 0, "reflect": 1}[pad_mode]
+
+
+def _need_pcm(who, pcm):
+    if not (isinstance(pcm, torch.Tensor) and pcm.is_cuda and pcm.dim() == 1):
+        raise RuntimeError(f"sed_crnn_amd.feature.{who} needs a 1-D CUDA(HIP) PCM buffer; there is no CPU fallback")
+
+
+def _need_ring(who, ring):
+    if not (isinstance(ring, torch.Tensor) and ring.is_cuda and ring.dim() == 1 and ring.dtype == torch.float32 and ring.is_contiguous()):
+        raise RuntimeError(f"sed_crnn_amd.feature.{who} needs a contiguous 1-D float32 CUDA(HIP) ring buffer; there is no CPU fallback")
+
+
+def _beam_sizes(who, channels, time_factor, hop):
+    nc, tf, hop = int(channels), int(time_factor), int(hop)
+    if not 2 <= nc <= GCC_MAX_CHANNELS or tf < 1 or hop < 1:
+        raise ValueError(f"{who} needs 2 to {GCC_MAX_CHANNELS} audio channels, time_factor >= 1 and hop >= 1, got channels={nc}, "
+                         f"time_factor={tf}, hop={hop}")
+    return nc, tf, hop
+
+
+def _linear_source(pcm, clips, nc, align_16=False):
+    """R >= 1 recordings of ``nc`` planar channels in the buffer ``pcm`` (``clips`` as ``mbe_planar`` takes them); ``align_16``: the
+    kernel loads 16 bytes at a time, a view into a larger buffer that starts elsewhere is copied"""
+    table = _clip_table(clips, nc, pcm.numel(), at_least_one=True)
+    pcm = pcm.contiguous().float()
+    if align_16 and pcm.data_ptr() % 16:
+        pcm = pcm.clone()
+    R = table.shape[0] // nc
+    spans_head = [pcm.numel(), C.c_void_p(table.ctypes.data), R, nc]
+    return _Source(pcm, table, R, nc, False, int(table[:, 1].max()), spans_head, [ptr(pcm)] + spans_head)
+
+
+def _ring_source(ring, cap, n, nc, need_16_byte=False):
+    """the rings of R live feeds of ``nc`` channels as ``ring_write`` fills them; ``n`` [R] host ints: the samples every feed has
+    received"""
+    n = np.ascontiguousarray(np.asarray(n, dtype=np.int64).reshape(-1))
+    R = n.shape[0]
+    if R < 1 or (n < 0).any():
+        raise ValueError(f"n must hold one sample count >= 0 per feed, got {n.tolist()[:8]}")
+    if cap < NFFT or cap % 4 or R * nc * cap > ring.numel() or (need_16_byte and ring.data_ptr() % 16):
+        raise ValueError(f"{R} feeds of {nc} rings of cap={cap} samples (a multiple of 4, at least {NFFT}, 16-byte aligned) do not fit the "
+                         f"ring buffer of {ring.numel()} samples" if need_16_byte else
+                         f"{R} feeds of {nc} rings of cap={cap} samples (a multiple of 4, at least {NFFT}) do not fit the ring buffer of "
+                         f"{ring.numel()} samples")
+    spans_head = [C.c_void_p(n.ctypes.data), R, nc]
+    return _Source(ring, n, R, nc, True, cap, spans_head, [ptr(ring), ring.numel(), cap] + spans_head)
+
+
+def _event_cols(events, R, rec_key, keys, dev):
+    """the columns ``keys`` of ``events`` as contiguous int32 tensors on ``dev``, equally long, and with more than one recording
+    the column ``rec_key`` that names an event's -> ({key: tensor}, the recording under "rec"; E)"""
+    col = {}
+    for k in keys + ((rec_key,) if R > 1 else ()):
+        if k not in events:
+            raise ValueError(f"events has no {k!r}" + (f" ({R} recordings need one)" if k == rec_key else
+                                                       " (the events must be located: feature.event_doa)" if k in ("dir", "loc_frames") else ""))
+        col["rec" if k == rec_key else k] = events[k].to(dev, torch.int32).contiguous()
+    E = col["onset"].numel()
+    if any(v.dim() != 1 or v.numel() != E for v in col.values()):
+        raise ValueError("the event columns must be 1-D and equally long")
+    return col, E
+
+
+def _cols(src, events, keys):
+    """``_event_cols`` for a source: the recording of an event is its ``rec`` column; on rings ``stream`` will do"""
+    rec_key = "stream" if src.ring and "stream" in events and "rec" not in events else "rec"
+    return _event_cols(events, src.R, rec_key, keys, src.x.device)
+
+
+def _col_ptrs(col, keys):
+    return [ptr(col.get("rec"))] + [ptr(col[k]) for k in keys]
+
+
+# ───────────────────────── where an event came from: TDOA and DOA ─────────────────────────
+def _doa_plan(doa, nc, sr):
+    """checks the settings of a DOA call (a ``localize.DOA`` for ``nc`` channels) -> its max_lag at rate ``sr``"""
+    from .localize import DOA
+    if not isinstance(doa, DOA):
+        raise TypeError(f"event_doa takes the settings as a sed.DOA(...) object, got {type(doa).__name__}")
+    if doa.channels != nc:
+        raise ValueError(f"the DOA settings hold {doa.channels} microphone positions, the audio has {nc} channels")
+    return doa.plan(sr)[0]
+
+
+def _doa_io(doa, sr, E, dev, out, return_map):
+    """the steering tables of ``doa`` at rate ``sr`` on ``dev`` (uploaded once per device and rate) and, added to ``out``, the
+    outputs a DOA call adds -> [J, D, Q, trig, dir, doa_power, srp or None] as the C entries take them (None without events)"""
+    _, J, trig = doa.plan(sr)
+    out["dir"] = torch.empty(E, dtype=torch.int32, device=dev)
+    out["doa_power"] = torch.empty(E, device=dev)
+    if return_map:
+        out["srp"] = torch.empty(E, J.shape[0], device=dev)
+    if E == 0:
+        return None
+    key = (dev.index or 0, float(sr))
+    if key not in doa._device:
+        doa._device[key] = (torch.from_numpy(J).to(dev), torch.from_numpy(trig).to(dev))
+    Jd, td = doa._device[key]
+    return [ptr(Jd), J.shape[0], doa.oversample, ptr(td), ptr(out["dir"]), ptr(out["doa_power"]), ptr(out.get("srp"))]
+
+
+def _locate(src, events, tf, hop, max_lag, max_frames, settings, return_curve, max_workspace_bytes, doa):
+    """what the four TDOA / DOA functions do once their arguments are checked.  ``settings``: what the C entry takes between ``hop``
+    and its outputs; ``doa``: None, or (the ``localize.DOA``, the rate of the PCM, return_map) for the same launches and one more
+    per slice"""
+    R, nc, dev = src.R, src.nc, src.x.device
+    col, E = _cols(src, events, _LOCATED[:3])
+    P, W = nc * (nc - 1) // 2, 2 * max_lag + 3
+    out = {"lag": torch.empty(E, P, device=dev), "strength": torch.empty(E, P, device=dev),
+           "loc_frames": torch.empty(E, dtype=torch.int32, device=dev)}
+    if return_curve:
+        out["acc"] = torch.empty(E, P, W, device=dev)
+    extra = _doa_io(doa[0], doa[1], E, dev, out, doa[2]) if doa is not None else []
+    if E == 0:
+        return out
+    tables = _tables(dev.index or 0, SR, NFFT, NB_MEL)                # the window and the twiddles; the mel plan is not read
+    sizes = _ENTRY["tdoa", src.ring] + "_workspace_bytes"             # (the steering launch reads the partials in place)
+    need_one = getattr(lib(), sizes)(R, nc, 1, src.extent, hop, max_frames)
+    need_all = getattr(lib(), sizes)(R, nc, E, src.extent, hop, max_frames)
+    if need_one == 0:
+        raise ValueError(f"sed_event_tdoa_ring_workspace_bytes refuses R={R}, channels={nc}, cap={src.extent}, hop={hop}, max_frames={max_frames}"
+                         if src.ring else
+                         f"sed_event_tdoa_workspace_bytes refuses R={R}, channels={nc}, hop={hop}, max_frames={max_frames}")
+    ws = torch.empty(min(need_all, max(need_one, int(max_workspace_bytes))), dtype=torch.uint8, device=dev)
+    name = _ENTRY["tdoa" if doa is None else "doa", src.ring]
+    check(getattr(lib(), name)(*src.head, ptr(tables), tables.numel() * 4, *_col_ptrs(col, _LOCATED[:3]), E, tf, hop, *settings,
+                               ptr(out["lag"]), ptr(out["strength"]), ptr(out["loc_frames"]), ptr(out.get("acc")), *extra, ptr(ws),
+                               ws.numel(), stream_ptr()), name)
+    return out
+
+
+def _tdoa_linear(pcm, clips, channels, events, time_factor, max_lag, max_frames, hop, pad_mode, return_curve, max_workspace_bytes, doa):
+    """``event_tdoa`` (``doa`` None) and ``event_doa``"""
+    from .localize import MAX_LAG_LIMIT
+    _need_pcm("event_tdoa", pcm)
+    pad = _pad_code(pad_mode)
+    nc, tf, max_lag, max_frames, hop = int(channels), int(time_factor), int(max_lag), int(max_frames), int(hop)
+    if doa is not None:
+        max_lag = _doa_plan(doa[0], nc, doa[1])
+    if not 2 <= nc <= GCC_MAX_CHANNELS:
+        raise ValueError(f"event_tdoa needs 2 to {GCC_MAX_CHANNELS} audio channels (one estimate per microphone pair), got channels={nc}")
+    if not 1 <= max_lag <= MAX_LAG_LIMIT or max_frames < 1 or tf < 1 or hop < 1:
+        raise ValueError(f"event_tdoa needs 1 <= max_lag <= {MAX_LAG_LIMIT}, max_frames >= 1, time_factor >= 1 and hop >= 1, got "
+                         f"max_lag={max_lag}, max_frames={max_frames}, time_factor={tf}, hop={hop}")
+    src = _linear_source(pcm, clips, nc)
+    return _locate(src, events, tf, hop, max_lag, max_frames, [pad, max_lag, max_frames], return_curve, max_workspace_bytes, doa)
+
+
+def _tdoa_ring(ring, cap, n, channels, events, time_factor, max_lag, max_frames, hop, lat_frames, history_frames, return_curve,
+               max_workspace_bytes, doa):
+    """``event_tdoa_ring`` (``doa`` None) and ``event_doa_ring``"""
+    from .localize import MAX_LAG_LIMIT
+    _need_ring("event_tdoa_ring", ring)
+    nc, tf, max_lag, max_frames, hop, cap = int(channels), int(time_factor), int(max_lag), int(max_frames), int(hop), int(cap)
+    lat, hist = int(lat_frames), int(history_frames)
+    if doa is not None:
+        max_lag = _doa_plan(doa[0], nc, doa[1])
+    if not 2 <= nc <= GCC_MAX_CHANNELS:
+        raise ValueError(f"event_tdoa_ring needs 2 to {GCC_MAX_CHANNELS} audio channels (one estimate per microphone pair), got channels={nc}")
+    if not 1 <= max_lag <= MAX_LAG_LIMIT or max_frames < 1 or tf < 1 or hop < 1 or lat < 0 or hist < 1:
+        raise ValueError(f"event_tdoa_ring needs 1 <= max_lag <= {MAX_LAG_LIMIT}, max_frames >= 1, time_factor >= 1, hop >= 1, lat_frames >= 0 "
+                         f"and history_frames >= 1, got max_lag={max_lag}, max_frames={max_frames}, time_factor={tf}, hop={hop}, "
+                         f"lat_frames={lat}, history_frames={hist}")
+    src = _ring_source(ring, cap, n, nc)
+    return _locate(src, events, tf, hop, max_lag, max_frames, [max_lag, max_frames, lat, hist], return_curve, max_workspace_bytes, doa)
+
+
+def event_tdoa(pcm, clips, channels, events, time_factor, max_lag=24, max_frames=256, hop=HOP, pad_mode="constant",
+               return_curve=False, max_workspace_bytes=128 << 20):
+    """Per-event time difference of arrival (``sed_event_tdoa``).  ``pcm`` / ``clips`` / ``channels``: R recordings of
+    2..8 planar channels in one float32 CUDA buffer, as ``mbe_planar`` takes them.  ``events``: a dict of int32 device tensors
+    ``onset``, ``offset`` (exclusive), ``peak_frame`` in output frames of ``time_factor`` feature frames, as the decoders return
+    them, with ``rec`` when R > 1.  For every event and microphone pair p = (i, j), i < j in lexicographic order, the GCC-PHAT of
+    the event's frames (``localize.event_frames``: all of them up to ``max_frames``, else ``max_frames`` around the peak) is
+    accumulated and searched over ``|tau| <= max_lag`` -> a dict of device tensors: ``lag`` float32 [E, P] in samples at the
+    PCM's rate (channel j = channel i delayed by d samples gives -d; seconds = lag / sr), ``strength`` float32 [E, P] in [-1, 1]
+    (the accumulated correlation at the peak per frame), ``loc_frames`` int32 [E] (0: the event names no recording or lies
+    beyond its end; its lag and strength are 0), and with ``return_curve=True`` ``acc`` float32 [E, P, 2*max_lag + 3], the
+    accumulated correlation at lags -(max_lag+1) .. max_lag+1.  The partial sums of at most ``max_workspace_bytes`` worth of
+    events are held at a time; the slicing changes no bit, and neither do the other events, the batch or the clip's place in
+    the buffer.  The host reads nothing back.  The cost is per located frame (every event transforms its own frames: 21 ns per
+    frame at 4 channels on an MI355X): for an event table that covers its recordings more than about five times over — many
+    long, heavily overlapping events — ``mbe_planar(..., spatial="gcc_phat")`` with ``n_mels = 2 * (max_lag + 2)`` followed by sums
+    of the GCC columns over each event's rows is the cheaper route."""
+    return _tdoa_linear(pcm, clips, channels, events, time_factor, max_lag, max_frames, hop, pad_mode, return_curve, max_workspace_bytes,
+                        None)
+
+
+def event_doa(pcm, clips, channels, events, time_factor, doa, sr=SR, hop=HOP, pad_mode="constant", return_curve=False,
+              return_map=False, max_workspace_bytes=128 << 20):
+    """Per-event direction of arrival for a known array (``sed_event_doa``): ``event_tdoa`` with ``max_lag`` and
+    ``max_frames`` taken from ``doa`` (a ``sed.DOA(positions, grid, ...)``; ``sr``: the rate of the PCM), and for every event
+    the direction of ``doa.grid`` with the largest steered response power, summed over all microphone pairs at lags of
+    ``1 / doa.oversample`` sample.  Returns the dict of ``event_tdoa`` — the same bits — with ``dir`` int32 [E] (a row of the
+    grid; -1: the event has no frames, or digital silence) and ``doa_power`` float32 [E] (the response per pair and frame at
+    that direction, in [-1, 1]; 0 where ``dir`` is -1); ``return_map=True`` adds ``srp`` float32 [E, D], the response at every
+    direction (secondary peaks are other sources or reflections).  One more launch per slice; the host reads nothing back."""
+    return _tdoa_linear(pcm, clips, channels, events, time_factor, 24, getattr(doa, "max_frames", 256), hop, pad_mode, return_curve,
+                        max_workspace_bytes, (doa, sr, return_map))
+
+
+def event_tdoa_ring(ring, cap, n, channels, events, time_factor, max_lag=24, max_frames=256, hop=HOP, lat_frames=0,
+                    history_frames=0x7fffffff, return_curve=False, max_workspace_bytes=128 << 20):
+    """``event_tdoa`` on the PCM rings of live feeds (``sed_event_tdoa_ring``).  ``ring`` / ``cap`` as ``ring_write``
+    fills them: feed r's ``channels`` lanes are the rings ``r*channels + c``; ``n`` [R] host ints: the samples feed r has
+    received.  ``events`` as ``event_tdoa`` takes them; the feed of an event is its ``rec`` — or ``stream`` — column (needed
+    when R > 1).  An event is located on ``localize.event_frames`` with ``n_feat = 1 + n // hop`` unless
+    ``offset*tf + lat_frames - f0 > history_frames`` (``localize.stream_locates``: the stream's rule) or its first sample has
+    left the ring (``max(0, f0*hop - 1024) < n - cap``): then ``loc_frames = 0``, ``lag = 0``, ``strength = 0`` and nothing is
+    read.  Samples before the start of the feed and beyond ``n`` read as 0 (constant padding).  A located event gets, bit for
+    bit, what ``event_tdoa`` gives on the feed's samples ``[0, n)`` laid out linearly, wherever the ring wraps.  Returns the
+    dict ``event_tdoa`` returns; the host reads nothing back."""
+    return _tdoa_ring(ring, cap, n, channels, events, time_factor, max_lag, max_frames, hop, lat_frames, history_frames, return_curve,
+                      max_workspace_bytes, None)
+
+
+def event_doa_ring(ring, cap, n, channels, events, time_factor, doa, sr=SR, hop=HOP, lat_frames=0, history_frames=0x7fffffff,
+                   return_curve=False, return_map=False, max_workspace_bytes=128 << 20):
+    """``event_doa`` on the PCM rings of live feeds (``sed_event_doa_ring``): the arguments and rules of
+    ``event_tdoa_ring``, the outputs of ``event_doa``; an event the stream's rule or the ring's depth refuses has ``dir = -1``
+    and ``doa_power = 0``.  A located event gets, bit for bit, what ``event_doa`` gives on the feed's samples laid out linearly."""
+    return _tdoa_ring(ring, cap, n, channels, events, time_factor, 24, getattr(doa, "max_frames", 256), hop, lat_frames, history_frames,
+                      return_curve, max_workspace_bytes, (doa, sr, return_map))
+
+
+def ring_write(ring, cap, src, table, workspace=None):
+    """A round's new samples into the PCM rings of live feeds (``sed_stream_ring_write``).  ``ring``: float32 CUDA
+    buffer of ``lanes * cap`` samples, lane l (feed s, channel c: ``s*C + c``) keeps its last ``cap`` samples, sample i of the
+    lane at ``ring[l*cap + i % cap]``; ``src``: the new samples, packed (float32 CUDA, or None when every count is 0);
+    ``table`` [lanes, 3] host ints ``{first sample in src, count <= cap, absolute index of the first sample}``.  One launch;
+    the host reads nothing back.  -> the workspace, for the next call."""
+    _need_ring("ring_write", ring)
+    table = np.ascontiguousarray(np.asarray(table, dtype=np.int64).reshape(-1, 3))
+    lanes, cap = table.shape[0], int(cap)
+    if lanes < 1 or cap < 4 or cap % 4 or lanes * cap > ring.numel():
+        raise ValueError(f"{lanes} lanes of cap={cap} samples (a multiple of 4) do not fit the ring buffer of {ring.numel()} samples")
+    if (table[:, 1] < 0).any() or (table[:, 1] > cap).any():
+        raise ValueError(f"a lane takes 0 to cap={cap} new samples per call, got {int(table[:, 1].min())} .. {int(table[:, 1].max())}")
+    if src is not None:
+        if not (isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.float32):
+            raise RuntimeError("sed_crnn_amd.feature.ring_write needs the new samples as a float32 CUDA(HIP) tensor")
+        src = src.contiguous().view(-1)
+    need = lib().sed_stream_ring_write_workspace_bytes(lanes)
+    if need == 0:
+        raise ValueError(f"sed_stream_ring_write takes 1..65535 lanes, got {lanes}")
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=ring.device)
+    check(lib().sed_stream_ring_write(ptr(ring), ring.numel(), lanes, cap, ptr(src), src.numel() if src is not None else 0,
+                                      C.c_void_p(table.ctypes.data), ptr(workspace), workspace.numel(), stream_ptr()),
+          "sed_stream_ring_write")
+    return workspace
+
+
+# ───────────────────────── a located event's audio: delay-and-sum and MVDR ─────────────────────────
+_BEAM_TAPS = {}              # (device, DelaySum) -> the filter on the device
+
+
+def _beam_empty(dev):
+    return {"audio": torch.empty(0, device=dev), "audio_start": torch.empty(0, dtype=torch.int64, device=dev),
+            "audio_len": torch.empty(0, dtype=torch.int32, device=dev)}
+
+
+def _mvdr_empty(dev, mvdr):
+    out = _beam_empty(dev)
+    if mvdr.noise_blocks:
+        out["noise_frames"] = torch.empty(0, dtype=torch.int32, device=dev)
+    return out
+
+
+@functools.lru_cache(maxsize=8)
+def _mvdr_tables(device_index):
+    """the 2048-point tables with the MVDR beam's window (``localize.mvdr_window``): the header, window and twiddle sections of a
+    ``build_tables`` blob — the mel plan behind them is not read and not kept — cached per device"""
+    from .localize import mvdr_window
+    blob = build_tables(mvdr_window(), slaney_mel_basis(SR, NFFT, NB_MEL), torch.device("cuda", device_index))
+    return blob[:_LM_OFF_ENT].clone()
+
+
+def _extract(src, kind, col, E, tf, hop, max_frames, D, settings, ws_bytes):
+    """the two calls behind the four beam functions: the spans, ONE blocking read of the total (8 bytes) to size ``audio``, the
+    beam ``kind``.  ``settings``: what the beam's C entry takes between ``max_frames`` and the spans; ``mvdr_noise``
+    adds ``noise_frames`` int32 [E] to the dict"""
+    dev = src.x.device
+    out = {"audio_start": torch.empty(E, dtype=torch.int64, device=dev), "audio_len": torch.empty(E, dtype=torch.int32, device=dev)}
+    total = torch.empty(1, dtype=torch.int64, device=dev)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    cols = _col_ptrs(col, _LOCATED)
+    spans, name = _ENTRY["spans", src.ring], _ENTRY[kind, src.ring]
+    check(getattr(lib(), spans)(*src.spans_head, *cols, E, tf, hop, max_frames, D, ptr(out["audio_len"]), ptr(out["audio_start"]), ptr(total),
+                                ptr(ws), ws.numel(), stream_ptr()), spans)
+    n_total = int(total.item())                                       # the one blocking read
+    out["audio"] = torch.empty(n_total, device=dev)
+    noise = []
+    if kind == "mvdr_noise":
+        out["noise_frames"] = torch.zeros(E, dtype=torch.int32, device=dev)      # (a call that extracts nothing launches nothing)
+        noise = [ptr(out["noise_frames"])]
+    check(getattr(lib(), name)(*src.head, *cols, E, tf, hop, max_frames, *settings, ptr(out["audio_len"]), ptr(out["audio_start"]),
+                               ptr(out["audio"]), n_total, *noise, ptr(ws), ws.numel(), stream_ptr()), name)
+    return out
+
+
+def _table_bytes(src):
+    """the workspace bytes of the recording table alone: all that the spans and the delay-and-sum beam need"""
+    return lib().sed_event_beam_ring_workspace_bytes(src.R) if src.ring else lib().sed_event_beam_workspace_bytes(src.R, src.nc)
+
+
+def _beamform(who, src, events, tf, hop, doa, beam, sr):
+    """``event_beamform`` / ``event_beamform_ring`` on their source; M and the taps are uploaded once per device, rate and filter"""
+    from .localize import DelaySum
+    _doa_plan(doa, src.nc, sr)
+    if not isinstance(beam, DelaySum):
+        raise TypeError(f"{who} takes the beam settings as a sed.DelaySum(...) object, got {type(beam).__name__}")
+    dev = src.x.device
+    col, E = _cols(src, events, _LOCATED)
+    key = (dev.index or 0, float(sr), beam.oversample)
+    if key not in doa._beam_device:
+        doa._beam_device[key] = torch.from_numpy(doa.delays(sr, beam.oversample)).to(dev)
+    tkey = (dev.index or 0, beam)
+    if tkey not in _BEAM_TAPS:
+        _BEAM_TAPS[tkey] = torch.from_numpy(beam.taps.copy()).to(dev)                # (the cached table is read-only)
+    if E == 0:
+        return _beam_empty(dev)
+    M = doa._beam_device[key]
+    return _extract(src, "delay_sum", col, E, tf, hop, doa.max_frames, M.shape[0],
+                    [ptr(M), M.shape[0], beam.oversample, beam.half_width, ptr(_BEAM_TAPS[tkey])], _table_bytes(src))
+
+
+def _mvdr(who, src, events, tf, hop, doa, mvdr, sr, max_workspace_bytes):
+    """``event_mvdr`` / ``event_mvdr_ring`` on their source; with ``mvdr.noise_blocks >= 1`` the entry's noise form"""
+    from .localize import MVDR
+    _doa_plan(doa, src.nc, sr)
+    if not isinstance(mvdr, MVDR):
+        raise TypeError(f"{who} takes the beam settings as a sed.MVDR(...) object, got {type(mvdr).__name__}")
+    R, nc, dev, max_frames = src.R, src.nc, src.x.device, doa.max_frames
+    col, E = _cols(src, events, _LOCATED)
+    if E == 0:
+        return _mvdr_empty(dev, mvdr)
+    kind, noise = ("mvdr_noise", [mvdr.noise_blocks, mvdr.noise_guard]) if mvdr.noise_blocks else ("mvdr", [])
+    name = _ENTRY[kind, src.ring] + "_workspace_bytes"
+    need_one = getattr(lib(), name)(R, nc, max_frames, hop, *noise[:1])          # the recording table and one event
+    if need_one == 0:
+        raise ValueError(f"{name} refuses R={R}, channels={nc}, max_frames={max_frames}, hop={hop}")
+    need_tab = _table_bytes(src)
+    key = (dev.index or 0, float(sr))
+    if key not in doa._steering_device:
+        doa._steering_device[key] = torch.from_numpy(doa.steering(sr)).to(dev)
+    tau = doa._steering_device[key]
+    tables = _mvdr_tables(dev.index or 0)
+    ws_bytes = min(need_tab + E * (need_one - need_tab), max(need_one, int(max_workspace_bytes)))
+    return _extract(src, kind, col, E, tf, hop, max_frames, tau.shape[0],
+                    [ptr(tau), tau.shape[0], mvdr.loading, *noise, ptr(tables), tables.numel() * 4], ws_bytes)
+
+
+def event_beamform(pcm, clips, channels, events, time_factor, doa, beam, sr=SR, hop=HOP):
+    """The audio of every located event with the array pointed at it (``sed_event_beam_spans`` + ``sed_event_beamform``, DESIGN
+    5r): a steered delay-and-sum beam.  ``pcm`` / ``clips`` / ``channels`` / ``events`` / ``time_factor`` as ``event_doa`` takes
+    them; the events must also hold ``dir`` and ``loc_frames`` as ``event_doa`` (with the same ``doa``, a ``sed.DOA``) returns
+    them; ``beam``: a ``sed.DelaySum(oversample, half_width, beta)``; ``sr``: the rate of the PCM.  An event with ``dir >= 0``
+    is extracted: its samples are ``localize.event_samples`` — the frames it was located on — and every output sample is the
+    mean over the channels of the channel evaluated ``doa.delays(sr, Q)[dir][c] / Q`` samples earlier, through the 2H-tap filter
+    ``beam.taps`` (samples outside the recording read as 0).  Returns device tensors ``{"audio": float32 [total], "audio_start":
+    int64 [E], "audio_len": int32 [E]}``: event e is ``audio[audio_start[e] : audio_start[e] + audio_len[e]]``, the events packed
+    in event order; events that are not extracted have length 0.  The host does ONE blocking read, the 8 bytes of the total,
+    to size ``audio``; nothing else is read back.  ``E == 0`` returns empty tensors without a launch.  Every sample depends on
+    its event's own samples alone: the batch, the order of the table, the other events and the clip's place in the buffer
+    change no bit."""
+    _need_pcm("event_beamform", pcm)
+    nc, tf, hop = _beam_sizes("event_beamform", channels, time_factor, hop)
+    return _beamform("event_beamform", _linear_source(pcm, clips, nc, align_16=True), events, tf, hop, doa, beam, sr)
+
+
+def event_beamform_ring(ring, cap, n, channels, events, time_factor, doa, beam, sr=SR, hop=HOP):
+    """``event_beamform`` on the PCM rings of live feeds (``sed_event_beam_spans_ring`` + ``sed_event_beamform_ring``):
+    ``ring`` / ``cap`` / ``n`` as ``event_doa_ring`` takes them, the events with the ``dir`` and ``loc_frames`` it returned (an
+    event the stream's rule or the ring's depth refused has ``dir = -1`` and length 0 here); the feed of an event is its
+    ``rec`` — or ``stream`` — column.  An extracted event gets, bit for bit, what ``event_beamform`` gives on the feed's samples
+    ``[0, n)`` laid out linearly, wherever the ring wraps.  Returns what ``event_beamform`` returns, with the same single
+    8-byte read."""
+    _need_ring("event_beamform_ring", ring)
+    nc, tf, hop = _beam_sizes("event_beamform_ring", channels, time_factor, hop)
+    return _beamform("event_beamform_ring", _ring_source(ring, int(cap), n, nc, need_16_byte=True), events, tf, hop, doa, beam, sr)
+
+
+def event_mvdr(pcm, clips, channels, events, time_factor, doa, mvdr, sr=SR, hop=HOP, max_workspace_bytes=128 << 20):
+    """The audio of every located event through an adaptive beam (``sed_event_beam_spans`` + ``sed_event_mvdr``):
+    the arguments, the events that are extracted, their samples and the returned dict — ``audio`` float32 [total],
+    ``audio_start`` int64 [E], ``audio_len`` int32 [E] — are ``event_beamform``'s; ``mvdr``: a ``sed.MVDR(loading)``.  On the
+    event's own grid of 2048-sample frames every 1024 samples (sqrt-Hann window; every sample outside the event read as 0) the
+    spatial covariance of every frequency bin is summed over the event's frames, the weights
+    ``w = (R + loading trace(R)/C I)^-1 d / (d^H (R + ...)^-1 d)`` for the steering vector ``d`` of ``doa.steering(sr)[dir]`` are
+    solved in float64 on the device, and the frames are combined, transformed back and overlap-added.  A source in the
+    event's direction passes unchanged; whatever else the event's frames contain — a second source, above all — is suppressed
+    as far as ``loading`` and the number of frames allow (DESIGN 5s has figures).  The covariance partials of at most
+    ``max_workspace_bytes`` worth of events are held at a time; the slicing changes no bit, and neither do the other events,
+    the batch, the clip's place in the buffer or the samples outside the event.  The host does ONE blocking read, the 8 bytes
+    of the total; ``E == 0`` returns empty tensors without a launch.
+
+    ``sed.MVDR(loading, noise_blocks=Kn, noise_guard=G)`` with ``Kn >= 1`` (``sed_event_mvdr_noise``): an event with
+    ``s0 >= (G + Kn + 1) 1024`` gets its weights from the covariance of the Kn frames before its onset, the samples
+    ``[s0 - (G + Kn + 1) 1024, s0 - G 1024)`` of its recording, which do not hold the target: a steering error no longer makes
+    the beam cancel it.  Every other event gets what ``Kn = 0`` gives, bit for bit.  The dict gains ``noise_frames`` int32 [E]:
+    Kn where the noise covariance was used, else 0.  An event's audio then depends on those samples and its own alone."""
+    _need_pcm("event_mvdr", pcm)
+    nc, tf, hop = _beam_sizes("event_mvdr", channels, time_factor, hop)
+    return _mvdr("event_mvdr", _linear_source(pcm, clips, nc), events, tf, hop, doa, mvdr, sr, max_workspace_bytes)
+
+
+def event_mvdr_ring(ring, cap, n, channels, events, time_factor, doa, mvdr, sr=SR, hop=HOP, max_workspace_bytes=128 << 20):
+    """``event_mvdr`` on the PCM rings of live feeds (``sed_event_beam_spans_ring`` + ``sed_event_mvdr_ring``): ``ring`` /
+    ``cap`` / ``n`` / ``events`` as ``event_beamform_ring`` takes them (an event the stream's rule or the ring's depth refused
+    has ``dir = -1`` and length 0 here; the feed of an event is its ``rec`` — or ``stream`` — column), ``mvdr`` and
+    ``max_workspace_bytes`` as ``event_mvdr``.  An extracted event gets, bit for bit, what ``event_mvdr`` gives on the feed's
+    samples ``[0, n)`` laid out linearly, wherever the ring wraps and whatever the slicing; a sample the ring no longer holds
+    reads as 0.  Returns what ``event_mvdr`` returns, with the same single 8-byte read; ``E == 0`` returns empty tensors without
+    a launch."""
+    _need_ring("event_mvdr_ring", ring)
+    nc, tf, hop = _beam_sizes("event_mvdr_ring", channels, time_factor, hop)
+    return _mvdr("event_mvdr_ring", _ring_source(ring, int(cap), n, nc), events, tf, hop, doa, mvdr, sr, max_workspace_bytes)

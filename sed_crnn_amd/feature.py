@@ -348,6 +348,24 @@ def mbe_packed(pcm, clips, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, pad_mode="
     return out, rows
 
 
+def _clip_table(clips, nc, n_pcm, at_least_one):
+    """checks the clip table of planar recordings of ``nc`` channels in a buffer of ``n_pcm`` samples — every channel inside the
+    buffer, the channels of a recording equally long, and with ``at_least_one`` a recording to work on — -> it as contiguous int64
+    [R * nc, 2]"""
+    table = np.ascontiguousarray(np.asarray(clips, dtype=np.int64).reshape(-1, 2))
+    if at_least_one and (table.shape[0] == 0 or table.shape[0] % nc):
+        raise ValueError(f"{table.shape[0]} clips are not a whole number (>= 1) of recordings of {nc} channels")
+    if table.shape[0] % nc:
+        raise ValueError(f"{table.shape[0]} clips are not a whole number of recordings of {nc} channels")
+    for i, (o, n) in enumerate(table.tolist()):
+        if n < 1 or o < 0 or o + n > n_pcm:
+            raise ValueError(f"recording {i // nc}, channel {i % nc} (first sample {o}, {n} samples) is empty or not inside the "
+                             f"buffer of {n_pcm} samples")
+        if n != table[i - i % nc, 1]:
+            raise ValueError(f"recording {i // nc}: channel {i % nc} has {n} samples, channel 0 has {int(table[i - i % nc, 1])}")
+    return table
+
+
 def mbe_planar(pcm, clips, channels, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, pad_mode="constant", mean=None, std=None,
                tables=None, spatial=None, compress=None):
     """The multichannel twin of ``mbe_packed``: R recordings of ``channels`` planar channels each, all in ONE mono float32 CUDA
@@ -372,16 +390,8 @@ def mbe_planar(pcm, clips, channels, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, 
     nc = int(channels)
     if not 1 <= nc <= 64:
         raise ValueError(f"channels must be 1..64, got {channels}")
-    table = np.ascontiguousarray(np.asarray(clips, dtype=np.int64).reshape(-1, 2))
-    if table.shape[0] % nc:
-        raise ValueError(f"{table.shape[0]} clips are not a whole number of recordings of {nc} channels")
+    table = _clip_table(clips, nc, pcm.numel(), at_least_one=False)
     R = table.shape[0] // nc
-    for i, (o, n) in enumerate(table.tolist()):
-        if n < 1 or o < 0 or o + n > pcm.numel():
-            raise ValueError(f"recording {i // nc}, channel {i % nc} (first sample {o}, {n} samples) is empty or not inside the "
-                             f"buffer of {pcm.numel()} samples")
-        if n != table[i - i % nc, 1]:
-            raise ValueError(f"recording {i // nc}: channel {i % nc} has {n} samples, channel 0 has {int(table[i - i % nc, 1])}")
     if tables is None:
         tables = _tables(pcm.device.index or 0, sr, n_fft, n_mels)
     else:
@@ -420,501 +430,6 @@ def mbe_planar(pcm, clips, channels, sr=SR, n_fft=NFFT, hop=HOP, n_mels=NB_MEL, 
     if compress is not None:
         _pcen_launch(out, compress, compress.smoothing(sr, hop), _rows_table(rows, rows[-1]), 0, nc * n_mels, *pc_scaler, None)
     return out, rows
-
-
-def _tdoa_io(events, R, rec_key, nc, max_lag, return_curve, dev):
-    """the event columns of ``event_tdoa`` / ``event_tdoa_ring`` as contiguous int32 device tensors (``rec_key`` names the
-    recording column, needed when R > 1) and the empty outputs -> (columns with the recording under "rec", E, outputs)"""
-    col = {}
-    for k in ("onset", "offset", "peak_frame") + ((rec_key,) if R > 1 else ()):
-        if k not in events:
-            raise ValueError(f"events has no {k!r}" + (f" ({R} recordings need one)" if k == rec_key else ""))
-        col["rec" if k == rec_key else k] = events[k].to(dev, torch.int32).contiguous()
-    E = col["onset"].numel()
-    if any(v.dim() != 1 or v.numel() != E for v in col.values()):
-        raise ValueError("the event columns must be 1-D and equally long")
-    P, W = nc * (nc - 1) // 2, 2 * max_lag + 3
-    out = {"lag": torch.empty(E, P, device=dev), "strength": torch.empty(E, P, device=dev),
-           "loc_frames": torch.empty(E, dtype=torch.int32, device=dev)}
-    if return_curve:
-        out["acc"] = torch.empty(E, P, W, device=dev)
-    return col, E, out
-
-
-def _doa_plan(doa, nc, sr):
-    """checks the settings of a DOA call (a ``localize.DOA`` for ``nc`` channels) -> its max_lag at rate ``sr``"""
-    from .localize import DOA
-    if not isinstance(doa, DOA):
-        raise TypeError(f"event_doa takes the settings as a sed.DOA(...) object, got {type(doa).__name__}")
-    if doa.channels != nc:
-        raise ValueError(f"the DOA settings hold {doa.channels} microphone positions, the audio has {nc} channels")
-    return doa.plan(sr)[0]
-
-
-def _doa_io(doa, sr, E, dev, out, return_map):
-    """the steering tables of ``doa`` at rate ``sr`` on ``dev`` (uploaded once per device and rate) and, added to ``out``, the
-    outputs a DOA call adds -> [J, D, Q, trig, dir, doa_power, srp or None] as the C entries take them (None without events)"""
-    _, J, trig = doa.plan(sr)
-    out["dir"] = torch.empty(E, dtype=torch.int32, device=dev)
-    out["doa_power"] = torch.empty(E, device=dev)
-    if return_map:
-        out["srp"] = torch.empty(E, J.shape[0], device=dev)
-    if E == 0:
-        return None
-    key = (dev.index or 0, float(sr))
-    if key not in doa._device:
-        doa._device[key] = (torch.from_numpy(J).to(dev), torch.from_numpy(trig).to(dev))
-    Jd, td = doa._device[key]
-    return [ptr(Jd), J.shape[0], doa.oversample, ptr(td), ptr(out["dir"]), ptr(out["doa_power"]), ptr(out.get("srp"))]
-
-
-def event_doa(pcm, clips, channels, events, time_factor, doa, sr=SR, hop=HOP, pad_mode="constant", return_curve=False,
-              return_map=False, max_workspace_bytes=128 << 20):
-    """Per-event direction of arrival for a known array (``sed_event_doa``): ``event_tdoa`` with ``max_lag`` and
-    ``max_frames`` taken from ``doa`` (a ``sed.DOA(positions, grid, ...)``; ``sr``: the rate of the PCM), and for every event
-    the direction of ``doa.grid`` with the largest steered response power, summed over all microphone pairs at lags of
-    ``1 / doa.oversample`` sample.  Returns the dict of ``event_tdoa`` — the same bits — with ``dir`` int32 [E] (a row of the
-    grid; -1: the event has no frames, or digital silence) and ``doa_power`` float32 [E] (the response per pair and frame at
-    that direction, in [-1, 1]; 0 where ``dir`` is -1); ``return_map=True`` adds ``srp`` float32 [E, D], the response at every
-    direction (secondary peaks are other sources or reflections).  One more launch per slice; the host reads nothing back."""
-    return event_tdoa(pcm, clips, channels, events, time_factor, max_frames=getattr(doa, "max_frames", 256),
-                      hop=hop, pad_mode=pad_mode, return_curve=return_curve, max_workspace_bytes=max_workspace_bytes,
-                      _doa=(doa, sr, return_map))
-
-
-def event_doa_ring(ring, cap, n, channels, events, time_factor, doa, sr=SR, hop=HOP, lat_frames=0, history_frames=0x7fffffff,
-                   return_curve=False, return_map=False, max_workspace_bytes=128 << 20):
-    """``event_doa`` on the PCM rings of live feeds (``sed_event_doa_ring``): the arguments and rules of
-    ``event_tdoa_ring``, the outputs of ``event_doa``; an event the stream's rule or the ring's depth refuses has ``dir = -1``
-    and ``doa_power = 0``.  A located event gets, bit for bit, what ``event_doa`` gives on the feed's samples laid out linearly."""
-    return event_tdoa_ring(ring, cap, n, channels, events, time_factor, max_frames=getattr(doa, "max_frames", 256),
-                           hop=hop, lat_frames=lat_frames, history_frames=history_frames, return_curve=return_curve,
-                           max_workspace_bytes=max_workspace_bytes, _doa=(doa, sr, return_map))
-
-
-def event_tdoa(pcm, clips, channels, events, time_factor, max_lag=24, max_frames=256, hop=HOP, pad_mode="constant",
-               return_curve=False, max_workspace_bytes=128 << 20, _doa=None):
-    """Per-event time difference of arrival (``sed_event_tdoa``).  ``pcm`` / ``clips`` / ``channels``: R recordings of
-    2..8 planar channels in one float32 CUDA buffer, as ``mbe_planar`` takes them.  ``events``: a dict of int32 device tensors
-    ``onset``, ``offset`` (exclusive), ``peak_frame`` in output frames of ``time_factor`` feature frames, as the decoders return
-    them, with ``rec`` when R > 1.  For every event and microphone pair p = (i, j), i < j in lexicographic order, the GCC-PHAT of
-    the event's frames (``localize.event_frames``: all of them up to ``max_frames``, else ``max_frames`` around the peak) is
-    accumulated and searched over ``|tau| <= max_lag`` -> a dict of device tensors: ``lag`` float32 [E, P] in samples at the
-    PCM's rate (channel j = channel i delayed by d samples gives -d; seconds = lag / sr), ``strength`` float32 [E, P] in [-1, 1]
-    (the accumulated correlation at the peak per frame), ``loc_frames`` int32 [E] (0: the event names no recording or lies
-    beyond its end; its lag and strength are 0), and with ``return_curve=True`` ``acc`` float32 [E, P, 2*max_lag + 3], the
-    accumulated correlation at lags -(max_lag+1) .. max_lag+1.  The partial sums of at most ``max_workspace_bytes`` worth of
-    events are held at a time; the slicing changes no bit, and neither do the other events, the batch or the clip's place in
-    the buffer.  The host reads nothing back.  The cost is per located frame (every event transforms its own frames: 21 ns per
-    frame at 4 channels on an MI355X): for an event table that covers its recordings more than about five times over — many
-    long, heavily overlapping events — ``mbe_planar(..., spatial="gcc_phat")`` with ``n_mels = 2 * (max_lag + 2)`` followed by sums
-    of the GCC columns over each event's rows is the cheaper route."""
-    import ctypes as C
-    from .localize import MAX_LAG_LIMIT
-    if not (isinstance(pcm, torch.Tensor) and pcm.is_cuda and pcm.dim() == 1):
-        raise RuntimeError("sed_crnn_amd.feature.event_tdoa needs a 1-D CUDA(HIP) PCM buffer; there is no CPU fallback")
-    if pad_mode not in ("constant", "reflect"):
-        raise ValueError(f"pad_mode must be 'constant' or 'reflect', got {pad_mode!r}")
-    nc, tf, max_lag, max_frames, hop = int(channels), int(time_factor), int(max_lag), int(max_frames), int(hop)
-    if _doa is not None:                                              # (doa, sr, return_map) of event_doa: its max_lag
-        max_lag = _doa_plan(_doa[0], nc, _doa[1])
-    if not 2 <= nc <= GCC_MAX_CHANNELS:
-        raise ValueError(f"event_tdoa needs 2 to {GCC_MAX_CHANNELS} audio channels (one estimate per microphone pair), got channels={nc}")
-    if not 1 <= max_lag <= MAX_LAG_LIMIT or max_frames < 1 or tf < 1 or hop < 1:
-        raise ValueError(f"event_tdoa needs 1 <= max_lag <= {MAX_LAG_LIMIT}, max_frames >= 1, time_factor >= 1 and hop >= 1, got "
-                         f"max_lag={max_lag}, max_frames={max_frames}, time_factor={tf}, hop={hop}")
-    table = np.ascontiguousarray(np.asarray(clips, dtype=np.int64).reshape(-1, 2))
-    if table.shape[0] == 0 or table.shape[0] % nc:
-        raise ValueError(f"{table.shape[0]} clips are not a whole number (>= 1) of recordings of {nc} channels")
-    R = table.shape[0] // nc
-    for i, (o, n) in enumerate(table.tolist()):
-        if n < 1 or o < 0 or o + n > pcm.numel():
-            raise ValueError(f"recording {i // nc}, channel {i % nc} (first sample {o}, {n} samples) is empty or not inside the "
-                             f"buffer of {pcm.numel()} samples")
-        if n != table[i - i % nc, 1]:
-            raise ValueError(f"recording {i // nc}: channel {i % nc} has {n} samples, channel 0 has {int(table[i - i % nc, 1])}")
-    dev = pcm.device
-    col, E, out = _tdoa_io(events, R, "rec", nc, max_lag, return_curve, dev)
-    extra = _doa_io(_doa[0], _doa[1], E, dev, out, _doa[2]) if _doa is not None else None
-    if E == 0:
-        return out
-    pcm = pcm.contiguous().float()
-    tables = _tables(dev.index or 0, SR, NFFT, NB_MEL)                # the window and the twiddles; the mel plan is not read
-    longest = int(table[:, 1].max())
-    need_one = lib().sed_event_tdoa_workspace_bytes(R, nc, 1, longest, hop, max_frames)
-    need_all = lib().sed_event_tdoa_workspace_bytes(R, nc, E, longest, hop, max_frames)
-    if need_one == 0:
-        raise ValueError(f"sed_event_tdoa_workspace_bytes refuses R={R}, channels={nc}, hop={hop}, max_frames={max_frames}")
-    ws = torch.empty(min(need_all, max(need_one, int(max_workspace_bytes))), dtype=torch.uint8, device=dev)
-    args = [ptr(pcm), pcm.numel(), C.c_void_p(table.ctypes.data), R, nc, ptr(tables), tables.numel() * 4, ptr(col.get("rec")),
-            ptr(col["onset"]), ptr(col["offset"]), ptr(col["peak_frame"]), E, tf, hop, {"constant": 0, "reflect": 1}[pad_mode], max_lag,
-            max_frames, ptr(out["lag"]), ptr(out["strength"]), ptr(out["loc_frames"]), ptr(out.get("acc"))]
-    if _doa is None:
-        check(lib().sed_event_tdoa(*args, ptr(ws), ws.numel(), stream_ptr()), "sed_event_tdoa")
-    else:                                                             # the same launches and one more (DESIGN 5q)
-        check(lib().sed_event_doa(*args, *extra, ptr(ws), ws.numel(), stream_ptr()), "sed_event_doa")
-    return out
-
-
-def ring_write(ring, cap, src, table, workspace=None):
-    """A round's new samples into the PCM rings of live feeds (``sed_stream_ring_write``).  ``ring``: float32 CUDA
-    buffer of ``lanes * cap`` samples, lane l (feed s, channel c: ``s*C + c``) keeps its last ``cap`` samples, sample i of the
-    lane at ``ring[l*cap + i % cap]``; ``src``: the new samples, packed (float32 CUDA, or None when every count is 0);
-    ``table`` [lanes, 3] host ints ``{first sample in src, count <= cap, absolute index of the first sample}``.  One launch;
-    the host reads nothing back.  -> the workspace, for the next call."""
-    import ctypes as C
-    if not (isinstance(ring, torch.Tensor) and ring.is_cuda and ring.dim() == 1 and ring.dtype == torch.float32 and ring.is_contiguous()):
-        raise RuntimeError("sed_crnn_amd.feature.ring_write needs a contiguous 1-D float32 CUDA(HIP) ring buffer; there is no CPU fallback")
-    table = np.ascontiguousarray(np.asarray(table, dtype=np.int64).reshape(-1, 3))
-    lanes, cap = table.shape[0], int(cap)
-    if lanes < 1 or cap < 4 or cap % 4 or lanes * cap > ring.numel():
-        raise ValueError(f"{lanes} lanes of cap={cap} samples (a multiple of 4) do not fit the ring buffer of {ring.numel()} samples")
-    if (table[:, 1] < 0).any() or (table[:, 1] > cap).any():
-        raise ValueError(f"a lane takes 0 to cap={cap} new samples per call, got {int(table[:, 1].min())} .. {int(table[:, 1].max())}")
-    if src is not None:
-        if not (isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.float32):
-            raise RuntimeError("sed_crnn_amd.feature.ring_write needs the new samples as a float32 CUDA(HIP) tensor")
-        src = src.contiguous().view(-1)
-    need = lib().sed_stream_ring_write_workspace_bytes(lanes)
-    if need == 0:
-        raise ValueError(f"sed_stream_ring_write takes 1..65535 lanes, got {lanes}")
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=ring.device)
-    check(lib().sed_stream_ring_write(ptr(ring), ring.numel(), lanes, cap, ptr(src), src.numel() if src is not None else 0,
-                                      C.c_void_p(table.ctypes.data), ptr(workspace), workspace.numel(), stream_ptr()),
-          "sed_stream_ring_write")
-    return workspace
-
-
-def event_tdoa_ring(ring, cap, n, channels, events, time_factor, max_lag=24, max_frames=256, hop=HOP, lat_frames=0,
-                    history_frames=0x7fffffff, return_curve=False, max_workspace_bytes=128 << 20, _doa=None):
-    """``event_tdoa`` on the PCM rings of live feeds (``sed_event_tdoa_ring``).  ``ring`` / ``cap`` as ``ring_write``
-    fills them: feed r's ``channels`` lanes are the rings ``r*channels + c``; ``n`` [R] host ints: the samples feed r has
-    received.  ``events`` as ``event_tdoa`` takes them; the feed of an event is its ``rec`` — or ``stream`` — column (needed
-    when R > 1).  An event is located on ``localize.event_frames`` with ``n_feat = 1 + n // hop`` unless
-    ``offset*tf + lat_frames - f0 > history_frames`` (``localize.stream_locates``: the stream's rule) or its first sample has
-    left the ring (``max(0, f0*hop - 1024) < n - cap``): then ``loc_frames = 0``, ``lag = 0``, ``strength = 0`` and nothing is
-    read.  Samples before the start of the feed and beyond ``n`` read as 0 (constant padding).  A located event gets, bit for
-    bit, what ``event_tdoa`` gives on the feed's samples ``[0, n)`` laid out linearly, wherever the ring wraps.  Returns the
-    dict ``event_tdoa`` returns; the host reads nothing back."""
-    import ctypes as C
-    from .localize import MAX_LAG_LIMIT
-    if not (isinstance(ring, torch.Tensor) and ring.is_cuda and ring.dim() == 1 and ring.dtype == torch.float32 and ring.is_contiguous()):
-        raise RuntimeError("sed_crnn_amd.feature.event_tdoa_ring needs a contiguous 1-D float32 CUDA(HIP) ring buffer; there is no CPU fallback")
-    nc, tf, max_lag, max_frames, hop, cap = int(channels), int(time_factor), int(max_lag), int(max_frames), int(hop), int(cap)
-    lat, hist = int(lat_frames), int(history_frames)
-    if _doa is not None:                                              # (doa, sr, return_map) of event_doa_ring: its max_lag
-        max_lag = _doa_plan(_doa[0], nc, _doa[1])
-    if not 2 <= nc <= GCC_MAX_CHANNELS:
-        raise ValueError(f"event_tdoa_ring needs 2 to {GCC_MAX_CHANNELS} audio channels (one estimate per microphone pair), got channels={nc}")
-    if not 1 <= max_lag <= MAX_LAG_LIMIT or max_frames < 1 or tf < 1 or hop < 1 or lat < 0 or hist < 1:
-        raise ValueError(f"event_tdoa_ring needs 1 <= max_lag <= {MAX_LAG_LIMIT}, max_frames >= 1, time_factor >= 1, hop >= 1, lat_frames >= 0 "
-                         f"and history_frames >= 1, got max_lag={max_lag}, max_frames={max_frames}, time_factor={tf}, hop={hop}, "
-                         f"lat_frames={lat}, history_frames={hist}")
-    n = np.ascontiguousarray(np.asarray(n, dtype=np.int64).reshape(-1))
-    R = n.shape[0]
-    if R < 1 or (n < 0).any():
-        raise ValueError(f"n must hold one sample count >= 0 per feed, got {n.tolist()[:8]}")
-    if cap < NFFT or cap % 4 or R * nc * cap > ring.numel():
-        raise ValueError(f"{R} feeds of {nc} rings of cap={cap} samples (a multiple of 4, at least {NFFT}) do not fit the ring buffer of "
-                         f"{ring.numel()} samples")
-    dev = ring.device
-    rec_key = "stream" if "stream" in events and "rec" not in events else "rec"
-    col, E, out = _tdoa_io(events, R, rec_key, nc, max_lag, return_curve, dev)
-    extra = _doa_io(_doa[0], _doa[1], E, dev, out, _doa[2]) if _doa is not None else None
-    if E == 0:
-        return out
-    tables = _tables(dev.index or 0, SR, NFFT, NB_MEL)                # the window and the twiddles; the mel plan is not read
-    need_one = lib().sed_event_tdoa_ring_workspace_bytes(R, nc, 1, cap, hop, max_frames)
-    need_all = lib().sed_event_tdoa_ring_workspace_bytes(R, nc, E, cap, hop, max_frames)
-    if need_one == 0:
-        raise ValueError(f"sed_event_tdoa_ring_workspace_bytes refuses R={R}, channels={nc}, cap={cap}, hop={hop}, max_frames={max_frames}")
-    ws = torch.empty(min(need_all, max(need_one, int(max_workspace_bytes))), dtype=torch.uint8, device=dev)
-    args = [ptr(ring), ring.numel(), cap, C.c_void_p(n.ctypes.data), R, nc, ptr(tables), tables.numel() * 4, ptr(col.get("rec")),
-            ptr(col["onset"]), ptr(col["offset"]), ptr(col["peak_frame"]), E, tf, hop, max_lag, max_frames, lat, hist, ptr(out["lag"]),
-            ptr(out["strength"]), ptr(out["loc_frames"]), ptr(out.get("acc"))]
-    if _doa is None:
-        check(lib().sed_event_tdoa_ring(*args, ptr(ws), ws.numel(), stream_ptr()), "sed_event_tdoa_ring")
-    else:
-        check(lib().sed_event_doa_ring(*args, *extra, ptr(ws), ws.numel(), stream_ptr()), "sed_event_doa_ring")
-    return out
-
-
-def _located_cols(events, R, rec_key, dev):
-    """the columns of located events as the C entries of both beams take them (``rec_key`` names the recording column, needed
-    when R > 1) -> ([rec, onset, offset, peak_frame, dir, loc_frames] as pointers to contiguous int32 device tensors, E)"""
-    col = {}
-    for k in ("onset", "offset", "peak_frame", "dir", "loc_frames") + ((rec_key,) if R > 1 else ()):
-        if k not in events:
-            raise ValueError(f"events has no {k!r}" + (f" ({R} recordings need one)" if k == rec_key else
-                                                       " (the events must be located: feature.event_doa)" if k in ("dir", "loc_frames") else ""))
-        col["rec" if k == rec_key else k] = events[k].to(dev, torch.int32).contiguous()
-    E = col["onset"].numel()
-    if any(v.dim() != 1 or v.numel() != E for v in col.values()):
-        raise ValueError("the event columns must be 1-D and equally long")
-    cols = [ptr(col.get("rec")), ptr(col["onset"]), ptr(col["offset"]), ptr(col["peak_frame"]), ptr(col["dir"]), ptr(col["loc_frames"])]
-    return _Kept(cols, col), E
-
-
-class _Kept(list):
-    """a list of pointers that keeps the tensors they point into alive"""
-
-    def __init__(self, items, owner):
-        super().__init__(items)
-        self.owner = owner
-
-
-def _beam_io(who, events, R, rec_key, nc, doa, beam, sr, dev):
-    """checks the settings of a beam call and gathers what both entries pass on -> (event columns as the C entries take them, E,
-    [max_frames, M, D, Q, H, taps] with M and the taps on ``dev``: uploaded once per device, rate and filter)"""
-    from .localize import DelaySum
-    _doa_plan(doa, nc, sr)
-    if not isinstance(beam, DelaySum):
-        raise TypeError(f"{who} takes the beam settings as a sed.DelaySum(...) object, got {type(beam).__name__}")
-    cols, E = _located_cols(events, R, rec_key, dev)
-    key = (dev.index or 0, float(sr), beam.oversample)
-    if key not in doa._beam_device:
-        doa._beam_device[key] = torch.from_numpy(doa.delays(sr, beam.oversample)).to(dev)
-    tkey = (dev.index or 0, beam)
-    if tkey not in _BEAM_TAPS:
-        _BEAM_TAPS[tkey] = torch.from_numpy(beam.taps.copy()).to(dev)                # (the cached table is read-only)
-    M = doa._beam_device[key]
-    return cols, E, [doa.max_frames, ptr(M), M.shape[0], beam.oversample, beam.half_width, ptr(_BEAM_TAPS[tkey])]
-
-
-_BEAM_TAPS = {}              # (device, DelaySum) -> the filter on the device
-
-
-def _beam_empty(dev):
-    return {"audio": torch.empty(0, device=dev), "audio_start": torch.empty(0, dtype=torch.int64, device=dev),
-            "audio_len": torch.empty(0, dtype=torch.int32, device=dev)}
-
-
-def _beam_run(names, head, cols, E, tf, hop, plan, need, dev):
-    """the two calls of a beam entry: the spans, ONE blocking read of the total (8 bytes) to size ``audio``, the beam"""
-    max_frames, M, D, Q, H, taps = plan
-    out = {"audio_start": torch.empty(E, dtype=torch.int64, device=dev), "audio_len": torch.empty(E, dtype=torch.int32, device=dev)}
-    total = torch.empty(1, dtype=torch.int64, device=dev)
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    check(getattr(lib(), names[0])(*head[1], *cols, E, tf, hop, max_frames, D, ptr(out["audio_len"]), ptr(out["audio_start"]), ptr(total),
-                                   ptr(ws), ws.numel(), stream_ptr()), names[0])
-    n_total = int(total.item())
-    out["audio"] = torch.empty(n_total, device=dev)
-    check(getattr(lib(), names[1])(*head[0], *head[1], *cols, E, tf, hop, max_frames, M, D, Q, H, taps, ptr(out["audio_len"]),
-                                   ptr(out["audio_start"]), ptr(out["audio"]), n_total, ptr(ws), ws.numel(), stream_ptr()), names[1])
-    return out
-
-
-def _planar_recordings(who, pcm, clips, channels, time_factor, hop):
-    """checks the PCM buffer and the clip table of ``event_beamform`` / ``event_mvdr`` -> (channels, time_factor, hop, the table as
-    int64 [R * channels, 2], R)"""
-    if not (isinstance(pcm, torch.Tensor) and pcm.is_cuda and pcm.dim() == 1):
-        raise RuntimeError(f"sed_crnn_amd.feature.{who} needs a 1-D CUDA(HIP) PCM buffer; there is no CPU fallback")
-    nc, tf, hop = int(channels), int(time_factor), int(hop)
-    if not 2 <= nc <= GCC_MAX_CHANNELS or tf < 1 or hop < 1:
-        raise ValueError(f"{who} needs 2 to {GCC_MAX_CHANNELS} audio channels, time_factor >= 1 and hop >= 1, got channels={nc}, "
-                         f"time_factor={tf}, hop={hop}")
-    table = np.ascontiguousarray(np.asarray(clips, dtype=np.int64).reshape(-1, 2))
-    if table.shape[0] == 0 or table.shape[0] % nc:
-        raise ValueError(f"{table.shape[0]} clips are not a whole number (>= 1) of recordings of {nc} channels")
-    for i, (o, n) in enumerate(table.tolist()):
-        if n < 1 or o < 0 or o + n > pcm.numel():
-            raise ValueError(f"recording {i // nc}, channel {i % nc} (first sample {o}, {n} samples) is empty or not inside the "
-                             f"buffer of {pcm.numel()} samples")
-        if n != table[i - i % nc, 1]:
-            raise ValueError(f"recording {i // nc}: channel {i % nc} has {n} samples, channel 0 has {int(table[i - i % nc, 1])}")
-    return nc, tf, hop, table, table.shape[0] // nc
-
-
-@functools.lru_cache(maxsize=8)
-def _mvdr_tables(device_index):
-    """the 2048-point tables with the MVDR beam's window (``localize.mvdr_window``): the header, window and twiddle sections of a
-    ``build_tables`` blob — the mel plan behind them is not read and not kept — cached per device"""
-    from .localize import mvdr_window
-    blob = build_tables(mvdr_window(), slaney_mel_basis(SR, NFFT, NB_MEL), torch.device("cuda", device_index))
-    return blob[:_LM_OFF_ENT].clone()
-
-
-def event_mvdr(pcm, clips, channels, events, time_factor, doa, mvdr, sr=SR, hop=HOP, max_workspace_bytes=128 << 20):
-    """The audio of every located event through an adaptive beam (``sed_event_beam_spans`` + ``sed_event_mvdr``):
-    the arguments, the events that are extracted, their samples and the returned dict — ``audio`` float32 [total],
-    ``audio_start`` int64 [E], ``audio_len`` int32 [E] — are ``event_beamform``'s; ``mvdr``: a ``sed.MVDR(loading)``.  On the
-    event's own grid of 2048-sample frames every 1024 samples (sqrt-Hann window; every sample outside the event read as 0) the
-    spatial covariance of every frequency bin is summed over the event's frames, the weights
-    ``w = (R + loading trace(R)/C I)^-1 d / (d^H (R + ...)^-1 d)`` for the steering vector ``d`` of ``doa.steering(sr)[dir]`` are
-    solved in float64 on the device, and the frames are combined, transformed back and overlap-added.  A source in the
-    event's direction passes unchanged; whatever else the event's frames contain — a second source, above all — is suppressed
-    as far as ``loading`` and the number of frames allow (DESIGN 5s has figures).  The covariance partials of at most
-    ``max_workspace_bytes`` worth of events are held at a time; the slicing changes no bit, and neither do the other events,
-    the batch, the clip's place in the buffer or the samples outside the event.  The host does ONE blocking read, the 8 bytes
-    of the total; ``E == 0`` returns empty tensors without a launch.
-
-    ``sed.MVDR(loading, noise_blocks=Kn, noise_guard=G)`` with ``Kn >= 1`` (``sed_event_mvdr_noise``): an event with
-    ``s0 >= (G + Kn + 1) 1024`` gets its weights from the covariance of the Kn frames before its onset, the samples
-    ``[s0 - (G + Kn + 1) 1024, s0 - G 1024)`` of its recording, which do not hold the target: a steering error no longer makes
-    the beam cancel it.  Every other event gets what ``Kn = 0`` gives, bit for bit.  The dict gains ``noise_frames`` int32 [E]:
-    Kn where the noise covariance was used, else 0.  An event's audio then depends on those samples and its own alone."""
-    import ctypes as C
-    from .localize import MVDR
-    nc, tf, hop, table, R = _planar_recordings("event_mvdr", pcm, clips, channels, time_factor, hop)
-    _doa_plan(doa, nc, sr)
-    if not isinstance(mvdr, MVDR):
-        raise TypeError(f"event_mvdr takes the beam settings as a sed.MVDR(...) object, got {type(mvdr).__name__}")
-    dev = pcm.device
-    cols, E = _located_cols(events, R, "rec", dev)
-    if E == 0:
-        return _mvdr_empty(dev, mvdr)
-    pcm = pcm.contiguous().float()
-    need_one = _mvdr_workspace("sed_event_mvdr", R, nc, doa.max_frames, hop, mvdr)
-    head = ([ptr(pcm)], [pcm.numel(), C.c_void_p(table.ctypes.data), R, nc])
-    return _mvdr_run(("sed_event_beam_spans", "sed_event_mvdr"), head, cols, E, tf, hop, doa, mvdr, sr,
-                     lib().sed_event_beam_workspace_bytes(R, nc), need_one, max_workspace_bytes, dev)
-
-
-def _mvdr_empty(dev, mvdr):
-    out = _beam_empty(dev)
-    if mvdr.noise_blocks:
-        out["noise_frames"] = torch.empty(0, dtype=torch.int32, device=dev)
-    return out
-
-
-def _mvdr_workspace(entry, R, nc, max_frames, hop, mvdr):
-    """the workspace bytes of the recording table and one event of ``entry`` (``sed_event_mvdr`` / ``sed_event_mvdr_ring``), or of
-    its noise form where ``mvdr.noise_blocks >= 1``"""
-    if mvdr.noise_blocks:
-        name, args = entry.replace("sed_event_mvdr", "sed_event_mvdr_noise") + "_workspace_bytes", (R, nc, max_frames, hop, mvdr.noise_blocks)
-    else:
-        name, args = entry + "_workspace_bytes", (R, nc, max_frames, hop)
-    need_one = getattr(lib(), name)(*args)
-    if need_one == 0:
-        raise ValueError(f"{name} refuses R={R}, channels={nc}, max_frames={max_frames}, hop={hop}")
-    return need_one
-
-
-def _mvdr_run(names, head, cols, E, tf, hop, doa, mvdr, sr, need_tab, need_one, max_workspace_bytes, dev):
-    """the two calls of an MVDR entry, linear or ring: the spans, ONE blocking read of the total (8 bytes) to size ``audio``, the
-    beam; ``need_tab`` / ``need_one``: the workspace bytes of the recording table alone and with one event.  With
-    ``mvdr.noise_blocks >= 1`` the beam is the entry's noise form and the dict gains ``noise_frames`` int32 [E]"""
-    key = (dev.index or 0, float(sr))
-    if key not in doa._steering_device:
-        doa._steering_device[key] = torch.from_numpy(doa.steering(sr)).to(dev)
-    tau = doa._steering_device[key]
-    tables = _mvdr_tables(dev.index or 0)
-    out = {"audio_start": torch.empty(E, dtype=torch.int64, device=dev), "audio_len": torch.empty(E, dtype=torch.int32, device=dev)}
-    total = torch.empty(1, dtype=torch.int64, device=dev)
-    per_event = need_one - need_tab
-    ws = torch.empty(min(need_tab + E * per_event, max(need_one, int(max_workspace_bytes))), dtype=torch.uint8, device=dev)
-    check(getattr(lib(), names[0])(*head[1], *cols, E, tf, hop, doa.max_frames, tau.shape[0], ptr(out["audio_len"]),
-                                   ptr(out["audio_start"]), ptr(total), ptr(ws), ws.numel(), stream_ptr()), names[0])
-    n_total = int(total.item())                                       # the one blocking read
-    out["audio"] = torch.empty(n_total, device=dev)
-    if mvdr.noise_blocks:
-        name = names[1].replace("sed_event_mvdr", "sed_event_mvdr_noise")
-        out["noise_frames"] = torch.zeros(E, dtype=torch.int32, device=dev)      # (a call that extracts nothing launches nothing)
-        check(getattr(lib(), name)(*head[0], *head[1], *cols, E, tf, hop, doa.max_frames, ptr(tau), tau.shape[0], mvdr.loading,
-                                   mvdr.noise_blocks, mvdr.noise_guard, ptr(tables), tables.numel() * 4, ptr(out["audio_len"]),
-                                   ptr(out["audio_start"]), ptr(out["audio"]), n_total, ptr(out["noise_frames"]), ptr(ws), ws.numel(),
-                                   stream_ptr()), name)
-        return out
-    check(getattr(lib(), names[1])(*head[0], *head[1], *cols, E, tf, hop, doa.max_frames, ptr(tau), tau.shape[0], mvdr.loading,
-                                   ptr(tables), tables.numel() * 4, ptr(out["audio_len"]), ptr(out["audio_start"]), ptr(out["audio"]),
-                                   n_total, ptr(ws), ws.numel(), stream_ptr()), names[1])
-    return out
-
-
-def event_beamform(pcm, clips, channels, events, time_factor, doa, beam, sr=SR, hop=HOP):
-    """The audio of every located event with the array pointed at it (``sed_event_beam_spans`` + ``sed_event_beamform``, DESIGN
-    5r): a steered delay-and-sum beam.  ``pcm`` / ``clips`` / ``channels`` / ``events`` / ``time_factor`` as ``event_doa`` takes
-    them; the events must also hold ``dir`` and ``loc_frames`` as ``event_doa`` (with the same ``doa``, a ``sed.DOA``) returns
-    them; ``beam``: a ``sed.DelaySum(oversample, half_width, beta)``; ``sr``: the rate of the PCM.  An event with ``dir >= 0``
-    is extracted: its samples are ``localize.event_samples`` — the frames it was located on — and every output sample is the
-    mean over the channels of the channel evaluated ``doa.delays(sr, Q)[dir][c] / Q`` samples earlier, through the 2H-tap filter
-    ``beam.taps`` (samples outside the recording read as 0).  Returns device tensors ``{"audio": float32 [total], "audio_start":
-    int64 [E], "audio_len": int32 [E]}``: event e is ``audio[audio_start[e] : audio_start[e] + audio_len[e]]``, the events packed
-    in event order; events that are not extracted have length 0.  The host does ONE blocking read, the 8 bytes of the total,
-    to size ``audio``; nothing else is read back.  ``E == 0`` returns empty tensors without a launch.  Every sample depends on
-    its event's own samples alone: the batch, the order of the table, the other events and the clip's place in the buffer
-    change no bit."""
-    import ctypes as C
-    nc, tf, hop, table, R = _planar_recordings("event_beamform", pcm, clips, channels, time_factor, hop)
-    dev = pcm.device
-    cols, E, plan = _beam_io("event_beamform", events, R, "rec", nc, doa, beam, sr, dev)
-    if E == 0:
-        return _beam_empty(dev)
-    pcm = pcm.contiguous().float()
-    if pcm.data_ptr() % 16:                                           # (a view into a larger buffer: the kernel loads 16 bytes at a time)
-        pcm = pcm.clone()
-    head = ([ptr(pcm)], [pcm.numel(), C.c_void_p(table.ctypes.data), R, nc])
-    return _beam_run(("sed_event_beam_spans", "sed_event_beamform"), head, cols, E, tf, hop, plan,
-                     lib().sed_event_beam_workspace_bytes(R, nc), dev)
-
-
-def event_beamform_ring(ring, cap, n, channels, events, time_factor, doa, beam, sr=SR, hop=HOP):
-    """``event_beamform`` on the PCM rings of live feeds (``sed_event_beam_spans_ring`` + ``sed_event_beamform_ring``):
-    ``ring`` / ``cap`` / ``n`` as ``event_doa_ring`` takes them, the events with the ``dir`` and ``loc_frames`` it returned (an
-    event the stream's rule or the ring's depth refused has ``dir = -1`` and length 0 here); the feed of an event is its
-    ``rec`` — or ``stream`` — column.  An extracted event gets, bit for bit, what ``event_beamform`` gives on the feed's samples
-    ``[0, n)`` laid out linearly, wherever the ring wraps.  Returns what ``event_beamform`` returns, with the same single
-    8-byte read."""
-    import ctypes as C
-    if not (isinstance(ring, torch.Tensor) and ring.is_cuda and ring.dim() == 1 and ring.dtype == torch.float32 and ring.is_contiguous()):
-        raise RuntimeError("sed_crnn_amd.feature.event_beamform_ring needs a contiguous 1-D float32 CUDA(HIP) ring buffer; there is no CPU fallback")
-    nc, tf, hop, cap = int(channels), int(time_factor), int(hop), int(cap)
-    if not 2 <= nc <= GCC_MAX_CHANNELS or tf < 1 or hop < 1:
-        raise ValueError(f"event_beamform_ring needs 2 to {GCC_MAX_CHANNELS} audio channels, time_factor >= 1 and hop >= 1, got "
-                         f"channels={nc}, time_factor={tf}, hop={hop}")
-    n = np.ascontiguousarray(np.asarray(n, dtype=np.int64).reshape(-1))
-    R = n.shape[0]
-    if R < 1 or (n < 0).any():
-        raise ValueError(f"n must hold one sample count >= 0 per feed, got {n.tolist()[:8]}")
-    if cap < NFFT or cap % 4 or R * nc * cap > ring.numel() or ring.data_ptr() % 16:
-        raise ValueError(f"{R} feeds of {nc} rings of cap={cap} samples (a multiple of 4, at least {NFFT}, 16-byte aligned) do not fit the "
-                         f"ring buffer of {ring.numel()} samples")
-    dev = ring.device
-    rec_key = "stream" if "stream" in events and "rec" not in events else "rec"
-    cols, E, plan = _beam_io("event_beamform_ring", events, R, rec_key, nc, doa, beam, sr, dev)
-    if E == 0:
-        return _beam_empty(dev)
-    head = ([ptr(ring), ring.numel(), cap], [C.c_void_p(n.ctypes.data), R, nc])
-    return _beam_run(("sed_event_beam_spans_ring", "sed_event_beamform_ring"), head, cols, E, tf, hop, plan,
-                     lib().sed_event_beam_ring_workspace_bytes(R), dev)
-
-
-def event_mvdr_ring(ring, cap, n, channels, events, time_factor, doa, mvdr, sr=SR, hop=HOP, max_workspace_bytes=128 << 20):
-    """``event_mvdr`` on the PCM rings of live feeds (``sed_event_beam_spans_ring`` + ``sed_event_mvdr_ring``): ``ring`` /
-    ``cap`` / ``n`` / ``events`` as ``event_beamform_ring`` takes them (an event the stream's rule or the ring's depth refused
-    has ``dir = -1`` and length 0 here; the feed of an event is its ``rec`` — or ``stream`` — column), ``mvdr`` and
-    ``max_workspace_bytes`` as ``event_mvdr``.  An extracted event gets, bit for bit, what ``event_mvdr`` gives on the feed's
-    samples ``[0, n)`` laid out linearly, wherever the ring wraps and whatever the slicing; a sample the ring no longer holds
-    reads as 0.  Returns what ``event_mvdr`` returns, with the same single 8-byte read; ``E == 0`` returns empty tensors without
-    a launch."""
-    import ctypes as C
-    from .localize import MVDR
-    if not (isinstance(ring, torch.Tensor) and ring.is_cuda and ring.dim() == 1 and ring.dtype == torch.float32 and ring.is_contiguous()):
-        raise RuntimeError("sed_crnn_amd.feature.event_mvdr_ring needs a contiguous 1-D float32 CUDA(HIP) ring buffer; there is no CPU fallback")
-    nc, tf, hop, cap = int(channels), int(time_factor), int(hop), int(cap)
-    if not 2 <= nc <= GCC_MAX_CHANNELS or tf < 1 or hop < 1:
-        raise ValueError(f"event_mvdr_ring needs 2 to {GCC_MAX_CHANNELS} audio channels, time_factor >= 1 and hop >= 1, got "
-                         f"channels={nc}, time_factor={tf}, hop={hop}")
-    n = np.ascontiguousarray(np.asarray(n, dtype=np.int64).reshape(-1))
-    R = n.shape[0]
-    if R < 1 or (n < 0).any():
-        raise ValueError(f"n must hold one sample count >= 0 per feed, got {n.tolist()[:8]}")
-    if cap < NFFT or cap % 4 or R * nc * cap > ring.numel():
-        raise ValueError(f"{R} feeds of {nc} rings of cap={cap} samples (a multiple of 4, at least {NFFT}) do not fit the ring buffer of "
-                         f"{ring.numel()} samples")
-    _doa_plan(doa, nc, sr)
-    if not isinstance(mvdr, MVDR):
-        raise TypeError(f"event_mvdr_ring takes the beam settings as a sed.MVDR(...) object, got {type(mvdr).__name__}")
-    dev = ring.device
-    rec_key = "stream" if "stream" in events and "rec" not in events else "rec"
-    cols, E = _located_cols(events, R, rec_key, dev)
-    if E == 0:
-        return _mvdr_empty(dev, mvdr)
-    need_one = _mvdr_workspace("sed_event_mvdr_ring", R, nc, doa.max_frames, hop, mvdr)
-    head = ([ptr(ring), ring.numel(), cap], [C.c_void_p(n.ctypes.data), R, nc])
-    return _mvdr_run(("sed_event_beam_spans_ring", "sed_event_mvdr_ring"), head, cols, E, tf, hop, doa, mvdr, sr,
-                     lib().sed_event_beam_ring_workspace_bytes(R), need_one, max_workspace_bytes, dev)
 
 
 def pack_clips(waves, device):
@@ -1035,3 +550,8 @@ def build_fold_packs(per_video, cache_dir, device="cuda"):
                  np.concatenate([v[1] for v in test]))
         paths.append(path)
     return paths
+
+
+# The entries over an event table live in events.py and stay importable from here.  This line stays LAST: events.py imports names
+# of this module while it is still being executed (whichever of the two is imported first) and may use what stands above only.
+from .events import event_beamform, event_beamform_ring, event_doa, event_doa_ring, event_mvdr, event_mvdr_ring, event_tdoa, event_tdoa_ring, ring_write  # noqa: E402,F401

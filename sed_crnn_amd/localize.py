@@ -1,19 +1,19 @@
 """Where a detected event came from: the host side of per-event TDOA (the kernels are csrc/tdoa.hip, the device
-entry ``feature.event_tdoa``).
+entry ``events.event_tdoa``).
 
 ``event_frames`` is the rule that picks the feature frames an event is located on — the kernels apply the same rule on the
 device.  ``stream_latency_frames``, ``stream_ring_samples`` and ``stream_locates`` are the arithmetic of a localising live
 stream: how late an event is emitted, how many samples a lane keeps, and which events are located.  ``TDOA`` holds
 the two settings of ``EventDetector(..., localize=TDOA(...))``.  ``max_lag_for`` and ``tdoa_to_azimuth`` are the far-field
 geometry of ONE microphone pair.  ``DirectionGrid``, ``steering_lags`` and ``DOA`` are the host side of per-event direction of
-arrival for a known array (the kernel is csrc/doa.hip, the device entry ``feature.event_doa``): the directions that
+arrival for a known array (the kernel is csrc/doa.hip, the device entry ``events.event_doa``): the directions that
 are searched, the time difference every direction means for every microphone pair, and the settings of
 ``EventDetector(..., localize=DOA(positions, grid))``.  ``DelaySum``, ``beam_taps``, ``steering_delays`` and ``event_samples`` are
 the host side of per-event audio extraction by a steered delay-and-sum beam (the kernels are csrc/beam.hip, the device
-entry ``feature.event_beamform``): the settings of ``EventDetector(..., localize=DOA(...), extract=DelaySum())``, the
+entry ``events.event_beamform``): the settings of ``EventDetector(..., localize=DOA(...), extract=DelaySum())``, the
 fractional-delay filter, the delay every direction means for every microphone, and the samples an event's audio consists of.
 ``MVDR`` and ``mvdr_window`` are the host side of the adaptive beam that extracts the same events (the kernels are
-csrc/mvdr.hip, the device entry ``feature.event_mvdr``).
+csrc/mvdr.hip, the device entry ``events.event_mvdr``).
 """
 import dataclasses
 import functools
@@ -426,7 +426,7 @@ def steering_delays(positions, grid, sr, c=SPEED_OF_SOUND):
 
 def event_samples(onset, offset, peak_frame, time_factor, n, hop, max_frames, direction, loc_frames):
     """The samples ``[s0, s1)`` of a recording of ``n`` samples that the audio of an event consists of (the kernels of
-    beam.hip apply the same rule).  An event is extracted iff ``direction >= 0`` (``dir`` of ``feature.event_doa``); it was then
+    beam.hip apply the same rule).  An event is extracted iff ``direction >= 0`` (``dir`` of ``events.event_doa``); it was then
     located on the frames ``[f0, f0 + loc_frames)`` with ``f0`` from ``event_frames`` (``n_feat = 1 + n // hop``;
     ``loc_frames`` is read as at most that range), and ``[s0, s1) = [f0 * hop, min((f0 + loc_frames) * hop, n))``.  An event
     that is not extracted — unlocated, beyond its recording, digital silence, refused by a stream's ring rule — and one whose

@@ -44,7 +44,7 @@ locates them from the rings in one ``sed_event_tdoa_ring`` call — an event ``[
 With ``localize=sed.DOA(...)`` that call is ``sed_event_doa_ring`` and the events also carry ``dir`` and ``doa_power``
 (``StreamEvents.doa()``); an event the rule refuses has ``dir = -1``.
 With ``extract=sed.DelaySum(...)`` or ``sed.MVDR(...)`` and ``emit_audio=True`` a step that emitted events makes one
-more call on the same rings, ``feature.event_beamform_ring`` or ``feature.event_mvdr_ring``: the events carry ``audio_start`` and
+more call on the same rings, ``events.event_beamform_ring`` or ``events.event_mvdr_ring``: the events carry ``audio_start`` and
 ``audio_len`` (and, with ``sed.MVDR(noise_blocks >= 1)``, ``noise_frames``: DESIGN 5u) and the call's ``StreamEvents.audio`` holds
 every located event's audio, the offline call's bit for bit.  Nothing
 of it persists between calls: the steps of one push hand their buffers to ``merge_step_audio``.
@@ -58,6 +58,7 @@ from . import feature
 from ._lib import SedHipError, check, lib, ptr, stream_ptr
 from .detect import (_BEAM_KEYS, _DOA_KEYS, _NOISE_KEYS, _TDOA_KEYS, EventDetector, _doa_angles, _event_audio, _event_tensors, _intervals,
                      _noise_frames, _timed, _window_jobs, plan_windows)
+from .events import _beam_empty, _mvdr_empty, event_beamform_ring, event_doa_ring, event_mvdr_ring, event_tdoa_ring, ring_write
 
 _KEYS = ("stream", "cls", "onset", "offset", "peak", "peak_frame")
 
@@ -235,8 +236,8 @@ class StreamDetector:
     others with zeros.  ``"min"`` = ``max_frames + lat``, the least that is accepted: every event of at most ``max_frames``
     feature frames is located.  The ring costs ``4 * C * localize.stream_ring_samples(...)`` bytes per feed.
     ``emit_audio=True`` (a detector with ``extract=sed.DelaySum(...)`` or ``sed.MVDR(...)``, which does not stream without it;
-    DESIGN 5t): a step that emits events also extracts their audio from the rings, ``feature.event_beamform_ring`` or
-    ``feature.event_mvdr_ring`` — every located event's audio is the offline call's, bit for bit, in any chunking; an event the
+    DESIGN 5t): a step that emits events also extracts their audio from the rings, ``events.event_beamform_ring`` or
+    ``events.event_mvdr_ring`` — every located event's audio is the offline call's, bit for bit, in any chunking; an event the
     rule above refuses has ``dir = -1`` and length 0 (``StreamEvents.audio`` / ``event_audio``).  With
     ``extract=sed.MVDR(noise_blocks=Kn)``, ``Kn >= 1``, ``history_frames="min"`` is ``max_frames + lat + nf``,
     ``nf = localize.stream_noise_frames(...)`` feature frames more, and a located event whose weights come from the frames
@@ -407,7 +408,7 @@ class StreamDetector:
         rows = np.where(clip, upto - done, 0)
         n_rows, n_work = int(clip_rows.sum()), int(((total_l + 3) & ~3).sum())
         if self._ring is not None and takes.any():                         # the new samples also go to the rings, from sample _n on
-            self._rws_ring = feature.ring_write(self._ring, self.cap, fresh, np.stack([_excl(takes_l), takes_l, lane(self._n)], 1),
+            self._rws_ring = ring_write(self._ring, self.cap, fresh, np.stack([_excl(takes_l), takes_l, lane(self._n)], 1),
                                                 self._rws_ring)
         self._n, self._fdone = n, upto
         self._cbase, self._clen = np.where(act, a_new, self._cbase), np.where(act, n - a_new, self._clen)
@@ -559,10 +560,10 @@ class StreamDetector:
         if (live & ((self._fdone - 1) * h + feature.NFFT // 2 > self._n)).any() or (self.sched.N > self._fdone).any():
             raise SedHipError("a stream holds final feature frames whose samples it has not received")
         if det.locates_directions:                                          # the same call with the steering launch
-            return _timed(self.marks, "locate", lambda: feature.event_doa_ring(
+            return _timed(self.marks, "locate", lambda: event_doa_ring(
                 self._ring, self.cap, self._n, self.C, events, det.model.time_factor, det.localize_settings, sr=det.sr, hop=h,
                 lat_frames=self.lat, history_frames=self.history_frames))
-        return _timed(self.marks, "locate", lambda: feature.event_tdoa_ring(
+        return _timed(self.marks, "locate", lambda: event_tdoa_ring(
             self._ring, self.cap, self._n, self.C, events, det.model.time_factor, max_lag=t.max_lag, max_frames=t.max_frames, hop=h,
             lat_frames=self.lat, history_frames=self.history_frames))
 
@@ -575,7 +576,7 @@ class StreamDetector:
         if E == 0:                                                          # no launch, no read
             events.update({k: v for k, v in self._no_audio(dev).items() if k != "audio"})
             return torch.empty(0, device=dev)
-        entry = feature.event_mvdr_ring if isinstance(det.extract_settings, MVDR) else feature.event_beamform_ring
+        entry = event_mvdr_ring if isinstance(det.extract_settings, MVDR) else event_beamform_ring
         given = events
         if self.noise_frames:
             given = {**events, "dir": self._dir_with_noise_history(events)}
@@ -588,8 +589,8 @@ class StreamDetector:
     def _no_audio(self, dev):
         """the extraction columns of an empty event table"""
         if self.noise_frames:
-            return feature._mvdr_empty(dev, self.det.extract_settings)
-        return feature._beam_empty(dev)
+            return _mvdr_empty(dev, self.det.extract_settings)
+        return _beam_empty(dev)
 
     def _dir_with_noise_history(self, events):
         """``dir`` for the extraction alone, by device tensor ops (no host read): -1 where the event's weights come from the
