@@ -681,6 +681,43 @@ int sed_event_mvdr_noise_ring(const float* ring, long ring_len, long cap, const 
                               const int* audio_len, const long* audio_start, float* audio, long audio_total, int* noise_frames_out,
                               void* workspace, size_t workspace_bytes, void* stream);
 
+/* sed_event_quiet_frames / sed_event_mvdr_quiet: the noise covariance of sed_event_mvdr_noise from the frames where the
+ * event's class is silent.  Settings: Kn = noise_blocks in [1, 256], G = noise_guard in [0, 64], S = noise_search in [Kn, 1024],
+ * M = noise_min in [1, Kn], n_classes in [1, 32], exclude_any 0 or 1; B = 1024, H = time_factor * hop.  All of the rule is integer:
+ *   mask[r][t], t < L_r = n_r / H + 1, has bit k set when some row of the WHOLE table — located or not — has rec = r, cls = k and
+ *     onset <= t < offset (both clamped to [0, L_r]); a row with rec outside [0, R), cls outside [0, n_classes) or onset < 0 marks nothing;
+ *   candidate q = 0..S-1 of an extracted event [s0, s1) is the 2048 samples from s0 - (G + 2 + q) B; it exists when that is >= 0 and
+ *     is eligible when mask[r][t] & excl == 0 for every t = max(lo, 0) / H .. ceil(hi / H) - 1 of [lo, hi) = [s0 - (2 G + 2 + q) B,
+ *     s0 - q B); excl = 1 << cls, or all bits with exclude_any;
+ *   the first Kn eligible candidates in ascending q are selected, n_e of them; an extracted event with cls in [0, n_classes) and
+ *     n_e >= M gets its weights from Rn = sum X X^H over them in ascending time (descending q; fp32, chunks of 32 frames added in
+ *     ascending order; a sample outside the recording reads as 0), by sed_event_mvdr's formula with Rn in place of R.  Every other
+ *     extracted event gets sed_event_mvdr's audio, bit for bit; an event whose Kn nearest candidates are eligible and whose
+ *     s0 >= (G + Kn + 1) B gets sed_event_mvdr_noise's, bit for bit.
+ * ev_cls: DEVICE int32 [E].  noise_frames_out: DEVICE int32 [E], n_e where the noise covariance is used, else 0; noise_sel_out: DEVICE
+ * int32 [E][Kn], the used q in summation order, -1 behind them (a row of -1 where it is unused).  Both are written for every row when
+ * something is launched (sed_event_quiet_frames: E > 0; sed_event_mvdr_quiet: E > 0 and audio_total > 0).  sed_event_quiet_frames is
+ * the activity and the selection alone and reads no sample; sed_event_mvdr_quiet takes sed_event_mvdr_noise's arguments and these.
+ * workspace: at least sed_event_quiet_frames_workspace_bytes(R, channels, mask_frames, noise_blocks) /
+ * sed_event_mvdr_quiet_workspace_bytes(R, channels, max_frames, hop, noise_blocks, mask_frames) with mask_frames = sum_r L_r (0:
+ * refused sizes) — the recording table, the mask and, for the beam, one event's partials and weights; the mask is made once from
+ * the whole table, whatever the slicing.  Every argument is checked on the host before anything is enqueued; messages begin with
+ * "quiet_frames:" / "mvdr_quiet:".  There is no ring form. */
+size_t sed_event_quiet_frames_workspace_bytes(int R, int channels, long mask_frames, int noise_blocks);
+int sed_event_quiet_frames(long pcm_len, const long* clips_host, int R, int channels, const int* ev_rec, const int* ev_cls,
+                           const int* ev_onset, const int* ev_offset, const int* ev_peak_frame, const int* ev_dir,
+                           const int* ev_loc_frames, long E, int time_factor, int hop, int max_frames, int D, int n_classes,
+                           int noise_blocks, int noise_guard, int noise_search, int noise_min, int exclude_any, int* noise_frames_out,
+                           int* noise_sel_out, void* workspace, size_t workspace_bytes, void* stream);
+size_t sed_event_mvdr_quiet_workspace_bytes(int R, int channels, int max_frames, int hop, int noise_blocks, long mask_frames);
+int sed_event_mvdr_quiet(const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const int* ev_rec,
+                         const int* ev_cls, const int* ev_onset, const int* ev_offset, const int* ev_peak_frame, const int* ev_dir,
+                         const int* ev_loc_frames, long E, int time_factor, int hop, int max_frames, const double* tau, int D,
+                         double loading, int noise_blocks, int noise_guard, int n_classes, int noise_search, int noise_min,
+                         int exclude_any, const void* tables, size_t tables_bytes, const int* audio_len, const long* audio_start,
+                         float* audio, long audio_total, int* noise_frames_out, int* noise_sel_out, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
 /* sed_pcen: per-channel energy normalisation, IN PLACE, of the columns [col0, col0 + W) of x [rows][stride], which
  * hold log-mel values (natural log, as sed_logmel* write them without a scaler); the other columns are not touched.  Every column
  * of a recording is one chain: E[t] = scale * exp(x[t]); M[t] = (1 - smooth_b) M[t-1] + smooth_b E[t] with M[0] = E[0] (librosa's

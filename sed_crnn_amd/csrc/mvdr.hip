@@ -41,6 +41,18 @@
 // mvdr_ring_noise_k are the covariance body over those frames (mv_load_abs / mv_load_abs_ring: direct loads, or guarded ones
 // with every index checked against the recording); a slice is then four launches — own covariance, noise covariance, weights,
 // apply — and each covariance launch returns at once for the other's events.  noise_frames_out says which events used it.
+//
+// The noise frames where the event's class is silent: sed_event_quiet_frames / sed_event_mvdr_quiet.  The whole
+// event table is rasterised once into mask[r][t], a uint32 of class bits per recording and output frame of H = tf hop samples
+// (mvdr_activity_k: atomicOr from vector lanes, the result is order-free); mvdr_select_k, a wave per event, walks the S
+// candidates q — the 2048 samples from s0 - (G + 2 + q) B, tested on [s0 - (2 G + 2 + q) B, s0 - q B) against the mask — with a
+// ballot and a prefix count, keeps the first Kn eligible ones and writes them in summation order (descending q) to noise_sel,
+// n_e >= noise_min of them to noise_frames (else 0 and a row of -1: the event keeps its own frames).  A slice is then
+// mvdr_quiet_own_k (the own covariance of the events with noise_frames = 0), mvdr_quiet_k (the covariance body over the selected
+// frames, mv_load_abs at s0 - (G + 2 + noise_sel[e][j]) B), mvdr_quiet_weights_k (the weight body with the chunk count taken from
+// noise_frames) and mvdr_apply_k as it is.  An event whose Kn nearest candidates are eligible reads the frames of
+// sed_event_mvdr_noise in its order through the same code: the same bits.  All of it is integer and a function of the table and
+// the settings alone.
 #include <math.h>
 #include "common.h"
 #include "fft2048.h"
@@ -184,6 +196,20 @@ __device__ __forceinline__ void mv_load_noise(f2 (&z)[32], const float* __restri
     else mv_load_abs(z, pcm + ta.sample_off[(long)rec * ta.C + ch], n, first, scr, fl);
 }
 
+// the frames mvdr_select_k listed for event e (0: it keeps its own), never more than the kn its row of noise_sel holds
+__device__ __forceinline__ int mv_quiet_frames(const MvArgs& ma, long e) {
+    const int n = ma.noise_frames[e];
+    return n < 0 ? 0 : n > ma.kn ? ma.kn : n;
+}
+
+// candidate q of channel ch of the event at s0 of recording rec: the 2048 samples from s0 - (guard + 2 + q) B on,
+// read from the recording; q = kn - 1 - j is mv_load_noise's frame j
+__device__ __forceinline__ void mv_load_quiet(f2 (&z)[32], const float* __restrict__ pcm, const TdArgs& ta, const MvArgs& ma, int rec, int ch,
+                                              long s0, int q, float* scr, const FftLane& fl) {
+    const long n = ta.n_samples[rec], first = s0 - (long)(ma.guard + 2 + q) * MV_B;
+    mv_load_abs(z, pcm + ta.sample_off[(long)rec * ta.C + ch], n, first, scr, fl);
+}
+
 // frame j of channel ch of the event at s0 of recording rec: RING = false from the planar PCM, RING = true from the feed's rings
 template <bool RING>
 __device__ __forceinline__ void mv_load(f2 (&z)[32], const float* __restrict__ pcm, const TdArgs& ta, int rec, int ch, long s0, int len,
@@ -200,20 +226,29 @@ __device__ __forceinline__ void mv_load(f2 (&z)[32], const float* __restrict__ p
 // of live feeds (mvdr_ring_cov_k, mvdr_ring_apply_k): two kernels each, not one with a run-time branch, so that the linear
 // kernels compile to what they were before the rings existed; only mv_load differs.  NOISE = true (mvdr_noise_k,
 // mvdr_ring_noise_k) is the same body over the kn frames before the onset of the events whose weights come from
-// them; with kn > 0 the two launches share the events between them and each leaves the other's alone.
-template <bool RING, bool NOISE>
+// them; with kn > 0 the two launches share the events between them and each leaves the other's alone.  MV_QUIET (mvdr_quiet_k;
+// DESIGN 5w) is the same body over the noise_frames[e] frames that mvdr_select_k listed in qsel [E][kn], and MV_QUIET_OWN
+// (mvdr_quiet_own_k) the own frames of the events it listed none for: the pair shares the events by noise_frames, which the
+// selection has written before the first slice.
+#define MV_OWN 0
+#define MV_NOISE 1
+#define MV_QUIET 2
+#define MV_QUIET_OWN 3
+template <bool RING, int MODE>
 __device__ __forceinline__ void mv_cov_body(const float* __restrict__ pcm, const uint32_t* __restrict__ tables, float2* __restrict__ ws,
-                                            TdArgs ta, MvArgs ma) {
+                                            TdArgs ta, MvArgs ma, const int* __restrict__ qsel = nullptr) {
+    constexpr bool NOISE = MODE == MV_NOISE, PRE = MODE == MV_NOISE || MODE == MV_QUIET;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x;
     const long e = ta.e0 + blockIdx.y;
     int rec, len;
     long s0;
     mv_event(ta, ma, e, rec, s0, len);
-    const bool noise = len != 0 && mv_uses_noise(ma, s0);
+    const int listed = MODE >= MV_QUIET ? mv_quiet_frames(ma, e) : 0;
+    const bool noise = len != 0 && (MODE >= MV_QUIET ? listed > 0 : mv_uses_noise(ma, s0));
     if (NOISE && blockIdx.x == 0 && tid == 0) ma.noise_frames[e] = noise ? ma.kn : 0;
-    if (len == 0 || noise != NOISE) return;                      // (block-uniform: before any barrier)
-    const int nfr = NOISE ? ma.kn : (len + MV_B - 1) / MV_B + 1; // the frames before the onset, or frames 0 .. J
+    if (len == 0 || noise != PRE) return;                        // (block-uniform: before any barrier)
+    const int nfr = NOISE ? ma.kn : MODE == MV_QUIET ? listed : (len + MV_B - 1) / MV_B + 1;     // the frames before the onset, or frames 0 .. J
     const int fc0 = blockIdx.x * MV_CHUNK;
     if (fc0 >= nfr) return;
     const int fc1 = fc0 + MV_CHUNK < nfr ? fc0 + MV_CHUNK : nfr;
@@ -243,6 +278,7 @@ __device__ __forceinline__ void mv_cov_body(const float* __restrict__ pcm, const
                 const int ch = (2 * wave + half < C) ? 2 * wave + half : C - 1;
                 f2 z[32];
                 if (NOISE) mv_load_noise<RING>(z, pcm, ta, ma, rec, ch, s0, j, scr, fl);
+                else if (MODE == MV_QUIET) mv_load_quiet(z, pcm, ta, ma, rec, ch, s0, qsel[e * ma.kn + j], scr, fl);
                 else mv_load<RING>(z, pcm, ta, rec, ch, s0, len, j, scr, fl);
                 fft2048_passes(z, fl, s_win, s_tw);
                 fft2048_spectrum(z, fl, s_pw, s_spec + ch * PHAT_SPEC);
@@ -274,126 +310,148 @@ __device__ __forceinline__ void mv_cov_body(const float* __restrict__ pcm, const
 
 __global__ __launch_bounds__(MV_THREADS) void mvdr_cov_k(const float* __restrict__ pcm, const uint32_t* __restrict__ tables,
                                                          float2* __restrict__ ws, TdArgs ta, MvArgs ma) {
-    mv_cov_body<false, false>(pcm, tables, ws, ta, ma);
+    mv_cov_body<false, MV_OWN>(pcm, tables, ws, ta, ma);
 }
 
 __global__ __launch_bounds__(MV_THREADS) void mvdr_ring_cov_k(const float* __restrict__ ring, const uint32_t* __restrict__ tables,
                                                               float2* __restrict__ ws, TdArgs ta, MvArgs ma) {
-    mv_cov_body<true, false>(ring, tables, ws, ta, ma);
+    mv_cov_body<true, MV_OWN>(ring, tables, ws, ta, ma);
 }
 
 __global__ __launch_bounds__(MV_THREADS) void mvdr_noise_k(const float* __restrict__ pcm, const uint32_t* __restrict__ tables,
                                                            float2* __restrict__ ws, TdArgs ta, MvArgs ma) {
-    mv_cov_body<false, true>(pcm, tables, ws, ta, ma);
+    mv_cov_body<false, MV_NOISE>(pcm, tables, ws, ta, ma);
 }
 
 __global__ __launch_bounds__(MV_THREADS) void mvdr_ring_noise_k(const float* __restrict__ ring, const uint32_t* __restrict__ tables,
                                                                 float2* __restrict__ ws, TdArgs ta, MvArgs ma) {
-    mv_cov_body<true, true>(ring, tables, ws, ta, ma);
+    mv_cov_body<true, MV_NOISE>(ring, tables, ws, ta, ma);
+}
+
+__global__ __launch_bounds__(MV_THREADS) void mvdr_quiet_own_k(const float* __restrict__ pcm, const uint32_t* __restrict__ tables,
+                                                               float2* __restrict__ ws, TdArgs ta, MvArgs ma) {
+    mv_cov_body<false, MV_QUIET_OWN>(pcm, tables, ws, ta, ma);
+}
+
+__global__ __launch_bounds__(MV_THREADS) void mvdr_quiet_k(const float* __restrict__ pcm, const uint32_t* __restrict__ tables,
+                                                           float2* __restrict__ ws, TdArgs ta, MvArgs ma, const int* __restrict__ qsel) {
+    mv_cov_body<false, MV_QUIET>(pcm, tables, ws, ta, ma, qsel);
 }
 
 // Every thread works in its own column of the three arrays: no thread reads what another writes, and there is no barrier.
+// One text for two kernels (a macro, not a shared function: mvdr_weights_k must compile to what it was before its sibling
+// existed, and with its body in an inlined function it does not).  FRAMES: the frames behind an extracted event's weights —
+// mvdr_weights_k: its own 0 .. J, or the kn before its onset; mvdr_quiet_weights_k: those that
+// mvdr_select_k listed for it.
+#define MV_WEIGHTS_BODY(FRAMES)                                                                                                              \
+    __shared__ double2 s_A[MV_MAX_TRI][MV_WT];                   /* the lower triangle of R + lambda I, then of its Cholesky factor */       \
+    __shared__ double2 s_d[TD_MAX_CH][MV_WT];                                                                                                \
+    __shared__ double2 s_v[TD_MAX_CH][MV_WT];                                                                                                \
+    const int tid = threadIdx.x, k = blockIdx.x * MV_WT + tid;                                                                               \
+    if (k > LM_N) return;                                                                                                                    \
+    const long e = ta.e0 + blockIdx.y;                                                                                                       \
+    int rec, len;                                                                                                                            \
+    long s0;                                                                                                                                 \
+    mv_event(ta, ma, e, rec, s0, len);                                                                                                       \
+    if (len == 0) return;                                                                                                                    \
+    const int C = ta.C, T = C * (C + 1) / 2;                                                                                                 \
+    const int nfr = FRAMES, nch = (nfr + MV_CHUNK - 1) / MV_CHUNK;                                                                           \
+    float2* wev = ws + (long)blockIdx.y * ma.rows * PHAT_SPEC;                                                                               \
+    float2* wout = wev + (long)ma.cpe * T * PHAT_SPEC;           /* [C][PHAT_SPEC] */                                                        \
+    _Pragma("unroll 1")                                                                                                                      \
+    for (int t = 0; t < T; ++t) {                                                                                                            \
+        float2 s = wev[(long)t * PHAT_SPEC + k];                                                                                             \
+    _Pragma("unroll 1")                                                                                                                      \
+        for (int c = 1; c < nch; ++c) {                          /* fp32, ascending chunks */                                                \
+            const float2 p = wev[((long)c * T + t) * PHAT_SPEC + k];                                                                         \
+            s.x += p.x; s.y += p.y;                                                                                                          \
+        }                                                                                                                                    \
+        s_A[t][tid] = make_double2((double)s.x, (double)s.y);                                                                                \
+    }                                                                                                                                        \
+    double trace = 0.0;                                                                                                                      \
+    _Pragma("unroll 1")                                                                                                                      \
+    for (int i = 0; i < C; ++i) trace += s_A[i * (i + 1) / 2 + i][tid].x;                                                                    \
+    const double* trow = tau + (long)ma.ev_dir[e] * C;           /* (0 <= dir < D: the event has samples) */                                 \
+    _Pragma("unroll 1")                                                                                                                      \
+    for (int c = 0; c < C; ++c) {                                                                                                            \
+        double sn, cs;                                                                                                                       \
+        sincospi((double)k * trow[c] * (1.0 / MV_B), &sn, &cs);  /* 2 pi k tau / 2048 */                                                     \
+        s_d[c][tid] = make_double2(cs, sn);                                                                                                  \
+    }                                                                                                                                        \
+    if (!(trace > 0.0)) {                                        /* digital silence (or NaN samples): the plain average */                   \
+    _Pragma("unroll 1")                                                                                                                      \
+        for (int c = 0; c < C; ++c) wout[(long)c * PHAT_SPEC + k] = make_float2((float)(s_d[c][tid].x / C), (float)(s_d[c][tid].y / C));     \
+        return;                                                                                                                              \
+    }                                                                                                                                        \
+    const double lambda = loading * trace / C;                                                                                               \
+    _Pragma("unroll 1")                                                                                                                      \
+    for (int i = 0; i < C; ++i) {                                                                                                            \
+        double2 a = s_A[i * (i + 1) / 2 + i][tid];                                                                                           \
+        s_A[i * (i + 1) / 2 + i][tid] = make_double2(a.x + lambda, 0.0);                                                                     \
+    }                                                                                                                                        \
+    /* ── Cholesky, in place: L[i][j], j <= i, at i (i + 1) / 2 + j; the diagonal holds 1 / L[j][j] in .y ── */                              \
+    _Pragma("unroll 1")                                                                                                                      \
+    for (int j = 0; j < C; ++j) {                                                                                                            \
+        const int rj = j * (j + 1) / 2;                                                                                                      \
+        double s = s_A[rj + j][tid].x;                                                                                                       \
+    _Pragma("unroll 1")                                                                                                                      \
+        for (int p = 0; p < j; ++p) { const double2 l = s_A[rj + p][tid]; s -= l.x * l.x + l.y * l.y; }                                      \
+        const double ljj = sqrt(s), inv = 1.0 / ljj;                                                                                         \
+        s_A[rj + j][tid] = make_double2(ljj, inv);                                                                                           \
+    _Pragma("unroll 1")                                                                                                                      \
+        for (int i = j + 1; i < C; ++i) {                                                                                                    \
+            const int ri = i * (i + 1) / 2;                                                                                                  \
+            double2 a = s_A[ri + j][tid];                                                                                                    \
+    _Pragma("unroll 1")                                                                                                                      \
+            for (int p = 0; p < j; ++p) {                        /* a -= L[i][p] conj L[j][p] */                                             \
+                const double2 li = s_A[ri + p][tid], lj = s_A[rj + p][tid];                                                                  \
+                a.x -= li.x * lj.x + li.y * lj.y;                                                                                            \
+                a.y -= li.y * lj.x - li.x * lj.y;                                                                                            \
+            }                                                                                                                                \
+            s_A[ri + j][tid] = make_double2(a.x * inv, a.y * inv);                                                                           \
+        }                                                                                                                                    \
+    }                                                                                                                                        \
+    /* ── L y = d, then L^H v = y ── */                                                                                                      \
+    _Pragma("unroll 1")                                                                                                                      \
+    for (int i = 0; i < C; ++i) {                                                                                                            \
+        const int ri = i * (i + 1) / 2;                                                                                                      \
+        double2 y = s_d[i][tid];                                                                                                             \
+    _Pragma("unroll 1")                                                                                                                      \
+        for (int p = 0; p < i; ++p) {                                                                                                        \
+            const double2 l = s_A[ri + p][tid], v = s_v[p][tid];                                                                             \
+            y.x -= l.x * v.x - l.y * v.y;                                                                                                    \
+            y.y -= l.x * v.y + l.y * v.x;                                                                                                    \
+        }                                                                                                                                    \
+        const double inv = s_A[ri + i][tid].y;                                                                                               \
+        s_v[i][tid] = make_double2(y.x * inv, y.y * inv);                                                                                    \
+    }                                                                                                                                        \
+    _Pragma("unroll 1")                                                                                                                      \
+    for (int i = C - 1; i >= 0; --i) {                                                                                                       \
+        double2 y = s_v[i][tid];                                                                                                             \
+    _Pragma("unroll 1")                                                                                                                      \
+        for (int p = i + 1; p < C; ++p) {                        /* y -= conj L[p][i] v[p] */                                                \
+            const double2 l = s_A[p * (p + 1) / 2 + i][tid], v = s_v[p][tid];                                                                \
+            y.x -= l.x * v.x + l.y * v.y;                                                                                                    \
+            y.y -= l.x * v.y - l.y * v.x;                                                                                                    \
+        }                                                                                                                                    \
+        const double inv = s_A[i * (i + 1) / 2 + i][tid].y;                                                                                  \
+        s_v[i][tid] = make_double2(y.x * inv, y.y * inv);                                                                                    \
+    }                                                                                                                                        \
+    double den = 0.0;                                            /* d^H v = d^H (R + lambda I)^-1 d: real and positive */                    \
+    _Pragma("unroll 1")                                                                                                                      \
+    for (int c = 0; c < C; ++c) den += s_d[c][tid].x * s_v[c][tid].x + s_d[c][tid].y * s_v[c][tid].y;                                        \
+    const double scale = 1.0 / den;                                                                                                          \
+    _Pragma("unroll 1")                                                                                                                      \
+    for (int c = 0; c < C; ++c) wout[(long)c * PHAT_SPEC + k] = make_float2((float)(s_v[c][tid].x * scale), (float)(s_v[c][tid].y * scale));
+
 __global__ __launch_bounds__(MV_WT) void mvdr_weights_k(float2* __restrict__ ws, const double* __restrict__ tau, double loading,
                                                         TdArgs ta, MvArgs ma) {
-    __shared__ double2 s_A[MV_MAX_TRI][MV_WT];                   // the lower triangle of R + lambda I, then of its Cholesky factor
-    __shared__ double2 s_d[TD_MAX_CH][MV_WT];
-    __shared__ double2 s_v[TD_MAX_CH][MV_WT];
-    const int tid = threadIdx.x, k = blockIdx.x * MV_WT + tid;
-    if (k > LM_N) return;
-    const long e = ta.e0 + blockIdx.y;
-    int rec, len;
-    long s0;
-    mv_event(ta, ma, e, rec, s0, len);
-    if (len == 0) return;
-    const int C = ta.C, T = C * (C + 1) / 2;
-    const int nfr = mv_uses_noise(ma, s0) ? ma.kn : (len + MV_B - 1) / MV_B + 1, nch = (nfr + MV_CHUNK - 1) / MV_CHUNK;
-    float2* wev = ws + (long)blockIdx.y * ma.rows * PHAT_SPEC;
-    float2* wout = wev + (long)ma.cpe * T * PHAT_SPEC;           // [C][PHAT_SPEC]
-#pragma unroll 1
-    for (int t = 0; t < T; ++t) {
-        float2 s = wev[(long)t * PHAT_SPEC + k];
-#pragma unroll 1
-        for (int c = 1; c < nch; ++c) {                          // fp32, ascending chunks
-            const float2 p = wev[((long)c * T + t) * PHAT_SPEC + k];
-            s.x += p.x; s.y += p.y;
-        }
-        s_A[t][tid] = make_double2((double)s.x, (double)s.y);
-    }
-    double trace = 0.0;
-#pragma unroll 1
-    for (int i = 0; i < C; ++i) trace += s_A[i * (i + 1) / 2 + i][tid].x;
-    const double* trow = tau + (long)ma.ev_dir[e] * C;           // (0 <= dir < D: the event has samples)
-#pragma unroll 1
-    for (int c = 0; c < C; ++c) {
-        double sn, cs;
-        sincospi((double)k * trow[c] * (1.0 / MV_B), &sn, &cs);  // 2 pi k tau / 2048
-        s_d[c][tid] = make_double2(cs, sn);
-    }
-    if (!(trace > 0.0)) {                                        // digital silence (or NaN samples): the plain average
-#pragma unroll 1
-        for (int c = 0; c < C; ++c) wout[(long)c * PHAT_SPEC + k] = make_float2((float)(s_d[c][tid].x / C), (float)(s_d[c][tid].y / C));
-        return;
-    }
-    const double lambda = loading * trace / C;
-#pragma unroll 1
-    for (int i = 0; i < C; ++i) {
-        double2 a = s_A[i * (i + 1) / 2 + i][tid];
-        s_A[i * (i + 1) / 2 + i][tid] = make_double2(a.x + lambda, 0.0);
-    }
-    // ── Cholesky, in place: L[i][j], j <= i, at i (i + 1) / 2 + j; the diagonal holds 1 / L[j][j] in .y ──
-#pragma unroll 1
-    for (int j = 0; j < C; ++j) {
-        const int rj = j * (j + 1) / 2;
-        double s = s_A[rj + j][tid].x;
-#pragma unroll 1
-        for (int p = 0; p < j; ++p) { const double2 l = s_A[rj + p][tid]; s -= l.x * l.x + l.y * l.y; }
-        const double ljj = sqrt(s), inv = 1.0 / ljj;
-        s_A[rj + j][tid] = make_double2(ljj, inv);
-#pragma unroll 1
-        for (int i = j + 1; i < C; ++i) {
-            const int ri = i * (i + 1) / 2;
-            double2 a = s_A[ri + j][tid];
-#pragma unroll 1
-            for (int p = 0; p < j; ++p) {                        // a -= L[i][p] conj L[j][p]
-                const double2 li = s_A[ri + p][tid], lj = s_A[rj + p][tid];
-                a.x -= li.x * lj.x + li.y * lj.y;
-                a.y -= li.y * lj.x - li.x * lj.y;
-            }
-            s_A[ri + j][tid] = make_double2(a.x * inv, a.y * inv);
-        }
-    }
-    // ── L y = d, then L^H v = y ──
-#pragma unroll 1
-    for (int i = 0; i < C; ++i) {
-        const int ri = i * (i + 1) / 2;
-        double2 y = s_d[i][tid];
-#pragma unroll 1
-        for (int p = 0; p < i; ++p) {
-            const double2 l = s_A[ri + p][tid], v = s_v[p][tid];
-            y.x -= l.x * v.x - l.y * v.y;
-            y.y -= l.x * v.y + l.y * v.x;
-        }
-        const double inv = s_A[ri + i][tid].y;
-        s_v[i][tid] = make_double2(y.x * inv, y.y * inv);
-    }
-#pragma unroll 1
-    for (int i = C - 1; i >= 0; --i) {
-        double2 y = s_v[i][tid];
-#pragma unroll 1
-        for (int p = i + 1; p < C; ++p) {                        // y -= conj L[p][i] v[p]
-            const double2 l = s_A[p * (p + 1) / 2 + i][tid], v = s_v[p][tid];
-            y.x -= l.x * v.x + l.y * v.y;
-            y.y -= l.x * v.y - l.y * v.x;
-        }
-        const double inv = s_A[i * (i + 1) / 2 + i][tid].y;
-        s_v[i][tid] = make_double2(y.x * inv, y.y * inv);
-    }
-    double den = 0.0;                                            // d^H v = d^H (R + lambda I)^-1 d: real and positive
-#pragma unroll 1
-    for (int c = 0; c < C; ++c) den += s_d[c][tid].x * s_v[c][tid].x + s_d[c][tid].y * s_v[c][tid].y;
-    const double scale = 1.0 / den;
-#pragma unroll 1
-    for (int c = 0; c < C; ++c) wout[(long)c * PHAT_SPEC + k] = make_float2((float)(s_v[c][tid].x * scale), (float)(s_v[c][tid].y * scale));
+    MV_WEIGHTS_BODY(mv_uses_noise(ma, s0) ? ma.kn : (len + MV_B - 1) / MV_B + 1)
+}
+
+__global__ __launch_bounds__(MV_WT) void mvdr_quiet_weights_k(float2* __restrict__ ws, const double* __restrict__ tau, double loading,
+                                                              TdArgs ta, MvArgs ma) {
+    MV_WEIGHTS_BODY(mv_quiet_frames(ma, e) > 0 ? mv_quiet_frames(ma, e) : (len + MV_B - 1) / MV_B + 1)
 }
 
 template <bool RING>
@@ -510,6 +568,134 @@ bool mv_sizes_ok(int R, int channels, int max_frames, int hop) {
 #define MV_MAX_NOISE 256                          // localize.MVDR: noise_blocks
 #define MV_MAX_GUARD 64                           //                noise_guard
 
+// ───────────────────────── DESIGN 5w: the noise frames where the event's class is silent ─────────────────────────
+#define MV_MAX_SEARCH 1024                        // localize.MVDR: noise_search
+#define MV_MAX_CLASSES 32                         // the bits of a mask word
+
+struct MqArgs {
+    const int* ev_cls;                           // [E]
+    long E;                                      // rows of the whole table
+    int n_classes, search, min_frames, any;      // S candidates, at least M of them, and whether every class excludes (else the event's own)
+    const long* mask_off;                        // [R] recording r's first word of mask
+    uint32_t* mask;                              // [sum L_r] the class bits of every output frame, L_r = n_r / (tf hop) + 1
+    int* sel;                                    // [E][kn] the candidates of every event in summation order, -1 behind them
+};
+
+// the activity of the WHOLE table, located or not: bit cls of mask[rec][t] for onset <= t < offset, both clamped to [0, L_rec].  A
+// wave per row, a lane per frame; the OR does not depend on the order, so nothing depends on the launch shape.
+__global__ __launch_bounds__(256) void mvdr_activity_k(TdArgs ta, MqArgs qa) {
+    const int lane = threadIdx.x & 63;
+    const long H = (long)ta.tf * ta.hop;
+    for (long e = (long)blockIdx.x * 4 + (threadIdx.x >> 6); e < qa.E; e += (long)gridDim.x * 4) {
+        const int rec = ta.ev_rec ? ta.ev_rec[e] : 0, cls = qa.ev_cls[e];
+        const long on = ta.ev_onset[e];
+        if (rec < 0 || rec >= ta.R || cls < 0 || cls >= qa.n_classes || on < 0) continue;
+        const long L = ta.n_samples[rec] / H + 1;
+        long off = ta.ev_offset[e];
+        if (off > L) off = L;
+        uint32_t* row = qa.mask + qa.mask_off[rec];
+        for (long t = on + lane; t < off; t += 64) atomicOr(row + t, 1u << cls);
+    }
+}
+
+// One wave per event walks the candidates q = 0 .. S-1, 64 at a time: candidate q is the 2048 samples from s0 - (G + 2 + q) B,
+// exists when that is >= 0, and is eligible when no output frame that [s0 - (2 G + 2 + q) B, s0 - q B) touches has a bit of
+// `excl` set.  The ballot's prefix count ranks the eligible ones, nearest first; the first kn are kept and written in summation
+// order, which is ascending time: descending q.
+__global__ __launch_bounds__(64) void mvdr_select_k(TdArgs ta, MvArgs ma, MqArgs qa) {
+    __shared__ int s_q[MV_MAX_NOISE];
+    const int lane = threadIdx.x;
+    const long H = (long)ta.tf * ta.hop;
+    for (long e = blockIdx.x; e < qa.E; e += gridDim.x) {
+        int rec, len;
+        long s0;
+        bm_event_span(ta, ma.ev_dir, ma.ev_loc, ma.D, e, rec, s0, len);
+        const int cls = qa.ev_cls[e];
+        int count = 0;
+        if (len != 0 && cls >= 0 && cls < qa.n_classes) {        // (block-uniform)
+            const uint32_t excl = qa.any ? 0xffffffffu : 1u << cls;
+            const uint32_t* row = qa.mask + qa.mask_off[rec];
+            const long L = ta.n_samples[rec] / H + 1;
+            for (int q0 = 0; q0 < qa.search && count < ma.kn && s0 >= (long)(ma.guard + 2 + q0) * MV_B; q0 += 64) {
+                const int q = q0 + lane;
+                bool ok = q < qa.search && s0 >= (long)(ma.guard + 2 + q) * MV_B;
+                if (ok) {
+                    long lo = s0 - (long)(2 * ma.guard + 2 + q) * MV_B;
+                    if (lo < 0) lo = 0;
+                    long t1 = (s0 - (long)q * MV_B + H - 1) / H;   // (s0 - q B >= 2 B: at least one frame is tested)
+                    if (t1 > L) t1 = L;
+                    for (long t = lo / H; t < t1 && ok; ++t) ok = (row[t] & excl) == 0;
+                }
+                const unsigned long long m = __ballot(ok);
+                const int rank = count + __popcll(m & ((1ull << lane) - 1ull));
+                if (ok && rank < ma.kn) s_q[rank] = q;
+                count += __popcll(m);
+            }
+            if (count > ma.kn) count = ma.kn;
+            if (count < qa.min_frames) count = 0;
+        }
+        __syncthreads();
+        for (int i = lane; i < ma.kn; i += 64) qa.sel[e * ma.kn + i] = i < count ? s_q[count - 1 - i] : -1;
+        if (lane == 0) ma.noise_frames[e] = count;
+        __syncthreads();                                         // s_q is free for the next event
+    }
+}
+
+// the words behind the recording table: mask_off [R], then the mask of `frames` words, each rounded to 16 bytes
+size_t mq_mask_bytes(int R, long frames) { return (((size_t)R * sizeof(long) + 15) & ~(size_t)15) + (((size_t)frames * 4 + 15) & ~(size_t)15); }
+bool mq_sizes_ok(int R, long frames, int kn) { return R >= 1 && frames >= R && frames <= (1L << 40) && kn >= 1 && kn <= MV_MAX_NOISE; }
+
+// the settings of a quiet call and its outputs beside frames_out (MvNoise)
+struct MvQuiet { const int* cls; int n_classes, search, min_frames, any; int* sel_out; };
+
+int mq_check(const char* who, const EvTable& ev, int kn, int guard, const int* frames_out, const MvQuiet& qz) {
+    SED_REQUIRE(kn >= 1 && kn <= MV_MAX_NOISE, "%s: noise_blocks must be in [1, %d], got %d", who, MV_MAX_NOISE, kn);
+    SED_REQUIRE(guard >= 0 && guard <= MV_MAX_GUARD, "%s: noise_guard must be in [0, %d], got %d", who, MV_MAX_GUARD, guard);
+    SED_REQUIRE(qz.search >= kn && qz.search <= MV_MAX_SEARCH, "%s: noise_search must be in [noise_blocks = %d, %d], got %d", who, kn,
+                MV_MAX_SEARCH, qz.search);
+    SED_REQUIRE(qz.min_frames >= 1 && qz.min_frames <= kn, "%s: noise_min must be in [1, noise_blocks = %d], got %d", who, kn, qz.min_frames);
+    SED_REQUIRE(qz.n_classes >= 1 && qz.n_classes <= MV_MAX_CLASSES, "%s: n_classes must be in [1, %d], got %d", who, MV_MAX_CLASSES,
+                qz.n_classes);
+    SED_REQUIRE(qz.any == 0 || qz.any == 1, "%s: exclude_any must be 0 or 1, got %d", who, qz.any);
+    SED_REQUIRE(ev.E == 0 || (qz.cls && frames_out && qz.sel_out), "%s: null pointer (ev_cls, noise_frames_out or noise_sel_out)", who);
+    return 0;
+}
+
+// the activity of the whole table into the mask behind the recording table (which is uploaded), then every event's frames:
+// frames_out [E] and sel_out [E][kn] are written for all E rows.  The workspace holds src.tab + mq_mask_bytes (checked by the caller).
+int mq_select(const char* who, const RecSource& src, const EvTable& ev, int kn, int guard, int* frames_out, const MvQuiet& qz,
+              void* workspace, hipStream_t s) {
+    const long H = (long)ev.tf * ev.hop;
+    const long* n = src.h.data() + (size_t)src.R * src.C;
+    std::vector<long> off((size_t)src.R);
+    long frames = 0;
+    for (int r = 0; r < src.R; ++r) { off[r] = frames; frames += n[r] / H + 1; }
+    char* base = (char*)workspace + src.tab;
+    long* d_off = (long*)base;
+    uint32_t* d_mask = (uint32_t*)(base + (((size_t)src.R * sizeof(long) + 15) & ~(size_t)15));
+    hipError_t err = hipMemcpyAsync(d_off, off.data(), off.size() * sizeof(long), hipMemcpyHostToDevice, s);
+    if (err == hipSuccess) err = hipMemsetAsync(d_mask, 0, (size_t)frames * 4, s);
+    if (err != hipSuccess) { sed_set_error("%s: upload of the mask offsets: %s", who, hipGetErrorString(err)); return (int)err; }
+    const TdArgs ta = td_args(src, ev, workspace);
+    MvArgs ma{};
+    ma.ev_dir = ev.dir; ma.ev_loc = ev.loc; ma.D = ev.D; ma.kn = kn; ma.guard = guard; ma.noise_frames = frames_out;
+    const MqArgs qa{qz.cls, ev.E, qz.n_classes, qz.search, qz.min_frames, qz.any, d_off, d_mask, qz.sel_out};
+    const long cap = 1L << 20;
+    mvdr_activity_k<<<(unsigned)((ev.E + 3) / 4 < cap ? (ev.E + 3) / 4 : cap), 256, 0, s>>>(ta, qa);
+    SED_LAUNCH_CHECK("mvdr (activity)");
+    mvdr_select_k<<<(unsigned)(ev.E < cap ? ev.E : cap), 64, 0, s>>>(ta, ma, qa);
+    SED_LAUNCH_CHECK("mvdr (selection)");
+    return 0;
+}
+
+// the mask's words of a checked source
+long mq_frames(const RecSource& src, const EvTable& ev) {
+    const long H = (long)ev.tf * ev.hop;
+    long frames = 0;
+    for (int r = 0; r < src.R; ++r) frames += src.h[(size_t)src.R * src.C + r] / H + 1;
+    return frames;
+}
+
 // the steering delays [D][C], the diagonal loading and the table blob
 struct MvTables { const double* tau; double loading; const void* tables; size_t tables_bytes; };
 // kn noise frames that end guard blocks before the onset, and which events used them; entry: one of the noise entries,
@@ -518,12 +704,15 @@ struct MvNoise { int kn, guard; int* frames_out; bool entry; };
 
 // what all entries do once the events and the recordings are checked.  kn = 0 (sed_event_mvdr, sed_event_mvdr_ring, or a noise
 // entry asked for no noise frames): three launches per slice, and the noise entries' frames_out is zeroed
+// qz (sed_event_mvdr_quiet; linear only): the mask lies between the table and the partials, the selection runs once over
+// the whole table, and a slice is own covariance, quiet covariance, weights, apply with the quiet kernels
 template <bool RING>
 int mv_run(const char* who, const RecSource& src, const EvTable& ev, const MvTables& mt, const MvNoise& nz, const BeamOut& out,
-           void* workspace, size_t workspace_bytes, void* stream) {
+           void* workspace, size_t workspace_bytes, void* stream, const MvQuiet* qz = nullptr) {
     const int kn = nz.kn;
     const long E = ev.E;
-    const size_t tab = src.tab;
+    if (qz) SED_TRY(mq_check(who, ev, kn, nz.guard, nz.frames_out, *qz));
+    const size_t tab = src.tab + (qz ? mq_mask_bytes(src.R, mq_frames(src, ev)) : 0);
     SED_REQUIRE(kn >= 0 && kn <= MV_MAX_NOISE, "%s: noise_blocks must be in [0, %d], got %d", who, MV_MAX_NOISE, kn);
     SED_REQUIRE(nz.guard >= 0 && nz.guard <= MV_MAX_GUARD, "%s: noise_guard must be in [0, %d], got %d", who, MV_MAX_GUARD, nz.guard);
     SED_REQUIRE(!nz.entry || E == 0 || nz.frames_out, "%s: null pointer (noise_frames_out)", who);
@@ -559,12 +748,14 @@ int mv_run(const char* who, const RecSource& src, const EvTable& ev, const MvTab
 
     hipStream_t s = as_stream(stream);
     SED_TRY(beam_upload(who, src, workspace, workspace_bytes, s));
-    const auto cov_k = RING ? mvdr_ring_cov_k : mvdr_cov_k;
+    if (qz) SED_TRY(mq_select(who, src, ev, kn, nz.guard, nz.frames_out, *qz, workspace, s));
+    const auto cov_k = RING ? mvdr_ring_cov_k : qz ? mvdr_quiet_own_k : mvdr_cov_k;
     const auto apply_k = RING ? mvdr_ring_apply_k : mvdr_apply_k;
     hipError_t err = hipFuncSetAttribute((const void*)cov_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MV_LDS_MAX);
     if (err == hipSuccess) err = hipFuncSetAttribute((const void*)apply_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MV_LDS_MAX);
     const auto noise_k = RING ? mvdr_ring_noise_k : mvdr_noise_k;
     if (err == hipSuccess && kn > 0) err = hipFuncSetAttribute((const void*)noise_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MV_LDS_MAX);
+    if (err == hipSuccess && qz) err = hipFuncSetAttribute((const void*)mvdr_quiet_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MV_LDS_MAX);
     if (err != hipSuccess) { sed_set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(err)); return (int)err; }
     if (kn == 0 && nz.frames_out) {
         err = hipMemsetAsync(nz.frames_out, 0, (size_t)E * sizeof(int), s);
@@ -580,11 +771,14 @@ int mv_run(const char* who, const RecSource& src, const EvTable& ev, const MvTab
         ta.n_ev = (int)(E - e0 < slice ? E - e0 : slice);
         cov_k<<<dim3(chunks, (unsigned)ta.n_ev), MV_THREADS, lds_cov, s>>>(src.x, tables, part, ta, ma);
         SED_LAUNCH_CHECK("mvdr (covariance)");
-        if (kn > 0) {                                            // the host does not know which events use it: both launches run
+        if (qz) {
+            mvdr_quiet_k<<<dim3((unsigned)mv_noise_chunks(kn), (unsigned)ta.n_ev), MV_THREADS, lds_cov, s>>>(src.x, tables, part, ta, ma, qz->sel_out);
+            SED_LAUNCH_CHECK("mvdr (quiet covariance)");
+        } else if (kn > 0) {                                     // the host does not know which events use it: both launches run
             noise_k<<<dim3((unsigned)mv_noise_chunks(kn), (unsigned)ta.n_ev), MV_THREADS, lds_cov, s>>>(src.x, tables, part, ta, ma);
             SED_LAUNCH_CHECK("mvdr (noise covariance)");
         }
-        mvdr_weights_k<<<dim3((LM_N + MV_WT) / MV_WT, (unsigned)ta.n_ev), MV_WT, 0, s>>>(part, mt.tau, mt.loading, ta, ma);
+        (qz ? mvdr_quiet_weights_k : mvdr_weights_k)<<<dim3((LM_N + MV_WT) / MV_WT, (unsigned)ta.n_ev), MV_WT, 0, s>>>(part, mt.tau, mt.loading, ta, ma);
         SED_LAUNCH_CHECK("mvdr (weights)");
         apply_k<<<dim3(runs, (unsigned)ta.n_ev), MV_THREADS, lds_apply, s>>>(src.x, tables, part, out.audio, ta, ma);
         SED_LAUNCH_CHECK("mvdr (apply)");
@@ -595,9 +789,23 @@ int mv_run(const char* who, const RecSource& src, const EvTable& ev, const MvTab
 // an entry: the events and the recordings checked, then the launches
 template <bool RING>
 int mv_entry(const char* who, RecSource src, const EvTable& ev, const MvTables& mt, const MvNoise& nz, const BeamOut& out, void* workspace,
-             size_t workspace_bytes, void* stream) {
+             size_t workspace_bytes, void* stream, const MvQuiet* qz = nullptr) {
     SED_TRY(beam_source<RING>(who, src, ev));
-    return mv_run<RING>(who, src, ev, mt, nz, out, workspace, workspace_bytes, stream);
+    return mv_run<RING>(who, src, ev, mt, nz, out, workspace, workspace_bytes, stream, qz);
+}
+
+// sed_event_quiet_frames: the activity and the selection alone; no sample is read
+int mq_frames_entry(const char* who, RecSource src, const EvTable& ev, int kn, int guard, int* frames_out, const MvQuiet& qz, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+    SED_TRY((beam_source<false, false>(who, src, ev)));
+    SED_TRY(mq_check(who, ev, kn, guard, frames_out, qz));
+    if (ev.E == 0) return 0;
+    const size_t need = src.tab + mq_mask_bytes(src.R, mq_frames(src, ev));
+    SED_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0, "%s: the workspace must be a 16-byte aligned device buffer", who);
+    SED_REQUIRE(workspace_bytes >= need, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
+    hipStream_t s = as_stream(stream);
+    SED_TRY(rec_upload(who, src, workspace, s));
+    return mq_select(who, src, ev, kn, guard, frames_out, qz, workspace, s);
 }
 
 }  // namespace
@@ -668,4 +876,40 @@ extern "C" int sed_event_mvdr_noise_ring(const float* ring, long ring_len, long 
                           {ev_rec, ev_onset, ev_offset, ev_peak_frame, ev_dir, ev_loc_frames, E, time_factor, hop, max_frames, D},
                           {tau, loading, tables, tables_bytes}, {noise_blocks, noise_guard, noise_frames_out, true},
                           {audio_len, audio_start, audio, audio_total}, workspace, workspace_bytes, stream);
+}
+
+// ── DESIGN 5w: the noise covariance from the frames where the event's class — or, with exclude_any, every class — is silent ──
+extern "C" size_t sed_event_quiet_frames_workspace_bytes(int R, int channels, long mask_frames, int noise_blocks) {
+    if (R < 1 || channels < 2 || channels > TD_MAX_CH || !mq_sizes_ok(R, mask_frames, noise_blocks)) return 0;
+    return rec_table_bytes(R, channels) + mq_mask_bytes(R, mask_frames);
+}
+
+extern "C" size_t sed_event_mvdr_quiet_workspace_bytes(int R, int channels, int max_frames, int hop, int noise_blocks, long mask_frames) {
+    if (!mv_sizes_ok(R, channels, max_frames, hop) || !mq_sizes_ok(R, mask_frames, noise_blocks)) return 0;
+    return rec_table_bytes(R, channels) + mq_mask_bytes(R, mask_frames) + mv_event_bytes(channels, mv_slots(max_frames, hop, noise_blocks));
+}
+
+extern "C" int sed_event_quiet_frames(long pcm_len, const long* clips_host, int R, int channels, const int* ev_rec, const int* ev_cls,
+                                      const int* ev_onset, const int* ev_offset, const int* ev_peak_frame, const int* ev_dir,
+                                      const int* ev_loc_frames, long E, int time_factor, int hop, int max_frames, int D, int n_classes,
+                                      int noise_blocks, int noise_guard, int noise_search, int noise_min, int exclude_any,
+                                      int* noise_frames_out, int* noise_sel_out, void* workspace, size_t workspace_bytes, void* stream) {
+    return mq_frames_entry("quiet_frames", {nullptr, false, 0, pcm_len, R, channels, clips_host},
+                           {ev_rec, ev_onset, ev_offset, ev_peak_frame, ev_dir, ev_loc_frames, E, time_factor, hop, max_frames, D},
+                           noise_blocks, noise_guard, noise_frames_out, {ev_cls, n_classes, noise_search, noise_min, exclude_any, noise_sel_out},
+                           workspace, workspace_bytes, stream);
+}
+
+extern "C" int sed_event_mvdr_quiet(const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const int* ev_rec,
+                                    const int* ev_cls, const int* ev_onset, const int* ev_offset, const int* ev_peak_frame,
+                                    const int* ev_dir, const int* ev_loc_frames, long E, int time_factor, int hop, int max_frames,
+                                    const double* tau, int D, double loading, int noise_blocks, int noise_guard, int n_classes,
+                                    int noise_search, int noise_min, int exclude_any, const void* tables, size_t tables_bytes,
+                                    const int* audio_len, const long* audio_start, float* audio, long audio_total, int* noise_frames_out,
+                                    int* noise_sel_out, void* workspace, size_t workspace_bytes, void* stream) {
+    const MvQuiet qz{ev_cls, n_classes, noise_search, noise_min, exclude_any, noise_sel_out};
+    return mv_entry<false>("mvdr_quiet", {pcm, false, 0, pcm_len, R, channels, clips_host},
+                           {ev_rec, ev_onset, ev_offset, ev_peak_frame, ev_dir, ev_loc_frames, E, time_factor, hop, max_frames, D},
+                           {tau, loading, tables, tables_bytes}, {noise_blocks, noise_guard, noise_frames_out, true},
+                           {audio_len, audio_start, audio, audio_total}, workspace, workspace_bytes, stream, &qz);
 }

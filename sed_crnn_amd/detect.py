@@ -31,6 +31,7 @@ _TDOA_KEYS = ("lag", "strength", "loc_frames")          # added to the events of
 _DOA_KEYS = ("dir", "doa_power")                        # ... and, with localize=DOA(...), a direction per event
 _BEAM_KEYS = ("audio_start", "audio_len")               # ... and, with extract=DelaySum(...), its place in result.audio
 _NOISE_KEYS = ("noise_frames",)                         # ... and, with extract=MVDR(noise_blocks >= 1), the pre-onset frames its weights used (5u)
+_QUIET_KEYS = ("noise_sel",)                            # ... and, with noise_select="quiet", which candidates they are (5w; offline only)
 
 
 def _doa_angles(events, grid, k):
@@ -324,7 +325,7 @@ class BatchDetectionResult:
         i = int(i) % R
         o0, o1 = self.out_offsets[i], self.out_offsets[i + 1]
         e0, e1 = self.event_offsets[i], self.event_offsets[i + 1]
-        keys = _EVENT_KEYS + tuple(k for k in _TDOA_KEYS + _DOA_KEYS + _BEAM_KEYS + _NOISE_KEYS if k in self.events)
+        keys = _EVENT_KEYS + tuple(k for k in _TDOA_KEYS + _DOA_KEYS + _BEAM_KEYS + _NOISE_KEYS + _QUIET_KEYS if k in self.events)
         return DetectionResult(self.probs[o0:o1], {k: self.events[k][e0:e1] for k in keys}, self.frame_seconds, self.plans[i], self.sr,
                                self.grid, self.audio)
 
@@ -378,7 +379,10 @@ class EventDetector:
     ``extract=sed.MVDR(loading)`` instead: the same events, samples and results through an adaptive beam that
     suppresses what else the event's frames contain (``events.event_mvdr``; live feeds: ``events.event_mvdr_ring``).  With
     ``sed.MVDR(noise_blocks=Kn)``, ``Kn >= 1``, the weights come from the Kn frames before the onset where the
-    recording has them, and the events and ``result.noise_frames`` also hold ``noise_frames``."""
+    recording has them, and the events and ``result.noise_frames`` also hold ``noise_frames``.  With
+    ``sed.MVDR(noise_blocks=Kn, noise_select="quiet")`` the Kn frames are the nearest before the onset in which the
+    detector's own events of that class are silent — the class count is the model's — and the events also hold ``noise_sel``
+    [E, Kn]; offline only: ``stream(..., emit_audio=True)`` of such a detector raises NotImplementedError."""
 
     def __init__(self, model, seq_len=SEQ_LEN_IN, hop=None, combine="mean", trim=0, threshold=0.5, low=None, median=1,
                  min_gap=0, min_len=1, mean=None, std=None, sr=feature.SR, hop_length=feature.HOP, max_batch=1024, spatial=None,
@@ -626,11 +630,12 @@ class EventDetector:
             if self.extract_settings is not None:            # the audio of the located events, from the same PCM
                 from .localize import MVDR
                 entry = event_mvdr if isinstance(self.extract_settings, MVDR) else event_beamform
+                quiet = dict(n_classes=self.model.dense[-1]) if getattr(self.extract_settings, "quiet", False) else {}
                 beam = entry(pcm, clips, self.audio_channels, {**result.events, **loc}, self.model.time_factor, t,
-                             self.extract_settings, sr=self.sr, hop=self.hop_length)
+                             self.extract_settings, sr=self.sr, hop=self.hop_length, **quiet)
                 result.audio = beam.pop("audio")
                 loc.update(beam)
-        result.events = {**{k: v for k, v in result.events.items() if k not in _TDOA_KEYS + _DOA_KEYS + _BEAM_KEYS + _NOISE_KEYS}, **loc}
+        result.events = {**{k: v for k, v in result.events.items() if k not in _TDOA_KEYS + _DOA_KEYS + _BEAM_KEYS + _NOISE_KEYS + _QUIET_KEYS}, **loc}
         result.sr = self.sr
         return result
 
@@ -873,6 +878,8 @@ class EventDetector:
             out.update(audio_start=torch.empty(0, dtype=torch.int64, device=dev), audio_len=torch.empty(0, dtype=torch.int32, device=dev))
         if getattr(self.extract_settings, "noise_blocks", 0):
             out.update(noise_frames=torch.empty(0, dtype=torch.int32, device=dev))
+        if getattr(self.extract_settings, "quiet", False):
+            out.update(noise_sel=torch.empty(0, self.extract_settings.noise_blocks, dtype=torch.int32, device=dev))
         return out
 
     def _detect_packed(self, mel, bp):

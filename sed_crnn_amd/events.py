@@ -20,7 +20,8 @@ _ENTRY = {("tdoa", False): "sed_event_tdoa", ("tdoa", True): "sed_event_tdoa_rin
           ("spans", False): "sed_event_beam_spans", ("spans", True): "sed_event_beam_spans_ring",
           ("delay_sum", False): "sed_event_beamform", ("delay_sum", True): "sed_event_beamform_ring",
           ("mvdr", False): "sed_event_mvdr", ("mvdr", True): "sed_event_mvdr_ring",
-          ("mvdr_noise", False): "sed_event_mvdr_noise", ("mvdr_noise", True): "sed_event_mvdr_noise_ring"}
+          ("mvdr_noise", False): "sed_event_mvdr_noise", ("mvdr_noise", True): "sed_event_mvdr_noise_ring",
+          ("mvdr_quiet", False): "sed_event_mvdr_quiet"}
 _LOCATED = ("onset", "offset", "peak_frame", "dir", "loc_frames")
 
 
@@ -306,6 +307,8 @@ def _mvdr_empty(dev, mvdr):
     out = _beam_empty(dev)
     if mvdr.noise_blocks:
         out["noise_frames"] = torch.empty(0, dtype=torch.int32, device=dev)
+    if mvdr.quiet:
+        out["noise_sel"] = torch.empty(0, mvdr.noise_blocks, dtype=torch.int32, device=dev)
     return out
 
 
@@ -318,10 +321,11 @@ def _mvdr_tables(device_index):
     return blob[:_LM_OFF_ENT].clone()
 
 
-def _extract(src, kind, col, E, tf, hop, max_frames, D, settings, ws_bytes):
+def _extract(src, kind, col, E, tf, hop, max_frames, D, settings, ws_bytes, Kn=0):
     """the two calls behind the four beam functions: the spans, ONE blocking read of the total (8 bytes) to size ``audio``, the
     beam ``kind``.  ``settings``: what the beam's C entry takes between ``max_frames`` and the spans; ``mvdr_noise``
-    adds ``noise_frames`` int32 [E] to the dict"""
+    adds ``noise_frames`` int32 [E] to the dict, ``mvdr_quiet`` (``Kn``: its noise_blocks) that and ``noise_sel`` int32
+    [E, Kn], and its C entry takes the ``cls`` column behind ``rec``"""
     dev = src.x.device
     out = {"audio_start": torch.empty(E, dtype=torch.int64, device=dev), "audio_len": torch.empty(E, dtype=torch.int32, device=dev)}
     total = torch.empty(1, dtype=torch.int64, device=dev)
@@ -333,9 +337,13 @@ def _extract(src, kind, col, E, tf, hop, max_frames, D, settings, ws_bytes):
     n_total = int(total.item())                                       # the one blocking read
     out["audio"] = torch.empty(n_total, device=dev)
     noise = []
-    if kind == "mvdr_noise":
+    if kind in ("mvdr_noise", "mvdr_quiet"):
         out["noise_frames"] = torch.zeros(E, dtype=torch.int32, device=dev)      # (a call that extracts nothing launches nothing)
         noise = [ptr(out["noise_frames"])]
+    if kind == "mvdr_quiet":
+        out["noise_sel"] = torch.full((E, Kn), -1, dtype=torch.int32, device=dev)
+        noise.append(ptr(out["noise_sel"]))
+        cols = cols[:1] + [ptr(col["cls"])] + cols[1:]
     check(getattr(lib(), name)(*src.head, *cols, E, tf, hop, max_frames, *settings, ptr(out["audio_len"]), ptr(out["audio_start"]),
                                ptr(out["audio"]), n_total, *noise, ptr(ws), ws.numel(), stream_ptr()), name)
     return out
@@ -367,22 +375,47 @@ def _beamform(who, src, events, tf, hop, doa, beam, sr):
                     [ptr(M), M.shape[0], beam.oversample, beam.half_width, ptr(_BEAM_TAPS[tkey])], _table_bytes(src))
 
 
-def _mvdr(who, src, events, tf, hop, doa, mvdr, sr, max_workspace_bytes):
-    """``event_mvdr`` / ``event_mvdr_ring`` on their source; with ``mvdr.noise_blocks >= 1`` the entry's noise form"""
+def _quiet_settings(who, mvdr, n_classes):
+    """the quiet settings as the C entries take them behind noise_guard -> [n_classes, S, M, exclude_any]"""
+    from .localize import MVDR_MAX_CLASSES
+    if n_classes is None:
+        raise ValueError(f"{who} with sed.MVDR(noise_select='quiet') needs n_classes, the number of classes the events' cls column counts in")
+    if isinstance(n_classes, bool) or int(n_classes) != n_classes or not 1 <= int(n_classes) <= MVDR_MAX_CLASSES:
+        raise ValueError(f"{who}: n_classes must be an integer in [1, {MVDR_MAX_CLASSES}] (an activity word has {MVDR_MAX_CLASSES} bits), "
+                         f"got {n_classes!r}")
+    return [int(n_classes), mvdr.noise_search, mvdr.noise_min, int(mvdr.noise_exclude == "any")]
+
+
+def _mask_frames(src, tf, hop):
+    """the words of the activity mask: ``n_r // (tf hop) + 1`` output frames per recording"""
+    return int((src.table[::src.nc, 1] // (tf * hop) + 1).sum())
+
+
+def _mvdr(who, src, events, tf, hop, doa, mvdr, sr, max_workspace_bytes, n_classes=None):
+    """``event_mvdr`` / ``event_mvdr_ring`` on their source; with ``mvdr.noise_blocks >= 1`` the entry's noise form,
+    with ``mvdr.quiet`` its quiet form"""
     from .localize import MVDR
     _doa_plan(doa, src.nc, sr)
     if not isinstance(mvdr, MVDR):
         raise TypeError(f"{who} takes the beam settings as a sed.MVDR(...) object, got {type(mvdr).__name__}")
     R, nc, dev, max_frames = src.R, src.nc, src.x.device, doa.max_frames
-    col, E = _cols(src, events, _LOCATED)
+    quiet = _quiet_settings(who, mvdr, n_classes) if mvdr.quiet else []
+    col, E = _cols(src, events, _LOCATED + (("cls",) if mvdr.quiet else ()))
     if E == 0:
         return _mvdr_empty(dev, mvdr)
-    kind, noise = ("mvdr_noise", [mvdr.noise_blocks, mvdr.noise_guard]) if mvdr.noise_blocks else ("mvdr", [])
+    Kn = mvdr.noise_blocks
+    kind = "mvdr" if not Kn else "mvdr_quiet" if mvdr.quiet else "mvdr_noise"
+    noise = [Kn, mvdr.noise_guard] + quiet if Kn else []                         # what the entry takes behind loading
     name = _ENTRY[kind, src.ring] + "_workspace_bytes"
-    need_one = getattr(lib(), name)(R, nc, max_frames, hop, *noise[:1])          # the recording table and one event
-    if need_one == 0:
+    if mvdr.quiet:                                                               # the mask lies behind the table, once per call
+        frames = _mask_frames(src, tf, hop)
+        need_tab = lib().sed_event_quiet_frames_workspace_bytes(R, nc, frames, Kn)
+        need_one = getattr(lib(), name)(R, nc, max_frames, hop, Kn, frames)      # the table, the mask and one event
+    else:
+        need_tab = _table_bytes(src)
+        need_one = getattr(lib(), name)(R, nc, max_frames, hop, *noise[:1])      # the recording table and one event
+    if need_one == 0 or need_tab == 0:
         raise ValueError(f"{name} refuses R={R}, channels={nc}, max_frames={max_frames}, hop={hop}")
-    need_tab = _table_bytes(src)
     key = (dev.index or 0, float(sr))
     if key not in doa._steering_device:
         doa._steering_device[key] = torch.from_numpy(doa.steering(sr)).to(dev)
@@ -390,7 +423,45 @@ def _mvdr(who, src, events, tf, hop, doa, mvdr, sr, max_workspace_bytes):
     tables = _mvdr_tables(dev.index or 0)
     ws_bytes = min(need_tab + E * (need_one - need_tab), max(need_one, int(max_workspace_bytes)))
     return _extract(src, kind, col, E, tf, hop, max_frames, tau.shape[0],
-                    [ptr(tau), tau.shape[0], mvdr.loading, *noise, ptr(tables), tables.numel() * 4], ws_bytes)
+                    [ptr(tau), tau.shape[0], mvdr.loading, *noise, ptr(tables), tables.numel() * 4], ws_bytes, Kn)
+
+
+def event_quiet_frames(clips, channels, events, time_factor, doa, mvdr, n_classes, hop=HOP):
+    """Which pre-onset frames ``event_mvdr`` with ``mvdr = sed.MVDR(..., noise_select="quiet")`` makes every event's noise
+    covariance from (``sed_event_quiet_frames``): the activity and the selection alone, no sample is read.  ``clips`` /
+    ``channels`` as ``event_mvdr`` takes them (the lengths of the recordings are all that is used); ``events``: the located table
+    with ``cls`` — every row marks activity, located or not; ``n_classes`` in 1..32: what ``cls`` counts in.  Returns device tensors
+    ``{"noise_frames": int32 [E], "noise_sel": int32 [E, Kn]}``: the number of frames used (0: the event keeps its own frames)
+    and their candidates q — frame q is the 2048 samples from ``s0 - (G + 2 + q) 1024`` — in summation order, -1 behind them.
+    Integer throughout and a function of the table and the settings alone; the host reads nothing back."""
+    from .localize import MVDR
+    nc, tf, hop = _beam_sizes("event_quiet_frames", channels, time_factor, hop)
+    if not isinstance(mvdr, MVDR) or not mvdr.quiet:
+        raise TypeError("event_quiet_frames takes the beam settings as a sed.MVDR(..., noise_select='quiet') object")
+    _doa_plan(doa, nc, SR)
+    quiet = _quiet_settings("event_quiet_frames", mvdr, n_classes)
+    dev = events["onset"].device if isinstance(events.get("onset"), torch.Tensor) else None
+    if dev is None or dev.type != "cuda":
+        raise RuntimeError("sed_crnn_amd.feature.event_quiet_frames needs the event columns as CUDA(HIP) tensors; there is no CPU fallback")
+    table = np.ascontiguousarray(np.asarray(clips, dtype=np.int64).reshape(-1, 2))
+    table = _clip_table(clips, nc, int((table[:, 0] + table[:, 1]).max()) if table.size else 0, at_least_one=True)
+    R = table.shape[0] // nc
+    col, E = _event_cols(events, R, "rec", _LOCATED + ("cls",), dev)
+    Kn = mvdr.noise_blocks
+    out = {"noise_frames": torch.zeros(E, dtype=torch.int32, device=dev), "noise_sel": torch.full((E, Kn), -1, dtype=torch.int32, device=dev)}
+    if E == 0:
+        return out
+    frames = int((table[::nc, 1] // (tf * hop) + 1).sum())
+    need = lib().sed_event_quiet_frames_workspace_bytes(R, nc, frames, Kn)
+    if need == 0:
+        raise ValueError(f"sed_event_quiet_frames_workspace_bytes refuses R={R}, channels={nc}, {frames} output frames, noise_blocks={Kn}")
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    cols = _col_ptrs(col, _LOCATED)
+    check(lib().sed_event_quiet_frames(int((table[:, 0] + table[:, 1]).max()), C.c_void_p(table.ctypes.data), R, nc, cols[0], ptr(col["cls"]),
+                                       *cols[1:], E, tf, hop, doa.max_frames, doa.grid.unit_vectors.shape[0], quiet[0], Kn, mvdr.noise_guard,
+                                       *quiet[1:], ptr(out["noise_frames"]), ptr(out["noise_sel"]), ptr(ws), ws.numel(), stream_ptr()),
+          "sed_event_quiet_frames")
+    return out
 
 
 def event_beamform(pcm, clips, channels, events, time_factor, doa, beam, sr=SR, hop=HOP):
@@ -423,7 +494,7 @@ def event_beamform_ring(ring, cap, n, channels, events, time_factor, doa, beam, 
     return _beamform("event_beamform_ring", _ring_source(ring, int(cap), n, nc, need_16_byte=True), events, tf, hop, doa, beam, sr)
 
 
-def event_mvdr(pcm, clips, channels, events, time_factor, doa, mvdr, sr=SR, hop=HOP, max_workspace_bytes=128 << 20):
+def event_mvdr(pcm, clips, channels, events, time_factor, doa, mvdr, sr=SR, hop=HOP, max_workspace_bytes=128 << 20, n_classes=None):
     """The audio of every located event through an adaptive beam (``sed_event_beam_spans`` + ``sed_event_mvdr``):
     the arguments, the events that are extracted, their samples and the returned dict — ``audio`` float32 [total],
     ``audio_start`` int64 [E], ``audio_len`` int32 [E] — are ``event_beamform``'s; ``mvdr``: a ``sed.MVDR(loading)``.  On the
@@ -441,10 +512,19 @@ def event_mvdr(pcm, clips, channels, events, time_factor, doa, mvdr, sr=SR, hop=
     ``s0 >= (G + Kn + 1) 1024`` gets its weights from the covariance of the Kn frames before its onset, the samples
     ``[s0 - (G + Kn + 1) 1024, s0 - G 1024)`` of its recording, which do not hold the target: a steering error no longer makes
     the beam cancel it.  Every other event gets what ``Kn = 0`` gives, bit for bit.  The dict gains ``noise_frames`` int32 [E]:
-    Kn where the noise covariance was used, else 0.  An event's audio then depends on those samples and its own alone."""
+    Kn where the noise covariance was used, else 0.  An event's audio then depends on those samples and its own alone.
+
+    ``sed.MVDR(..., noise_blocks=Kn, noise_select="quiet")`` (``sed_event_mvdr_quiet``): the Kn frames are the nearest
+    of ``noise_search`` candidates before the onset in which no event of the table with the same class (``noise_exclude="any"``:
+    any class) is active; the events must also hold ``cls``, and ``n_classes`` in 1..32 — what ``cls`` counts in — is required.
+    Every row of the table marks activity, located or not, and the activity is made once from the whole table, whatever the
+    slicing.  The dict gains ``noise_frames`` int32 [E], the number of frames used (0: fewer than ``noise_min`` were found and
+    the event keeps its own frames, bit for bit what ``Kn = 0`` gives), and ``noise_sel`` int32 [E, Kn], their candidates q
+    in summation order, -1 behind them (``event_quiet_frames`` returns the two alone).  An event whose Kn nearest candidates
+    are all eligible gets the audio of ``noise_select="fixed"``, bit for bit."""
     _need_pcm("event_mvdr", pcm)
     nc, tf, hop = _beam_sizes("event_mvdr", channels, time_factor, hop)
-    return _mvdr("event_mvdr", _linear_source(pcm, clips, nc), events, tf, hop, doa, mvdr, sr, max_workspace_bytes)
+    return _mvdr("event_mvdr", _linear_source(pcm, clips, nc), events, tf, hop, doa, mvdr, sr, max_workspace_bytes, n_classes)
 
 
 def event_mvdr_ring(ring, cap, n, channels, events, time_factor, doa, mvdr, sr=SR, hop=HOP, max_workspace_bytes=128 << 20):
@@ -455,6 +535,8 @@ def event_mvdr_ring(ring, cap, n, channels, events, time_factor, doa, mvdr, sr=S
     samples ``[0, n)`` laid out linearly, wherever the ring wraps and whatever the slicing; a sample the ring no longer holds
     reads as 0.  Returns what ``event_mvdr`` returns, with the same single 8-byte read; ``E == 0`` returns empty tensors without
     a launch."""
+    if getattr(mvdr, "quiet", False):
+        raise NotImplementedError("event_mvdr_ring: sed.MVDR(noise_select='quiet') has no ring form yet; extract on the recording (event_mvdr)")
     _need_ring("event_mvdr_ring", ring)
     nc, tf, hop = _beam_sizes("event_mvdr_ring", channels, time_factor, hop)
     return _mvdr("event_mvdr_ring", _ring_source(ring, int(cap), n, nc), events, tf, hop, doa, mvdr, sr, max_workspace_bytes)

@@ -363,6 +363,8 @@ def beam_taps(oversample, half_width, beta):
 MVDR_BLOCK = 1024               # mvdr.hip: MV_B, the hop of an event's own transform grid
 MVDR_MAX_NOISE_BLOCKS = 256     # mvdr.hip: MV_MAX_NOISE
 MVDR_MAX_NOISE_GUARD = 64       # mvdr.hip: MV_MAX_GUARD
+MVDR_MAX_NOISE_SEARCH = 1024    # mvdr.hip: MV_MAX_SEARCH
+MVDR_MAX_CLASSES = 32           # mvdr.hip: MV_MAX_CLASSES, the bits of an activity word
 
 
 @dataclasses.dataclass(frozen=True)
@@ -379,10 +381,24 @@ class MVDR:
     but that of the Kn frames of 2048 samples before the onset, ``[s0 - (G + Kn + 1) 1024, s0 - G 1024)`` of the recording.  An
     event that starts earlier than ``(G + Kn + 1) 1024`` samples into its recording keeps its own covariance, wholly;
     ``noise_frames`` in the results says which events used which (Kn or 0).  ``Kn = 0``: the own frames, for every event.  On
-    live feeds the ring keeps ``stream_noise_frames`` more feature frames."""
+    live feeds the ring keeps ``stream_noise_frames`` more feature frames.
+
+    ``noise_select="quiet"`` (needs ``Kn >= 1``) picks the Kn frames by the detector's own class tracks instead of
+    taking one fixed stretch: candidate q = 0.. ``noise_search`` - 1 is the 2048 samples from ``s0 - (G + 2 + q) 1024``; it is
+    eligible when no event of the table with the event's class (``noise_exclude="same"``; ``"any"``: with any class) is active
+    in an output frame that the candidate, widened by G blocks on either side, touches; the Kn nearest eligible candidates make
+    the covariance, as long as there are at least ``noise_min`` of them — else the event keeps its own frames.  A repeated
+    source, an event longer than ``max_frames`` and an event near the start of its recording then still get a covariance
+    without the target in it.  ``noise_search = 0`` means ``min(1024, 4 Kn)`` and is stored resolved; ``noise_frames`` in the
+    results is the number of frames used and ``noise_sel`` [E, Kn] lists their q in summation order (-1 behind them).  An
+    event whose Kn nearest candidates are all eligible gets the audio of ``noise_select="fixed"``, bit for bit.  Offline only."""
     loading: float = 1e-2
     noise_blocks: int = 0
     noise_guard: int = 1
+    noise_select: str = "fixed"
+    noise_search: int = 0
+    noise_min: int = 1
+    noise_exclude: str = "same"
 
     def __post_init__(self):
         v = self.loading
@@ -394,6 +410,29 @@ class MVDR:
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= most:
                 raise ValueError(f"MVDR: {name} must be an integer in [0, {most}], got {v!r}")
             object.__setattr__(self, name, int(v))
+        for name, allowed in (("noise_select", ("fixed", "quiet")), ("noise_exclude", ("same", "any"))):
+            if getattr(self, name) not in allowed:
+                raise ValueError(f"MVDR: {name} must be one of {allowed}, got {getattr(self, name)!r}")
+        for name, least, most in (("noise_search", 0, MVDR_MAX_NOISE_SEARCH), ("noise_min", 1, MVDR_MAX_NOISE_BLOCKS)):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not least <= int(v) <= most:
+                raise ValueError(f"MVDR: {name} must be an integer in [{least}, {most}], got {v!r}")
+            object.__setattr__(self, name, int(v))
+        if self.quiet:
+            Kn = self.noise_blocks
+            if Kn < 1:
+                raise ValueError("MVDR: noise_select='quiet' selects among pre-onset frames and needs noise_blocks >= 1")
+            if self.noise_search == 0:
+                object.__setattr__(self, "noise_search", min(MVDR_MAX_NOISE_SEARCH, 4 * Kn))
+            if self.noise_search < Kn:
+                raise ValueError(f"MVDR: noise_search must be 0 or at least noise_blocks = {Kn}, got {self.noise_search}")
+            if self.noise_min > Kn:
+                raise ValueError(f"MVDR: noise_min must be at most noise_blocks = {Kn}, got {self.noise_min}")
+
+    @property
+    def quiet(self):
+        """whether the noise frames are picked by the class tracks (``noise_select="quiet"``)"""
+        return self.noise_select == "quiet"
 
     @property
     def noise_lead_blocks(self):

@@ -255,6 +255,11 @@ class StreamDetector:
                                       "sed.MVDR(...) streams with emit_audio=True (and history_frames=), which costs one more "
                                       "blocking read and one device allocation per step (DESIGN 5t); pass emit_audio=True, or make "
                                       "the stream from a detector without extract=")
+        if self.emit_audio and getattr(det.extract_settings, "quiet", False):
+            raise NotImplementedError("sed.MVDR(noise_select='quiet') is offline only so far; live feeds are a follow-up: with "
+                                      "noise_exclude='same' every earlier event of the class is final when an event is emitted, so "
+                                      "it needs only noise_search more blocks of ring; with 'any' it also needs the other classes' "
+                                      "open events.  Stream with noise_select='fixed', or extract offline (DESIGN 5w)")
         if self.emit_audio and det.extract_settings is None:
             raise ValueError("emit_audio=True needs a detector that extracts audio: EventDetector(..., localize=sed.DOA(...), "
                              "extract=sed.DelaySum(...) or sed.MVDR(...))")
