@@ -574,6 +574,45 @@ int sed_event_doa_ring(const float* ring, long ring_len, long cap, const long* n
                        float* lag_out, float* strength_out, int* frames_out, float* acc_out, const int* steer_lags, int D, int Q,
                        const float* trig, int* dir_out, float* power_out, float* srp_out, void* workspace, size_t workspace_bytes,
                        void* stream);
+/* sed_event_doa_track: sed_event_doa, and a direction per BLOCK of block_chunks = W chunks of 32 located frames, for
+ * a source that moves while it sounds.  Every argument it shares with sed_event_doa means what it means there, and lag_out,
+ * strength_out, frames_out, acc_out, dir_out, power_out and srp_out receive the bits that call writes.  An event located on nf
+ * frames has nch = ceil(nf / 32) chunks, T0 = ceil(nch / W) and nl = nf - 32 W (T0 - 1); T = T0 - 1 where T0 > 1 and nl < 16 W (the
+ * short tail joins the block before it), else T0; nf = 0 gives T = 0.  Block b covers the chunks [b W, (b + 1) W), the last block
+ * up to nch, and its map m_b [D] is srp of sed_event_doa with S summed over the block's chunks alone (the first chunk starts the
+ * sum, the others are added in ascending order: a block of all the event's chunks is the event's srp bit for bit).  With
+ * Tm = ceil(ceil(max_frames / 32) / W) <= 256: trk_len_out: device int32 [E], T; trk_raw_out: device int32 [E][Tm], the first
+ * maximum of m_b in ascending d, -1 for a silent block; trk_power_out: device float [E][Tm], m_b[raw] / (P n_b) with n_b the
+ * block's frames, 0 where raw is -1; trk_map_out (may be NULL): device float [E][Tm][D]; rows b >= T are -1 / 0.
+ * nbr_off / nbr_idx: DEVICE int32 [D + 1] / [nbr_off[D]], row d of a neighbour table lists the directions the path may come to d
+ * from (localize.track_neighbours); both NULL: no smoothing, trk_dir_out: device int32 [E][Tm] is a copy of trk_raw_out.  With a
+ * table, s_0 = m_0, s_b[d] = m_b[d] + max_j s_{b-1}[nbr_idx[nbr_off[d] + j]] (the first maximum in ascending j, one fp32 add per
+ * cell; an index outside [0, D) is read as the nearer end), the path ends at the first maximum of s_{T-1} in ascending d and
+ * trk_dir_out[e][b] is its direction in block b, -1 where trk_raw_out[e][b] is -1.  1 <= W <= 64.  The workspace is
+ * sed_event_tdoa's followed, with a table (smooth != 0), by [Tw][D] floats and [Tw][D] 16-bit words per event, Tw =
+ * ceil(chunk slots per event / W): sed_event_doa_track_workspace_bytes; a smaller one that takes one event (E = 1) is walked in
+ * slices and changes no bit (0: the sizes are refused).  One launch more per slice than sed_event_tdoa, two with a table; the
+ * host reads nothing back; every argument is checked before anything is enqueued.
+ * sed_event_doa_track_ring is the same on the rings of live feeds: sed_event_doa_ring's arguments, rules and bits. */
+size_t sed_event_doa_track_workspace_bytes(int R, int channels, long E, long max_n_samples, int hop, int max_frames, int D,
+                                           int block_chunks, int smooth);
+int sed_event_doa_track(const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const void* tables,
+                        size_t tables_bytes, const int* ev_rec, const int* ev_onset, const int* ev_offset, const int* ev_peak_frame,
+                        long E, int time_factor, int hop, int pad_mode, int max_lag, int max_frames, float* lag_out,
+                        float* strength_out, int* frames_out, float* acc_out, const int* steer_lags, int D, int Q, const float* trig,
+                        int* dir_out, float* power_out, float* srp_out, int block_chunks, const int* nbr_off, const int* nbr_idx,
+                        int* trk_len_out, int* trk_raw_out, int* trk_dir_out, float* trk_power_out, float* trk_map_out,
+                        void* workspace, size_t workspace_bytes, void* stream);
+size_t sed_event_doa_track_ring_workspace_bytes(int R, int channels, long E, long cap, int hop, int max_frames, int D,
+                                                int block_chunks, int smooth);
+int sed_event_doa_track_ring(const float* ring, long ring_len, long cap, const long* n_host, int R, int channels, const void* tables,
+                             size_t tables_bytes, const int* ev_rec, const int* ev_onset, const int* ev_offset,
+                             const int* ev_peak_frame, long E, int time_factor, int hop, int max_lag, int max_frames, int lat_frames,
+                             int history_frames, float* lag_out, float* strength_out, int* frames_out, float* acc_out,
+                             const int* steer_lags, int D, int Q, const float* trig, int* dir_out, float* power_out, float* srp_out,
+                             int block_chunks, const int* nbr_off, const int* nbr_idx, int* trk_len_out, int* trk_raw_out,
+                             int* trk_dir_out, float* trk_power_out, float* trk_map_out, void* workspace, size_t workspace_bytes,
+                             void* stream);
 /* sed_event_beam_spans / sed_event_beamform: the audio of every located event, with the array pointed at it by a
  * steered delay-and-sum beam.  The event columns, clips_host, R, channels, time_factor, hop and max_frames are sed_event_doa's;
  * ev_dir and ev_loc_frames are the dir_out and frames_out it wrote.  An event is extracted iff 0 <= dir < D; its samples are

@@ -158,6 +158,12 @@ SIGNATURES = {
     "sed_event_doa_ring_workspace_bytes": (_sz, [_i, _i, _l, _l, _i, _i]),
     "sed_event_doa_ring": (_i, [_fp, _l, _l, _fp, _i, _i, _fp, _sz, _fp, _fp, _fp, _fp, _l, _i, _i, _i, _i, _i, _i, _fp, _fp, _fp, _fp,
                                 _fp, _i, _i, _fp, _fp, _fp, _fp, _fp, _sz, _stream]),
+    "sed_event_doa_track_workspace_bytes": (_sz, [_i, _i, _l, _l, _i, _i, _i, _i, _i]),
+    "sed_event_doa_track": (_i, [_fp, _l, _fp, _i, _i, _fp, _sz, _fp, _fp, _fp, _fp, _l, _i, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _i,
+                                 _i, _fp, _fp, _fp, _fp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _sz, _stream]),
+    "sed_event_doa_track_ring_workspace_bytes": (_sz, [_i, _i, _l, _l, _i, _i, _i, _i, _i]),
+    "sed_event_doa_track_ring": (_i, [_fp, _l, _l, _fp, _i, _i, _fp, _sz, _fp, _fp, _fp, _fp, _l, _i, _i, _i, _i, _i, _i, _fp, _fp, _fp,
+                                      _fp, _fp, _i, _i, _fp, _fp, _fp, _fp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _sz, _stream]),
     "sed_event_beam_workspace_bytes": (_sz, [_i, _i]),
     "sed_event_beam_ring_workspace_bytes": (_sz, [_i]),
     "sed_event_beam_spans": (_i, [_l, _fp, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _l, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _sz, _stream]),

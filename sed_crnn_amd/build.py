@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libsedcrnn.so")
-SOURCES = ["api.cpp", "conv.hip", "conv_bf16.hip", "wino.hip", "conv1.hip", "bnpool.hip", "gemm.hip", "gru.hip", "misc.hip", "logmel.hip", "gcc.hip", "tdoa.hip", "doa.hip", "beam.hip", "mvdr.hip", "pcen.hip", "resample.hip", "data.hip", "detect.hip", "tune.hip", "psds.hip", "stream.hip", "net.hip"]
+SOURCES = ["api.cpp", "conv.hip", "conv_bf16.hip", "wino.hip", "conv1.hip", "bnpool.hip", "gemm.hip", "gru.hip", "misc.hip", "logmel.hip", "gcc.hip", "tdoa.hip", "doa.hip", "doatrack.hip", "beam.hip", "mvdr.hip", "pcen.hip", "resample.hip", "data.hip", "detect.hip", "tune.hip", "psds.hip", "stream.hip", "net.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # per-file extras.  logmel: the SLP vectoriser packs the FFT's scalar adds into v_pk_add_f32 and pays for it with ~600
 # v_mov per frame pair to build the register pairs (packed f32 is no faster than scalar on gfx950)
@@ -20,6 +20,7 @@ EXTRA_FLAGS = {"logmel.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-reso
                "gcc.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"],
                "tdoa.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"],
                "doa.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"],
+               "doatrack.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"],
                "beam.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"],
                "mvdr.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"],
                "pcen.hip": ["-Rpass-analysis=kernel-resource-usage"],
@@ -52,6 +53,9 @@ NO_SCRATCH_KERNELS = {"wino.hip": ("conv3x3_wino_k",),
                       # per-event direction: the fine-lag loop is tdoa_finish_k's with an index unfolding per read; scratch in it
                       # would multiply the cost of the one loop the launch consists of
                       "doa.hip": ("doa_steer_k",),
+                      # direction tracks: the steering kernel is doa_steer_k's loop per block of chunks; the path kernel's inner loop
+                      # is one LDS read and a compare per neighbour: scratch in either would be the same silent cliff
+                      "doatrack.hip": ("doa_track_steer_k", "doa_track_path_k"),
                       # delay-and-sum beam: 8 outputs, 8 channel sums and a 16-sample window live per thread, indexed by unrolled
                       # loops; one of them in scratch would put a memory round trip on every fma of the launch's one loop
                       "beam.hip": ("beam_sum_k", "beam_spans_k"),

@@ -29,6 +29,7 @@ from .model import HipCRNN
 _EVENT_KEYS = ("cls", "onset", "offset", "peak", "peak_frame")
 _TDOA_KEYS = ("lag", "strength", "loc_frames")          # added to the events of a localising detector
 _DOA_KEYS = ("dir", "doa_power")                        # ... and, with localize=DOA(...), a direction per event
+_TRACK_KEYS = ("trk_len", "trk_raw", "trk_dir", "trk_power")   # ... and, with DOA(..., track=DirectionTrack(...)), a direction per block (5x)
 _BEAM_KEYS = ("audio_start", "audio_len")               # ... and, with extract=DelaySum(...), its place in result.audio
 _NOISE_KEYS = ("noise_frames",)                         # ... and, with extract=MVDR(noise_blocks >= 1), the pre-onset frames its weights used (5u)
 _QUIET_KEYS = ("noise_sel",)                            # ... and, with noise_select="quiet", which candidates they are (5w; offline only)
@@ -43,6 +44,35 @@ def _doa_angles(events, grid, k):
     out[ok, 0], out[ok, 1] = grid.azimuth[d[ok]], grid.elevation[d[ok]]
     out[ok, 2] = events["doa_power"].cpu().numpy().astype(np.float64)[ok]
     return out if k is None else out[events["cls"].cpu().numpy() == int(k)]
+
+
+def _doa_track(result, e):
+    """[T_e, 4] host float64 of event ``e``: per block its centre time in seconds, the azimuth and elevation (radians) of the track
+    and the block's power; NaN angles where a block is silent; no rows for an event that was not located"""
+    from .localize import event_frames, track_blocks
+    if "trk_len" not in result.events or result.grid is None or result.track is None:
+        raise ValueError("this result holds no direction tracks: detect with EventDetector(..., localize=sed.DOA(..., "
+                         "track=sed.DirectionTrack(...))) or pass it through det.localize(result, waveform, ...)")
+    ev = result.events
+    E = int(ev["trk_len"].numel())
+    if not -E <= int(e) < E:
+        raise IndexError(f"event {e} of {E}")
+    e = int(e) % E
+    trk, max_frames, tf, hop = result.track
+    T = int(ev["trk_len"][e])
+    out = np.full((T, 4), np.nan)
+    if T == 0:
+        return out
+    # (a detector's events end within their recording: the frames of localize.event_frames do not depend on its length)
+    f0, _ = event_frames(int(ev["onset"][e]), int(ev["offset"][e]), int(ev["peak_frame"][e]), tf, 0x7fffffff, max_frames)
+    T_rule, first, n = track_blocks(int(ev["loc_frames"][e]), trk.block_chunks)
+    assert T_rule == T
+    out[:, 0] = (f0 + first + (n - 1) / 2.0) * hop / float(result.sr)
+    d = ev["trk_dir"][e, :T].cpu().numpy().astype(np.int64)
+    ok = d >= 0
+    out[ok, 1], out[ok, 2] = result.grid.azimuth[d[ok]], result.grid.elevation[d[ok]]
+    out[:, 3] = ev["trk_power"][e, :T].cpu().numpy().astype(np.float64)
+    return out
 
 
 def _is_per_class(v):
@@ -237,8 +267,10 @@ class DetectionResult:
     """``probs`` [n_out, K] device track; ``events`` dict of device tensors (``cls``, ``onset``, ``offset``, ``peak_frame``
     int32 output frames, offset exclusive; ``peak`` float32), sorted by (class, onset); ``frame_seconds`` = tf*hop_length/sr."""
 
-    def __init__(self, probs, events, frame_seconds, plan, sr=None, grid=None, audio=None):
+    def __init__(self, probs, events, frame_seconds, plan, sr=None, grid=None, audio=None, track=None):
         self.probs, self.events, self.frame_seconds, self.plan = probs, events, frame_seconds, plan
+        # (DirectionTrack, max_frames, time_factor, hop_length): set on results located with DOA(..., track=...) settings (5x)
+        self.track = track
         self.sr = sr                            # the detector's rate: set on located results (lags are in samples at that rate)
         self.grid = grid                        # the DirectionGrid that ``dir`` indexes: set on results located with DOA settings
         # the packed beamformed audio that ``audio_start`` / ``audio_len`` index (DESIGN 5r): set by a detector with extract=; a
@@ -271,6 +303,13 @@ class DetectionResult:
             raise ValueError("this result holds no directions: detect with EventDetector(..., localize=sed.DOA(...)) or pass it "
                              "through det.localize(result, waveform, ...)")
         return _doa_angles(self.events, self.grid, k)
+
+    def doa_track(self, e):
+        """the direction track of event ``e``, a host array [T_e, 4]: per block of the event's located frames
+        (``localize.track_blocks``) its centre time in seconds, the azimuth and elevation in radians of ``trk_dir`` and the
+        block's steered response power per pair and frame; a silent block has NaN angles, an event that was not located no
+        rows.  Only on the result of a detector with ``localize=DOA(..., track=DirectionTrack(...))``."""
+        return _doa_track(self, e)
 
     def event_audio(self, e):
         """the beamformed audio of event ``e``: a float32 device slice of ``audio`` at the detector's rate, empty
@@ -310,10 +349,10 @@ class BatchDetectionResult:
     ``events`` dict of device tensors with ``rec`` (sorted by recording, class, onset), and the host lists ``out_offsets``
     [R+1] (recording i = rows [out_offsets[i], out_offsets[i+1])) and ``event_offsets`` [R+1]."""
 
-    def __init__(self, probs, events, frame_seconds, plans, out_offsets, event_offsets, sr=None, grid=None, audio=None):
+    def __init__(self, probs, events, frame_seconds, plans, out_offsets, event_offsets, sr=None, grid=None, audio=None, track=None):
         self.probs, self.events, self.frame_seconds, self.plans = probs, events, frame_seconds, tuple(plans)
         self.out_offsets, self.event_offsets = list(out_offsets), list(event_offsets)
-        self.sr, self.grid, self.audio = sr, grid, audio         # as in DetectionResult
+        self.sr, self.grid, self.audio, self.track = sr, grid, audio, track          # as in DetectionResult
 
     def __len__(self):
         return len(self.plans)
@@ -325,9 +364,13 @@ class BatchDetectionResult:
         i = int(i) % R
         o0, o1 = self.out_offsets[i], self.out_offsets[i + 1]
         e0, e1 = self.event_offsets[i], self.event_offsets[i + 1]
-        keys = _EVENT_KEYS + tuple(k for k in _TDOA_KEYS + _DOA_KEYS + _BEAM_KEYS + _NOISE_KEYS + _QUIET_KEYS if k in self.events)
+        keys = _EVENT_KEYS + tuple(k for k in _TDOA_KEYS + _DOA_KEYS + _TRACK_KEYS + _BEAM_KEYS + _NOISE_KEYS + _QUIET_KEYS if k in self.events)
         return DetectionResult(self.probs[o0:o1], {k: self.events[k][e0:e1] for k in keys}, self.frame_seconds, self.plans[i], self.sr,
-                               self.grid, self.audio)
+                               self.grid, self.audio, self.track)
+
+    def doa_track(self, e):
+        """the direction track of event ``e`` of the packed table (``DetectionResult.doa_track``)"""
+        return _doa_track(self, e)
 
     def event_audio(self, e):
         """the beamformed audio of event ``e`` of the packed table (``DetectionResult.event_audio``)"""
@@ -371,7 +414,8 @@ class EventDetector:
     ``from_features*`` has no audio and returns un-located events, which ``det.localize(result, waveform, ...)`` locates.
     ``localize=sed.DOA(positions, grid, ...)`` for a known array: the same three keys, with ``max_lag`` taken from the
     array's aperture, and ``dir`` [E] (a row of ``grid``, -1: not located) and ``doa_power`` [E] (``events.event_doa``;
-    ``result.doa()`` in radians).  ``extract=sed.DelaySum(...)`` (needs ``localize=sed.DOA(...)``): every located event
+    ``result.doa()`` in radians); with ``sed.DOA(..., track=sed.DirectionTrack(block_chunks, max_step_deg))`` also a direction
+    per block of the event's located frames, ``trk_len`` [E], ``trk_raw``, ``trk_dir`` and ``trk_power`` [E, Tm] (``result.doa_track(e)``).  ``extract=sed.DelaySum(...)`` (needs ``localize=sed.DOA(...)``): every located event
     also comes with its audio, the array pointed at ``dir`` by a delay-and-sum beam (``events.event_beamform`` on the PCM that
     is kept anyway): ``audio_start`` / ``audio_len`` [E] in the events, the packed float32 buffer ``result.audio`` and
     ``result.event_audio(e)``; ``from_features*`` returns events without audio, ``det.localize`` adds it, ``det.stream`` of such a
@@ -623,7 +667,7 @@ class EventDetector:
             if self.locates_directions:
                 loc = event_doa(pcm, clips, self.audio_channels, result.events, self.model.time_factor, t, sr=self.sr,
                                         hop=self.hop_length)
-                result.grid = t.grid
+                result.grid, result.track = t.grid, self._track_info()
             else:
                 loc = event_tdoa(pcm, clips, self.audio_channels, result.events, self.model.time_factor, max_lag=t.max_lag,
                                          max_frames=t.max_frames, hop=self.hop_length)
@@ -635,7 +679,7 @@ class EventDetector:
                              self.extract_settings, sr=self.sr, hop=self.hop_length, **quiet)
                 result.audio = beam.pop("audio")
                 loc.update(beam)
-        result.events = {**{k: v for k, v in result.events.items() if k not in _TDOA_KEYS + _DOA_KEYS + _BEAM_KEYS + _NOISE_KEYS + _QUIET_KEYS}, **loc}
+        result.events = {**{k: v for k, v in result.events.items() if k not in _TDOA_KEYS + _DOA_KEYS + _TRACK_KEYS + _BEAM_KEYS + _NOISE_KEYS + _QUIET_KEYS}, **loc}
         result.sr = self.sr
         return result
 
@@ -644,6 +688,13 @@ class EventDetector:
         """whether the localisation settings are ``DOA(...)``: the events also hold ``dir`` and ``doa_power``"""
         from .localize import DOA
         return isinstance(self.localize_settings, DOA)
+
+    def _track_info(self):
+        """what ``doa_track`` of a result needs beside its events: (DirectionTrack, max_frames, time_factor, hop_length), or None"""
+        t = self.localize_settings
+        if not self.locates_directions or t.track is None:
+            return None
+        return (t.track, t.max_frames, self.model.time_factor, self.hop_length)
 
     def localize(self, result, waveforms, sr=None, channels=None):
         """Locate events that were detected without their audio at hand (``from_features*``): ``result`` — a DetectionResult with
@@ -669,6 +720,7 @@ class EventDetector:
             if self.extract_settings is not None:
                 result.audio = torch.empty(0, device=self.model.flat_parameters().device)
             result.grid = self.localize_settings.grid if self.locates_directions else None
+            result.track = self._track_info()
             return result
         from .resample import resample_many
         pcm, clips = resample_many(waves, self.sr if sr is None else sr, self.sr, channels, self.model.flat_parameters().device,
@@ -865,7 +917,7 @@ class EventDetector:
         return BatchDetectionResult(torch.empty(0, m.dense[-1], device=dev), ev, self.frame_seconds, (), [0], [0],
                                     self.sr if self.localize_settings is not None else None,
                                     self.localize_settings.grid if self.locates_directions else None,
-                                    torch.empty(0, device=dev) if self.extract_settings is not None else None)
+                                    torch.empty(0, device=dev) if self.extract_settings is not None else None, self._track_info())
 
     def _no_lags(self):
         """the localisation columns of an empty event table"""
@@ -874,6 +926,10 @@ class EventDetector:
                "loc_frames": torch.empty(0, dtype=torch.int32, device=dev)}
         if self.locates_directions:
             out.update(dir=torch.empty(0, dtype=torch.int32, device=dev), doa_power=torch.empty(0, device=dev))
+            if self.localize_settings.track is not None:
+                Tm = self.localize_settings.track.max_blocks(self.localize_settings.max_frames)
+                out.update(trk_len=torch.empty(0, dtype=torch.int32, device=dev), trk_raw=torch.empty(0, Tm, dtype=torch.int32, device=dev),
+                           trk_dir=torch.empty(0, Tm, dtype=torch.int32, device=dev), trk_power=torch.empty(0, Tm, device=dev))
         if self.extract_settings is not None:
             out.update(audio_start=torch.empty(0, dtype=torch.int64, device=dev), audio_len=torch.empty(0, dtype=torch.int32, device=dev))
         if getattr(self.extract_settings, "noise_blocks", 0):

@@ -17,6 +17,7 @@ from .feature import GCC_MAX_CHANNELS, HOP, NB_MEL, NFFT, SR, _LM_OFF_ENT, _clip
 # (what is computed, on rings) -> the C entry; its workspace function is the name + "_workspace_bytes"
 _ENTRY = {("tdoa", False): "sed_event_tdoa", ("tdoa", True): "sed_event_tdoa_ring",
           ("doa", False): "sed_event_doa", ("doa", True): "sed_event_doa_ring",
+          ("doa_track", False): "sed_event_doa_track", ("doa_track", True): "sed_event_doa_track_ring",
           ("spans", False): "sed_event_beam_spans", ("spans", True): "sed_event_beam_spans_ring",
           ("delay_sum", False): "sed_event_beamform", ("delay_sum", True): "sed_event_beamform_ring",
           ("mvdr", False): "sed_event_mvdr", ("mvdr", True): "sed_event_mvdr_ring",
@@ -142,6 +143,29 @@ def _doa_io(doa, sr, E, dev, out, return_map):
     return [ptr(Jd), J.shape[0], doa.oversample, ptr(td), ptr(out["dir"]), ptr(out["doa_power"]), ptr(out.get("srp"))]
 
 
+def _track_io(doa, E, dev, out, return_map):
+    """the outputs a track call adds, added to ``out``, and the neighbour table of ``doa`` on ``dev`` (uploaded once per
+    device and step) -> [block_chunks, nbr_off, nbr_idx, trk_len, trk_raw, trk_dir, trk_power, trk_map or None] (None without events)"""
+    trk = doa.track
+    Tm, D = trk.max_blocks(doa.max_frames), len(doa.grid)
+    out["trk_len"] = torch.empty(E, dtype=torch.int32, device=dev)
+    out["trk_raw"] = torch.empty(E, Tm, dtype=torch.int32, device=dev)
+    out["trk_dir"] = torch.empty(E, Tm, dtype=torch.int32, device=dev)
+    out["trk_power"] = torch.empty(E, Tm, device=dev)
+    if return_map:
+        out["trk_map"] = torch.empty(E, Tm, D, device=dev)
+    if E == 0:
+        return None
+    nbr = [None, None]
+    if trk.max_step_deg is not None:
+        key = (dev.index or 0, trk.max_step_deg)
+        if key not in doa._neighbours_device:
+            doa._neighbours_device[key] = tuple(torch.from_numpy(a).to(dev) for a in doa.neighbours())
+        nbr = doa._neighbours_device[key]
+    return [trk.block_chunks, ptr(nbr[0]), ptr(nbr[1]), ptr(out["trk_len"]), ptr(out["trk_raw"]), ptr(out["trk_dir"]), ptr(out["trk_power"]),
+            ptr(out.get("trk_map"))]
+
+
 def _locate(src, events, tf, hop, max_lag, max_frames, settings, return_curve, max_workspace_bytes, doa):
     """what the four TDOA / DOA functions do once their arguments are checked.  ``settings``: what the C entry takes between ``hop``
     and its outputs; ``doa``: None, or (the ``localize.DOA``, the rate of the PCM, return_map) for the same launches and one more
@@ -154,18 +178,22 @@ def _locate(src, events, tf, hop, max_lag, max_frames, settings, return_curve, m
     if return_curve:
         out["acc"] = torch.empty(E, P, W, device=dev)
     extra = _doa_io(doa[0], doa[1], E, dev, out, doa[2]) if doa is not None else []
+    track = doa is not None and getattr(doa[0], "track", None) is not None          # a direction per block too
+    if track:
+        extra = (extra or []) + (_track_io(doa[0], E, dev, out, doa[2]) or [])
     if E == 0:
         return out
     tables = _tables(dev.index or 0, SR, NFFT, NB_MEL)                # the window and the twiddles; the mel plan is not read
-    sizes = _ENTRY["tdoa", src.ring] + "_workspace_bytes"             # (the steering launch reads the partials in place)
-    need_one = getattr(lib(), sizes)(R, nc, 1, src.extent, hop, max_frames)
-    need_all = getattr(lib(), sizes)(R, nc, E, src.extent, hop, max_frames)
+    sizes = _ENTRY["doa_track" if track else "tdoa", src.ring] + "_workspace_bytes"   # (the steering launch reads the partials in place)
+    more = [len(doa[0].grid), doa[0].track.block_chunks, int(doa[0].track.max_step_deg is not None)] if track else []
+    need_one = getattr(lib(), sizes)(R, nc, 1, src.extent, hop, max_frames, *more)
+    need_all = getattr(lib(), sizes)(R, nc, E, src.extent, hop, max_frames, *more)
     if need_one == 0:
         raise ValueError(f"sed_event_tdoa_ring_workspace_bytes refuses R={R}, channels={nc}, cap={src.extent}, hop={hop}, max_frames={max_frames}"
                          if src.ring else
                          f"sed_event_tdoa_workspace_bytes refuses R={R}, channels={nc}, hop={hop}, max_frames={max_frames}")
     ws = torch.empty(min(need_all, max(need_one, int(max_workspace_bytes))), dtype=torch.uint8, device=dev)
-    name = _ENTRY["tdoa" if doa is None else "doa", src.ring]
+    name = _ENTRY["tdoa" if doa is None else "doa_track" if track else "doa", src.ring]
     check(getattr(lib(), name)(*src.head, ptr(tables), tables.numel() * 4, *_col_ptrs(col, _LOCATED[:3]), E, tf, hop, *settings,
                                ptr(out["lag"]), ptr(out["strength"]), ptr(out["loc_frames"]), ptr(out.get("acc")), *extra, ptr(ws),
                                ws.numel(), stream_ptr()), name)
@@ -237,7 +265,16 @@ def event_doa(pcm, clips, channels, events, time_factor, doa, sr=SR, hop=HOP, pa
     ``1 / doa.oversample`` sample.  Returns the dict of ``event_tdoa`` — the same bits — with ``dir`` int32 [E] (a row of the
     grid; -1: the event has no frames, or digital silence) and ``doa_power`` float32 [E] (the response per pair and frame at
     that direction, in [-1, 1]; 0 where ``dir`` is -1); ``return_map=True`` adds ``srp`` float32 [E, D], the response at every
-    direction (secondary peaks are other sources or reflections).  One more launch per slice; the host reads nothing back."""
+    direction (secondary peaks are other sources or reflections).  One more launch per slice; the host reads nothing back.
+
+    With ``doa.track`` set (a ``sed.DirectionTrack(block_chunks, max_step_deg)``; ``sed_event_doa_track``) every key
+    above keeps its bits and the dict gains a direction per block of ``32 * block_chunks`` located frames
+    (``localize.track_blocks``), ``Tm = ceil(ceil(max_frames / 32) / block_chunks)`` columns an event: ``trk_len`` int32 [E], the
+    blocks T of the event; ``trk_raw`` int32 [E, Tm], the maximum of every block's own map (-1: a silent block, and behind T);
+    ``trk_dir`` int32 [E, Tm], the best path through the block maps that turns by at most ``max_step_deg`` a block (-1 where
+    ``trk_raw`` is; ``trk_raw`` itself without ``max_step_deg``); ``trk_power`` float32 [E, Tm], the block's response at
+    ``trk_raw`` per pair and frame; and with ``return_map=True`` ``trk_map`` float32 [E, Tm, D].  No frame is transformed twice:
+    the blocks are steered from the chunk sums the event's own direction is made from."""
     return _tdoa_linear(pcm, clips, channels, events, time_factor, 24, getattr(doa, "max_frames", 256), hop, pad_mode, return_curve,
                         max_workspace_bytes, (doa, sr, return_map))
 

@@ -13,11 +13,14 @@ the host side of per-event audio extraction by a steered delay-and-sum beam (DES
 entry ``events.event_beamform``): the settings of ``EventDetector(..., localize=DOA(...), extract=DelaySum())``, the
 fractional-delay filter, the delay every direction means for every microphone, and the samples an event's audio consists of.
 ``MVDR`` and ``mvdr_window`` are the host side of the adaptive beam that extracts the same events (the kernels are
-csrc/mvdr.hip, the device entry ``events.event_mvdr``).
+csrc/mvdr.hip, the device entry ``events.event_mvdr``).  ``DirectionTrack``, ``track_blocks`` and ``track_neighbours`` are the host side
+of direction tracks (the kernels are csrc/doatrack.hip): the settings of ``DOA(..., track=DirectionTrack(...))``, the
+blocks an event's located frames are cut into, and the directions a smoothed track may step between.
 """
 import dataclasses
 import functools
 import math
+import typing
 
 import numpy as np
 
@@ -224,15 +227,92 @@ def trig_table(oversample):
     return np.array([[math.cos(x), math.sin(x)] for x in a], dtype=np.float64).astype(np.float32)
 
 
+# ── direction tracks ──
+TRACK_CHUNK = 32               # tdoa.hip: TD_CHUNK, the located frames of one chunk partial
+TRACK_MAX_BLOCK_CHUNKS = 64    # doatrack.hip: TRK_MAX_W
+TRACK_MAX_BLOCKS = 256         # doatrack.hip: TRK_MAX_BLOCKS
+
+
+@dataclasses.dataclass(frozen=True)
+class DirectionTrack:
+    """Settings of a direction track (``sed.DOA(positions, grid, ..., track=DirectionTrack(...))``): every located
+    event also gets a direction per block of ``block_chunks`` = W chunks of 32 located frames (``track_blocks``), for a source
+    that moves while it sounds.  ``max_step_deg``: None — every block's direction is the maximum of its own map — or a finite
+    angle in (0, 180]: the directions are the best path through the block maps that turns by at most this much from one block to
+    the next (``track_neighbours``), which does not jump to a reflection for the length of one block."""
+    block_chunks: int = 1
+    max_step_deg: typing.Optional[float] = None
+
+    def __post_init__(self):
+        w = self.block_chunks
+        if isinstance(w, bool) or not isinstance(w, (int, np.integer)) or not 1 <= int(w) <= TRACK_MAX_BLOCK_CHUNKS:
+            raise ValueError(f"DirectionTrack: block_chunks must be an integer in [1, {TRACK_MAX_BLOCK_CHUNKS}], got {w!r}")
+        object.__setattr__(self, "block_chunks", int(w))
+        s = self.max_step_deg
+        if s is not None:
+            if isinstance(s, bool) or not isinstance(s, (int, float, np.floating, np.integer)) or not math.isfinite(float(s)) \
+                    or not 0.0 < float(s) <= 180.0:
+                raise ValueError(f"DirectionTrack: max_step_deg must be None or a finite angle in (0, 180] degrees, got {s!r}")
+            object.__setattr__(self, "max_step_deg", float(s))
+
+    def max_blocks(self, max_frames):
+        """``Tm``: the most blocks an event located on up to ``max_frames`` frames has, ``ceil(ceil(max_frames / 32) / W)``"""
+        return -(-(-(-int(max_frames) // TRACK_CHUNK)) // self.block_chunks)
+
+
+def track_blocks(nf, block_chunks):
+    """The blocks of an event located on ``nf`` frames, with W = ``block_chunks`` (doatrack.hip applies the same rule)
+    -> ``(T, first_frame [T], n_frames [T])``, the frames counted from the event's first.  ``nch = ceil(nf / 32)``,
+    ``T0 = ceil(nch / W)``, ``nl = nf - 32 W (T0 - 1)``; a last block of fewer than ``16 W`` frames joins the block before it
+    (``T = T0 - 1`` where ``T0 > 1`` and ``nl < 16 W``).  ``nf = 0`` has no blocks."""
+    nf, W = int(nf), int(block_chunks)
+    if nf < 0 or not 1 <= W <= TRACK_MAX_BLOCK_CHUNKS:
+        raise ValueError(f"track_blocks needs nf >= 0 and 1 <= block_chunks <= {TRACK_MAX_BLOCK_CHUNKS}, got {nf}, {block_chunks}")
+    if nf == 0:
+        return 0, np.zeros(0, np.int64), np.zeros(0, np.int64)
+    step = TRACK_CHUNK * W
+    nch = -(-nf // TRACK_CHUNK)
+    T0 = -(-nch // W)
+    T = T0 - 1 if T0 > 1 and nf - step * (T0 - 1) < step // 2 else T0
+    first = step * np.arange(T, dtype=np.int64)
+    n = np.full(T, step, np.int64)
+    n[-1] = nf - first[-1]
+    return T, first, n
+
+
+def track_neighbours(grid, max_step_deg):
+    """The directions a path may come to direction d from -> ``(off int32 [D + 1], idx int32 [nnz])``: row d,
+    ``idx[off[d]:off[d + 1]]``, lists in ascending order every d' with ``arccos(clip(u_d . u_d', -1, 1)) <=
+    radians(max_step_deg) + 1e-9`` in float64; it always contains d."""
+    if not isinstance(grid, DirectionGrid):
+        raise TypeError(f"track_neighbours: grid must be a DirectionGrid, got {type(grid).__name__}")
+    s = max_step_deg
+    if isinstance(s, bool) or not isinstance(s, (int, float, np.floating, np.integer)) or not math.isfinite(float(s)) or not 0.0 < float(s) <= 180.0:
+        raise ValueError(f"track_neighbours: max_step_deg must be a finite angle in (0, 180] degrees, got {s!r}")
+    u, bound = grid.unit_vectors, math.radians(float(s)) + 1e-9
+    D = u.shape[0]
+    off, rows = np.zeros(D + 1, np.int64), []
+    for d0 in range(0, D, 1024):                                  # (1024 rows of the D x D angles at a time)
+        near = np.arccos(np.clip(u[d0:d0 + 1024] @ u.T, -1.0, 1.0)) <= bound
+        near[np.arange(near.shape[0]), d0 + np.arange(near.shape[0])] = True
+        r, c = np.nonzero(near)                                   # row-major: ascending within a row
+        rows.append(c)
+        off[d0 + 1:d0 + 1 + near.shape[0]] = np.bincount(r, minlength=near.shape[0])
+    off = np.cumsum(off)
+    assert off[-1] < 2 ** 31
+    return off.astype(np.int32), np.ascontiguousarray(np.concatenate(rows).astype(np.int32))
+
+
 class DOA:
     """Settings of per-event direction of arrival (``EventDetector(model, ..., localize=DOA(positions, grid))``):
     steered response power (SRP-PHAT) over ``grid`` for the microphones at ``positions`` [C, 3] (metres, in the order of the
     audio channels).  ``oversample`` Q in {1, 2, 4, 8, 16}: the correlation of every pair is evaluated at lags of 1/Q sample,
     exactly.  ``max_frames`` as in ``TDOA``; ``max_lag`` follows from the array: ``max_lag_for`` of its largest spacing at the
     detector's rate, which must not exceed 127 samples.  ``c``: the speed of sound in m/s.  A detector with these settings
-    also returns everything a ``TDOA(max_lag, max_frames)`` detector returns."""
+    also returns everything a ``TDOA(max_lag, max_frames)`` detector returns.  ``track``: None, or a ``DirectionTrack``: every
+    event also gets a direction per block of its located frames."""
 
-    def __init__(self, positions, grid, max_frames=256, oversample=8, c=SPEED_OF_SOUND):
+    def __init__(self, positions, grid, max_frames=256, oversample=8, c=SPEED_OF_SOUND, track=None):
         r = _positions(positions, "DOA")
         if not isinstance(grid, DirectionGrid):
             raise TypeError(f"DOA: grid must be a DirectionGrid, got {type(grid).__name__}")
@@ -249,6 +329,14 @@ class DOA:
         if dist.min() <= 0.0:
             i, j = _pairs(r.shape[0])[int(dist.argmin())]
             raise ValueError(f"DOA: microphones {i} and {j} are at the same position")
+        if track is not None:
+            if not isinstance(track, DirectionTrack):
+                raise TypeError(f"DOA: track must be None or a DirectionTrack(...), got {type(track).__name__}")
+            if track.max_blocks(max_frames) > TRACK_MAX_BLOCKS:
+                raise ValueError(f"DOA: max_frames={max_frames} in blocks of {track.block_chunks} chunks is {track.max_blocks(max_frames)} "
+                                 f"blocks an event, more than {TRACK_MAX_BLOCKS}; use a larger block_chunks")
+            self._neighbours, self._neighbours_device = {}, {}   # per max_step_deg: track_neighbours of the grid; per device: its copy
+        self.track = track
         r.setflags(write=False)
         self.positions, self.grid = r, grid
         self.max_frames, self.oversample, self.c = int(max_frames), int(oversample), float(c)
@@ -303,9 +391,18 @@ class DOA:
         """the ``TDOA`` settings whose outputs a detector with these settings also returns"""
         return TDOA(self.max_lag(sr), self.max_frames)
 
+    def neighbours(self):
+        """``track_neighbours`` of the grid for the track's ``max_step_deg``, cached; None without smoothing"""
+        if self.track is None or self.track.max_step_deg is None:
+            return None
+        key = self.track.max_step_deg
+        if key not in self._neighbours:
+            self._neighbours[key] = track_neighbours(self.grid, key)
+        return self._neighbours[key]
+
     def __repr__(self):
         return (f"DOA({self.channels} microphones, aperture {self.aperture:.4g} m, {len(self.grid)} directions, max_frames={self.max_frames}, "
-                f"oversample={self.oversample}, c={self.c:g})")
+                f"oversample={self.oversample}, c={self.c:g}" + (f", track={self.track!r}" if self.track is not None else "") + ")")
 
 
 # ── the audio of a located event: a steered delay-and-sum beam (DESIGN 5r) ──

@@ -42,7 +42,9 @@ last ``cap`` samples in a ring on the device (``sed_stream_ring_write``, one lau
 locates them from the rings in one ``sed_event_tdoa_ring`` call — an event ``[a, b)`` with frames from ``f0`` iff ``b*tf + lat - f0
 <= history_frames`` (``localize.stream_locates``), with the bits of the offline call; ``flush`` / ``reset`` need no ring work either.
 With ``localize=sed.DOA(...)`` that call is ``sed_event_doa_ring`` and the events also carry ``dir`` and ``doa_power``
-(``StreamEvents.doa()``); an event the rule refuses has ``dir = -1``.
+(``StreamEvents.doa()``); an event the rule refuses has ``dir = -1``.  With ``sed.DOA(..., track=sed.DirectionTrack(...))`` (DESIGN
+5x) the call is ``sed_event_doa_track_ring`` and the events also carry a direction per block (``StreamEvents.doa_track(e)``); no new
+state is kept, and an event the rule refuses has ``trk_len = 0``.
 With ``extract=sed.DelaySum(...)`` or ``sed.MVDR(...)`` and ``emit_audio=True`` a step that emitted events makes one
 more call on the same rings, ``events.event_beamform_ring`` or ``events.event_mvdr_ring``: the events carry ``audio_start`` and
 ``audio_len`` (and, with ``sed.MVDR(noise_blocks >= 1)``, ``noise_frames``: DESIGN 5u) and the call's ``StreamEvents.audio`` holds
@@ -56,7 +58,7 @@ import torch
 
 from . import feature
 from ._lib import SedHipError, check, lib, ptr, stream_ptr
-from .detect import (_BEAM_KEYS, _DOA_KEYS, _NOISE_KEYS, _TDOA_KEYS, EventDetector, _doa_angles, _event_audio, _event_tensors, _intervals,
+from .detect import (_BEAM_KEYS, _DOA_KEYS, _NOISE_KEYS, _TDOA_KEYS, _TRACK_KEYS, EventDetector, _doa_angles, _doa_track, _event_audio, _event_tensors, _intervals,
                      _noise_frames, _timed, _window_jobs, plan_windows)
 from .events import _beam_empty, _mvdr_empty, event_beamform_ring, event_doa_ring, event_mvdr_ring, event_tdoa_ring, ring_write
 
@@ -179,12 +181,13 @@ class StreamEvents:
     by stream and class, the buffer is in step order)."""
 
     def __init__(self, events, event_offsets, final_frames, frame_seconds, probs=None, prob_offsets=None, sr=None, grid=None,
-                 audio=None):
+                 audio=None, track=None):
         self.events, self.event_offsets, self.final_frames = events, list(event_offsets), list(final_frames)
         self.frame_seconds, self.probs, self.prob_offsets = frame_seconds, probs, prob_offsets
         self.sr = sr                            # the detector's rate: set by a localising stream (lags are in samples at that rate)
         self.grid = grid                        # the DirectionGrid that ``dir`` indexes: set by a stream with DOA settings
         self.audio = audio                      # the packed extracted audio of this call: set by a stream with emit_audio=True
+        self.track = track                      # as in DetectionResult: set by a stream with DOA(..., track=...) settings (DESIGN 5x)
 
     def __len__(self):
         return self.event_offsets[-1]
@@ -213,6 +216,12 @@ class StreamEvents:
                              "det.stream(S, history_frames=...)")
         out = _doa_angles(self.events, self.grid, None)
         return out if stream is None else out[self.event_offsets[int(stream)]:self.event_offsets[int(stream) + 1]]
+
+    def doa_track(self, e):
+        """the direction track of event ``e`` (in event order), a host array [T_e, 4] as ``DetectionResult.doa_track``: the times
+        count from the start of the event's feed; an event the stream's history rule refused has no rows.  Only on what a
+        stream with ``localize=sed.DOA(..., track=sed.DirectionTrack(...))`` returns."""
+        return _doa_track(self, e)
 
     def event_audio(self, e):
         """the extracted audio of event ``e`` of this call (``DetectionResult.event_audio``): a float32 device slice of ``audio``
@@ -317,7 +326,8 @@ class StreamDetector:
                 raise ValueError(f"history_frames={self.history_frames} is less than the minimum max_frames + lat = "
                                  f"{det.localize_settings.max_frames} + {self.lat} = {least} feature frames (\"min\")")
             self.cap = stream_ring_samples(self.history_frames, self.step_frames, h, feature.NFFT)
-            self._ev_keys = _KEYS + _TDOA_KEYS + (_DOA_KEYS if det.locates_directions else ()) + (_BEAM_KEYS if self.emit_audio else ()) + \
+            self._ev_keys = _KEYS + _TDOA_KEYS + (_DOA_KEYS if det.locates_directions else ()) + \
+                            (_TRACK_KEYS if det._track_info() is not None else ()) + (_BEAM_KEYS if self.emit_audio else ()) + \
                             (_NOISE_KEYS if self.noise_frames else ())
         self._dims = (S, self.K, self.win_out, self.hop_out, det.median_max, self.max_new)
         self._core_bytes = lib().sed_stream_state_bytes(*self._dims)
@@ -661,13 +671,15 @@ class StreamDetector:
                       loc_frames=torch.empty(0, dtype=torch.int32, device=dev))
             if self.det.locates_directions:
                 ev.update(dir=torch.empty(0, dtype=torch.int32, device=dev), doa_power=torch.empty(0, device=dev))
+                ev.update({k: v for k, v in self.det._no_lags().items() if k in _TRACK_KEYS})
             if self.emit_audio:
                 ev.update({k: v for k, v in self._no_audio(dev).items() if k != "audio"})
         return ev
 
     def _events(self, ev, offs, final, probs, poffs, audio=None):
         return StreamEvents(ev, offs, final, self.frame_seconds, probs, poffs, self.det.sr if self.cap else None,
-                            self.det.localize_settings.grid if self.cap and self.det.locates_directions else None, audio)
+                            self.det.localize_settings.grid if self.cap and self.det.locates_directions else None, audio,
+                            self.det._track_info() if self.cap else None)
 
     def _pieces(self, xs, what, check_one, axis=0):
         xs = list(xs)
