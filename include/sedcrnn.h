@@ -757,6 +757,51 @@ int sed_event_mvdr_quiet(const float* pcm, long pcm_len, const long* clips_host,
                          float* audio, long audio_total, int* noise_frames_out, int* noise_sel_out, void* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* sed_event_mvdr_track / sed_event_mvdr_track_ring / sed_event_mvdr_quiet_track: sed_event_mvdr_noise /
+ * sed_event_mvdr_noise_ring / sed_event_mvdr_quiet with the beam steered along every event's direction track, as
+ * sed_event_doa_track(_ring) wrote it: block_chunks = W in [1, 64], track_slots = Tm in [1, 256] (the columns of trk_dir), trk_len
+ * DEVICE int32 [E], trk_dir DEVICE int32 [E][Tm].  The samples, the spans, the covariance (noise_blocks = 0: the own frames; Kn >= 1:
+ * the frames before the onset, or the quiet selection), the transform grid, the inverse transform and the overlap-add are the
+ * untracked entry's.  The rule is integer: with T = trk_len[e] clamped to [0, Tm], frame j = 0..J of an event is combined with
+ *   b_j = min((j * 1024 / hop) / (32 W), T - 1),   d_j = trk_dir[e][b_j] where T > 0 and 0 <= trk_dir[e][b_j] < D, else ev_dir[e]
+ *   w_b = (R + lambda I)^-1 d_b / (d_b^H (R + lambda I)^-1 d_b)     float64, ONE Cholesky factor per (event, bin), a pair of
+ *                                                                   solves per block b < max(T, 1); trace(R) not > 0: d_b / C; fp32
+ *   Y_j = sum_c conj(w_{b_j,c}) X_{c,j}                              ascending c
+ * (the centre of frame j is sample j * 1024 of the event, which lies in located frame j * 1024 / hop).  A silent block (-1), a row
+ * outside [0, D) and an event without a track (T = 0) are steered at ev_dir and never index tau.  A track whose every used row
+ * equals ev_dir gives the untracked entry's audio, bit for bit.  noise_frames_out (and noise_sel_out) as in the untracked entry.
+ * workspace: at least sed_event_mvdr_track_workspace_bytes(R, channels, max_frames, hop, noise_blocks, track_slots) (..._track_ring_...;
+ * sed_event_mvdr_quiet_track_workspace_bytes(R, channels, max_frames, hop, noise_blocks, mask_frames, track_slots); 0: refused sizes)
+ * — per event the chunk slots of the untracked entry and C rows of weights for each of Tm blocks.  Every argument is checked on the
+ * host before anything is enqueued; messages begin with "mvdr_track:" / "mvdr_track_ring:" / "mvdr_quiet_track:".  E = 0 or
+ * audio_total = 0 launches nothing. */
+size_t sed_event_mvdr_track_workspace_bytes(int R, int channels, int max_frames, int hop, int noise_blocks, int track_slots);
+int sed_event_mvdr_track(const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const int* ev_rec,
+                         const int* ev_onset, const int* ev_offset, const int* ev_peak_frame, const int* ev_dir,
+                         const int* ev_loc_frames, long E, int time_factor, int hop, int max_frames, const double* tau, int D,
+                         double loading, int noise_blocks, int noise_guard, const void* tables, size_t tables_bytes,
+                         const int* audio_len, const long* audio_start, float* audio, long audio_total, int* noise_frames_out,
+                         int block_chunks, int track_slots, const int* trk_len, const int* trk_dir, void* workspace,
+                         size_t workspace_bytes, void* stream);
+size_t sed_event_mvdr_track_ring_workspace_bytes(int R, int channels, int max_frames, int hop, int noise_blocks, int track_slots);
+int sed_event_mvdr_track_ring(const float* ring, long ring_len, long cap, const long* n_host, int R, int channels, const int* ev_rec,
+                              const int* ev_onset, const int* ev_offset, const int* ev_peak_frame, const int* ev_dir,
+                              const int* ev_loc_frames, long E, int time_factor, int hop, int max_frames, const double* tau, int D,
+                              double loading, int noise_blocks, int noise_guard, const void* tables, size_t tables_bytes,
+                              const int* audio_len, const long* audio_start, float* audio, long audio_total, int* noise_frames_out,
+                              int block_chunks, int track_slots, const int* trk_len, const int* trk_dir, void* workspace,
+                              size_t workspace_bytes, void* stream);
+size_t sed_event_mvdr_quiet_track_workspace_bytes(int R, int channels, int max_frames, int hop, int noise_blocks, long mask_frames,
+                                                  int track_slots);
+int sed_event_mvdr_quiet_track(const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const int* ev_rec,
+                               const int* ev_cls, const int* ev_onset, const int* ev_offset, const int* ev_peak_frame,
+                               const int* ev_dir, const int* ev_loc_frames, long E, int time_factor, int hop, int max_frames,
+                               const double* tau, int D, double loading, int noise_blocks, int noise_guard, int n_classes,
+                               int noise_search, int noise_min, int exclude_any, const void* tables, size_t tables_bytes,
+                               const int* audio_len, const long* audio_start, float* audio, long audio_total, int* noise_frames_out,
+                               int* noise_sel_out, int block_chunks, int track_slots, const int* trk_len, const int* trk_dir,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
 /* sed_pcen: per-channel energy normalisation, IN PLACE, of the columns [col0, col0 + W) of x [rows][stride], which
  * hold log-mel values (natural log, as sed_logmel* write them without a scaler); the other columns are not touched.  Every column
  * of a recording is one chain: E[t] = scale * exp(x[t]); M[t] = (1 - smooth_b) M[t-1] + smooth_b E[t] with M[0] = E[0] (librosa's

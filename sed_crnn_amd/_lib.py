@@ -190,6 +190,15 @@ SIGNATURES = {
     "sed_event_mvdr_quiet_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _l]),
     "sed_event_mvdr_quiet": (_i, [_fp, _l, _fp, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _l, _i, _i, _i, _fp, _i, _d, _i, _i, _i, _i, _i,
                                   _i, _fp, _sz, _fp, _fp, _fp, _l, _fp, _fp, _fp, _sz, _stream]),
+    "sed_event_mvdr_track_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "sed_event_mvdr_track": (_i, [_fp, _l, _fp, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _l, _i, _i, _i, _fp, _i, _d, _i, _i, _fp, _sz, _fp,
+                                  _fp, _fp, _l, _fp, _i, _i, _fp, _fp, _fp, _sz, _stream]),
+    "sed_event_mvdr_track_ring_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "sed_event_mvdr_track_ring": (_i, [_fp, _l, _l, _fp, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _l, _i, _i, _i, _fp, _i, _d, _i, _i, _fp,
+                                       _sz, _fp, _fp, _fp, _l, _fp, _i, _i, _fp, _fp, _fp, _sz, _stream]),
+    "sed_event_mvdr_quiet_track_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _l, _i]),
+    "sed_event_mvdr_quiet_track": (_i, [_fp, _l, _fp, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _l, _i, _i, _i, _fp, _i, _d, _i, _i, _i, _i,
+                                        _i, _i, _fp, _sz, _fp, _fp, _fp, _l, _fp, _fp, _i, _i, _fp, _fp, _fp, _sz, _stream]),
     "sed_pcen_workspace_bytes": (_sz, [_l, _i, _i]),
     "sed_pcen": (_i, [_fp, _l, _i, _i, _i, _fp, _i, _fp, _d, _f, _f, _f, _f, _f, _fp, _fp, _fp, _sz, _stream]),
     "sed_resample_workspace_bytes": (_sz, [_i]),

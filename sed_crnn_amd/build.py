@@ -64,10 +64,13 @@ NO_SCRATCH_KERNELS = {"wino.hip": ("conv3x3_wino_k",),
                       # weight kernel keeps its matrices in LDS so that its float64 solve needs no scratch either; the ring forms
                       # (live feeds) are the same bodies behind another frame load, and so are the covariance kernels of the frames
                       # before the onset and of the frames where the event's class is silent, whose weight kernel is the
-                      # weight kernel's text once more; the activity and the selection kernel are a few integers per lane
+                      # weight kernel's text once more; the activity and the selection kernel are a few integers per lane;
+                      # the tracked kernels are the weight body with its solves in a loop over the track blocks and the
+                      # apply body with the weight pointer taken per frame: the same hazards
                       "mvdr.hip": ("mvdr_cov_k", "mvdr_weights_k", "mvdr_apply_k", "mvdr_ring_cov_k", "mvdr_ring_apply_k", "mvdr_noise_k",
                                    "mvdr_ring_noise_k", "mvdr_quiet_own_k", "mvdr_quiet_k", "mvdr_quiet_weights_k", "mvdr_activity_k",
-                                   "mvdr_select_k"),
+                                   "mvdr_select_k", "mvdr_trk_weights_k", "mvdr_trk_quiet_weights_k", "mvdr_trk_apply_k",
+                                   "mvdr_trk_ring_apply_k"),
                       # PCEN: the powers of (1-b) travel by value and are indexed in a loop; a copy of them in scratch, or a spilled
                       # powf, would turn a bandwidth-bound pass into a latency-bound one without failing any test
                       "pcen.hip": ("pcen_pass_k", "pcen_carry_k"),

@@ -53,6 +53,15 @@
 // noise_frames) and mvdr_apply_k as it is.  An event whose Kn nearest candidates are eligible reads the frames of
 // sed_event_mvdr_noise in its order through the same code: the same bits.  All of it is integer and a function of the table and
 // the settings alone.
+//
+// The beam steered along the event's direction track: sed_event_mvdr_track / sed_event_mvdr_track_ring /
+// sed_event_mvdr_quiet_track.  The samples, the covariance launches above and the transform grid are untouched; with T = trk_len[e]
+// clamped to [0, Tm] and W = block_chunks, frame j is combined with the weights of track block b_j = min((j B / hop) / (32 W), T - 1),
+// steered at trk_dir[e][b_j] where T > 0 and that is a row of tau, else at dir.  mvdr_trk_weights_k / mvdr_trk_quiet_weights_k are the
+// weight body with ONE Cholesky factor per (event, bin) and the steering vector, the two solves and the normalisation per block
+// b < max(T, 1) — block b's C rows of w behind block b - 1's, an event's rows cpe C(C+1)/2 + C Tm; mvdr_trk_apply_k /
+// mvdr_trk_ring_apply_k are the apply body with the weight pointer taken per frame.  The overlap-add is the cross-fade between
+// consecutive blocks' beams.  A track whose every used row equals dir gives the untracked kernels' bits.
 #include <math.h>
 #include "common.h"
 #include "fft2048.h"
@@ -342,8 +351,11 @@ __global__ __launch_bounds__(MV_THREADS) void mvdr_quiet_k(const float* __restri
 // One text for two kernels (a macro, not a shared function: mvdr_weights_k must compile to what it was before its sibling
 // existed, and with its body in an inlined function it does not).  FRAMES: the frames behind an extracted event's weights —
 // mvdr_weights_k: its own 0 .. J, or the kn before its onset; mvdr_quiet_weights_k: those that
-// mvdr_select_k listed for it.
-#define MV_WEIGHTS_BODY(FRAMES)                                                                                                              \
+// mvdr_select_k listed for it.  The text is in five parts — the chunk sums and the trace, the steering vector, the silent bin, the
+// loading and the Cholesky factor, the two solves and the store — which the tracked kernels put together with the
+// steering vector, the silent bin and the solves inside a loop over the event's track blocks: one factor per (event, bin), a
+// pair of solves per block.
+#define MV_WB_SUM(FRAMES)                                                                                                                    \
     __shared__ double2 s_A[MV_MAX_TRI][MV_WT];                   /* the lower triangle of R + lambda I, then of its Cholesky factor */       \
     __shared__ double2 s_d[TD_MAX_CH][MV_WT];                                                                                                \
     __shared__ double2 s_v[TD_MAX_CH][MV_WT];                                                                                                \
@@ -370,19 +382,22 @@ __global__ __launch_bounds__(MV_THREADS) void mvdr_quiet_k(const float* __restri
     }                                                                                                                                        \
     double trace = 0.0;                                                                                                                      \
     _Pragma("unroll 1")                                                                                                                      \
-    for (int i = 0; i < C; ++i) trace += s_A[i * (i + 1) / 2 + i][tid].x;                                                                    \
-    const double* trow = tau + (long)ma.ev_dir[e] * C;           /* (0 <= dir < D: the event has samples) */                                 \
+    for (int i = 0; i < C; ++i) trace += s_A[i * (i + 1) / 2 + i][tid].x;
+#define MV_WB_STEER(DIR)                                                                                                                     \
+    const double* trow = tau + (long)DIR * C;                    /* (0 <= dir < D: the event has samples) */                                 \
     _Pragma("unroll 1")                                                                                                                      \
     for (int c = 0; c < C; ++c) {                                                                                                            \
         double sn, cs;                                                                                                                       \
         sincospi((double)k * trow[c] * (1.0 / MV_B), &sn, &cs);  /* 2 pi k tau / 2048 */                                                     \
         s_d[c][tid] = make_double2(cs, sn);                                                                                                  \
-    }                                                                                                                                        \
+    }
+#define MV_WB_SILENT(EXIT)                                                                                                                   \
     if (!(trace > 0.0)) {                                        /* digital silence (or NaN samples): the plain average */                   \
     _Pragma("unroll 1")                                                                                                                      \
         for (int c = 0; c < C; ++c) wout[(long)c * PHAT_SPEC + k] = make_float2((float)(s_d[c][tid].x / C), (float)(s_d[c][tid].y / C));     \
-        return;                                                                                                                              \
-    }                                                                                                                                        \
+        EXIT;                                                                                                                                \
+    }
+#define MV_WB_CHOL                                                                                                                           \
     const double lambda = loading * trace / C;                                                                                               \
     _Pragma("unroll 1")                                                                                                                      \
     for (int i = 0; i < C; ++i) {                                                                                                            \
@@ -410,7 +425,8 @@ __global__ __launch_bounds__(MV_THREADS) void mvdr_quiet_k(const float* __restri
             }                                                                                                                                \
             s_A[ri + j][tid] = make_double2(a.x * inv, a.y * inv);                                                                           \
         }                                                                                                                                    \
-    }                                                                                                                                        \
+    }
+#define MV_WB_SOLVE                                                                                                                          \
     /* ── L y = d, then L^H v = y ── */                                                                                                      \
     _Pragma("unroll 1")                                                                                                                      \
     for (int i = 0; i < C; ++i) {                                                                                                            \
@@ -444,6 +460,8 @@ __global__ __launch_bounds__(MV_THREADS) void mvdr_quiet_k(const float* __restri
     _Pragma("unroll 1")                                                                                                                      \
     for (int c = 0; c < C; ++c) wout[(long)c * PHAT_SPEC + k] = make_float2((float)(s_v[c][tid].x * scale), (float)(s_v[c][tid].y * scale));
 
+#define MV_WEIGHTS_BODY(FRAMES) MV_WB_SUM(FRAMES) MV_WB_STEER(ma.ev_dir[e]) MV_WB_SILENT(return) MV_WB_CHOL MV_WB_SOLVE
+
 __global__ __launch_bounds__(MV_WT) void mvdr_weights_k(float2* __restrict__ ws, const double* __restrict__ tau, double loading,
                                                         TdArgs ta, MvArgs ma) {
     MV_WEIGHTS_BODY(mv_uses_noise(ma, s0) ? ma.kn : (len + MV_B - 1) / MV_B + 1)
@@ -454,9 +472,69 @@ __global__ __launch_bounds__(MV_WT) void mvdr_quiet_weights_k(float2* __restrict
     MV_WEIGHTS_BODY(mv_quiet_frames(ma, e) > 0 ? mv_quiet_frames(ma, e) : (len + MV_B - 1) / MV_B + 1)
 }
 
-template <bool RING>
+// ───────────────────────── DESIGN 5y: the beam steered along the event's direction track ─────────────────────────
+// The track of sed_event_doa_track: trk_len [E] blocks of 32 W located frames an event, their directions in trk_dir [E][Tm].  An
+// event's workspace rows are then cpe x C(C+1)/2 partials and C rows of w for each of Tm blocks, block b's behind block b - 1's.
+struct MvTrack {
+    const int *len, *dir;                        // [E], [E][Tm]
+    int W, Tm;                                   // block_chunks; the columns of dir
+};
+
+// the blocks of event e that the rule reads: trk_len clamped to [0, Tm]
+__device__ __forceinline__ int mv_trk_blocks(const MvTrack& tk, long e) {
+    const int T = tk.len[e];
+    return T < 0 ? 0 : T > tk.Tm ? tk.Tm : T;
+}
+
+// THE RULE, device side (localize.mvdr_frame_blocks; tests/mvdr_track_ref.py): the centre of frame j is sample j B of the event,
+// which lies in located frame j B / hop, and that in track block (j B / hop) / (32 W); frame J and the short tail that joins the
+// last block take block T - 1.  T = 0: block 0, whose weights are steered at dir
+__device__ __forceinline__ int mv_trk_frame_block(const MvTrack& tk, int hop, int T, int j) {
+    const unsigned b = ((unsigned)j * MV_B / (unsigned)hop) / (unsigned)(TD_CHUNK * tk.W);     // (j B < len + B < 2^32: mv_sizes_ok)
+    return T < 1 ? 0 : b < (unsigned)(T - 1) ? (int)b : T - 1;
+}
+
+// the direction block b < max(T, 1) is steered at: its row of the track where that names a direction, else the event's dir — a
+// silent block (-1), an event without a track (T = 0) and a row outside [0, D) never index tau
+__device__ __forceinline__ int mv_trk_dir(const MvArgs& ma, const MvTrack& tk, long e, int T, int b) {
+    int d = ma.ev_dir[e];
+    if (T > 0) {
+        const int t = tk.dir[e * tk.Tm + b];
+        if (t >= 0 && t < ma.D) d = t;
+    }
+    return d;
+}
+
+// mvdr_trk_weights_k / mvdr_trk_quiet_weights_k: the parts of the weight body with ONE factor per (event, bin) and the steering
+// vector, the two solves and the normalisation once per block — the float64 expressions of mvdr_weights_k in their order, so that a
+// block steered at dir holds mvdr_weights_k's bits.  A silent bin (trace not > 0) gets d_b / C in every block.
+#define MV_TRK_WEIGHTS_BODY(FRAMES)                                                                                                          \
+    MV_WB_SUM(FRAMES)                                                                                                                        \
+    const int nblk = mv_trk_blocks(tk, e);                                                                                                   \
+    if (trace > 0.0) { MV_WB_CHOL }                                                                                                          \
+    _Pragma("unroll 1")                                                                                                                      \
+    for (int b = 0; b < (nblk > 1 ? nblk : 1); ++b, wout += (long)C * PHAT_SPEC) {                                                           \
+        MV_WB_STEER(mv_trk_dir(ma, tk, e, nblk, b))                                                                                          \
+        MV_WB_SILENT(continue)                                                                                                               \
+        MV_WB_SOLVE                                                                                                                          \
+    }
+
+__global__ __launch_bounds__(MV_WT) void mvdr_trk_weights_k(float2* __restrict__ ws, const double* __restrict__ tau, double loading,
+                                                            TdArgs ta, MvArgs ma, MvTrack tk) {
+    MV_TRK_WEIGHTS_BODY(mv_uses_noise(ma, s0) ? ma.kn : (len + MV_B - 1) / MV_B + 1)
+}
+
+__global__ __launch_bounds__(MV_WT) void mvdr_trk_quiet_weights_k(float2* __restrict__ ws, const double* __restrict__ tau, double loading,
+                                                                  TdArgs ta, MvArgs ma, MvTrack tk) {
+    MV_TRK_WEIGHTS_BODY(mv_quiet_frames(ma, e) > 0 ? mv_quiet_frames(ma, e) : (len + MV_B - 1) / MV_B + 1)
+}
+
+// TRK (mvdr_trk_apply_k, mvdr_trk_ring_apply_k): frame j is combined with the weights of its track block, the rows at
+// wts + b_j C PHAT_SPEC; nothing else differs, and the sqrt-Hann overlap-add cross-fades from one block's beam to the next
+template <bool RING, bool TRK = false>
 __device__ __forceinline__ void mv_apply_body(const float* __restrict__ pcm, const uint32_t* __restrict__ tables,
-                                              const float2* __restrict__ ws, float* __restrict__ audio, TdArgs ta, MvArgs ma) {
+                                              const float2* __restrict__ ws, float* __restrict__ audio, TdArgs ta, MvArgs ma,
+                                              MvTrack tk = MvTrack{}) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x;
     const long e = ta.e0 + blockIdx.y;
@@ -486,6 +564,7 @@ __device__ __forceinline__ void mv_apply_body(const float* __restrict__ pcm, con
     float* scr = wscr + half * LM_SCR;
     const float2* wts = ws + ((long)blockIdx.y * ma.rows + (long)ma.cpe * T) * PHAT_SPEC;        // [C][PHAT_SPEC] w
     float* dst = audio + ma.audio_start[e];
+    const int nblk = TRK ? mv_trk_blocks(tk, e) : 0;             // the event's track blocks
     __syncthreads();                                             // the tables are in LDS
 
     // Step j: the transforming waves turn frame j into spectra while wave nfw turns Y_{j-1} into the windowed frame j - 1; after
@@ -516,10 +595,12 @@ __device__ __forceinline__ void mv_apply_body(const float* __restrict__ pcm, con
             }
         }
         if (j <= b1) {
+            const float2* wj = wts;
+            if (TRK) wj += (long)mv_trk_frame_block(tk, ta.hop, nblk, j) * C * PHAT_SPEC;
             for (int k = tid; k <= LM_N; k += MV_THREADS) {
                 float2 y = make_float2(0.f, 0.f);
                 for (int c = 0; c < C; ++c) {                    // conj(w) x, ascending c
-                    const float2 w = wts[(long)c * PHAT_SPEC + k], x = s_spec[c * PHAT_SPEC + k];
+                    const float2 w = wj[(long)c * PHAT_SPEC + k], x = s_spec[c * PHAT_SPEC + k];
                     y.x += w.x * x.x + w.y * x.y;
                     y.y += w.x * x.y - w.y * x.x;
                 }
@@ -542,6 +623,18 @@ __global__ __launch_bounds__(MV_THREADS) void mvdr_ring_apply_k(const float* __r
     mv_apply_body<true>(ring, tables, ws, audio, ta, ma);
 }
 
+__global__ __launch_bounds__(MV_THREADS) void mvdr_trk_apply_k(const float* __restrict__ pcm, const uint32_t* __restrict__ tables,
+                                                               const float2* __restrict__ ws, float* __restrict__ audio, TdArgs ta, MvArgs ma,
+                                                               MvTrack tk) {
+    mv_apply_body<false, true>(pcm, tables, ws, audio, ta, ma, tk);
+}
+
+__global__ __launch_bounds__(MV_THREADS) void mvdr_trk_ring_apply_k(const float* __restrict__ ring, const uint32_t* __restrict__ tables,
+                                                                    const float2* __restrict__ ws, float* __restrict__ audio, TdArgs ta,
+                                                                    MvArgs ma, MvTrack tk) {
+    mv_apply_body<true, true>(ring, tables, ws, audio, ta, ma, tk);
+}
+
 // rows of 1026 float2 per event: the chunk partials of every entry of the triangle, then w
 long mv_chunks(int max_frames, int hop) {
     const long J = ((long)max_frames * hop + MV_B - 1) / MV_B;   // no event has more output blocks
@@ -554,6 +647,8 @@ long mv_slots(int max_frames, int hop, int kn) {
     return own > nz ? own : nz;
 }
 size_t mv_event_bytes(int C, long cpe) { return ((size_t)cpe * (C * (C + 1) / 2) + C) * TD_ROW_BYTES; }
+// ... with the weights of Tm track blocks behind the partials
+size_t mv_trk_event_bytes(int C, long cpe, int Tm) { return ((size_t)cpe * (C * (C + 1) / 2) + (size_t)C * Tm) * TD_ROW_BYTES; }
 size_t mv_cov_lds(int C, int batch) {
     return ((size_t)MV_TAB_WORDS + (size_t)C * PHAT_SPEC * 2 + (size_t)((C + 1) / 2) * MV_FFT_SCR + (size_t)batch * PHAT_SPEC * 2) * sizeof(float);
 }
@@ -567,6 +662,9 @@ bool mv_sizes_ok(int R, int channels, int max_frames, int hop) {
 
 #define MV_MAX_NOISE 256                          // localize.MVDR: noise_blocks
 #define MV_MAX_GUARD 64                           //                noise_guard
+#define MV_MAX_TRK_W 64                           // localize.DirectionTrack: block_chunks (doatrack.hip: TRK_MAX_W)
+#define MV_MAX_TRK_BLOCKS 256                     //                          the blocks of an event (doatrack.hip: TRK_MAX_BLOCKS)
+bool mv_trk_sizes_ok(int Tm) { return Tm >= 1 && Tm <= MV_MAX_TRK_BLOCKS; }
 
 // ───────────────────────── DESIGN 5w: the noise frames where the event's class is silent ─────────────────────────
 #define MV_MAX_SEARCH 1024                        // localize.MVDR: noise_search
@@ -701,14 +799,18 @@ struct MvTables { const double* tau; double loading; const void* tables; size_t 
 // kn noise frames that end guard blocks before the onset, and which events used them; entry: one of the noise entries,
 // which must be given frames_out
 struct MvNoise { int kn, guard; int* frames_out; bool entry; };
+// the track of a track entry — W = block_chunks, Tm = track_slots, trk_len [E], trk_dir [E][Tm]
+struct MvTrackIn { int W, Tm; const int *len, *dir; };
 
 // what all entries do once the events and the recordings are checked.  kn = 0 (sed_event_mvdr, sed_event_mvdr_ring, or a noise
 // entry asked for no noise frames): three launches per slice, and the noise entries' frames_out is zeroed
 // qz (sed_event_mvdr_quiet; linear only): the mask lies between the table and the partials, the selection runs once over
 // the whole table, and a slice is own covariance, quiet covariance, weights, apply with the quiet kernels
+// trk (the track entries): the covariance launches as they are, then the tracked weight and apply kernels on rows of
+// Tm weight sets an event; without it exactly the launches above
 template <bool RING>
 int mv_run(const char* who, const RecSource& src, const EvTable& ev, const MvTables& mt, const MvNoise& nz, const BeamOut& out,
-           void* workspace, size_t workspace_bytes, void* stream, const MvQuiet* qz = nullptr) {
+           void* workspace, size_t workspace_bytes, void* stream, const MvQuiet* qz = nullptr, const MvTrackIn* trk = nullptr) {
     const int kn = nz.kn;
     const long E = ev.E;
     if (qz) SED_TRY(mq_check(who, ev, kn, nz.guard, nz.frames_out, *qz));
@@ -716,6 +818,11 @@ int mv_run(const char* who, const RecSource& src, const EvTable& ev, const MvTab
     SED_REQUIRE(kn >= 0 && kn <= MV_MAX_NOISE, "%s: noise_blocks must be in [0, %d], got %d", who, MV_MAX_NOISE, kn);
     SED_REQUIRE(nz.guard >= 0 && nz.guard <= MV_MAX_GUARD, "%s: noise_guard must be in [0, %d], got %d", who, MV_MAX_GUARD, nz.guard);
     SED_REQUIRE(!nz.entry || E == 0 || nz.frames_out, "%s: null pointer (noise_frames_out)", who);
+    if (trk) {
+        SED_REQUIRE(trk->W >= 1 && trk->W <= MV_MAX_TRK_W, "%s: block_chunks must be in [1, %d], got %d", who, MV_MAX_TRK_W, trk->W);
+        SED_REQUIRE(mv_trk_sizes_ok(trk->Tm), "%s: track_slots must be in [1, %d], got %d", who, MV_MAX_TRK_BLOCKS, trk->Tm);
+        SED_REQUIRE(E == 0 || (trk->len && trk->dir), "%s: null pointer (trk_len or trk_dir)", who);
+    }
     SED_REQUIRE(mt.loading >= 1e-6 && mt.loading <= 1e6, "%s: loading must be in [1e-6, 1e6], got %g", who, mt.loading);
     SED_REQUIRE(out.total >= 0, "%s: a total of %ld samples", who, out.total);
     SED_REQUIRE(E == 0 || (mt.tau && out.audio_len && out.audio_start), "%s: null pointer (tau, audio_len or audio_start)", who);
@@ -728,7 +835,7 @@ int mv_run(const char* who, const RecSource& src, const EvTable& ev, const MvTab
     if (E == 0 || out.total == 0) return 0;                      // nothing to launch (frames_out is not written: no event is extracted)
     const int C = src.C, T = C * (C + 1) / 2;
     const long cpe = mv_slots(ev.max_frames, ev.hop, kn);
-    const size_t per_event = mv_event_bytes(C, cpe);
+    const size_t per_event = trk ? mv_trk_event_bytes(C, cpe, trk->Tm) : mv_event_bytes(C, cpe);
     SED_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0, "%s: the workspace must be a 16-byte aligned device buffer", who);
     SED_REQUIRE(workspace_bytes >= tab + per_event, "%s: workspace of %zu bytes, at least %zu needed (one event)", who, workspace_bytes,
                 tab + per_event);
@@ -751,8 +858,10 @@ int mv_run(const char* who, const RecSource& src, const EvTable& ev, const MvTab
     if (qz) SED_TRY(mq_select(who, src, ev, kn, nz.guard, nz.frames_out, *qz, workspace, s));
     const auto cov_k = RING ? mvdr_ring_cov_k : qz ? mvdr_quiet_own_k : mvdr_cov_k;
     const auto apply_k = RING ? mvdr_ring_apply_k : mvdr_apply_k;
+    const auto trk_apply_k = RING ? mvdr_trk_ring_apply_k : mvdr_trk_apply_k;
     hipError_t err = hipFuncSetAttribute((const void*)cov_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MV_LDS_MAX);
-    if (err == hipSuccess) err = hipFuncSetAttribute((const void*)apply_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MV_LDS_MAX);
+    if (err == hipSuccess) err = hipFuncSetAttribute(trk ? (const void*)trk_apply_k : (const void*)apply_k,
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)MV_LDS_MAX);
     const auto noise_k = RING ? mvdr_ring_noise_k : mvdr_noise_k;
     if (err == hipSuccess && kn > 0) err = hipFuncSetAttribute((const void*)noise_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MV_LDS_MAX);
     if (err == hipSuccess && qz) err = hipFuncSetAttribute((const void*)mvdr_quiet_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MV_LDS_MAX);
@@ -762,8 +871,9 @@ int mv_run(const char* who, const RecSource& src, const EvTable& ev, const MvTab
         if (err != hipSuccess) { sed_set_error("%s: hipMemsetAsync: %s", who, hipGetErrorString(err)); return (int)err; }
     }
     TdArgs ta = td_args(src, ev, workspace);
-    const MvArgs ma{ev.dir, ev.loc, ev.D, out.audio_len, out.audio_start, out.total, (int)cpe, (int)(cpe * T + C), batch, kn, nz.guard,
-                    nz.frames_out};
+    const MvArgs ma{ev.dir, ev.loc, ev.D, out.audio_len, out.audio_start, out.total, (int)cpe, (int)(cpe * T + C * (trk ? trk->Tm : 1)), batch,
+                    kn, nz.guard, nz.frames_out};
+    const MvTrack tk = trk ? MvTrack{trk->len, trk->dir, trk->W, trk->Tm} : MvTrack{};
     const uint32_t* tables = (const uint32_t*)mt.tables;
     float2* part = (float2*)((char*)workspace + tab);
     for (long e0 = 0; e0 < E; e0 += slice) {
@@ -778,6 +888,14 @@ int mv_run(const char* who, const RecSource& src, const EvTable& ev, const MvTab
             noise_k<<<dim3((unsigned)mv_noise_chunks(kn), (unsigned)ta.n_ev), MV_THREADS, lds_cov, s>>>(src.x, tables, part, ta, ma);
             SED_LAUNCH_CHECK("mvdr (noise covariance)");
         }
+        if (trk) {
+            (qz ? mvdr_trk_quiet_weights_k : mvdr_trk_weights_k)<<<dim3((LM_N + MV_WT) / MV_WT, (unsigned)ta.n_ev), MV_WT, 0, s>>>(
+                part, mt.tau, mt.loading, ta, ma, tk);
+            SED_LAUNCH_CHECK("mvdr (tracked weights)");
+            trk_apply_k<<<dim3(runs, (unsigned)ta.n_ev), MV_THREADS, lds_apply, s>>>(src.x, tables, part, out.audio, ta, ma, tk);
+            SED_LAUNCH_CHECK("mvdr (tracked apply)");
+            continue;
+        }
         (qz ? mvdr_quiet_weights_k : mvdr_weights_k)<<<dim3((LM_N + MV_WT) / MV_WT, (unsigned)ta.n_ev), MV_WT, 0, s>>>(part, mt.tau, mt.loading, ta, ma);
         SED_LAUNCH_CHECK("mvdr (weights)");
         apply_k<<<dim3(runs, (unsigned)ta.n_ev), MV_THREADS, lds_apply, s>>>(src.x, tables, part, out.audio, ta, ma);
@@ -789,9 +907,9 @@ int mv_run(const char* who, const RecSource& src, const EvTable& ev, const MvTab
 // an entry: the events and the recordings checked, then the launches
 template <bool RING>
 int mv_entry(const char* who, RecSource src, const EvTable& ev, const MvTables& mt, const MvNoise& nz, const BeamOut& out, void* workspace,
-             size_t workspace_bytes, void* stream, const MvQuiet* qz = nullptr) {
+             size_t workspace_bytes, void* stream, const MvQuiet* qz = nullptr, const MvTrackIn* trk = nullptr) {
     SED_TRY(beam_source<RING>(who, src, ev));
-    return mv_run<RING>(who, src, ev, mt, nz, out, workspace, workspace_bytes, stream, qz);
+    return mv_run<RING>(who, src, ev, mt, nz, out, workspace, workspace_bytes, stream, qz, trk);
 }
 
 // sed_event_quiet_frames: the activity and the selection alone; no sample is read
@@ -912,4 +1030,66 @@ extern "C" int sed_event_mvdr_quiet(const float* pcm, long pcm_len, const long* 
                            {ev_rec, ev_onset, ev_offset, ev_peak_frame, ev_dir, ev_loc_frames, E, time_factor, hop, max_frames, D},
                            {tau, loading, tables, tables_bytes}, {noise_blocks, noise_guard, noise_frames_out, true},
                            {audio_len, audio_start, audio, audio_total}, workspace, workspace_bytes, stream, &qz);
+}
+
+// ── DESIGN 5y: the beam steered along the event's direction track; noise_blocks = 0 is the own-frames form ──
+extern "C" size_t sed_event_mvdr_track_workspace_bytes(int R, int channels, int max_frames, int hop, int noise_blocks, int track_slots) {
+    if (!mv_sizes_ok(R, channels, max_frames, hop) || noise_blocks < 0 || noise_blocks > MV_MAX_NOISE || !mv_trk_sizes_ok(track_slots)) return 0;
+    return rec_table_bytes(R, channels) + mv_trk_event_bytes(channels, mv_slots(max_frames, hop, noise_blocks), track_slots);
+}
+
+extern "C" size_t sed_event_mvdr_track_ring_workspace_bytes(int R, int channels, int max_frames, int hop, int noise_blocks, int track_slots) {
+    if (!mv_sizes_ok(R, channels, max_frames, hop) || noise_blocks < 0 || noise_blocks > MV_MAX_NOISE || !mv_trk_sizes_ok(track_slots)) return 0;
+    return rec_ring_table_bytes(R) + mv_trk_event_bytes(channels, mv_slots(max_frames, hop, noise_blocks), track_slots);
+}
+
+extern "C" size_t sed_event_mvdr_quiet_track_workspace_bytes(int R, int channels, int max_frames, int hop, int noise_blocks, long mask_frames,
+                                                             int track_slots) {
+    if (!mv_sizes_ok(R, channels, max_frames, hop) || !mq_sizes_ok(R, mask_frames, noise_blocks) || !mv_trk_sizes_ok(track_slots)) return 0;
+    return rec_table_bytes(R, channels) + mq_mask_bytes(R, mask_frames) +
+           mv_trk_event_bytes(channels, mv_slots(max_frames, hop, noise_blocks), track_slots);
+}
+
+extern "C" int sed_event_mvdr_track(const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const int* ev_rec,
+                                    const int* ev_onset, const int* ev_offset, const int* ev_peak_frame, const int* ev_dir,
+                                    const int* ev_loc_frames, long E, int time_factor, int hop, int max_frames, const double* tau, int D,
+                                    double loading, int noise_blocks, int noise_guard, const void* tables, size_t tables_bytes,
+                                    const int* audio_len, const long* audio_start, float* audio, long audio_total, int* noise_frames_out,
+                                    int block_chunks, int track_slots, const int* trk_len, const int* trk_dir, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+    const MvTrackIn trk{block_chunks, track_slots, trk_len, trk_dir};
+    return mv_entry<false>("mvdr_track", {pcm, false, 0, pcm_len, R, channels, clips_host},
+                           {ev_rec, ev_onset, ev_offset, ev_peak_frame, ev_dir, ev_loc_frames, E, time_factor, hop, max_frames, D},
+                           {tau, loading, tables, tables_bytes}, {noise_blocks, noise_guard, noise_frames_out, true},
+                           {audio_len, audio_start, audio, audio_total}, workspace, workspace_bytes, stream, nullptr, &trk);
+}
+
+extern "C" int sed_event_mvdr_track_ring(const float* ring, long ring_len, long cap, const long* n_host, int R, int channels,
+                                         const int* ev_rec, const int* ev_onset, const int* ev_offset, const int* ev_peak_frame,
+                                         const int* ev_dir, const int* ev_loc_frames, long E, int time_factor, int hop, int max_frames,
+                                         const double* tau, int D, double loading, int noise_blocks, int noise_guard, const void* tables,
+                                         size_t tables_bytes, const int* audio_len, const long* audio_start, float* audio,
+                                         long audio_total, int* noise_frames_out, int block_chunks, int track_slots, const int* trk_len,
+                                         const int* trk_dir, void* workspace, size_t workspace_bytes, void* stream) {
+    const MvTrackIn trk{block_chunks, track_slots, trk_len, trk_dir};
+    return mv_entry<true>("mvdr_track_ring", {ring, true, cap, ring_len, R, channels, n_host},
+                          {ev_rec, ev_onset, ev_offset, ev_peak_frame, ev_dir, ev_loc_frames, E, time_factor, hop, max_frames, D},
+                          {tau, loading, tables, tables_bytes}, {noise_blocks, noise_guard, noise_frames_out, true},
+                          {audio_len, audio_start, audio, audio_total}, workspace, workspace_bytes, stream, nullptr, &trk);
+}
+
+extern "C" int sed_event_mvdr_quiet_track(const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const int* ev_rec,
+                                          const int* ev_cls, const int* ev_onset, const int* ev_offset, const int* ev_peak_frame,
+                                          const int* ev_dir, const int* ev_loc_frames, long E, int time_factor, int hop, int max_frames,
+                                          const double* tau, int D, double loading, int noise_blocks, int noise_guard, int n_classes,
+                                          int noise_search, int noise_min, int exclude_any, const void* tables, size_t tables_bytes,
+                                          const int* audio_len, const long* audio_start, float* audio, long audio_total,
+                                          int* noise_frames_out, int* noise_sel_out, int block_chunks, int track_slots, const int* trk_len,
+                                          const int* trk_dir, void* workspace, size_t workspace_bytes, void* stream) {
+    const MvQuiet qz{ev_cls, n_classes, noise_search, noise_min, exclude_any, noise_sel_out};
+    const MvTrackIn trk{block_chunks, track_slots, trk_len, trk_dir};
+    return mv_entry<false>("mvdr_quiet_track", {pcm, false, 0, pcm_len, R, channels, clips_host},
+                           {ev_rec, ev_onset, ev_offset, ev_peak_frame, ev_dir, ev_loc_frames, E, time_factor, hop, max_frames, D},
+                           {tau, loading, tables, tables_bytes}, {noise_blocks, noise_guard, noise_frames_out, true},
+                           {audio_len, audio_start, audio, audio_total}, workspace, workspace_bytes, stream, &qz, &trk);
 }

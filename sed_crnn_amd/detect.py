@@ -453,6 +453,9 @@ class EventDetector:
         if extract is not None and not isinstance(localize, DOA):
             raise ValueError(f"extract={type(extract).__name__}(...) points the array at every event's direction and needs "
                              f"localize=sed.DOA(positions, grid), got localize={localize!r}")
+        if getattr(extract, "follow_track", False) and localize.track is None:
+            raise ValueError("extract=sed.MVDR(follow_track=True) steers the beam along every event's direction track and needs "
+                             "localize=sed.DOA(positions, grid, track=sed.DirectionTrack(...))")
         self.extract_settings = extract         # per-event audio: a delay-and-sum or an MVDR beam (5s), or None
         if localize is not None and not isinstance(localize, (TDOA, DOA)):
             raise TypeError(f"localize must be None, a TDOA(...) or a DOA(...) settings object, got {type(localize).__name__}")

@@ -22,7 +22,9 @@ _ENTRY = {("tdoa", False): "sed_event_tdoa", ("tdoa", True): "sed_event_tdoa_rin
           ("delay_sum", False): "sed_event_beamform", ("delay_sum", True): "sed_event_beamform_ring",
           ("mvdr", False): "sed_event_mvdr", ("mvdr", True): "sed_event_mvdr_ring",
           ("mvdr_noise", False): "sed_event_mvdr_noise", ("mvdr_noise", True): "sed_event_mvdr_noise_ring",
-          ("mvdr_quiet", False): "sed_event_mvdr_quiet"}
+          ("mvdr_quiet", False): "sed_event_mvdr_quiet",
+          ("mvdr_track", False): "sed_event_mvdr_track", ("mvdr_track", True): "sed_event_mvdr_track_ring",
+          ("mvdr_quiet_track", False): "sed_event_mvdr_quiet_track"}
 _LOCATED = ("onset", "offset", "peak_frame", "dir", "loc_frames")
 
 
@@ -358,11 +360,12 @@ def _mvdr_tables(device_index):
     return blob[:_LM_OFF_ENT].clone()
 
 
-def _extract(src, kind, col, E, tf, hop, max_frames, D, settings, ws_bytes, Kn=0):
+def _extract(src, kind, col, E, tf, hop, max_frames, D, settings, ws_bytes, Kn=0, track=()):
     """the two calls behind the four beam functions: the spans, ONE blocking read of the total (8 bytes) to size ``audio``, the
     beam ``kind``.  ``settings``: what the beam's C entry takes between ``max_frames`` and the spans; ``mvdr_noise``
     adds ``noise_frames`` int32 [E] to the dict, ``mvdr_quiet`` (``Kn``: its noise_blocks) that and ``noise_sel`` int32
-    [E, Kn], and its C entry takes the ``cls`` column behind ``rec``"""
+    [E, Kn], and its C entry takes the ``cls`` column behind ``rec``; the track forms are ``mvdr_noise`` and ``mvdr_quiet``
+    with ``track`` — block_chunks, Tm and the two columns — behind their outputs, and ``noise_frames`` in the dict only with Kn >= 1"""
     dev = src.x.device
     out = {"audio_start": torch.empty(E, dtype=torch.int64, device=dev), "audio_len": torch.empty(E, dtype=torch.int32, device=dev)}
     total = torch.empty(1, dtype=torch.int64, device=dev)
@@ -374,15 +377,17 @@ def _extract(src, kind, col, E, tf, hop, max_frames, D, settings, ws_bytes, Kn=0
     n_total = int(total.item())                                       # the one blocking read
     out["audio"] = torch.empty(n_total, device=dev)
     noise = []
-    if kind in ("mvdr_noise", "mvdr_quiet"):
-        out["noise_frames"] = torch.zeros(E, dtype=torch.int32, device=dev)      # (a call that extracts nothing launches nothing)
-        noise = [ptr(out["noise_frames"])]
-    if kind == "mvdr_quiet":
+    if kind in ("mvdr_noise", "mvdr_quiet", "mvdr_track", "mvdr_quiet_track"):
+        frames = torch.zeros(E, dtype=torch.int32, device=dev)        # (a call that extracts nothing launches nothing)
+        noise = [ptr(frames)]
+        if Kn or kind != "mvdr_track":                                # (the own-frames track form returns the dict of sed_event_mvdr)
+            out["noise_frames"] = frames
+    if kind in ("mvdr_quiet", "mvdr_quiet_track"):
         out["noise_sel"] = torch.full((E, Kn), -1, dtype=torch.int32, device=dev)
         noise.append(ptr(out["noise_sel"]))
         cols = cols[:1] + [ptr(col["cls"])] + cols[1:]
     check(getattr(lib(), name)(*src.head, *cols, E, tf, hop, max_frames, *settings, ptr(out["audio_len"]), ptr(out["audio_start"]),
-                               ptr(out["audio"]), n_total, *noise, ptr(ws), ws.numel(), stream_ptr()), name)
+                               ptr(out["audio"]), n_total, *noise, *track, ptr(ws), ws.numel(), stream_ptr()), name)
     return out
 
 
@@ -437,20 +442,35 @@ def _mvdr(who, src, events, tf, hop, doa, mvdr, sr, max_workspace_bytes, n_class
         raise TypeError(f"{who} takes the beam settings as a sed.MVDR(...) object, got {type(mvdr).__name__}")
     R, nc, dev, max_frames = src.R, src.nc, src.x.device, doa.max_frames
     quiet = _quiet_settings(who, mvdr, n_classes) if mvdr.quiet else []
+    follow = mvdr.follow_track
+    if follow and (doa.track is None or "trk_len" not in events or "trk_dir" not in events):
+        raise ValueError(f"{who} with sed.MVDR(follow_track=True) steers along the direction track: it needs sed.DOA(..., track="
+                         f"sed.DirectionTrack(...)) and the events' trk_len and trk_dir columns as event_doa returns them with track=")
     col, E = _cols(src, events, _LOCATED + (("cls",) if mvdr.quiet else ()))
+    track = []
+    if follow:                                                                   #  W, Tm and the two columns
+        Tm = doa.track.max_blocks(max_frames)
+        tlen, tdir = events["trk_len"].to(dev, torch.int32).contiguous(), events["trk_dir"].to(dev, torch.int32).contiguous()
+        if tlen.shape != (E,) or tdir.shape != (E, Tm):
+            raise ValueError(f"{who}: trk_len must be [E] = [{E}] and trk_dir [E, Tm] = [{E}, {Tm}] (track= of the same sed.DOA), got "
+                             f"{tuple(tlen.shape)} and {tuple(tdir.shape)}")
+        track = [doa.track.block_chunks, Tm, ptr(tlen), ptr(tdir)]
     if E == 0:
         return _mvdr_empty(dev, mvdr)
     Kn = mvdr.noise_blocks
     kind = "mvdr" if not Kn else "mvdr_quiet" if mvdr.quiet else "mvdr_noise"
     noise = [Kn, mvdr.noise_guard] + quiet if Kn else []                         # what the entry takes behind loading
+    if follow:                                                                   # the track entries take noise_blocks = 0 too
+        kind = "mvdr_quiet_track" if mvdr.quiet else "mvdr_track"
+        noise = [Kn, mvdr.noise_guard] + quiet
     name = _ENTRY[kind, src.ring] + "_workspace_bytes"
     if mvdr.quiet:                                                               # the mask lies behind the table, once per call
         frames = _mask_frames(src, tf, hop)
         need_tab = lib().sed_event_quiet_frames_workspace_bytes(R, nc, frames, Kn)
-        need_one = getattr(lib(), name)(R, nc, max_frames, hop, Kn, frames)      # the table, the mask and one event
+        need_one = getattr(lib(), name)(R, nc, max_frames, hop, Kn, frames, *track[1:2])     # the table, the mask and one event
     else:
         need_tab = _table_bytes(src)
-        need_one = getattr(lib(), name)(R, nc, max_frames, hop, *noise[:1])      # the recording table and one event
+        need_one = getattr(lib(), name)(R, nc, max_frames, hop, *noise[:1], *track[1:2])     # the recording table and one event
     if need_one == 0 or need_tab == 0:
         raise ValueError(f"{name} refuses R={R}, channels={nc}, max_frames={max_frames}, hop={hop}")
     key = (dev.index or 0, float(sr))
@@ -460,7 +480,7 @@ def _mvdr(who, src, events, tf, hop, doa, mvdr, sr, max_workspace_bytes, n_class
     tables = _mvdr_tables(dev.index or 0)
     ws_bytes = min(need_tab + E * (need_one - need_tab), max(need_one, int(max_workspace_bytes)))
     return _extract(src, kind, col, E, tf, hop, max_frames, tau.shape[0],
-                    [ptr(tau), tau.shape[0], mvdr.loading, *noise, ptr(tables), tables.numel() * 4], ws_bytes, Kn)
+                    [ptr(tau), tau.shape[0], mvdr.loading, *noise, ptr(tables), tables.numel() * 4], ws_bytes, Kn, track)
 
 
 def event_quiet_frames(clips, channels, events, time_factor, doa, mvdr, n_classes, hop=HOP):
@@ -558,7 +578,14 @@ def event_mvdr(pcm, clips, channels, events, time_factor, doa, mvdr, sr=SR, hop=
     slicing.  The dict gains ``noise_frames`` int32 [E], the number of frames used (0: fewer than ``noise_min`` were found and
     the event keeps its own frames, bit for bit what ``Kn = 0`` gives), and ``noise_sel`` int32 [E, Kn], their candidates q
     in summation order, -1 behind them (``event_quiet_frames`` returns the two alone).  An event whose Kn nearest candidates
-    are all eligible gets the audio of ``noise_select="fixed"``, bit for bit."""
+    are all eligible gets the audio of ``noise_select="fixed"``, bit for bit.
+
+    ``sed.MVDR(..., follow_track=True)`` (``sed_event_mvdr_track`` / ``sed_event_mvdr_quiet_track``): ``doa`` must have
+    ``track=`` and the events the ``trk_len`` / ``trk_dir`` columns ``event_doa`` then returns (else ValueError).  The samples, the
+    covariance of the settings above and the returned dict are unchanged; frame j of an event is combined with the weights of
+    track block ``localize.mvdr_frame_blocks(...)[j]``, steered at that block's ``trk_dir`` — ``dir`` for a silent block, a row
+    outside the grid and an event with ``trk_len = 0`` — one weight set per block from the event's one covariance.  A track
+    whose every used row equals ``dir`` gives the audio of ``follow_track=False``, bit for bit."""
     _need_pcm("event_mvdr", pcm)
     nc, tf, hop = _beam_sizes("event_mvdr", channels, time_factor, hop)
     return _mvdr("event_mvdr", _linear_source(pcm, clips, nc), events, tf, hop, doa, mvdr, sr, max_workspace_bytes, n_classes)
@@ -571,7 +598,8 @@ def event_mvdr_ring(ring, cap, n, channels, events, time_factor, doa, mvdr, sr=S
     ``max_workspace_bytes`` as ``event_mvdr``.  An extracted event gets, bit for bit, what ``event_mvdr`` gives on the feed's
     samples ``[0, n)`` laid out linearly, wherever the ring wraps and whatever the slicing; a sample the ring no longer holds
     reads as 0.  Returns what ``event_mvdr`` returns, with the same single 8-byte read; ``E == 0`` returns empty tensors without
-    a launch."""
+    a launch.  ``sed.MVDR(..., follow_track=True)`` (``sed_event_mvdr_track_ring``) as in ``event_mvdr``, with the
+    ``trk_len`` / ``trk_dir`` of ``event_doa_ring``."""
     if getattr(mvdr, "quiet", False):
         raise NotImplementedError("event_mvdr_ring: sed.MVDR(noise_select='quiet') has no ring form yet; extract on the recording (event_mvdr)")
     _need_ring("event_mvdr_ring", ring)

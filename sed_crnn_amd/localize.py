@@ -488,7 +488,13 @@ class MVDR:
     source, an event longer than ``max_frames`` and an event near the start of its recording then still get a covariance
     without the target in it.  ``noise_search = 0`` means ``min(1024, 4 Kn)`` and is stored resolved; ``noise_frames`` in the
     results is the number of frames used and ``noise_sel`` [E, Kn] lists their q in summation order (-1 behind them).  An
-    event whose Kn nearest candidates are all eligible gets the audio of ``noise_select="fixed"``, bit for bit.  Offline only."""
+    event whose Kn nearest candidates are all eligible gets the audio of ``noise_select="fixed"``, bit for bit.  Offline only.
+
+    ``follow_track=True`` (needs ``DOA(..., track=DirectionTrack(...))``): the beam follows a source that moves while it
+    sounds.  The samples, the covariance and the transform grid stay what they are; frame j of an event is combined with weights
+    steered at the direction of the track block it lies in (``mvdr_frame_blocks``; ``trk_dir`` of the events), one weight set per
+    block from the event's one covariance, and the sqrt-Hann overlap-add cross-fades from one block's beam to the next.  A silent
+    block and an event without a track keep ``dir``.  Offline, in batches and on live feeds; ``False``: every bit as before."""
     loading: float = 1e-2
     noise_blocks: int = 0
     noise_guard: int = 1
@@ -496,8 +502,12 @@ class MVDR:
     noise_search: int = 0
     noise_min: int = 1
     noise_exclude: str = "same"
+    follow_track: bool = False
 
     def __post_init__(self):
+        if not isinstance(self.follow_track, (bool, np.bool_)):
+            raise ValueError(f"MVDR: follow_track must be a bool, got {self.follow_track!r}")
+        object.__setattr__(self, "follow_track", bool(self.follow_track))
         v = self.loading
         if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not 1e-6 <= float(v) <= 1e6:
             raise ValueError(f"MVDR: loading must be a number in [1e-6, 1e6], got {v!r}")
@@ -536,6 +546,21 @@ class MVDR:
         """``G + Kn + 1``: an event uses the noise covariance iff it starts at least this many blocks of 1024 samples into its
         recording; 0 with ``noise_blocks = 0``"""
         return self.noise_guard + self.noise_blocks + 1 if self.noise_blocks else 0
+
+
+def mvdr_frame_blocks(length, hop_length, block_chunks, n_blocks):
+    """The track block every frame of an MVDR beam with ``follow_track=True`` takes its weights from (mvdr.hip applies
+    the same rule) -> int64 [J + 1], ``J = ceil(length / 1024)``: an event of ``length`` samples has the frames j = 0..J, the
+    centre of frame j is sample ``j * 1024`` of the event, which lies in located frame ``j * 1024 // hop_length`` and that in block
+    ``(j * 1024 // hop_length) // (32 * block_chunks)`` of the track; frame J and the short tail that ``track_blocks`` joins to the
+    last block take block ``T - 1``, T = ``n_blocks``.  ``n_blocks = 0`` — an event without a track — is a row of zeros: the one
+    weight set steered at ``dir``."""
+    length, hop, W, T = int(length), int(hop_length), int(block_chunks), int(n_blocks)
+    if length < 0 or hop < 1 or not 1 <= W <= TRACK_MAX_BLOCK_CHUNKS or not 0 <= T <= TRACK_MAX_BLOCKS:
+        raise ValueError(f"mvdr_frame_blocks needs length >= 0, hop_length >= 1, 1 <= block_chunks <= {TRACK_MAX_BLOCK_CHUNKS} and "
+                         f"0 <= n_blocks <= {TRACK_MAX_BLOCKS}, got {length}, {hop_length}, {block_chunks}, {n_blocks}")
+    j = np.arange(-(-length // MVDR_BLOCK) + 1, dtype=np.int64)
+    return np.minimum((j * MVDR_BLOCK // hop) // (TRACK_CHUNK * W), max(T - 1, 0))
 
 
 @functools.lru_cache(maxsize=1)
