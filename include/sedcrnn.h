@@ -613,6 +613,59 @@ int sed_event_doa_track_ring(const float* ring, long ring_len, long cap, const l
                              int block_chunks, const int* nbr_off, const int* nbr_idx, int* trk_len_out, int* trk_raw_out,
                              int* trk_dir_out, float* trk_power_out, float* trk_map_out, void* workspace, size_t workspace_bytes,
                              void* stream);
+/* sed_event_contrast_frames / sed_event_doa_contrast / sed_event_doa_track_contrast: contrast SRP-PHAT, for an event
+ * that sounds over a louder source of another class.  sed_event_doa gives such an event the louder source's direction; here the
+ * share of that source is estimated from frames before the onset in which the event's own class is silent, and removed from the
+ * event's accumulated cross spectrum before the map is steered: S'[k] = S[k] - w Sb[k], w = (float)((double)weight nf / nb), one
+ * fmaf per component, with S the sum over the event's nf located frames and Sb the sum over its nb background frames, each of
+ * them loaded, transformed and whitened exactly as the located frame of that index is, added in chunks of 32 consecutive list
+ * entries and the chunk partials in ascending order.
+ * The rule is integer and reads the event table and the settings alone.  ev_cls: device int32 [E], the class of every row,
+ * counted in n_classes in [1, 32].  With H = time_factor hop and L_r = n_r / H + 1: mask[r][t] has bit cls of every row of the
+ * table with 0 <= cls < n_classes, onset >= 0 and a recording in range, for onset <= t < min(offset, L_r), located or not.  An
+ * event with frames (frames_out > 0) and a class in range has the candidates q = 0 .. search - 1: feature frame
+ * g = onset time_factor - guard - 1 - q, which exists when g >= 0 and is eligible when bit cls of mask[r][t] is clear for
+ * t = max(g hop - 1024, 0) / H .. min(ceil((g hop + 1024) / H), L_r) - 1.  The first `frames` eligible candidates in ascending q
+ * are its background frames; bg_frames_out: device int32 [E], their number nb, 0 where fewer than min_frames were found;
+ * bg_sel_out: device int32 [E][frames], their q in summation order (descending q, ascending time), -1 behind them.
+ * 1 <= frames <= 256, frames <= search <= 4096, 0 <= guard <= 64, 1 <= min_frames <= frames, weight finite in (0, 4].
+ * sed_event_contrast_frames does the activity and the selection alone and reads no sample.  sed_event_doa_contrast takes the
+ * arguments of sed_event_doa with ev_cls behind ev_rec, the six settings behind max_frames and the two outputs behind srp_out:
+ * lag_out, strength_out, frames_out and acc_out come from S and keep the bits of sed_event_doa; dir_out, power_out = srp[dir] /
+ * (P nf) and srp_out come from S'; an event with nb = 0 gets the bits of sed_event_doa throughout.  sed_event_doa_track_contrast
+ * is sed_event_doa_track in the same way: every block's map is made from S_b - w_b Sb with the event's one Sb and
+ * w_b = (float)((double)weight n_b / nb), and trk_raw, trk_power, trk_map and the path come from those maps.
+ * mask_frames: sum_r L_r.  The workspace is the recording table, the mask (built once per call from the whole table, whatever
+ * the slicing) and, per event, the chunk slots of sed_event_tdoa and ceil(frames / 32) more (then the track's tail); the
+ * _workspace_bytes functions return 0 for sizes that are refused; a smaller workspace that takes one event is walked in slices
+ * and changes no bit.  Every output depends on the event's own samples, those of its background frames, the table and the
+ * settings alone.  Everything that can be checked on the host is checked before anything is enqueued; the messages begin
+ * "contrast_frames:" / "doa_contrast:" / "doa_track_contrast:"; E = 0 launches nothing.  There are no ring forms. */
+size_t sed_event_contrast_frames_workspace_bytes(int R, int channels, long mask_frames, int frames);
+int sed_event_contrast_frames(long pcm_len, const long* clips_host, int R, int channels, const int* ev_rec, const int* ev_cls,
+                              const int* ev_onset, const int* ev_offset, const int* ev_peak_frame, long E, int time_factor, int hop,
+                              int max_frames, int n_classes, int frames, int search, int guard, int min_frames, int* bg_frames_out,
+                              int* bg_sel_out, void* workspace, size_t workspace_bytes, void* stream);
+size_t sed_event_doa_contrast_workspace_bytes(int R, int channels, long E, long max_n_samples, int hop, int max_frames,
+                                              long mask_frames, int frames);
+int sed_event_doa_contrast(const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const void* tables,
+                           size_t tables_bytes, const int* ev_rec, const int* ev_cls, const int* ev_onset, const int* ev_offset,
+                           const int* ev_peak_frame, long E, int time_factor, int hop, int pad_mode, int max_lag, int max_frames,
+                           int n_classes, int frames, int search, int guard, int min_frames, double weight, float* lag_out,
+                           float* strength_out, int* frames_out, float* acc_out, const int* steer_lags, int D, int Q,
+                           const float* trig, int* dir_out, float* power_out, float* srp_out, int* bg_frames_out, int* bg_sel_out,
+                           void* workspace, size_t workspace_bytes, void* stream);
+size_t sed_event_doa_track_contrast_workspace_bytes(int R, int channels, long E, long max_n_samples, int hop, int max_frames, int D,
+                                                    int block_chunks, int smooth, long mask_frames, int frames);
+int sed_event_doa_track_contrast(const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const void* tables,
+                                 size_t tables_bytes, const int* ev_rec, const int* ev_cls, const int* ev_onset, const int* ev_offset,
+                                 const int* ev_peak_frame, long E, int time_factor, int hop, int pad_mode, int max_lag, int max_frames,
+                                 int n_classes, int frames, int search, int guard, int min_frames, double weight, float* lag_out,
+                                 float* strength_out, int* frames_out, float* acc_out, const int* steer_lags, int D, int Q,
+                                 const float* trig, int* dir_out, float* power_out, float* srp_out, int block_chunks,
+                                 const int* nbr_off, const int* nbr_idx, int* trk_len_out, int* trk_raw_out, int* trk_dir_out,
+                                 float* trk_power_out, float* trk_map_out, int* bg_frames_out, int* bg_sel_out, void* workspace,
+                                 size_t workspace_bytes, void* stream);
 /* sed_event_beam_spans / sed_event_beamform: the audio of every located event, with the array pointed at it by a
  * steered delay-and-sum beam.  The event columns, clips_host, R, channels, time_factor, hop and max_frames are sed_event_doa's;
  * ev_dir and ev_loc_frames are the dir_out and frames_out it wrote.  An event is extracted iff 0 <= dir < D; its samples are

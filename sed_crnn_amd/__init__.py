@@ -12,7 +12,7 @@ from .detect import (BatchDetectionResult, BatchPlan, DetectionResult, EventDete
 from .feature import PCEN  # noqa: F401
 from .fit import EpochTally, fit, fit_folds, run_epoch, run_epoch_device  # noqa: F401
 from .lightning import CRNNLightning, fit_lightning  # noqa: F401
-from .localize import (DOA, MVDR, TDOA, DelaySum, DirectionGrid, DirectionTrack, event_frames, event_samples, max_lag_for,  # noqa: F401
+from .localize import (DOA, MVDR, TDOA, Contrast, DelaySum, DirectionGrid, DirectionTrack, event_frames, event_samples, max_lag_for,  # noqa: F401
                        mvdr_frame_blocks, steering_lags, steering_delays, stream_extracts, stream_latency_frames, stream_locates, stream_noise_frames,
                        stream_ring_samples, tdoa_to_azimuth, track_blocks, track_neighbours)
 from .losses import BCEWithLogitsLoss, FocalBCELoss  # noqa: F401

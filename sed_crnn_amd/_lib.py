@@ -164,6 +164,16 @@ SIGNATURES = {
     "sed_event_doa_track_ring_workspace_bytes": (_sz, [_i, _i, _l, _l, _i, _i, _i, _i, _i]),
     "sed_event_doa_track_ring": (_i, [_fp, _l, _l, _fp, _i, _i, _fp, _sz, _fp, _fp, _fp, _fp, _l, _i, _i, _i, _i, _i, _i, _fp, _fp, _fp,
                                       _fp, _fp, _i, _i, _fp, _fp, _fp, _fp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _sz, _stream]),
+    "sed_event_contrast_frames_workspace_bytes": (_sz, [_i, _i, _l, _i]),
+    "sed_event_contrast_frames": (_i, [_l, _fp, _i, _i, _fp, _fp, _fp, _fp, _fp, _l, _i, _i, _i, _i, _i, _i, _i, _i, _fp, _fp, _fp, _sz,
+                                       _stream]),
+    "sed_event_doa_contrast_workspace_bytes": (_sz, [_i, _i, _l, _l, _i, _i, _l, _i]),
+    "sed_event_doa_contrast": (_i, [_fp, _l, _fp, _i, _i, _fp, _sz, _fp, _fp, _fp, _fp, _fp, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _d,
+                                    _fp, _fp, _fp, _fp, _fp, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _sz, _stream]),
+    "sed_event_doa_track_contrast_workspace_bytes": (_sz, [_i, _i, _l, _l, _i, _i, _i, _i, _i, _l, _i]),
+    "sed_event_doa_track_contrast": (_i, [_fp, _l, _fp, _i, _i, _fp, _sz, _fp, _fp, _fp, _fp, _fp, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i,
+                                          _d, _fp, _fp, _fp, _fp, _fp, _i, _i, _fp, _fp, _fp, _fp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp,
+                                          _fp, _fp, _fp, _sz, _stream]),
     "sed_event_beam_workspace_bytes": (_sz, [_i, _i]),
     "sed_event_beam_ring_workspace_bytes": (_sz, [_i]),
     "sed_event_beam_spans": (_i, [_l, _fp, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _l, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _sz, _stream]),

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libsedcrnn.so")
-SOURCES = ["api.cpp", "conv.hip", "conv_bf16.hip", "wino.hip", "conv1.hip", "bnpool.hip", "gemm.hip", "gru.hip", "misc.hip", "logmel.hip", "gcc.hip", "tdoa.hip", "doa.hip", "doatrack.hip", "beam.hip", "mvdr.hip", "pcen.hip", "resample.hip", "data.hip", "detect.hip", "tune.hip", "psds.hip", "stream.hip", "net.hip"]
+SOURCES = ["api.cpp", "conv.hip", "conv_bf16.hip", "wino.hip", "conv1.hip", "bnpool.hip", "gemm.hip", "gru.hip", "misc.hip", "logmel.hip", "gcc.hip", "tdoa.hip", "doa.hip", "doatrack.hip", "contrast.hip", "beam.hip", "mvdr.hip", "pcen.hip", "resample.hip", "data.hip", "detect.hip", "tune.hip", "psds.hip", "stream.hip", "net.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # per-file extras.  logmel: the SLP vectoriser packs the FFT's scalar adds into v_pk_add_f32 and pays for it with ~600
 # v_mov per frame pair to build the register pairs (packed f32 is no faster than scalar on gfx950)
@@ -21,6 +21,7 @@ EXTRA_FLAGS = {"logmel.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-reso
                "tdoa.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"],
                "doa.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"],
                "doatrack.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"],
+               "contrast.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"],
                "beam.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"],
                "mvdr.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"],
                "pcen.hip": ["-Rpass-analysis=kernel-resource-usage"],
@@ -56,6 +57,10 @@ NO_SCRATCH_KERNELS = {"wino.hip": ("conv3x3_wino_k",),
                       # direction tracks: the steering kernel is doa_steer_k's loop per block of chunks; the path kernel's inner loop
                       # is one LDS read and a compare per neighbour: scratch in either would be the same silent cliff
                       "doatrack.hip": ("doa_track_steer_k", "doa_track_path_k"),
+                      # contrast SRP-PHAT: the accumulate kernel is tdoa_accum_k's body on other frames, with the same FFT and
+                      # the same hazard; the activity and the selection kernel are a few integers per lane.  (The steer kernels that
+                      # subtract the background are instantiations of doa_steer_k and doa_track_steer_k: guarded above.)
+                      "contrast.hip": ("contrast_accum_k", "contrast_activity_k", "contrast_select_k"),
                       # delay-and-sum beam: 8 outputs, 8 channel sums and a 16-sample window live per thread, indexed by unrolled
                       # loops; one of them in scratch would put a memory round trip on every fma of the launch's one loop
                       "beam.hip": ("beam_sum_k", "beam_spans_k"),
@@ -120,7 +125,7 @@ def check_no_spill(remarks, kernels, allow_agprs=False):
 def build(force=False, verbose=False):
     os.makedirs(OBJ, exist_ok=True)
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_shared.h"), os.path.join(CSRC, "detect_shared.h"), os.path.join(CSRC, "tune_shared.h"), os.path.join(CSRC, "fft2048.h"), os.path.join(CSRC, "tdoa_shared.h"), os.path.join(CSRC, "phat_shared.h"), os.path.join(CSRC, "beam_shared.h"), os.path.join(HERE, "..", "include", "sedcrnn.h")]
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_shared.h"), os.path.join(CSRC, "detect_shared.h"), os.path.join(CSRC, "tune_shared.h"), os.path.join(CSRC, "fft2048.h"), os.path.join(CSRC, "tdoa_shared.h"), os.path.join(CSRC, "tdoa_accum.h"), os.path.join(CSRC, "contrast_shared.h"), os.path.join(CSRC, "phat_shared.h"), os.path.join(CSRC, "beam_shared.h"), os.path.join(HERE, "..", "include", "sedcrnn.h")]
     jobs = []
     objs = []
     for src in SOURCES:

@@ -1,0 +1,223 @@
+// contrast.hip — contrast SRP-PHAT: the background frames of every located event and their whitened cross spectra:
+// sed_event_contrast_frames, and the steps that sed_event_doa_contrast (doa.hip) and sed_event_doa_track_contrast (doatrack.hip) run
+// in front of their steer launches.
+//
+// An event that sounds over a louder source of another class gets that source's direction from sed_event_doa: the whitening
+// gives every bin to whichever source is loudest in it.  In the frames before the onset in which the event's own class is silent
+// the other source sounds and the event does not, and the inverse transform and the steering are linear in the cross spectrum:
+//   S'[k] = S[k] - w Sb[k],   w = (float)((double)weight nf / nb)
+// with S the event's sum over its nf located frames and Sb the sum over nb background frames.  The bins the other source wins
+// cancel, the bins the event wins stay.
+//
+// The rule is integer and reads the event table and the settings alone.  With H = tf hop and L_r = n_r / H + 1 output frames:
+//   mask[r][t]  bit cls of every row of the table for onset <= t < min(offset, L_r), located or not (DESIGN 5w's activity)
+//   candidate q = 0 .. S-1 of an event of class k whose first feature frame is a = onset tf: feature frame g = a - G - 1 - q,
+//   which exists when g >= 0 and is eligible when bit k of mask[r][t] is clear in every output frame its 2048 samples
+//   [g hop - 1024, g hop + 1024) touch: t = max(g hop - 1024, 0) / H .. min(ceil((g hop + 1024) / H), L_r) - 1
+//   the first Nb eligible candidates in ascending q are the event's background frames, nb of them; fewer than M: none (nb = 0)
+//   bg_sel[e][0 .. nb) lists them in summation order: descending q, ascending time; -1 behind them
+//
+// Shape (gfx950), plain launches, no workgroup waits on another, no atomics but the mask's OR:
+//   contrast_activity_k   a wave per row of the table, a lane per output frame: atomicOr from vector lanes, order-free
+//   contrast_select_k     a wave per event walks the candidates 64 at a time; a ballot and its prefix count rank the eligible
+//                         ones; the first Nb are written out reversed.  Both run once per call, over the whole table, before
+//                         the first slice.
+//   contrast_accum_k      per slice: one workgroup per chunk of 32 consecutive entries of an event's list, the body of
+//                         tdoa_accum_k (td_accum_chunk, tdoa_accum.h) on the frames a - G - 1 - bg_sel[e][j]; its partial goes to
+//                         the chunk rows behind the event's own.  A frame is loaded, transformed and whitened exactly as the
+//                         located frame of that index is; the pipelined (C <= 4) and the pair-batch (C >= 5) paths are the body's.
+// The steer kernels add the chunk partials in ascending chunk order, as they add S's (ct_sum_chunks, contrast_shared.h): every
+// sum has one order, which depends on the event and its selected frames alone.
+#include <math.h>
+#include <cmath>
+#include <vector>
+#include "common.h"
+#include "fft2048.h"
+#include "tdoa_shared.h"
+#include "tdoa_accum.h"
+#include "contrast_shared.h"
+
+namespace {
+
+// DESIGN 5w's activity, word for word: every row counts, located or not; out-of-range rows mark nothing
+__global__ __launch_bounds__(256) void contrast_activity_k(TdArgs ta, CtArgs ca) {
+    const int lane = threadIdx.x & 63;
+    const long H = (long)ta.tf * ta.hop;
+    for (long e = (long)blockIdx.x * 4 + (threadIdx.x >> 6); e < ca.E; e += (long)gridDim.x * 4) {
+        const int rec = ta.ev_rec ? ta.ev_rec[e] : 0, cls = ca.ev_cls[e];
+        const long on = ta.ev_onset[e];
+        if (rec < 0 || rec >= ta.R || cls < 0 || cls >= ca.n_classes || on < 0) continue;
+        const long L = ta.n_samples[rec] / H + 1;
+        long off = ta.ev_offset[e];
+        if (off > L) off = L;
+        uint32_t* row = ca.mask + ca.mask_off[rec];
+        for (long t = on + lane; t < off; t += 64) atomicOr(row + t, 1u << cls);
+    }
+}
+
+__global__ __launch_bounds__(64) void contrast_select_k(TdArgs ta, CtArgs ca) {
+    __shared__ int s_q[CT_MAX_FRAMES];
+    const int lane = threadIdx.x;
+    const long H = (long)ta.tf * ta.hop;
+    for (long e = blockIdx.x; e < ca.E; e += gridDim.x) {
+        int rec, nf;
+        long f0;
+        td_linear_range(ta, e, rec, f0, nf);
+        const int cls = ca.ev_cls[e];
+        int count = 0;
+        if (nf != 0 && cls >= 0 && cls < ca.n_classes) {         // (block-uniform)
+            const uint32_t own = 1u << cls;                      // other classes never block: they are what is subtracted
+            const uint32_t* row = ca.mask + ca.mask_off[rec];
+            const long L = ta.n_samples[rec] / H + 1;
+            const long g0 = (long)ta.ev_onset[e] * ta.tf - ca.guard - 1;         // candidate q is feature frame g0 - q
+            for (int q0 = 0; q0 < ca.search && count < ca.Nb && g0 - q0 >= 0; q0 += 64) {
+                const int q = q0 + lane;
+                const long g = g0 - q;
+                bool ok = q < ca.search && g >= 0;
+                if (ok) {
+                    long lo = g * ta.hop - LM_NFFT / 2;
+                    if (lo < 0) lo = 0;
+                    long t1 = (g * ta.hop + LM_NFFT / 2 + H - 1) / H;            // (g < the recording's frames: lo / H < L)
+                    if (t1 > L) t1 = L;
+                    for (long t = lo / H; t < t1 && ok; ++t) ok = (row[t] & own) == 0;
+                }
+                const unsigned long long m = __ballot(ok);
+                const int rank = count + __popcll(m & ((1ull << lane) - 1ull));
+                if (ok && rank < ca.Nb) s_q[rank] = q;
+                count += __popcll(m);
+            }
+            if (count > ca.Nb) count = ca.Nb;
+            if (count < ca.min_frames) count = 0;
+        }
+        __syncthreads();
+        for (int i = lane; i < ca.Nb; i += 64) ca.bg_sel[e * ca.Nb + i] = i < count ? s_q[count - 1 - i] : -1;
+        if (lane == 0) ca.bg_frames[e] = count;
+        __syncthreads();                                         // s_q is free for the next event
+    }
+}
+
+// The chunk's frames are entries fc0 .. of the event's list; the body is tdoa_accum_k's.  An event with a list was located
+// (nf > 0), so its recording is in range; a list entry that the selection did not write (none is read: the chunk ends at nb)
+// would still name a frame whose every load is guarded.
+__global__ __launch_bounds__(TD_THREADS) void contrast_accum_k(const float* __restrict__ pcm, const uint32_t* __restrict__ tables,
+                                                               float2* __restrict__ ws, int pad_mode, TdArgs ta, CtArgs ca) {
+    const long e = ta.e0 + blockIdx.y;
+    const int nb = ct_bg_frames(ca, e);
+    const int fc0 = blockIdx.x * TD_CHUNK;                       // the chunk's first entry of the list
+    if (fc0 >= nb) return;                                       // (block-uniform: before any barrier)
+    const int fc1 = fc0 + TD_CHUNK < nb ? fc0 + TD_CHUNK : nb;
+    int rec = ta.ev_rec ? ta.ev_rec[e] : 0;
+    if (rec < 0 || rec >= ta.R) return;
+    const long g0 = (long)ta.ev_onset[e] * ta.tf - ca.guard - 1;
+    const int* sel = ca.bg_sel + e * ca.Nb + fc0;
+    float2* wrow = ws + ((long)blockIdx.y * ta.cpe + ca.cpo + blockIdx.x) * ta.P * PHAT_SPEC;
+    td_accum_chunk<false>(pcm, tables, wrow, pad_mode, ta, rec, fc1 - fc0, [&](int step) -> long { return g0 - sel[step]; });
+}
+
+size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+}  // namespace
+
+bool ct_sizes_ok(int R, long mask_frames, int frames) {
+    return R >= 1 && mask_frames >= R && mask_frames <= (1L << 40) && frames >= 1 && frames <= CT_MAX_FRAMES;
+}
+
+size_t ct_mask_bytes(int R, long frames) { return round16((size_t)R * sizeof(long)) + round16((size_t)frames * 4); }
+
+long ct_mask_frames(const long* clips_host, int R, int channels, int tf, int hop) {
+    if (!clips_host || R < 1 || channels < 1 || tf < 1 || hop < 1) return 0;
+    const long H = (long)tf * hop;
+    long frames = 0;
+    for (int r = 0; r < R; ++r) {
+        const long n = clips_host[2 * ((long)r * channels) + 1];
+        if (n < 1) return 0;
+        frames += n / H + 1;
+    }
+    return frames;
+}
+
+int ct_check(const char* who, long E, const CtSettings& cs) {
+    SED_REQUIRE(cs.frames >= 1 && cs.frames <= CT_MAX_FRAMES, "%s: frames must be in [1, %d], got %d", who, CT_MAX_FRAMES, cs.frames);
+    SED_REQUIRE(cs.search >= cs.frames && cs.search <= CT_MAX_SEARCH, "%s: search must be in [frames = %d, %d], got %d", who, cs.frames,
+                CT_MAX_SEARCH, cs.search);
+    SED_REQUIRE(cs.guard >= 0 && cs.guard <= CT_MAX_GUARD, "%s: guard must be in [0, %d], got %d", who, CT_MAX_GUARD, cs.guard);
+    SED_REQUIRE(cs.min_frames >= 1 && cs.min_frames <= cs.frames, "%s: min_frames must be in [1, frames = %d], got %d", who, cs.frames,
+                cs.min_frames);
+    SED_REQUIRE(std::isfinite(cs.weight) && cs.weight > 0.0 && cs.weight <= CT_MAX_WEIGHT, "%s: weight must be finite and in (0, %g], got %g",
+                who, CT_MAX_WEIGHT, cs.weight);
+    SED_REQUIRE(cs.n_classes >= 1 && cs.n_classes <= CT_MAX_CLASSES, "%s: n_classes must be in [1, %d], got %d", who, CT_MAX_CLASSES,
+                cs.n_classes);
+    SED_REQUIRE(E == 0 || (cs.cls && cs.frames_out && cs.sel_out), "%s: null pointer (ev_cls, bg_frames_out or bg_sel_out)", who);
+    return 0;
+}
+
+int ct_pre(void* ctx, const RecSource& src, const EvTable& ev, void* workspace, hipStream_t s) {
+    CtRun& run = *static_cast<CtRun*>(ctx);
+    const CtSettings& cs = run.cs;
+    const long H = (long)ev.tf * ev.hop;
+    const long* n = src.h.data() + (size_t)src.R * src.C;
+    std::vector<long> off((size_t)src.R);
+    long frames = 0;
+    for (int r = 0; r < src.R; ++r) { off[r] = frames; frames += n[r] / H + 1; }
+    char* base = (char*)workspace + src.tab;
+    long* d_off = (long*)base;
+    uint32_t* d_mask = (uint32_t*)(base + round16((size_t)src.R * sizeof(long)));
+    hipError_t err = hipMemcpyAsync(d_off, off.data(), off.size() * sizeof(long), hipMemcpyHostToDevice, s);
+    if (err == hipSuccess) err = hipMemsetAsync(d_mask, 0, (size_t)frames * 4, s);
+    if (err != hipSuccess) { sed_set_error("contrast: upload of the mask offsets: %s", hipGetErrorString(err)); return (int)err; }
+    const TdArgs ta = td_args(src, ev, workspace);
+    run.ca = CtArgs{cs.cls, ev.E, cs.n_classes, cs.frames, cs.search, cs.guard, cs.min_frames, cs.weight, d_off, d_mask, cs.frames_out,
+                    cs.sel_out, 0};
+    const long cap = 1L << 20;
+    contrast_activity_k<<<(unsigned)((ev.E + 3) / 4 < cap ? (ev.E + 3) / 4 : cap), 256, 0, s>>>(ta, run.ca);
+    SED_LAUNCH_CHECK("contrast (activity)");
+    contrast_select_k<<<(unsigned)(ev.E < cap ? ev.E : cap), 64, 0, s>>>(ta, run.ca);
+    SED_LAUNCH_CHECK("contrast (selection)");
+    return 0;
+}
+
+int ct_accum(const char* who, CtRun& run, const TdArgs& ta, const float2* part, hipStream_t s) {
+    SED_REQUIRE(ta.cpe > run.cpb && ta.cap == 0, "%s: the slice has %d chunk slots per event, %d of them for the background", who, ta.cpe,
+                run.cpb);
+    run.ca.cpo = ta.cpe - run.cpb;
+    const hipError_t err = hipFuncSetAttribute((const void*)contrast_accum_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TD_LDS_MAX);
+    if (err != hipSuccess) { sed_set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(err)); return (int)err; }
+    const size_t lds = tdoa_lds_bytes(ta.C, ta.pairs_per_batch, ta.pipelined ? 2 : 1);
+    contrast_accum_k<<<dim3((unsigned)run.cpb, (unsigned)ta.n_ev), TD_THREADS, lds, s>>>(run.pcm, (const uint32_t*)run.tables,
+                                                                                          const_cast<float2*>(part), run.pad_mode, ta, run.ca);
+    SED_LAUNCH_CHECK("contrast (accumulate)");
+    return 0;
+}
+
+// workspace: sample_off [R*C] and n_samples [R], then mask_off [R] and the mask
+extern "C" size_t sed_event_contrast_frames_workspace_bytes(int R, int channels, long mask_frames, int frames) {
+    if (R < 1 || channels < 2 || channels > TD_MAX_CH || !ct_sizes_ok(R, mask_frames, frames)) return 0;
+    return rec_table_bytes(R, channels) + ct_mask_bytes(R, mask_frames);
+}
+
+// the activity and the selection alone; no sample is read
+extern "C" int sed_event_contrast_frames(long pcm_len, const long* clips_host, int R, int channels, const int* ev_rec, const int* ev_cls,
+                                         const int* ev_onset, const int* ev_offset, const int* ev_peak_frame, long E, int time_factor,
+                                         int hop, int max_frames, int n_classes, int frames, int search, int guard, int min_frames,
+                                         int* bg_frames_out, int* bg_sel_out, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "contrast_frames";
+    RecSource src{nullptr, false, 0, pcm_len, R, channels, clips_host};
+    const EvTable ev{ev_rec, ev_onset, ev_offset, ev_peak_frame, nullptr, nullptr, E, time_factor, hop, max_frames, 0};
+    SED_REQUIRE(channels >= 2 && channels <= TD_MAX_CH, "%s: 2 to %d channels, got %d", who, TD_MAX_CH, channels);
+    SED_REQUIRE(max_frames >= 1, "%s: max_frames must be >= 1, got %d", who, max_frames);
+    SED_REQUIRE(time_factor >= 1 && hop >= 1 && R >= 1 && E >= 0, "%s: bad sizes (time_factor=%d, hop=%d, R=%d, E=%ld)", who, time_factor,
+                hop, R, E);
+    SED_REQUIRE(E == 0 || (ev_onset && ev_offset && ev_peak_frame), "%s: null pointer (an event column)", who);
+    SED_REQUIRE(E == 0 || ev_rec || R == 1, "%s: %d recordings need ev_rec", who, R);
+    CtRun run{};
+    run.cs = CtSettings{ev_cls, n_classes, frames, search, guard, min_frames, 1.0, bg_frames_out, bg_sel_out};
+    SED_TRY(ct_check(who, E, run.cs));
+    SED_TRY(rec_source_linear(who, src, hop));
+    if (E == 0) return 0;
+    const size_t need = src.tab + ct_mask_bytes(R, ct_mask_frames(clips_host, R, channels, time_factor, hop));
+    SED_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0, "%s: the workspace must be a 16-byte aligned device buffer", who);
+    SED_REQUIRE(workspace_bytes >= need, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
+    hipStream_t s = as_stream(stream);
+    SED_TRY(rec_upload(who, src, workspace, s));
+    return ct_pre(&run, src, ev, workspace, s);
+}

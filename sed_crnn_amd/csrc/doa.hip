@@ -23,6 +23,7 @@
 #include "common.h"
 #include "fft2048.h"
 #include "tdoa_shared.h"
+#include "contrast_shared.h"
 
 #define DOA_WAVES 8
 #define DOA_THREADS (DOA_WAVES * 64)
@@ -45,7 +46,10 @@ size_t doa_lds_bytes(int D, int Q, int max_lag) {
     return ((size_t)2 * PHAT_SPEC + (size_t)2 * (512 * Q + 1) + (size_t)(2 * max_lag * Q + 1) + (size_t)D) * sizeof(float);
 }
 
-__global__ __launch_bounds__(DOA_THREADS) void doa_steer_k(const float2* __restrict__ ws, DoaArgs da, TdArgs ta) {
+// CT (sed_event_doa_contrast): an event with background frames steers S' = S - w Sb, formed in LDS where S is formed; an
+// event without them, and every event of doa_steer_k<false>, takes the plain path and gives the plain bits.
+template <bool CT>
+__global__ __launch_bounds__(DOA_THREADS) void doa_steer_k(const float2* __restrict__ ws, DoaArgs da, TdArgs ta, CtArgs ca) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ float r_best[DOA_WAVES], r_low[DOA_WAVES];
     __shared__ int r_at[DOA_WAVES];
@@ -72,8 +76,13 @@ __global__ __launch_bounds__(DOA_THREADS) void doa_steer_k(const float2* __restr
         }
         const int nch = (nf + TD_CHUNK - 1) / TD_CHUNK;
         const float2* wev = ws + (long)el * ta.cpe * P * PHAT_SPEC;
+        const int nb = CT ? ct_bg_frames(ca, e) : 0;             // (block-uniform)
         for (int p = 0; p < P; ++p) {
-            phat_sum_chunks(s_S, wev, p, P, nch, tid, DOA_THREADS);
+            if (CT && nb > 0)
+                ct_sum_chunks(s_S, wev, wev + (long)ca.cpo * P * PHAT_SPEC, p, P, nch, (nb + TD_CHUNK - 1) / TD_CHUNK,
+                              ct_weight(ca.weight, nf, nb), tid, DOA_THREADS);
+            else
+                phat_sum_chunks(s_S, wev, p, P, nch, tid, DOA_THREADS);
             __syncthreads();
             // ── fine lags: item = j = 0..F, 8 lanes per item; fine[+j] = A - B, fine[-j] = A + B ──
             const int grp = tid >> 3, j8 = tid & 7;
@@ -130,10 +139,25 @@ __global__ __launch_bounds__(DOA_THREADS) void doa_steer_k(const float2* __restr
 int doa_hook(void* ctx, const TdArgs& ta, const float2* part, hipStream_t s) {
     const DoaArgs& da = *static_cast<const DoaArgs*>(ctx);
     const char* who = ta.cap > 0 ? "event_doa_ring (steer)" : "event_doa (steer)";
-    const hipError_t err = hipFuncSetAttribute((const void*)doa_steer_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DOA_LDS_MAX - 256);
+    const hipError_t err = hipFuncSetAttribute((const void*)doa_steer_k<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DOA_LDS_MAX - 256);
     if (err != hipSuccess) { sed_set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(err)); return (int)err; }
     const int blocks = ta.n_ev < 2048 ? ta.n_ev : 2048;
-    doa_steer_k<<<blocks, DOA_THREADS, doa_lds_bytes(da.D, da.Q, ta.max_lag), s>>>(part, da, ta);
+    doa_steer_k<false><<<blocks, DOA_THREADS, doa_lds_bytes(da.D, da.Q, ta.max_lag), s>>>(part, da, ta, CtArgs{});
+    SED_LAUNCH_CHECK(who);
+    return 0;
+}
+
+// sed_event_doa_contrast: the slice's background chunks behind its own, then the steer launch that subtracts them
+struct DoaContrast { DoaArgs da; CtRun run; };
+
+int doa_contrast_hook(void* ctx, const TdArgs& ta, const float2* part, hipStream_t s) {
+    DoaContrast& dc = *static_cast<DoaContrast*>(ctx);
+    const char* who = "doa_contrast (steer)";
+    SED_TRY(ct_accum("doa_contrast", dc.run, ta, part, s));
+    const hipError_t err = hipFuncSetAttribute((const void*)doa_steer_k<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DOA_LDS_MAX - 256);
+    if (err != hipSuccess) { sed_set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(err)); return (int)err; }
+    const int blocks = ta.n_ev < 2048 ? ta.n_ev : 2048;
+    doa_steer_k<true><<<blocks, DOA_THREADS, doa_lds_bytes(dc.da.D, dc.da.Q, ta.max_lag), s>>>(part, dc.da, ta, dc.run.ca);
     SED_LAUNCH_CHECK(who);
     return 0;
 }
@@ -191,4 +215,36 @@ extern "C" int sed_event_doa_ring(const float* ring, long ring_len, long cap, co
                            {ev_rec, ev_onset, ev_offset, ev_peak_frame, nullptr, nullptr, E, time_factor, hop, max_frames, 0},
                            {tables, tables_bytes, 0, max_lag, lat_frames, history_frames}, {lag_out, strength_out, frames_out, acc_out},
                            workspace, workspace_bytes, stream, doa_hook, &da);
+}
+
+// ───────────────────────── contrast SRP-PHAT ─────────────────────────
+// workspace: the recording table, mask_off [R] and the mask of mask_frames words, then, for every event, its own chunk slots and
+// ceil(frames / 32) more for its background: rows of 1026 float2 per pair
+extern "C" size_t sed_event_doa_contrast_workspace_bytes(int R, int channels, long E, long max_n_samples, int hop, int max_frames,
+                                                         long mask_frames, int frames) {
+    const size_t one = sed_event_tdoa_workspace_bytes(R, channels, 1, max_n_samples, hop, max_frames);
+    if (one == 0 || E < 0 || !ct_sizes_ok(R, mask_frames, frames)) return 0;
+    const size_t tab = rec_table_bytes(R, channels);
+    const size_t bg = (size_t)((frames + TD_CHUNK - 1) / TD_CHUNK) * (channels * (channels - 1) / 2) * TD_ROW_BYTES;
+    return tab + ct_mask_bytes(R, mask_frames) + (size_t)E * (one - tab + bg);
+}
+
+extern "C" int sed_event_doa_contrast(const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const void* tables,
+                                      size_t tables_bytes, const int* ev_rec, const int* ev_cls, const int* ev_onset, const int* ev_offset,
+                                      const int* ev_peak_frame, long E, int time_factor, int hop, int pad_mode, int max_lag, int max_frames,
+                                      int n_classes, int frames, int search, int guard, int min_frames, double weight, float* lag_out,
+                                      float* strength_out, int* frames_out, float* acc_out, const int* steer_lags, int D, int Q,
+                                      const float* trig, int* dir_out, float* power_out, float* srp_out, int* bg_frames_out,
+                                      int* bg_sel_out, void* workspace, size_t workspace_bytes, void* stream) {
+    DoaContrast dc{};
+    SED_TRY(doa_check("doa_contrast", steer_lags, D, Q, trig, max_lag, dir_out, power_out, srp_out, dc.da));
+    dc.run.cs = CtSettings{ev_cls, n_classes, frames, search, guard, min_frames, weight, bg_frames_out, bg_sel_out};
+    SED_TRY(ct_check("doa_contrast", E, dc.run.cs));
+    dc.run.pcm = pcm; dc.run.tables = tables; dc.run.pad_mode = pad_mode;
+    dc.run.cpb = (frames + TD_CHUNK - 1) / TD_CHUNK;
+    const TdExtra extra{ct_mask_bytes(R, ct_mask_frames(clips_host, R, channels, time_factor, hop)), dc.run.cpb, ct_pre, &dc.run};
+    return tdoa_entry("doa_contrast", {pcm, false, 0, pcm_len, R, channels, clips_host},
+                      {ev_rec, ev_onset, ev_offset, ev_peak_frame, nullptr, nullptr, E, time_factor, hop, max_frames, 0},
+                      {tables, tables_bytes, pad_mode, max_lag, 0, 0}, {lag_out, strength_out, frames_out, acc_out}, workspace,
+                      workspace_bytes, stream, doa_contrast_hook, &dc, &extra);
 }

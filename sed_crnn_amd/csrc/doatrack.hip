@@ -27,6 +27,7 @@
 #include "common.h"
 #include "fft2048.h"
 #include "tdoa_shared.h"
+#include "contrast_shared.h"
 
 #define TRK_WAVES 8
 #define TRK_THREADS (TRK_WAVES * 64)
@@ -74,7 +75,11 @@ size_t trk_lds_bytes(int D, int Q, int max_lag) {
     return ((size_t)2 * PHAT_SPEC + (size_t)2 * (512 * Q + 1) + (size_t)(2 * max_lag * Q + 1) + (size_t)D) * sizeof(float);
 }
 
-__global__ __launch_bounds__(TRK_THREADS) void doa_track_steer_k(const float2* __restrict__ ws, TrkArgs ka, TdArgs ta) {
+// CT (sed_event_doa_track_contrast): every block of an event with background frames — and the whole event — steers
+// S_b - w_b Sb with the event's one Sb and w_b from the block's frames; an event without them, and every event of
+// doa_track_steer_k<false>, takes the plain path and gives the plain bits.
+template <bool CT>
+__global__ __launch_bounds__(TRK_THREADS) void doa_track_steer_k(const float2* __restrict__ ws, TrkArgs ka, TdArgs ta, CtArgs ca) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ float r_best[TRK_WAVES], r_low[TRK_WAVES];
     __shared__ int r_at[TRK_WAVES], r_none;
@@ -117,8 +122,13 @@ __global__ __launch_bounds__(TRK_THREADS) void doa_track_steer_k(const float2* _
         if (!blk && !evt) continue;
         if (b == Tm) { tb.c0 = 0; tb.nc = (nf + TD_CHUNK - 1) / TD_CHUNK; tb.n = nf; }
         const float2* wev = ws + ((long)el * ta.cpe + tb.c0) * P * PHAT_SPEC;    // the block's first chunk is chunk 0 of the sum
+        const int nb = CT ? ct_bg_frames(ca, e) : 0;             // (block-uniform)
         for (int p = 0; p < P; ++p) {
-            phat_sum_chunks(s_S, wev, p, P, tb.nc, tid, TRK_THREADS);
+            if (CT && nb > 0)
+                ct_sum_chunks(s_S, wev, ws + ((long)el * ta.cpe + ca.cpo) * P * PHAT_SPEC, p, P, tb.nc, (nb + TD_CHUNK - 1) / TD_CHUNK,
+                              ct_weight(ca.weight, tb.n, nb), tid, TRK_THREADS);
+            else
+                phat_sum_chunks(s_S, wev, p, P, tb.nc, tid, TRK_THREADS);
             __syncthreads();
             // ── fine lags: item = j = 0..F, 8 lanes per item; fine[+j] = A - B, fine[-j] = A + B ──
             const int grp = tid >> 3, j8 = tid & 7;
@@ -285,6 +295,7 @@ __global__ __launch_bounds__(TRK_THREADS) void doa_track_path_k(TrkArgs ka, TdAr
 
 // what the entry works out before it hands the rest to tdoa_entry
 struct TrkCtx {
+    CtRun* contrast;            // sed_event_doa_track_contrast: the run whose background chunks every slice steers against (else null)
     TrkArgs ka;
     size_t per_event;           // tail bytes per event of a sub-slice (0 without smoothing)
     long fit;                   // events the tail holds
@@ -302,10 +313,12 @@ long trk_cpe(long max_rec_frames, int max_frames) {              // (tdoa.hip: t
 
 int trk_hook(void* ctx, const TdArgs& ta, const float2* part, hipStream_t s) {
     const TrkCtx& tc = *static_cast<const TrkCtx*>(ctx);
-    const char* who = ta.cap > 0 ? "event_doa_track_ring" : "event_doa_track";
+    const char* who = tc.contrast ? "doa_track_contrast" : ta.cap > 0 ? "event_doa_track_ring" : "event_doa_track";
+    if (tc.contrast) SED_TRY(ct_accum(who, *tc.contrast, ta, part, s));
     SED_REQUIRE(ta.cpe == tc.cpe && (!tc.ka.nbr_off || tc.fit >= 1), "%s: the slice has %d chunk slots per event, the workspace was split for "
                 "%d (%ld events)", who, ta.cpe, tc.cpe, tc.fit);
-    hipError_t err = hipFuncSetAttribute((const void*)doa_track_steer_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TRK_LDS_MAX - 256);
+    hipError_t err = hipFuncSetAttribute(tc.contrast ? (const void*)doa_track_steer_k<true> : (const void*)doa_track_steer_k<false>,
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)TRK_LDS_MAX - 256);
     if (err == hipSuccess && tc.ka.nbr_off)
         err = hipFuncSetAttribute((const void*)doa_track_path_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TRK_LDS_MAX - 256);
     if (err != hipSuccess) { sed_set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(err)); return (int)err; }
@@ -315,8 +328,12 @@ int trk_hook(void* ctx, const TdArgs& ta, const float2* part, hipStream_t s) {
         ka.sub0 = (int)s0;
         ka.n_sub = (int)(ta.n_ev - s0 < step ? ta.n_ev - s0 : step);
         const long items = (long)ka.n_sub * (ka.Tm + 1);
-        doa_track_steer_k<<<(unsigned)(items < 2048 ? items : 2048), TRK_THREADS, trk_lds_bytes(ka.D, ka.Q, ta.max_lag), s>>>(part, ka, ta);
-        SED_LAUNCH_CHECK(ta.cap > 0 ? "event_doa_track_ring (steer)" : "event_doa_track (steer)");
+        const unsigned blocks = (unsigned)(items < 2048 ? items : 2048);
+        if (tc.contrast)
+            doa_track_steer_k<true><<<blocks, TRK_THREADS, trk_lds_bytes(ka.D, ka.Q, ta.max_lag), s>>>(part, ka, ta, tc.contrast->ca);
+        else
+            doa_track_steer_k<false><<<blocks, TRK_THREADS, trk_lds_bytes(ka.D, ka.Q, ta.max_lag), s>>>(part, ka, ta, CtArgs{});
+        SED_LAUNCH_CHECK(tc.contrast ? "doa_track_contrast (steer)" : ta.cap > 0 ? "event_doa_track_ring (steer)" : "event_doa_track (steer)");
         if (ka.nbr_off) {
             doa_track_path_k<<<ka.n_sub < 2048 ? ka.n_sub : 2048, TRK_THREADS, (size_t)2 * ka.D * sizeof(float), s>>>(ka, ta);
             SED_LAUNCH_CHECK(ta.cap > 0 ? "event_doa_track_ring (path)" : "event_doa_track (path)");
@@ -329,7 +346,7 @@ int trk_hook(void* ctx, const TdArgs& ta, const float2* part, hipStream_t s) {
 int trk_check(const char* who, bool ring, const long* host, long cap, int R, int channels, long E, int hop, int max_lag, int max_frames,
               const int* steer_lags, int D, int Q, const float* trig, int* dir_out, float* power_out, float* srp_out, int block_chunks, const int* nbr_off,
               const int* nbr_idx, int* trk_len_out, int* trk_raw_out, int* trk_dir_out, float* trk_power_out, float* trk_map_out,
-              void* workspace, size_t workspace_bytes, TrkCtx& tc, size_t& td_bytes) {
+              void* workspace, size_t workspace_bytes, TrkCtx& tc, size_t& td_bytes, size_t extra_tab = 0, int extra_chunks = 0) {
     SED_REQUIRE(steer_lags && trig && dir_out && power_out, "%s: null pointer (steering lags, angle table, dir_out or power_out)", who);
     SED_REQUIRE(trk_len_out && trk_raw_out && trk_dir_out && trk_power_out, "%s: null pointer (trk_len_out, trk_raw_out, trk_dir_out or "
                 "trk_power_out)", who);
@@ -361,12 +378,12 @@ int trk_check(const char* who, bool ring, const long* host, long cap, int R, int
     }
     const long cpe = trk_cpe(1 + longest / hop, max_frames);
     if (cpe < 1 || cpe > 0x7fffffffL) return 0;                  // (recordings tdoa_entry refuses)
-    tc.cpe = (int)cpe;
+    tc.cpe = (int)cpe + extra_chunks;                            // (an event's background chunks lie behind its own)
     tc.ka.Tw = (int)((cpe + block_chunks - 1) / block_chunks);
     tc.per_event = trk_tail_bytes(tc.ka.Tw, D, nbr_off != nullptr);
     if (!tc.per_event) return 0;                                 // no smoothing: nothing is kept, the workspace is the TDOA one
-    const size_t tab = ring ? rec_ring_table_bytes(R) : rec_table_bytes(R, channels);
-    const size_t one = (size_t)cpe * (channels * (channels - 1) / 2) * TD_ROW_BYTES + tc.per_event;
+    const size_t tab = (ring ? rec_ring_table_bytes(R) : rec_table_bytes(R, channels)) + extra_tab;
+    const size_t one = (size_t)tc.cpe * (channels * (channels - 1) / 2) * TD_ROW_BYTES + tc.per_event;
     SED_REQUIRE(workspace_bytes >= tab + one, "%s: workspace of %zu bytes, at least %zu needed (one event)", who, workspace_bytes, tab + one);
     const size_t wb = workspace_bytes & ~(size_t)15;             // (the table, a row and an event's tail are multiples of 16 bytes)
     tc.fit = (long)((wb - tab) / one);
@@ -435,4 +452,44 @@ extern "C" int sed_event_doa_track_ring(const float* ring, long ring_len, long c
                       {ev_rec, ev_onset, ev_offset, ev_peak_frame, nullptr, nullptr, E, time_factor, hop, max_frames, 0},
                       {tables, tables_bytes, 0, max_lag, lat_frames, history_frames}, {lag_out, strength_out, frames_out, acc_out},
                       workspace, td_bytes, stream, trk_hook, &tc);
+}
+
+// ───────────────────────── contrast SRP-PHAT ─────────────────────────
+// the workspace of sed_event_doa_contrast and, with smoothing, the tail of sed_event_doa_track
+extern "C" size_t sed_event_doa_track_contrast_workspace_bytes(int R, int channels, long E, long max_n_samples, int hop, int max_frames, int D,
+                                                               int block_chunks, int smooth, long mask_frames, int frames) {
+    const size_t one = sed_event_tdoa_workspace_bytes(R, channels, 1, max_n_samples, hop, max_frames);
+    if (one == 0 || E < 0 || !ct_sizes_ok(R, mask_frames, frames)) return 0;
+    const size_t tab = rec_table_bytes(R, channels);
+    const size_t bg = (size_t)((frames + TD_CHUNK - 1) / TD_CHUNK) * (channels * (channels - 1) / 2) * TD_ROW_BYTES;
+    const size_t td = tab + ct_mask_bytes(R, mask_frames) + (size_t)E * (one - tab + bg);
+    return trk_workspace_bytes(td, channels, E, 1 + max_n_samples / hop, max_frames, D, block_chunks, smooth);
+}
+
+extern "C" int sed_event_doa_track_contrast(const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const void* tables,
+                                            size_t tables_bytes, const int* ev_rec, const int* ev_cls, const int* ev_onset,
+                                            const int* ev_offset, const int* ev_peak_frame, long E, int time_factor, int hop, int pad_mode,
+                                            int max_lag, int max_frames, int n_classes, int frames, int search, int guard, int min_frames,
+                                            double weight, float* lag_out, float* strength_out, int* frames_out, float* acc_out,
+                                            const int* steer_lags, int D, int Q, const float* trig, int* dir_out, float* power_out,
+                                            float* srp_out, int block_chunks, const int* nbr_off, const int* nbr_idx, int* trk_len_out,
+                                            int* trk_raw_out, int* trk_dir_out, float* trk_power_out, float* trk_map_out, int* bg_frames_out,
+                                            int* bg_sel_out, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "doa_track_contrast";
+    CtRun run{};
+    run.cs = CtSettings{ev_cls, n_classes, frames, search, guard, min_frames, weight, bg_frames_out, bg_sel_out};
+    SED_TRY(ct_check(who, E, run.cs));
+    run.pcm = pcm; run.tables = tables; run.pad_mode = pad_mode;
+    run.cpb = (frames + TD_CHUNK - 1) / TD_CHUNK;
+    const TdExtra extra{ct_mask_bytes(R, ct_mask_frames(clips_host, R, channels, time_factor, hop)), run.cpb, ct_pre, &run};
+    TrkCtx tc;
+    size_t td_bytes;
+    SED_TRY(trk_check(who, false, clips_host, 0, R, channels, E, hop, max_lag, max_frames, steer_lags, D, Q, trig, dir_out, power_out, srp_out,
+                      block_chunks, nbr_off, nbr_idx, trk_len_out, trk_raw_out, trk_dir_out, trk_power_out, trk_map_out, workspace,
+                      workspace_bytes, tc, td_bytes, extra.tab_bytes, extra.chunks));
+    tc.contrast = &run;
+    return tdoa_entry(who, {pcm, false, 0, pcm_len, R, channels, clips_host},
+                      {ev_rec, ev_onset, ev_offset, ev_peak_frame, nullptr, nullptr, E, time_factor, hop, max_frames, 0},
+                      {tables, tables_bytes, pad_mode, max_lag, 0, 0}, {lag_out, strength_out, frames_out, acc_out}, workspace, td_bytes,
+                      stream, trk_hook, &tc, &extra);
 }

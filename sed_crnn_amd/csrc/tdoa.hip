@@ -35,24 +35,17 @@
 #include "common.h"
 #include "fft2048.h"
 #include "tdoa_shared.h"
+#include "tdoa_accum.h"
 
-#define TD_WAVES 8
-#define TD_THREADS (TD_WAVES * 64)
-#define TD_TAB_WORDS LM_OFF_ENT                   // of the log-mel blob: header, window, inter-pass and pairing twiddles
-#define TD_FFT_SCR (2 * LM_SCR)                   // floats of exchange scratch per transforming wave
-#define TD_LDS_MAX ((size_t)160 * 1024)
-#define TD_FIN_THREADS 256
+#define TD_FIN_THREADS 256                        // (the accumulate kernel's sizes: tdoa_accum.h)
 
 // (TdArgs, td_event_range and the workspace's row layout: tdoa_shared.h, shared with doa.hip)
 namespace {
 
-// RING: the channels are rings (TdArgs.cap); a frame that does not wrap takes the same 8-byte loads, one that does goes through
-// the guarded loads, and either way the registers hold the same samples: everything after the loads is one code.
+// The chunk's frames are f0 + fc0 .. of the event; the body is td_accum_chunk (tdoa_accum.h), which contrast.hip runs on other frames.
 template <bool RING>
 __global__ __launch_bounds__(TD_THREADS) void tdoa_accum_k(const float* __restrict__ pcm, const uint32_t* __restrict__ tables,
                                                            float2* __restrict__ ws, int pad_mode, TdArgs ta) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int tid = threadIdx.x;
     const long e = ta.e0 + blockIdx.y;
     int rec, nf;
     long f0;
@@ -60,85 +53,8 @@ __global__ __launch_bounds__(TD_THREADS) void tdoa_accum_k(const float* __restri
     const int fc0 = blockIdx.x * TD_CHUNK;                       // the chunk's first frame, counted from f0
     if (fc0 >= nf) return;                                       // (block-uniform: before any barrier)
     const int fc1 = fc0 + TD_CHUNK < nf ? fc0 + TD_CHUNK : nf;
-    fft_stage_tables(lds, tables, TD_TAB_WORDS, tid, TD_THREADS);
-    const f2* s_win = reinterpret_cast<const f2*>(lds + LM_OFF_WIN);
-    const f2* s_tw = reinterpret_cast<const f2*>(lds + LM_OFF_TW);
-    const f2* s_pw = reinterpret_cast<const f2*>(lds + LM_OFF_PW);
-    const int C = ta.C, P = ta.P;
-    const int nfw = (C + 1) >> 1;                                // waves that transform
-    const bool pipe = ta.pipelined != 0;
-    float2* s_spec = reinterpret_cast<float2*>(lds + TD_TAB_WORDS);                              // [1 or 2][C][PHAT_SPEC]
-    float* s_scr = lds + TD_TAB_WORDS + (pipe ? 2 : 1) * C * PHAT_SPEC * 2;                      // [nfw][TD_FFT_SCR]
-    float2* s_acc = reinterpret_cast<float2*>(s_scr + nfw * TD_FFT_SCR);                         // [batch][PHAT_SPEC]
-
-    const int wave = tid >> 6;
-    float* wscr = s_scr + (wave < nfw ? wave : 0) * TD_FFT_SCR;  // (only used by waves < nfw)
-    const FftLane fl = fft_lane(tid & 63, wscr - lds);
-    const int half = fl.half(), r = fl.r();
-    float* scr = wscr + half * LM_SCR;
-    const long ns = ta.n_samples[rec];
-    float2* wrow = ws + ((long)blockIdx.y * ta.cpe + blockIdx.x) * P * PHAT_SPEC;
-    // Pipelined (the spectra fit twice, C <= 4): in step s the transforming waves fill buffer s & 1 with frame s while the other
-    // waves whiten frame s - 1 from the other buffer; one barrier per step.  Otherwise every wave whitens, between two barriers.
-    // Either way an accumulator entry belongs to one lane and receives the frames in ascending order: the same sums.
-    const int wt0 = pipe ? nfw * 64 : 0, wstride = TD_THREADS - wt0;
-    const int n_fr = fc1 - fc0;
-
-    for (int p0 = 0; p0 < P; p0 += ta.pairs_per_batch) {
-        const int nb = (P - p0 < ta.pairs_per_batch) ? P - p0 : ta.pairs_per_batch;
-        for (int idx = tid; idx < nb * PHAT_SPEC; idx += TD_THREADS) s_acc[idx] = make_float2(0.f, 0.f);
-        __syncthreads();                                         // the tables are in LDS (first batch); the spectra are free
-        for (int step = 0; step < n_fr + (pipe ? 1 : 0); ++step) {
-            const long frame = f0 + fc0 + step;
-            if (wave < nfw && step < n_fr) {
-                // ── the frame of channel 2 wave + half (an odd C: the last half wave repeats channel C-1 and stores the same values) ──
-                const int ch = (2 * wave + half < C) ? 2 * wave + half : C - 1;
-                const float* cpcm = pcm + (RING ? ((long)rec * C + ch) * ta.cap : ta.sample_off[(long)rec * C + ch]);
-                const long start = frame * ta.hop - LM_NFFT / 2;
-                // RING: sample i lives at i % cap while max(0, ns - cap) <= i < ns; `pos` is the frame's first sample in the ring
-                const long kept = RING && ns > ta.cap ? ns - ta.cap : 0;
-                long pos = 0;
-                if (RING) { pos = start % ta.cap; if (pos < 0) pos += ta.cap; }
-                const bool fast = (ta.hop & 1) == 0 && (reinterpret_cast<uintptr_t>(cpcm) & 7) == 0 && start >= kept && start + LM_NFFT <= ns &&
-                                  (!RING || pos + LM_NFFT <= ta.cap);
-                auto sample = [&](int off) -> float {            // sample start + off of the channel, 0 <= off < 2048
-                    if (!RING) return pcm_at(cpcm, start + off, ns, pad_mode);
-                    const long i = start + off, p = pos + off;   // (cap >= 2048: p < 2 cap)
-                    return i >= kept && i < ns ? cpcm[p >= ta.cap ? p - ta.cap : p] : 0.f;
-                };
-                f2 z[32];                                        // z[n] = (x[2n], x[2n+1]): one complex point per VGPR pair
-                if (__all(fast)) {
-                    const f2* src = reinterpret_cast<const f2*>(cpcm + (RING ? pos : start)) + r;
-#pragma unroll
-                    for (int n1 = 0; n1 < 32; ++n1) z[n1] = src[32 * n1];
-                } else {                                         // edge frames / odd hop / unaligned clips / a frame that wraps
-                    fft_load_guarded(z, scr, fl, sample);
-                }
-                fft2048_passes(z, fl, s_win, s_tw);
-                fft2048_spectrum(z, fl, s_pw, s_spec + ((pipe ? (step & 1) : 0) * C + ch) * PHAT_SPEC);
-            }
-            if (!pipe) __syncthreads();
-            // ── Pk of the batch's pairs, added to the accumulators.  Entry idx is read and written by this lane alone, frame
-            //    after frame. ──
-            const int wf = pipe ? step - 1 : step;               // the frame of the chunk whose spectra are whitened now
-            const float2* wspec = s_spec + (pipe ? (wf & 1) : 0) * C * PHAT_SPEC;
-            for (int idx = wf >= 0 && tid >= wt0 ? tid - wt0 : nb * 1025; idx < nb * 1025; idx += wstride) {
-                const int pb = idx / 1025, k = idx - pb * 1025;
-                int i, j;
-                phat_pair(p0 + pb, C, i, j);
-                const float2 pk = phat_bin(wspec[i * PHAT_SPEC + k], wspec[j * PHAT_SPEC + k], k);
-                float2 s = s_acc[pb * PHAT_SPEC + k];
-                s.x += pk.x; s.y += pk.y;
-                s_acc[pb * PHAT_SPEC + k] = s;
-            }
-            __syncthreads();                                     // the spectra (of this buffer) may be overwritten
-        }
-        for (int idx = tid; idx < nb * 1025; idx += TD_THREADS) {
-            const int pb = idx / 1025, k = idx - pb * 1025;
-            wrow[(long)(p0 + pb) * PHAT_SPEC + k] = s_acc[pb * PHAT_SPEC + k];
-        }
-        __syncthreads();                                         // the accumulators are zeroed for the next batch
-    }
+    float2* wrow = ws + ((long)blockIdx.y * ta.cpe + blockIdx.x) * ta.P * PHAT_SPEC;
+    td_accum_chunk<RING>(pcm, tables, wrow, pad_mode, ta, rec, fc1 - fc0, [&](int step) -> long { return f0 + fc0 + step; });
 }
 
 // One (persistent) workgroup per event at a time: every pair of the event in turn.
@@ -210,30 +126,20 @@ __global__ __launch_bounds__(TD_FIN_THREADS) void tdoa_finish_k(const uint32_t* 
     }
 }
 
-// LDS of the accumulate kernel for C channels with `batch` pairs of accumulators resident and 1 or 2 spectra buffers
-size_t tdoa_lds_bytes(int C, int batch, int buffers) {
-    return ((size_t)TD_TAB_WORDS + (size_t)buffers * C * PHAT_SPEC * 2 + (size_t)((C + 1) / 2) * TD_FFT_SCR + (size_t)batch * PHAT_SPEC * 2) * sizeof(float);
-}
-
-// chunk slots per event: no event is located on more than min(max_frames, the longest recording's frames) frames
-long tdoa_chunks_per_event(long max_rec_frames, int max_frames) {
-    const long f = max_rec_frames < max_frames ? max_rec_frames : max_frames;
-    return (f + TD_CHUNK - 1) / TD_CHUNK;
-}
-
 // What both entries share once their recordings are checked: the argument checks, the upload of the recording table and the
 // two launches per slice of the event table.  A ring's longest "recording" is its capacity: no located event has more than
 // 1 + cap / hop frames.
 template <bool RING>
 int tdoa_run(const char* who, const RecSource& src, const EvTable& ev, const TdSettings& st, const TdOut& out, void* workspace,
-             size_t workspace_bytes, void* stream, TdSliceHook hook, void* hook_ctx) {
+             size_t workspace_bytes, void* stream, TdSliceHook hook, void* hook_ctx, const TdExtra* extra) {
     const int channels = src.C, P = channels * (channels - 1) / 2;
     const long E = ev.E;
-    const size_t tab = src.tab;
+    const size_t tab = src.tab + (extra ? extra->tab_bytes : 0);  // (the activity mask lies behind the table)
     SED_REQUIRE(ev.onset && ev.offset && ev.peak && out.lag && out.strength && out.frames && workspace, "%s: null pointer", who);
     SED_REQUIRE(ev.rec || src.R == 1, "%s: %d recordings need ev_rec", who, src.R);
     SED_REQUIRE(((uintptr_t)workspace & 15) == 0, "%s: workspace must be 16-byte aligned", who);
-    const long cpe = tdoa_chunks_per_event(1 + (RING ? src.cap : src.longest) / ev.hop, ev.max_frames);
+    const long own = tdoa_chunks_per_event(1 + (RING ? src.cap : src.longest) / ev.hop, ev.max_frames);
+    const long cpe = own + (extra ? extra->chunks : 0);           // (... and an event's background chunks behind its own)
     SED_REQUIRE(cpe <= 0x7fffffffL, "%s: too many chunks per event", who);         // (gridDim.x and TdArgs.cpe; frames are < 2^31)
     const size_t per_event = (size_t)cpe * P * TD_ROW_BYTES;
     SED_REQUIRE(workspace_bytes >= tab + per_event, "%s: workspace of %zu bytes, at least %zu needed (one event)", who, workspace_bytes,
@@ -252,6 +158,7 @@ int tdoa_run(const char* who, const RecSource& src, const EvTable& ev, const TdS
 
     hipStream_t s = as_stream(stream);
     SED_TRY(rec_upload(who, src, workspace, s));
+    if (extra && extra->pre) SED_TRY(extra->pre(extra->ctx, src, ev, workspace, s));
     const hipError_t err = hipFuncSetAttribute((const void*)tdoa_accum_k<RING>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TD_LDS_MAX);
     if (err != hipSuccess) { sed_set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(err)); return (int)err; }
     TdArgs ta = td_args(src, ev, workspace);
@@ -262,7 +169,7 @@ int tdoa_run(const char* who, const RecSource& src, const EvTable& ev, const TdS
     for (long e0 = 0; e0 < E; e0 += slice) {
         ta.e0 = e0;
         ta.n_ev = (int)(E - e0 < slice ? E - e0 : slice);
-        tdoa_accum_k<RING><<<dim3((unsigned)cpe, (unsigned)ta.n_ev), TD_THREADS, lds, s>>>(src.x, tables, part, st.pad_mode, ta);
+        tdoa_accum_k<RING><<<dim3((unsigned)own, (unsigned)ta.n_ev), TD_THREADS, lds, s>>>(src.x, tables, part, st.pad_mode, ta);
         SED_LAUNCH_CHECK(RING ? "event_tdoa_ring (accumulate)" : "event_tdoa (accumulate)");
         const int blocks = ta.n_ev < 2048 ? ta.n_ev : 2048;
         tdoa_finish_k<<<blocks, TD_FIN_THREADS, 0, s>>>(tables, part, out.lag, out.strength, out.frames, out.acc, ta);
@@ -304,7 +211,7 @@ extern "C" size_t sed_event_tdoa_workspace_bytes(int R, int channels, long E, lo
 // the host side of sed_event_tdoa / sed_event_tdoa_ring (src.ring) and, with a hook, of their DOA siblings: each form keeps its
 // own checks in its own order
 int tdoa_entry(const char* who, RecSource src, const EvTable& ev, const TdSettings& st, const TdOut& out, void* workspace,
-               size_t workspace_bytes, void* stream, TdSliceHook hook, void* hook_ctx) {
+               size_t workspace_bytes, void* stream, TdSliceHook hook, void* hook_ctx, const TdExtra* extra) {
     SED_REQUIRE(src.C >= 2 && src.C <= TD_MAX_CH, "%s: 2 to %d channels, got %d", who, TD_MAX_CH, src.C);
     SED_REQUIRE(st.max_lag >= 1 && st.max_lag <= TD_MAX_LAG, "%s: max_lag must be in [1,%d], got %d", who, TD_MAX_LAG, st.max_lag);
     SED_REQUIRE(ev.max_frames >= 1, "%s: max_frames must be >= 1, got %d", who, ev.max_frames);
@@ -323,8 +230,8 @@ int tdoa_entry(const char* who, RecSource src, const EvTable& ev, const TdSettin
                 st.tables_bytes);
     SED_TRY(!src.ring ? rec_source_linear(who, src, ev.hop) : rec_source_ring(who, src, ev.hop));
     if (ev.E == 0) return 0;                                     // nothing to launch
-    return !src.ring ? tdoa_run<false>(who, src, ev, st, out, workspace, workspace_bytes, stream, hook, hook_ctx)
-                     : tdoa_run<true>(who, src, ev, st, out, workspace, workspace_bytes, stream, hook, hook_ctx);
+    return !src.ring ? tdoa_run<false>(who, src, ev, st, out, workspace, workspace_bytes, stream, hook, hook_ctx, extra)
+                     : tdoa_run<true>(who, src, ev, st, out, workspace, workspace_bytes, stream, hook, hook_ctx, extra);
 }
 
 extern "C" int sed_event_tdoa(const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const void* tables,

@@ -169,6 +169,16 @@ inline TdArgs td_args(const RecSource& src, const EvTable& ev, const void* works
 struct TdSettings { const void* tables; size_t tables_bytes; int pad_mode, max_lag, lat, hist; };
 struct TdOut { float *lag, *strength; int* frames; float* acc; };
 
-// sed_event_tdoa / sed_event_tdoa_ring (src.ring) with the entry's name for the messages and an optional hook (tdoa.hip)
+// What an entry may add to the run: `tab_bytes` of its own between the recording table and the partials (a multiple
+// of 16), `chunks` more chunk slots behind every event's own (TdArgs.cpe counts both; the accumulate launch fills the own ones),
+// and a step `pre` that is run once, on the same stream, after the table's upload and before the first slice.
+struct TdExtra {
+    size_t tab_bytes;
+    int chunks;
+    int (*pre)(void* ctx, const RecSource& src, const EvTable& ev, void* workspace, hipStream_t stream);
+    void* ctx;
+};
+
+// sed_event_tdoa / sed_event_tdoa_ring (src.ring) with the entry's name for the messages, an optional hook and extra (tdoa.hip)
 int tdoa_entry(const char* who, RecSource src, const EvTable& ev, const TdSettings& st, const TdOut& out, void* workspace,
-               size_t workspace_bytes, void* stream, TdSliceHook hook, void* hook_ctx);
+               size_t workspace_bytes, void* stream, TdSliceHook hook, void* hook_ctx, const TdExtra* extra = nullptr);

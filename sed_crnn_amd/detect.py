@@ -33,6 +33,7 @@ _TRACK_KEYS = ("trk_len", "trk_raw", "trk_dir", "trk_power")   # ... and, with D
 _BEAM_KEYS = ("audio_start", "audio_len")               # ... and, with extract=DelaySum(...), its place in result.audio
 _NOISE_KEYS = ("noise_frames",)                         # ... and, with extract=MVDR(noise_blocks >= 1), the pre-onset frames its weights used (5u)
 _QUIET_KEYS = ("noise_sel",)                            # ... and, with noise_select="quiet", which candidates they are (5w; offline only)
+_CONTRAST_KEYS = ("bg_frames", "bg_sel")                # ... and, with DOA(..., contrast=Contrast(...)), the background frames of its map (5z)
 
 
 def _doa_angles(events, grid, k):
@@ -324,12 +325,26 @@ class DetectionResult:
         ``extract=sed.MVDR(noise_blocks >= 1)``: otherwise AttributeError."""
         return _noise_frames(self)
 
+    @property
+    def bg_frames(self):
+        """int32 [E] on the device: the background frames every event's contrasted map was made with — up to ``Contrast.frames``, or
+        0 for an event whose map is the plain one.  Only on the result of a detector with
+        ``localize=sed.DOA(..., contrast=sed.Contrast(...))``: otherwise AttributeError."""
+        return _bg_frames(self)
+
 
 def _noise_frames(result):
     if "noise_frames" not in result.events:
         raise AttributeError("this result holds no noise_frames: detect with EventDetector(..., localize=sed.DOA(...), "
                              "extract=sed.MVDR(noise_blocks=...))")
     return result.events["noise_frames"]
+
+
+def _bg_frames(result):
+    if "bg_frames" not in result.events:
+        raise AttributeError("this result holds no bg_frames: detect with EventDetector(..., localize=sed.DOA(..., "
+                             "contrast=sed.Contrast(...)))")
+    return result.events["bg_frames"]
 
 
 def _event_audio(result, e):
@@ -364,7 +379,7 @@ class BatchDetectionResult:
         i = int(i) % R
         o0, o1 = self.out_offsets[i], self.out_offsets[i + 1]
         e0, e1 = self.event_offsets[i], self.event_offsets[i + 1]
-        keys = _EVENT_KEYS + tuple(k for k in _TDOA_KEYS + _DOA_KEYS + _TRACK_KEYS + _BEAM_KEYS + _NOISE_KEYS + _QUIET_KEYS if k in self.events)
+        keys = _EVENT_KEYS + tuple(k for k in _TDOA_KEYS + _DOA_KEYS + _TRACK_KEYS + _BEAM_KEYS + _NOISE_KEYS + _QUIET_KEYS + _CONTRAST_KEYS if k in self.events)
         return DetectionResult(self.probs[o0:o1], {k: self.events[k][e0:e1] for k in keys}, self.frame_seconds, self.plans[i], self.sr,
                                self.grid, self.audio, self.track)
 
@@ -382,6 +397,13 @@ class BatchDetectionResult:
         an event that fell back to its own frames or was not extracted.  Only on the result of a detector with
         ``extract=sed.MVDR(noise_blocks >= 1)``: otherwise AttributeError."""
         return _noise_frames(self)
+
+    @property
+    def bg_frames(self):
+        """int32 [E] on the device: the background frames every event's contrasted map was made with — up to ``Contrast.frames``, or
+        0 for an event whose map is the plain one.  Only on the result of a detector with
+        ``localize=sed.DOA(..., contrast=sed.Contrast(...))``: otherwise AttributeError."""
+        return _bg_frames(self)
 
     def __iter__(self):
         return (self[i] for i in range(len(self)))
@@ -415,7 +437,10 @@ class EventDetector:
     ``localize=sed.DOA(positions, grid, ...)`` for a known array: the same three keys, with ``max_lag`` taken from the
     array's aperture, and ``dir`` [E] (a row of ``grid``, -1: not located) and ``doa_power`` [E] (``events.event_doa``;
     ``result.doa()`` in radians); with ``sed.DOA(..., track=sed.DirectionTrack(block_chunks, max_step_deg))`` also a direction
-    per block of the event's located frames, ``trk_len`` [E], ``trk_raw``, ``trk_dir`` and ``trk_power`` [E, Tm] (``result.doa_track(e)``).  ``extract=sed.DelaySum(...)`` (needs ``localize=sed.DOA(...)``): every located event
+    per block of the event's located frames, ``trk_len`` [E], ``trk_raw``, ``trk_dir`` and ``trk_power`` [E, Tm] (``result.doa_track(e)``).
+    With ``sed.DOA(..., contrast=sed.Contrast(...))`` (offline only) the directions are made after the share of the sources
+    that sound before the onset is removed — an event over a louder source of another class gets its own direction — the class
+    count is the model's, and the events also hold ``bg_frames`` [E] (``result.bg_frames``) and ``bg_sel`` [E, frames].  ``extract=sed.DelaySum(...)``(needs ``localize=sed.DOA(...)``): every located event
     also comes with its audio, the array pointed at ``dir`` by a delay-and-sum beam (``events.event_beamform`` on the PCM that
     is kept anyway): ``audio_start`` / ``audio_len`` [E] in the events, the packed float32 buffer ``result.audio`` and
     ``result.event_audio(e)``; ``from_features*`` returns events without audio, ``det.localize`` adds it, ``det.stream`` of such a
@@ -668,8 +693,9 @@ class EventDetector:
         t = self.localize_settings
         with torch.no_grad():
             if self.locates_directions:
+                contrast = dict(n_classes=self.model.dense[-1]) if t.contrast is not None else {}   # the class count is the model's
                 loc = event_doa(pcm, clips, self.audio_channels, result.events, self.model.time_factor, t, sr=self.sr,
-                                        hop=self.hop_length)
+                                        hop=self.hop_length, **contrast)
                 result.grid, result.track = t.grid, self._track_info()
             else:
                 loc = event_tdoa(pcm, clips, self.audio_channels, result.events, self.model.time_factor, max_lag=t.max_lag,
@@ -682,7 +708,7 @@ class EventDetector:
                              self.extract_settings, sr=self.sr, hop=self.hop_length, **quiet)
                 result.audio = beam.pop("audio")
                 loc.update(beam)
-        result.events = {**{k: v for k, v in result.events.items() if k not in _TDOA_KEYS + _DOA_KEYS + _TRACK_KEYS + _BEAM_KEYS + _NOISE_KEYS + _QUIET_KEYS}, **loc}
+        result.events = {**{k: v for k, v in result.events.items() if k not in _TDOA_KEYS + _DOA_KEYS + _TRACK_KEYS + _BEAM_KEYS + _NOISE_KEYS + _QUIET_KEYS + _CONTRAST_KEYS}, **loc}
         result.sr = self.sr
         return result
 
@@ -933,6 +959,9 @@ class EventDetector:
                 Tm = self.localize_settings.track.max_blocks(self.localize_settings.max_frames)
                 out.update(trk_len=torch.empty(0, dtype=torch.int32, device=dev), trk_raw=torch.empty(0, Tm, dtype=torch.int32, device=dev),
                            trk_dir=torch.empty(0, Tm, dtype=torch.int32, device=dev), trk_power=torch.empty(0, Tm, device=dev))
+            if self.localize_settings.contrast is not None:
+                out.update(bg_frames=torch.empty(0, dtype=torch.int32, device=dev),
+                           bg_sel=torch.empty(0, self.localize_settings.contrast.frames, dtype=torch.int32, device=dev))
         if self.extract_settings is not None:
             out.update(audio_start=torch.empty(0, dtype=torch.int64, device=dev), audio_len=torch.empty(0, dtype=torch.int32, device=dev))
         if getattr(self.extract_settings, "noise_blocks", 0):

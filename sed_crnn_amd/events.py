@@ -18,6 +18,7 @@ from .feature import GCC_MAX_CHANNELS, HOP, NB_MEL, NFFT, SR, _LM_OFF_ENT, _clip
 _ENTRY = {("tdoa", False): "sed_event_tdoa", ("tdoa", True): "sed_event_tdoa_ring",
           ("doa", False): "sed_event_doa", ("doa", True): "sed_event_doa_ring",
           ("doa_track", False): "sed_event_doa_track", ("doa_track", True): "sed_event_doa_track_ring",
+          ("doa_contrast", False): "sed_event_doa_contrast", ("doa_track_contrast", False): "sed_event_doa_track_contrast",
           ("spans", False): "sed_event_beam_spans", ("spans", True): "sed_event_beam_spans_ring",
           ("delay_sum", False): "sed_event_beamform", ("delay_sum", True): "sed_event_beamform_ring",
           ("mvdr", False): "sed_event_mvdr", ("mvdr", True): "sed_event_mvdr_ring",
@@ -168,12 +169,27 @@ def _track_io(doa, E, dev, out, return_map):
             ptr(out.get("trk_map"))]
 
 
-def _locate(src, events, tf, hop, max_lag, max_frames, settings, return_curve, max_workspace_bytes, doa):
+def _contrast_classes(who, n_classes):
+    """the class count of a contrast call, checked"""
+    from .localize import CONTRAST_MAX_CLASSES
+    if n_classes is None:
+        raise ValueError(f"{who} with sed.DOA(..., contrast=sed.Contrast(...)) needs n_classes, the number of classes the events' cls column "
+                         f"counts in")
+    if isinstance(n_classes, bool) or int(n_classes) != n_classes or not 1 <= int(n_classes) <= CONTRAST_MAX_CLASSES:
+        raise ValueError(f"{who}: n_classes must be an integer in [1, {CONTRAST_MAX_CLASSES}] (an activity word has {CONTRAST_MAX_CLASSES} "
+                         f"bits), got {n_classes!r}")
+    return int(n_classes)
+
+
+def _locate(src, events, tf, hop, max_lag, max_frames, settings, return_curve, max_workspace_bytes, doa, n_classes=None):
     """what the four TDOA / DOA functions do once their arguments are checked.  ``settings``: what the C entry takes between ``hop``
     and its outputs; ``doa``: None, or (the ``localize.DOA``, the rate of the PCM, return_map) for the same launches and one more
-    per slice"""
+    per slice; with ``doa.contrast`` (linear only) the entry takes the ``cls`` column behind ``rec``, the
+    class count and the six settings behind ``settings`` and ``bg_frames`` / ``bg_sel`` behind its outputs"""
     R, nc, dev = src.R, src.nc, src.x.device
-    col, E = _cols(src, events, _LOCATED[:3])
+    ct = getattr(doa[0], "contrast", None) if doa is not None else None
+    classes = _contrast_classes("event_doa", n_classes) if ct is not None else None
+    col, E = _cols(src, events, _LOCATED[:3] + (("cls",) if ct is not None else ()))
     P, W = nc * (nc - 1) // 2, 2 * max_lag + 3
     out = {"lag": torch.empty(E, P, device=dev), "strength": torch.empty(E, P, device=dev),
            "loc_frames": torch.empty(E, dtype=torch.int32, device=dev)}
@@ -183,11 +199,19 @@ def _locate(src, events, tf, hop, max_lag, max_frames, settings, return_curve, m
     track = doa is not None and getattr(doa[0], "track", None) is not None          # a direction per block too
     if track:
         extra = (extra or []) + (_track_io(doa[0], E, dev, out, doa[2]) or [])
+    if ct is not None:
+        out["bg_frames"] = torch.zeros(E, dtype=torch.int32, device=dev)
+        out["bg_sel"] = torch.full((E, ct.frames), -1, dtype=torch.int32, device=dev)
+        extra = (extra or []) + [ptr(out["bg_frames"]), ptr(out["bg_sel"])]
+        settings = list(settings) + [classes, ct.frames, ct.search, ct.guard, ct.min_frames, ct.weight]
     if E == 0:
         return out
     tables = _tables(dev.index or 0, SR, NFFT, NB_MEL)                # the window and the twiddles; the mel plan is not read
-    sizes = _ENTRY["doa_track" if track else "tdoa", src.ring] + "_workspace_bytes"   # (the steering launch reads the partials in place)
+    kind = "tdoa" if doa is None else ("doa_track" if track else "doa") + ("_contrast" if ct is not None else "")
+    sizes = _ENTRY[kind if track or ct is not None else "tdoa", src.ring] + "_workspace_bytes"   # (the steering launch reads the partials in place)
     more = [len(doa[0].grid), doa[0].track.block_chunks, int(doa[0].track.max_step_deg is not None)] if track else []
+    if ct is not None:                                                # the mask lies behind the table, once per call
+        more += [_mask_frames(src, tf, hop), ct.frames]
     need_one = getattr(lib(), sizes)(R, nc, 1, src.extent, hop, max_frames, *more)
     need_all = getattr(lib(), sizes)(R, nc, E, src.extent, hop, max_frames, *more)
     if need_one == 0:
@@ -195,14 +219,18 @@ def _locate(src, events, tf, hop, max_lag, max_frames, settings, return_curve, m
                          if src.ring else
                          f"sed_event_tdoa_workspace_bytes refuses R={R}, channels={nc}, hop={hop}, max_frames={max_frames}")
     ws = torch.empty(min(need_all, max(need_one, int(max_workspace_bytes))), dtype=torch.uint8, device=dev)
-    name = _ENTRY["tdoa" if doa is None else "doa_track" if track else "doa", src.ring]
-    check(getattr(lib(), name)(*src.head, ptr(tables), tables.numel() * 4, *_col_ptrs(col, _LOCATED[:3]), E, tf, hop, *settings,
+    name = _ENTRY[kind, src.ring]
+    cols = _col_ptrs(col, _LOCATED[:3])
+    if ct is not None:
+        cols = cols[:1] + [ptr(col["cls"])] + cols[1:]
+    check(getattr(lib(), name)(*src.head, ptr(tables), tables.numel() * 4, *cols, E, tf, hop, *settings,
                                ptr(out["lag"]), ptr(out["strength"]), ptr(out["loc_frames"]), ptr(out.get("acc")), *extra, ptr(ws),
                                ws.numel(), stream_ptr()), name)
     return out
 
 
-def _tdoa_linear(pcm, clips, channels, events, time_factor, max_lag, max_frames, hop, pad_mode, return_curve, max_workspace_bytes, doa):
+def _tdoa_linear(pcm, clips, channels, events, time_factor, max_lag, max_frames, hop, pad_mode, return_curve, max_workspace_bytes, doa,
+                 n_classes=None):
     """``event_tdoa`` (``doa`` None) and ``event_doa``"""
     from .localize import MAX_LAG_LIMIT
     _need_pcm("event_tdoa", pcm)
@@ -216,7 +244,7 @@ def _tdoa_linear(pcm, clips, channels, events, time_factor, max_lag, max_frames,
         raise ValueError(f"event_tdoa needs 1 <= max_lag <= {MAX_LAG_LIMIT}, max_frames >= 1, time_factor >= 1 and hop >= 1, got "
                          f"max_lag={max_lag}, max_frames={max_frames}, time_factor={tf}, hop={hop}")
     src = _linear_source(pcm, clips, nc)
-    return _locate(src, events, tf, hop, max_lag, max_frames, [pad, max_lag, max_frames], return_curve, max_workspace_bytes, doa)
+    return _locate(src, events, tf, hop, max_lag, max_frames, [pad, max_lag, max_frames], return_curve, max_workspace_bytes, doa, n_classes)
 
 
 def _tdoa_ring(ring, cap, n, channels, events, time_factor, max_lag, max_frames, hop, lat_frames, history_frames, return_curve,
@@ -260,7 +288,7 @@ def event_tdoa(pcm, clips, channels, events, time_factor, max_lag=24, max_frames
 
 
 def event_doa(pcm, clips, channels, events, time_factor, doa, sr=SR, hop=HOP, pad_mode="constant", return_curve=False,
-              return_map=False, max_workspace_bytes=128 << 20):
+              return_map=False, max_workspace_bytes=128 << 20, n_classes=None):
     """Per-event direction of arrival for a known array (``sed_event_doa``): ``event_tdoa`` with ``max_lag`` and
     ``max_frames`` taken from ``doa`` (a ``sed.DOA(positions, grid, ...)``; ``sr``: the rate of the PCM), and for every event
     the direction of ``doa.grid`` with the largest steered response power, summed over all microphone pairs at lags of
@@ -276,9 +304,58 @@ def event_doa(pcm, clips, channels, events, time_factor, doa, sr=SR, hop=HOP, pa
     ``trk_dir`` int32 [E, Tm], the best path through the block maps that turns by at most ``max_step_deg`` a block (-1 where
     ``trk_raw`` is; ``trk_raw`` itself without ``max_step_deg``); ``trk_power`` float32 [E, Tm], the block's response at
     ``trk_raw`` per pair and frame; and with ``return_map=True`` ``trk_map`` float32 [E, Tm, D].  No frame is transformed twice:
-    the blocks are steered from the chunk sums the event's own direction is made from."""
+    the blocks are steered from the chunk sums the event's own direction is made from.
+
+    With ``doa.contrast`` set (a ``sed.Contrast(frames, search, guard, min_frames, weight)``; ``sed_event_doa_contrast`` /
+    ``sed_event_doa_track_contrast``) the events must also hold ``cls`` and ``n_classes`` in 1..32 — what ``cls`` counts
+    in — is required.  ``lag``, ``strength``, ``loc_frames`` and ``acc`` keep their bits; ``dir``, ``doa_power``, ``srp`` and every
+    ``trk_`` key are made from ``S' = S - weight (nf / nb) Sb``, with ``Sb`` the summed whitened cross spectrum of the nb frames
+    before the onset that ``localize.Contrast`` describes: an event that sounds over a louder source of another class gets its
+    own direction, not that source's.  The dict gains ``bg_frames`` int32 [E], nb (0: fewer than ``min_frames`` were found and
+    every key of the event is the plain one, bit for bit), and ``bg_sel`` int32 [E, frames], the candidates q in summation order,
+    -1 behind them (``event_contrast_frames`` returns the two alone).  Every row of the table marks activity, located or not, and
+    the activity is made once from the whole table, whatever the slicing.  An event's outputs then depend on its own samples and
+    those of its background frames alone."""
     return _tdoa_linear(pcm, clips, channels, events, time_factor, 24, getattr(doa, "max_frames", 256), hop, pad_mode, return_curve,
-                        max_workspace_bytes, (doa, sr, return_map))
+                        max_workspace_bytes, (doa, sr, return_map), n_classes)
+
+
+def event_contrast_frames(clips, channels, events, time_factor, doa, n_classes, hop=HOP):
+    """Which frames before its onset ``event_doa`` with ``doa = sed.DOA(..., contrast=sed.Contrast(...))`` makes every event's background
+    spectrum from (``sed_event_contrast_frames``): the activity and the selection alone, no sample is read.  ``clips`` /
+    ``channels`` as ``event_doa`` takes them (the lengths of the recordings are all that is used); ``events``: the table with
+    ``cls`` — every row marks activity, located or not; ``n_classes`` in 1..32: what ``cls`` counts in.  Returns device tensors
+    ``{"bg_frames": int32 [E], "bg_sel": int32 [E, frames]}``: the number of frames used (0: the event's map is the plain one) and
+    their candidates q — candidate q is feature frame ``onset * tf - guard - 1 - q`` — in summation order, -1 behind them.  Integer
+    throughout and a function of the table and the settings alone; the host reads nothing back."""
+    from .localize import DOA
+    nc, tf, hop = _beam_sizes("event_contrast_frames", channels, time_factor, hop)
+    if not isinstance(doa, DOA) or doa.contrast is None:
+        raise TypeError("event_contrast_frames takes the settings as a sed.DOA(..., contrast=sed.Contrast(...)) object")
+    if doa.channels != nc:
+        raise ValueError(f"the DOA settings hold {doa.channels} microphone positions, the audio has {nc} channels")
+    ct, classes = doa.contrast, _contrast_classes("event_contrast_frames", n_classes)
+    dev = events["onset"].device if isinstance(events.get("onset"), torch.Tensor) else None
+    if dev is None or dev.type != "cuda":
+        raise RuntimeError("sed_crnn_amd.feature.event_contrast_frames needs the event columns as CUDA(HIP) tensors; there is no CPU fallback")
+    table = np.ascontiguousarray(np.asarray(clips, dtype=np.int64).reshape(-1, 2))
+    table = _clip_table(clips, nc, int((table[:, 0] + table[:, 1]).max()) if table.size else 0, at_least_one=True)
+    R = table.shape[0] // nc
+    col, E = _event_cols(events, R, "rec", _LOCATED[:3] + ("cls",), dev)
+    out = {"bg_frames": torch.zeros(E, dtype=torch.int32, device=dev), "bg_sel": torch.full((E, ct.frames), -1, dtype=torch.int32, device=dev)}
+    if E == 0:
+        return out
+    frames = int((table[::nc, 1] // (tf * hop) + 1).sum())
+    need = lib().sed_event_contrast_frames_workspace_bytes(R, nc, frames, ct.frames)
+    if need == 0:
+        raise ValueError(f"sed_event_contrast_frames_workspace_bytes refuses R={R}, channels={nc}, {frames} output frames, frames={ct.frames}")
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    cols = _col_ptrs(col, _LOCATED[:3])
+    check(lib().sed_event_contrast_frames(int((table[:, 0] + table[:, 1]).max()), C.c_void_p(table.ctypes.data), R, nc, cols[0], ptr(col["cls"]),
+                                          *cols[1:], E, tf, hop, doa.max_frames, classes, ct.frames, ct.search, ct.guard, ct.min_frames,
+                                          ptr(out["bg_frames"]), ptr(out["bg_sel"]), ptr(ws), ws.numel(), stream_ptr()),
+          "sed_event_contrast_frames")
+    return out
 
 
 def event_tdoa_ring(ring, cap, n, channels, events, time_factor, max_lag=24, max_frames=256, hop=HOP, lat_frames=0,
@@ -300,7 +377,11 @@ def event_doa_ring(ring, cap, n, channels, events, time_factor, doa, sr=SR, hop=
                    return_curve=False, return_map=False, max_workspace_bytes=128 << 20):
     """``event_doa`` on the PCM rings of live feeds (``sed_event_doa_ring``): the arguments and rules of
     ``event_tdoa_ring``, the outputs of ``event_doa``; an event the stream's rule or the ring's depth refuses has ``dir = -1``
-    and ``doa_power = 0``.  A located event gets, bit for bit, what ``event_doa`` gives on the feed's samples laid out linearly."""
+    and ``doa_power = 0``.  A located event gets, bit for bit, what ``event_doa`` gives on the feed's samples laid out linearly.
+    A ``doa`` with ``contrast=`` has no ring form yet: NotImplementedError."""
+    if getattr(doa, "contrast", None) is not None:
+        raise NotImplementedError("event_doa_ring: sed.DOA(..., contrast=...) has no ring form yet (it needs search + guard more feature "
+                                  "frames of ring and a per-feed activity ring); locate on the recording (event_doa)")
     return _tdoa_ring(ring, cap, n, channels, events, time_factor, 24, getattr(doa, "max_frames", 256), hop, lat_frames, history_frames,
                       return_curve, max_workspace_bytes, (doa, sr, return_map))
 

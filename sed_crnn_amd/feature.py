@@ -554,4 +554,4 @@ def build_fold_packs(per_video, cache_dir, device="cuda"):
 
 # The entries over an event table live in events.py and stay importable from here.  This line stays LAST: events.py imports names
 # of this module while it is still being executed (whichever of the two is imported first) and may use what stands above only.
-from .events import event_beamform, event_beamform_ring, event_doa, event_doa_ring, event_mvdr, event_mvdr_ring, event_quiet_frames, event_tdoa, event_tdoa_ring, ring_write  # noqa: E402,F401
+from .events import event_beamform, event_beamform_ring, event_contrast_frames, event_doa, event_doa_ring, event_mvdr, event_mvdr_ring, event_quiet_frames, event_tdoa, event_tdoa_ring, ring_write  # noqa: E402,F401

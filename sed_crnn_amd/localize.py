@@ -15,7 +15,9 @@ fractional-delay filter, the delay every direction means for every microphone, a
 ``MVDR`` and ``mvdr_window`` are the host side of the adaptive beam that extracts the same events (the kernels are
 csrc/mvdr.hip, the device entry ``events.event_mvdr``).  ``DirectionTrack``, ``track_blocks`` and ``track_neighbours`` are the host side
 of direction tracks (the kernels are csrc/doatrack.hip): the settings of ``DOA(..., track=DirectionTrack(...))``, the
-blocks an event's located frames are cut into, and the directions a smoothed track may step between.
+blocks an event's located frames are cut into, and the directions a smoothed track may step between.  ``Contrast`` holds the settings
+of contrast SRP-PHAT (the kernels are csrc/contrast.hip): ``DOA(..., contrast=Contrast(...))`` locates an event that sounds
+over a louder source of another class.
 """
 import dataclasses
 import functools
@@ -303,6 +305,54 @@ def track_neighbours(grid, max_step_deg):
     return off.astype(np.int32), np.ascontiguousarray(np.concatenate(rows).astype(np.int32))
 
 
+# ── contrast SRP-PHAT ──
+CONTRAST_MAX_FRAMES = 256      # contrast.hip: CT_MAX_FRAMES
+CONTRAST_MAX_SEARCH = 4096     #               CT_MAX_SEARCH
+CONTRAST_MAX_GUARD = 64        #               CT_MAX_GUARD
+CONTRAST_MAX_CLASSES = 32      #               CT_MAX_CLASSES, the bits of an activity word
+CONTRAST_MAX_WEIGHT = 4.0      #               CT_MAX_WEIGHT
+
+
+@dataclasses.dataclass(frozen=True)
+class Contrast:
+    """Settings of contrast SRP-PHAT (``sed.DOA(positions, grid, ..., contrast=Contrast(...))``): the direction of an event
+    that sounds over a louder source of another class.  PHAT whitening gives every frequency bin to whichever source is loudest
+    in it, so the plain map of such an event peaks at the louder source.  In feature frames before the onset in which the
+    event's own class is silent that source sounds and the event does not: their summed whitened cross spectrum ``Sb``, scaled
+    to the event's frames, is subtracted from the event's ``S`` before the map is steered, ``S' = S - weight (nf / nb) Sb``.
+    The bins the other source wins cancel, the bins the event wins stay.
+
+    Candidate q = 0 .. ``search`` - 1 is feature frame ``onset * tf - guard - 1 - q``; it is eligible when no row of the event
+    table with the event's class is active in an output frame its 2048 samples touch (other classes never block a candidate:
+    they are what is subtracted).  The ``frames`` nearest eligible candidates make ``Sb``, as long as there are at least
+    ``min_frames`` of them — else the event's map is the plain one, bit for bit.  ``frames`` in [1, 256], ``search`` in
+    [``frames``, 4096], ``guard`` in [0, 64], ``min_frames`` in [1, ``frames``], ``weight`` finite in (0, 4].  ``bg_frames`` in the
+    results is the number of frames used and ``bg_sel`` [E, frames] lists their q in summation order (-1 behind them).  The
+    events need ``cls`` and the calls the number of classes.  Offline only."""
+    frames: int = 32
+    search: int = 256
+    guard: int = 2
+    min_frames: int = 8
+    weight: float = 1.0
+
+    def __post_init__(self):
+        for name, least, most in (("frames", 1, CONTRAST_MAX_FRAMES), ("search", 1, CONTRAST_MAX_SEARCH), ("guard", 0, CONTRAST_MAX_GUARD),
+                                  ("min_frames", 1, CONTRAST_MAX_FRAMES)):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not least <= int(v) <= most:
+                raise ValueError(f"Contrast: {name} must be an integer in [{least}, {most}], got {v!r}")
+            object.__setattr__(self, name, int(v))
+        if self.search < self.frames:
+            raise ValueError(f"Contrast: search must be at least frames = {self.frames}, got {self.search}")
+        if self.min_frames > self.frames:
+            raise ValueError(f"Contrast: min_frames must be at most frames = {self.frames}, got {self.min_frames}")
+        w = self.weight
+        if isinstance(w, bool) or not isinstance(w, (int, float, np.floating, np.integer)) or not math.isfinite(float(w)) \
+                or not 0.0 < float(w) <= CONTRAST_MAX_WEIGHT:
+            raise ValueError(f"Contrast: weight must be a finite number in (0, {CONTRAST_MAX_WEIGHT:g}], got {w!r}")
+        object.__setattr__(self, "weight", float(w))
+
+
 class DOA:
     """Settings of per-event direction of arrival (``EventDetector(model, ..., localize=DOA(positions, grid))``):
     steered response power (SRP-PHAT) over ``grid`` for the microphones at ``positions`` [C, 3] (metres, in the order of the
@@ -310,9 +360,10 @@ class DOA:
     exactly.  ``max_frames`` as in ``TDOA``; ``max_lag`` follows from the array: ``max_lag_for`` of its largest spacing at the
     detector's rate, which must not exceed 127 samples.  ``c``: the speed of sound in m/s.  A detector with these settings
     also returns everything a ``TDOA(max_lag, max_frames)`` detector returns.  ``track``: None, or a ``DirectionTrack``: every
-    event also gets a direction per block of its located frames."""
+    event also gets a direction per block of its located frames.  ``contrast``: None, or a ``Contrast``: the map of
+    every event — and of every block — is made after the share of the sources that sound before its onset is removed."""
 
-    def __init__(self, positions, grid, max_frames=256, oversample=8, c=SPEED_OF_SOUND, track=None):
+    def __init__(self, positions, grid, max_frames=256, oversample=8, c=SPEED_OF_SOUND, track=None, contrast=None):
         r = _positions(positions, "DOA")
         if not isinstance(grid, DirectionGrid):
             raise TypeError(f"DOA: grid must be a DirectionGrid, got {type(grid).__name__}")
@@ -337,6 +388,9 @@ class DOA:
                                  f"blocks an event, more than {TRACK_MAX_BLOCKS}; use a larger block_chunks")
             self._neighbours, self._neighbours_device = {}, {}   # per max_step_deg: track_neighbours of the grid; per device: its copy
         self.track = track
+        if contrast is not None and not isinstance(contrast, Contrast):
+            raise TypeError(f"DOA: contrast must be None or a Contrast(...), got {type(contrast).__name__}")
+        self.contrast = contrast
         r.setflags(write=False)
         self.positions, self.grid = r, grid
         self.max_frames, self.oversample, self.c = int(max_frames), int(oversample), float(c)
@@ -402,7 +456,8 @@ class DOA:
 
     def __repr__(self):
         return (f"DOA({self.channels} microphones, aperture {self.aperture:.4g} m, {len(self.grid)} directions, max_frames={self.max_frames}, "
-                f"oversample={self.oversample}, c={self.c:g}" + (f", track={self.track!r}" if self.track is not None else "") + ")")
+                f"oversample={self.oversample}, c={self.c:g}" + (f", track={self.track!r}" if self.track is not None else "") +
+                (f", contrast={self.contrast!r}" if self.contrast is not None else "") + ")")
 
 
 # ── the audio of a located event: a steered delay-and-sum beam ──

@@ -259,6 +259,11 @@ class StreamDetector:
         self.det = _det if _det is not None else EventDetector(model, **kw)
         det, m = self.det, self.det.model
         self.emit_audio = bool(emit_audio)
+        if getattr(det.localize_settings, "contrast", None) is not None:
+            raise NotImplementedError("sed.DOA(..., contrast=sed.Contrast(...)) is offline only so far; live feeds are a follow-up: the rule "
+                                      "already reads only feature frames before the onset and only the event's own class, which is final "
+                                      "when the event is emitted, but it needs search + guard more feature frames of ring and a per-feed "
+                                      "activity ring (DESIGN 5z); make the stream from a detector without contrast=")
         if det.extract_settings is not None and not self.emit_audio:
             raise NotImplementedError("live feeds extract audio only when asked to: a detector with extract=sed.DelaySum(...) or "
                                       "sed.MVDR(...) streams with emit_audio=True (and history_frames=), which costs one more "
