@@ -83,3 +83,8 @@ __device__ __forceinline__ void wino_pack_one(const float* __restrict__ w, float
 int sed_internal_wino_rows(int B, int Cin, int F, int T, int Cout);
 int sed_internal_wino_launch(const float* x, const float* uq, const float* bias, float* y, float* stat, const ConvBnRed* br,
                              int rgc, int B, int Cin, int F, int T, int Cout, hipStream_t s);
+// the kernel's prologue index math run on the host (tests only, not part of the ABI): the workgroup mapping and the 14 patch-DMA
+// byte offsets (0x80000000: zero padding) of one lane, or of every lane of the launch (out [B][grid x][4][64][14], map [B][grid x][3])
+extern "C" int sed_internal_wino_patch_offsets(int B, int F, int T, int Cout, int block_x, int block_y, int wave, int lane,
+                                               unsigned* out, int* b, int* blka, int* coh);
+extern "C" int sed_internal_wino_patch_offsets_grid(int B, int F, int T, int Cout, unsigned* out, int* map);

@@ -20,6 +20,12 @@
 //     8 positions per KiB, quad-major inside ([quad][position]): a wave's DMA covers 8 whole positions (coalesced), a lane's
 //     ds_read_b128 of (position, quad) is conflict-free over consecutive positions, and the k-group g of a step is an
 //     immediate offset.  Mel columns are stored even ones first, so that the tiles of a row are consecutive positions.
+//   * prologue: a workgroup can do nothing before its first slice has arrived, so what stands in front of the first request is
+//     paid in full by every workgroup.  The workgroup mapping is scalar multiplies by reciprocals prepared on the host (WinoDiv),
+//     the lane's 14 offsets come from one decode and a carry per KiB block (WinoWalk), each request leaves as soon as its offset
+//     is known, and the step-0 weight fragments follow the 14th: about 110 instructions in front of the first request, none of
+//     them a division or an exec-masked block (tests/test_cpu_wino_prologue_isa.py); the same helpers run on the host
+//     (sed_internal_wino_patch_offsets, tests/test_cpu_wino_offsets.py).
 //   * the input transform happens in registers on the way to the A operand: wave xi reads the two time rows of its row
 //     combination (B^T d: d0 - d2, d1 + d2, d2 - d1, d1 - d3), 4 columns each, and forms the four column combinations on
 //     register PAIRS (v_pk_fma_f32 / v_pk_add_f32): 16 ds_read_b128 + 32 vector instructions per 64 MFMAs, shared by both
@@ -44,10 +50,26 @@
 typedef __attribute__((address_space(1))) const void* sed_gptr_t;
 typedef __attribute__((address_space(3))) void* sed_lptr_t;
 
+// n / d for 0 <= n < 2^31 as one multiplication and a shift: m = ceil(2^s / d), s = 31 + ceil(log2 d).  Exact: with e = m d - 2^s
+// (0 <= e < d <= 2^(s-31)) the product is n / d + n e / (d 2^s), and n e < 2^s keeps the excess below 1 / d.  (sed_fdiv is exact
+// only below 2^20; a workgroup index may exceed that at very large batches.)
+struct WinoDiv { unsigned m; int s; };
+__host__ __device__ __forceinline__ int wn_div(int n, WinoDiv d) { return (int)(((unsigned long long)(unsigned)n * d.m) >> d.s); }
+static WinoDiv wn_div_make(int d) {
+    int l = 0;
+    while (((long long)1 << l) < d) ++l;
+    const unsigned long long p = (unsigned long long)1 << (31 + l);
+    return WinoDiv{(unsigned)((p + (unsigned)d - 1) / (unsigned)d), 31 + l};
+}
+
 struct WinoGeo {
     int Fw;        // tiles per row of a COLUMN GROUP (the mel axis is cut into ncg groups of Fw tiles when a whole row's patch is too large)
     int ncg, Tw, ntile, nblk, TR, F2, H2, HR, nb8, ncoh, NH;      // ntile / nblk: per sequence and column group
-    float invFw, invF2;
+    float invFw;
+    // the workgroup mapping and the patch walk without a division (wino_workgroup, wino_patch_offsets): reciprocals of ncoh, nba = nblk x ncg,
+    // Fw and F2, ncg = 1 << ncg_sh, and one KiB block of the patch further on = 32 positions = q32 rows + r32 columns of F2
+    WinoDiv d_ncoh, d_nba, d_Fw, d_F2;
+    int nba, ncg_sh, q32, r32;
     size_t lds;
     unsigned long long* dbg;      // measurement only (sed_conv3x3_wino_phase_ticks): per-phase s_memrealtime sums, NULL in production
 };
@@ -110,7 +132,12 @@ static bool wino_geo(int B, int Cin, int F, int T, int Cout, WinoGeo* g) {
     if (!ok) return false;
     g->NH = WN_NHMAX;
     g->ncoh = Cout / 64;
-    g->invFw = 1.0f / (float)g->Fw; g->invF2 = 1.0f / (float)g->F2;
+    g->invFw = 1.0f / (float)g->Fw;
+    g->nba = g->nblk * g->ncg;
+    g->d_ncoh = wn_div_make(g->ncoh); g->d_nba = wn_div_make(g->nba); g->d_Fw = wn_div_make(g->Fw); g->d_F2 = wn_div_make(g->F2);
+    g->ncg_sh = 0;
+    while ((1 << g->ncg_sh) < g->ncg) ++g->ncg_sh;
+    g->q32 = 32 / g->F2; g->r32 = 32 % g->F2;
     // two patch buffers; the epilogue's exchange of the four waves' partial output transforms (4 x 2 x 2 x 2 tiles of 4 KB) + the
     // statistics exchange reuse them; the row table behind
     size_t fl = (size_t)2 * g->NH * 1024;
@@ -123,6 +150,116 @@ static bool wino_geo(int B, int Cin, int F, int T, int Cout, WinoGeo* g) {
 int sed_internal_wino_rows(int B, int Cin, int F, int T, int Cout) {
     WinoGeo g;
     return wino_geo(B, Cin, F, T, Cout, &g) ? B * g.nblk * g.ncg : 0;
+}
+
+// ───────────────────────── the prologue's index math (kernel and host: sed_internal_wino_patch_offsets) ─────────────────────────
+// workgroup -> (sequence, tile block x column group, channel half).  Workgroups are dealt round-robin to the 8 XCDs in launch order:
+// the channel halves of a block and the blocks of a sequence are given to the same XCD (they share the input patch through its L2).
+// Everything here is workgroup-uniform: scalar multiplies and shifts on the reciprocals wino_geo prepared, exact for every grid it
+// accepts (an index stays far below 2^31: B x T x F x 128 < 2^32).  The grid is (nba x ncoh, B) by construction of the launcher.
+struct WinoWg { int b, blka, coh, blk, cgp, ty0; };
+__host__ __device__ __forceinline__ WinoWg wino_workgroup(const WinoGeo& g, int B, int bx, int by) {
+    // B a multiple of 8: workgroup id = 8 j + xcd, j = (sequence / 8, blka, coh), sequence = 8 (j / (nba ncoh)) + xcd; otherwise
+    // block_x = (blka, coh) and block_y the sequence — the same two divisions with j = block_x, whose second quotient is 0 then.
+    // (Selects, not a branch: every kernel argument is requested in one go.)
+    WinoWg w;
+    const bool xo = (B & 7) == 0;
+    const int id = by * (g.nba * g.ncoh) + bx, j = xo ? id >> 3 : bx;
+    const int jj = wn_div(j, g.d_ncoh), bq = wn_div(jj, g.d_nba);
+    w.coh = j - jj * g.ncoh;
+    w.blka = jj - bq * g.nba;
+    w.b = xo ? (id & 7) + 8 * bq : by;
+    w.blk = w.blka >> g.ncg_sh;                          // neighbouring column groups are neighbours in launch order
+    w.cgp = w.blka - (w.blk << g.ncg_sh);
+    w.ty0 = wn_div(w.blk * 64, g.d_Fw);                  // first tile row of the block
+    return w;
+}
+
+// The byte offsets, inside the workgroup's sequence, of the patch positions a lane requests per 32-channel slice: KiB block
+// k = 4 u + wave, lane = 8 quad + position-in-block, position P_u = (4 u + wave) 8 + (lane & 7) of the patch of (2 TR + 2) time rows x
+// F2 columns (even mel columns first).  P_0 = (tt, cx) is decoded once; a block further on is 32 positions = q32 rows + r32 columns
+// with at most one wrap of the column (r32 < F2), and the byte offset follows by two additions.  Zero padding — the frame around the
+// (time, mel) plane, a position past the patch — gets `oob`.  In range means: tt inside [tlo, tlo + tn) (the patch rows that lie
+// inside the plane) and cx inside [clo, clo + cn) (cx = 0 is the column left of the first column group, cx = F2 - 1 the one right
+// of the last); both walk as distances from their lower bound, so a test is one unsigned compare.  Selects only, no branch.
+struct WinoWalk {
+    int F2, r32, q32, cw, ch;                    // uniform
+    unsigned tn, cn, step, wrap, odd;
+    int ta, ca;                                  // the lane's (tt - tlo, cx - clo)
+    unsigned lin;                                // byte offset of (tt, mel column 2 cx of the group): the unfolding of the odd columns comes off in offset()
+    __host__ __device__ __forceinline__ WinoWalk(const WinoGeo& g, const WinoWg& w, int F, int T, int wave, int lane) {
+        F2 = g.F2; r32 = g.r32; q32 = g.q32;
+        const int t0 = 2 * w.ty0 - 1;                    // the patch's first time row (-1: the frame)
+        const int tlo = t0 < 0 ? 1 : 0, thi = 2 * g.TR + 2 < T - t0 ? 2 * g.TR + 2 : T - t0;
+        const int clo = w.cgp == 0 ? 1 : 0, chi = w.cgp == g.ncg - 1 ? F2 - 1 : F2;
+        tn = (unsigned)(thi - tlo); cn = (unsigned)(chi - clo);
+        const unsigned rowb = (unsigned)F * (WN_CIN * 4);        // bytes of a time row
+        step = (unsigned)q32 * rowb + (unsigned)r32 * (2 * WN_CIN * 4); wrap = rowb - (unsigned)F2 * (2 * WN_CIN * 4);
+        odd = (unsigned)(F2 - 1) * (WN_CIN * 4);                 // cx >= H2 is mel column 2 (cx - H2) + 1 = 2 cx - (F2 - 1) of the group
+        cw = F2 - clo; ch = g.H2 - clo;
+        const int P0 = wave * 8 + (lane & 7);
+        const int tt = wn_div(P0, g.d_F2), cx = P0 - tt * F2;
+        ta = tt - tlo; ca = cx - clo;
+        lin = (unsigned)(t0 + tt) * rowb + (unsigned)(2 * w.cgp * g.Fw - 1) * (WN_CIN * 4) + (unsigned)cx * (2 * WN_CIN * 4) + (unsigned)(lane >> 3) * 16u;
+    }
+    __host__ __device__ __forceinline__ unsigned offset(unsigned oob) const {
+        const bool in = (unsigned)ta < tn && (unsigned)ca < cn;
+        return in ? lin - (ca >= ch ? odd : 0u) : oob;
+    }
+    __host__ __device__ __forceinline__ void next() {    // 32 positions on
+        ca += r32;
+        const bool c = ca >= cw;
+        ca -= c ? F2 : 0;
+        ta += q32 + (c ? 1 : 0);
+        lin += step + (c ? wrap : 0u);
+    }
+};
+template <int NH>
+__host__ __device__ __forceinline__ void wino_patch_offsets(const WinoGeo& g, const WinoWg& w, int F, int T, int wave, int lane,
+                                                            unsigned oob, unsigned (&hp)[NH]) {
+    WinoWalk k(g, w, F, T, wave, lane);
+#pragma unroll
+    for (int u = 0; u < NH; ++u) {
+        hp[u] = k.offset(oob);
+        k.next();
+    }
+}
+
+// The same helpers on the host (tests/test_cpu_wino_offsets.py): what workgroup (block_x, block_y) of the launch for this shape is
+// mapped to, and the WN_NHMAX offsets lane `lane` of wave `wave` requests there.
+extern "C" int sed_internal_wino_patch_offsets(int B, int F, int T, int Cout, int block_x, int block_y, int wave, int lane,
+                                               unsigned* out, int* b, int* blka, int* coh) {
+    WinoGeo g;
+    SED_REQUIRE(out && b && blka && coh, "wino_patch_offsets: null pointer");
+    SED_REQUIRE(wino_geo(B, WN_CIN, F, T, Cout, &g), "wino_patch_offsets: shape B=%d F=%d T=%d Cout=%d is not supported (sed_conv3x3_wino_rows)", B, F, T, Cout);
+    SED_REQUIRE(block_x >= 0 && block_x < g.nba * g.ncoh && block_y >= 0 && block_y < B && wave >= 0 && wave < 4 && lane >= 0 && lane < 64,
+                "wino_patch_offsets: workgroup (%d, %d), wave %d, lane %d outside the launch", block_x, block_y, wave, lane);
+    const WinoWg w = wino_workgroup(g, B, block_x, block_y);
+    unsigned hp[WN_NHMAX];
+    wino_patch_offsets<WN_NHMAX>(g, w, F, T, wave, lane, 0x80000000u, hp);
+    for (int u = 0; u < WN_NHMAX; ++u) out[u] = hp[u];
+    *b = w.b; *blka = w.blka; *coh = w.coh;
+    return 0;
+}
+// ... of every workgroup, wave and lane of the launch: out [B][grid x][4][64][WN_NHMAX], map [B][grid x][3] = (b, blka, coh)
+extern "C" int sed_internal_wino_patch_offsets_grid(int B, int F, int T, int Cout, unsigned* out, int* map) {
+    WinoGeo g;
+    SED_REQUIRE(out && map, "wino_patch_offsets_grid: null pointer");
+    SED_REQUIRE(wino_geo(B, WN_CIN, F, T, Cout, &g), "wino_patch_offsets_grid: shape B=%d F=%d T=%d Cout=%d is not supported (sed_conv3x3_wino_rows)", B, F, T, Cout);
+    const int gx = g.nba * g.ncoh;
+    for (int by = 0; by < B; ++by)
+        for (int bx = 0; bx < gx; ++bx) {
+            const size_t i = (size_t)by * gx + bx;
+            const WinoWg w = wino_workgroup(g, B, bx, by);
+            map[i * 3 + 0] = w.b; map[i * 3 + 1] = w.blka; map[i * 3 + 2] = w.coh;
+            for (int wave = 0; wave < 4; ++wave)
+                for (int lane = 0; lane < 64; ++lane) {
+                    unsigned hp[WN_NHMAX];
+                    wino_patch_offsets<WN_NHMAX>(g, w, F, T, wave, lane, 0x80000000u, hp);
+                    for (int u = 0; u < WN_NHMAX; ++u) out[((i * 4 + wave) * 64 + lane) * WN_NHMAX + u] = hp[u];
+                }
+        }
+    return 0;
 }
 
 // packed fp32 pairs (see the kernel)
@@ -163,34 +300,17 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_k(
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, h = lane >> 5;
-    unsigned long long tk0 = 0, tk1 = 0, tk2 = 0;
-    if (geo.dbg) tk0 = __builtin_amdgcn_s_memrealtime();
+    // (the start stamp is read whether or not anybody asks for it: a branch here would split the kernel-argument loads in two, and
+    // the second half's round trip would stand in front of the first patch request)
+    unsigned long long tk1 = 0, tk2 = 0;
+    const unsigned long long tk0 = __builtin_amdgcn_s_memrealtime();
+    __builtin_amdgcn_sched_barrier(0);                 // (the stamp stays in front of the index math)
 
-    // workgroup -> (sequence, tile block, channel half).  Workgroups are dealt round-robin to the 8 XCDs in launch order: the
-    // channel halves of a block and the blocks of a sequence are given to the same XCD (they share the input patch through its L2)
-    int blka, coh, b;                                  // blka = block x column group of the sequence
-    {
-        const int bx = blockIdx.x, by = blockIdx.y, nba = geo.nblk * geo.ncg;
-        if ((gridDim.y & 7) == 0) {
-            const int id = by * (int)gridDim.x + bx, xcd = id & 7, j = id >> 3;
-            coh = j % geo.ncoh;
-            const int jj = j / geo.ncoh;
-            b = xcd + 8 * (jj / nba);
-            blka = jj % nba;
-        } else {
-            coh = bx % geo.ncoh; blka = bx / geo.ncoh; b = by;
-        }
-    }
-    const int blk = blka / geo.ncg, cgp = blka - blk * geo.ncg;      // neighbouring column groups are neighbours in launch order
-    const int fg0 = 2 * cgp * geo.Fw;                                   // first mel column of the group
-    const int Fw = geo.Fw, F2 = geo.F2, H2 = geo.H2, ntile = geo.ntile;
-    const int q0 = blk * 64, ty0 = q0 / Fw;
-    const int co0 = coh * 64;
-
-    // this wave's row combination of B^T d: rows (ra, rb), d[ra] + sg d[rb]
-    const int ra = wave == 0 ? 0 : (wave == 2 ? 2 : 1);
-    const int rb = wave == 0 ? 2 : (wave == 1 ? 2 : (wave == 2 ? 1 : 3));
-    const float sg = wave == 1 ? 1.f : -1.f;
+    // workgroup -> (sequence, tile block x column group, channel half): wino_workgroup, scalar multiplies and shifts (the grid is
+    // (nba x ncoh, B): nothing is read from the dispatch packet)
+    const WinoWg wg = wino_workgroup(geo, B, (int)blockIdx.x, (int)blockIdx.y);
+    const int blka = wg.blka, coh = wg.coh, b = wg.b;  // blka = block x column group of the sequence
+    const int blk = wg.blk, cgp = wg.cgp, ty0 = wg.ty0;
 
     // patch staging (LDS-DMA): item = KiB block k = 4 u + wave, lane = 8 quad + position-in-block.  Every lane of every block issues
     // (no branch: the loads interleave with the MFMAs).  The loads go through a buffer descriptor of this workgroup's sequence
@@ -202,30 +322,52 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_k(
     // answers 0 — into LDS too — and the lane can reach no neighbouring row or sequence.  (A select between two offsets, not a
     // masked or branched load: behind a branch hipcc no longer counts the loads in flight.)
     constexpr unsigned WN_OOB = 0x80000000u;
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)(x + (size_t)b * T * F * CIN), 0, T * F * CIN * 4, 0x00020000);
+    // (b T F < 2^25 — wino_geo: B T F 128 < 2^32 —, so the sequence's first element costs one 32-bit multiply and a shift)
+    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)(x + (size_t)(unsigned)(b * (T * F)) * CIN), 0, T * F * CIN * 4, 0x00020000);
+    // The offsets come from WinoWalk: one decode of the lane's first position, then a carry per block — no division, no reciprocal,
+    // no exec-masked block in front of a request.
     unsigned hp[NH];
-    {
-        const int Q = lane >> 3, pp = lane & 7;
-#pragma unroll
-        for (int u = 0; u < NH; ++u) {
-            const int P = (u * 4 + wave) * 8 + pp;
-            const int tt = sed_fdiv(P, geo.invF2), cx = P - tt * F2;
-            const int ff = cx < H2 ? 2 * cx : 2 * (cx - H2) + 1;
-            const int t = 2 * ty0 - 1 + tt, f = fg0 + ff - 1;
-            const bool in = P < geo.HR && t >= 0 && t < T && f >= 0 && f < F;
-            hp[u] = in ? (unsigned)((t * F + f) * CIN + Q * 4) * 4u : WN_OOB;
-        }
-    }
     auto issue_one = [&](int cc, float* buf, int u) {
         __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (sed_lptr_t)(buf + (u * 4 + wave) * 256), 16, (int)hp[u], cc * 128, 0, 0);
     };
-    auto issue = [&](int cc, float* buf) {
+    // The first slice is requested as soon as the workgroup knows where it is: in front of it stand the mapping and the offset walk
+    // only.  The step-0 weight fragments (a scalar base + a lane offset) follow directly, so that both round trips run under the
+    // rest of the set-up (operand offsets, the epilogue's tables, the RG input patch, the accumulators); what remains exposed of
+    // the DMA's latency is the workgroup's prologue.  DMAs first, fragments behind: vmcnt retires in order, and the prologue
+    // barrier waits for the DMAs with the 8 fragment loads still in flight (tests/test_cpu_wino_waits.py).  (Measured, profiles/r10:
+    // the walk is what shortened the prologue, 4.0 -> 2.7 us; where the fragment loads stand shows in no launch time.)
+    // Each block's request leaves as soon as its offset is known, the walk to the next block behind it.
+    {
+        WinoWalk walk(geo, wg, F, T, wave, lane);
 #pragma unroll
-        for (int u = 0; u < NH; ++u) issue_one(cc, buf, u);
+        for (int u = 0; u < NH; ++u) {
+            hp[u] = walk.offset(WN_OOB);
+            issue_one(0, smem, u);
+            __builtin_amdgcn_sched_barrier(0);
+            if (u + 1 < NH) walk.next();
+        }
+    }
+    const f32x4* wl = (const f32x4*)uq + (size_t)(coh * 16 + wave * 4) * (NCHUNK * 4 * 2 * 64);      // wave-uniform
+    f32x4 bq[4][2];
+    const unsigned lane16 = (unsigned)lane * 16u;
+    auto load_b = [&](int nu, int st) {
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt)          // (scalar base + 32-bit lane offset: the address costs scalar adds, no vector instruction)
+            bq[nu][nt] = *(const f32x4*)((const char*)(wl + ((nu * NSTEP + st) * 2 + nt) * 64) + lane16);
     };
-    // the first slice is requested before anything else is set up (its latency is the workgroup's prologue: 4.4 us)
-    issue(0, smem);
+#pragma unroll
+    for (int nu = 0; nu < 4; ++nu) load_b(nu, 0);
     __builtin_amdgcn_sched_barrier(0);
+
+    const int fg0 = 2 * cgp * geo.Fw;                                   // first mel column of the group
+    const int Fw = geo.Fw, F2 = geo.F2, H2 = geo.H2, ntile = geo.ntile;
+    const int q0 = blk * 64;
+    const int co0 = coh * 64;
+
+    // this wave's row combination of B^T d: rows (ra, rb), d[ra] + sg d[rb]
+    const int ra = wave == 0 ? 0 : (wave == 2 ? 2 : 1);
+    const int rb = wave == 0 ? 2 : (wave == 1 ? 2 : (wave == 2 ? 1 : 3));
+    const float sg = wave == 1 ? 1.f : -1.f;
 
     // LDS float offset of (patch position P, quad h) for the 2 m-tiles x 2 rows x 4 columns this lane reads every step
     int aoff[2][2][4];
@@ -279,14 +421,6 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_k(
 #pragma unroll
                 for (int j = 0; j < 16; ++j) acc[nu][mt][nt][j] = 0.f;
 
-    const f32x4* wl = (const f32x4*)uq + (size_t)(coh * 16 + wave * 4) * (NCHUNK * 4 * 2 * 64);      // wave-uniform
-    f32x4 bq[4][2];
-    const unsigned lane16 = (unsigned)lane * 16u;
-    auto load_b = [&](int nu, int st) {
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)          // (scalar base + 32-bit lane offset: the address costs scalar adds, no vector instruction)
-            bq[nu][nt] = *(const f32x4*)((const char*)(wl + ((nu * NSTEP + st) * 2 + nt) * 64) + lane16);
-    };
     // Operands of a step: vp[parity][mt][nu][half] — the four k values (j) of an MFMA group as two register PAIRS.  The input transform
     // runs on pairs (v_pk_fma_f32 / v_pk_add_f32, written out: hipcc splits <2 x float> arithmetic into scalar instructions): beside the
     // MFMAs an instruction costs its issue slot, not the vector ALU's time, so 32 instead of 64 per step.  Inline assembly is invisible to
@@ -359,9 +493,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_k(
         if (RG) btd[n] = bitq[off >> 4];
     };
 
-#pragma unroll
-    for (int nu = 0; nu < 4; ++nu) load_b(nu, 0);
-    __syncthreads();                                   // behind hipcc's counted wait for the 14 DMAs (the 8 fragment loads stay in flight)
+    __syncthreads();                                   // behind hipcc's counted wait for the 14 DMAs (the 8 step-0 fragment loads stay in flight)
 #pragma unroll
     for (int i = 0; i < 16; ++i) slot_read(smem, 0, i);
 #pragma unroll
