@@ -161,6 +161,39 @@ def bn_finalize_train(stat, count, gamma, beta, running_mean, running_var, momen
     return mean, rstd, scale, shift
 
 
+def bn_stat_sums(stat):
+    """stat [rows,2,C] partial rows -> sums [2,C] (sum x, sum x^2; double accumulation, rounded to fp32): the first half of the
+    multi-rank statistics, whose second half is bn_finalize_from_sums on the all-reduced sums"""
+    rows, _, Cc = stat.shape
+    sums = torch.empty(2, Cc, device=stat.device)
+    check(lib().sed_bn_stat_sums(ptr(_f32c(stat)), rows, Cc, ptr(sums), stream_ptr()), "bn_stat_sums")
+    return sums
+
+
+def bn_finalize_from_sums(sums, count, gamma, beta, running_mean, running_var, momentum=0.1, eps=1e-5):
+    Cc = sums.numel() // 2
+    mean, rstd, scale, shift = (torch.empty(Cc, device=sums.device) for _ in range(4))
+    check(lib().sed_bn_finalize_from_sums(ptr(_f32c(sums)), Cc, float(count), ptr(gamma), ptr(beta), ptr(running_mean),
+                                          ptr(running_var), momentum, eps, ptr(mean), ptr(rstd), ptr(scale), ptr(shift),
+                                          stream_ptr()), "bn_finalize_from_sums")
+    return mean, rstd, scale, shift
+
+
+def reduce_rows(part, Cc=None):
+    """part [rows, row_stride] -> out[c] = sum_r part[r, c] for the first Cc (default: all) columns"""
+    rows, stride = part.shape
+    Cc = stride if Cc is None else Cc
+    out = torch.empty(Cc, device=part.device)
+    check(lib().sed_reduce_rows(ptr(_f32c(part)), rows, Cc, stride, ptr(out), stream_ptr()), "reduce_rows")
+    return out
+
+
+def scale_(x, alpha):
+    """x *= alpha in place"""
+    check(lib().sed_scale(ptr(_f32c(x)), x.numel(), float(alpha), stream_ptr()), "scale")
+    return x
+
+
 def bn_finalize_eval(gamma, beta, rm, rv, eps=1e-5):
     Cc = gamma.numel()
     scale, shift = torch.empty(Cc, device=gamma.device), torch.empty(Cc, device=gamma.device)
