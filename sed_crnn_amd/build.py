@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libsedcrnn.so")
-SOURCES = ["api.cpp", "conv.hip", "conv_bf16.hip", "wino.hip", "conv1.hip", "bnpool.hip", "gemm.hip", "gru.hip", "misc.hip", "logmel.hip", "gcc.hip", "tdoa.hip", "doa.hip", "doatrack.hip", "contrast.hip", "beam.hip", "mvdr.hip", "pcen.hip", "resample.hip", "data.hip", "detect.hip", "tune.hip", "psds.hip", "stream.hip", "net.hip"]
+SOURCES = ["api.cpp", "conv.hip", "conv_bf16.hip", "wino.hip", "conv1.hip", "bnpool.hip", "gemm.hip", "gru.hip", "misc.hip", "logmel.hip", "gcc.hip", "tdoa.hip", "doa.hip", "doatrack.hip", "contrast.hip", "activity.hip", "beam.hip", "mvdr.hip", "pcen.hip", "resample.hip", "data.hip", "detect.hip", "tune.hip", "psds.hip", "stream.hip", "net.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # per-file extras.  logmel: the SLP vectoriser packs the FFT's scalar adds into v_pk_add_f32 and pays for it with ~600
 # v_mov per frame pair to build the register pairs (packed f32 is no faster than scalar on gfx950)
@@ -22,6 +22,7 @@ EXTRA_FLAGS = {"logmel.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-reso
                "doa.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"],
                "doatrack.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"],
                "contrast.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"],
+               "activity.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"],
                "beam.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"],
                "mvdr.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"],
                "pcen.hip": ["-Rpass-analysis=kernel-resource-usage"],
@@ -58,9 +59,10 @@ NO_SCRATCH_KERNELS = {"wino.hip": ("conv3x3_wino_k",),
                       # is one LDS read and a compare per neighbour: scratch in either would be the same silent cliff
                       "doatrack.hip": ("doa_track_steer_k", "doa_track_path_k"),
                       # contrast SRP-PHAT: the accumulate kernel is tdoa_accum_k's body on other frames, with the same FFT and
-                      # the same hazard; the activity and the selection kernel are a few integers per lane.  (The steer kernels that
-                      # subtract the background are instantiations of doa_steer_k and doa_track_steer_k: guarded above.)
-                      "contrast.hip": ("contrast_accum_k", "contrast_activity_k", "contrast_select_k"),
+                      # the same hazard; the selection kernel is a few integers per lane.  (The steer kernels that subtract the
+                      # background are instantiations of doa_steer_k and doa_track_steer_k: guarded above.)
+                      "contrast.hip": ("contrast_accum_k", "contrast_select_k"),
+                      "activity.hip": ("event_activity_k",),      # the activity mask of DESIGN 5w and 5z: a few integers per lane
                       # delay-and-sum beam: 8 outputs, 8 channel sums and a 16-sample window live per thread, indexed by unrolled
                       # loops; one of them in scratch would put a memory round trip on every fma of the launch's one loop
                       "beam.hip": ("beam_sum_k", "beam_spans_k"),
@@ -69,12 +71,12 @@ NO_SCRATCH_KERNELS = {"wino.hip": ("conv3x3_wino_k",),
                       # weight kernel keeps its matrices in LDS so that its float64 solve needs no scratch either; the ring forms
                       # (live feeds) are the same bodies behind another frame load, and so are the covariance kernels of the frames
                       # before the onset and of the frames where the event's class is silent, whose weight kernel is the
-                      # weight kernel's text once more; the activity and the selection kernel are a few integers per lane;
+                      # weight kernel's text once more; the selection kernel is a few integers per lane (the activity: activity.hip);
                       # the tracked kernels are the weight body with its solves in a loop over the track blocks and the
                       # apply body with the weight pointer taken per frame: the same hazards
                       "mvdr.hip": ("mvdr_cov_k", "mvdr_weights_k", "mvdr_apply_k", "mvdr_ring_cov_k", "mvdr_ring_apply_k", "mvdr_noise_k",
-                                   "mvdr_ring_noise_k", "mvdr_quiet_own_k", "mvdr_quiet_k", "mvdr_quiet_weights_k", "mvdr_activity_k",
-                                   "mvdr_select_k", "mvdr_trk_weights_k", "mvdr_trk_quiet_weights_k", "mvdr_trk_apply_k",
+                                   "mvdr_ring_noise_k", "mvdr_quiet_own_k", "mvdr_quiet_k", "mvdr_quiet_weights_k", "mvdr_select_k",
+                                   "mvdr_trk_weights_k", "mvdr_trk_quiet_weights_k", "mvdr_trk_apply_k",
                                    "mvdr_trk_ring_apply_k"),
                       # PCEN: the powers of (1-b) travel by value and are indexed in a loop; a copy of them in scratch, or a spilled
                       # powf, would turn a bandwidth-bound pass into a latency-bound one without failing any test
@@ -125,7 +127,7 @@ def check_no_spill(remarks, kernels, allow_agprs=False):
 def build(force=False, verbose=False):
     os.makedirs(OBJ, exist_ok=True)
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_shared.h"), os.path.join(CSRC, "detect_shared.h"), os.path.join(CSRC, "tune_shared.h"), os.path.join(CSRC, "fft2048.h"), os.path.join(CSRC, "tdoa_shared.h"), os.path.join(CSRC, "tdoa_accum.h"), os.path.join(CSRC, "contrast_shared.h"), os.path.join(CSRC, "phat_shared.h"), os.path.join(CSRC, "beam_shared.h"), os.path.join(HERE, "..", "include", "sedcrnn.h")]
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_shared.h"), os.path.join(CSRC, "detect_shared.h"), os.path.join(CSRC, "tune_shared.h"), os.path.join(CSRC, "fft2048.h"), os.path.join(CSRC, "tdoa_shared.h"), os.path.join(CSRC, "tdoa_accum.h"), os.path.join(CSRC, "contrast_shared.h"), os.path.join(CSRC, "activity_shared.h"), os.path.join(CSRC, "phat_shared.h"), os.path.join(CSRC, "beam_shared.h"), os.path.join(HERE, "..", "include", "sedcrnn.h")]
     jobs = []
     objs = []
     for src in SOURCES:

@@ -10,18 +10,17 @@
 // cancel, the bins the event wins stay.
 //
 // The rule is integer and reads the event table and the settings alone.  With H = tf hop and L_r = n_r / H + 1 output frames:
-//   mask[r][t]  bit cls of every row of the table for onset <= t < min(offset, L_r), located or not (DESIGN 5w's activity)
+//   mask[r][t]  bit cls of every row of the table for onset <= t < min(offset, L_r), located or not (DESIGN 5w's, activity.hip)
 //   candidate q = 0 .. S-1 of an event of class k whose first feature frame is a = onset tf: feature frame g = a - G - 1 - q,
 //   which exists when g >= 0 and is eligible when bit k of mask[r][t] is clear in every output frame its 2048 samples
 //   [g hop - 1024, g hop + 1024) touch: t = max(g hop - 1024, 0) / H .. min(ceil((g hop + 1024) / H), L_r) - 1
 //   the first Nb eligible candidates in ascending q are the event's background frames, nb of them; fewer than M: none (nb = 0)
 //   bg_sel[e][0 .. nb) lists them in summation order: descending q, ascending time; -1 behind them
 //
-// Shape (gfx950), plain launches, no workgroup waits on another, no atomics but the mask's OR:
-//   contrast_activity_k   a wave per row of the table, a lane per output frame: atomicOr from vector lanes, order-free
-//   contrast_select_k     a wave per event walks the candidates 64 at a time; a ballot and its prefix count rank the eligible
-//                         ones; the first Nb are written out reversed.  Both run once per call, over the whole table, before
-//                         the first slice.
+// Shape (gfx950), plain launches, no workgroup waits on another, no atomics but the mask's OR (event_activity_k's atomicOr):
+//   contrast_select_k     a wave per event gives its window to the shared walk (act_select_walk, activity_shared.h) over the
+//                         candidates 64 at a time; a ballot and its prefix count rank the eligible ones; the first Nb are written
+//                         out reversed.  Once per call, over the whole table, behind the activity launch, before the first slice.
 //   contrast_accum_k      per slice: one workgroup per chunk of 32 consecutive entries of an event's list, the body of
 //                         tdoa_accum_k (td_accum_chunk, tdoa_accum.h) on the frames a - G - 1 - bg_sel[e][j]; its partial goes to
 //                         the chunk rows behind the event's own.  A frame is loaded, transformed and whitened exactly as the
@@ -30,7 +29,6 @@
 // sum has one order, which depends on the event and its selected frames alone.
 #include <math.h>
 #include <cmath>
-#include <vector>
 #include "common.h"
 #include "fft2048.h"
 #include "tdoa_shared.h"
@@ -39,60 +37,17 @@
 
 namespace {
 
-// DESIGN 5w's activity, word for word: every row counts, located or not; out-of-range rows mark nothing
-__global__ __launch_bounds__(256) void contrast_activity_k(TdArgs ta, CtArgs ca) {
-    const int lane = threadIdx.x & 63;
-    const long H = (long)ta.tf * ta.hop;
-    for (long e = (long)blockIdx.x * 4 + (threadIdx.x >> 6); e < ca.E; e += (long)gridDim.x * 4) {
-        const int rec = ta.ev_rec ? ta.ev_rec[e] : 0, cls = ca.ev_cls[e];
-        const long on = ta.ev_onset[e];
-        if (rec < 0 || rec >= ta.R || cls < 0 || cls >= ca.n_classes || on < 0) continue;
-        const long L = ta.n_samples[rec] / H + 1;
-        long off = ta.ev_offset[e];
-        if (off > L) off = L;
-        uint32_t* row = ca.mask + ca.mask_off[rec];
-        for (long t = on + lane; t < off; t += 64) atomicOr(row + t, 1u << cls);
-    }
-}
-
+// other classes never block: they are what is subtracted; the window of candidate q is feature frame g0 - q's 2048 samples
 __global__ __launch_bounds__(64) void contrast_select_k(TdArgs ta, CtArgs ca) {
-    __shared__ int s_q[CT_MAX_FRAMES];
-    const int lane = threadIdx.x;
-    const long H = (long)ta.tf * ta.hop;
-    for (long e = blockIdx.x; e < ca.E; e += gridDim.x) {
+    for (long e = blockIdx.x; e < ca.act.E; e += gridDim.x) {
         int rec, nf;
         long f0;
         td_linear_range(ta, e, rec, f0, nf);
-        const int cls = ca.ev_cls[e];
-        int count = 0;
-        if (nf != 0 && cls >= 0 && cls < ca.n_classes) {         // (block-uniform)
-            const uint32_t own = 1u << cls;                      // other classes never block: they are what is subtracted
-            const uint32_t* row = ca.mask + ca.mask_off[rec];
-            const long L = ta.n_samples[rec] / H + 1;
-            const long g0 = (long)ta.ev_onset[e] * ta.tf - ca.guard - 1;         // candidate q is feature frame g0 - q
-            for (int q0 = 0; q0 < ca.search && count < ca.Nb && g0 - q0 >= 0; q0 += 64) {
-                const int q = q0 + lane;
-                const long g = g0 - q;
-                bool ok = q < ca.search && g >= 0;
-                if (ok) {
-                    long lo = g * ta.hop - LM_NFFT / 2;
-                    if (lo < 0) lo = 0;
-                    long t1 = (g * ta.hop + LM_NFFT / 2 + H - 1) / H;            // (g < the recording's frames: lo / H < L)
-                    if (t1 > L) t1 = L;
-                    for (long t = lo / H; t < t1 && ok; ++t) ok = (row[t] & own) == 0;
-                }
-                const unsigned long long m = __ballot(ok);
-                const int rank = count + __popcll(m & ((1ull << lane) - 1ull));
-                if (ok && rank < ca.Nb) s_q[rank] = q;
-                count += __popcll(m);
-            }
-            if (count > ca.Nb) count = ca.Nb;
-            if (count < ca.min_frames) count = 0;
-        }
-        __syncthreads();
-        for (int i = lane; i < ca.Nb; i += 64) ca.bg_sel[e * ca.Nb + i] = i < count ? s_q[count - 1 - i] : -1;
-        if (lane == 0) ca.bg_frames[e] = count;
-        __syncthreads();                                         // s_q is free for the next event
+        const int cls = ca.act.ev_cls[e];
+        const bool takes = nf != 0 && cls >= 0 && cls < ca.act.n_classes;            // (block-uniform)
+        const ActWindow w{((long)ta.ev_onset[e] * ta.tf - ca.guard - 1) * ta.hop, ta.hop, LM_NFFT / 2, LM_NFFT / 2, 0};
+        act_select_walk(ta, ca.act, takes, rec, takes ? 1u << cls : 0u, w, ca.Nb, ca.search, ca.min_frames, ca.bg_sel + e * ca.Nb,
+                        ca.bg_frames + e);
     }
 }
 
@@ -114,27 +69,9 @@ __global__ __launch_bounds__(TD_THREADS) void contrast_accum_k(const float* __re
     td_accum_chunk<false>(pcm, tables, wrow, pad_mode, ta, rec, fc1 - fc0, [&](int step) -> long { return g0 - sel[step]; });
 }
 
-size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 }  // namespace
 
-bool ct_sizes_ok(int R, long mask_frames, int frames) {
-    return R >= 1 && mask_frames >= R && mask_frames <= (1L << 40) && frames >= 1 && frames <= CT_MAX_FRAMES;
-}
-
-size_t ct_mask_bytes(int R, long frames) { return round16((size_t)R * sizeof(long)) + round16((size_t)frames * 4); }
-
-long ct_mask_frames(const long* clips_host, int R, int channels, int tf, int hop) {
-    if (!clips_host || R < 1 || channels < 1 || tf < 1 || hop < 1) return 0;
-    const long H = (long)tf * hop;
-    long frames = 0;
-    for (int r = 0; r < R; ++r) {
-        const long n = clips_host[2 * ((long)r * channels) + 1];
-        if (n < 1) return 0;
-        frames += n / H + 1;
-    }
-    return frames;
-}
+bool ct_sizes_ok(int R, long mask_frames, int frames) { return act_mask_ok(R, mask_frames) && frames >= 1 && frames <= CT_MAX_FRAMES; }
 
 int ct_check(const char* who, long E, const CtSettings& cs) {
     SED_REQUIRE(cs.frames >= 1 && cs.frames <= CT_MAX_FRAMES, "%s: frames must be in [1, %d], got %d", who, CT_MAX_FRAMES, cs.frames);
@@ -154,24 +91,10 @@ int ct_check(const char* who, long E, const CtSettings& cs) {
 int ct_pre(void* ctx, const RecSource& src, const EvTable& ev, void* workspace, hipStream_t s) {
     CtRun& run = *static_cast<CtRun*>(ctx);
     const CtSettings& cs = run.cs;
-    const long H = (long)ev.tf * ev.hop;
-    const long* n = src.h.data() + (size_t)src.R * src.C;
-    std::vector<long> off((size_t)src.R);
-    long frames = 0;
-    for (int r = 0; r < src.R; ++r) { off[r] = frames; frames += n[r] / H + 1; }
-    char* base = (char*)workspace + src.tab;
-    long* d_off = (long*)base;
-    uint32_t* d_mask = (uint32_t*)(base + round16((size_t)src.R * sizeof(long)));
-    hipError_t err = hipMemcpyAsync(d_off, off.data(), off.size() * sizeof(long), hipMemcpyHostToDevice, s);
-    if (err == hipSuccess) err = hipMemsetAsync(d_mask, 0, (size_t)frames * 4, s);
-    if (err != hipSuccess) { sed_set_error("contrast: upload of the mask offsets: %s", hipGetErrorString(err)); return (int)err; }
-    const TdArgs ta = td_args(src, ev, workspace);
-    run.ca = CtArgs{cs.cls, ev.E, cs.n_classes, cs.frames, cs.search, cs.guard, cs.min_frames, cs.weight, d_off, d_mask, cs.frames_out,
-                    cs.sel_out, 0};
+    run.ca = CtArgs{{}, cs.frames, cs.search, cs.guard, cs.min_frames, cs.weight, cs.frames_out, cs.sel_out, 0};
+    SED_TRY(act_mask_build("contrast", "contrast (activity)", src, ev, cs.cls, cs.n_classes, workspace, s, &run.ca.act));
     const long cap = 1L << 20;
-    contrast_activity_k<<<(unsigned)((ev.E + 3) / 4 < cap ? (ev.E + 3) / 4 : cap), 256, 0, s>>>(ta, run.ca);
-    SED_LAUNCH_CHECK("contrast (activity)");
-    contrast_select_k<<<(unsigned)(ev.E < cap ? ev.E : cap), 64, 0, s>>>(ta, run.ca);
+    contrast_select_k<<<(unsigned)(ev.E < cap ? ev.E : cap), 64, 0, s>>>(td_args(src, ev, workspace), run.ca);
     SED_LAUNCH_CHECK("contrast (selection)");
     return 0;
 }
@@ -192,7 +115,7 @@ int ct_accum(const char* who, CtRun& run, const TdArgs& ta, const float2* part, 
 // workspace: sample_off [R*C] and n_samples [R], then mask_off [R] and the mask
 extern "C" size_t sed_event_contrast_frames_workspace_bytes(int R, int channels, long mask_frames, int frames) {
     if (R < 1 || channels < 2 || channels > TD_MAX_CH || !ct_sizes_ok(R, mask_frames, frames)) return 0;
-    return rec_table_bytes(R, channels) + ct_mask_bytes(R, mask_frames);
+    return rec_table_bytes(R, channels) + act_mask_bytes(R, mask_frames);
 }
 
 // the activity and the selection alone; no sample is read
@@ -214,7 +137,7 @@ extern "C" int sed_event_contrast_frames(long pcm_len, const long* clips_host, i
     SED_TRY(ct_check(who, E, run.cs));
     SED_TRY(rec_source_linear(who, src, hop));
     if (E == 0) return 0;
-    const size_t need = src.tab + ct_mask_bytes(R, ct_mask_frames(clips_host, R, channels, time_factor, hop));
+    const size_t need = src.tab + act_mask_bytes(R, act_mask_frames(src, ev));
     SED_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0, "%s: the workspace must be a 16-byte aligned device buffer", who);
     SED_REQUIRE(workspace_bytes >= need, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
     hipStream_t s = as_stream(stream);

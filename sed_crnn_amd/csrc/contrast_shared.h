@@ -1,26 +1,26 @@
-// contrast_shared.h — contrast SRP-PHAT: what contrast.hip (the activity, the selection of an event's background frames
-// and their accumulate launch), doa.hip and doatrack.hip (the steer kernels that subtract the background's share) agree on.
+// contrast_shared.h — contrast SRP-PHAT: what contrast.hip (the selection of an event's background frames and their
+// accumulate launch), doa.hip and doatrack.hip (the steer kernels that subtract the background's share) agree on.
 // Device code: the kernel arguments and the one place where S' = S - w Sb is formed.  Host code: the settings of an entry, their
-// checks, the bytes of the activity mask behind the recording table, and the two steps an entry hands to the shared runner
-// (tdoa_shared.h): ct_pre, once per call, and ct_accum, once per slice in front of the steer launch.
+// checks, and the two steps an entry hands to the shared runner (tdoa_shared.h): ct_pre, once per call, and ct_accum, once per
+// slice in front of the steer launch.  The activity mask behind the recording table — its bytes, its bounds, its build — and the
+// selection walk are activity_shared.h's, shared with the quiet-frame MVDR.
 #pragma once
 #include <stdint.h>
 #include "common.h"
 #include "tdoa_shared.h"
+#include "activity_shared.h"
 
 #define CT_MAX_FRAMES 256                         // localize.Contrast: frames
 #define CT_MAX_SEARCH 4096                        //                    search
 #define CT_MAX_GUARD 64                           //                    guard
 #define CT_MAX_CLASSES 32                         // the bits of a mask word
 #define CT_MAX_WEIGHT 4.0
+static_assert(CT_MAX_FRAMES <= ACT_MAX_SEL, "act_select_walk keeps at most ACT_MAX_SEL entries");
 
 struct CtArgs {
-    const int* ev_cls;          // [E]
-    long E;                     // rows of the whole table
-    int n_classes, Nb, search, guard, min_frames;
+    ActMask act;                // the event classes, the rows of the whole table and the activity mask
+    int Nb, search, guard, min_frames;
     double weight;
-    const long* mask_off;       // [R] recording r's first word of mask
-    uint32_t* mask;             // [sum L_r] the class bits of every output frame, L_r = n_r / (tf hop) + 1
     int* bg_frames;             // [E] nb: the background frames of every event (0: its map is the plain one)
     int* bg_sel;                // [E][Nb] their candidates q in summation order, -1 behind them
     int cpo;                    // an event's own chunk slots: its background chunks are the rows cpo .. of its TdArgs.cpe
@@ -79,11 +79,8 @@ __device__ __forceinline__ int ct_bg_frames(const CtArgs& ca, long e) {
 // ── host (contrast.hip) ──
 // the settings, checked before anything is enqueued
 int ct_check(const char* who, long E, const CtSettings& cs);
+// act_mask_ok and the bound of `frames`
 bool ct_sizes_ok(int R, long mask_frames, int frames);
-// the bytes behind the recording table: mask_off [R], then the mask of `frames` words, each rounded to 16 bytes
-size_t ct_mask_bytes(int R, long frames);
-// the mask's words of a caller's clip table, 0 where the shared checks will refuse the call anyway
-long ct_mask_frames(const long* clips_host, int R, int channels, int tf, int hop);
 // TdExtra.pre (ctx: a CtRun): the activity of the whole table, then every event's background frames into frames_out / sel_out
 int ct_pre(void* ctx, const RecSource& src, const EvTable& ev, void* workspace, hipStream_t s);
 // the background chunks of a slice's events into the rows behind their own

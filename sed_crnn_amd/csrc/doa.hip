@@ -226,7 +226,7 @@ extern "C" size_t sed_event_doa_contrast_workspace_bytes(int R, int channels, lo
     if (one == 0 || E < 0 || !ct_sizes_ok(R, mask_frames, frames)) return 0;
     const size_t tab = rec_table_bytes(R, channels);
     const size_t bg = (size_t)((frames + TD_CHUNK - 1) / TD_CHUNK) * (channels * (channels - 1) / 2) * TD_ROW_BYTES;
-    return tab + ct_mask_bytes(R, mask_frames) + (size_t)E * (one - tab + bg);
+    return tab + act_mask_bytes(R, mask_frames) + (size_t)E * (one - tab + bg);
 }
 
 extern "C" int sed_event_doa_contrast(const float* pcm, long pcm_len, const long* clips_host, int R, int channels, const void* tables,
@@ -242,7 +242,7 @@ extern "C" int sed_event_doa_contrast(const float* pcm, long pcm_len, const long
     SED_TRY(ct_check("doa_contrast", E, dc.run.cs));
     dc.run.pcm = pcm; dc.run.tables = tables; dc.run.pad_mode = pad_mode;
     dc.run.cpb = (frames + TD_CHUNK - 1) / TD_CHUNK;
-    const TdExtra extra{ct_mask_bytes(R, ct_mask_frames(clips_host, R, channels, time_factor, hop)), dc.run.cpb, ct_pre, &dc.run};
+    const TdExtra extra{act_mask_bytes(R, act_mask_frames(clips_host, R, channels, time_factor, hop)), dc.run.cpb, ct_pre, &dc.run};
     return tdoa_entry("doa_contrast", {pcm, false, 0, pcm_len, R, channels, clips_host},
                       {ev_rec, ev_onset, ev_offset, ev_peak_frame, nullptr, nullptr, E, time_factor, hop, max_frames, 0},
                       {tables, tables_bytes, pad_mode, max_lag, 0, 0}, {lag_out, strength_out, frames_out, acc_out}, workspace,

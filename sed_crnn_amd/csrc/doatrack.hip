@@ -462,7 +462,7 @@ extern "C" size_t sed_event_doa_track_contrast_workspace_bytes(int R, int channe
     if (one == 0 || E < 0 || !ct_sizes_ok(R, mask_frames, frames)) return 0;
     const size_t tab = rec_table_bytes(R, channels);
     const size_t bg = (size_t)((frames + TD_CHUNK - 1) / TD_CHUNK) * (channels * (channels - 1) / 2) * TD_ROW_BYTES;
-    const size_t td = tab + ct_mask_bytes(R, mask_frames) + (size_t)E * (one - tab + bg);
+    const size_t td = tab + act_mask_bytes(R, mask_frames) + (size_t)E * (one - tab + bg);
     return trk_workspace_bytes(td, channels, E, 1 + max_n_samples / hop, max_frames, D, block_chunks, smooth);
 }
 
@@ -481,7 +481,7 @@ extern "C" int sed_event_doa_track_contrast(const float* pcm, long pcm_len, cons
     SED_TRY(ct_check(who, E, run.cs));
     run.pcm = pcm; run.tables = tables; run.pad_mode = pad_mode;
     run.cpb = (frames + TD_CHUNK - 1) / TD_CHUNK;
-    const TdExtra extra{ct_mask_bytes(R, ct_mask_frames(clips_host, R, channels, time_factor, hop)), run.cpb, ct_pre, &run};
+    const TdExtra extra{act_mask_bytes(R, act_mask_frames(clips_host, R, channels, time_factor, hop)), run.cpb, ct_pre, &run};
     TrkCtx tc;
     size_t td_bytes;
     SED_TRY(trk_check(who, false, clips_host, 0, R, channels, E, hop, max_lag, max_frames, steer_lags, D, Q, trig, dir_out, power_out, srp_out,

@@ -44,9 +44,9 @@
 //
 // The noise frames where the event's class is silent: sed_event_quiet_frames / sed_event_mvdr_quiet.  The whole
 // event table is rasterised once into mask[r][t], a uint32 of class bits per recording and output frame of H = tf hop samples
-// (mvdr_activity_k: atomicOr from vector lanes, the result is order-free); mvdr_select_k, a wave per event, walks the S
-// candidates q — the 2048 samples from s0 - (G + 2 + q) B, tested on [s0 - (2 G + 2 + q) B, s0 - q B) against the mask — with a
-// ballot and a prefix count, keeps the first Kn eligible ones and writes them in summation order (descending q) to noise_sel,
+// (act_mask_build, activity.hip: shared with the contrast SRP-PHAT); mvdr_select_k, a wave per event, gives the S
+// candidates q — the 2048 samples from s0 - (G + 2 + q) B, tested on [s0 - (2 G + 2 + q) B, s0 - q B) against the mask — to the
+// shared walk (act_select_walk, activity_shared.h): the first Kn eligible ones in summation order (descending q) to noise_sel,
 // n_e >= noise_min of them to noise_frames (else 0 and a row of -1: the event keeps its own frames).  A slice is then
 // mvdr_quiet_own_k (the own covariance of the events with noise_frames = 0), mvdr_quiet_k (the covariance body over the selected
 // frames, mv_load_abs at s0 - (G + 2 + noise_sel[e][j]) B), mvdr_quiet_weights_k (the weight body with the chunk count taken from
@@ -67,6 +67,7 @@
 #include "fft2048.h"
 #include "tdoa_shared.h"
 #include "beam_shared.h"
+#include "activity_shared.h"
 
 #define MV_WAVES 8
 #define MV_THREADS (MV_WAVES * 64)
@@ -670,78 +671,29 @@ bool mv_trk_sizes_ok(int Tm) { return Tm >= 1 && Tm <= MV_MAX_TRK_BLOCKS; }
 #define MV_MAX_SEARCH 1024                        // localize.MVDR: noise_search
 #define MV_MAX_CLASSES 32                         // the bits of a mask word
 
+static_assert(MV_MAX_NOISE <= ACT_MAX_SEL, "act_select_walk keeps at most ACT_MAX_SEL entries");
+
 struct MqArgs {
-    const int* ev_cls;                           // [E]
-    long E;                                      // rows of the whole table
-    int n_classes, search, min_frames, any;      // S candidates, at least M of them, and whether every class excludes (else the event's own)
-    const long* mask_off;                        // [R] recording r's first word of mask
-    uint32_t* mask;                              // [sum L_r] the class bits of every output frame, L_r = n_r / (tf hop) + 1
+    ActMask act;                                 // the event classes, the rows of the whole table and the activity mask
+    int search, min_frames, any;                 // S candidates, at least M of them, and whether every class excludes (else the event's own)
     int* sel;                                    // [E][kn] the candidates of every event in summation order, -1 behind them
 };
 
-// the activity of the WHOLE table, located or not: bit cls of mask[rec][t] for onset <= t < offset, both clamped to [0, L_rec].  A
-// wave per row, a lane per frame; the OR does not depend on the order, so nothing depends on the launch shape.
-__global__ __launch_bounds__(256) void mvdr_activity_k(TdArgs ta, MqArgs qa) {
-    const int lane = threadIdx.x & 63;
-    const long H = (long)ta.tf * ta.hop;
-    for (long e = (long)blockIdx.x * 4 + (threadIdx.x >> 6); e < qa.E; e += (long)gridDim.x * 4) {
-        const int rec = ta.ev_rec ? ta.ev_rec[e] : 0, cls = qa.ev_cls[e];
-        const long on = ta.ev_onset[e];
-        if (rec < 0 || rec >= ta.R || cls < 0 || cls >= qa.n_classes || on < 0) continue;
-        const long L = ta.n_samples[rec] / H + 1;
-        long off = ta.ev_offset[e];
-        if (off > L) off = L;
-        uint32_t* row = qa.mask + qa.mask_off[rec];
-        for (long t = on + lane; t < off; t += 64) atomicOr(row + t, 1u << cls);
-    }
-}
-
-// One wave per event walks the candidates q = 0 .. S-1, 64 at a time: candidate q is the 2048 samples from s0 - (G + 2 + q) B,
-// exists when that is >= 0, and is eligible when no output frame that [s0 - (2 G + 2 + q) B, s0 - q B) touches has a bit of
-// `excl` set.  The ballot's prefix count ranks the eligible ones, nearest first; the first kn are kept and written in summation
-// order, which is ascending time: descending q.
+// candidate q: the 2048 samples from s0 - (G + 2 + q) B, which exist when that is >= 0, tested on [s0 - (2 G + 2 + q) B, s0 - q B)
 __global__ __launch_bounds__(64) void mvdr_select_k(TdArgs ta, MvArgs ma, MqArgs qa) {
-    __shared__ int s_q[MV_MAX_NOISE];
-    const int lane = threadIdx.x;
-    const long H = (long)ta.tf * ta.hop;
-    for (long e = blockIdx.x; e < qa.E; e += gridDim.x) {
+    for (long e = blockIdx.x; e < qa.act.E; e += gridDim.x) {
         int rec, len;
         long s0;
         bm_event_span(ta, ma.ev_dir, ma.ev_loc, ma.D, e, rec, s0, len);
-        const int cls = qa.ev_cls[e];
-        int count = 0;
-        if (len != 0 && cls >= 0 && cls < qa.n_classes) {        // (block-uniform)
-            const uint32_t excl = qa.any ? 0xffffffffu : 1u << cls;
-            const uint32_t* row = qa.mask + qa.mask_off[rec];
-            const long L = ta.n_samples[rec] / H + 1;
-            for (int q0 = 0; q0 < qa.search && count < ma.kn && s0 >= (long)(ma.guard + 2 + q0) * MV_B; q0 += 64) {
-                const int q = q0 + lane;
-                bool ok = q < qa.search && s0 >= (long)(ma.guard + 2 + q) * MV_B;
-                if (ok) {
-                    long lo = s0 - (long)(2 * ma.guard + 2 + q) * MV_B;
-                    if (lo < 0) lo = 0;
-                    long t1 = (s0 - (long)q * MV_B + H - 1) / H;   // (s0 - q B >= 2 B: at least one frame is tested)
-                    if (t1 > L) t1 = L;
-                    for (long t = lo / H; t < t1 && ok; ++t) ok = (row[t] & excl) == 0;
-                }
-                const unsigned long long m = __ballot(ok);
-                const int rank = count + __popcll(m & ((1ull << lane) - 1ull));
-                if (ok && rank < ma.kn) s_q[rank] = q;
-                count += __popcll(m);
-            }
-            if (count > ma.kn) count = ma.kn;
-            if (count < qa.min_frames) count = 0;
-        }
-        __syncthreads();
-        for (int i = lane; i < ma.kn; i += 64) qa.sel[e * ma.kn + i] = i < count ? s_q[count - 1 - i] : -1;
-        if (lane == 0) ma.noise_frames[e] = count;
-        __syncthreads();                                         // s_q is free for the next event
+        const int cls = qa.act.ev_cls[e];
+        const bool takes = len != 0 && cls >= 0 && cls < qa.act.n_classes;           // (block-uniform)
+        const ActWindow w{s0, MV_B, (long)(2 * ma.guard + 2) * MV_B, 0, (long)(ma.guard + 2) * MV_B};
+        act_select_walk(ta, qa.act, takes, rec, qa.any ? 0xffffffffu : takes ? 1u << cls : 0u, w, ma.kn, qa.search, qa.min_frames,
+                        qa.sel + e * ma.kn, ma.noise_frames + e);
     }
 }
 
-// the words behind the recording table: mask_off [R], then the mask of `frames` words, each rounded to 16 bytes
-size_t mq_mask_bytes(int R, long frames) { return (((size_t)R * sizeof(long) + 15) & ~(size_t)15) + (((size_t)frames * 4 + 15) & ~(size_t)15); }
-bool mq_sizes_ok(int R, long frames, int kn) { return R >= 1 && frames >= R && frames <= (1L << 40) && kn >= 1 && kn <= MV_MAX_NOISE; }
+bool mq_sizes_ok(int R, long frames, int kn) { return act_mask_ok(R, frames) && kn >= 1 && kn <= MV_MAX_NOISE; }
 
 // the settings of a quiet call and its outputs beside frames_out (MvNoise)
 struct MvQuiet { const int* cls; int n_classes, search, min_frames, any; int* sel_out; };
@@ -760,38 +712,17 @@ int mq_check(const char* who, const EvTable& ev, int kn, int guard, const int* f
 }
 
 // the activity of the whole table into the mask behind the recording table (which is uploaded), then every event's frames:
-// frames_out [E] and sel_out [E][kn] are written for all E rows.  The workspace holds src.tab + mq_mask_bytes (checked by the caller).
+// frames_out [E] and sel_out [E][kn] are written for all E rows.  The workspace holds src.tab + act_mask_bytes (checked by the caller).
 int mq_select(const char* who, const RecSource& src, const EvTable& ev, int kn, int guard, int* frames_out, const MvQuiet& qz,
               void* workspace, hipStream_t s) {
-    const long H = (long)ev.tf * ev.hop;
-    const long* n = src.h.data() + (size_t)src.R * src.C;
-    std::vector<long> off((size_t)src.R);
-    long frames = 0;
-    for (int r = 0; r < src.R; ++r) { off[r] = frames; frames += n[r] / H + 1; }
-    char* base = (char*)workspace + src.tab;
-    long* d_off = (long*)base;
-    uint32_t* d_mask = (uint32_t*)(base + (((size_t)src.R * sizeof(long) + 15) & ~(size_t)15));
-    hipError_t err = hipMemcpyAsync(d_off, off.data(), off.size() * sizeof(long), hipMemcpyHostToDevice, s);
-    if (err == hipSuccess) err = hipMemsetAsync(d_mask, 0, (size_t)frames * 4, s);
-    if (err != hipSuccess) { sed_set_error("%s: upload of the mask offsets: %s", who, hipGetErrorString(err)); return (int)err; }
-    const TdArgs ta = td_args(src, ev, workspace);
     MvArgs ma{};
     ma.ev_dir = ev.dir; ma.ev_loc = ev.loc; ma.D = ev.D; ma.kn = kn; ma.guard = guard; ma.noise_frames = frames_out;
-    const MqArgs qa{qz.cls, ev.E, qz.n_classes, qz.search, qz.min_frames, qz.any, d_off, d_mask, qz.sel_out};
+    MqArgs qa{{}, qz.search, qz.min_frames, qz.any, qz.sel_out};
+    SED_TRY(act_mask_build(who, "mvdr (activity)", src, ev, qz.cls, qz.n_classes, workspace, s, &qa.act));
     const long cap = 1L << 20;
-    mvdr_activity_k<<<(unsigned)((ev.E + 3) / 4 < cap ? (ev.E + 3) / 4 : cap), 256, 0, s>>>(ta, qa);
-    SED_LAUNCH_CHECK("mvdr (activity)");
-    mvdr_select_k<<<(unsigned)(ev.E < cap ? ev.E : cap), 64, 0, s>>>(ta, ma, qa);
+    mvdr_select_k<<<(unsigned)(ev.E < cap ? ev.E : cap), 64, 0, s>>>(td_args(src, ev, workspace), ma, qa);
     SED_LAUNCH_CHECK("mvdr (selection)");
     return 0;
-}
-
-// the mask's words of a checked source
-long mq_frames(const RecSource& src, const EvTable& ev) {
-    const long H = (long)ev.tf * ev.hop;
-    long frames = 0;
-    for (int r = 0; r < src.R; ++r) frames += src.h[(size_t)src.R * src.C + r] / H + 1;
-    return frames;
 }
 
 // the steering delays [D][C], the diagonal loading and the table blob
@@ -814,7 +745,7 @@ int mv_run(const char* who, const RecSource& src, const EvTable& ev, const MvTab
     const int kn = nz.kn;
     const long E = ev.E;
     if (qz) SED_TRY(mq_check(who, ev, kn, nz.guard, nz.frames_out, *qz));
-    const size_t tab = src.tab + (qz ? mq_mask_bytes(src.R, mq_frames(src, ev)) : 0);
+    const size_t tab = src.tab + (qz ? act_mask_bytes(src.R, act_mask_frames(src, ev)) : 0);
     SED_REQUIRE(kn >= 0 && kn <= MV_MAX_NOISE, "%s: noise_blocks must be in [0, %d], got %d", who, MV_MAX_NOISE, kn);
     SED_REQUIRE(nz.guard >= 0 && nz.guard <= MV_MAX_GUARD, "%s: noise_guard must be in [0, %d], got %d", who, MV_MAX_GUARD, nz.guard);
     SED_REQUIRE(!nz.entry || E == 0 || nz.frames_out, "%s: null pointer (noise_frames_out)", who);
@@ -918,7 +849,7 @@ int mq_frames_entry(const char* who, RecSource src, const EvTable& ev, int kn, i
     SED_TRY((beam_source<false, false>(who, src, ev)));
     SED_TRY(mq_check(who, ev, kn, guard, frames_out, qz));
     if (ev.E == 0) return 0;
-    const size_t need = src.tab + mq_mask_bytes(src.R, mq_frames(src, ev));
+    const size_t need = src.tab + act_mask_bytes(src.R, act_mask_frames(src, ev));
     SED_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0, "%s: the workspace must be a 16-byte aligned device buffer", who);
     SED_REQUIRE(workspace_bytes >= need, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
     hipStream_t s = as_stream(stream);
@@ -999,12 +930,12 @@ extern "C" int sed_event_mvdr_noise_ring(const float* ring, long ring_len, long 
 // ── DESIGN 5w: the noise covariance from the frames where the event's class — or, with exclude_any, every class — is silent ──
 extern "C" size_t sed_event_quiet_frames_workspace_bytes(int R, int channels, long mask_frames, int noise_blocks) {
     if (R < 1 || channels < 2 || channels > TD_MAX_CH || !mq_sizes_ok(R, mask_frames, noise_blocks)) return 0;
-    return rec_table_bytes(R, channels) + mq_mask_bytes(R, mask_frames);
+    return rec_table_bytes(R, channels) + act_mask_bytes(R, mask_frames);
 }
 
 extern "C" size_t sed_event_mvdr_quiet_workspace_bytes(int R, int channels, int max_frames, int hop, int noise_blocks, long mask_frames) {
     if (!mv_sizes_ok(R, channels, max_frames, hop) || !mq_sizes_ok(R, mask_frames, noise_blocks)) return 0;
-    return rec_table_bytes(R, channels) + mq_mask_bytes(R, mask_frames) + mv_event_bytes(channels, mv_slots(max_frames, hop, noise_blocks));
+    return rec_table_bytes(R, channels) + act_mask_bytes(R, mask_frames) + mv_event_bytes(channels, mv_slots(max_frames, hop, noise_blocks));
 }
 
 extern "C" int sed_event_quiet_frames(long pcm_len, const long* clips_host, int R, int channels, const int* ev_rec, const int* ev_cls,
@@ -1046,7 +977,7 @@ extern "C" size_t sed_event_mvdr_track_ring_workspace_bytes(int R, int channels,
 extern "C" size_t sed_event_mvdr_quiet_track_workspace_bytes(int R, int channels, int max_frames, int hop, int noise_blocks, long mask_frames,
                                                              int track_slots) {
     if (!mv_sizes_ok(R, channels, max_frames, hop) || !mq_sizes_ok(R, mask_frames, noise_blocks) || !mv_trk_sizes_ok(track_slots)) return 0;
-    return rec_table_bytes(R, channels) + mq_mask_bytes(R, mask_frames) +
+    return rec_table_bytes(R, channels) + act_mask_bytes(R, mask_frames) +
            mv_trk_event_bytes(channels, mv_slots(max_frames, hop, noise_blocks), track_slots);
 }
 

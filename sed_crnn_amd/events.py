@@ -169,16 +169,36 @@ def _track_io(doa, E, dev, out, return_map):
             ptr(out.get("trk_map"))]
 
 
-def _contrast_classes(who, n_classes):
-    """the class count of a contrast call, checked"""
-    from .localize import CONTRAST_MAX_CLASSES
+def _n_classes(who, settings, n_classes, most):
+    """the class count of a call that reads the activity mask, checked; ``settings``: what asks for it"""
     if n_classes is None:
-        raise ValueError(f"{who} with sed.DOA(..., contrast=sed.Contrast(...)) needs n_classes, the number of classes the events' cls column "
-                         f"counts in")
-    if isinstance(n_classes, bool) or int(n_classes) != n_classes or not 1 <= int(n_classes) <= CONTRAST_MAX_CLASSES:
-        raise ValueError(f"{who}: n_classes must be an integer in [1, {CONTRAST_MAX_CLASSES}] (an activity word has {CONTRAST_MAX_CLASSES} "
-                         f"bits), got {n_classes!r}")
+        raise ValueError(f"{who} with {settings} needs n_classes, the number of classes the events' cls column counts in")
+    if isinstance(n_classes, bool) or int(n_classes) != n_classes or not 1 <= int(n_classes) <= most:
+        raise ValueError(f"{who}: n_classes must be an integer in [1, {most}] (an activity word has {most} bits), got {n_classes!r}")
     return int(n_classes)
+
+
+def _contrast_classes(who, n_classes):
+    from .localize import CONTRAST_MAX_CLASSES
+    return _n_classes(who, "sed.DOA(..., contrast=sed.Contrast(...))", n_classes, CONTRAST_MAX_CLASSES)
+
+
+def _mask_frames(table, nc, tf, hop):
+    """the words of the activity mask of a clip table: ``n_r // (tf hop) + 1`` output frames per recording"""
+    return int((table[::nc, 1] // (tf * hop) + 1).sum())
+
+
+def _frames_only(who, clips, nc, events, keys):
+    """the selection-only entries' prologue: the event columns must be on the GPU, the clip table is checked without a PCM buffer
+    -> (the device, the table, R, the columns ``keys`` and ``cls``, E, the PCM extent the C entry takes)"""
+    dev = events["onset"].device if isinstance(events.get("onset"), torch.Tensor) else None
+    if dev is None or dev.type != "cuda":
+        raise RuntimeError(f"sed_crnn_amd.feature.{who} needs the event columns as CUDA(HIP) tensors; there is no CPU fallback")
+    table = np.ascontiguousarray(np.asarray(clips, dtype=np.int64).reshape(-1, 2))
+    table = _clip_table(clips, nc, int((table[:, 0] + table[:, 1]).max()) if table.size else 0, at_least_one=True)
+    R = table.shape[0] // nc
+    col, E = _event_cols(events, R, "rec", keys + ("cls",), dev)
+    return dev, table, R, col, E, int((table[:, 0] + table[:, 1]).max())
 
 
 def _locate(src, events, tf, hop, max_lag, max_frames, settings, return_curve, max_workspace_bytes, doa, n_classes=None):
@@ -211,7 +231,7 @@ def _locate(src, events, tf, hop, max_lag, max_frames, settings, return_curve, m
     sizes = _ENTRY[kind if track or ct is not None else "tdoa", src.ring] + "_workspace_bytes"   # (the steering launch reads the partials in place)
     more = [len(doa[0].grid), doa[0].track.block_chunks, int(doa[0].track.max_step_deg is not None)] if track else []
     if ct is not None:                                                # the mask lies behind the table, once per call
-        more += [_mask_frames(src, tf, hop), ct.frames]
+        more += [_mask_frames(src.table, nc, tf, hop), ct.frames]
     need_one = getattr(lib(), sizes)(R, nc, 1, src.extent, hop, max_frames, *more)
     need_all = getattr(lib(), sizes)(R, nc, E, src.extent, hop, max_frames, *more)
     if need_one == 0:
@@ -335,23 +355,17 @@ def event_contrast_frames(clips, channels, events, time_factor, doa, n_classes, 
     if doa.channels != nc:
         raise ValueError(f"the DOA settings hold {doa.channels} microphone positions, the audio has {nc} channels")
     ct, classes = doa.contrast, _contrast_classes("event_contrast_frames", n_classes)
-    dev = events["onset"].device if isinstance(events.get("onset"), torch.Tensor) else None
-    if dev is None or dev.type != "cuda":
-        raise RuntimeError("sed_crnn_amd.feature.event_contrast_frames needs the event columns as CUDA(HIP) tensors; there is no CPU fallback")
-    table = np.ascontiguousarray(np.asarray(clips, dtype=np.int64).reshape(-1, 2))
-    table = _clip_table(clips, nc, int((table[:, 0] + table[:, 1]).max()) if table.size else 0, at_least_one=True)
-    R = table.shape[0] // nc
-    col, E = _event_cols(events, R, "rec", _LOCATED[:3] + ("cls",), dev)
+    dev, table, R, col, E, extent = _frames_only("event_contrast_frames", clips, nc, events, _LOCATED[:3])
     out = {"bg_frames": torch.zeros(E, dtype=torch.int32, device=dev), "bg_sel": torch.full((E, ct.frames), -1, dtype=torch.int32, device=dev)}
     if E == 0:
         return out
-    frames = int((table[::nc, 1] // (tf * hop) + 1).sum())
+    frames = _mask_frames(table, nc, tf, hop)
     need = lib().sed_event_contrast_frames_workspace_bytes(R, nc, frames, ct.frames)
     if need == 0:
         raise ValueError(f"sed_event_contrast_frames_workspace_bytes refuses R={R}, channels={nc}, {frames} output frames, frames={ct.frames}")
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
     cols = _col_ptrs(col, _LOCATED[:3])
-    check(lib().sed_event_contrast_frames(int((table[:, 0] + table[:, 1]).max()), C.c_void_p(table.ctypes.data), R, nc, cols[0], ptr(col["cls"]),
+    check(lib().sed_event_contrast_frames(extent, C.c_void_p(table.ctypes.data), R, nc, cols[0], ptr(col["cls"]),
                                           *cols[1:], E, tf, hop, doa.max_frames, classes, ct.frames, ct.search, ct.guard, ct.min_frames,
                                           ptr(out["bg_frames"]), ptr(out["bg_sel"]), ptr(ws), ws.numel(), stream_ptr()),
           "sed_event_contrast_frames")
@@ -501,17 +515,8 @@ def _beamform(who, src, events, tf, hop, doa, beam, sr):
 def _quiet_settings(who, mvdr, n_classes):
     """the quiet settings as the C entries take them behind noise_guard -> [n_classes, S, M, exclude_any]"""
     from .localize import MVDR_MAX_CLASSES
-    if n_classes is None:
-        raise ValueError(f"{who} with sed.MVDR(noise_select='quiet') needs n_classes, the number of classes the events' cls column counts in")
-    if isinstance(n_classes, bool) or int(n_classes) != n_classes or not 1 <= int(n_classes) <= MVDR_MAX_CLASSES:
-        raise ValueError(f"{who}: n_classes must be an integer in [1, {MVDR_MAX_CLASSES}] (an activity word has {MVDR_MAX_CLASSES} bits), "
-                         f"got {n_classes!r}")
-    return [int(n_classes), mvdr.noise_search, mvdr.noise_min, int(mvdr.noise_exclude == "any")]
-
-
-def _mask_frames(src, tf, hop):
-    """the words of the activity mask: ``n_r // (tf hop) + 1`` output frames per recording"""
-    return int((src.table[::src.nc, 1] // (tf * hop) + 1).sum())
+    return [_n_classes(who, "sed.MVDR(noise_select='quiet')", n_classes, MVDR_MAX_CLASSES), mvdr.noise_search, mvdr.noise_min,
+            int(mvdr.noise_exclude == "any")]
 
 
 def _mvdr(who, src, events, tf, hop, doa, mvdr, sr, max_workspace_bytes, n_classes=None):
@@ -546,7 +551,7 @@ def _mvdr(who, src, events, tf, hop, doa, mvdr, sr, max_workspace_bytes, n_class
         noise = [Kn, mvdr.noise_guard] + quiet
     name = _ENTRY[kind, src.ring] + "_workspace_bytes"
     if mvdr.quiet:                                                               # the mask lies behind the table, once per call
-        frames = _mask_frames(src, tf, hop)
+        frames = _mask_frames(src.table, nc, tf, hop)
         need_tab = lib().sed_event_quiet_frames_workspace_bytes(R, nc, frames, Kn)
         need_one = getattr(lib(), name)(R, nc, max_frames, hop, Kn, frames, *track[1:2])     # the table, the mask and one event
     else:
@@ -578,24 +583,18 @@ def event_quiet_frames(clips, channels, events, time_factor, doa, mvdr, n_classe
         raise TypeError("event_quiet_frames takes the beam settings as a sed.MVDR(..., noise_select='quiet') object")
     _doa_plan(doa, nc, SR)
     quiet = _quiet_settings("event_quiet_frames", mvdr, n_classes)
-    dev = events["onset"].device if isinstance(events.get("onset"), torch.Tensor) else None
-    if dev is None or dev.type != "cuda":
-        raise RuntimeError("sed_crnn_amd.feature.event_quiet_frames needs the event columns as CUDA(HIP) tensors; there is no CPU fallback")
-    table = np.ascontiguousarray(np.asarray(clips, dtype=np.int64).reshape(-1, 2))
-    table = _clip_table(clips, nc, int((table[:, 0] + table[:, 1]).max()) if table.size else 0, at_least_one=True)
-    R = table.shape[0] // nc
-    col, E = _event_cols(events, R, "rec", _LOCATED + ("cls",), dev)
+    dev, table, R, col, E, extent = _frames_only("event_quiet_frames", clips, nc, events, _LOCATED)
     Kn = mvdr.noise_blocks
     out = {"noise_frames": torch.zeros(E, dtype=torch.int32, device=dev), "noise_sel": torch.full((E, Kn), -1, dtype=torch.int32, device=dev)}
     if E == 0:
         return out
-    frames = int((table[::nc, 1] // (tf * hop) + 1).sum())
+    frames = _mask_frames(table, nc, tf, hop)
     need = lib().sed_event_quiet_frames_workspace_bytes(R, nc, frames, Kn)
     if need == 0:
         raise ValueError(f"sed_event_quiet_frames_workspace_bytes refuses R={R}, channels={nc}, {frames} output frames, noise_blocks={Kn}")
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
     cols = _col_ptrs(col, _LOCATED)
-    check(lib().sed_event_quiet_frames(int((table[:, 0] + table[:, 1]).max()), C.c_void_p(table.ctypes.data), R, nc, cols[0], ptr(col["cls"]),
+    check(lib().sed_event_quiet_frames(extent, C.c_void_p(table.ctypes.data), R, nc, cols[0], ptr(col["cls"]),
                                        *cols[1:], E, tf, hop, doa.max_frames, doa.grid.unit_vectors.shape[0], quiet[0], Kn, mvdr.noise_guard,
                                        *quiet[1:], ptr(out["noise_frames"]), ptr(out["noise_sel"]), ptr(ws), ws.numel(), stream_ptr()),
           "sed_event_quiet_frames")

@@ -27,7 +27,7 @@ import mvdr_ref  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = ("sed_event_contrast_frames", "sed_event_doa_contrast", "sed_event_doa_track_contrast")
-KERNELS = ("contrast_activity_k", "contrast_select_k", "contrast_accum_k")
+KERNELS = ("contrast_select_k", "contrast_accum_k")
 ROW = 1026 * 8
 
 
@@ -192,14 +192,16 @@ def test_c_entries_check_their_arguments_on_the_host():
 def test_build_guards_the_contrast_kernels_against_scratch():
     from sed_crnn_amd.build import NO_SCRATCH_KERNELS, SOURCES
     assert "contrast.hip" in SOURCES and set(KERNELS) <= set(NO_SCRATCH_KERNELS["contrast.hip"])
+    assert "activity.hip" in SOURCES and "event_activity_k" in NO_SCRATCH_KERNELS["activity.hip"]
     assert NO_SCRATCH_KERNELS["tdoa.hip"] == ("tdoa_accum_k", "tdoa_finish_k") and "doa_steer_k" in NO_SCRATCH_KERNELS["doa.hip"]
     assert "doa_track_steer_k" in NO_SCRATCH_KERNELS["doatrack.hip"]        # (their contrast forms are instantiations: found by substring)
     every = [k for ks in NO_SCRATCH_KERNELS.values() for k in ks]
-    for name in KERNELS:                                                     # the assembly tests and the guard find kernels by substring
+    for name in KERNELS + ("event_activity_k",):                             # the assembly tests and the guard find kernels by substring
         assert not any(o in name or name in o for o in every if o != name), name
     src = open(os.path.join(ROOT, "sed_crnn_amd", "csrc", "contrast.hip")).read()
     for name in KERNELS:
         assert re.search(r"\b%s\b" % name, src), name
+    assert re.search(r"\bevent_activity_k\b", open(os.path.join(ROOT, "sed_crnn_amd", "csrc", "activity.hip")).read())
     assert "atomicOr" in src and not re.search(r"atomic(Add|Max|Min|CAS|Exch|And|Xor)", src)     # no atomics beyond the mask's OR
 
 
